@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: training tokens/s of TransformerLM_scaled (fwd + bwd + AdamW) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config scaled] [--batch B] [--precision bf16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config scaled] [--batch B] [--precision bf16] [--dump-outputs DIR]
 
 N > 1 is launched by the driver as `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`
 (one process per GPU, RCCL): weak scaling, every rank trains B_local rows of the same global batch and
@@ -67,6 +67,9 @@ def main():
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the extra_configs leg (p = 0, B = 256, GPT-2-small)")
     ap.add_argument("--dropout", type=float, default=None, help="override the preset's dropout")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, updated parameters, gradients) as "
+                    "DIR/<name>.npy in float32, at most 64 MB in all (see dump_outputs)")
     ap.add_argument("--dp-buckets", type=int, default=None, help="N > 1: layer groups whose gradient ranges are all-reduced while the "
                     "next group's backward runs (default: by gradient size, see TrainEngine._choose_buckets)")
     args = ap.parse_args()
@@ -155,6 +158,8 @@ def main():
         dt = tt.item()
     final_loss = eng.loss.item()
     eng.check_status()          # raises (non-zero exit) if a dW hand-over of any timed step ran out: such a number must not be reported
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(eng, model, args.dump_outputs)      # before the kernel-timing leg: its eager replay steps the weights again
     tokens = args.steps * B * T * world
     tok_s = tokens / dt
     fpt = flops_per_token(cfg, V)
@@ -216,6 +221,35 @@ def main():
         import torch.distributed as dist
         barrier()                      # rank 0 did the kernel-timing leg: leave together
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(eng, model, out_dir):
+    """what the last timed step handed its caller, as float32 .npy files: `loss` (shape (1,)), `param.<name>` (the updated
+    weights, model.named_parameters()) and `grad.<name>` (the step's gradient, TrainEngine.named_grads()).  If the arrays
+    hold more than DUMP_BYTES in all, each is cut to the same fraction of its elements, taken at sorted flat indices drawn
+    by a generator seeded from the array's name: the same elements in every run and every build."""
+    import zlib
+
+    import numpy as np
+    arrays = {"loss": eng.loss.detach().reshape(1)}
+    arrays.update((f"param.{k}", v.detach()) for k, v in model.named_parameters())
+    arrays.update((f"grad.{k}", v.detach()) for k, v in eng.named_grads().items())
+    total = sum(v.numel() for v in arrays.values())
+    frac = min(1.0, (DUMP_BYTES // 4 - 64 * len(arrays)) / total)      # 256 B per file kept for its header and the 1-element floor
+    os.makedirs(out_dir, exist_ok=True)
+    nbytes = 0
+    for name, v in arrays.items():
+        a = v.float().cpu()
+        k = max(1, int(a.numel() * frac))
+        if k < a.numel():
+            gen = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            a = a.reshape(-1)[torch.randperm(a.numel(), generator=gen)[:k].sort().values]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.numpy())
+        nbytes += 4 * a.numel()
+    log(f"dumped {len(arrays)} arrays ({nbytes / 2**20:.1f} MB{'' if frac == 1.0 else f', {frac:.3f} of each'}) to {out_dir}")
 
 
 def run_extra(config_name, B, dropout, steps, warmup, dev, precision="bf16"):

@@ -70,7 +70,7 @@ def build(force: bool = False, save_temps: bool = False, verbose: bool = True) -
         stamp = obj + ".sha"
         dig = _digest([sp]) + hdr_digest + " ".join(flags)
         if not force and os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read() == dig:
-            return obj, False
+            return obj, dig, False
         cmd = [hipcc, *flags, "-c", sp, "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
@@ -79,13 +79,17 @@ def build(force: bool = False, save_temps: bool = False, verbose: bool = True) -
             sys.stderr.write(r.stderr)
         with open(stamp, "w") as f:
             f.write(dig)
-        return obj, True
+        return obj, dig, True
 
     with ThreadPoolExecutor(max_workers=min(8, len(SOURCES))) as ex:
         results = list(ex.map(compile_one, SOURCES))
-    objs = [o for o, _ in results]
-    rebuilt = any(c for _, c in results)
-    if rebuilt or force or not os.path.exists(LIB):
+    objs = [o for o, _, _ in results]
+    rebuilt = any(c for _, _, c in results)
+    # the library records the sources it was linked from: one left in the tree by another build is relinked
+    lib_stamp = LIB + ".sha"
+    lib_dig = hashlib.sha256("".join(d for _, d, _ in results).encode()).hexdigest()
+    linked = os.path.exists(LIB) and os.path.exists(lib_stamp) and open(lib_stamp).read() == lib_dig
+    if rebuilt or force or not linked:
         # link with the host C++ driver: hipcc's own link step hard-wires -rpath /opt/rocm/lib, which
         # could pull a second HIP runtime into a process where torch already loaded its own
         rocm_lib = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "lib")
@@ -93,6 +97,8 @@ def build(force: bool = False, save_temps: bool = False, verbose: bool = True) -
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
+        with open(lib_stamp, "w") as f:
+            f.write(lib_dig)
         if verbose:
             print(f"[drakegpt_amd.build] linked {LIB}")
     elif verbose:

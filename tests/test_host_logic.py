@@ -226,3 +226,33 @@ def test_check_ids_raises_like_torch():
         with pytest.raises(IndexError, match="out of range"):
             ops.check_ids(torch.tensor(bad), 80, "idx")
     ops.check_ids(torch.zeros((0,), dtype=torch.long), 80, "idx")
+
+
+def test_bench_dump_outputs_bounded_and_repeatable(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: loss, parameters and gradients as float32 .npy; above the byte budget every array keeps the
+    same fraction of its elements at the same indices in every run."""
+    import importlib
+    import types
+
+    import numpy as np
+    monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))   # bench sets it on import
+    monkeypatch.syspath_prepend(ROOT)
+    bench = importlib.import_module("bench")
+    m = torch.nn.Sequential(torch.nn.Linear(300, 200), torch.nn.Linear(200, 50))
+    eng = types.SimpleNamespace(loss=torch.tensor(2.5), named_grads=lambda: {k: v.detach() * 3 for k, v in m.named_parameters()})
+    bench.dump_outputs(eng, m, str(tmp_path / "full"))
+    names = {"loss"} | {f"{p}.{k}" for p in ("param", "grad") for k, _ in m.named_parameters()}
+    assert {f[:-4] for f in os.listdir(tmp_path / "full")} == names
+    w = np.load(tmp_path / "full" / "param.0.weight.npy")
+    assert w.dtype == np.float32 and np.array_equal(w, m[0].weight.detach().numpy())
+    assert np.load(tmp_path / "full" / "loss.npy").tolist() == [2.5]
+    budget = 100_000
+    monkeypatch.setattr(bench, "DUMP_BYTES", budget)
+    for d in ("a", "b"):
+        bench.dump_outputs(eng, m, str(tmp_path / d))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= budget
+    for f in os.listdir(tmp_path / "a"):
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+    g = np.load(tmp_path / "a" / "grad.0.weight.npy")
+    assert 0 < g.size < 300 * 200 and np.isin(g, 3 * w).all()
