@@ -18,7 +18,8 @@ DG_F32 = 0
 DG_BF16 = 1
 DG_FP8_E4M3 = 2
 DG_FP8_E5M2 = 3
-ABI_VERSION = 20
+DG_F32X3 = 4          # fp32 operands, split-bf16 contraction (dg_gemm_nt in_dtype / dg_gemm_tn dtype only)
+ABI_VERSION = 21
 
 
 class GemmNtArgs(C.Structure):

@@ -28,6 +28,7 @@ SOURCES = [
     "layernorm.hip",
     "gemm.hip",
     "gemm_fp8.hip",
+    "gemm_x3.hip",
     "fp8.hip",
     "attention.hip",
     "attention_simple.hip",

@@ -17,6 +17,9 @@
 //   gemm_tn_grouped256_kernel  all dW of a backward pass in one launch, 256x128 tiles, chained K halves
 //   gemm_tn_grouped_kernel     the same with 128x128 tiles (DG_TN_TILE=128)
 //   gemm_tn_ws_kernel, gemm_tn_bf16_kernel, gemm_tn_f32_kernel   one dW per launch, split-K fp32 slabs
+//   gemm_nt_x3_kernel, gemm_tn_x3_kernel   precision "bf16x3": fp32 operands split into bf16 hi + lo in registers,
+//                              3 bf16 MFMAs per block (gemm_nt_kernel / gemm_tn_f32_kernel geometry); the wave-specialised
+//                              split NT form is instantiated in gemm_x3.hip
 // Earlier variants that were measured slower (LDS-DMA without loader waves, one tile per workgroup, 256x128 NT
 // tiles, two co-resident workgroups per CU) are in the history of this file and listed in DESIGN.md section 4.
 #include "common.h"
@@ -97,8 +100,11 @@ __device__ __forceinline__ void nt_epilogue(const float* stage, int row_base, in
     }
 }
 
-template <typename T, typename TO>
-__global__ __launch_bounds__(256) void gemm_nt_kernel(NtParams p) {
+// X3: fp32 operands contracted as split bf16 (precision "bf16x3"): a K step's two 16-byte chunks g and 4 + g of a row form one
+// 8-float 16x16x32 fragment per lane (the same k set for A and B), split into hi / lo after the LDS read, 3 bf16 MFMAs per block
+template <typename T, typename TO, bool X3>
+__device__ __forceinline__ void gemm_nt_body(const NtParams& p) {
+    static_assert(!X3 || sizeof(T) == 4, "split-bf16 operands are fp32");
     constexpr int EPC = MmaTraits<T>::EPC;
     constexpr int BK = 8 * EPC;                      // elements of K per step (128 bytes)
     __shared__ __attribute__((aligned(16))) char lds_raw[NT_LDS_BYTES];   // operands [buf][A|B][16 KB]; the epilogue staging reuses it
@@ -149,19 +155,38 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(NtParams p) {
     for (int kt = 0; kt < nk; ++kt) {
         const int buf = kt & 1;
         if (kt + 1 < nk) load_tile(kt + 1);              // in flight under the MFMAs below
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            u32x4 fa[4], fb[4];
-            const int chunk = ks * 4 + fg;
+        if constexpr (X3) {
+            bf16x8 ah[4], al[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                fa[i] = *(const u32x4*)(&lds[buf][0][nt_lds_off(wm * 64 + i * 16 + fr, chunk)]);
-                fb[i] = *(const u32x4*)(&lds[buf][1][nt_lds_off(wn * 64 + i * 16 + fr, chunk)]);
+                const int r = wm * 64 + i * 16 + fr;
+                dg_split_bf16(*(const u32x4*)(&lds[buf][0][nt_lds_off(r, fg)]), *(const u32x4*)(&lds[buf][0][nt_lds_off(r, 4 + fg)]),
+                              ah[i], al[i]);
             }
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
+            for (int j = 0; j < 4; ++j) {
+                const int r = wn * 64 + j * 16 + fr;
+                bf16x8 bh, bl;
+                dg_split_bf16(*(const u32x4*)(&lds[buf][1][nt_lds_off(r, fg)]), *(const u32x4*)(&lds[buf][1][nt_lds_off(r, 4 + fg)]),
+                              bh, bl);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) mma16<T>(fa[i], fb[j], acc[i][j]);
+                for (int i = 0; i < 4; ++i) dg_mma16_x3(ah[i], al[i], bh, bl, acc[i][j]);
+            }
+        } else {
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                u32x4 fa[4], fb[4];
+                const int chunk = ks * 4 + fg;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    fa[i] = *(const u32x4*)(&lds[buf][0][nt_lds_off(wm * 64 + i * 16 + fr, chunk)]);
+                    fb[i] = *(const u32x4*)(&lds[buf][1][nt_lds_off(wn * 64 + i * 16 + fr, chunk)]);
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) mma16<T>(fa[i], fb[j], acc[i][j]);
+            }
         }
         if (kt + 1 < nk) store_tile(buf ^ 1);
         __syncthreads();
@@ -179,6 +204,11 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(NtParams p) {
     __builtin_amdgcn_wave_barrier();
     nt_epilogue<T, TO, 64>(stage, m0 + wm * 64, n0 + wn * 64, p, lane);
 }
+
+template <typename T, typename TO>
+__global__ __launch_bounds__(256) void gemm_nt_kernel(NtParams p) { gemm_nt_body<T, TO, false>(p); }
+// precision "bf16x3": every shape the wave-specialised split form does not take (K % 32 != 0 or K < 128)
+__global__ __launch_bounds__(256) void gemm_nt_x3_kernel(NtParams p) { gemm_nt_body<float, float, true>(p); }
 
 static unsigned long long* g_stamp_buffer = nullptr;
 // diagnostic only (tools/gemm_stamps.py): not part of the public header
@@ -268,20 +298,22 @@ extern "C" int dg_gemm_nt_colsum_rows(const dg_gemm_nt_args* a) {
 }
 
 int dg_gemm_nt_fp8_launch(const NtParams& p, int f8, int out_dtype, bool pf, bool wide, int epi, dim3 pgrid, hipStream_t s);   // gemm_fp8.hip
+int dg_gemm_nt_x3_launch(const NtParams& p, bool wide, int epi, dim3 pgrid, hipStream_t s);   // gemm_x3.hip
 
 extern "C" int dg_gemm_nt(const dg_gemm_nt_args* a, void* stream) {
     if (!a || !a->A || !a->B || !a->C || a->M <= 0 || a->N <= 0 || a->K <= 0) return DG_ERR_ARG;
     const bool fp8 = a->in_dtype == DG_FP8_E4M3 || a->in_dtype == DG_FP8_E5M2;
+    const bool x3 = a->in_dtype == DG_F32X3;                  // fp32 operands, split-bf16 contraction
     const int esz = fp8 ? 1 : (a->in_dtype == DG_BF16 ? 2 : 4);
     const int epc = 16 / esz;
-    if (a->in_dtype != DG_BF16 && a->in_dtype != DG_F32 && !fp8) return DG_ERR_DTYPE;
+    if (a->in_dtype != DG_BF16 && a->in_dtype != DG_F32 && !fp8 && !x3) return DG_ERR_DTYPE;
     if (a->out_dtype != DG_BF16 && a->out_dtype != DG_F32) return DG_ERR_DTYPE;
-    if (a->in_dtype == DG_F32 && a->out_dtype == DG_BF16) return DG_ERR_DTYPE;
+    if ((a->in_dtype == DG_F32 || x3) && a->out_dtype == DG_BF16) return DG_ERR_DTYPE;
     if (fp8) {
         // B (the weight operand) is e4m3; per-tensor dequantisation factors are mandatory; only the LDS-DMA kernel has an fp8 form
         if (a->b_dtype != DG_FP8_E4M3 || !a->scale_a || !a->scale_b || a->relu_mask) return DG_ERR_ARG;
         if (a->K % 128 || a->K < 256 || dg_nt_mode() != 0) return DG_ERR_ARG;
-    } else if (a->b_dtype != 0 && a->b_dtype != a->in_dtype) return DG_ERR_DTYPE;
+    } else if (a->b_dtype != 0 && a->b_dtype != a->in_dtype && !(x3 && a->b_dtype == DG_F32)) return DG_ERR_DTYPE;
     if (a->K % epc || a->lda % epc || a->ldb % epc || !dg_aligned16(a->A) || !dg_aligned16(a->B)) return DG_ERR_ALIGN;
     if (a->lda < a->K || a->ldb < a->K || a->ldc < a->N) return DG_ERR_ARG;
     if (a->dropout_p < 0.f || a->dropout_p >= 1.f) return DG_ERR_ARG;
@@ -302,7 +334,10 @@ extern "C" int dg_gemm_nt(const dg_gemm_nt_args* a, void* stream) {
     p.A = (const char*)a->A; p.lda_b = a->lda * esz;
     p.B = (const char*)a->B; p.ldb_b = a->ldb * esz;
     p.C = a->C; p.ldc = a->ldc;
-    p.M = a->M; p.N = a->N; p.K = fp8 ? a->K / 2 : a->K;      // fp8: K in 2-byte units, the kernel's K step is 128 BYTES
+    // split form (x3_ws): the wave-specialised kernel where K is whole 128-byte steps, at least two; the generic one otherwise
+    const bool x3_ws = x3 && a->K % 32 == 0 && a->K >= 128 && dg_nt_mode() == 0;
+    p.M = a->M; p.N = a->N;
+    p.K = fp8 ? a->K / 2 : (x3_ws ? 2 * a->K : a->K);        // fp8 / split: K in 2-byte units, the kernel's K step is 128 BYTES
     p.scale_a = a->scale_a; p.scale_b = a->scale_b;
     p.bias = a->bias; p.relu = a->relu;
     p.relu_mask = a->relu_mask; p.ldmask = a->ldmask;
@@ -332,7 +367,7 @@ extern "C" int dg_gemm_nt(const dg_gemm_nt_args* a, void* stream) {
     p.n_tiles = tiles_m * p.tiles_n;
     dim3 grid(p.n_tiles), block(256);
     hipStream_t s = (hipStream_t)stream;
-    if (fp8 || (a->in_dtype == DG_BF16 && a->K % 64 == 0 && a->K >= 128 && dg_nt_mode() == 0)) {
+    if (fp8 || x3_ws || (a->in_dtype == DG_BF16 && a->K % 64 == 0 && a->K >= 128 && dg_nt_mode() == 0)) {
         dim3 pgrid(p.n_tiles < dg_num_cus() ? p.n_tiles : dg_num_cus());
         static const int pf_mode = [] { const char* e = getenv("DG_GEMM_PF"); return e ? atoi(e) : 1; }();   // 0 = load the mask bits inside the epilogue (A/B runs)
         const bool pf = pf_mode && a->sign_bits != nullptr && p.vec_ok && (!a->bias || dg_aligned16(a->bias)) &&
@@ -357,6 +392,12 @@ extern "C" int dg_gemm_nt(const dg_gemm_nt_args* a, void* stream) {
                 else if (a->bias && !a->relu && !a->relu_mask && !p.drop && !a->residual && !a->sign_bits && !a->sign_bits_out) epi = 5;
                 else if (a->bias && !p.drop && a->residual && !a->relu && !a->relu_mask && !a->sign_bits && !a->sign_bits_out) epi = 7;
             }
+        }
+        if (x3) {
+            const int rc = dg_gemm_nt_x3_launch(p, wide, epi, pgrid, s);
+            if (rc != DG_OK) return rc;
+            DG_LAUNCH_CHECK();
+            return DG_OK;
         }
         if (fp8) {
             const int rc = dg_gemm_nt_fp8_launch(p, a->in_dtype == DG_FP8_E5M2 ? 2 : 1, a->out_dtype, pf, wide, epi, pgrid, s);
@@ -386,6 +427,8 @@ extern "C" int dg_gemm_nt(const dg_gemm_nt_args* a, void* stream) {
         hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, bf16_t>), grid, block, 0, s, p);
     else if (a->in_dtype == DG_BF16)
         hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, float>), grid, block, 0, s, p);
+    else if (x3)
+        hipLaunchKernelGGL(gemm_nt_x3_kernel, grid, block, 0, s, p);
     else
         hipLaunchKernelGGL((gemm_nt_kernel<float, float>), grid, block, 0, s, p);
     DG_LAUNCH_CHECK();
@@ -1260,7 +1303,11 @@ __global__ __launch_bounds__(WT ? 512 : 768) void gemm_tn_grouped256_kernel(type
 // ---- f32: [32 r][128 cols] tiles with 144-float row pitch (pad 16 floats: rows r, r+1 of one
 //      ds_read_b32 half-wave land on different banks)
 #define TNF_PITCH 144
-__global__ __launch_bounds__(256) void gemm_tn_f32_kernel(TnParams p) {
+// X3 (precision "bf16x3"): the 32 rows of a stage are ONE 16x16x32 bf16 k block.  Lane group g supplies rows 4e + g (e < 8) of its
+// column -- 8 scalar LDS reads per fragment, the f32 kernel's count per row, and rows 4 apart per group keep the reads of a wave
+// on distinct banks as there -- split into hi / lo, 3 bf16 MFMAs per block.  Same k permutation for A and B.
+template <bool X3>
+__device__ __forceinline__ void gemm_tn_f32_body(const TnParams& p) {
     constexpr int BR = 32;
     __shared__ __attribute__((aligned(16))) float lds[2][2][BR * TNF_PITCH];     // 73.7 KB
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform -> SGPR
@@ -1305,20 +1352,41 @@ __global__ __launch_bounds__(256) void gemm_tn_f32_kernel(TnParams p) {
     for (int kt = 0; kt < nk; ++kt) {
         const int buf = kt & 1;
         if (kt + 1 < nk) load_tile(kt + 1);
-#pragma unroll
-        for (int ks = 0; ks < BR / 4; ++ks) {
-            float fa[4], fb[4];
-            const int r = ks * 4 + fg;
+        if constexpr (X3) {
+            bf16x8 ah[4], al[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                fa[i] = lds[buf][0][r * TNF_PITCH + wp * 64 + i * 16 + fr];
-                fb[i] = lds[buf][1][r * TNF_PITCH + wq * 64 + i * 16 + fr];
+                float x[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) x[e] = lds[buf][0][(4 * e + fg) * TNF_PITCH + wp * 64 + i * 16 + fr];
+                dg_split_bf16(x, ah[i], al[i]);
             }
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
+            for (int j = 0; j < 4; ++j) {
+                float x[8];
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
+                for (int e = 0; e < 8; ++e) x[e] = lds[buf][1][(4 * e + fg) * TNF_PITCH + wq * 64 + j * 16 + fr];
+                bf16x8 bh, bl;
+                dg_split_bf16(x, bh, bl);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) dg_mma16_x3(ah[i], al[i], bh, bl, acc[i][j]);
+            }
+        } else {
+#pragma unroll
+            for (int ks = 0; ks < BR / 4; ++ks) {
+                float fa[4], fb[4];
+                const int r = ks * 4 + fg;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    fa[i] = lds[buf][0][r * TNF_PITCH + wp * 64 + i * 16 + fr];
+                    fb[i] = lds[buf][1][r * TNF_PITCH + wq * 64 + i * 16 + fr];
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
+            }
         }
         if (kt + 1 < nk) store_tile(buf ^ 1);
         __syncthreads();
@@ -1338,11 +1406,14 @@ __global__ __launch_bounds__(256) void gemm_tn_f32_kernel(TnParams p) {
     }
 }
 
+__global__ __launch_bounds__(256) void gemm_tn_f32_kernel(TnParams p) { gemm_tn_f32_body<false>(p); }
+__global__ __launch_bounds__(256) void gemm_tn_x3_kernel(TnParams p) { gemm_tn_f32_body<true>(p); }
+
 extern "C" int dg_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb,
                           float* out, int64_t ldo, int64_t split_stride, int n_splits,
                           int R, int P, int Q, int dtype, void* stream) {
     if (!A || !B || !out || R <= 0 || P <= 0 || Q <= 0 || n_splits <= 0) return DG_ERR_ARG;
-    if (dtype != DG_BF16 && dtype != DG_F32) return DG_ERR_DTYPE;
+    if (dtype != DG_BF16 && dtype != DG_F32 && dtype != DG_F32X3) return DG_ERR_DTYPE;
     const int esz = dtype == DG_BF16 ? 2 : 4, epc = 16 / esz;
     if (lda % epc || ldb % epc || !dg_aligned16(A) || !dg_aligned16(B)) return DG_ERR_ALIGN;
     if (lda < P || ldb < Q || ldo < Q) return DG_ERR_ARG;
@@ -1374,6 +1445,7 @@ extern "C" int dg_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb
     if (dtype == DG_BF16 && R % 64 == 0 && (tn_mode == 3 || (tn_mode == 0 && one_round)))
         hipLaunchKernelGGL(gemm_tn_ws_kernel, grid, dim3(768), 0, s, p);
     else if (dtype == DG_BF16) hipLaunchKernelGGL(gemm_tn_bf16_kernel, grid, block, 0, s, p);
+    else if (dtype == DG_F32X3) hipLaunchKernelGGL(gemm_tn_x3_kernel, grid, block, 0, s, p);
     else hipLaunchKernelGGL(gemm_tn_f32_kernel, grid, block, 0, s, p);
     DG_LAUNCH_CHECK();
     return DG_OK;

@@ -3,6 +3,7 @@
 #pragma once
 #include "common.h"
 #include <stdlib.h>
+#include <type_traits>
 
 #define BM 128
 #define BN 128
@@ -32,6 +33,30 @@ template <> __device__ __forceinline__ void mma16<float>(const u32x4& a, const u
     f32x4 af = __builtin_bit_cast(f32x4, a), bf = __builtin_bit_cast(f32x4, b);
 #pragma unroll
     for (int j = 0; j < 4; ++j) c = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], bf[j], c, 0, 0, 0);
+}
+
+// Split-bf16 contraction of fp32 operands (precision "bf16x3"): x = hi + lo with hi = bf16(x), lo = bf16(x - hi), and
+// a.b ~ lo_a.hi_b + hi_a.lo_b + hi_a.hi_b on the bf16 matrix cores, fp32 accumulation (the dropped lo_a.lo_b term and the
+// rounding of lo are ~2^-17 of |a.b| per product).  A lane's 8 floats of one 16x16x32 fragment -> its hi and lo parts.
+__device__ __forceinline__ void dg_split_bf16(const float (&x)[8], bf16x8& hi, bf16x8& lo) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const bf16_t h = (bf16_t)x[e];
+        hi[e] = h;
+        lo[e] = (bf16_t)(x[e] - (float)h);
+    }
+}
+// two 16-byte chunks (4 floats each) -> one split fragment
+__device__ __forceinline__ void dg_split_bf16(const u32x4& c0, const u32x4& c1, bf16x8& hi, bf16x8& lo) {
+    const f32x4 a = __builtin_bit_cast(f32x4, c0), b = __builtin_bit_cast(f32x4, c1);
+    const float x[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+    dg_split_bf16(x, hi, lo);
+}
+// c += a.b as three bf16 MFMAs, small terms first
+__device__ __forceinline__ void dg_mma16_x3(const bf16x8& ah, const bf16x8& al, const bf16x8& bh, const bf16x8& bl, f32x4& c) {
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, c, 0, 0, 0);
 }
 
 // LDS image of a [128 rows][128 bytes] operand tile: 16-byte chunk index XORed with row&7
@@ -102,6 +127,9 @@ __device__ __forceinline__ float dpp_f32(float x) {
 // e4m3, A e4m3 (1: forward activations) or e5m2 (2: gradients); p.K then counts 2-byte units (K elements / 2).  The byte
 // geometry of loads, LDS images and fragment reads is identical: lane group g of a fragment holds the 16-byte chunks g and
 // 4 + g of the row's 128 bytes, the same k set for the A and the B operand, which is all a dot product needs.
+// F8 = 3: fp32 operands contracted as split bf16 (precision "bf16x3", dg_mma16_x3): the same geometry gives a lane 8 floats of
+// one 16x16x32 fragment per 128-byte K step, split in registers after the LDS read into hi / lo; THREE bf16 MFMAs per K step and
+// block; p.K counts 2-byte units as for fp8; fp32 output; the tensor-valued relu_mask is read as fp32.
 template <typename TO, bool PF, int NJ, int EPI, int F8 = 0>
 __global__ __launch_bounds__(768) void gemm_nt_ws_kernel(NtParams p) {
     constexpr bool GEN = EPI == 0;
@@ -253,8 +281,22 @@ __global__ __launch_bounds__(768) void gemm_nt_ws_kernel(NtParams p) {
             }
         }
     };
+    auto mma_x3 = [&](const u32x4 (&fa_lo)[2], const u32x4 (&fa_hi)[2], const u32x4 (&fb_lo)[NJ], const u32x4 (&fb_hi)[NJ]) {
+        bf16x8 ah[2], al[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) dg_split_bf16(fa_lo[i], fa_hi[i], ah[i], al[i]);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            bf16x8 bh, bl;
+            dg_split_bf16(fb_lo[j], fb_hi[j], bh, bl);
+#pragma unroll
+            for (int i = 0; i < 2; ++i) dg_mma16_x3(bh, bl, ah[i], al[i], acc[i][j]);     // transposed: D rows = n, cols = m
+        }
+    };
+    constexpr bool SCALED = F8 == 1 || F8 == 2;
+    typedef typename std::conditional<F8 == 3, float, bf16_t>::type MaskT;
     float e_sab = 1.f;
-    if constexpr (F8 != 0) e_sab = p.scale_a[0] * p.scale_b[0];
+    if constexpr (SCALED) e_sab = p.scale_a[0] * p.scale_b[0];
     // EPI 8: scale of the e4m3 copy from the maxima this call site recorded one step ago; this launch's maximum goes to the
     // other slot, one entry per workgroup (zeroed here by its first wave, raised by all eight at the end of the launch)
     float q_sc = 1.f, q_m = 0.f;
@@ -372,7 +414,7 @@ __global__ __launch_bounds__(768) void gemm_nt_ws_kernel(NtParams p) {
                 acc[i][2 * q + 1] = (f32x4){0.f, 0.f, 0.f, 0.f};
                 if (row >= p.M || col >= p.N) continue;
                 if (e_dbg >= 3 && v[0] != 12345.678f) continue;      // ablation: no stores
-                if constexpr (F8 != 0) {
+                if constexpr (SCALED) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] *= e_sab;
                 }
@@ -390,9 +432,10 @@ __global__ __launch_bounds__(768) void gemm_nt_ws_kernel(NtParams p) {
                     for (int e = 0; e < 8; ++e) v[e] = ((bm >> e) & 1u) ? v[e] : 0.f;
                 }
                 if (e_mask) {
-                    const bf16_t* mp = (const bf16_t*)e_mask + (int64_t)row * p.ldmask + col;
+                    const MaskT* mp = (const MaskT*)e_mask + (int64_t)row * p.ldmask + col;
                     if (full && p.mask_vec_ok) {
-                        const bf16x4 m0v = *(const bf16x4*)mp, m1v = *(const bf16x4*)(mp + 4);
+                        typedef MaskT MaskT4 __attribute__((ext_vector_type(4)));
+                        const MaskT4 m0v = *(const MaskT4*)mp, m1v = *(const MaskT4*)(mp + 4);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             v[e] = (float)m0v[e] > 0.f ? v[e] : 0.f;
@@ -495,7 +538,7 @@ __global__ __launch_bounds__(768) void gemm_nt_ws_kernel(NtParams p) {
                 }
                 acc[i][2 * q] = (f32x4){0.f, 0.f, 0.f, 0.f};
                 acc[i][2 * q + 1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                if constexpr (F8 != 0) {
+                if constexpr (SCALED) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] *= e_sab;
                 }
@@ -613,7 +656,15 @@ __global__ __launch_bounds__(768) void gemm_nt_ws_kernel(NtParams p) {
     for (int g = 0; g < total; ++g) {
         const char* buf = lds + (g & (GL_NST - 1)) * STAGE;
         if (PF && kt == pf_at) prefetch_operands(tile_i);
-        if constexpr (F8 != 0) {
+        if constexpr (F8 == 3) {
+            // as fp8: both 16-byte halves of the step's 128 bytes form one fragment (8 floats per lane), split into hi / lo
+            read_frags(fa1, fb1, buf, 1);
+            mma_x3(fa0, fa1, fb0, fb1);
+            if (g + 1 < total) {
+                __builtin_amdgcn_s_barrier();
+                read_frags(fa0, fb0, lds + ((g + 1) & (GL_NST - 1)) * STAGE, 0);
+            }
+        } else if constexpr (F8 != 0) {
             // both halves of the step's fragments feed ONE MFMA per block; the next stage's first half is requested behind
             // the barrier while those MFMAs run
             read_frags(fa1, fb1, buf, 1);

@@ -186,6 +186,9 @@ class TrainEngine:
         self.dev = p0.device
         self.act = model.act_dtype
         self.fp8 = bool(getattr(model, "fp8", False))
+        # precision "bf16x3": the fp32 program (act fp32: split-K dW slabs, no chain kernel, no grouped dW) with every GEMM
+        # contracted as split bf16
+        self.split_bf16 = bool(getattr(model, "split_bf16", False))
         self.fp8_sites: Dict[str, Tensor] = {}
         self._fp8_seeded = False
         self.B = int(batch_size)
@@ -784,7 +787,7 @@ class TrainEngine:
         seed = self.fp8 and not self._fp8_seeded
         if seed:
             self._fp8_seeded = True
-        return S.Run(act=self.act, rng=self.state if self.p_drop > 0.0 else None, weights=self.weights, fp8=self.fp8,
+        return S.Run(act=self.act, rng=self.state if self.p_drop > 0.0 else None, weights=self.weights, fp8=self.fp8, split=self.split_bf16,
                      fp8_sites=self.fp8_sites if self.fp8 else None, fp8_seed=seed, step_word=self.state, stream=self.stream_dtype,
                      fp8_only=self.fp8 and self.fp8_dw and self.grouped_dw and _os_env("DG_FP8_ONLY", "1") != "0")
 
@@ -1015,7 +1018,7 @@ class TrainEngine:
     @torch.no_grad()
     def eval_loss(self, x: Tensor, y: Tensor) -> Tensor:
         """forward only, dropout off (ref: evaluate_loss, src/train.py:61-75)"""
-        run = S.Run(act=self.act, rng=None, weights=self.weights, fp8=self.fp8)
+        run = S.Run(act=self.act, rng=None, weights=self.weights, fp8=self.fp8, split=self.split_bf16)
         _, rows, _ = self._forward(run, x, y, False)
         return ops.reduce_sum(rows, 1.0 / rows.numel())
 
@@ -1040,7 +1043,7 @@ class TrainEngine:
             self.ev_loss = torch.zeros(1, dtype=torch.float32, device=self.dev)
 
             def prog():
-                run = S.Run(act=self.act, rng=None, weights=self.weights, fp8=self.fp8)
+                run = S.Run(act=self.act, rng=None, weights=self.weights, fp8=self.fp8, split=self.split_bf16)
                 _, rows, _ = self._forward(run, self.ev_x, self.ev_y, False)
                 ops.reduce_sum(rows, 1.0 / rows.numel(), out=self.ev_loss)
             side = torch.cuda.Stream(device=self.dev)

@@ -14,10 +14,11 @@ Tensor = torch.Tensor
 
 
 def _run(act, rng: Optional[Tensor]) -> S.Run:
-    """act: the activation dtype, or "fp8" (HipModule.run_mode): bf16 activations, fp8 operands for the block Linears"""
-    fp8 = act == "fp8"
-    dt = torch.bfloat16 if fp8 else act
-    return S.Run(act=dt, rng=rng, weights=S.OnTheFlyWeights(dt), fp8=fp8)
+    """act: the activation dtype, or "fp8" (HipModule.run_mode): bf16 activations, fp8 operands for the block Linears, or
+    "bf16x3": fp32 activations, every GEMM contracted as split bf16"""
+    fp8, split = act == "fp8", act == "bf16x3"
+    dt = torch.bfloat16 if fp8 else (torch.float32 if split else act)
+    return S.Run(act=dt, rng=rng, weights=S.OnTheFlyWeights(dt), fp8=fp8, split=split)
 
 
 class EmbedFn(torch.autograd.Function):

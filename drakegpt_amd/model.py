@@ -67,7 +67,7 @@ class _LM(HipModule):
         return False
 
     def _head(self, x):
-        return HF.linear(x, self.lm_head.weight, self.lm_head.bias, self.act_dtype)
+        return HF.linear(x, self.lm_head.weight, self.lm_head.bias, "bf16x3" if self.split_bf16 else self.act_dtype)
 
     check_ids = True      # False: skip the id range check (one or two device-to-host syncs per forward that nn.Embedding does not
                           # have) once a data source has been validated -- ids out of range are then CLAMPED by the kernels
@@ -229,20 +229,21 @@ class TransformerLM(_BlocksLM):
     def _decode_step(self, tok_col, t, caches, ws, w_lm):
         """logits (B, V) of the token at position t; K/V of position t are appended to the caches."""
         act = self.act_dtype
+        sp = self.split_bf16          # precision bf16x3: split-bf16 contractions
         B = tok_col.shape[0]
         NH = len(self.blocks[0].sa_head.heads)
         H = self.blocks[0].sa_head.heads[0].head_size
         x = ops.embed_fwd(tok_col, self.token_embedding_table.weight, self.position_embedding_table.weight[t:t + 1]).view(B, -1)
         for W, cache in zip(ws, caches):
             h, _, _ = ops.layernorm_fwd(x, W["ln1w"], W["ln1b"], act)
-            ops.gemm_nt(h, W["wqkv"], act, out=cache[:, t])                       # q/k/v row t straight into the cache
+            ops.gemm_nt(h, W["wqkv"], act, out=cache[:, t], split=sp)             # q/k/v row t straight into the cache
             o = ops.attn_decode(cache, t, NH, H, H ** -0.5)
-            x = ops.gemm_nt(o, W["wproj"], torch.float32, bias=W["bproj"], residual=x)
+            x = ops.gemm_nt(o, W["wproj"], torch.float32, bias=W["bproj"], residual=x, split=sp)
             h, _, _ = ops.layernorm_fwd(x, W["ln2w"], W["ln2b"], act)
-            f = ops.gemm_nt(h, W["w1"], act, bias=W["b1"], relu=True)
-            x = ops.gemm_nt(f, W["w2"], torch.float32, bias=W["b2"], residual=x)
+            f = ops.gemm_nt(h, W["w1"], act, bias=W["b1"], relu=True, split=sp)
+            x = ops.gemm_nt(f, W["w2"], torch.float32, bias=W["b2"], residual=x, split=sp)
         xa = x if act == torch.float32 else ops.cast(x, act)
-        return ops.gemm_nt(xa, w_lm, torch.float32, bias=self.lm_head.bias)
+        return ops.gemm_nt(xa, w_lm, torch.float32, bias=self.lm_head.bias, split=sp)
 
     @torch.no_grad()
     def _prefill(self, idx, caches, ws, w_lm):
@@ -250,22 +251,23 @@ class TransformerLM(_BlocksLM):
         K/V cache rows [0, t0) and returns the logits (B, V) of the last prompt position -- the values the reference's full
         forward produces for it (the uncached path runs exactly these kernels)."""
         act = self.act_dtype
+        sp = self.split_bf16          # precision bf16x3: split-bf16 contractions
         B, t0 = idx.shape
         NH = len(self.blocks[0].sa_head.heads)
         H = self.blocks[0].sa_head.heads[0].head_size
         x = ops.embed_fwd(idx, self.token_embedding_table.weight, self.position_embedding_table.weight).view(B * t0, -1)
         for W, cache in zip(ws, caches):
             h, _, _ = ops.layernorm_fwd(x, W["ln1w"], W["ln1b"], act)
-            qkv = ops.gemm_nt(h, W["wqkv"], act)
+            qkv = ops.gemm_nt(h, W["wqkv"], act, split=sp)
             cache[:, :t0].copy_(qkv.view(B, t0, -1))
             o, _ = ops.attn_fwd(qkv, B, t0, NH, H, H ** -0.5, 0.0, None, 0)
-            x = ops.gemm_nt(o, W["wproj"], torch.float32, bias=W["bproj"], residual=x)
+            x = ops.gemm_nt(o, W["wproj"], torch.float32, bias=W["bproj"], residual=x, split=sp)
             h, _, _ = ops.layernorm_fwd(x, W["ln2w"], W["ln2b"], act)
-            f = ops.gemm_nt(h, W["w1"], act, bias=W["b1"], relu=True)
-            x = ops.gemm_nt(f, W["w2"], torch.float32, bias=W["b2"], residual=x)
+            f = ops.gemm_nt(h, W["w1"], act, bias=W["b1"], relu=True, split=sp)
+            x = ops.gemm_nt(f, W["w2"], torch.float32, bias=W["b2"], residual=x, split=sp)
         last = x.view(B, t0, -1)[:, -1].contiguous()
         xa = last if act == torch.float32 else ops.cast(last, act)
-        return ops.gemm_nt(xa, w_lm, torch.float32, bias=self.lm_head.bias)
+        return ops.gemm_nt(xa, w_lm, torch.float32, bias=self.lm_head.bias, split=sp)
 
     def generate(self, idx, max_new_tokens, generator: Optional[torch.Generator] = None, use_cache: bool = True):
         """ref: src/model.py:611-636.  While the sequence still fits the context window the per-layer K/V of the

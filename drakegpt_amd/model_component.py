@@ -14,7 +14,9 @@ path in this package.
 
 precision: "fp32" (default; exact-fp32 MFMA, tracks the reference to ~1e-6), "bf16" (bf16 MFMA
 operands and stored activations, fp32 accumulation / residual stream / master weights) or "fp8" (as
-"bf16", with the Linears of the residual blocks on OCP fp8 operands: e4m3 forward, e5m2 gradients).
+"bf16", with the Linears of the residual blocks on OCP fp8 operands: e4m3 forward, e5m2 gradients) or "bf16x3" (stored as
+"fp32"; every GEMM contracted on the bf16 matrix cores as hi.hi + hi.lo + lo.hi of split operands, hi = bf16(x),
+lo = bf16(x - hi): about fp32 accuracy at several times the exact-fp32 MFMA rate).
 """
 from __future__ import annotations
 
@@ -28,7 +30,8 @@ from . import ops
 
 # "fp8": activations are stored as in "bf16"; the operands of the residual blocks' Linears (forward and dX) are quantised to OCP
 # fp8 (e4m3 forward, e5m2 gradients) with per-tensor just-in-time scales for the block-scaled MFMA (BASELINE.json configs[4])
-_PRECISIONS = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp8": torch.bfloat16}
+# "bf16x3": stored exactly as "fp32"; only the contractions change (split-bf16 GEMMs, sublayers.Run.split)
+_PRECISIONS = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp8": torch.bfloat16, "bf16x3": torch.float32}
 
 
 class HipModule(nn.Module):
@@ -52,9 +55,14 @@ class HipModule(nn.Module):
         return self.precision == "fp8"
 
     @property
+    def split_bf16(self) -> bool:
+        return self.precision == "bf16x3"
+
+    @property
     def run_mode(self):
-        """what the autograd shells hand to sublayers.Run: the activation dtype, or "fp8" (bf16 activations + fp8 GEMM operands)"""
-        return "fp8" if self.fp8 else self.act_dtype
+        """what the autograd shells hand to sublayers.Run: the activation dtype, "fp8" (bf16 activations + fp8 GEMM operands)
+        or "bf16x3" (fp32 activations + split-bf16 GEMMs)"""
+        return "fp8" if self.fp8 else ("bf16x3" if self.split_bf16 else self.act_dtype)
 
     def set_precision(self, precision: str) -> "HipModule":
         if precision not in _PRECISIONS:

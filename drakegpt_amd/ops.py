@@ -13,7 +13,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import DG_BF16, DG_F32, DG_FP8_E4M3, DG_FP8_E5M2, GemmNtArgs, check, lib
+from ._lib import DG_BF16, DG_F32, DG_F32X3, DG_FP8_E4M3, DG_FP8_E5M2, GemmNtArgs, check, lib
 
 Tensor = torch.Tensor
 
@@ -262,8 +262,10 @@ def gemm_nt(A: Tensor, Bm: Tensor, out_dtype: torch.dtype, *, N: Optional[int] =
             residual: Optional[Tensor] = None, dropout_p: float = 0.0, rng_state: Optional[Tensor] = None,
             site: int = 0, out: Optional[Tensor] = None, sign_bits_out: Optional[Tensor] = None,
             sign_bits: Optional[Tensor] = None, colsum_part: Optional[Tensor] = None,
-            scale_a: Optional[Tensor] = None, scale_b: Optional[Tensor] = None, fp8_out=None, fp8_out_only: bool = False) -> Tensor:
+            scale_a: Optional[Tensor] = None, scale_b: Optional[Tensor] = None, fp8_out=None, fp8_out_only: bool = False,
+            split: bool = False) -> Tensor:
     """out[M,N] = epilogue(A[M,K] @ Bm[N,K]^T).  A/Bm may carry padding columns beyond K (ld > K).
+    split: fp32 A / Bm / relu_mask contracted as split bf16 (hi.hi + hi.lo + lo.hi, precision "bf16x3"); fp32 output.
     fp8_out_only: with fp8_out, do not write `out` (nobody reads the bf16 form); the returned tensor is marked dg_unwritten.
     fp8_out: (q8 [M, N] float8_e4m3fn -- float8_e5m2 in the dX direction --, parts2 fp32 [2 * FP8_AMAX_PARTS], step_state, scale_inv fp32 [1]) -- the epilogue also
     writes the output as e4m3 with delayed scaling (what fp8_quantize_delayed would make of it); only where
@@ -275,6 +277,9 @@ def gemm_nt(A: Tensor, Bm: Tensor, out_dtype: torch.dtype, *, N: Optional[int] =
     _chk(A, "A", contiguous=False)
     _chk(Bm, "B", contiguous=False)
     fp8 = A.dtype in FP8_DTYPES
+    if split and (A.dtype != torch.float32 or Bm.dtype != torch.float32 or out_dtype != torch.float32
+                  or (out is not None and out.dtype != torch.float32)):
+        raise TypeError(f"gemm_nt: split=True needs fp32 operands and an fp32 output (got {A.dtype}, {Bm.dtype} -> {out_dtype})")
     if fp8:
         if Bm.dtype != torch.float8_e4m3fn or scale_a is None or scale_b is None:
             raise TypeError("gemm_nt: fp8 operands need a float8_e4m3fn B operand and both dequantisation scales")
@@ -292,7 +297,7 @@ def gemm_nt(A: Tensor, Bm: Tensor, out_dtype: torch.dtype, *, N: Optional[int] =
     a.B, a.ldb = _p(Bm), _ld(Bm)
     a.C, a.ldc = _p(out), _ld(out)
     a.M, a.N, a.K = M, N, K
-    a.in_dtype, a.out_dtype = dt_code(A.dtype), dt_code(out.dtype)
+    a.in_dtype, a.out_dtype = (DG_F32X3 if split else dt_code(A.dtype)), dt_code(out.dtype)
     if fp8:
         a.b_dtype, a.scale_a, a.scale_b = dt_code(Bm.dtype), _p(scale_a), _p(scale_b)
     if bias is not None:
@@ -425,15 +430,19 @@ def new_sign_bits(M: int, N: int, device) -> Tensor:
     return torch.empty(int(lib.dg_gemm_nt_sign_bits_bytes(M, N)), dtype=torch.uint8, device=device)
 
 
-def gemm_tn(A: Tensor, Bm: Tensor, out_part: Tensor, split_stride: int, n_splits: int, P: int, Q: int, ldo: Optional[int] = None) -> None:
-    """partials of dW[P,Q] = sum_r A[r,:P]^T B[r,:Q] into out_part (+ s*split_stride)."""
+def gemm_tn(A: Tensor, Bm: Tensor, out_part: Tensor, split_stride: int, n_splits: int, P: int, Q: int, ldo: Optional[int] = None,
+            split: bool = False) -> None:
+    """partials of dW[P,Q] = sum_r A[r,:P]^T B[r,:Q] into out_part (+ s*split_stride).
+    split: fp32 operands contracted as split bf16 (precision "bf16x3")."""
     _chk(A, "A", contiguous=False)
     _chk(Bm, "B", contiguous=False)
     _chk(out_part, "out_part", torch.float32, contiguous=False)
+    if split and (A.dtype != torch.float32 or Bm.dtype != torch.float32):
+        raise TypeError(f"gemm_tn: split=True needs fp32 operands (got {A.dtype}, {Bm.dtype})")
     if A.dtype != Bm.dtype or A.shape[0] != Bm.shape[0]:
         raise RuntimeError("gemm_tn: operand mismatch")
     check(lib.dg_gemm_tn(_p(A), _ld(A), _p(Bm), _ld(Bm), _p(out_part), Q if ldo is None else ldo, split_stride, n_splits,
-                         A.shape[0], P, Q, dt_code(A.dtype), _stream()), "dg_gemm_tn")
+                         A.shape[0], P, Q, DG_F32X3 if split else dt_code(A.dtype), _stream()), "dg_gemm_tn")
 
 
 def _tn_problem_array(problems):

@@ -149,14 +149,14 @@ class LocalSink:
         return out
 
 
-def weight_grad(sink, key: str, dy: Tensor, x: Tensor, P: int, Q: int) -> None:
+def weight_grad(sink, key: str, dy: Tensor, x: Tensor, P: int, Q: int, split: bool = False) -> None:
     """dW[P,Q] = dy[:, :P]^T x[:, :Q].  A sink with `defer` (engine, bf16) only records the operands and computes
     every dW of the step in one grouped launch at the end of backward; otherwise split-K partials now."""
     defer = getattr(sink, "defer", None)
     if defer is not None and defer(key, dy, x, P, Q):
         return
     part, stride, n = sink.matrix(key, P, Q)
-    ops.gemm_tn(dy, x, part, stride, n, P, Q)
+    ops.gemm_tn(dy, x, part, stride, n, P, Q, split=split)
 
 
 @dataclass
@@ -172,6 +172,7 @@ class Run:
     stream: torch.dtype = torch.float32  # type of the residual-branch gradient stream (engine, bf16 / fp8 modes: bf16)
     fp8_only: bool = False               # engine, precision fp8 with the fp8 dW: the FFN hidden layer and its gradient are read as fp8
                                          # only (by the next GEMM and by the grouped dW launch), so their bf16 form is not written
+    split: bool = False                  # precision = "bf16x3": fp32 operands, every GEMM contracted as split bf16 (hi + lo)
 
     def p(self, p: float) -> float:
         return p if (self.rng is not None and p > 0.0) else 0.0
@@ -214,7 +215,7 @@ def linear_nt(run: Run, x: Tensor, W: Tensor, out_dtype: torch.dtype, fp8_site: 
         x.dg_fp8x = (xq, xs)        # the e4m3 copy travels with the activation: it is also the X operand of this Linear's fp8 dW
         return ops.gemm_nt(xq, wq, out_dtype, scale_a=xs, scale_b=ws, **epi)
     _refuse_unwritten(x)
-    return ops.gemm_nt(x, run.weights.fwd(W), out_dtype, **epi)
+    return ops.gemm_nt(x, run.weights.fwd(W), out_dtype, split=run.split, **epi)
 
 
 def _fused_fp8_out(run: Run, site: str, M: int, N: int, K: int, dev, grad: bool = False):
@@ -241,7 +242,7 @@ def linear_dx(run: Run, g: Tensor, W: Tensor, out_dtype: torch.dtype, fp8_site: 
             g.dg_fp8 = (gq, gs)     # (also the dY operand of this Linear's fp8 dW, looked up when the grouped launch is assembled)
             return ops.gemm_nt(gq, wq, out_dtype, K=K, scale_a=gs, scale_b=ws, **epi)
     _refuse_unwritten(g)
-    return ops.gemm_nt(g, run.weights.bwd(W), out_dtype, K=K, **epi)
+    return ops.gemm_nt(g, run.weights.bwd(W), out_dtype, K=K, split=run.split, **epi)
 
 
 def _op_dtype(run: Run, k: int, grad: bool = False):
@@ -388,7 +389,7 @@ def attn_bwd(run: Run, saved, dy: Tensor, ln_w: Optional[Tensor], wqkv: Tensor, 
             part, stride, n = sink.vector(keys["bproj"], wproj.shape[0])
             g = ops.dropout_bwd_cast(dy, run.act, run.p(p_proj), run.rng, site_proj(layer), colsum_part=part,
                                      part_stride=stride, n_partials=n)
-        weight_grad(sink, keys["wproj"], g, o, wproj.shape[0], wproj.shape[1])
+        weight_grad(sink, keys["wproj"], g, o, wproj.shape[0], wproj.shape[1], split=run.split)
         do = linear_dx(run, g, wproj, run.act, fp8_site=f"{layer}.g_proj")
     else:
         do = _as_act(run, dy)
@@ -400,7 +401,7 @@ def attn_bwd(run: Run, saved, dy: Tensor, ln_w: Optional[Tensor], wqkv: Tensor, 
                         fp8_out_only=f8 is not None and run.fp8_only)
     if need_dx and run.fp8_seed:
         _attn_fp8_out(run, gkey, dqkv, B, T, NH, H, wqkv.shape[0])
-    weight_grad(sink, keys["wqkv"], dqkv, h, wqkv.shape[0], wqkv.shape[1])
+    weight_grad(sink, keys["wqkv"], dqkv, h, wqkv.shape[0], wqkv.shape[1], split=run.split)
     if not need_dx:
         return None
     if ln_w is not None:
@@ -464,7 +465,7 @@ def ffn_bwd(run: Run, saved, dy: Tensor, ln_w: Optional[Tensor], w1: Tensor, w2:
             part, stride, n = sink.vector(keys["b2"], w2.shape[0])
             g = ops.dropout_bwd_cast(dy, run.act, run.p(p), run.rng, site_ffn(layer), colsum_part=part, part_stride=stride,
                                      n_partials=n)
-        weight_grad(sink, keys["w2"], g, f, w2.shape[0], w2.shape[1])
+        weight_grad(sink, keys["w2"], g, f, w2.shape[0], w2.shape[1], split=run.split)
         cs_part = None
         vector_rows = getattr(sink, "vector_rows", None)
         if bits is not None and vector_rows is not None:
@@ -483,10 +484,10 @@ def ffn_bwd(run: Run, saved, dy: Tensor, ln_w: Optional[Tensor], w1: Tensor, w2:
             if bits is not None:
                 df = linear_dx(run, g, w2, run.act, fp8_site=f"{layer}.g_ffn", sign_bits=bits)
             else:
-                df = ops.gemm_nt(g, run.weights.bwd(w2), run.act, K=w2.shape[0], relu_mask=f)
+                df = ops.gemm_nt(g, run.weights.bwd(w2), run.act, K=w2.shape[0], relu_mask=f, split=run.split)
             part, stride, n = sink.vector(keys["b1"], w1.shape[0])
             ops.colsum(df, part, stride, n)
-    weight_grad(sink, keys["w1"], df, h, w1.shape[0], w1.shape[1])
+    weight_grad(sink, keys["w1"], df, h, w1.shape[0], w1.shape[1], split=run.split)
     if not need_dx:
         return None
     d8 = (df8[0], df8[3]) if (w2 is not None and df8 is not None) else None
@@ -508,7 +509,7 @@ def linear_fwd(run: Run, x2d: Tensor, w: Tensor, b: Optional[Tensor], pad_rows: 
     N = w.shape[0]
     if out is None and pad_rows and N % 4:
         out = torch.empty((x2d.shape[0], pad_to(N, 4)), dtype=torch.float32, device=x2d.device)[:, :N]
-    y = ops.gemm_nt(xa, run.weights.fwd(w), out.dtype if out is not None else torch.float32, bias=b, out=out)
+    y = ops.gemm_nt(xa, run.weights.fwd(w), out.dtype if out is not None else torch.float32, bias=b, out=out, split=run.split)
     return y, (xa,)
 
 
@@ -520,7 +521,7 @@ def linear_bwd_from_act(run: Run, saved, g: Tensor, w: Tensor, has_bias: bool, s
     if has_bias and not bias_done:
         part, stride, n = sink.vector(keys["b"], N)
         ops.colsum(g, part, stride, n, N=N)
-    weight_grad(sink, keys["w"], g, xa, N, K)
+    weight_grad(sink, keys["w"], g, xa, N, K, split=run.split)
     if not need_dx:
         return None
     d8 = getattr(g, "dg_fp8", None)
@@ -532,7 +533,7 @@ def linear_bwd_from_act(run: Run, saved, g: Tensor, w: Tensor, has_bias: bool, s
     if d8 is not None and w8 is not None and fp8_k_ok(Kp) and ops._ld(d8[0]) >= Kp and w8[0].shape[1] >= Kp:
         # fp8 head: e5m2 dlogits (a-priori scale, from the loss kernel) x the e4m3 W^T shadow, contraction over the padded vocabulary
         return ops.gemm_nt(d8[0], w8[0], run.stream, K=Kp, scale_a=d8[1], scale_b=w8[1])
-    return ops.gemm_nt(g, run.weights.bwd(w), run.stream, K=Kp)   # the head of the gradient stream
+    return ops.gemm_nt(g, run.weights.bwd(w), run.stream, K=Kp, split=run.split)   # the head of the gradient stream
 
 
 def linear_bwd(run: Run, saved, dy: Tensor, w: Tensor, has_bias: bool, sink, keys, need_dx: bool = True):

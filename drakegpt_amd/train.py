@@ -113,7 +113,7 @@ def engine_loop(engine, n_train: int, T: int, B: int, rank: int, world: int, ite
     engine.check_status()         # end of the run: a timed-out dW hand-over must not end in a saved checkpoint
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="Train a DrakeGPT language model on MI355X")
     ap.add_argument("--model", default="TransformerLM", choices=list(MODEL_CLASSES))
     ap.add_argument("--scale", action="store_true", help="use SCALE_PARAMS (ref: --scale True)")
@@ -128,10 +128,14 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=TRAIN["iters"])
     ap.add_argument("--eval-interval", type=int, default=TRAIN["eval_interval"])
     ap.add_argument("--eval-iters", type=int, default=TRAIN["eval_iters"])
-    ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32", "fp8"])
+    ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32", "fp8", "bf16x3"])
     ap.add_argument("--model-dir", default="model")
     ap.add_argument("--sample", type=int, default=100)
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
 
     torch.manual_seed(42)
     if not torch.cuda.is_available():

@@ -39,13 +39,16 @@ extern "C" {
 #define DG_BF16 1
 #define DG_FP8_E4M3 2      /* OCP e4m3fn (gfx950's fp8; NOT MI300's fnuz encoding), max 448 */
 #define DG_FP8_E5M2 3      /* OCP e5m2, max 57344 */
+#define DG_F32X3 4         /* fp32 operands in memory, contracted as split bf16 (hi.hi + hi.lo + lo.hi, hi = bf16(x),
+                              lo = bf16(x - hi), fp32 accumulation): in_dtype of dg_gemm_nt (out_dtype DG_F32) and dtype of
+                              dg_gemm_tn only; every other entry point rejects it with DG_ERR_DTYPE */
 
 #define DG_OK 0
 #define DG_ERR_ARG (-1)       /* bad size / null pointer / unsupported combination */
 #define DG_ERR_ALIGN (-2)     /* pointer or leading dimension not 16-byte aligned */
 #define DG_ERR_DTYPE (-3)
 
-#define DG_ABI_VERSION 20   /* bump whenever a signature or struct of this header changes: the Python binding refuses a stale library */
+#define DG_ABI_VERSION 21   /* bump whenever a signature or struct of this header changes: the Python binding refuses a stale library */
 
 int dg_version(void);
 const char* dg_error_string(int code);
@@ -141,7 +144,8 @@ int dg_layernorm_bwd_fused_fp8(const void* dy, int dy_dtype, const float* x, con
  *    v = acc + bias[n];  v = max(v,0) if relu;  v = 0 where relu_mask[m,n] <= 0 (or its sign_bits bit is clear);
  *    v = dropout(v; p, site);  v += residual[m,n];  C[m,n] = (out_dtype) v
  * in_dtype: type of A, B and relu_mask.  K and lda/ldb must be multiples of 16 bytes' worth of
- * elements (8 bf16 / 4 f32) and A, B 16-byte aligned.
+ * elements (8 bf16 / 4 f32) and A, B 16-byte aligned.  DG_F32X3: fp32 A, B and relu_mask, split-bf16 contraction, fp32
+ * output; no sign_bits / colsum / fp8 outputs.
  * sign_bits_out / sign_bits: the ReLU mask as one BIT per element (C[m,n] > 0).  The forward Linear+ReLU of
  * FeedForward (ref: src/model_component.py:321-322) emits it next to C; the dX GEMM of the second Linear consumes it
  * instead of re-reading the 16x larger activation.  The buffer (dg_gemm_nt_sign_bits_bytes(M, N) bytes) is OPAQUE: bits
@@ -227,7 +231,8 @@ int dg_fp8_quantize_delayed(const void* x, int dtype, void* q, int fmt, int64_t 
  * The contraction over the R = B*T rows is split n_splits ways across workgroups; split s
  * writes its fp32 partial to out + s*split_stride (finish with dg_reduce_partials).
  * P and Q need no alignment; lda/ldb must be multiples of 8 bf16 / 4 f32 and every 16-byte
- * chunk that starts left of P (resp. Q) must be readable. */
+ * chunk that starts left of P (resp. Q) must be readable.  dtype DG_BF16, DG_F32, or DG_F32X3 (fp32
+ * operands, split-bf16 contraction). */
 int dg_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb,
                float* out, int64_t ldo, int64_t split_stride, int n_splits,
                int R, int P, int Q, int dtype, void* stream);
