@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: training tokens/s of TransformerLM_scaled (fwd + bwd + AdamW) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config scaled] [--batch B] [--precision bf16] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config scaled] [--batch B] [--precision bf16] [--dump-outputs DIR] [--full]
 
 N > 1 is launched by the driver as `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`
 (one process per GPU, RCCL): weak scaling, every rank trains B_local rows of the same global batch and
@@ -13,15 +13,18 @@ dropout 0.2 (src/config.py:27-38), batch 64 per GPU, synthetic uniform char corp
 fp32 accumulation / master weights.  Inputs (corpus, window offsets) are resident in HBM when the
 timed region starts.
 
-Beside the headline line's fields the JSON carries (N = 1 only, timed AFTER the headline region, each with its own engine):
-`extra_configs` -- the same model at dropout 0 and at the largest batch (B = 256), and the GPT-2-small shape (BASELINE.json
-configs[2]: V 50257, C 768, T 1024, 12 x 12, B = 8), each as tokens/s + fraction of the bf16 MFMA peak; `hbm_kernels` -- the
-HBM-bound kernels of the step (LayerNorm fwd / bwd, cross entropy, AdamW, embedding fwd / bwd, batch gather) as achieved GB/s
-= algorithmic bytes / launch duration (HIP events, back to back), SURVEY.md section 8d.
+A plain run sets up, warms up, times the K steps, writes its outputs if --dump-outputs is given and prints the line: the
+fields below stay null.  --full fills them too, each in runs of its own AFTER the headline region (which is the same either way).
 
-roofline: the MFMA-bound kernel symbol that takes the most time in the step; `achieved` is its
+`extra_configs` (N = 1, each with its own engine) -- the same model at dropout 0 and at the largest batch (B = 256), and the
+GPT-2-small shape (BASELINE.json configs[2]: V 50257, C 768, T 1024, 12 x 12, B = 8), each as tokens/s + fraction of the bf16
+MFMA peak; `hbm_kernels` (beside roofline) -- the HBM-bound kernels of the step (LayerNorm fwd / bwd, cross entropy, AdamW,
+embedding fwd / bwd, batch gather) as achieved GB/s = algorithmic bytes / launch duration (HIP events, back to back), SURVEY.md
+section 8d.
+
+roofline (--full, any N, rank 0): the MFMA-bound kernel symbol that takes the most time in the step; `achieved` is its
 algorithmic FLOP per launch / its average launch duration, both taken live with HIP events on the
-launch stream in an eager (un-captured) replay of the same step.  cpu_baseline: the CPU oracle
+launch stream in an eager (un-captured) replay of the same step.  cpu_baseline (--full, N = 1): the CPU oracle
 (oracle/drake_ref.py, bit-identical to the reference) timed on this host on a bounded sample.
 """
 from __future__ import annotations
@@ -54,7 +57,7 @@ def flops_per_token(cfg, V):
     return 3 * (L * (24 * C * C + 2 * (T + 1) * C) + 2 * C * V)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
@@ -63,16 +66,36 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="rows per GPU (default: the preset's batch_size)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32", "fp8"])
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra_configs leg (p = 0, B = 256, GPT-2-small)")
+    ap.add_argument("--full", action="store_true", help="after the headline line's timed steps also run the legs that take runs "
+                    "of their own: roofline + hbm_kernels, extra_configs (N = 1) and cpu_baseline (N = 1); a plain run skips them")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="--full without the roofline / hbm_kernels leg")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the extra_configs leg (p = 0, B = 256, GPT-2-small, ...)")
     ap.add_argument("--dropout", type=float, default=None, help="override the preset's dropout")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (loss, updated parameters, gradients) as "
                     "DIR/<name>.npy in float32, at most 64 MB in all (see dump_outputs)")
     ap.add_argument("--dp-buckets", type=int, default=None, help="N > 1: layer groups whose gradient ranges are all-reduced while the "
                     "next group's backward runs (default: by gradient size, see TrainEngine._choose_buckets)")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def after_legs(args, world):
+    """the legs rank 0 runs after the headline line's timed steps: none in a plain run"""
+    if not args.full:
+        return set()
+    legs = set()
+    if not args.no_kernel_timing:
+        legs.add("roofline")
+    if world == 1 and not args.no_extra and args.config == "scaled" and args.precision == "bf16":
+        legs.add("extra_configs")
+    if world == 1 and not args.no_cpu_baseline:
+        legs.add("cpu_baseline")
+    return legs
+
+
+def main():
+    args = parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -167,11 +190,12 @@ def main():
 
     if rank == 0:
         log(f"{tok_s:.0f} tokens/s, {1e3 * dt / args.steps:.3f} ms/step, loss {final_loss:.4f}")
+    legs = after_legs(args, world) if rank == 0 else set()
     roofline = hbm_kernels = None
-    if rank == 0 and not args.no_kernel_timing:
+    if "roofline" in legs:
         roofline, hbm_kernels = kernel_roofline(eng, offs[0], peak)
     extra = None
-    if rank == 0 and world == 1 and not args.no_extra and args.config == "scaled" and args.precision == "bf16":
+    if "extra_configs" in legs:
         del eng, model
         torch.cuda.empty_cache()
         extra = {}
@@ -194,7 +218,7 @@ def main():
                 log(f"extra {name} failed: {extra[name]['error']}")
             torch.cuda.empty_cache()
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if "cpu_baseline" in legs:
         cpu_baseline = cpu_baseline_leg(args.config, cfg, V)
 
     if rank == 0:

@@ -371,6 +371,28 @@ def test_bench_entry_under_torch_distributed_run():
     assert out["config"]["parallelism"] == "dp1" and "TransformerLM_scaled" in out["config"]["workload"] and out["dtype"] == "bf16"
 
 
+def test_bench_plain_run_is_the_headline_only():
+    """`python bench.py --steps K --warmup W` without --full: the headline line's fields, and none of the legs that take
+    runs of their own (roofline / hbm_kernels, extra_configs, cpu_baseline) -- the line says so with nulls"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2"],
+                       env=env, capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["metric"] == "training tokens/sec (fwd+bwd+AdamW)" and out["unit"] == "tokens/s" and out["higher_is_better"] is True
+    assert out["steps"] == 3 and out["warmup"] == 2 and out["dtype"] == "bf16" and out["value"] > 0 and out["ms_per_step"] > 0
+    assert out["roofline"] is None and out["hbm_kernels"] is None and out["extra_configs"] is None and out["cpu_baseline"] is None
+    assert "[bench] cpu baseline" not in r.stderr and "[bench] extra " not in r.stderr, r.stderr[-2000:]
+
+
 def rel(a, b):
     a, b = a.double().cpu(), b.double().cpu()
     return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()

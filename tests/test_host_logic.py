@@ -256,3 +256,21 @@ def test_bench_dump_outputs_bounded_and_repeatable(tmp_path, monkeypatch):
         assert a.dtype == np.float32 and np.array_equal(a, b)
     g = np.load(tmp_path / "a" / "grad.0.weight.npy")
     assert 0 < g.size < 300 * 200 and np.isin(g, 3 * w).all()
+
+
+def test_bench_plain_run_has_no_after_legs(monkeypatch):
+    """bench.py without --full times the headline steps and nothing else; --full adds the roofline, extra_configs and
+    cpu_baseline legs, each of which its --no-* switch still drops, and only the roofline runs at N > 1."""
+    import importlib
+    monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))   # bench sets it on import
+    monkeypatch.syspath_prepend(ROOT)
+    bench = importlib.import_module("bench")
+    legs = lambda *argv, world=1: bench.after_legs(bench.parse_args(list(argv)), world)
+    everything = {"roofline", "extra_configs", "cpu_baseline"}
+    assert legs() == set() and legs("--steps", "5", "--warmup", "2", "--dump-outputs", "d") == set()
+    assert legs("--gpus", "8", world=8) == set() and legs("--precision", "fp8") == set()
+    assert legs("--full") == everything
+    assert legs("--full", "--no-extra") == {"roofline", "cpu_baseline"}
+    assert legs("--full", "--no-cpu-baseline", "--no-kernel-timing") == {"extra_configs"}
+    assert legs("--full", "--precision", "fp8") == {"roofline", "cpu_baseline"}
+    assert legs("--full", "--gpus", "8", world=8) == {"roofline"}

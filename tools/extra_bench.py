@@ -1,4 +1,4 @@
-"""one extra_configs line of bench.py on its own:  python tools/extra_bench.py gpt2_medium 8 fp8 [steps] [warmup]"""
+"""one extra_configs line of bench.py --full on its own:  python tools/extra_bench.py gpt2_medium 8 fp8 [steps] [warmup]"""
 import json
 import os
 import sys
