@@ -8,7 +8,6 @@ int dg_attn_bwd_simple(const void*, const void*, const void*, const float*, void
 int dg_attn_fwd_mfma(const void*, void*, float*, int, int, int, int, float, float, const uint32_t*, uint32_t, void*, const dg_attn_fp8_out*, hipStream_t);
 int dg_attn_bwd_mfma(const void*, const void*, const void*, const float*, void*, float*, void*, int, int, int, int, float, float,
                      const uint32_t*, uint32_t, const void*, const dg_attn_fp8_out*, hipStream_t);
-bool dg_attn_mfma_f8_supported();
 int64_t dg_attn_mfma_keep_bytes(int B, int T, int NH);
 int64_t dg_attn_bwd_mfma_tile_bytes(int B, int T, int NH);
 bool dg_attn_mfma_supported(int B, int T, int NH, int H);
@@ -19,7 +18,7 @@ extern "C" int64_t dg_attn_keep_bits_bytes(int B, int T, int NH, int H, int dtyp
 }
 
 extern "C" int dg_attn_fp8_out_supported(int B, int T, int NH, int H, int dtype) {
-    return (B > 0 && T > 0 && NH > 0 && dtype == DG_BF16 && dg_attn_mfma_supported(B, T, NH, H) && dg_attn_mfma_f8_supported()) ? 1 : 0;
+    return (B > 0 && T > 0 && NH > 0 && dtype == DG_BF16 && dg_attn_mfma_supported(B, T, NH, H)) ? 1 : 0;
 }
 
 extern "C" int dg_attn_fwd_fp8(const void* qkv, void* out, float* lse, int B, int T, int NH, int H,

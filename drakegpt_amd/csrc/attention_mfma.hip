@@ -18,7 +18,6 @@
 // Scores per (b,h): T*(T+1)/2; FLOP per score element: fwd 4*64, bwd 10*64 (+2 recomputed products
 // because dQ and dK/dV are separate deterministic passes: no atomics, bitwise reproducible).
 #include "common.h"
-#include <stdlib.h>
 #include <type_traits>
 
 #define HD 64
@@ -35,15 +34,13 @@ struct AttnP {
     int64_t n_items;
     float scale;
     int drop; float inv_keep; uint32_t thr; const uint32_t* rng; uint32_t site;
-    int balance, rot_div;      // balance: 0 plain, 1 = cost-balanced item order (nblk % 4 == 0); rot_div = #CUs
-    int xcd;                   // 1 = the workgroups of one (batch, head) land on one XCD (balanced order only)
+    int balance, rot_div;      // balance: 0 plain, 1 = equal-cost item order, 2 = heavy first (nblk % 4 == 0; see fill); rot_div = #CUs
     char* tiles;               // optional: [B*NH][nblk(nblk+1)/2] tiles, see attn_bwd_dq_mfma_kernel
     // optional (round 3): the keep decisions of the dropout, left by the forward pass as 16 wave masks (64 bits: one per lane) per
     // 32 x 32 tile -- mask r, lane (c, hh) = element (query q0 + c, key k0 + krow(r, hh)), the layout both the forward kernel and
     // the dQ pass hold a tile in -- so that the dQ pass selects with scalar masks instead of hashing 16 keys per lane again
     unsigned long long* keep;
     unsigned long long* stamps;  // diagnostic (tools/attn_dq_stamps.py): per workgroup 8 words = cycles wave 0 spent in each phase of the dQ tile loop; NULL in production
-    int tiles_mode;            // 1: 4 KB tiles [32 q][P | dS] (LDS-staged); 2: 2 KB tiles, the lanes' 16 signed probabilities as they hold them
     // optional (round 3, precision fp8; the F8 template instances only): the output a second time as fp8 (o: e4m3, dqkv: e5m2; same
     // [rows][columns] as the bf16 tensor, one byte per element) with delayed per-tensor scaling -- see attn_f8_begin
     uint8_t* q8; float* hist3; const uint32_t* step; float* sinv; int only8;      // only8: the bf16 form is not written
@@ -105,8 +102,8 @@ __device__ __forceinline__ float attn_f8_chunk(u32x4 v, float sc, float m, uint8
 __device__ __forceinline__ int64_t attn_keep_index(const AttnP& p, int64_t bh, int qb, int kb) {       // in 128-byte records
     return bh * (p.nblk * (p.nblk + 1) / 2) + qb * (qb + 1) / 2 + kb;
 }
-__device__ __forceinline__ int64_t attn_tile_index(const AttnP& p, int64_t bh, int qb, int kb) {
-    return (bh * (p.nblk * (p.nblk + 1) / 2) + qb * (qb + 1) / 2 + kb) * (p.tiles_mode == 2 ? 2048 : 4096);
+__device__ __forceinline__ int64_t attn_tile_index(const AttnP& p, int64_t bh, int qb, int kb) {      // in bytes: [32 q][P | dS] bf16
+    return (bh * (p.nblk * (p.nblk + 1) / 2) + qb * (qb + 1) / 2 + kb) * 4096;
 }
 
 // Which 32-row block does this wave work on?  A causal block b costs b+1 tile iterations (nblk-b for the dK/dV
@@ -140,7 +137,7 @@ __device__ __forceinline__ void attn_item(const AttnP& p, int wave, int64_t& bh,
     // Workgroups are dealt to the 8 XCDs round-robin (blockIdx % 8, a speed assumption only), each with its own L2.  The
     // remap gives XCD k a contiguous range of (batch, head) pairs, so the wpq workgroups of one pair share K / V (Q / dO
     // in the dK/dV pass) through one L2 instead of fetching them wpq times: backward 62.6 -> 58.4 us per layer.
-    const int wg = p.xcd ? dg_xcd_remap((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
+    const int wg = dg_xcd_remap((int)blockIdx.x, (int)gridDim.x);
     const int g = wg % wpq;
     bh = wg / wpq;
     valid = bh < (int64_t)p.B * p.NH;
@@ -404,178 +401,10 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_mfma_kernel(AttnP p) {
 }
 
 // =============================================================================================
-// Forward, shared-tile form (T % 128 == 0, the balanced item order): the four waves of a workgroup own four query blocks of ONE
-// (batch, head), so they all walk the same key tiles -- in the kernel above every wave stages its own copy in private LDS and
-// runs its own dependent chain of up to nblk 32-key tiles: the launch takes as long as the longest wave (8 tiles x ~2 500 cycles
-// at T = 256) while the SIMDs are busy a third of that time.  Here
-//   * a key tile is 64 keys, loaded ONCE per workgroup (each wave fetches a quarter: 16 registers of prefetch instead of 32)
-//     into double-buffered shared LDS: one workgroup barrier per 64 keys, no second one (buffer i is refilled two barriers on);
-//   * a wave computes BOTH 32-key halves of the tile together: two independent score chains (8 MFMAs), one running-max / rescale
-//     step per 64 keys instead of two, then 8 MFMAs into O -- half as many dependent iterations, twice the work in flight;
-//   * waves whose query block is finished keep loading and keep the barriers (wave-uniform branches only).
-// Same arithmetic per element as attn_fwd_mfma_kernel (scores, exp2, keep hash, bf16 P), only the order of the running-max
-// updates differs (per 64 keys): results agree to fp32 rounding of the rescale factors.
-// MEASURED (round 2, one box, DG_ATTN_SHARED=1 vs 0): T = 256 (B 64, 6 heads): 24.9 us vs 19.9 us with dropout, 17.4 vs 15.2
-// without; T = 1024 (B 8, 12 heads): 68.7 vs 59.3 / 38.6 vs 39.7.  SLOWER: a wave's time is its own instruction stream (about
-// 100 VALU instructions per 32 keys, 56 of them the keep hash, issued in order at 4 cycles each), which "two tiles in flight"
-// does not shorten -- it only removes latency gaps, and those the two other waves of the SIMD already fill -- while the
-// workgroup barrier ties every wave to the slowest one of each step.  What is left for this kernel is fewer instructions per
-// score (the hash), not more overlap.  Kept as an A/B variant; the default stays the per-wave form.
-#define FWD2_BUF 16384                       // per buffer: K row image [64][128 B] + V transposed-read image [64][128 B]
-template <bool DROP>
-__global__ __launch_bounds__(256, 3) void attn_fwd_mfma2_kernel(AttnP p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];           // 2 x FWD2_BUF
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    int64_t bh; int blk; bool valid;
-    attn_item(p, wave, bh, blk, valid);
-    if (!valid) return;                                                   // (uniform per workgroup: all four waves share bh)
-    const int qb = blk;                                                   // balanced order only
-    int n_it = 0;                                                         // 64-key steps of the workgroup's longest wave
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        int64_t b2; int k2; bool v2;
-        attn_item(p, w, b2, k2, v2);
-        n_it = max(n_it, (k2 + 2) >> 1);
-    }
-    const int my_it = (qb + 2) >> 1;
-    const int h = (int)(bh % p.NH), b = (int)(bh / p.NH);
-    const int T = p.T, C = p.NH * HD;
-    const int64_t ld = 3 * (int64_t)C;
-    const bf16_t* Qb = p.qkv + (int64_t)b * T * ld + h * HD;
-    const bf16_t* Kb = Qb + C;
-    const bf16_t* Vb = Qb + 2 * C;
-    const int q0 = qb * TILE, c = lane & 31, hh = lane >> 5;
-    const int qi = q0 + c;
-
-    bf16x8 qf[4];
-    frags_global(qf, Qb, ld, q0, T, lane);
-    f32x16 O[2];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { O[0][i] = 0.f; O[1][i] = 0.f; }
-    float m = -INFINITY, lsum = 0.f;
-    const float sc = p.scale * LOG2E;
-    const uint32_t key = DROP ? dg_site_key_dev(p.rng, p.site) : 0u;
-    const uint32_t wbase = (((uint32_t)(((uint64_t)bh * T + qi) * (uint64_t)T) + 4u * hh) >> 1) * DG_WEYL;
-
-    // cooperative loads: a [64 keys][64 d] tile is 512 chunks of 16 B per operand, two per thread
-    u32x4 rk[2], rv[2];
-    const int tid = threadIdx.x;
-    auto load2 = [&](int it) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int cc = tid + 256 * i, row = cc >> 3, ch = cc & 7;
-            int gr = it * 64 + row; gr = gr < T ? gr : T - 1;
-            rk[i] = *(const u32x4*)(Kb + row_off(gr, ld) + ch * 8);
-            rv[i] = *(const u32x4*)(Vb + row_off(gr, ld) + ch * 8);
-        }
-    };
-    auto store2 = [&](char* buf) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int cc = tid + 256 * i, row = cc >> 3, ch = cc & 7;
-            *(u32x4*)(buf + off_row(row, ch)) = rk[i];
-            *(u32x4*)(buf + 8192 + off_tr(row, ch)) = rv[i];
-        }
-    };
-    // MODE 0: both halves unmasked; 1: first half unmasked, second half on the diagonal (odd query block); 2: first half on the
-    // diagonal, second half entirely in the future = skipped (even query block)
-    auto step = [&](auto mode_tag, int it, const char* buf) {
-        constexpr int MODE = decltype(mode_tag)::value;
-        const char* imgK = buf;
-        const char* imgV = buf + 8192;
-        f32x16 Sa, Sb;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { Sa[i] = 0.f; Sb[i] = 0.f; }
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            Sa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_row(imgK, ks, lane), qf[ks], Sa, 0, 0, 0);
-            if (MODE != 2) Sb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_row(imgK + 4096, ks, lane), qf[ks], Sb, 0, 0, 0);
-        }
-        const int k0 = it * 64;
-        const uint32_t wta = wbase + (uint32_t)(k0 >> 1) * DG_WEYL, wtb = wta + 16u * DG_WEYL;
-        float mx = -INFINITY;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            float sa = Sa[r] * sc;
-            if (MODE == 2 && k0 + krow(r, hh) > qi) sa = -INFINITY;
-            Sa[r] = sa;
-            mx = fmaxf(mx, sa);
-            if (MODE != 2) {
-                float sb = Sb[r] * sc;
-                if (MODE == 1 && k0 + 32 + krow(r, hh) > qi) sb = -INFINITY;
-                Sb[r] = sb;
-                mx = fmaxf(mx, sb);
-            }
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float mn = fmaxf(m, mx);
-        const float alpha = __builtin_amdgcn_exp2f(m - mn);
-        m = mn;
-        float ps = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-            const uint32_t wo = (uint32_t)(((r & 3) >> 1) + 4 * (r >> 2)) * DG_WEYL;
-            float e0 = __builtin_amdgcn_exp2f(Sa[r] - mn), e1 = __builtin_amdgcn_exp2f(Sa[r + 1] - mn);
-            ps += e0 + e1;
-            if (DROP) {
-                const uint32_t x = dg_hash_w(key, wta + wo);
-                e0 = dg_keep_lo(x, p.thr) ? e0 * p.inv_keep : 0.f;
-                e1 = dg_keep_hi(x, p.thr) ? e1 * p.inv_keep : 0.f;
-            }
-            Sa[r] = e0; Sa[r + 1] = e1;
-            if (MODE != 2) {
-                float f0 = __builtin_amdgcn_exp2f(Sb[r] - mn), f1 = __builtin_amdgcn_exp2f(Sb[r + 1] - mn);
-                ps += f0 + f1;
-                if (DROP) {
-                    const uint32_t x = dg_hash_w(key, wtb + wo);
-                    f0 = dg_keep_lo(x, p.thr) ? f0 * p.inv_keep : 0.f;
-                    f1 = dg_keep_hi(x, p.thr) ? f1 * p.inv_keep : 0.f;
-                }
-                Sb[r] = f0; Sb[r + 1] = f1;
-            }
-        }
-        lsum = lsum * alpha + ps;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { O[0][i] *= alpha; O[1][i] *= alpha; }
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-            const bf16x8 pa = pack8(Sa, s2);
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-                O[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr(imgV, dt, s2, lane), pa, O[dt], 0, 0, 0);
-            if (MODE != 2) {
-                const bf16x8 pb = pack8(Sb, s2);
-#pragma unroll
-                for (int dt = 0; dt < 2; ++dt)
-                    O[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr(imgV + 4096, dt, s2, lane), pb, O[dt], 0, 0, 0);
-            }
-        }
-    };
-    load2(0);
-    for (int it = 0; it < n_it; ++it) {
-        char* buf = smem + (it & 1) * FWD2_BUF;
-        store2(buf);
-        if (it + 1 < n_it) load2(it + 1);
-        __syncthreads();                       // tile `it` is complete; the other buffer is not touched before the next barrier
-        if (it < my_it) {
-            if (it + 1 < my_it) step(std::integral_constant<int, 0>{}, it, buf);
-            else if (qb & 1) step(std::integral_constant<int, 1>{}, it, buf);
-            else step(std::integral_constant<int, 2>{}, it, buf);
-        }
-    }
-    lsum += __shfl_xor(lsum, 32, 64);
-    if (hh == 0 && qi < T) p.lse[bh * T + qi] = (m + log2f(lsum)) * (1.f / LOG2E);
-    __syncthreads();                           // every wave is done with the shared tiles: reuse them as private staging
-    store_T_acc(smem + wave * 4096, O, 1.f / lsum, p.out_w + (int64_t)b * T * C + h * HD, C, q0, T, lane);
-}
-
-// =============================================================================================
 // dQ: wave = 32 queries; per key tile: S^T = K Q^T, dP^T = V dO^T, dQ^T += K^T dS^T
 #define WAVE_LDS_DQ 13312     // K row image, K transposed-read image, V row image (4 KB each) + 1 KB: the first Q fragment, parked
-// Without dropout the compiler wants 208 registers for this loop (everything of a tile in flight at once); capped at 168 (three
-// workgroups per CU) it spilled 39 of them inside the loop: 56.6 us per layer against 36.4 us WITH dropout, which made a
-// dropout-0 step slower than a dropout-0.2 step.  The no-dropout variant therefore takes two workgroups per CU and no spills.
-// TM: what the pass leaves behind for the dK/dV pass -- 0 nothing, 1 the [32 q][P | dS] tiles, 2 the signed probabilities only
+// The dropout code always runs: without dropout the host passes a threshold of 0 (dg_attn_bwd_mfma).
+// TILES: the pass also leaves the [32 q][P | dS] tiles for the dK/dV pass
 // KB: the keep decisions come as wave masks from the forward pass (AttnP::keep) instead of being hashed again
 // F8: dQ also as e5m2 into the fp8 copy of dqkv (AttnP::q8 ...; the dK/dV pass adds its two thirds under the same history)
 // SH (round 3; the balanced block orders, where a workgroup's four query blocks belong to one (batch, head)): the K / V tiles are
@@ -583,8 +412,8 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_mfma2_kernel(AttnP p) {
 // workgroup barrier per key tile, as in attn_bwd_dkv_tiles_shared_kernel; the loop runs to the workgroup's LAST query block and a
 // wave whose own block is finished only helps loading.  The P | dS staging area and the parked Q fragment stay private.
 #define WG_LDS_DQS (4 * 5120 + 2 * 12288)
-template <bool DROP, int TM, bool KB = false, bool F8 = false, bool SH = false>      // dropout on the probabilities (compile-time: no per-element uniform branch)
-__global__ __launch_bounds__(256, DROP ? 3 : 2) void attn_bwd_dq_mfma_kernel(AttnP p) {
+template <bool TILES, bool KB = false, bool F8 = false, bool SH = false>
+__global__ __launch_bounds__(256, 3) void attn_bwd_dq_mfma_kernel(AttnP p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform: block, pointers and loop bounds live in SGPRs
     int64_t bh; int blk; bool valid;
@@ -643,7 +472,7 @@ __global__ __launch_bounds__(256, DROP ? 3 : 2) void attn_bwd_dq_mfma_kernel(Att
 #pragma unroll
     for (int i = 0; i < 16; ++i) { dQ[0][i] = 0.f; dQ[1][i] = 0.f; }
     const float sc = p.scale * LOG2E;
-    const uint32_t key = DROP ? dg_site_key_dev(p.rng, p.site) : 0u;
+    const uint32_t key = dg_site_key_dev(p.rng, p.site);
     const uint32_t wbase = (((uint32_t)(((uint64_t)bh * T + qi) * (uint64_t)T) + 4u * hh) >> 1) * DG_WEYL;      // pair of (qi, key 4 hh)
     const uint32_t zs = p.thr >> 16;               // thr <= 0xFFFF: always 0, but not to the compiler (see the hash below)
 
@@ -727,11 +556,9 @@ __global__ __launch_bounds__(256, DROP ? 3 : 2) void attn_bwd_dq_mfma_kernel(Att
         // [32 queries][P: 32 keys | dS: 32 keys] bf16 image, for attn_bwd_dkv_tiles_kernel: the dK/dV pass then needs no
         // score recomputation at all.  Staged through the V image (its MFMAs are done) so that the store is four full
         // 1 KB rows per instruction.
-        constexpr bool emit = TM == 1, emit2 = TM == 2;
         if (KB) asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(mkA), "+s"(mkB));
         int qlim = kt == qb ? qi : 0x7fffffff;
         asm volatile("" : "+v"(qlim));                             // (opaque: one loop body for interior and diagonal tiles, no peeled copy)
-        bf16x8 p2[2];                                              // (tiles_mode 2) this lane's 16 signed probabilities
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             bf16x4 pv, dv;
@@ -745,10 +572,10 @@ __global__ __launch_bounds__(256, DROP ? 3 : 2) void attn_bwd_dq_mfma_kernel(Att
 #pragma unroll
                 for (int jj = 0; jj < 2; ++jj) {
                     const int j = jp + jj, r = 4 * g + j;
-                    if (DROP && KB) {
+                    if (KB) {
                         const uint32_t mlo = r < 8 ? mkA[2 * (r & 7)] : mkB[2 * (r & 7)], mhi = r < 8 ? mkA[2 * (r & 7) + 1] : mkB[2 * (r & 7) + 1];
                         kf2[jj] = __builtin_amdgcn_inverse_ballot_w64(((unsigned long long)mhi << 32) | mlo) ? p.inv_keep : 0.f;
-                    } else if (DROP) {
+                    } else {
                         // Keys j, j + 1 of this run read the two fields of one hash word, but the word is hashed again for
                         // each: holding it across the pair costs this kernel 43 spilled registers (measured, +3 us per
                         // layer), so the pair saving is taken in the forward kernels only.  `zs` (a run-time zero) on
@@ -768,14 +595,8 @@ __global__ __launch_bounds__(256, DROP ? 3 : 2) void attn_bwd_dq_mfma_kernel(Att
                 S[r0] = ds2[0]; S[r0 + 1] = ds2[1];
                 pv[jp] = (bf16_t)pk2[0]; pv[jp + 1] = (bf16_t)pk2[1];
                 dv[jp] = (bf16_t)ds2[0]; dv[jp + 1] = (bf16_t)ds2[1];
-                // tiles_mode 2: only the probability travels, its sign bit says "dropped" (P >= 0 always); the dK/dV pass
-                // recomputes dP = dO V^T with four MFMAs and dS from it -- half the tile bytes, no LDS staging here
-                if (emit2) {
-                    p2[g >> 1][4 * (g & 1) + jp] = (bf16_t)(kf2[0] != 0.f ? pr2[0] : -pr2[0]);
-                    p2[g >> 1][4 * (g & 1) + jp + 1] = (bf16_t)(kf2[1] != 0.f ? pr2[1] : -pr2[1]);
-                }
             }
-            if (emit) {
+            if (TILES) {
                 // row = lane: the 16-byte chunk index is XOR-ed with the row so that the 32 lanes of a row-per-lane write do
                 // not all land on the same two banks (unswizzled this was 3.5 conflict cycles per LDS cycle in the PMC pass)
                 *(bf16x4*)(imgE + c * 128 + ((g ^ (c & 7)) << 4) + 8 * hh) = pv;
@@ -786,7 +607,7 @@ __global__ __launch_bounds__(256, DROP ? 3 : 2) void attn_bwd_dq_mfma_kernel(Att
             if (KB) __builtin_amdgcn_sched_barrier(0);
         }
         stamp(2);
-        if (emit) {
+        if (TILES) {
             __builtin_amdgcn_wave_barrier();
             char* tb = p.tiles + attn_tile_index(p, bh, qb, kt);
 #pragma unroll
@@ -794,11 +615,6 @@ __global__ __launch_bounds__(256, DROP ? 3 : 2) void attn_bwd_dq_mfma_kernel(Att
                 const int cc = ln + 64 * i, row = cc >> 3, ch = cc & 7;
                 *(u32x4*)(tb + cc * 16) = *(const u32x4*)(imgE + row * 128 + ((ch ^ (row & 7)) << 4));
             }
-        }
-        if (emit2) {
-            char* tb = p.tiles + attn_tile_index(p, bh, qb, kt) + ln * 32;      // 64 lanes x 32 B, contiguous
-            *(bf16x8*)tb = p2[0];
-            *(bf16x8*)(tb + 16) = p2[1];
         }
         stamp(3);
 #pragma unroll
@@ -1117,118 +933,6 @@ __device__ __forceinline__ void attn_bwd_dkv_tiles_shared_body(const AttnP& p) {
 __global__ __launch_bounds__(256, 3) void attn_bwd_dkv_tiles_shared_kernel(AttnP p) { attn_bwd_dkv_tiles_shared_body<false>(p); }
 __global__ __launch_bounds__(256, 3) void attn_bwd_dkv_tiles_shared_f8_kernel(AttnP p) { attn_bwd_dkv_tiles_shared_body<true>(p); }
 
-// =============================================================================================
-// dK/dV from the SIGNED-PROBABILITY tiles of the dQ pass (tiles_mode 2): per 32 x 32 tile the dQ pass leaves 2 KB -- every lane's 16
-// probabilities exactly as it holds them (lane = query, registers = keys), negative where the element was dropped -- instead of
-// 4 KB of P | dS staged through its LDS.  This pass (HBM-bound: 119 MB per launch at the scaled configuration with the 4 KB
-// tiles) turns a tile around in its own LDS ([32 q] rows of 80 B: the two half-waves of a column read hit disjoint banks),
-// recomputes dP = dO V^T with four MFMAs (V of its key block stays in registers; dO row fragments are read from the
-// transposed-read image) and dS = P (dP keep/(1-p) - delta) in registers, where they already are the A operands of
-// dV += Pd^T dO and dK += dS^T Q.  No exp, no hash, no scores.
-// MEASURED (round 2, one box, DG_ATTN_TILES=2 vs 1): backward pair 62.8 us vs 52.3 us per layer at T = 256, 180 vs 166 us at
-// T = 1024 -- SLOWER although it moves 55 MB less per layer: like the other attention kernels this pass is as long as its
-// longest wave's instruction stream (the key block that sees all 8 query tiles), and 16 two-byte LDS reads + ~100 VALU
-// instructions + 4 MFMAs per tile lengthen that stream more than the halved tile traffic shortens anything.  (The dQ side
-// does get leaner: no LDS staging, 0 spilled registers instead of 4.)  Kept as an A/B variant.
-#define WAVE_LDS_DKVP 10752                  // 2560 (P image) + 4096 (Q^T image) + 4096 (dO^T image)
-__global__ __launch_bounds__(256, 3) void attn_bwd_dkv_ptiles_kernel(AttnP p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    int64_t bh; int blk; bool valid;
-    attn_item(p, wave, bh, blk, valid);
-    if (!valid) return;
-    char* imgP = smem + wave * WAVE_LDS_DKVP;       // [32 q][80 B]: 32 keys of bf16 + padding
-    char* imgQt = imgP + 2560;
-    char* imgGt = imgQt + 4096;
-    const int kb = p.balance ? p.nblk - 1 - blk : blk;
-    const int h = (int)(bh % p.NH), b = (int)(bh / p.NH);
-    const int T = p.T, C = p.NH * HD;
-    const int64_t ld = 3 * (int64_t)C;
-    const bf16_t* Qb = p.qkv + (int64_t)b * T * ld + h * HD;
-    const bf16_t* Vb = Qb + 2 * C;
-    const bf16_t* dOb = p.dout + (int64_t)b * T * C + h * HD;
-    const int k0 = kb * TILE, c = lane & 31, hh = lane >> 5;
-    bf16x8 vf[4];
-    frags_global(vf, Vb, ld, k0, T, lane);
-    f32x16 dK[2], dV[2];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { dK[0][i] = 0.f; dK[1][i] = 0.f; dV[0][i] = 0.f; dV[1][i] = 0.f; }
-    const float* dlt = p.delta_r + bh * T;
-    const bool vec4 = (T % 4 == 0) && ((((uintptr_t)p.delta_r) & 15) == 0);
-    const float ik = p.drop ? p.inv_keep : 1.f;
-    auto load_pt = [&](u32x4 (&r)[2], int qt) {
-        const char* tb = p.tiles + attn_tile_index(p, bh, qt, kb) + lane * 32;
-        r[0] = *(const u32x4*)tb; r[1] = *(const u32x4*)(tb + 16);
-    };
-    u32x4 rp[2], rq[4], rg[4];
-    load_pt(rp, kb);
-    tile_load(rq, Qb, ld, k0, T, lane);
-    tile_load(rg, dOb, C, k0, T, lane);
-    for (int qt = kb; qt < p.nblk; ++qt) {
-        // the producer's lane (query c, half hh) held keys krow(r, hh): four runs of four consecutive keys (8 bytes each)
-        {
-            const bf16x8 a = __builtin_bit_cast(bf16x8, rp[0]), bq = __builtin_bit_cast(bf16x8, rp[1]);
-            char* row = imgP + c * 80 + 8 * hh;
-            *(bf16x4*)(row) = __builtin_shufflevector(a, a, 0, 1, 2, 3);            // keys 4 hh + 0..3
-            *(bf16x4*)(row + 16) = __builtin_shufflevector(a, a, 4, 5, 6, 7);       // keys 8 + 4 hh ..
-            *(bf16x4*)(row + 32) = __builtin_shufflevector(bq, bq, 0, 1, 2, 3);     // keys 16 + 4 hh ..
-            *(bf16x4*)(row + 48) = __builtin_shufflevector(bq, bq, 4, 5, 6, 7);     // keys 24 + 4 hh ..
-        }
-        tile_store<true>(imgQt, rq, lane);
-        tile_store<true>(imgGt, rg, lane);
-        if (qt + 1 < p.nblk) {
-            load_pt(rp, qt + 1);
-            tile_load(rq, Qb, ld, (qt + 1) * TILE, T, lane);
-            tile_load(rg, dOb, C, (qt + 1) * TILE, T, lane);
-        }
-        __builtin_amdgcn_wave_barrier();
-        // dP[q, key] = sum_d dO[q, d] V[key, d]: rows q on the registers, key on the lane -- the layout the products below take
-        f32x16 dP;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) dP[i] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            const bf16x8 go = __builtin_bit_cast(bf16x8, *(const u32x4*)(imgGt + off_tr(lane & 31, 2 * ks + (lane >> 5))));   // row fragment of dO
-            dP = __builtin_amdgcn_mfma_f32_32x32x16_bf16(go, vf[ks], dP, 0, 0, 0);
-        }
-        const int q0 = qt * TILE;
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            bf16x8 pf, df;
-#pragma unroll
-            for (int g2 = 0; g2 < 2; ++g2) {
-                const int g = 2 * s + g2;
-                const int qr = q0 + 8 * g + 4 * hh;                 // rows qr .. qr + 3 = registers 4 g .. 4 g + 3
-                f32x4 D4;
-                if (vec4) { const int qc = qr + 3 < T ? qr : T - 4; D4 = *(const f32x4*)(dlt + qc); }
-                else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { const int qc = qr + j < T ? qr + j : T - 1; D4[j] = dlt[qc]; }
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int r = 4 * g + j;
-                    const float ps = (float)*(const bf16_t*)(imgP + (8 * g + 4 * hh + j) * 80 + 2 * c);   // P[q = krow(r, hh)][key c], signed
-                    const float pr = fabsf(ps);
-                    const float kf = (__float_as_uint(ps) >> 31) ? 0.f : ik;
-                    pf[4 * g2 + j] = (bf16_t)(pr * kf);
-                    df[4 * g2 + j] = (bf16_t)(pr * (dP[r] * kf - D4[j]));
-                }
-            }
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt) {
-                dV[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pf, frag_tr(imgGt, dt, s, lane), dV[dt], 0, 0, 0);
-                dK[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(df, frag_tr(imgQt, dt, s, lane), dK[dt], 0, 0, 0);
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-    bf16_t* dKb = p.dqkv + (int64_t)b * T * ld + C + h * HD;
-    store_N_acc(imgQt, dK, p.scale, dKb, ld, k0, T, lane);
-    __builtin_amdgcn_wave_barrier();
-    store_N_acc(imgQt, dV, 1.f, dKb + C, ld, k0, T, lane);
-}
-
 static unsigned long long* g_attn_stamps = nullptr;
 // diagnostic only (tools/attn_dq_stamps.py): not part of the public header
 extern "C" void dg_debug_set_attn_stamps(void* q) { g_attn_stamps = (unsigned long long*)q; }
@@ -1242,52 +946,24 @@ static void fill(AttnP& p, int B, int T, int NH, float scale, float dp, const ui
     p.inv_keep = 1.f / (1.f - dp);
     p.thr = dg_drop_threshold(dp);
     p.rng = rng; p.site = site;
-    static const int mode = [] { const char* e = getenv("DG_ATTN_BALANCE"); return e ? atoi(e) : 2; }();   // 0 = plain order, 1 = equal-cost workgroups always, 2 (default) = equal-cost for one residency, heavy first beyond
     static const int ncu = [] {
         int dev = 0, n = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
         return n;
     }();
-    p.balance = (mode != 0 && p.nblk % 4 == 0) ? 1 : 0;
-    // heavy-first order when the launch is more than one residency (three 256-thread workgroups per CU); DG_ATTN_BALANCE=1 keeps the
-    // equal-cost order everywhere (A/B)
+    p.balance = p.nblk % 4 == 0 ? 1 : 0;
+    // heavy-first order when the launch is more than one residency (three 256-thread workgroups per CU)
     // ... and from 16 blocks on (T >= 512) at any size: with the K / V and Q / dO tiles shared by a workgroup's waves (round 3) the
     // consecutive blocks of this order beat the equal-cost pairs at one residency too (GPT-2-small B = 8: 11.75 / 11.65 -> 11.66 /
-    // 11.56 ms; no difference at the headline shape's 8 blocks).  (mode 3: heavy first always -- A/B)
-    if (p.balance && mode != 1 && ((int64_t)B * NH * (p.nblk / 4) > (int64_t)3 * ncu * 11 / 10 || p.nblk >= 16 || mode == 3)) p.balance = 2;
+    // 11.56 ms; no difference at the headline shape's 8 blocks)
+    if (p.balance && ((int64_t)B * NH * (p.nblk / 4) > (int64_t)3 * ncu * 11 / 10 || p.nblk >= 16)) p.balance = 2;
     p.rot_div = ncu;
-    static const int xcd = [] { const char* e = getenv("DG_ATTN_XCD"); return e ? atoi(e) : 1; }();   // 0 = plain blockIdx order (A/B runs)
-    p.xcd = xcd;
 }
 
 int64_t dg_attn_mfma_keep_bytes(int B, int T, int NH) {
     const int64_t nblk = (T + TILE - 1) / TILE;
     return (int64_t)B * NH * (nblk * (nblk + 1) / 2) * 128;
 }
-
-// the dK/dV tile pass with shared Q / dO tiles: the balanced block orders (a workgroup = four key blocks of ONE (batch, head)); DG_ATTN_DKV_SHARED=0 = the per-wave form (A/B)
-static bool attn_dkv_shared(const AttnP& p) {
-    static const int mode = [] { const char* e = getenv("DG_ATTN_DKV_SHARED"); return e ? atoi(e) : 1; }();
-    return mode != 0 && p.balance != 0;
-}
-// the dQ pass with shared K / V tiles: the heavy-first order only, where a workgroup's four query blocks are CONSECUTIVE (the shared
-// loop runs to the last of them: three idle tiles at most).  In the equal-cost order (blocks j and nblk - 1 - j in one workgroup) the
-// short waves would sit at the barriers of the long ones: measured slower at the headline shape (2.326 / 2.336 -> 2.344 / 2.342 ms) and
-// no better at GPT-2-small B = 8.  DG_ATTN_DQ_SHARED=0 = the per-wave form everywhere, 2 = shared in both balanced orders (A/B).
-static bool attn_dq_shared(const AttnP& p) {
-    static const int mode = [] { const char* e = getenv("DG_ATTN_DQ_SHARED"); return e ? atoi(e) : 1; }();
-    return mode == 2 ? p.balance != 0 : (mode != 0 && p.balance == 2);
-}
-static int attn_tile_mode() {
-    static const int tile_mode = [] { const char* e = getenv("DG_ATTN_TILES"); return e ? atoi(e) : 1; }();   // 1 = P | dS tiles (default), 2 = signed P tiles (measured slower), 0 = recompute in the dK/dV pass
-    return tile_mode;
-}
-static int attn_shared_mode() {
-    static const int shared_mode = [] { const char* e = getenv("DG_ATTN_SHARED"); return e ? atoi(e) : 0; }();   // 1 = shared 64-key tiles (measured slower, see attn_fwd_mfma2_kernel)
-    return shared_mode;
-}
-// can the kernels leave their outputs as fp8 too (DgAttnF8)?  The default kernel forms only.
-bool dg_attn_mfma_f8_supported() { return attn_tile_mode() == 1 && !attn_shared_mode(); }
 
 static int attn_f8_fill(AttnP& p, const dg_attn_fp8_out* f8) {
     if (!f8->q8 || !f8->hist3 || !f8->step_state || !f8->scale_inv || !dg_aligned16(f8->q8) || !dg_aligned16(f8->hist3)) return DG_ERR_ARG;
@@ -1303,19 +979,12 @@ int dg_attn_fwd_mfma(const void* qkv, void* out, float* lse, int B, int T, int N
     p.qkv = (const bf16_t*)qkv; p.out_w = (bf16_t*)out; p.lse = lse;
     p.keep = (unsigned long long*)keep;
     dim3 grid((unsigned)((p.n_items + 3) / 4)), block(256);
-    const int shared_mode = attn_shared_mode();
     if (f8) {
-        if (!dg_attn_mfma_f8_supported() || (p.drop && !p.keep)) return DG_ERR_ARG;
+        if (p.drop && !p.keep) return DG_ERR_ARG;
         if (int rc = attn_f8_fill(p, f8)) return rc;
         if (p.only8) return DG_ERR_ARG;                   // (the dQ pass reads the bf16 output: delta = rowsum(dO o))
         if (p.drop) hipLaunchKernelGGL((attn_fwd_mfma_kernel<true, true, true>), grid, block, 4 * WAVE_LDS_FWD, s, p);
         else hipLaunchKernelGGL((attn_fwd_mfma_kernel<false, false, true>), grid, block, 4 * WAVE_LDS_FWD, s, p);
-        DG_LAUNCH_CHECK();
-        return DG_OK;
-    }
-    if (shared_mode && p.balance && T % 64 == 0 && !keep) {      // balance: nblk % 4 == 0, i.e. T % 128 == 0 (whole 64-key tiles)
-        if (p.drop) hipLaunchKernelGGL(attn_fwd_mfma2_kernel<true>, grid, block, 2 * FWD2_BUF, s, p);
-        else hipLaunchKernelGGL(attn_fwd_mfma2_kernel<false>, grid, block, 2 * FWD2_BUF, s, p);
         DG_LAUNCH_CHECK();
         return DG_OK;
     }
@@ -1332,6 +1001,16 @@ int64_t dg_attn_bwd_mfma_tile_bytes(int B, int T, int NH) {
     return (int64_t)B * NH * (nblk * (nblk + 1) / 2) * 4096;
 }
 
+// The dQ pass with shared K / V tiles: the heavy-first order only, where a workgroup's four query blocks are CONSECUTIVE (the shared
+// loop runs to the last of them: three idle tiles at most).  In the equal-cost order (blocks j and nblk - 1 - j in one workgroup) the
+// short waves would sit at the barriers of the long ones: measured slower at the headline shape (2.326 / 2.336 -> 2.344 / 2.342 ms) and
+// no better at GPT-2-small B = 8.  The recompute form (no tiles) has the per-wave form only.
+template <bool TILES, bool KB, bool F8>
+static void attn_dq_launch(const AttnP& p, dim3 grid, hipStream_t s) {
+    if (TILES && p.balance == 2) hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<true, KB, F8, true>), grid, dim3(256), WG_LDS_DQS, s, p);
+    else hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<TILES, KB, F8>), grid, dim3(256), 4 * WAVE_LDS_DQ, s, p);
+}
+
 int dg_attn_bwd_mfma(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* delta, void* tiles,
                      int B, int T, int NH, int H, float scale, float dp, const uint32_t* rng, uint32_t site, const void* keep,
                      const dg_attn_fp8_out* f8, hipStream_t s) {
@@ -1342,64 +1021,31 @@ int dg_attn_bwd_mfma(const void* qkv, const void* out, const void* dout, const f
     fill(p, B, T, NH, scale, dp, rng, site);
     p.qkv = (const bf16_t*)qkv; p.out = (const bf16_t*)out; p.dout = (const bf16_t*)dout; p.dqkv = (bf16_t*)dqkv;
     p.lse_r = lse; p.delta = delta; p.delta_r = delta;
-    const int tile_mode = attn_tile_mode();
-    p.tiles = tile_mode ? (char*)tiles : nullptr;
-    p.tiles_mode = tile_mode == 1 ? 1 : 2;
-    // keep masks from the forward pass: the default tile form (DG_ATTN_TILES=1) only; DG_ATTN_KEEPBITS=0 ignores them (A/B runs)
-    static const int keep_mode = [] { const char* e = getenv("DG_ATTN_KEEPBITS"); return e ? atoi(e) : 1; }();
-    p.keep = (keep_mode && keep && dp > 0.f && rng) ? (unsigned long long*)keep : nullptr;
-    dim3 grid((unsigned)((p.n_items + 3) / 4)), block(256);
-    // Without dropout the dQ pass still runs the DROP = true code with a threshold of 0 (every hash >= 0: keep everything) and
-    // a keep scale of 1: bit-identical results, and 36 us per layer instead of the 48 us of the DROP = false variant (whose loop
-    // the compiler schedules into 208 registers: 2 workgroups per CU; at 168 registers it spilled: 57 us).  The hash key is
-    // read from any readable device words (the head of qkv): with threshold 0 its value cannot matter.  DG_ATTN_DQ_NODROP=1 restores it.
-    static const int nodrop_variant = [] { const char* e = getenv("DG_ATTN_DQ_NODROP"); return e ? atoi(e) : 0; }();
-    const int tm = p.tiles ? p.tiles_mode : 0;
+    p.tiles = (char*)tiles;
+    // keep masks: the tile form only (the recompute form's dQ loop would spill 16 registers with them; it hashes instead)
+    p.keep = (keep && p.drop && tiles) ? (unsigned long long*)keep : nullptr;
     if (f8) {
         // dqkv also as e5m2: dQ from the dQ pass, dK / dV from the tile pass, one history, one scale
-        if (!dg_attn_mfma_f8_supported() || tm != 1) return DG_ERR_ARG;
+        if (!p.tiles) return DG_ERR_ARG;
         if (int rc = attn_f8_fill(p, f8)) return rc;
-        const bool sh = attn_dq_shared(p);
-        if (p.drop && p.keep) {
-            if (sh) hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<true, 1, true, true, true>), grid, block, WG_LDS_DQS, s, p);
-            else hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<true, 1, true, true>), grid, block, 4 * WAVE_LDS_DQ, s, p);
-        } else {
-            AttnP q = p;
-            if (!p.drop) { q.thr = 0u; q.inv_keep = 1.f; q.rng = (const uint32_t*)qkv; q.site = 0; }     // (as below: the DROP code with a threshold of 0)
-            if (sh) hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<true, 1, false, true, true>), grid, block, WG_LDS_DQS, s, q);
-            else hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<true, 1, false, true>), grid, block, 4 * WAVE_LDS_DQ, s, q);
-        }
-        DG_LAUNCH_CHECK();
-        p.sinv = nullptr;                                 // (written by the dQ pass)
-        if (attn_dkv_shared(p)) hipLaunchKernelGGL(attn_bwd_dkv_tiles_shared_f8_kernel, grid, block, WG_LDS_DKVS, s, p);
-        else hipLaunchKernelGGL(attn_bwd_dkv_tiles_f8_kernel, grid, block, 4 * WAVE_LDS_DKVT, s, p);
-        DG_LAUNCH_CHECK();
-        return DG_OK;
     }
-#define DQ_LAUNCH(DROP_, Q_) do { \
-        if (tm == 2) hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<DROP_, 2>), grid, block, 4 * WAVE_LDS_DQ, s, Q_); \
-        else if (tm == 1) hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<DROP_, 1>), grid, block, 4 * WAVE_LDS_DQ, s, Q_); \
-        else hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<DROP_, 0>), grid, block, 4 * WAVE_LDS_DQ, s, Q_); } while (0)
-    const bool sh = tm == 1 && attn_dq_shared(p);
-    if (p.drop && p.keep && tm == 1) {
-        if (sh) hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<true, 1, true, false, true>), grid, block, WG_LDS_DQS, s, p);
-        else hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<true, 1, true>), grid, block, 4 * WAVE_LDS_DQ, s, p);
-    } else if (p.drop) {
-        if (sh) hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<true, 1, false, false, true>), grid, block, WG_LDS_DQS, s, p);
-        else DQ_LAUNCH(true, p);
-    } else if (nodrop_variant) DQ_LAUNCH(false, p);
-    else {
-        AttnP q = p;
-        q.thr = 0u; q.inv_keep = 1.f; q.rng = (const uint32_t*)qkv; q.site = 0;     // (qkv: at least 384 readable bytes)
-        if (sh) hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<true, 1, false, false, true>), grid, block, WG_LDS_DQS, s, q);
-        else DQ_LAUNCH(true, q);
-    }
-#undef DQ_LAUNCH
+    dim3 grid((unsigned)((p.n_items + 3) / 4)), block(256);
+    // no dropout: threshold 0 (keep all), scale 1: bit-identical, faster than a dropout-free dQ build (36 vs 48 us per layer); key read from qkv (>= 384 B)
+    AttnP q = p;
+    if (!p.drop) { q.thr = 0u; q.inv_keep = 1.f; q.rng = (const uint32_t*)qkv; q.site = 0; }
+    if (!p.tiles) attn_dq_launch<false, false, false>(q, grid, s);
+    else if (!f8) (p.keep ? attn_dq_launch<true, true, false> : attn_dq_launch<true, false, false>)(q, grid, s);
+    else (p.keep ? attn_dq_launch<true, true, true> : attn_dq_launch<true, false, true>)(q, grid, s);
     DG_LAUNCH_CHECK();
-    if (tm == 2) hipLaunchKernelGGL(attn_bwd_dkv_ptiles_kernel, grid, block, 4 * WAVE_LDS_DKVP, s, p);
-    else if (p.tiles && attn_dkv_shared(p)) hipLaunchKernelGGL(attn_bwd_dkv_tiles_shared_kernel, grid, block, WG_LDS_DKVS, s, p);
-    else if (p.tiles) hipLaunchKernelGGL(attn_bwd_dkv_tiles_kernel, grid, block, 4 * WAVE_LDS_DKVT, s, p);
-    else if (p.drop) hipLaunchKernelGGL(attn_bwd_dkv_mfma_kernel<true>, grid, block, 4 * WAVE_LDS_DKV, s, p);
+    p.sinv = nullptr;                                     // (f8: written by the dQ pass)
+    // the tile pass with Q / dO tiles shared by a workgroup's waves: the balanced block orders (a workgroup = four key blocks of ONE (batch, head))
+    if (p.tiles && p.balance) {
+        if (f8) hipLaunchKernelGGL(attn_bwd_dkv_tiles_shared_f8_kernel, grid, block, WG_LDS_DKVS, s, p);
+        else hipLaunchKernelGGL(attn_bwd_dkv_tiles_shared_kernel, grid, block, WG_LDS_DKVS, s, p);
+    } else if (p.tiles) {
+        if (f8) hipLaunchKernelGGL(attn_bwd_dkv_tiles_f8_kernel, grid, block, 4 * WAVE_LDS_DKVT, s, p);
+        else hipLaunchKernelGGL(attn_bwd_dkv_tiles_kernel, grid, block, 4 * WAVE_LDS_DKVT, s, p);
+    } else if (p.drop) hipLaunchKernelGGL(attn_bwd_dkv_mfma_kernel<true>, grid, block, 4 * WAVE_LDS_DKV, s, p);
     else hipLaunchKernelGGL(attn_bwd_dkv_mfma_kernel<false>, grid, block, 4 * WAVE_LDS_DKV, s, p);
     DG_LAUNCH_CHECK();
     return DG_OK;

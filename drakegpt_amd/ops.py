@@ -629,10 +629,13 @@ def attn_fwd(qkv: Tensor, B: int, T: int, NH: int, H: int, scale: float, p: floa
 
 
 def attn_bwd(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, B: int, T: int, NH: int, H: int, scale: float, p: float,
-             rng_state: Optional[Tensor], site: int, keep_bits: Optional[Tensor] = None, fp8_out=None, fp8_out_only: bool = False) -> Tensor:
+             rng_state: Optional[Tensor], site: int, keep_bits: Optional[Tensor] = None, fp8_out=None, fp8_out_only: bool = False, *,
+             tile_scratch: bool = True) -> Tensor:
     """keep_bits: the forward pass's keep masks (attn_fwd(..., keep=True) leaves them as out.dg_keep); default: taken from `out`.
     fp8_out = (hist3, step_state): dqkv also as e5m2 (attribute `dg_fp8` = (e5m2 copy, scale_inv)); fp8_out_only: the bf16 dqkv is
-    not written (marked `dg_unwritten`)."""
+    not written (marked `dg_unwritten`).
+    tile_scratch=False: the workspace holds the delta floats only, and the dK/dV pass recomputes the scores instead of reading the
+    dQ pass's P | dS tiles (the fp8 output needs the tiles)."""
     _chk(qkv, "qkv")
     if keep_bits is None:
         keep_bits = getattr(out, "dg_keep", None)
@@ -642,7 +645,8 @@ def attn_bwd(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, B: int, T: int
     _chk(dout, "dout", qkv.dtype)
     _chk(lse, "lse", torch.float32)
     dqkv = torch.empty_like(qkv)
-    ws = torch.empty(int(lib.dg_attn_bwd_workspace_bytes(B, T, NH, H, dt_code(qkv.dtype))), dtype=torch.uint8, device=qkv.device)
+    nws = lib.dg_attn_bwd_workspace_bytes(B, T, NH, H, dt_code(qkv.dtype)) if tile_scratch else B * NH * T * 4
+    ws = torch.empty(int(nws), dtype=torch.uint8, device=qkv.device)
     if fp8_out is not None:
         import ctypes
         arg, q8, sinv = _attn_fp8_arg(fp8_out, tuple(qkv.shape), torch.float8_e5m2, qkv.device, only8=fp8_out_only)

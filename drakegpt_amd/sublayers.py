@@ -274,14 +274,11 @@ def _ln_fwd(run: Run, x2d: Tensor, ln_w: Tensor, ln_b: Tensor, site: str):
     return h, mean, rstd, None
 
 
-ATTN_FP8_OUT = os.environ.get("DG_FP8_FUSED_ATTN", "1") != "0"     # fp8 training: o / dqkv leave the attention kernels as e4m3 / e5m2 too (A/B: 0 = cast launches)
-
-
 def _attn_fp8_out(run: Run, key: str, t: Optional[Tensor], B: int, T: int, NH: int, H: int, k: int):
     """fp8_out argument of ops.attn_fwd / ops.attn_bwd for call site `key` (training engine, precision fp8, the consumer's
     contraction length k takes the fp8 GEMM): (history, step words) once the history is seeded, else None.  During the engine's
     eager warm-up step (`t` = the tensor the unfused path just produced) the history is seeded with that tensor's maximum."""
-    if not (ATTN_FP8_OUT and run.fp8 and run.fp8_sites is not None and run.step_word is not None and run.act == torch.bfloat16
+    if not (run.fp8 and run.fp8_sites is not None and run.step_word is not None and run.act == torch.bfloat16
             and fp8_k_ok(k) and ops.attn_fp8_out_supported(B, T, NH, H, run.act)):
         return None
     if run.fp8_seed:

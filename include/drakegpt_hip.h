@@ -337,7 +337,7 @@ int dg_attn_bwd(const void* qkv, const void* out, const void* dout, const float*
  * (s * 64 + i) * 32) -- slot step % 3 (step = step_state[2]) collects this step's maxima by atomic max, slot (step + 2) % 3 holds
  * last step's (the scale of this launch, *scale_inv = its inverse), slot (step + 1) % 3 is cleared for the next step; seed every
  * partial with a just-in-time maximum.  q8: [B*T, NH*H] (forward) / [B*T, 3*NH*H] (backward), one byte per element, 16-byte aligned.  only8 (backward only): the
- * bf16 dqkv is not written.  dg_attn_fp8_out_supported: 1 when the shape takes the MFMA kernels in their default forms (else cast). */
+ * bf16 dqkv is not written.  dg_attn_fp8_out_supported: 1 when the shape takes the MFMA kernels (else cast). */
 #define DG_ATTN_FP8_HIST (3 * 64 * 32)
 typedef struct dg_attn_fp8_out {
     void* q8; float* hist3; const uint32_t* step_state; float* scale_inv; int only8;
