@@ -152,6 +152,10 @@ SIGNATURES = {
     "dg_reduce_sum": [_vp, _i64, _f, _vp, _vp],
     "dg_softmax_rows": [_vp, _i64, _vp, _i64, _i, _i, _vp],
     "dg_adamw_step": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _f, _vp, _i, _vp],
+    "dg_sumsq_parts": [_i64],
+    "dg_sumsq_partials": [_vp, _i64, _vp, _vp],
+    "dg_grad_norm_finalize": [_vp, _i, _f, _vp, _vp, _vp],
+    "dg_adamw_step_clip": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _f, _vp, _vp, _i, _vp],
     "dg_block_chain_supported": [_i, _i],
     "dg_block_chain_fwd": [C.POINTER(BlockChainArgs), _vp],
     "dg_l2_warm": [_vp, _i64, _vp],
@@ -179,6 +183,7 @@ def _load() -> C.CDLL:
     lib.dg_gemm_tn_grouped_workspace_bytes.restype = C.c_int64
     lib.dg_attn_bwd_workspace_bytes.restype = C.c_int64
     lib.dg_attn_keep_bits_bytes.restype = C.c_int64
+    lib.dg_sumsq_parts.restype = C.c_int64
     lib.dg_error_string.argtypes = [C.c_int]
     lib.dg_error_string.restype = C.c_char_p
     v = lib.dg_version()

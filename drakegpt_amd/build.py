@@ -36,6 +36,7 @@ SOURCES = [
     "cross_entropy.hip",
     "chain.hip",
     "chain_bwd.hip",
+    "grad_clip.hip",
 ]
 
 

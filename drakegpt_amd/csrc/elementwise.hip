@@ -851,10 +851,14 @@ extern "C" int dg_softmax_rows(const float* logits, int64_t ldl, float* probs, i
 // advance: the step word moves on inside this launch -- every workgroup reads it first thing and registers at an arrival
 // counter (word 3 of the state) when it is done; the last one to arrive writes step + 1 and clears the counter.  (A separate
 // one-thread launch for that cost 4 us of the step.)
+// CLIP: the gradient clipping coefficient (dg_grad_norm_finalize) is read from device memory and multiplied into grad_scale once per
+// workgroup; CLIP = false is the unclipped kernel unchanged, and a coefficient of exactly 1 gives the same bits (grad_scale * 1.0f).
+template <bool CLIP>
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                              float* __restrict__ v, int64_t n, const float* __restrict__ hyper,
                              uint32_t* rng_state, float grad_scale,
-                             bf16_t* __restrict__ shadow, int advance) {
+                             bf16_t* __restrict__ shadow, int advance, const float* __restrict__ clip_coef) {
+    if (CLIP) grad_scale *= clip_coef[0];
     const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4];
     const uint32_t step_now = rng_state[2];
     const float t = (float)(step_now + 1u);
@@ -912,16 +916,32 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
     }
 }
 
-extern "C" int dg_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper,
-                             uint32_t* rng_state, float grad_scale, void* shadow_bf16, int advance_step, void* stream) {
+static int adamw_launch(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, uint32_t* rng_state,
+                        float grad_scale, const float* clip_coef, void* shadow_bf16, int advance_step, void* stream) {
     if (!p || !g || !m || !v || !hyper || !rng_state || n <= 0) return DG_ERR_ARG;
     if (!dg_aligned16(p) || !dg_aligned16(g) || !dg_aligned16(m) || !dg_aligned16(v)) return DG_ERR_ALIGN;
     unsigned grid = (unsigned)((n / 4 + 255) / 256);
     if (grid == 0) grid = 1;
     if (grid > 2048) grid = 2048;
-    hipLaunchKernelGGL(adamw_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, hyper, rng_state, grad_scale, (bf16_t*)shadow_bf16, advance_step);
+    if (clip_coef)
+        hipLaunchKernelGGL(adamw_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, hyper, rng_state, grad_scale,
+                           (bf16_t*)shadow_bf16, advance_step, clip_coef);
+    else
+        hipLaunchKernelGGL(adamw_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, hyper, rng_state, grad_scale,
+                           (bf16_t*)shadow_bf16, advance_step, (const float*)nullptr);
     DG_LAUNCH_CHECK();
     return DG_OK;
+}
+
+extern "C" int dg_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper,
+                             uint32_t* rng_state, float grad_scale, void* shadow_bf16, int advance_step, void* stream) {
+    return adamw_launch(p, g, m, v, n, hyper, rng_state, grad_scale, nullptr, shadow_bf16, advance_step, stream);
+}
+
+extern "C" int dg_adamw_step_clip(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, uint32_t* rng_state,
+                                  float grad_scale, const float* clip_coef, void* shadow_bf16, int advance_step, void* stream) {
+    if (!clip_coef) return DG_ERR_ARG;
+    return adamw_launch(p, g, m, v, n, hyper, rng_state, grad_scale, clip_coef, shadow_bf16, advance_step, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

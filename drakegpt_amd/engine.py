@@ -31,6 +31,7 @@ import torch
 from . import ops
 from . import sublayers as S
 from .model import TransformerLM
+from .optim import check_max_grad_norm
 
 Tensor = torch.Tensor
 ALIGN = 64          # floats: every tensor starts on a 256-byte boundary of the flat buffer
@@ -176,7 +177,8 @@ class TrainEngine:
     def __init__(self, model: TransformerLM, batch_size: int, context_length: Optional[int] = None, *,
                  lr: float = 1e-3, betas=(0.9, 0.95), eps: float = 1e-8, weight_decay: float = 1e-2,
                  seed: int = 42, rank: int = 0, world_size: int = 1, process_group=None, use_graph: bool = True,
-                 dp_buckets: Optional[int] = None, logits: str = "auto", grad_stream: str = "auto", fp8_dw: Optional[bool] = None):
+                 dp_buckets: Optional[int] = None, logits: str = "auto", grad_stream: str = "auto", fp8_dw: Optional[bool] = None,
+                 max_grad_norm: Optional[float] = None):
         if not isinstance(model, TransformerLM):
             raise TypeError("TrainEngine drives TransformerLM (the other five models train through the autograd path)")
         p0 = next(model.parameters())
@@ -264,6 +266,15 @@ class TrainEngine:
             self.chain_bwd = False
         self._alloc_and_adopt()
         self.hyper = torch.tensor([lr, betas[0], betas[1], eps, weight_decay], dtype=torch.float32, device=self.dev)
+        # global-norm gradient clipping (ref: clip_grad_norm_(model.parameters(), max_norm) before optimizer.step()): the norm of
+        # the mean gradient over ranks, gflat[0, n_active) * 1 / world, is computed inside the step and its coefficient applied
+        # inside the AdamW launch; gflat / named_grads() keep the unclipped gradient.  clip_state = {total_norm, coef, max_norm, 0}
+        self.max_grad_norm = None if max_grad_norm is None else check_max_grad_norm(max_grad_norm)
+        self.clip_state = self.norm_work = self.last_grad_norm = None
+        if self.max_grad_norm is not None:
+            self.clip_state = torch.tensor([0.0, 1.0, self.max_grad_norm, 0.0], dtype=torch.float32, device=self.dev)
+            self.norm_work = ops.grad_norm_workspace([self.gflat], self.dev)
+            self.last_grad_norm = self.clip_state[0]          # 0-d view: the pre-clip norm of the latest step
         # dropout stream differs per data-parallel rank; the step word also drives Adam's bias correction
         self.state = ops.new_rng_state(seed + 0x9E3779B97F4A7C15 * rank & 0xFFFFFFFFFFFFFFFF, self.dev, 0)
         # window offsets: a staged block [rows, B] the captured step walks through by itself (row = step word - off_ctl[0],
@@ -833,8 +844,16 @@ class TrainEngine:
 
     def _prog_update(self):
         # (the step word moves on inside the AdamW launch: nothing after it reads the word)
-        ops.adamw_step(self.flat, self.gflat, self.m_, self.v_, self.hyper, self.state, 1.0 / self.world,
-                       shadow_bf16=self.shadow, n=self.n_active, advance=True)
+        if self.clip_state is None:
+            ops.adamw_step(self.flat, self.gflat, self.m_, self.v_, self.hyper, self.state, 1.0 / self.world,
+                           shadow_bf16=self.shadow, n=self.n_active, advance=True)
+        else:
+            # the gradient is final here on every path (the data-parallel optimizer graph runs after the exchange): norm of the mean
+            # over ranks, then AdamW on g * coef.  The alignment gaps of gflat are zero (no producer writes them), so the norm
+            # over the whole active range is the norm over the parameters.
+            ops.grad_norm(self.gflat, 1.0 / self.world, self.clip_state[2:3], self.clip_state, self.norm_work)
+            ops.adamw_step(self.flat, self.gflat, self.m_, self.v_, self.hyper, self.state, 1.0 / self.world,
+                           shadow_bf16=self.shadow, n=self.n_active, advance=True, clip=self.clip_state[1:2])
         self._refresh_transposes()
 
     def _dp(self) -> bool:
@@ -909,6 +928,13 @@ class TrainEngine:
 
     def set_lr(self, lr: float):
         self.hyper[0:1].fill_(float(lr))
+
+    def set_max_grad_norm(self, max_norm: float):
+        """a new clipping threshold for the following steps (a device write: captured graphs stay valid)"""
+        if self.clip_state is None:
+            raise RuntimeError("set_max_grad_norm: this engine was built without clipping (TrainEngine(..., max_grad_norm=...))")
+        self.max_grad_norm = check_max_grad_norm(max_norm)
+        self.clip_state[2:3].fill_(self.max_grad_norm)
 
     def set_offsets(self, ix: Tensor):
         """window offsets of THIS rank's rows for the next step (drawn by the host CPU generator, ref: preprocessing.py:43)"""

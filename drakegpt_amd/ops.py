@@ -755,13 +755,51 @@ def softmax_rows(logits: Tensor) -> Tensor:
 
 
 def adamw_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, hyper: Tensor, rng_state: Tensor, grad_scale: float = 1.0,
-               shadow_bf16: Optional[Tensor] = None, n: Optional[int] = None, advance: bool = False) -> None:
-    """advance: the launch also moves the step word of rng_state on (what state_advance does, without its launch)"""
+               shadow_bf16: Optional[Tensor] = None, n: Optional[int] = None, advance: bool = False, *,
+               clip: Optional[Tensor] = None) -> None:
+    """advance: the launch also moves the step word of rng_state on (what state_advance does, without its launch).
+    clip: a device fp32 scalar, the clipping coefficient written by grad_norm (out[1:2]); the step then applies g * grad_scale * coef
+    (dg_adamw_step_clip) and g itself stays unclipped.  None: dg_adamw_step, unchanged."""
     for t, nm in ((p, "p"), (g, "g"), (m, "m"), (v, "v"), (hyper, "hyper")):
         _chk(t, nm, torch.float32)
     n = p.numel() if n is None else n
-    check(lib.dg_adamw_step(_p(p), _p(g), _p(m), _p(v), n, _p(hyper), _p(rng_state), float(grad_scale), _p(shadow_bf16), int(advance),
-                            _stream()), "dg_adamw_step")
+    if clip is None:
+        check(lib.dg_adamw_step(_p(p), _p(g), _p(m), _p(v), n, _p(hyper), _p(rng_state), float(grad_scale), _p(shadow_bf16), int(advance),
+                                _stream()), "dg_adamw_step")
+        return
+    _chk(clip, "clip", torch.float32)
+    check(lib.dg_adamw_step_clip(_p(p), _p(g), _p(m), _p(v), n, _p(hyper), _p(rng_state), float(grad_scale), _p(clip), _p(shadow_bf16),
+                                 int(advance), _stream()), "dg_adamw_step_clip")
+
+
+def grad_norm_workspace(gs, device) -> Tensor:
+    """the fp64 partial sums grad_norm needs for the flat gradients gs (one range per buffer); reusable across steps"""
+    return torch.empty(sum(int(lib.dg_sumsq_parts(g.numel())) for g in gs), dtype=torch.float64, device=device)
+
+
+def grad_norm(gs, grad_scale: float, max_norm: Tensor, out: Tensor, work: Optional[Tensor] = None) -> Tensor:
+    """global 2-norm of the flat fp32 gradients gs (a tensor or a list of them: one norm over all) times grad_scale, and the
+    clipping coefficient -- the norm and coef of torch.nn.utils.clip_grad_norm_(params, max_norm) (norm_type 2), without touching
+    the gradients.  Writes out[0] = total_norm, out[1] = min(1, max_norm / (total_norm + 1e-6)); max_norm is a device fp32 scalar.
+    One dg_sumsq_partials launch per buffer and one dg_grad_norm_finalize launch; the result is bitwise reproducible."""
+    gs = [gs] if isinstance(gs, Tensor) else list(gs)
+    for i, g in enumerate(gs):
+        _chk(g, f"gs[{i}]", torch.float32)
+    _chk(max_norm, "max_norm", torch.float32)
+    _chk(out, "out", torch.float32)
+    if out.numel() < 2:
+        raise ValueError("grad_norm: out needs 2 floats {total_norm, coef}")
+    if work is None:
+        work = grad_norm_workspace(gs, out.device)
+    parts = [int(lib.dg_sumsq_parts(g.numel())) for g in gs]
+    if work.dtype != torch.float64 or work.numel() < sum(parts):
+        raise ValueError(f"grad_norm: work must be float64 with at least {sum(parts)} elements")
+    base = 0
+    for g, k in zip(gs, parts):
+        check(lib.dg_sumsq_partials(_p(g), g.numel(), work.data_ptr() + 8 * base, _stream()), "dg_sumsq_partials")
+        base += k
+    check(lib.dg_grad_norm_finalize(_p(work), base, float(grad_scale), _p(max_norm), _p(out), _stream()), "dg_grad_norm_finalize")
+    return out
 
 
 def block_chain_supported(M: int, C: int, dtype: torch.dtype) -> bool:

@@ -7,9 +7,16 @@ MI355X-first: on the first step the parameters that have a gradient are moved in
 ``.data`` become views of it, so ``state_dict()`` keeps working), with flat ``m`` / ``v`` / gradient buffers beside it:
 a step is one fused copy of the gradients, one ``dg_adamw_step`` launch (which also moves the step counter on) instead of two
 launches per parameter tensor (168 for the tiny TransformerLM).  With a process group the flat gradient is
-all-reduced (SUM) first and the kernel applies 1 / world: data-parallel training for all six models."""
+all-reduced (SUM) first and the kernel applies 1 / world: data-parallel training for all six models.
+
+max_grad_norm: global-norm clipping, ``torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm)`` just before ``step()``,
+over every parameter group, on the mean gradient over ranks.  ``step()`` then copies (and all-reduces) every group's gradient
+first, computes one norm over all groups' flat gradients on the GPU and updates every group with the same coefficient, which the
+AdamW launch applies: ``p.grad`` keeps the unclipped gradient (clip_grad_norm_ clips it in place).  ``last_grad_norm`` is the
+pre-clip norm of the latest step, a device scalar."""
 from __future__ import annotations
 
+import math
 from typing import Optional
 
 import torch
@@ -17,6 +24,17 @@ import torch
 from . import ops
 
 _ALIGN = 64          # floats: every tensor starts on a 256-byte boundary of the flat buffer
+
+
+def check_max_grad_norm(v) -> float:
+    """a clipping threshold must be a finite number > 0 (None, for no clipping, is handled by the callers)"""
+    try:
+        f = float(v)
+    except (TypeError, ValueError):
+        raise ValueError(f"max_grad_norm must be a finite number > 0, got {v!r}") from None
+    if not math.isfinite(f) or f <= 0.0:
+        raise ValueError(f"max_grad_norm must be a finite number > 0, got {v!r}")
+    return f
 
 
 class _Flat:
@@ -41,10 +59,20 @@ class _Flat:
 
 
 class AdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, *, process_group=None, world_size: int = 1):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, *, process_group=None, world_size: int = 1,
+                 max_grad_norm: Optional[float] = None):
+        self.max_grad_norm = None if max_grad_norm is None else check_max_grad_norm(max_grad_norm)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.process_group, self.world_size = process_group, int(world_size)
         self._flat = {}
+        self._clip = None               # device {total_norm, coef, max_norm, 0} (clipping on, after the first step)
+        self._clip_host = None
+        self._norm_work = None
+
+    @property
+    def last_grad_norm(self) -> Optional[torch.Tensor]:
+        """pre-clip global gradient norm of the latest step (0-d device tensor; None without clipping or before the first step)"""
+        return None if self._clip is None else self._clip[0]
 
     def _adopt(self, gi: int, params) -> _Flat:
         old = self._flat.get(gi)
@@ -71,28 +99,53 @@ class AdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        for gi, group in enumerate(self.param_groups):
-            params = [p for p in group["params"] if p.grad is not None]
-            if not params:
-                continue
-            if any(not p.is_cuda for p in params):
-                raise RuntimeError("drakegpt_amd.optim.AdamW updates GPU parameters only (no CPU path)")
-            fl = self._flat.get(gi)
-            if fl is None or fl.key != tuple(id(p) for p in params) or any(p.data.data_ptr() != fl.flat.data_ptr() + 4 * o
-                                                                           for p, o in zip(params, fl.offsets)):
-                fl = self._adopt(gi, params)
-            hy = (group["lr"], group["betas"][0], group["betas"][1], group["eps"], group["weight_decay"])
-            if hy != fl.hyper_host:
-                fl.hyper.copy_(torch.tensor(hy, dtype=torch.float32))
-                fl.hyper_host = hy
-            torch._foreach_copy_(fl.gviews, [p.grad for p in params])           # one fused launch
-            scale = 1.0
-            if self.world_size > 1:
-                import torch.distributed as dist
-                dist.all_reduce(fl.g, op=dist.ReduceOp.SUM, group=self.process_group)
-                scale = 1.0 / self.world_size
-            ops.adamw_step(fl.flat, fl.g, fl.m, fl.v, fl.hyper, fl.t, grad_scale=scale, advance=True)
+        scale = 1.0 / self.world_size if self.world_size > 1 else 1.0
+        if self.max_grad_norm is None:
+            for gi, group in enumerate(self.param_groups):
+                fl = self._gather(gi, group)
+                if fl is not None:
+                    ops.adamw_step(fl.flat, fl.g, fl.m, fl.v, fl.hyper, fl.t, grad_scale=scale, advance=True)
+            return loss
+        # clipping: every group's (all-reduced) gradient first, then ONE norm over all of them, then every group's update with it
+        flats = [fl for fl in (self._gather(gi, group) for gi, group in enumerate(self.param_groups)) if fl is not None]
+        if not flats:
+            return loss
+        dev = flats[0].g.device
+        if self._clip is None or self._clip.device != dev:
+            self._clip = torch.tensor([0.0, 1.0, 0.0, 0.0], dtype=torch.float32, device=dev)
+            self._clip_host = None
+        if self._clip_host != self.max_grad_norm:
+            self.max_grad_norm = check_max_grad_norm(self.max_grad_norm)
+            self._clip[2:3].fill_(self.max_grad_norm)
+            self._clip_host = self.max_grad_norm
+        key = tuple(fl.n for fl in flats)
+        if self._norm_work is None or self._norm_work[0] != key or self._norm_work[1].device != dev:
+            self._norm_work = (key, ops.grad_norm_workspace([fl.g for fl in flats], dev))
+        ops.grad_norm([fl.g for fl in flats], scale, self._clip[2:3], self._clip, self._norm_work[1])
+        for fl in flats:
+            ops.adamw_step(fl.flat, fl.g, fl.m, fl.v, fl.hyper, fl.t, grad_scale=scale, advance=True, clip=self._clip[1:2])
         return loss
+
+    def _gather(self, gi: int, group) -> Optional[_Flat]:
+        """the group's flat buffers, current hyperparameters and gradient (all-reduced under data parallelism); None: no gradients"""
+        params = [p for p in group["params"] if p.grad is not None]
+        if not params:
+            return None
+        if any(not p.is_cuda for p in params):
+            raise RuntimeError("drakegpt_amd.optim.AdamW updates GPU parameters only (no CPU path)")
+        fl = self._flat.get(gi)
+        if fl is None or fl.key != tuple(id(p) for p in params) or any(p.data.data_ptr() != fl.flat.data_ptr() + 4 * o
+                                                                       for p, o in zip(params, fl.offsets)):
+            fl = self._adopt(gi, params)
+        hy = (group["lr"], group["betas"][0], group["betas"][1], group["eps"], group["weight_decay"])
+        if hy != fl.hyper_host:
+            fl.hyper.copy_(torch.tensor(hy, dtype=torch.float32))
+            fl.hyper_host = hy
+        torch._foreach_copy_(fl.gviews, [p.grad for p in params])           # one fused launch
+        if self.world_size > 1:
+            import torch.distributed as dist
+            dist.all_reduce(fl.g, op=dist.ReduceOp.SUM, group=self.process_group)
+        return fl
 
     # ---- checkpointing: the moments and the step count live in the flat buffers, not in torch's per-parameter `state`; export /
     # import them in torch.optim.AdamW's own format (state[i] = {"step", "exp_avg", "exp_avg_sq"}) so that a resumed run keeps

@@ -131,6 +131,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32", "fp8", "bf16x3"])
     ap.add_argument("--model-dir", default="model")
     ap.add_argument("--sample", type=int, default=100)
+    ap.add_argument("--grad-clip", type=float, default=None, metavar="MAX_NORM",
+                    help="clip the gradient to this global 2-norm before every AdamW step (ref: clip_grad_norm_; default: off); each "
+                    "evaluation line then also reports the last step's pre-clip norm as grad_norm")
     return ap
 
 
@@ -179,12 +182,14 @@ def main(argv=None):
     engine = None
     if args.model == "TransformerLM":
         from .engine import TrainEngine
-        engine = TrainEngine(model, B, T, lr=base_lr, betas=params["betas"], seed=42, rank=rank, world_size=world, process_group=pg)
+        engine = TrainEngine(model, B, T, lr=base_lr, betas=params["betas"], seed=42, rank=rank, world_size=world, process_group=pg,
+                             max_grad_norm=args.grad_clip)
         engine.set_corpus(train_dev)
     else:
         # the five earlier-stage models train through the autograd path; their flat-buffer AdamW all-reduces the gradient
         from .optim import AdamW
-        optimizer = AdamW(model.parameters(), lr=base_lr, betas=params["betas"], process_group=pg, world_size=world)
+        optimizer = AdamW(model.parameters(), lr=base_lr, betas=params["betas"], process_group=pg, world_size=world,
+                          max_grad_norm=args.grad_clip)
 
     model.train()
     sched = {"steps": 0}
@@ -207,8 +212,12 @@ def main(argv=None):
                 g["lr"] = lr
         if rank == 0:
             el = time.perf_counter() - t0
-            print(json.dumps({"step": it + 1, "train_loss": float(losses["train"]), "val_loss": float(losses["val"]), "lr": lr,
-                              "tokens_per_s": (it + 1) * B * T * world / el}), flush=True)
+            line = {"step": it + 1, "train_loss": float(losses["train"]), "val_loss": float(losses["val"]), "lr": lr,
+                    "tokens_per_s": (it + 1) * B * T * world / el}
+            if args.grad_clip is not None:
+                # the last step's pre-clip norm: the evaluation has synchronised the stream already
+                line["grad_norm"] = float((engine if engine is not None else optimizer).last_grad_norm)
+            print(json.dumps(line), flush=True)
         model.train()
 
     if engine is not None:

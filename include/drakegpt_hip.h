@@ -407,6 +407,25 @@ int dg_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, const
                   uint32_t* rng_state, float grad_scale, void* shadow_bf16, int advance_step, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Global-norm gradient clipping -- ref: torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) (norm_type 2,
+ * error_if_nonfinite False) ahead of optimizer.step(), on the gradient the optimizer applies, without clipping it in place:
+ *   dg_sumsq_partials: sum of squares of g[0, n) (fp32, 16-byte aligned), one fp64 partial per workgroup written to
+ *     part[0, dg_sumsq_parts(n)).  The partition depends on n alone, so the partials are bitwise reproducible.  Several
+ *     buffers (parameter groups) share one norm: each writes its own range of one partial array.
+ *   dg_grad_norm_finalize: ONE workgroup sums part[0, n_parts) in index order (fp64) and writes, in fp32,
+ *     out[0] = total_norm = grad_scale * sqrt(sum)          (what clip_grad_norm_ returns, before clipping)
+ *     out[1] = coef = min(1, max_norm[0] / (total_norm + 1e-6))   (torch's formula; a NaN norm gives a NaN coef)
+ *     max_norm is read from device memory (a captured graph picks up a new value without recapture).
+ *   dg_adamw_step_clip: dg_adamw_step with grad_scale multiplied by clip_coef[0] (a device float, e.g. out + 1) inside the
+ *     launch: the AdamW step on g * grad_scale * coef.  The stored gradient g is left unclipped.  A coefficient of exactly 1
+ *     gives the same bits as dg_adamw_step. */
+int64_t dg_sumsq_parts(int64_t n);
+int dg_sumsq_partials(const float* g, int64_t n, double* part, void* stream);
+int dg_grad_norm_finalize(const double* part, int n_parts, float grad_scale, const float* max_norm, float* out, void* stream);
+int dg_adamw_step_clip(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, uint32_t* rng_state,
+                       float grad_scale, const float* clip_coef, void* shadow_bf16, int advance_step, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * The row-local chain of one residual block in ONE launch (bf16 operands, C = 384, M % 64 == 0) -- ref:
  * src/model_component.py:454 (proj) + :505 (x + ...), :506 + :488-489 (LayerNorm 2), :320-325 (FeedForward3), the second
  * residual add, and the NEXT block's :505 LayerNorm 1 + :392-393,404 (its 3 * NH per-head Linears as one packed operand):
