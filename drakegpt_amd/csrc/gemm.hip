@@ -14,16 +14,15 @@
 //   gemm_nt_kernel             fp32 parity mode (v_mfma_f32_16x16x4_f32 = exact fp32 FMA accumulation) and bf16
 //                              shapes the default does not cover: 128x128 tile / 256 threads, register-prefetched
 //                              global -> LDS staging, double-buffered XOR-swizzled LDS, LDS-staged epilogue
-//   gemm_tn_grouped256_kernel  all dW of a backward pass in one launch, 256x128 tiles, chained K halves
-//   gemm_tn_grouped_kernel     the same with 128x128 tiles (DG_TN_TILE=128)
+//   gemm_tn_grouped256_kernel  all dW of a backward pass in one launch, 256x128 tiles, chained K halves (bf16 and fp8)
 //   gemm_tn_ws_kernel, gemm_tn_bf16_kernel, gemm_tn_f32_kernel   one dW per launch, split-K fp32 slabs
 //   gemm_nt_x3_kernel, gemm_tn_x3_kernel   precision "bf16x3": fp32 operands split into bf16 hi + lo in registers,
 //                              3 bf16 MFMAs per block (gemm_nt_kernel / gemm_tn_f32_kernel geometry); the wave-specialised
 //                              split NT form is instantiated in gemm_x3.hip
 // Earlier variants that were measured slower (LDS-DMA without loader waves, one tile per workgroup, 256x128 NT
-// tiles, two co-resident workgroups per CU) are in the history of this file and listed in DESIGN.md section 4.
+// tiles, two co-resident workgroups per CU, 128x128 grouped dW tiles, 128x64 grouped dW wave tiles) are in the history
+// of this file and listed in DESIGN.md section 4.  The kernel choice follows from the call's arguments alone.
 #include "common.h"
-#include <stdlib.h>
 
 #include "gemm_nt_ws.h"
 #define NT_LDS_BYTES (4 * 64 * EPI_PITCH * 4)  // 69632: four 64x68 fp32 staging slices >= the 4 x 16 KB operand buffers
@@ -214,11 +213,6 @@ static unsigned long long* g_stamp_buffer = nullptr;
 // diagnostic only (tools/gemm_stamps.py): not part of the public header
 extern "C" void dg_debug_set_stamp_buffer(void* p) { g_stamp_buffer = (unsigned long long*)p; }
 
-// bf16 NT variant switch for A/B benchmarking: DG_GEMM_NT = 0 wave-specialised persistent LDS-DMA (default), 1 register-staged
-static int dg_nt_mode() {
-    static const int v = [] { const char* e = getenv("DG_GEMM_NT"); return e ? atoi(e) : 0; }();
-    return v;
-}
 static int dg_num_cus() {
     static const int v = [] {
         int dev = 0, n = 256;
@@ -232,37 +226,32 @@ static int dg_num_cus() {
 }
 
 extern "C" int dg_gemm_nt_sign_bits_supported(const dg_gemm_nt_args* a) {
-    if (!a || a->N <= 0 || a->N % 8 || dg_nt_mode() != 0) return 0;
+    if (!a || a->N <= 0 || a->N % 8) return 0;
     if (a->in_dtype == DG_BF16) return a->K % 64 == 0 && a->K >= 128;
     return (a->in_dtype == DG_FP8_E4M3 || a->in_dtype == DG_FP8_E5M2) && a->K % 128 == 0 && a->K >= 256;
 }
 
-// bytes of the lane-ordered bit mask: one bit per element of every (whole) output tile of the kernel that will run
-static bool dg_nt_wide(int N) {
-    static const int wide_mode = [] { const char* e = getenv("DG_GEMM_WIDE"); return e ? atoi(e) : 1; }();   // 0 = square tiles only (A/B runs)
-    return wide_mode && N % 192 == 0;
-}
+// 128 x 192 tiles of the wave-specialised kernel (otherwise 128 x 128)
+static bool dg_nt_wide(int N) { return N % 192 == 0; }
 // fp8 copy of the output from the epilogue: (EPI 8) the bias + ReLU + sign-bit form with e4m3 operands -> e4m3 copy, or (EPI 9)
 // the sign-bit-masked dX form with column sums and e5m2 gradients -> e5m2 copy; bf16 output, every tile whole and on the
 // vector path, and exactly DG_FP8_AMAX_PARTS persistent workgroups (one partial maximum each).
 extern "C" int dg_gemm_nt_colsum_supported(const dg_gemm_nt_args* a);
 extern "C" int dg_gemm_nt_fp8_out_supported(const dg_gemm_nt_args* a) {
-    if (!a || !dg_gemm_nt_sign_bits_supported(a) || a->out_dtype != DG_BF16) return 0;
-    static const int dbg = [] { const char* e = getenv("DG_GEMM_DBG"); return e ? atoi(e) : 0; }();
-    static const int mode = [] { const char* e = getenv("DG_FP8_FUSED_OUT"); return e ? atoi(e) : 3; }();   // bit 0: forward form, bit 1: dX form (A/B runs)
-    if (dbg || g_stamp_buffer) return 0;
+    if (!a || !dg_gemm_nt_sign_bits_supported(a) || a->out_dtype != DG_BF16 || g_stamp_buffer) return 0;
     const int bn = dg_nt_wide(a->N) ? 192 : 128;
     if (a->M % BM || a->N % bn || a->ldc % 8 || !dg_aligned16(a->C)) return 0;
     const int64_t n_tiles = (int64_t)(a->M / BM) * (a->N / bn);
     if (dg_num_cus() != DG_FP8_AMAX_PARTS || n_tiles < DG_FP8_AMAX_PARTS) return 0;
     if (a->in_dtype == DG_FP8_E4M3)
-        return (mode & 1) && a->bias && dg_aligned16(a->bias) && a->relu && a->sign_bits_out && !a->relu_mask && !a->residual && !a->sign_bits &&
+        return a->bias && dg_aligned16(a->bias) && a->relu && a->sign_bits_out && !a->relu_mask && !a->residual && !a->sign_bits &&
                !a->colsum_part && !(a->dropout_p > 0.f && a->rng_state);
     if (a->in_dtype == DG_FP8_E5M2)
-        return (mode & 2) && a->colsum_part && dg_gemm_nt_colsum_supported(a);
+        return a->colsum_part && dg_gemm_nt_colsum_supported(a);
     return 0;
 }
 
+// bytes of the lane-ordered bit mask: one bit per element of every (whole) output tile of the kernel that will run
 extern "C" int64_t dg_gemm_nt_sign_bits_bytes(int M, int N) {
     if (M <= 0 || N <= 0) return 0;
     const int bn = dg_nt_wide(N) ? 192 : 128;
@@ -270,14 +259,11 @@ extern "C" int64_t dg_gemm_nt_sign_bits_bytes(int M, int N) {
 }
 
 // Column sums in the epilogue: only the sign-bit-masked dX form (the one whose output is the pre-activation gradient a bias
-// gradient is the column sum of), every tile interior and on the vector path, debug switches off.
+// gradient is the column sum of), every tile interior and on the vector path, no stamp buffer.
 extern "C" int dg_gemm_nt_colsum_supported(const dg_gemm_nt_args* a) {
     if (!a || !dg_gemm_nt_sign_bits_supported(a) || !a->sign_bits || a->out_dtype != DG_BF16) return 0;
     if (a->bias || a->relu || a->relu_mask || a->residual || a->sign_bits_out || (a->dropout_p > 0.f && a->rng_state)) return 0;
-    static const int pf_mode = [] { const char* e = getenv("DG_GEMM_PF"); return e ? atoi(e) : 1; }();
-    static const int dbg = [] { const char* e = getenv("DG_GEMM_DBG"); return e ? atoi(e) : 0; }();
-    static const int cs_mode = [] { const char* e = getenv("DG_GEMM_COLSUM"); return e ? atoi(e) : 1; }();   // 0 = never (A/B runs)
-    if (!pf_mode || dbg || g_stamp_buffer || !cs_mode) return 0;
+    if (g_stamp_buffer) return 0;
     const int bn = dg_nt_wide(a->N) ? 192 : 128;
     return a->M % BM == 0 && a->N % bn == 0 && a->ldc % 8 == 0 && dg_aligned16(a->C);
 }
@@ -312,7 +298,7 @@ extern "C" int dg_gemm_nt(const dg_gemm_nt_args* a, void* stream) {
     if (fp8) {
         // B (the weight operand) is e4m3; per-tensor dequantisation factors are mandatory; only the LDS-DMA kernel has an fp8 form
         if (a->b_dtype != DG_FP8_E4M3 || !a->scale_a || !a->scale_b || a->relu_mask) return DG_ERR_ARG;
-        if (a->K % 128 || a->K < 256 || dg_nt_mode() != 0) return DG_ERR_ARG;
+        if (a->K % 128 || a->K < 256) return DG_ERR_ARG;
     } else if (a->b_dtype != 0 && a->b_dtype != a->in_dtype && !(x3 && a->b_dtype == DG_F32)) return DG_ERR_DTYPE;
     if (a->K % epc || a->lda % epc || a->ldb % epc || !dg_aligned16(a->A) || !dg_aligned16(a->B)) return DG_ERR_ALIGN;
     if (a->lda < a->K || a->ldb < a->K || a->ldc < a->N) return DG_ERR_ARG;
@@ -335,7 +321,7 @@ extern "C" int dg_gemm_nt(const dg_gemm_nt_args* a, void* stream) {
     p.B = (const char*)a->B; p.ldb_b = a->ldb * esz;
     p.C = a->C; p.ldc = a->ldc;
     // split form (x3_ws): the wave-specialised kernel where K is whole 128-byte steps, at least two; the generic one otherwise
-    const bool x3_ws = x3 && a->K % 32 == 0 && a->K >= 128 && dg_nt_mode() == 0;
+    const bool x3_ws = x3 && a->K % 32 == 0 && a->K >= 128;
     p.M = a->M; p.N = a->N;
     p.K = fp8 ? a->K / 2 : (x3_ws ? 2 * a->K : a->K);        // fp8 / split: K in 2-byte units, the kernel's K step is 128 BYTES
     p.scale_a = a->scale_a; p.scale_b = a->scale_b;
@@ -352,14 +338,10 @@ extern "C" int dg_gemm_nt(const dg_gemm_nt_args* a, void* stream) {
     p.vec_ok = (a->ldc % 4 == 0) && ((((uintptr_t)a->C) % (4 * osz)) == 0) &&
                (!a->residual || ((a->ldr % 4 == 0) && dg_aligned16(a->residual)));
     p.mask_vec_ok = a->relu_mask && (a->ldmask % 4 == 0) && ((((uintptr_t)a->relu_mask) % (4 * esz)) == 0);
-    { static const int dbg = [] { const char* e = getenv("DG_GEMM_DBG"); return e ? atoi(e) : 0; }(); p.dbg = dbg; }
-    { static const int rpf = [] { const char* e = getenv("DG_NT_RESPF"); return e ? atoi(e) : 0; }(); p.res_prefetch = rpf; }
-    {   // weights of at most 2 MB (every block Linear of the scaled model; not lm_head at the GPT-2 vocabulary), one touch per lane
-        static const int wm = [] { const char* e = getenv("DG_NT_WARM"); return e ? atoi(e) : 1; }();     // same box, headline step: 2.498 -> 2.478 ms
-        // (wm = the largest operand in MB that is warmed: 2 by default; DG_NT_WARM=8 also covers the GPT-2 widths' matrices, which
-        // exceed an XCD's 4 MB of L2 -- A/B)
+    {   // weights of at most 2 MB (every block Linear of the scaled model; not lm_head at the GPT-2 vocabulary), one touch per
+        // lane (headline step: 2.498 -> 2.478 ms); warm_b = touch rounds of 2 MB each
         const int64_t wbytes = (int64_t)a->N * a->ldb * esz;
-        p.warm_b = (wm && wbytes <= ((int64_t)(wm < 2 ? 2 : wm) << 20) && (a->ldb * esz) % 128 == 0 && (((uintptr_t)a->B) & 127) == 0) ? (int)((wbytes + (2 << 20) - 1) >> 21) : 0;
+        p.warm_b = (wbytes <= ((int64_t)2 << 20) && (a->ldb * esz) % 128 == 0 && (((uintptr_t)a->B) & 127) == 0) ? (int)((wbytes + (2 << 20) - 1) >> 21) : 0;
     }
     p.stamps = g_stamp_buffer;
     const int tiles_m = (a->M + BM - 1) / BM;
@@ -367,10 +349,10 @@ extern "C" int dg_gemm_nt(const dg_gemm_nt_args* a, void* stream) {
     p.n_tiles = tiles_m * p.tiles_n;
     dim3 grid(p.n_tiles), block(256);
     hipStream_t s = (hipStream_t)stream;
-    if (fp8 || x3_ws || (a->in_dtype == DG_BF16 && a->K % 64 == 0 && a->K >= 128 && dg_nt_mode() == 0)) {
+    if (fp8 || x3_ws || (a->in_dtype == DG_BF16 && a->K % 64 == 0 && a->K >= 128)) {
         dim3 pgrid(p.n_tiles < dg_num_cus() ? p.n_tiles : dg_num_cus());
-        static const int pf_mode = [] { const char* e = getenv("DG_GEMM_PF"); return e ? atoi(e) : 1; }();   // 0 = load the mask bits inside the epilogue (A/B runs)
-        const bool pf = pf_mode && a->sign_bits != nullptr && p.vec_ok && (!a->bias || dg_aligned16(a->bias)) &&
+        // the mask bits of the sign-bit dX form are prefetched ahead of the epilogue
+        const bool pf = a->sign_bits != nullptr && p.vec_ok && (!a->bias || dg_aligned16(a->bias)) &&
                         (a->ldc * (a->out_dtype == DG_BF16 ? 2 : 4)) % 16 == 0 && dg_aligned16(a->C);
         const bool wide = dg_nt_wide(a->N);                       // 128 x 192 tiles
         if (wide) {
@@ -380,11 +362,11 @@ extern "C" int dg_gemm_nt(const dg_gemm_nt_args* a, void* stream) {
         }
         p.cs_accum = dg_nt_cs_accum(p.n_tiles, p.tiles_n) ? 1 : 0;
         const dim3 wsb(512 + 64 * WS_NLOAD);
-        // epilogue specialisation (see the kernel's EPI parameter); anything else, and every debug run, takes the generic form
+        // epilogue specialisation (see the kernel's EPI parameter); anything else, and every stamped run, takes the generic form
         int epi = 0;
         {
             const bool plain = !a->bias && !a->relu && !a->relu_mask && !p.drop && !a->residual && !a->sign_bits && !a->sign_bits_out;
-            if (p.dbg == 0 && !p.stamps) {
+            if (!p.stamps) {
                 if (plain) epi = 1;
                 else if (a->out_dtype == DG_BF16 && a->bias && a->relu && a->sign_bits_out && !a->relu_mask && !p.drop && !a->residual && !a->sign_bits) epi = a->fp8_out ? 8 : 2;
                 else if (a->bias && p.drop && a->residual && !a->relu && !a->relu_mask && !a->sign_bits && !a->sign_bits_out) epi = 3;
@@ -683,14 +665,14 @@ __global__ __launch_bounds__(768) void gemm_tn_ws_kernel(TnParams p) {
 // (of any problem of the group) with ONE continuous stage pipeline and each tile runs over the whole
 // contraction, so there are no split-K slabs to write, re-read and reduce (they were ~790 MB per step)
 // and no per-matrix launch: 651 tiles of 256 K steps instead of 25 launches of <= 256 short workgroups.
-#define TN_MAX_GROUP 64                       // 24 + 64 x 56 B of kernel arguments (limit 4 KB): GPT-2-small's 49 matrices in one launch
+#define TN_MAX_GROUP 64                       // 32 + 64 x 56 B of kernel arguments (limit 4 KB): GPT-2-small's 49 matrices in one launch
 struct TnProblem {
     const char* A; const char* B; float* out;
     int lda_b, ldb_b, ldo;                    // byte strides of A and B (< 2 GB), element stride of out
     int P, Q, R, tiles_q, tile_begin;
 };
-// ws (256-row-tile kernel only): split-K workspace, [total_tiles][8 waves][16 KB] fp32 partials then [total_tiles][8] flags
-struct TnGroup { int n, total_tiles; int splits, tiles_pad; char* ws; unsigned* err; unsigned* sync; int sync_every, pad_; TnProblem pr[TN_MAX_GROUP]; };
+// ws: split-K workspace, [total_tiles][8 waves][16 KB] fp32 partials then [total_tiles][8] flags
+struct TnGroup { int n, total_tiles; int splits, tiles_pad; char* ws; unsigned* err; TnProblem pr[TN_MAX_GROUP]; };
 // fp8 operands (round 3): e5m2 dY x e4m3 X with one dequantisation factor per operand (device scalars).  Two more pointers per
 // problem: 48 problems per launch keep the kernel arguments under 4 KB (GPT-2-medium's 96 block matrices: two launches).
 #define TN_MAX_GROUP8 48
@@ -700,188 +682,34 @@ struct TnProblem8 {
     int lda_b, ldb_b, ldo;
     int P, Q, R, tiles_q, tile_begin;
 };
-struct TnGroup8 { int n, total_tiles; int splits, tiles_pad; char* ws; unsigned* err; unsigned* sync; int sync_every, pad_; TnProblem8 pr[TN_MAX_GROUP8]; };
+struct TnGroup8 { int n, total_tiles; int splits, tiles_pad; char* ws; unsigned* err; TnProblem8 pr[TN_MAX_GROUP8]; };
 template <bool F8> struct TnGroupOf { typedef TnGroup type; };
 template <> struct TnGroupOf<true> { typedef TnGroup8 type; };
 
-__global__ __launch_bounds__(768) void gemm_tn_grouped_kernel(TnGroup gp) {
-    __shared__ __attribute__((aligned(16))) char lds[GL_NST * GL_STAGE];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform -> SGPR
-    const int wp = wave >> 1, wq = wave & 1;
-    const int G = gridDim.x;
-    const int my_tiles = (gp.total_tiles - (int)blockIdx.x + G - 1) / G;
-    auto locate = [&](int ti, int& pi, int& p0, int& q0) {
-        const int tile = dg_xcd_remap((int)blockIdx.x + ti * G, gp.total_tiles);
-        pi = 0;
-        for (int i = 1; i < gp.n; ++i)
-            if (tile >= gp.pr[i].tile_begin) pi = i;
-        const int local = tile - gp.pr[pi].tile_begin;
-        p0 = (local / gp.pr[pi].tiles_q) * 128; q0 = (local % gp.pr[pi].tiles_q) * 128;
-    };
-    int total = 0;
-    for (int ti = 0; ti < my_tiles; ++ti) {
-        int pi, p0, q0;
-        locate(ti, pi, p0, q0);
-        total += gp.pr[pi].R / 64;
-    }
-
-    if (wave >= 8) {
-        // ---- loader role: piece = 1 KB = 4 rows x 256 B; this wave moves pieces 4lw..4lw+3 of A and of B per stage
-        const int lw = wave - 8;
-        const int prow = lane >> 4, slot = lane & 15;
-        const char* srcA[4];
-        const char* srcB[4];
-        int64_t stepA = 0, stepB = 0;
-        int nk_iss = 1;
-        auto set_src = [&](int ti) {
-            int pi, p0, q0;
-            locate(ti, pi, p0, q0);
-            const TnProblem& pr = gp.pr[pi];
-            nk_iss = pr.R / 64;
-            stepA = 64 * (int64_t)pr.lda_b; stepB = 64 * (int64_t)pr.ldb_b;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int q = 4 * lw + i;
-                const int row = 4 * q + prow;
-                const int chunk = slot ^ ((prow << 2) | (q & 3));
-                int ca = p0 + chunk * 8; if (ca + 8 > pr.lda_b / 2) ca = 0;   // past the leading dimension: clamp
-                int cb = q0 + chunk * 8; if (cb + 8 > pr.ldb_b / 2) cb = 0;
-                srcA[i] = pr.A + (int64_t)row * pr.lda_b + (int64_t)ca * 2;
-                srcB[i] = pr.B + (int64_t)row * pr.ldb_b + (int64_t)cb * 2;
-            }
-        };
-        int iss_tile = 0, iss_kt = 0;
-        auto issue = [&](int g) {
-            char* base = lds + (g & (GL_NST - 1)) * GL_STAGE + (4 * lw) * 1024;
-            const int64_t ra = (int64_t)iss_kt * stepA, rb = (int64_t)iss_kt * stepB;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                __builtin_amdgcn_global_load_lds((gptr_t)(srcA[i] + ra), (lptr_t)(base + i * 1024), 16, 0, 0);
-                __builtin_amdgcn_global_load_lds((gptr_t)(srcB[i] + rb), (lptr_t)(base + 16384 + i * 1024), 16, 0, 0);
-            }
-            if (++iss_kt == nk_iss) { iss_kt = 0; if (++iss_tile < my_tiles) set_src(iss_tile); }
-        };
-        if (total > 0) {
-            set_src(0);
-            const int npre = total < GL_NST - 1 ? total : GL_NST - 1;
-            for (int g = 0; g < npre; ++g) issue(g);
-            if (npre >= 3) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-            else if (npre == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            for (int g = 0; g + 1 < total; ++g) {
-                int issued = g + GL_NST - 1; if (issued > total) issued = total;
-                if (issued - (g + 2) >= 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                if (g + GL_NST - 1 < total) issue(g + GL_NST - 1);
-            }
-        }
-        return;
-    }
-    if (total == 0) return;
-
-    f32x4 acc[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const int fr = lane & 15, fg = lane >> 4;
-    auto read_frags = [&](u32x4 (&fa)[2], u32x4 (&fb)[4], const char* buf, int ks) {
-        const int r0 = ks * 32 + fg * 8;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) fa[i] = tn_frag_bf16(buf, r0, wp * 32 + i * 16, lane);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) fb[j] = tn_frag_bf16(buf + 16384, r0, wq * 64 + j * 16, lane);
-    };
-    auto mma_all = [&](const u32x4 (&fa)[2], const u32x4 (&fb)[4]) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) mma16<bf16_t>(fb[j], fa[i], acc[i][j]);
-    };
-    int cur_pi, cur_p0, cur_q0;
-    locate(0, cur_pi, cur_p0, cur_q0);
-    int nk_cur = gp.pr[cur_pi].R / 64;
-    auto store_tile = [&]() {
-        const TnProblem& pr = gp.pr[cur_pi];
-        float* out = pr.out;
-        const bool vec = (pr.ldo % 4 == 0) && ((((uintptr_t)out) & 15) == 0);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int row = cur_p0 + wp * 32 + i * 16 + fr;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int col = cur_q0 + wq * 64 + j * 16 + 4 * fg;
-                if (row < pr.P) {
-                    float* op = out + (int64_t)row * pr.ldo + col;
-                    if (vec && col + 3 < pr.Q) *(f32x4*)op = acc[i][j];
-                    else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            if (col + e < pr.Q) op[e] = acc[i][j][e];
-                    }
-                }
-                acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            }
-        }
-    };
-    u32x4 fa0[2], fb0[4], fa1[2], fb1[4];
-    __builtin_amdgcn_s_barrier();                                  // stage 0 published by the loaders
-    read_frags(fa0, fb0, lds, 0);
-    int kt = 0, tile_i = 0;
-    for (int g = 0; g < total; ++g) {
-        const char* buf = lds + (g & (GL_NST - 1)) * GL_STAGE;
-        read_frags(fa1, fb1, buf, 1);
-        mma_all(fa0, fb0);
-        if (g + 1 < total) {
-            __builtin_amdgcn_s_barrier();
-            read_frags(fa0, fb0, lds + ((g + 1) & (GL_NST - 1)) * GL_STAGE, 0);
-        }
-        mma_all(fa1, fb1);
-        if (++kt == nk_cur) {
-            store_tile();
-            kt = 0;
-            if (++tile_i < my_tiles) { locate(tile_i, cur_pi, cur_p0, cur_q0); nk_cur = gp.pr[cur_pi].R / 64; }
-        }
-    }
-}
-
 // ---------------------------------------------------------------------------------------------
-// 256 x 128 output tiles for the grouped dW GEMM: 8 MFMA waves in 4 x 2, wave tile 64 x 64.  The dW K step is bound by
-// the transposed LDS reads (ds_read_b64_tr_b16: ~5 cycles each; tools/fillbench.hip), and a 64 x 64 wave tile needs
-// 32 of them per 32 MFMAs where the 32 x 64 tile of gemm_tn_grouped_kernel needs 24 per 16.  Stage = three
-// [64 r][128 cols] images (A columns 0..127, A columns 128..255, B) = 48 KB, three stages.
+// 256 x 128 output tiles for the grouped dW GEMM: 8 MFMA waves in 4 x 2, wave tile 64 x 64, two MFMA waves per SIMD, each
+// reading a whole stage and then issuing its 32 MFMAs.  The dW K step is bound by the transposed LDS reads
+// (ds_read_b64_tr_b16: ~5 cycles each; tools/fillbench.hip): 256 per K step and CU against 1024 MFMA cycles.  A 64 x 64 wave
+// tile needs 32 of them per 32 MFMAs where a 32 x 64 one (128 x 128 output tiles) needs 24 per 16.  Stage = three
+// [64 r][128 cols] images (A columns 0..127, A columns 128..255, B) = 48 KB, three stages.  The kernel is also closer to its
+// HBM bound than to its LDS bound: 1.87 GB in 455 us = 4.1 TB/s of the ~5.2 TB/s the chip sustains.
+// The straight K loop below overlaps by itself: the two MFMA waves of a SIMD drift apart and one's reads run under the other's
+// MFMAs.  The alternatives measured slower (128 x 64 wave tiles on 4 MFMA waves, the NT kernel's barrier-in-the-middle loop,
+// 128 x 128 output tiles) are listed in DESIGN.md section 4.
 #define TN2_STAGE 49152
 #define TN2_NST 3
-// WT (wave tile): 0 = 8 MFMA waves of 64 x 64 (4 x 2), two per SIMD, each reading a whole stage and then issuing its 32 MFMAs:
-// 256 transposed reads per K step and CU against 1024 MFMA cycles -- read-bound.  1 = 4 MFMA waves of 128 x 64 (2 x 2), one per
-// SIMD: 8 + 4 fragments per 32 MFMAs = 192 transposed reads per K step and CU (three quarters), and since a lone wave per SIMD
-// has nobody to overlap with, the reads of the next K half are in flight while the MFMAs of the current one run (the NT
-// kernel's barrier-in-the-middle loop, row fragments refilled in place).  MEASURED (round 2, same box, DG_TN_WAVETILE=1 vs 0):
-// 857 us vs 470 us -- 1.8x slower.  With the loader waves the kernel has 2 waves per SIMD, i.e. 256 registers per lane; 128
-// accumulators + 64 fragments fit on paper, but the allocator rotates the accumulators through the loop and reloads three
-// 16-byte values from scratch per K half, each a memory round trip in front of an MFMA that a single wave per SIMD cannot
-// hide.  Kept as an A/B variant; the default stays WT 0.  (The default is also closer to its HBM bound than to its LDS bound:
-// 1.87 GB in 455 us = 4.1 TB/s of the ~5.2 TB/s the chip sustains.)
-// Also tried for WT 0 (round 2, same box, removed again): the NT kernel's barrier-in-the-middle loop -- second K half requested,
-// first half multiplied, barrier, next stage's first half requested, second half multiplied, with the factored fragment
-// addresses of the WT 1 branch so that the loop has no scratch traffic -- 466 us against 445 us with the reads and MFMAs held
-// in that order by sched_barriers, 594 us with the order left to the compiler.  The straight loop below already overlaps:
-// the two MFMA waves of a SIMD drift apart by themselves and one's reads run under the other's MFMAs.
-// F8 (round 3, WT 0 only): OCP fp8 operands -- A = dY as e5m2, B = X as e4m3, the copies the fp8 forward / dX GEMMs already made of
+// F8 (round 3): OCP fp8 operands -- A = dY as e5m2, B = X as e4m3, the copies the fp8 forward / dX GEMMs already made of
 // them.  A stage is 128 rows of the contraction instead of 64 at the same 48 KB (three [128 r][128 B] images), read with
 // ds_read_b64_tr_b8 (per 16-lane group an 8-row x 16-byte-column block, lane i receiving column i's eight rows; lane 2 r + h
 // supplies row r, bytes 8 h .. 8 h + 7 -- probed with tools/tr8_probe.hip) and multiplied with ONE v_mfma_f32_16x16x128_f8f6f4
 // per 16 x 16 block: per 128 rows the same 32 transposed reads per wave as the bf16 form needs for 64, half the operand bytes from
 // HBM, 16 MFMAs instead of 32.  Swizzle of the image: physical 16-byte chunk = chunk ^ (((row >> 1) & 3) | (((row >> 5) & 1) << 2))
 // -- rows two apart share their banks (128-byte rows, 64 banks), the two 16-lane groups of a half-wave read rows 32 apart.
+// WT is always 0 (64 x 64 wave tiles): it stays a template parameter only to keep the kernel symbol that bench.py's labels name.
 template <int WT, bool F8 = false>
-__global__ __launch_bounds__(WT ? 512 : 768) void gemm_tn_grouped256_kernel(typename TnGroupOf<F8>::type gp) {
-    static_assert(!(F8 && WT), "the fp8 form exists for 64 x 64 wave tiles only");
+__global__ __launch_bounds__(768) void gemm_tn_grouped256_kernel(typename TnGroupOf<F8>::type gp) {
+    static_assert(WT == 0, "64 x 64 wave tiles only");
     constexpr int KROWS = F8 ? 128 : 64;           // rows of the contraction per stage
-    constexpr int NMW = WT ? 4 : 8;                // MFMA waves
-    constexpr int NI = WT ? 8 : 4;                 // 16-row fragments of A per wave
     __shared__ __attribute__((aligned(16))) char lds[TN2_NST * TN2_STAGE];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform -> SGPR
     const int G = gridDim.x;
@@ -936,9 +764,9 @@ __global__ __launch_bounds__(WT ? 512 : 768) void gemm_tn_grouped256_kernel(type
     }
     if (total == 0) return;
 
-    if (wave >= NMW) {
+    if (wave >= 8) {
         // ---- loader role: 48 pieces of 1 KB (4 rows x 256 B) per stage, 12 per wave: pieces 0-15 -> image A0, 16-31 -> A1, 32-47 -> B
-        const int lw = wave - NMW;
+        const int lw = wave - 8;
         const int prow = lane >> 4, slot = lane & 15;
         const char* src[12];
         int64_t step[12];
@@ -996,67 +824,35 @@ __global__ __launch_bounds__(WT ? 512 : 768) void gemm_tn_grouped256_kernel(type
         else if (npre == 2) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                              // stage 0 published
-        // Pacing experiment (DG_TN_SYNC = n > 0; default off): the workgroups of one XCD that walk the same item sequence meet every
-        // n K steps (one relaxed counter per XCD, class and epoch; bounded wait), so that concurrently running tiles stay at the
-        // same K offset and keep finding each other's operand panels in the XCD's 4 MB L2.  See the measurement in DESIGN section 4.
-        unsigned* sync_ctr = nullptr;
-        unsigned sync_expect = 0;
-        if (gp.sync_every > 0 && gp.sync && lw == 0 && (G & 7) == 0) {
-            const int cls = lo_have ? 1 : 0;
-            int cnt = 0;
-            for (int j = 0; j < (G >> 3); ++j) {
-                const int t2 = (gp.splits == 3) ? q_whole * G + 8 * (j >> 1) + 2 * (lo_x >> 1) + (j & 1) : 0;
-                const bool have = gp.splits == 3 && t2 < gp.total_tiles;
-                if ((have ? 1 : 0) == cls) ++cnt;
-            }
-            sync_expect = (unsigned)cnt;
-            sync_ctr = gp.sync + (lo_x * 2 + cls) * 64;
-        }
         for (int g = 0; g + 1 < total; ++g) {
             int issued = g + TN2_NST; if (issued > total) issued = total;
             if (issued - (g + 2) >= 1) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");   // stage g+1 landed, g+2 may fly
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();                          // publishes stage g+1; stage g's buffer is free
             if (g + TN2_NST < total) issue();
-            if (sync_ctr && g > 0 && (g % gp.sync_every) == 0 && (g / gp.sync_every) < 64) {
-                unsigned* c = sync_ctr + g / gp.sync_every;
-                if (lane == 0) {
-                    __hip_atomic_fetch_add(c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    for (int spin = 0; spin < 2000 && __hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < sync_expect; ++spin)
-                        __builtin_amdgcn_s_sleep(2);
-                }
-            }
-        }
-        if (gp.sync_every > 0 && gp.sync && lw == 0 && lane == 0) {
-            // the workgroup that finishes last zeroes the counters for the next launch
-            const unsigned prev = __hip_atomic_fetch_add(gp.sync + 1024, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (prev == (unsigned)G - 1u) {
-                for (int i = 0; i < 1025; ++i) __hip_atomic_store(gp.sync + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
         }
         return;
     }
 
     // ---- MFMA role
-    const int wp = wave >> 1, wq = wave & 1;       // WT 0: wp 0..3 (64 rows each), WT 1: wp 0..1 (128 rows = one A image each)
-    constexpr int WROWS = WT ? 128 : 64;
-    f32x4 acc[NI][4];
+    const int wp = wave >> 1, wq = wave & 1;       // wp 0..3: 64 rows each
+    f32x4 acc[4][4];
 #pragma unroll
-    for (int i = 0; i < NI; ++i)
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const int fr = lane & 15, fg = lane >> 4;
-    const int aimg = WT ? wp * 16384 : (wp >> 1) * 16384, acol = WT ? 0 : (wp & 1) * 64;
-    auto read_frags = [&](u32x4 (&fa)[NI], u32x4 (&fb)[4], const char* buf, int ks) {
+    const int aimg = (wp >> 1) * 16384, acol = (wp & 1) * 64;
+    auto read_frags = [&](u32x4 (&fa)[4], u32x4 (&fb)[4], const char* buf, int ks) {
         const int r0 = ks * 32 + fg * 8;
 #pragma unroll
-        for (int i = 0; i < NI; ++i) fa[i] = tn_frag_bf16(buf + aimg, r0, acol + i * 16, lane);
+        for (int i = 0; i < 4; ++i) fa[i] = tn_frag_bf16(buf + aimg, r0, acol + i * 16, lane);
 #pragma unroll
         for (int j = 0; j < 4; ++j) fb[j] = tn_frag_bf16(buf + 32768, r0, wq * 64 + j * 16, lane);
     };
-    auto mma_all = [&](const u32x4 (&fa)[NI], const u32x4 (&fb)[4]) {
+    auto mma_all = [&](const u32x4 (&fa)[4], const u32x4 (&fb)[4]) {
 #pragma unroll
-        for (int i = 0; i < NI; ++i)
+        for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) mma16<bf16_t>(fb[j], fa[i], acc[i][j]);
     };
@@ -1069,8 +865,8 @@ __global__ __launch_bounds__(WT ? 512 : 768) void gemm_tn_grouped256_kernel(type
     auto store_tile = [&]() {
         const auto& pr = gp.pr[cx.pi];
         if (cx.half != 2) {
-            // per wave NI x 4 accumulators of 1 KB (64 lanes x 16 B): 16 KB (WT 0) or 32 KB (WT 1: two of the tile's eight slots)
-            float* part = (float*)(gp.ws + ((size_t)cx.tile * 8 + wave * (8 / NMW)) * 16384);
+            // per wave 4 x 4 accumulators of 1 KB (64 lanes x 16 B): 16 KB
+            float* part = (float*)(gp.ws + ((size_t)cx.tile * 8 + wave) * 16384);
             unsigned* flag = (unsigned*)(gp.ws + (size_t)gp.total_tiles * 8 * 16384) + cx.tile * 8 + wave;
             // The partials move as (64 lanes x 16 B) pieces with the sc0 sc1 cache bits: system-scope write-through
             // stores and L2-bypassing loads, i.e. coherent between XCDs without any cache-wide maintenance.  (One relaxed
@@ -1078,7 +874,7 @@ __global__ __launch_bounds__(WT ? 512 : 768) void gemm_tn_grouped256_kernel(type
             char* pw = (char*)part + lane * 16;
             if (cx.half == 0) {
 #pragma unroll
-                for (int i = 0; i < NI; ++i)
+                for (int i = 0; i < 4; ++i)
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" :: "v"(pw + (i * 4 + j) * 1024), "v"(acc[i][j]) : "memory");
@@ -1094,19 +890,10 @@ __global__ __launch_bounds__(WT ? 512 : 768) void gemm_tn_grouped256_kernel(type
                                "+v"(acc[1][2]), "+v"(acc[1][3]), "+v"(acc[2][0]), "+v"(acc[2][1]), "+v"(acc[2][2]), "+v"(acc[2][3]),
                                "+v"(acc[3][0]), "+v"(acc[3][1]), "+v"(acc[3][2]), "+v"(acc[3][3])
                              :: "memory");
-                if constexpr (WT != 0) {
-                    // (the other sixteen: an asm statement takes at most 30 operands; volatile statements keep their order, so
-                    // these registers stay live and untouched through the wait above)
-                    asm volatile(""
-                                 : "+v"(acc[4][0]), "+v"(acc[4][1]), "+v"(acc[4][2]), "+v"(acc[4][3]), "+v"(acc[5][0]), "+v"(acc[5][1]),
-                                   "+v"(acc[5][2]), "+v"(acc[5][3]), "+v"(acc[6][0]), "+v"(acc[6][1]), "+v"(acc[6][2]), "+v"(acc[6][3]),
-                                   "+v"(acc[NI - 1][0]), "+v"(acc[NI - 1][1]), "+v"(acc[NI - 1][2]), "+v"(acc[NI - 1][3])
-                                 :: "memory");
-                }
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 if (lane == 0) __hip_atomic_store(flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
-                for (int i = 0; i < NI; ++i)
+                for (int i = 0; i < 4; ++i)
 #pragma unroll
                     for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
                 return;
@@ -1120,7 +907,7 @@ __global__ __launch_bounds__(WT ? 512 : 768) void gemm_tn_grouped256_kernel(type
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 #pragma unroll
-            for (int c = 0; c < NI / 2; ++c) {                 // eight 1 KB pieces at a time (32 registers)
+            for (int c = 0; c < 2; ++c) {                      // eight 1 KB pieces at a time (32 registers)
                 f32x4 t[8];
 #pragma unroll
                 for (int k = 0; k < 8; ++k) asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1" : "=v"(t[k]) : "v"(pw + (c * 8 + k) * 1024) : "memory");
@@ -1139,13 +926,13 @@ __global__ __launch_bounds__(WT ? 512 : 768) void gemm_tn_grouped256_kernel(type
         if constexpr (F8) {
             const float sab = pr.sa[0] * pr.sb[0];
 #pragma unroll
-            for (int i = 0; i < NI; ++i)
+            for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) acc[i][j] *= sab;
         }
 #pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            const int row = cx.p0 + wp * WROWS + i * 16 + fr;
+        for (int i = 0; i < 4; ++i) {
+            const int row = cx.p0 + wp * 64 + i * 16 + fr;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int col = cx.q0 + wq * 64 + j * 16 + 4 * fg;
@@ -1162,83 +949,10 @@ __global__ __launch_bounds__(WT ? 512 : 768) void gemm_tn_grouped256_kernel(type
             }
         }
     };
-    u32x4 fa0[NI], fb0[4], fa1[NI], fb1[4];
+    u32x4 fa0[4], fb0[4], fa1[4], fb1[4];
     __builtin_amdgcn_s_barrier();                                  // stage 0 published by the loaders
     int kt = 0, buf_i = 0;
-    if constexpr (WT != 0) {
-        // One MFMA wave per SIMD, nobody to overlap with: while the 32 MFMAs of a K half run, the fragments of the NEXT half are
-        // requested -- row fragment i right after its four MFMAs have been issued, into the registers they free (A: 8 live
-        // fragments instead of 16), the 4 column fragments up front.  The next stage's first half sits behind the barrier
-        // that publishes it.
-        // Fragment addresses by hand (tn_frag_bf16's arithmetic, factored): the two transposed reads of fragment I (16 columns
-        // at 16 I of a 128-column image) at K half ks of the stage at byte offset sb are
-        //     sb + img + 8192 ks + ((P0 | P1) ^ (I << 5)),   P = lane part with the swizzle's lane bits folded in,
-        // i.e. ONE v_xor with a literal per read on top of two per-lane registers per operand -- the generic form kept ~50
-        // hoisted address registers alive and pushed the kernel over its 256-register budget (690 spilled dwords).
-        typedef __attribute__((address_space(3))) char lds_char;
-        typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-        lds_char* const lbase = (lds_char*)lds;
-        const int q4 = (lane & 15) >> 2, pp = lane & 3, b0 = pp >> 1;
-        const int mswz = ((q4 << 1) | (fg & 1)) << 5;
-        const int P0 = (2048 * fg + 256 * q4 + 16 * b0 + 8 * (pp & 1)) ^ mswz;
-        const int P1 = (2048 * fg + 256 * q4 + 1024 + 16 * (b0 ^ 1) + 8 * (pp & 1)) ^ mswz;
-        const int PA0 = P0 + wp * 16384, PA1 = P1 + wp * 16384;                    // A image of this wave row
-        const int PB0 = (P0 ^ (wq << 7)) + 32768, PB1 = (P1 ^ (wq << 7)) + 32768;  // B image, fragments 4 wq + j
-        auto frag2 = [&](int a0, int a1) -> u32x4 {
-            bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(lbase + a0));
-            bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(lbase + a1));
-            return __builtin_bit_cast(u32x4, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-        };
-        // (the four stage bases pass through an empty asm once per K half: opaque to the optimiser, which otherwise hoists all
-        // 48 xor results out of the loop again and spills them)
-        int sa0, sa1, sb0, sb1;
-        auto stage_bases = [&](int sb) {
-            sa0 = PA0 + sb; sa1 = PA1 + sb; sb0 = PB0 + sb; sb1 = PB1 + sb;
-            asm volatile("" : "+v"(sa0), "+v"(sa1), "+v"(sb0), "+v"(sb1));
-        };
-        auto read_a = [&](u32x4& f, int ks, int i) { f = frag2((sa0 ^ (i << 5)) + 8192 * ks, (sa1 ^ (i << 5)) + 8192 * ks); };
-        auto read_b = [&](u32x4 (&fb)[4], int ks) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) fb[j] = frag2((sb0 ^ (j << 5)) + 8192 * ks, (sb1 ^ (j << 5)) + 8192 * ks);
-        };
-        // fb0 / fb1: column fragments of the two K halves; fa0: row fragments of the half in progress, refilled in place
-        stage_bases(0);
-#pragma unroll
-        for (int i = 0; i < NI; ++i) read_a(fa0[i], 0, i);
-        read_b(fb0, 0);
-        for (int g = 0; g < total; ++g) {
-            stage_bases(buf_i * TN2_STAGE);
-            if (++buf_i == TN2_NST) buf_i = 0;
-            read_b(fb1, 1);
-#pragma unroll
-            for (int i = 0; i < NI; ++i) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) mma16<bf16_t>(fb0[j], fa0[i], acc[i][j]);
-                __builtin_amdgcn_sched_barrier(0);         // the refill below reuses fragment i's registers: keep it behind its MFMAs
-                read_a(fa0[i], 1, i);
-            }
-            if (g + 1 < total) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // every read of stage g has returned: the loaders refill its buffer
-                __builtin_amdgcn_s_barrier();
-            }
-            // (after the last stage these reads fetch stale LDS contents that nobody uses: unconditional, so that the eight
-            // refills stay straight-line code between the MFMAs)
-            stage_bases(buf_i * TN2_STAGE);
-            read_b(fb0, 0);
-#pragma unroll
-            for (int i = 0; i < NI; ++i) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) mma16<bf16_t>(fb1[j], fa0[i], acc[i][j]);
-                __builtin_amdgcn_sched_barrier(0);
-                read_a(fa0[i], 0, i);
-            }
-            if (++kt == cx.kb - cx.ka) {
-                store_tile();
-                kt = 0;
-                next_item();
-            }
-        }
-    } else if constexpr (F8) {
+    if constexpr (F8) {
         typedef int i32x2 __attribute__((ext_vector_type(2)));
         typedef int i32x8 __attribute__((ext_vector_type(8)));
         typedef __attribute__((address_space(3))) i32x2 lds_i32x2;
@@ -1438,11 +1152,10 @@ extern "C" int dg_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb
         grid = dim3(per_x * 8, 1);
     }
     hipStream_t s = (hipStream_t)stream;
-    static const int tn_mode = [] { const char* e = getenv("DG_GEMM_TN"); return e ? atoi(e) : 0; }();   // 1 = register-staged
     // the LDS-DMA kernel owns a CU (128 KB LDS): use it when the launch fits one wave of workgroups,
     // otherwise two register-staged workgroups per CU finish sooner than a second round
     const bool one_round = (int64_t)p.n_tiles * n_splits <= dg_num_cus();
-    if (dtype == DG_BF16 && R % 64 == 0 && (tn_mode == 3 || (tn_mode == 0 && one_round)))
+    if (dtype == DG_BF16 && R % 64 == 0 && one_round)
         hipLaunchKernelGGL(gemm_tn_ws_kernel, grid, dim3(768), 0, s, p);
     else if (dtype == DG_BF16) hipLaunchKernelGGL(gemm_tn_bf16_kernel, grid, block, 0, s, p);
     else if (dtype == DG_F32X3) hipLaunchKernelGGL(gemm_tn_x3_kernel, grid, block, 0, s, p);
@@ -1451,31 +1164,24 @@ extern "C" int dg_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb
     return DG_OK;
 }
 
-#define TN_SYNC_BYTES 4128                    // 8 XCDs x 2 classes x 64 epochs of counters + the completion counter (DG_TN_SYNC)
-static int tn_tile_p() {
-    static const int v = [] { const char* e = getenv("DG_TN_TILE"); return (e && atoi(e) == 128) ? 128 : 256; }();   // output tile rows
-    return v;
-}
 static int64_t tn_group_tiles(const dg_tn_problem* problems, int n) {
     int64_t tiles = 0;
-    for (int i = 0; i < n; ++i) tiles += (int64_t)((problems[i].P + tn_tile_p() - 1) / tn_tile_p()) * ((problems[i].Q + 127) / 128);
+    for (int i = 0; i < n; ++i) tiles += (int64_t)((problems[i].P + 255) / 256) * ((problems[i].Q + 127) / 128);
     return tiles;
 }
 // split-K workspace for the largest launch group of the call: per 256 x 128 tile 8 x 16 KB of wave partials + 8 flags
 extern "C" int64_t dg_gemm_tn_grouped_workspace_bytes(const dg_tn_problem* problems, int n) {
-    if (!problems || n <= 0 || tn_tile_p() != 256) return 0;
+    if (!problems || n <= 0) return 0;
     int64_t most = 0;
     for (int base = 0; base < n; base += TN_MAX_GROUP) {
         const int64_t t = tn_group_tiles(problems + base, n - base < TN_MAX_GROUP ? n - base : TN_MAX_GROUP);
         if (t > most) most = t;
     }
-    return most * (8 * 16384 + 8 * 4) + TN_SYNC_BYTES + 16;       // + the pacing counters + the sticky error word (last 16 bytes)
+    return most * (8 * 16384 + 8 * 4) + 16;       // + the sticky error word (last 16 bytes)
 }
 
 template <typename GroupT, typename ProbT, bool F8, int MAXG>
 static int tn_grouped_launch(const dg_tn_problem* problems, int n, void* workspace, hipStream_t s) {
-    static const int split_mode = [] { const char* e = getenv("DG_TN_SPLIT"); return e ? atoi(e) : 1; }();   // 0 = never split (A/B runs)
-    const int tile_p = F8 ? 256 : tn_tile_p();
     constexpr int KROWS = F8 ? 128 : 64, ESZ = F8 ? 1 : 2;
     for (int base = 0; base < n; base += MAXG) {
         GroupT gp;
@@ -1490,7 +1196,7 @@ static int tn_grouped_launch(const dg_tn_problem* problems, int n, void* workspa
             if constexpr (F8) { t.sa = q.scale_a; t.sb = q.scale_b; }
             t.tiles_q = (q.Q + 127) / 128;
             t.tile_begin = tiles;
-            tiles += ((q.P + tile_p - 1) / tile_p) * t.tiles_q;
+            tiles += ((q.P + 255) / 256) * t.tiles_q;
             const int nk = q.R / KROWS;
             if (nk < nk_min) nk_min = nk;
             if (nk > nk_max) nk_max = nk;
@@ -1500,14 +1206,8 @@ static int tn_grouped_launch(const dg_tn_problem* problems, int n, void* workspa
         gp.splits = 1;
         gp.ws = nullptr;
         gp.err = workspace ? (unsigned*)((char*)workspace + dg_gemm_tn_grouped_workspace_bytes(problems, n) - 16) : nullptr;
-        {
-            static const int sync_every = [] { const char* e = getenv("DG_TN_SYNC"); return e ? atoi(e) : 0; }();
-            gp.sync_every = (workspace && tile_p == 256) ? sync_every : 0;
-            gp.sync = workspace ? (unsigned*)((char*)workspace + dg_gemm_tn_grouped_workspace_bytes(problems, n) - 16 - TN_SYNC_BYTES) : nullptr;
-            gp.pad_ = 0;
-        }
         const int ncu = dg_num_cus();
-        if (tile_p == 256 && workspace && split_mode && nk_min >= 2) {
+        if (workspace && nk_min >= 2) {
             // two K halves per tile when that shortens the schedule: rounds x steps per round
             const int64_t whole = (int64_t)((tiles + ncu - 1) / ncu) * nk_max;
             const int64_t halves = (int64_t)((2 * gp.tiles_pad + ncu - 1) / ncu) * ((nk_max + 1) / 2);
@@ -1515,25 +1215,19 @@ static int tn_grouped_launch(const dg_tn_problem* problems, int n, void* workspa
             // (workgroup tiles_pad + t) then waits for workgroup t, a lower-numbered one that never waits -- safe whatever part of
             // the grid is resident.  With several items per workgroup the second halves of tiles [G - tiles_pad % G, G) would sit
             // on LOWER-numbered workgroups than their producers: a deadlock as soon as fewer than G workgroups are resident.
+            // (With a CU count that is a multiple of 16 the leftover cut below is at least as short whenever cutting every tile
+            // would shorten a multi-round schedule, so the guard only decides on other CU counts.)
             if (halves < whole && 2 * gp.tiles_pad <= ncu) { gp.splits = 2; gp.ws = (char*)workspace; }
             // cut only the leftover tiles when their halves fit into one half round (see the kernel)
-            static const int lo_mode = [] { const char* e = getenv("DG_TN_LEFTOVER"); return e ? atoi(e) : 1; }();   // 0 = cut every tile (A/B runs)
             const int r = tiles % ncu;
-            if (lo_mode && tiles > ncu && ncu % 16 == 0 && r > 0 && 16 * ((r + 7) / 8) <= ncu) {
+            if (tiles > ncu && ncu % 16 == 0 && r > 0 && 16 * ((r + 7) / 8) <= ncu) {
                 const int64_t lo = (int64_t)(tiles / ncu) * nk_max + (nk_max + 1) / 2;
                 if (lo <= (gp.splits == 2 ? halves : whole)) { gp.splits = 3; gp.ws = (char*)workspace; }
             }
         }
         const int items = gp.splits == 3 ? tiles : gp.splits * gp.tiles_pad;
         const int grid = items < ncu ? items : ncu;
-        if constexpr (F8) {
-            hipLaunchKernelGGL((gemm_tn_grouped256_kernel<0, true>), dim3(grid), dim3(768), 0, s, gp);
-        } else {
-            static const int wt_mode = [] { const char* e = getenv("DG_TN_WAVETILE"); return e ? atoi(e) : 0; }();   // 1 = 4 MFMA waves of 128 x 64 (measured 1.8x SLOWER: see the kernel's WT note)
-            if (tile_p == 256 && wt_mode) hipLaunchKernelGGL((gemm_tn_grouped256_kernel<1, false>), dim3(grid), dim3(512), 0, s, gp);
-            else if (tile_p == 256) hipLaunchKernelGGL((gemm_tn_grouped256_kernel<0, false>), dim3(grid), dim3(768), 0, s, gp);
-            else hipLaunchKernelGGL(gemm_tn_grouped_kernel, dim3(tiles < ncu ? tiles : ncu), dim3(768), 0, s, gp);
-        }
+        hipLaunchKernelGGL((gemm_tn_grouped256_kernel<0, F8>), dim3(grid), dim3(768), 0, s, gp);
         DG_LAUNCH_CHECK();
     }
     return DG_OK;
@@ -1555,7 +1249,6 @@ extern "C" int dg_gemm_tn_grouped(const dg_tn_problem* problems, int n, int dtyp
         if (f8 && (!q.scale_a || !q.scale_b)) return DG_ERR_ARG;
     }
     if (workspace && (!dg_aligned16(workspace) || workspace_bytes < dg_gemm_tn_grouped_workspace_bytes(problems, n))) return DG_ERR_ARG;
-    if (f8 && tn_tile_p() != 256) return DG_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     if (f8) return tn_grouped_launch<TnGroup8, TnProblem8, true, TN_MAX_GROUP8>(problems, n, workspace, s);
     return tn_grouped_launch<TnGroup, TnProblem, false, TN_MAX_GROUP>(problems, n, workspace, s);

@@ -2,7 +2,6 @@
 // and gemm_fp8.hip (fp8 instantiations: one translation unit each so that they compile in parallel).
 #pragma once
 #include "common.h"
-#include <stdlib.h>
 #include <type_traits>
 
 #define BM 128
@@ -80,10 +79,8 @@ struct NtParams {
     int tiles_n, n_tiles;
     int vec_ok, mask_vec_ok;
     unsigned long long* stamps;   // diagnostic build aid: per-workgroup s_memtime stamps (NULL in production)
-    int dbg;      // ablation only (DG_GEMM_DBG): 1 = no operand loads after the first stage, 2 = no LDS reads / MFMA, 3 = no stores, 4 = 1 + 3
     const float* scale_a; const float* scale_b;   // fp8 operands: per-tensor dequantisation factors (device scalars), acc *= sa * sb
     int warm_b;                   // touch the B operand's lines from the idle MFMA waves before the first barrier (weights cold inside the step)
-    int res_prefetch;             // EPI 3 / 7: loader waves touch the residual tile ahead of the epilogue (DG_NT_RESPF, default 0: measured slower)
     // EPI 8: the output is ALSO written as e4m3 (the next GEMM's fp8 operand) with delayed per-tensor scaling
     unsigned char* q8; int64_t ldq8;          // [M][ldq8] bytes
     int q8_only;                              // EPI 8 / 9: C is not written (nobody reads the bf16 form: fp8 consumers only)
@@ -113,7 +110,7 @@ __device__ __forceinline__ float dpp_f32(float x) {
 // makes N = 384 / 1152 / 1536 an exact number of rounds on 256 CUs at M = 16384 (256 / 768 / 1024 tiles; the square tile needs
 // 384 = 1.5 rounds for N = 384) and amortises the per-tile epilogue and barrier costs over 1.5x the MFMA work.
 // EPI: which epilogue options exist at compile time.  0 = all of them behind run-time flags (any combination, plus the
-// DG_GEMM_DBG ablations and s_memtime stamps); 1 = plain store; 2 = bias + ReLU + sign-bit emission (Linear+ReLU of
+// s_memtime stamps); 1 = plain store; 2 = bias + ReLU + sign-bit emission (Linear+ReLU of
 // FeedForward); 3 = bias + dropout + residual (proj / second FFN Linear); 4 = sign-bit mask (dX of the second FFN Linear);
 // 5 = bias only (lm_head: 1.65 GB of fp32 logits at the GPT-2 vocabulary); 6 = 4 + column sums; 7 = bias + residual (3 at dropout 0:
 // eval mode and p = 0 training ran the generic form, 2.64 instead of 2.54 ms per step); 8 = 2 + an e4m3 copy of the output with
@@ -144,7 +141,6 @@ __global__ __launch_bounds__(768) void gemm_nt_ws_kernel(NtParams p) {
     constexpr bool QOUT = EPI == 8 || EPI == 9;                  // fp8 copy of the output (8: e4m3 behind the ReLU, 9: e5m2, signed)
     constexpr float QMAX = EPI == 9 ? 57344.f : 448.f;    // interior tiles only: the host picks EPI 6 only when every tile is one
     unsigned char* const e_bout = (GEN || EPI == 2 || EPI == 8) ? p.bits_out : nullptr;
-    const int e_dbg = GEN ? p.dbg : 0;
     unsigned long long* const e_stamps = GEN ? p.stamps : nullptr;
     constexpr int BNW = NJ * 32;                               // tile width
     constexpr int STAGE = 16384 + BNW * 128;                   // A [128][128 B] + B [BNW][128 B]
@@ -163,37 +159,11 @@ __global__ __launch_bounds__(768) void gemm_nt_ws_kernel(NtParams p) {
     const int lw = wave - 8;
     const char* srcA[PPA];
     const char* srcB[PPB];
-    // Residual prefetch (EPI 3 / 7): the epilogue of these GEMMs reads a 128 x BNW fp32 tile of the residual stream, from HBM,
-    // with the matrix cores idle.  The loader waves touch one dword of each of its 128-byte lines RES_LEAD K steps before the
-    // tile's last stage is issued, so that the lines are on their way into L2 while the K loop still runs.  The touches are
-    // issued in FRONT of that stage's LDS-DMA pieces: every counted vmcnt wait below stays correct (loads return in order).
-    // MEASURED (round 2, same box, DG_NT_RESPF=1 vs 0): proj 18.0 vs 16.7 us, second FFN Linear 30.0 vs 27.5 us, step 2.540 vs
-    // 2.507 ms -- SLOWER.  The epilogue's residual reads are not exposed latency; the touches are 768 more requests per tile on a
-    // memory path that is the bound already.  Kept as an A/B switch, default off.
-    constexpr bool RESPF = (EPI == 3 || EPI == 7) && (BNW % 32 == 0);
-    constexpr int RES_LEAD = 3;
-    constexpr int RES_LINES = 32 * (BNW / 32);                 // lines of one loader wave's 32 rows
-    constexpr int RES_NT = (RES_LINES + 63) / 64;
-    int cur_m0 = 0, cur_n0 = 0;
-    float res_touch[RESPF ? RES_NT : 1];
-    auto touch_residual = [&]() {
-        if constexpr (RESPF) {
-            if (!(p.vec_ok && p.residual && cur_m0 + BM <= p.M && cur_n0 + BNW <= p.N)) return;
-#pragma unroll
-            for (int j = 0; j < RES_NT; ++j) {
-                const int idx = j * 64 + lane;
-                if (idx < RES_LINES) {
-                    const int row = idx / (BNW / 32), line = idx % (BNW / 32);
-                    const float* a = p.residual + (int64_t)(cur_m0 + 32 * lw + row) * p.ldr + cur_n0 + 32 * line;
-                    asm volatile("global_load_dword %0, %1, off" : "=v"(res_touch[j]) : "v"(a) : "memory");
-                }
-            }
-        }
-    };
+    // (The loader waves do not prefetch the residual tile of EPI 3 / 7: the epilogue's residual reads are not exposed latency, and
+    // the extra requests on the memory path measured slower -- DESIGN.md section 4.)
     auto set_src = [&](int ti) {
         const int tile = dg_xcd_remap((int)blockIdx.x + ti * G, p.n_tiles);
         const int m0 = (tile / p.tiles_n) * BM, n0 = (tile % p.tiles_n) * BNW;
-        cur_m0 = m0; cur_n0 = n0;
 #pragma unroll
         for (int i = 0; i < PPA; ++i) {
             int gm = m0 + (PPA * lw + i) * 8 + prow; if (gm > p.M - 1) gm = p.M - 1;
@@ -209,15 +179,12 @@ __global__ __launch_bounds__(768) void gemm_nt_ws_kernel(NtParams p) {
     auto issue = [&](int g) {
         char* base = lds + (g & (GL_NST - 1)) * STAGE;
         const int64_t koff = (int64_t)iss_kt * 128;
-        if (RESPF && p.res_prefetch && iss_kt == (nk > RES_LEAD ? nk - RES_LEAD : 0)) touch_residual();
-        if (!((e_dbg == 1 || e_dbg == 4) && g > 0)) {           // ablation: no operand traffic after the first stage
 #pragma unroll
-            for (int i = 0; i < PPA; ++i)
-                __builtin_amdgcn_global_load_lds((gptr_t)(srcA[i] + koff), (lptr_t)(base + (PPA * lw + i) * 1024), 16, 0, 0);
+        for (int i = 0; i < PPA; ++i)
+            __builtin_amdgcn_global_load_lds((gptr_t)(srcA[i] + koff), (lptr_t)(base + (PPA * lw + i) * 1024), 16, 0, 0);
 #pragma unroll
-            for (int i = 0; i < PPB; ++i)
-                __builtin_amdgcn_global_load_lds((gptr_t)(srcB[i] + koff), (lptr_t)(base + 16384 + (PPB * lw + i) * 1024), 16, 0, 0);
-        }
+        for (int i = 0; i < PPB; ++i)
+            __builtin_amdgcn_global_load_lds((gptr_t)(srcB[i] + koff), (lptr_t)(base + 16384 + (PPB * lw + i) * 1024), 16, 0, 0);
         if (++iss_kt == nk) { iss_kt = 0; if (++iss_tile < my_tiles) set_src(iss_tile); }
     };
     if (loader) {
@@ -235,12 +202,6 @@ __global__ __launch_bounds__(768) void gemm_nt_ws_kernel(NtParams p) {
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();                          // publishes stage g+1; stage g-1's buffer is free
             if (g + GL_NST - 1 < total) issue(g + GL_NST - 1);
-        }
-        if constexpr (RESPF) {
-            // the touch registers stay reserved until every touch has returned (the compiler knows nothing of the loads in flight)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-            for (int j = 0; j < RES_NT; ++j) asm volatile("" :: "v"(res_touch[j]));
         }
         return;
     }
@@ -413,7 +374,6 @@ __global__ __launch_bounds__(768) void gemm_nt_ws_kernel(NtParams p) {
                 acc[i][2 * q] = (f32x4){0.f, 0.f, 0.f, 0.f};
                 acc[i][2 * q + 1] = (f32x4){0.f, 0.f, 0.f, 0.f};
                 if (row >= p.M || col >= p.N) continue;
-                if (e_dbg >= 3 && v[0] != 12345.678f) continue;      // ablation: no stores
                 if constexpr (SCALED) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] *= e_sab;
@@ -634,7 +594,7 @@ __global__ __launch_bounds__(768) void gemm_nt_ws_kernel(NtParams p) {
     };
     stamp();
     // ---- MFMA role
-    // L2 warm-up of the weight operand (round 3; p.warm_b, DG_NT_WARM): inside the training step B -- a bf16 shadow or W^T the
+    // L2 warm-up of the weight operand (round 3; p.warm_b): inside the training step B -- a bf16 shadow or W^T the
     // optimizer step rewrote a millisecond ago -- is cold, and the tiles of an XCD all miss on its lines.  These waves idle until
     // the first barrier: each touches one 128-byte line of B (workgroup j of the XCD: lines j + 32 k), all requests in flight at once.
     if (p.warm_b) {
@@ -674,12 +634,13 @@ __global__ __launch_bounds__(768) void gemm_nt_ws_kernel(NtParams p) {
                 read_frags(fa0, fb0, lds + ((g + 1) & (GL_NST - 1)) * STAGE, 0);
             }
         } else {
-            if (e_dbg != 2) { read_frags(fa1, fb1, buf, 1); mma_all(fa0, fb0); }
+            read_frags(fa1, fb1, buf, 1);
+            mma_all(fa0, fb0);
             if (g + 1 < total) {
                 __builtin_amdgcn_s_barrier();                          // stage g+1 is visible; nothing to wait for here
-                if (e_dbg != 2) read_frags(fa0, fb0, lds + ((g + 1) & (GL_NST - 1)) * STAGE, 0);
+                read_frags(fa0, fb0, lds + ((g + 1) & (GL_NST - 1)) * STAGE, 0);
             }
-            if (e_dbg != 2) mma_all(fa1, fb1);
+            mma_all(fa1, fb1);
         }
         stamp();
         if (++kt == nk) { finish_tile(tile_i); kt = 0; ++tile_i; stamp(); }
