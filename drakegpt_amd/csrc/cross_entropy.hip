@@ -296,7 +296,10 @@ __global__ __launch_bounds__(CE_BLOCK, 8) void cross_entropy_row_bf16_kernel(con
     s = red[0];
 #pragma unroll
     for (int k = 1; k < 16; ++k) s += red[k];             // fixed order
-    if (tid == 0) loss_rows[row] = mx + logf(s) - xt;
+    // (mx - xt first: exact for bf16 logits within 2^16 of each other, so a target at the row maximum gives logf(s) itself.  mx + logf(s)
+    // rounds at the size of mx -- 2^-24 |mx| = 1.2e-4 at |mx| = 2000 -- on top of the 2^-24 |mx| that the rounding of mx log2(e) already
+    // costs through ce_exp_fast: tests/test_gpu_conditioning.py, logit range 2000)
+    if (tid == 0) loss_rows[row] = (mx - xt) + logf(s);
     if (dlogits) {
         bf16_t* d = dlogits + (int64_t)row * ldd;
         const float inv = 1.f / s;

@@ -87,6 +87,10 @@ def test_gemm_nt_fp8_plain(dev, a_fmt, out_dtype, M, N, K):
     torch.cuda.synchronize()
     assert out.dtype == out_dtype
     assert rel(out, ref) < (4e-5 if out_dtype == torch.float32 else 3e-3), rel(out, ref)
+    if out_dtype == torch.bfloat16:
+        # every element: one bf16 rounding of fp64 on the dequantised operands plus the accumulation envelope (oracle/parity.py)
+        from oracle import parity as P
+        P.assert_within_rounding(out, ref, P.gemm_envelope(A, B, K, scale=(sa.double() * sb.double()).item()), 1, "fp8 gemm, bf16 out")
 
 
 def test_gemm_nt_fp8_asymmetric_identity(dev):
@@ -108,6 +112,7 @@ def test_gemm_nt_fp8_asymmetric_identity(dev):
 def test_gemm_nt_fp8_epilogues(dev, M, N, K):
     """the epilogue forms the fp8 step uses: bias + ReLU + sign-bit emission (FeedForward's first Linear), the sign-bit-masked
     dX with column sums (its backward, e5m2 gradients), bias + dropout + residual and bias + residual (proj / second Linear)"""
+    from oracle import parity as P
     from oracle import rng_ref
     from drakegpt_amd import ops
     g = torch.Generator().manual_seed(K)
@@ -119,6 +124,7 @@ def test_gemm_nt_fp8_epilogues(dev, M, N, K):
     resid = torch.randn(M, N, generator=g)
     sa, sb = torch.tensor([0.01]), torch.tensor([0.02])
     d = lambda t: t.to(dev)
+    ss = (sa.double() * sb.double()).item()                  # the fp32 scales as the kernel reads them
     acc = (A.double() @ B.double().T) * (0.01 * 0.02)
     # bias + ReLU + sign bits, then consume the bits in the dX form
     sup = ops.gemm_nt_sign_bits_supported(torch.bfloat16, N, K, in_dtype=E4) and ops.gemm_nt_sign_bits_supported(torch.bfloat16, N, K, in_dtype=E5)
@@ -128,6 +134,9 @@ def test_gemm_nt_fp8_epilogues(dev, M, N, K):
         f = ops.gemm_nt(d(A), d(B), torch.bfloat16, bias=d(bias), relu=True, sign_bits_out=bits, scale_a=d(sa), scale_b=d(sb))
         ref_f = torch.relu(acc + bias.double())
         assert rel(f, ref_f) < 3e-3
+        env = P.gemm_envelope(A, B, K, bias, scale=ss)
+        decided = P.mask_margin(acc + bias.double(), env)
+        P.assert_within_rounding(f, ref_f, env, 1, "fp8 bias + relu + sign bits out", where=decided)
         # dX of the Linear that consumed f ... here just the masking semantics: out[m, n] = (G2 B2^T)[m, n] where f[m, n] > 0
         G2 = _rand_fp8((M, K), E5, g, 10.0)
         B2 = _rand_fp8((N, K), E4, g, 1.0)
@@ -136,6 +145,7 @@ def test_gemm_nt_fp8_epilogues(dev, M, N, K):
         out = ops.gemm_nt(d(G2), d(B2), torch.bfloat16, sign_bits=bits, scale_a=d(sa), scale_b=d(sb), colsum_part=cs if rows else None)
         ref = (G2.double() @ B2.double().T) * (0.01 * 0.02) * (f.double().cpu() > 0)
         assert rel(out, ref) < 3e-3
+        P.assert_within_rounding(out, ref, P.gemm_envelope(G2, B2, K, scale=ss) * (f.double().cpu() > 0), 1, "fp8 sign bits in")
         if rows:
             assert rel(cs.sum(0), ref.sum(0)) < 1e-4
     # bias + dropout + residual (fp32 out) with the shared keep-mask, and bias + residual
@@ -148,6 +158,7 @@ def test_gemm_nt_fp8_epilogues(dev, M, N, K):
     # e5m2 gradient x e4m3 W^T, plain bf16 out (dX of proj / QKV / first FFN Linear)
     dx = ops.gemm_nt(d(G), d(Bt), torch.bfloat16, scale_a=d(sa), scale_b=d(sb))
     assert rel(dx, (G.double() @ Bt.double().T) * (0.01 * 0.02)) < 3e-3
+    P.assert_within_rounding(dx, (G.double() @ Bt.double().T) * ss, P.gemm_envelope(G, Bt, N, scale=ss), 1, "fp8 dX, bf16 out")
 
 
 @pytest.mark.parametrize("M,N,K", [(4096, 1536, 256), (8192, 1024, 384)])

@@ -1,0 +1,262 @@
+"""oracle/parity.py on the CPU: the derived bounds hold for the reference's own rounding model, and every localized check
+fails on a planted defect that the whole-tensor ratio at the suite's old tolerance lets through.
+
+The "kernel output" here is always an emulation in torch on the host (fp64 arithmetic with bf16 roundings at the kernels'
+documented rounding points, or fp32 torch ops where a kernel accumulates in fp32); defects are planted in those tensors."""
+import pytest
+import torch
+import torch.nn.functional as F
+
+from oracle import parity as P
+from oracle import rng_ref
+
+bf = torch.bfloat16
+
+# the bf16 attention cases of tests/test_gpu_ops.py::test_attention / test_attention_more_shapes, of tests/test_gpu_gpt2_parity.py
+# (B * NH cut to 1 .. 2 where T >= 640; 14 x 32 heads cut to 2 x 4) and of tests/test_gpu_conditioning.py (T = 256 form)
+ATTN_CASES = [(2, 8, 4, 8, 0.0), (3, 37, 2, 16, 0.1), (2, 256, 3, 64, 0.2), (1, 1, 1, 32, 0.0), (2, 130, 2, 64, 0.0), (3, 100, 2, 64, 0.3),
+              (2, 255, 2, 64, 0.1), (2, 256, 2, 128, 0.1), (1, 1024, 1, 64, 0.1), (1, 640, 1, 64, 0.0), (1, 1000, 1, 64, 0.1), (2, 256, 4, 64, 0.1)]
+TOL_FWD, TOL_BWD = 8e-3, 2e-2                  # the suite's whole-tensor bounds (tests/test_gpu_ops.py, tests/test_gpu_gpt2_parity.py)
+
+
+def _attn_inputs(B, T, NH, H, p, seed=None):
+    g = torch.Generator().manual_seed(T * 7 + H if seed is None else seed)
+    C = NH * H
+    qkv = torch.randn(B * T, 3 * C, generator=g).to(bf)
+    dout = torch.randn(B * T, C, generator=g).to(bf)
+    keep = None
+    if p > 0:
+        keep = torch.from_numpy(rng_ref.keep_mask(77, 3, 4, p, B * NH * T * T).reshape(B, NH, T, T)).double()
+    return qkv, dout, keep
+
+
+@pytest.mark.parametrize("B,T,NH,H,p", ATTN_CASES)
+def test_attention_rounding_model_stays_inside_its_bounds(B, T, NH, H, p):
+    qkv, dout, keep = _attn_inputs(B, T, NH, H, p)
+    ref = P.attention_fp64(qkv, dout, B, T, NH, H, keep, p)
+    mod = P.attention_fp64(qkv, dout, B, T, NH, H, keep, p, model=True)
+    P.assert_within_rounding(mod["out"], ref["out"], P.attention_fwd_envelope(ref), 1, "model forward")
+    P.assert_rowwise(mod["out"], ref["out"], H, TOL_FWD, "model forward", T)
+    # the hand-written backward is the autograd gradient of the hand-written forward
+    qd = qkv.double().requires_grad_(True)
+    q, k, v = qd.view(B, T, 3, NH, H).permute(2, 0, 3, 1, 4)
+    w = (q @ k.transpose(-2, -1) * H ** -0.5).masked_fill(~torch.tril(torch.ones(T, T, dtype=torch.bool)), float("-inf")).softmax(-1)
+    if keep is not None:
+        w = w * keep / (1 - p)
+    (w @ v).permute(0, 2, 1, 3).reshape(B * T, NH * H).backward(dout.double())
+    assert P.rel(ref["dqkv"], qd.grad) < 1e-12
+    # the model's worst (row, head) is what the GPU tests multiply by BWD_MARGIN.  It is a rounding-sized number: the model
+    # as a whole meets the whole-tensor bound the project already uses for the backward, and its worst group stays within
+    # the few bf16 roundings that enter one gradient row (a (row, head) of H = 8 averages over 8 elements only)
+    bounds = P.attention_bwd_bounds(ref, mod, H)
+    assert P.rel(mod["dqkv"], ref["dqkv"]) < TOL_BWD
+    print(f"[parity-model] {(B, T, NH, H, p)}: fwd {P.rowwise_rel(mod['out'], ref['out'], H).max().item():.2e} "
+          + " ".join(f"{n} {b / P.BWD_MARGIN:.2e}" for n, b in bounds.items()))
+    pos = P.attention_bwd_bounds_by_position(ref, mod, B, T, NH, H)
+    for n, b in bounds.items():
+        assert 0 <= b / P.BWD_MARGIN < 0.5, (n, b)          # (dq: the first query rows, see attention_bwd_bounds_by_position)
+        assert pos[n].max().item() <= b and (T < 128 or pos[n].median().item() < TOL_BWD)
+        if b > 0:
+            P.assert_rowwise(mod[n], ref[n], H, b, n, T)
+            P.assert_rowwise_each(mod[n], ref[n], H, pos[n], n, T)
+
+
+@pytest.mark.parametrize("B,T,NH,H,p", [(2, 256, 3, 64, 0.2), (1, 513, 1, 96, 0.2), (2, 300, 2, 128, 0.0), (1, 1024, 1, 64, 0.1)])
+def test_attention_fp32_model_meets_the_fp32_tolerances(B, T, NH, H, p):
+    """the fp32 kernels' counterpart (torch float32 arithmetic): every (row, head) at the suite's fp32 tolerances, except where dq
+    cancels (the first query rows: delta from an fp32-rounded output against a denominator at its floor), which is what the
+    position-resolved bound is for"""
+    qkv, dout, keep = _attn_inputs(B, T, NH, H, p)
+    qkv, dout = qkv.float() + 0.001, dout.float()               # (not bf16-representable: fp32 operands)
+    ref = P.attention_fp64(qkv, dout, B, T, NH, H, keep, p)
+    mod = P.attention_fp64(qkv, dout, B, T, NH, H, keep, p, model="fp32")
+    P.assert_rowwise(mod["out"], ref["out"], H, 2e-5, "fp32 model forward", T)
+    pos = P.attention_bwd_bounds_by_position(ref, mod, B, T, NH, H, at_least=3e-5)
+    for n in ("dq", "dk", "dv"):
+        e = P.rowwise_rel(mod[n], ref[n], H).view(B, T, NH)
+        assert e[:, 64:].max().item() < 3e-5 and pos[n].view(B, T, NH)[:, 64 + P.BWD_WINDOW:].max().item() == 3e-5, n
+        P.assert_rowwise_each(mod[n], ref[n], H, pos[n], n, T)
+
+
+def _conditioning():
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location("_dg_conditioning", os.path.join(os.path.dirname(__file__), "test_gpu_conditioning.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+@pytest.mark.parametrize("kind,T,p", [("rising", 256, 0.0), ("rising", 1024, 0.1), ("falling", 256, 0.1), ("falling", 1024, 0.0), ("onehot", 256, 0.0),
+                                      ("uniform", 256, 0.1), ("same_keys", 256, 0.0), ("randn", 8, 0.9), ("randn", 64, 0.9)])
+def test_attention_rounding_model_on_structured_operands(kind, T, p):
+    """the operands of tests/test_gpu_conditioning.py (B * NH = 1 at T = 1024): the model stays inside the forward envelope, finite
+    everywhere, and the position-resolved backward bounds it yields are finite"""
+    cond = _conditioning()
+    assert (kind, T, p) in cond.ATTN_KINDS
+    B, NH, H = (4, 4, 64) if T <= 64 else (1, 1 if T == 1024 else 2, 64)
+    g = torch.Generator().manual_seed(T + len(kind))
+    q, k, v = cond._attn_operands(kind, B, T, NH, H, g)
+    qkv = torch.stack([q, k, v], 2).reshape(B * T, 3 * NH * H).to(bf)
+    dout = torch.randn(B * T, NH * H, generator=g).to(bf)
+    keep = torch.from_numpy(rng_ref.keep_mask(5, 2, 8, p, B * NH * T * T).reshape(B, NH, T, T)).double() if p > 0 else None
+    ref = P.attention_fp64(qkv, dout, B, T, NH, H, keep, p)
+    mod = P.attention_fp64(qkv, dout, B, T, NH, H, keep, p, model=True)
+    P.assert_within_rounding(mod["out"], ref["out"], P.attention_fwd_envelope(ref), 1, f"{kind} model forward")
+    floors = {n: P.structured_floor(ref, n, H) for n in ("dq", "dk", "dv")}
+    bounds = P.attention_bwd_bounds_by_position(ref, mod, B, T, NH, H, at_least=3e-5, floors=floors)
+    for n in ("dq", "dk", "dv"):
+        # (the bound means something: see the comment at the same assertion in tests/test_gpu_conditioning.py)
+        assert torch.isfinite(mod[n]).all() and bounds[n].max().item() < 10 and (n == "dq" or bounds[n].median().item() < 0.1), (n, bounds[n].max().item())
+        P.assert_rowwise_each(mod[n], ref[n], H, bounds[n], n, T, floor=floors[n])
+
+
+def _gemm_case(M=40000, N=192, K=128):
+    g = torch.Generator().manual_seed(1)
+    A = torch.randn(M, K, generator=g).to(bf)
+    B = torch.randn(N, K, generator=g).to(bf)
+    bias = torch.randn(N, generator=g)
+    resid = torch.randn(M, N, generator=g)
+    return A, B, bias, resid
+
+
+@pytest.mark.parametrize("M,N,K", [(320, 200, 128), (300, 384, 128), (1100, 1152, 192), (256, 1536, 128), (40000, 192, 128)])
+def test_gemm_envelope_holds_for_fp32_accumulation(M, N, K):
+    """bf16 operands, fp32 accumulation (torch's fp32 matmul: another summation order than the MFMA's, the same bound), bias +
+    ReLU and bias + dropout + residual, rounded once to bf16"""
+    A, B, bias, resid = _gemm_case(M, N, K)
+    acc = A.double() @ B.double().T + bias.double()
+    env = P.gemm_envelope(A, B, K, bias)
+    got = (A.float() @ B.float().T + bias).clamp_min(0).to(bf)
+    decided = P.mask_margin(acc, env)
+    P.assert_within_rounding(got, acc.clamp_min(0), env, 1, "bias + relu", where=decided)
+    keep = torch.from_numpy(rng_ref.keep_mask(1234, 5, 9, 0.25, M * N).reshape(M, N)).double()
+    got = ((A.float() @ B.float().T + bias) * keep.float() * (1 / 0.75) + resid).to(bf)
+    env = P.gemm_envelope(A, B, K, bias, resid, keep_scale=keep / 0.75)
+    P.assert_within_rounding(got, acc * keep / 0.75 + resid.double(), env, 1, "bias + dropout + residual")
+
+
+@pytest.mark.parametrize("C", [32, 384, 1024, 100])
+def test_single_rounding_envelopes(C):
+    g = torch.Generator().manual_seed(C)
+    x = torch.randn(517, C, generator=g) * 2 + 0.5
+    w, b = torch.randn(C, generator=g), torch.randn(C, generator=g)
+    ref = F.layer_norm(x.double(), (C,), w.double(), b.double(), 1e-5)
+    P.assert_within_rounding(F.layer_norm(x, (C,), w, b, 1e-5).to(bf), ref, P.single_rounding_envelope(ref, C), 1, "layernorm")
+    V = C
+    logits = torch.randn(64, V, generator=g) * 3
+    tgt = torch.randint(0, V, (64,), generator=g)
+    gref = (torch.softmax(logits.double(), 1) - F.one_hot(tgt, V)) / 64
+    got = ((torch.softmax(logits, 1) - F.one_hot(tgt, V)) / 64).to(bf)
+    P.assert_within_rounding(got, gref, P.single_rounding_envelope(gref, V), 1, "cross entropy gradient")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# planted defects
+# ---------------------------------------------------------------------------------------------------------------------
+def _subjects():
+    """name -> (emulated kernel output, fp64 reference, new check, old whole-tensor tolerance, elements per group)"""
+    out = {}
+    # attention: the (14, 256, 32, 64) case of the long-sequence tests
+    B, T, NH, H, p = 14, 256, 32, 64, 0.1
+    qkv, dout, keep = _attn_inputs(B, T, NH, H, p)
+    ref = P.attention_fp64(qkv, dout, B, T, NH, H, keep, p)
+    mod = P.attention_fp64(qkv, dout, B, T, NH, H, keep, p, model=True)
+    env = P.attention_fwd_envelope(ref)
+
+    def fwd_check(x):
+        P.assert_within_rounding(x, ref["out"], env, 1, "out")
+        P.assert_rowwise(x, ref["out"], H, TOL_FWD, "out", T)
+    out["attention forward"] = (mod["out"], ref["out"], fwd_check, TOL_FWD, H)
+    bounds = P.attention_bwd_bounds_by_position(ref, mod, B, T, NH, H)
+
+    def bwd_check(x):
+        for i, n in enumerate(("dq", "dk", "dv")):
+            P.assert_rowwise_each(x.view(B * T, 3, NH * H)[:, i], ref[n], H, bounds[n], n, T)
+    out["attention backward"] = (mod["dqkv"], ref["dqkv"], bwd_check, TOL_BWD, H)
+    # bf16-output GEMM, bias + ReLU, 40000 x 192 (the many-tiles-per-workgroup case of test_gemm_nt_epilogue)
+    A, Bm, bias, _ = _gemm_case()
+    acc = A.double() @ Bm.double().T + bias.double()
+    genv = P.gemm_envelope(A, Bm, 128, bias)
+    decided = P.mask_margin(acc, genv)
+    out["gemm bf16 out"] = ((A.float() @ Bm.float().T + bias).clamp_min(0).to(bf).double(), acc.clamp_min(0),
+                            lambda x: P.assert_within_rounding(x, acc.clamp_min(0), genv, 1, "gemm", where=decided), 6e-3, 32)
+    # LayerNorm bf16 output (517 x 2048, the widest case of test_layernorm); the defects are one 16-byte chunk wide
+    g = torch.Generator().manual_seed(2048)
+    x = torch.randn(517, 2048, generator=g) * 2 + 0.5
+    w, b = torch.randn(2048, generator=g), torch.randn(2048, generator=g)
+    lref = F.layer_norm(x.double(), (2048,), w.double(), b.double(), 1e-5)
+    lenv = P.single_rounding_envelope(lref, 2048)
+    out["layernorm bf16 out"] = (F.layer_norm(x, (2048,), w, b, 1e-5).to(bf).double(), lref,
+                                 lambda y: P.assert_within_rounding(y, lref, lenv, 1, "layernorm"), 4e-3, 8)
+    return out
+
+
+_SUBJECTS = {}
+# the one pair that the old check does notice at the size of the test it is taken from (ratio 4.3e-3 against 4e-3: two
+# chunks' worth of difference in 1.06 M elements on top of 2.2e-3 of bf16 rounding)
+OLD_CHECK_SEES_IT = {("layernorm bf16 out", "chunk_from_neighbour")}
+
+
+def _subject(name):
+    if not _SUBJECTS:
+        _SUBJECTS.update(_subjects())
+    return _SUBJECTS[name]
+
+
+@pytest.mark.parametrize("third", [0, 1, 2])
+@pytest.mark.parametrize("defect", P.DEFECTS)
+def test_planted_defect_in_attention_backward(defect, third):
+    _planted("attention backward", defect, third)
+
+
+@pytest.mark.parametrize("defect", P.DEFECTS)
+@pytest.mark.parametrize("name", ["attention forward", "gemm bf16 out", "layernorm bf16 out"])
+def test_planted_defect_is_caught_by_the_new_check_and_missed_by_the_old(name, defect):
+    _planted(name, defect)
+
+
+def _planted(name, defect, third=1):
+    got, ref, check, old_tol, group = _subject(name)
+    check(got)                                              # the undamaged emulation passes
+    assert P.rel(got, ref) < old_tol
+    if name == "attention backward":
+        # plant in one third: the other two, correct, must not hide it
+        C = got.shape[1] // 3
+        bad = got.clone()
+        bad[:, third * C:(third + 1) * C] = P.plant(got[:, third * C:(third + 1) * C], defect, group)
+    else:
+        bad = P.plant(got, defect, group)
+    assert not torch.equal(bad, got)
+    with pytest.raises(AssertionError, match="tile"):
+        check(bad)
+    # the table of the issue as a test: the whole-tensor ratio at the old tolerance does not see it
+    if (name, defect) not in OLD_CHECK_SEES_IT:
+        assert P.rel(bad, ref) < old_tol, (name, defect, P.rel(bad, ref))
+
+
+def test_rowwise_rel_floors_tiny_rows_and_reports_the_worst_group():
+    ref = torch.ones(64, 128, dtype=torch.float64)
+    ref[5] *= 1e-6                                          # a legitimately tiny row
+    got = ref.clone()
+    got[5, :64] += 1e-6                                     # 100 % of itself, nothing at the tensor's scale
+    assert P.rowwise_rel(got, ref, 64).max().item() < 1e-5
+    got[40, 64:] *= 1.5
+    e = P.rowwise_rel(got, ref, 64)
+    assert int(e.argmax()) == 81 and abs(e.max().item() - 0.5) < 1e-12
+    with pytest.raises(AssertionError, match=r"row 40.*head 1, 32-row tile 1 \(row 8 of it\)"):
+        P.assert_rowwise(got, ref, 64, 1e-2, "x")
+    got[40, 64] = float("nan")
+    assert P.rowwise_rel(got, ref, 64).max().item() == float("inf")
+
+
+def test_assert_within_rounding_counts_and_locates():
+    ref = torch.linspace(1, 2, 64 * 96, dtype=torch.float64).reshape(64, 96)
+    P.assert_within_rounding(P.rb(ref), ref, 0.0, 1, "rounded")           # one round-to-nearest is inside one ulp, no envelope
+    got = P.rb(ref)
+    got[33, 72:80] += 0.1
+    with pytest.raises(AssertionError, match=r"8 of 6144 elements.*tile \(1, 2\), 8-element chunk 9 of row 33"):
+        P.assert_within_rounding(got, ref, 0.0, 1, "x")
+    got[0, 0] = float("inf")
+    with pytest.raises(AssertionError, match="9 of 6144"):
+        P.assert_within_rounding(got, ref, 0.0, 1, "x")
