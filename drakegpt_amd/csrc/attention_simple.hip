@@ -230,6 +230,75 @@ extern "C" int dg_attn_decode(const void* qkv_cache, void* out, int B, int Tcap,
     return DG_OK;
 }
 
+// attn_decode_kernel with t = L - 1 read from the decode state (a captured decode step replays for every token).  The new token's
+// q/k/v row arrives in a staging buffer [B, 3*NH*H] (the QKV GEMM of a captured graph needs a fixed output pointer); the wave of
+// (b, h) copies its own three H-wide slices into cache[b, t] for the tokens to come and, for row t, reads the staging row itself
+// (same values; no store-to-load ordering needed inside the launch).  Arithmetic and order are attn_decode_kernel's.
+// t >= Tcap (or L == 0): nothing is read or written.
+template <typename T>
+__global__ void attn_decode_append_kernel(const T* __restrict__ row, T* __restrict__ cache, T* __restrict__ out,
+                                          const uint32_t* __restrict__ state, int B, int Tcap, int NH, int H, float scale) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const uint32_t Lw = state[2];
+    if (Lw == 0u || Lw > (uint32_t)Tcap) return;
+    const int t = (int)Lw - 1;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int Tn = t + 1;
+    float* sc = smem + w * (Tcap + H);
+    float* qs = sc + Tcap;
+    const int gid = blockIdx.x * AS_WAVES + w;            // (b, h)
+    if (gid >= B * NH) return;
+    const int h = gid % NH, b = gid / NH;
+    const int64_t ld = 3 * (int64_t)NH * H;
+    T* base = cache + (int64_t)b * Tcap * ld + h * H;
+    const T* nr = row + (int64_t)b * ld + h * H;          // the new row's q slice; k at + NH*H, v at + 2*NH*H
+    T* cr = base + (int64_t)t * ld;
+    for (int d = lane; d < H; d += 64) {
+        const T q = nr[d], k = nr[NH * H + d], v = nr[2 * NH * H + d];
+        cr[d] = q; cr[NH * H + d] = k; cr[2 * NH * H + d] = v;
+        qs[d] = to_f32<T>(q);
+    }
+    __builtin_amdgcn_wave_barrier();
+    float mx = -INFINITY;
+    for (int j = lane; j < Tn; j += 64) {
+        const T* kr = (j == t ? nr : base + (int64_t)j * ld) + NH * H;
+        float s = 0.f;
+        for (int d = 0; d < H; ++d) s += qs[d] * to_f32<T>(kr[d]);
+        s *= scale;
+        sc[j] = s;
+        mx = fmaxf(mx, s);
+    }
+    mx = wave_max(mx);
+    float sum = 0.f;
+    for (int j = lane; j < Tn; j += 64) { float e = expf(sc[j] - mx); sc[j] = e; sum += e; }
+    sum = wave_sum(sum);
+    const float inv = 1.f / sum;
+    for (int j = lane; j < Tn; j += 64) sc[j] *= inv;
+    __builtin_amdgcn_wave_barrier();
+    T* orow = out + (int64_t)b * (NH * H) + h * H;
+    for (int d = lane; d < H; d += 64) {
+        float o = 0.f;
+        for (int j = 0; j < Tn; ++j) o += sc[j] * to_f32<T>((j == t ? nr : base + (int64_t)j * ld)[2 * NH * H + d]);
+        orow[d] = from_f32<T>(o);
+    }
+}
+
+extern "C" int dg_attn_decode_append(const void* qkv_row, void* qkv_cache, void* out, const uint32_t* state, int B, int Tcap,
+                                     int NH, int H, float scale, int dtype, void* stream) {
+    if (!qkv_row || !qkv_cache || !out || !state || B <= 0 || Tcap <= 0 || NH <= 0 || H <= 0 || H > 256 || Tcap > 8192)
+        return DG_ERR_ARG;
+    dim3 grid((B * NH + AS_WAVES - 1) / AS_WAVES), block(64 * AS_WAVES);
+    size_t sm = (size_t)AS_WAVES * (Tcap + H) * sizeof(float);
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == DG_BF16)
+        hipLaunchKernelGGL(attn_decode_append_kernel<bf16_t>, grid, block, sm, s, (const bf16_t*)qkv_row, (bf16_t*)qkv_cache, (bf16_t*)out, state, B, Tcap, NH, H, scale);
+    else if (dtype == DG_F32)
+        hipLaunchKernelGGL(attn_decode_append_kernel<float>, grid, block, sm, s, (const float*)qkv_row, (float*)qkv_cache, (float*)out, state, B, Tcap, NH, H, scale);
+    else return DG_ERR_DTYPE;
+    DG_LAUNCH_CHECK();
+    return DG_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 static int check_common(int B, int T, int NH, int H, float p) {
     if (B <= 0 || T <= 0 || NH <= 0 || H <= 0 || H > 256 || T > 4096) return DG_ERR_ARG;

@@ -153,6 +153,42 @@ extern "C" int dg_batch_embed_fwd(const int64_t* corpus, int64_t n_corpus, const
     return DG_OK;
 }
 
+// The embedding of a captured decode step (ref: src/model.py:625 crop + :595-597): the position comes from the decode state
+// {seed_lo, seed_hi, L, 0}, L = current sequence length, so one captured launch serves every token.  A wave per output row.
+//   mode 0: x[b, :]    = tok[ids[b, L - 1]] + pos[L - 1]            (1 <= L <= Tw)
+//   mode 1: x[b, i, :] = tok[ids[b, L - Tw + i]] + pos[i], i < Tw   (L >= Tw)
+// An L outside the mode's range, or beyond the ld_ids columns of ids, writes nothing: a device position never indexes outside a buffer.
+__global__ void embed_window_kernel(const int64_t* __restrict__ ids, int64_t ld_ids, const uint32_t* __restrict__ state,
+                                    const float* __restrict__ tok, const float* __restrict__ pos, float* __restrict__ x,
+                                    int B, int Tw, int C, int V, int mode) {
+    const int64_t L = (int64_t)state[2];
+    if (L < 1 || L > ld_ids || (mode == 0 ? L > Tw : L < Tw)) return;
+    const int rows_per_b = mode == 0 ? 1 : Tw;
+    const int lane = threadIdx.x & 63;
+    const int64_t wave0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const int64_t Mrows = (int64_t)B * rows_per_b;
+    for (int64_t m = wave0; m < Mrows; m += nwaves) {
+        const int b = (int)(m / rows_per_b), i = (int)(m % rows_per_b);
+        const int64_t col = mode == 0 ? L - 1 : L - Tw + i;
+        const int t = mode == 0 ? (int)(L - 1) : i;
+        int64_t v = ids[(int64_t)b * ld_ids + col];
+        v = v < 0 ? 0 : (v >= V ? V - 1 : v);
+        for (int c = lane; c < C; c += 64) x[m * C + c] = tok[v * C + c] + pos[(int64_t)t * C + c];
+    }
+}
+
+extern "C" int dg_embed_window(const int64_t* ids, int64_t ld_ids, const uint32_t* state, const float* tok, const float* pos,
+                               float* x, int B, int Tw, int C, int V, int mode, void* stream) {
+    if (!ids || !state || !tok || !pos || !x || ld_ids <= 0 || B <= 0 || Tw <= 0 || C <= 0 || V <= 0 || (mode != 0 && mode != 1))
+        return DG_ERR_ARG;
+    const int64_t rows = (int64_t)B * (mode == 0 ? 1 : Tw);
+    unsigned grid = (unsigned)((rows + 3) / 4);
+    if (grid > 4096) grid = 4096;
+    hipLaunchKernelGGL(embed_window_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, ids, ld_ids, state, tok, pos, x, B, Tw, C, V, mode);
+    DG_LAUNCH_CHECK();
+    return DG_OK;
+}
+
 // zero fill.  NOT hipMemsetAsync: inside a captured hipGraph the runtime's memset node (a fillBufferAligned dispatch whose
 // fill pattern lives in a runtime-owned argument buffer) filled the token-table gradient with garbage on every replay that
 // followed the load of a new code object -- e.g. the first torch `.double()` kernel of the process, launched between two steps

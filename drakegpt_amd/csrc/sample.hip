@@ -1,0 +1,185 @@
+// Token sampling on the device for generate() -- ref: src/model.py:625-635 (F.softmax at :631, torch.multinomial at :633).
+// One workgroup per row of fp32 logits; the row (201 KB at V = 50257) does not fit LDS, so the kernel makes a few passes over
+// the L2-resident row:
+//   1. max z and its lowest index (z = logit * inv_temp; coalesced)            -> greedy ends here
+//   2. top-k only: radix select of the k-th largest z on order-preserving 32-bit keys, 4 passes of 8 bits, LDS histograms
+//      with INTEGER atomics (counts do not depend on arrival order)
+//   3. blocked scan: thread t owns the contiguous chunk [t * chunk, (t + 1) * chunk); its e_j = exp(z_j - max) (fp64 exp of the
+//      fp32 difference) are summed in index order in fp64, the chunk sums are scanned (wave shuffles, then the wave totals in
+//      wave order), S = the last prefix
+//   4. the thread whose prefix interval holds u * S walks its chunk again and writes the token; all threads write probs
+// z and z - max are single fp32 roundings (__fmul_rn / __fsub_rn: never contracted into an fma), so a host restatement can match.
+// No floating-point atomics anywhere: tokens and probs are a pure function of (logits, state, params, row).
+// exp and the prefix sums are fp64: with a few terms kept by top-k the errors of an fp32 expf do not average out of S (measured:
+// probs off by 4.5 x 2^-24 at k = 40), and fp64 is cheap here -- a few passes over one row.  The CDF is then exact to ~1e-14.
+#include "common.h"
+
+#define DG_SITE_SAMPLE 0x53414D50u      // "SAMP": not of the form 4 * layer + k for any layer a model can have
+
+struct SampleParams { float inv_temp; int32_t top_k; };
+
+__device__ __forceinline__ uint32_t f32_key(float z) {          // a < b  <=>  key(a) < key(b)  (no NaNs)
+    const uint32_t b = __float_as_uint(z);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float key_f32(uint32_t k) {
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void sample_rows_kernel(const float* __restrict__ logits, int64_t ldl, int M, int V,
+                                                         const uint32_t* __restrict__ state, const SampleParams* __restrict__ params,
+                                                         int64_t* __restrict__ ids, int64_t ld_ids, float* __restrict__ probs,
+                                                         int64_t ldp) {
+    constexpr int NW = NT / 64;
+    __shared__ float s_mx[NW];
+    __shared__ int s_ix[NW];
+    __shared__ int s_hist[256];
+    __shared__ uint32_t s_sel[2];          // {key prefix, k still to find below it}
+    __shared__ double s_wtot[NW];
+    __shared__ int s_owner, s_last;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int row = blockIdx.x;
+    const float* x = logits + (int64_t)row * ldl;
+    float* prow = probs ? probs + (int64_t)row * ldp : nullptr;
+    const float inv_temp = params->inv_temp;
+    int top_k = params->top_k;
+    const bool greedy = !(inv_temp > 0.f);
+    const float sc = greedy ? 1.f : inv_temp;
+
+    // ---- pass 1: max and the lowest index that attains it
+    float mx = -INFINITY; int ix = V;
+    for (int i = tid; i < V; i += NT) {
+        const float z = __fmul_rn(x[i], sc);
+        if (ix == V || z > mx) { mx = z; ix = i; }              // strict: a thread keeps the lowest of its equal maxima
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float om = __shfl_xor(mx, o, 64); const int oi = __shfl_xor(ix, o, 64);
+        if (om > mx || (om == mx && oi < ix)) { mx = om; ix = oi; }
+    }
+    if (lane == 0) { s_mx[w] = mx; s_ix[w] = ix; }
+    if (tid == 0) { s_owner = NT; s_last = -1; }
+    __syncthreads();
+    mx = s_mx[0]; ix = s_ix[0];
+#pragma unroll
+    for (int v = 1; v < NW; ++v) {
+        const float om = s_mx[v]; const int oi = s_ix[v];
+        if (om > mx || (om == mx && oi < ix)) { mx = om; ix = oi; }
+    }
+    if (ix >= V) ix = V - 1;
+    const uint32_t L = state ? state[2] : 0u;
+    const bool write_tok = ids != nullptr && (ld_ids == 0 || (int64_t)L < ld_ids);
+    int64_t* tok_out = ids ? (ld_ids == 0 ? ids + row : ids + (int64_t)row * ld_ids + L) : nullptr;
+
+    if (greedy) {
+        if (tid == 0 && write_tok) *tok_out = ix;
+        if (prow) for (int i = tid; i < V; i += NT) prow[i] = i == ix ? 1.f : 0.f;
+        return;
+    }
+
+    // ---- pass 2: tau = the k-th largest z (ties at tau are all kept; -inf never is)
+    float tau = -INFINITY;
+    if (top_k > V) top_k = V;
+    if (top_k > 0 && top_k < V) {
+        if (tid == 0) { s_sel[0] = 0u; s_sel[1] = (uint32_t)top_k; }
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            for (int i = tid; i < 256; i += NT) s_hist[i] = 0;
+            __syncthreads();
+            const uint32_t prefix = s_sel[0];
+            const uint32_t himask = shift == 24 ? 0u : (0xFFFFFFFFu << (shift + 8));
+            for (int i = tid; i < V; i += NT) {
+                const uint32_t key = f32_key(__fmul_rn(x[i], sc));
+                if (((key ^ prefix) & himask) == 0u) atomicAdd(&s_hist[(key >> shift) & 255u], 1);
+            }
+            __syncthreads();
+            if (w == 0) {
+                // lane l owns bins 4l .. 4l + 3; `above` = keys in the bins of higher lanes
+                const int c0 = s_hist[4 * lane], c1 = s_hist[4 * lane + 1], c2 = s_hist[4 * lane + 2], c3 = s_hist[4 * lane + 3];
+                const int c = c0 + c1 + c2 + c3;
+                int suf = c;                                   // inclusive suffix sum over lanes >= lane
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_down(suf, o, 64); if (lane + o < 64) suf += t; }
+                int above = suf - c;
+                const int k = (int)s_sel[1];
+                if (above < k && k <= suf) {                   // exactly one lane
+                    int bin = 4 * lane + 3;
+                    if (above + c3 >= k) bin = 4 * lane + 3;
+                    else if ((above += c3, above + c2 >= k)) bin = 4 * lane + 2;
+                    else if ((above += c2, above + c1 >= k)) bin = 4 * lane + 1;
+                    else { above += c1; bin = 4 * lane; }
+                    s_sel[0] = prefix | ((uint32_t)bin << shift);
+                    s_sel[1] = (uint32_t)(k - above);
+                }
+            }
+            __syncthreads();
+        }
+        tau = key_f32(s_sel[0]);
+    }
+
+    // ---- pass 3: chunk sums in index order, fp64, and their scan
+    const int chunk = (V + NT - 1) / NT;
+    const int j0 = min(tid * chunk, V), j1 = min(j0 + chunk, V);
+    double csum = 0.0; int last = -1;
+    for (int j = j0; j < j1; ++j) {
+        const float z = __fmul_rn(x[j], sc);
+        if (z >= tau && z > -INFINITY) { csum += exp((double)__fsub_rn(z, mx)); last = j; }
+    }
+    double incl = csum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const double t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
+    if (lane == 63) s_wtot[w] = incl;
+    if (last >= 0) atomicMax(&s_last, last);
+    __syncthreads();
+    double woff = 0.0, S = 0.0;
+    for (int v = 0; v < NW; ++v) { if (v == w) woff = S; S += s_wtot[v]; }
+    incl += woff;
+    double excl = __shfl_up(incl, 1, 64);
+    if (lane == 0) excl = woff;                                // == the last inclusive prefix of wave w - 1, bit for bit
+
+    if (prow) {
+        for (int i = tid; i < V; i += NT) {
+            const float z = __fmul_rn(x[i], sc);
+            prow[i] = (z >= tau && z > -INFINITY) ? (float)(exp((double)__fsub_rn(z, mx)) / S) : 0.f;
+        }
+    }
+    if (!write_tok) return;
+
+    // ---- pass 4: the smallest n with sum_{j <= n} e_j > u * S
+    const uint32_t h = dg_hash_w(dg_site_key(state[0], state[1], L, DG_SITE_SAMPLE), (uint32_t)row * DG_WEYL);
+    const double target = (double)((float)(h >> 8) * 0x1p-24f) * S;
+    if (incl > target && !(excl > target)) atomicMin(&s_owner, tid);     // excl(t) == incl(t - 1): at most one thread
+    __syncthreads();
+    const int owner = s_owner;
+    if (owner == NT) {                                         // rounding (or an empty / non-finite row) left no such n
+        if (tid == 0) { const int l = s_last; *tok_out = l >= 0 ? l : ix; }
+        return;
+    }
+    if (tid != owner) return;
+    double run = excl; int tok = last;                         // last: if re-adding from excl rounds below target
+    for (int j = j0; j < j1; ++j) {
+        const float z = __fmul_rn(x[j], sc);
+        if (z >= tau && z > -INFINITY) {
+            run += exp((double)__fsub_rn(z, mx));
+            if (run > target) { tok = j; break; }
+        }
+    }
+    *tok_out = tok;
+}
+
+extern "C" int dg_sample_rows(const float* logits, int64_t ldl, int M, int V, const uint32_t* state, const void* params,
+                              int64_t* ids, int64_t ld_ids, float* probs, int64_t ldp, void* stream) {
+    if (!logits || !params || M <= 0 || V <= 0 || V > (1 << 20) || ldl < V || ld_ids < 0) return DG_ERR_ARG;
+    if (!ids && !probs) return DG_ERR_ARG;
+    if (ids && !state) return DG_ERR_ARG;
+    if (probs && ldp < V) return DG_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const SampleParams* p = (const SampleParams*)params;
+    // a chunk of at most 32 (small rows) or V / 1024 (52 at V = 53248) elements per thread
+    if (V <= 8192)
+        hipLaunchKernelGGL(sample_rows_kernel<256>, dim3(M), dim3(256), 0, s, logits, ldl, M, V, state, p, ids, ld_ids, probs, ldp);
+    else
+        hipLaunchKernelGGL(sample_rows_kernel<1024>, dim3(M), dim3(1024), 0, s, logits, ldl, M, V, state, p, ids, ld_ids, probs, ldp);
+    DG_LAUNCH_CHECK();
+    return DG_OK;
+}

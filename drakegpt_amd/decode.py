@@ -1,0 +1,121 @@
+"""Graph-replayed decoding for TransformerLM.generate(sampler="device") -- ref: src/model.py:611-636.
+
+The training step is one graph launch that walks a device-side step counter; generation gets the same shape here.  The decode
+state {seed_lo, seed_hi, L, 0} lives on the device (L = current sequence length), every kernel of a step reads its position from
+it, the sampler writes token L into the ids buffer and dg_state_advance moves L on.  Two linear chains are captured once per
+(batch, device, precision) and replayed once per token, with no host work in between:
+
+  graph A (K/V-cached step, valid while L <= ctx): embed_window mode 0, per layer LN / QKV GEMM into a staging row /
+      attn_decode_append / proj / LN / FFN, lm_head, sample_rows, state_advance
+  graph B (sliding-window step, valid for L >= ctx): embed_window mode 1, the eval forward kernels at T = ctx
+      (TransformerLM._forward_rows), lm_head on the last row, sample_rows, state_advance
+
+Graphs hold raw pointers, so the decoder owns every operand: staged copies of the weights (refreshed on every generate call),
+the K/V caches, the ids buffer, the state and the sampler parameters.
+"""
+from __future__ import annotations
+
+import weakref
+
+import torch
+
+from . import ops
+
+
+class DeviceDecoder:
+    def __init__(self, model, B: int, device, min_cap: int):
+        ctx = model.context_length
+        C = model.token_embedding_table.weight.shape[1]
+        self.B, self.ctx, self.C = B, ctx, C
+        self.NH = len(model.blocks[0].sa_head.heads)
+        self.H = model.blocks[0].sa_head.heads[0].head_size
+        self.act, self.split = model.act_dtype, model.split_bf16
+        self.device = device
+        self._mref = weakref.ref(model)          # the model owns the decoder, not the other way round
+        # the ids row length is a launch argument of the captured kernels: round the capacity up so that calls of similar length
+        # share one capture
+        self.cap = max(ctx + 1, (min_cap + 255) // 256 * 256)
+        self.ids = torch.zeros((B, self.cap), dtype=torch.int64, device=device)
+        self.state = torch.zeros(4, dtype=torch.int32, device=device)
+        self.params = ops.new_sample_params(1.0, None, device)
+        self.caches = [torch.zeros((B, ctx, 3 * C), dtype=self.act, device=device) for _ in model.blocks]
+        self.row = torch.zeros((B, 3 * C), dtype=self.act, device=device)       # staging: the new token's q/k/v
+        self.ws = self.w_lm = self.tok = self.pos = self.lm_bias = None
+        self.graphs = None
+
+    # ------------------------------------------------------------------ operands
+    @torch.no_grad()
+    def refresh(self, model) -> None:
+        """copy the model's current weights into the staged operands (allocated on the first call)"""
+        ws, w_lm = model._decode_weights()
+        src = [t for W in ws for t in W.values()] + [w_lm, model.token_embedding_table.weight,
+                                                     model.position_embedding_table.weight, model.lm_head.bias]
+        if self.ws is None:
+            own = [t.detach().clone() for t in src]
+            n = len(ws[0])
+            keys = list(ws[0].keys())
+            self.ws = [dict(zip(keys, own[l * n:(l + 1) * n])) for l in range(len(ws))]
+            self.w_lm, self.tok, self.pos, self.lm_bias = own[len(ws) * n:]
+            self._flat = own
+        else:
+            for d, s in zip(self._flat, src):
+                d.copy_(s)
+
+    # ------------------------------------------------------------------ the two steps
+    def _tail(self, logits) -> None:
+        ops.sample_rows(logits, self.state, self.params, ids=self.ids)
+        ops.state_advance(self.state)
+
+    def _step_cached(self) -> None:
+        """TransformerLM._decode_step at the device position L - 1"""
+        act, sp = self.act, self.split
+        x = ops.embed_window(self.ids, self.state, self.tok, self.pos, 0)
+        for W, cache in zip(self.ws, self.caches):
+            h, _, _ = ops.layernorm_fwd(x, W["ln1w"], W["ln1b"], act)
+            ops.gemm_nt(h, W["wqkv"], act, out=self.row, split=sp)
+            o = ops.attn_decode_append(self.row, cache, self.state, self.NH, self.H, self.H ** -0.5)
+            x = ops.gemm_nt(o, W["wproj"], torch.float32, bias=W["bproj"], residual=x, split=sp)
+            h, _, _ = ops.layernorm_fwd(x, W["ln2w"], W["ln2b"], act)
+            f = ops.gemm_nt(h, W["w1"], act, bias=W["b1"], relu=True, split=sp)
+            x = ops.gemm_nt(f, W["w2"], torch.float32, bias=W["b2"], residual=x, split=sp)
+        xa = x if act == torch.float32 else ops.cast(x, act)
+        self._tail(ops.gemm_nt(xa, self.w_lm, torch.float32, bias=self.lm_bias, split=sp))
+
+    def _step_window(self, model) -> None:
+        """the full forward on the last ctx tokens (the reference algorithm once the window slides)"""
+        x = ops.embed_window(self.ids, self.state, self.tok, self.pos, 1).view(self.B * self.ctx, self.C)
+        self._tail(model._forward_rows(x, self.B, self.ctx, None, self.ws, self.w_lm, self.lm_bias))
+
+    # ------------------------------------------------------------------ capture / replay
+    @torch.no_grad()
+    def capture(self) -> None:
+        """capture both steps once (as TrainEngine._capture does: warm-up on a side stream first, which loads every code object and
+        fills the allocator; the state word is restored afterwards).  A warm-up step writes cache row L - 1 and ids[:, L]: both are
+        rewritten by the real step at that L before anything reads them."""
+        if self.graphs is not None:
+            return
+        model = self._mref()
+        graphs = []
+        for L, fn in ((1, self._step_cached), (self.ctx, lambda: self._step_window(model))):
+            self.state.copy_(ops.new_rng_state(0, self.device, step=L))
+            side = torch.cuda.Stream(device=self.device)
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                fn()
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize(self.device)
+            self.state.copy_(ops.new_rng_state(0, self.device, step=L))
+            torch.cuda.synchronize(self.device)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                fn()
+            graphs.append(g)
+        self.graphs = tuple(graphs)
+
+    def step(self, cached: bool, graph: bool = True) -> None:
+        if graph:
+            self.graphs[0 if cached else 1].replay()
+        elif cached:
+            self._step_cached()
+        else:
+            self._step_window(self._mref())

@@ -18,6 +18,7 @@ Reference quirks kept on purpose:
 """
 from __future__ import annotations
 
+import math
 from collections import OrderedDict
 from typing import Optional
 
@@ -50,6 +51,29 @@ def model_params(params: dict, model_type: str, vocab_size: int) -> int:
     if model_type == "TransformerLM":
         total += (attention + mlp) * L + vocab_size
     return total
+
+
+def check_sampling_args(sampler, temperature, top_k, vocab_size: int):
+    """the argument checks of generate(): plain Python, raised before anything touches a device.  Returns (temperature as a
+    float, top_k clamped to the vocabulary or None)."""
+    if sampler not in ("host", "device"):
+        raise ValueError(f"generate: sampler must be 'host' or 'device', got {sampler!r}")
+    try:
+        t = float(temperature)
+    except (TypeError, ValueError):
+        raise ValueError(f"generate: temperature must be a number, got {temperature!r}") from None
+    if not math.isfinite(t) or t < 0.0:
+        raise ValueError(f"generate: temperature must be finite and >= 0, got {temperature!r}")
+    if top_k is not None:
+        if isinstance(top_k, bool) or int(top_k) != top_k or top_k < 1:
+            raise ValueError(f"generate: top_k must be an integer >= 1 (or None), got {top_k!r}")
+        top_k = min(int(top_k), int(vocab_size))
+    return t, top_k
+
+
+def draw_seed(generator: Optional[torch.Generator]) -> int:
+    """one sampling seed from the CPU generator (the global one unless `generator` is given)"""
+    return int(torch.randint(0, 2 ** 62, (1,), generator=generator))
 
 
 class _LM(HipModule):
@@ -97,19 +121,74 @@ class _LM(HipModule):
         return logits, loss
 
     @torch.no_grad()
-    def _last_probs(self, idx):
+    def _last_probs(self, idx, params=None):
         logits, _ = self(idx)
-        return ops.softmax_rows(logits[:, -1, :])
+        return self._probs(logits[:, -1, :], params)
 
-    def generate(self, idx, max_new_tokens, generator: Optional[torch.Generator] = None):
-        """ref: src/model.py:611-636.  softmax runs on the GPU; torch.multinomial runs on the host CPU
-        generator (the global one unless `generator` is given), as it does in the reference on CPU."""
+    @staticmethod
+    def _probs(logits, params):
+        """params None: the plain softmax (the reference's distribution); else the temperature / top-k filtered one"""
+        if params is None:
+            return ops.softmax_rows(logits)
+        return ops.sample_rows(logits, params=params, tokens=False, probs=True)
+
+    @staticmethod
+    def _host_params(device, temperature, top_k):
+        return None if temperature == 1.0 and top_k is None else ops.new_sample_params(temperature, top_k, device)
+
+    def generate(self, idx, max_new_tokens, generator: Optional[torch.Generator] = None, *, sampler: str = "host",
+                 temperature: float = 1.0, top_k: Optional[int] = None, seed: Optional[int] = None):
+        """ref: src/model.py:611-636.  sampler="host" (default): softmax runs on the GPU; torch.multinomial runs on the host CPU
+        generator (the global one unless `generator` is given), as it does in the reference on CPU.  A temperature other than 1
+        (0 = greedy) or a top_k filters the distribution on the GPU first (dg_sample_rows).
+        sampler="device": the tokens are drawn by dg_sample_rows from a counter-based stream keyed by `seed` (drawn once from the
+        CPU generator when None) and the sequence length, and never leave the GPU inside the loop."""
+        temperature, top_k = check_sampling_args(sampler, temperature, top_k, self.token_embedding_table.weight.shape[0])
+        if sampler == "device":
+            return self._generate_device(idx, max_new_tokens, generator, temperature, top_k, seed)
+        params = self._host_params(idx.device, temperature, top_k)
         for _ in range(max_new_tokens):
             cond = idx if self.context_length is None else idx[:, -self.context_length:]
-            probs = self._last_probs(cond.contiguous())
+            probs = self._last_probs(cond.contiguous(), params)
             nxt = torch.multinomial(probs.cpu(), num_samples=1, generator=generator)
             idx = torch.cat((idx, nxt.to(idx.device)), dim=1)
         return idx
+
+    def _decode_begin(self, idx, max_new_tokens, generator, temperature, top_k, seed, ids=None):
+        """shared start of the device-sampler paths: checks the prompt once, returns (ids buffer, decode state, params)"""
+        ops._chk(idx, "idx", torch.int64, contiguous=False)
+        if idx.dim() != 2 or idx.shape[1] < 1:
+            raise ValueError("idx must be (B, T) with T >= 1")
+        self._check_ids(idx, None)
+        B, t0 = idx.shape
+        if seed is None:
+            seed = draw_seed(generator)
+        if ids is None:
+            ids = torch.zeros((B, t0 + max_new_tokens), dtype=torch.int64, device=idx.device)
+        ids[:, :t0] = idx
+        return ids, ops.new_rng_state(int(seed), idx.device, step=t0), ops.new_sample_params(temperature, top_k, idx.device)
+
+    @torch.no_grad()
+    def _generate_device(self, idx, max_new_tokens, generator, temperature, top_k, seed):
+        """the reference algorithm (full forward on the cropped window per token) with the sampler on the device: the kernel writes
+        token L into ids[:, L]; no host copy or sync inside the loop (the ids were range-checked once, sampled ids are in range)."""
+        ids, state, params = self._decode_begin(idx, max_new_tokens, generator, temperature, top_k, seed)
+        t0, ctx = idx.shape[1], self.context_length
+        had = "check_ids" in self.__dict__
+        saved = self.check_ids
+        self.check_ids = False
+        try:
+            for L in range(t0, t0 + max_new_tokens):
+                lo = 0 if ctx is None else max(0, L - ctx)
+                logits, _ = self(ids[:, lo:L].contiguous())
+                ops.sample_rows(logits[:, -1, :], state, params, ids=ids)
+                ops.state_advance(state)
+        finally:
+            if had:
+                self.check_ids = saved
+            else:
+                del self.check_ids
+        return ids
 
 
 class BigramLM(_LM):
@@ -246,46 +325,63 @@ class TransformerLM(_BlocksLM):
         return ops.gemm_nt(xa, w_lm, torch.float32, bias=self.lm_head.bias, split=sp)
 
     @torch.no_grad()
-    def _prefill(self, idx, caches, ws, w_lm):
-        """the prompt in ONE pass through the training-forward kernels (not one decode step per position): fills every layer's
-        K/V cache rows [0, t0) and returns the logits (B, V) of the last prompt position -- the values the reference's full
-        forward produces for it (the uncached path runs exactly these kernels)."""
+    def _forward_rows(self, x, B, T, caches, ws, w_lm, lm_bias=None):
+        """x (B*T, C), the embedded rows of B sequences of T positions -> logits (B, V) of every sequence's last position, through
+        the training-forward kernels; caches (nullable): every layer's q/k/v rows [0, T) are also left in its K/V cache."""
         act = self.act_dtype
         sp = self.split_bf16          # precision bf16x3: split-bf16 contractions
-        B, t0 = idx.shape
         NH = len(self.blocks[0].sa_head.heads)
         H = self.blocks[0].sa_head.heads[0].head_size
-        x = ops.embed_fwd(idx, self.token_embedding_table.weight, self.position_embedding_table.weight).view(B * t0, -1)
-        for W, cache in zip(ws, caches):
+        for l, W in enumerate(ws):
             h, _, _ = ops.layernorm_fwd(x, W["ln1w"], W["ln1b"], act)
             qkv = ops.gemm_nt(h, W["wqkv"], act, split=sp)
-            cache[:, :t0].copy_(qkv.view(B, t0, -1))
-            o, _ = ops.attn_fwd(qkv, B, t0, NH, H, H ** -0.5, 0.0, None, 0)
+            if caches is not None:
+                caches[l][:, :T].copy_(qkv.view(B, T, -1))
+            o, _ = ops.attn_fwd(qkv, B, T, NH, H, H ** -0.5, 0.0, None, 0)
             x = ops.gemm_nt(o, W["wproj"], torch.float32, bias=W["bproj"], residual=x, split=sp)
             h, _, _ = ops.layernorm_fwd(x, W["ln2w"], W["ln2b"], act)
             f = ops.gemm_nt(h, W["w1"], act, bias=W["b1"], relu=True, split=sp)
             x = ops.gemm_nt(f, W["w2"], torch.float32, bias=W["b2"], residual=x, split=sp)
-        last = x.view(B, t0, -1)[:, -1].contiguous()
+        last = x.view(B, T, -1)[:, -1].contiguous()
         xa = last if act == torch.float32 else ops.cast(last, act)
-        return ops.gemm_nt(xa, w_lm, torch.float32, bias=self.lm_head.bias, split=sp)
+        return ops.gemm_nt(xa, w_lm, torch.float32, bias=self.lm_head.bias if lm_bias is None else lm_bias, split=sp)
 
-    def generate(self, idx, max_new_tokens, generator: Optional[torch.Generator] = None, use_cache: bool = True):
+    @torch.no_grad()
+    def _prefill(self, idx, caches, ws, w_lm):
+        """the prompt in ONE pass through the training-forward kernels (not one decode step per position): fills every layer's
+        K/V cache rows [0, t0) and returns the logits (B, V) of the last prompt position -- the values the reference's full
+        forward produces for it (the uncached path runs exactly these kernels)."""
+        B, t0 = idx.shape
+        x = ops.embed_fwd(idx, self.token_embedding_table.weight, self.position_embedding_table.weight).view(B * t0, -1)
+        return self._forward_rows(x, B, t0, caches, ws, w_lm)
+
+    def generate(self, idx, max_new_tokens, generator: Optional[torch.Generator] = None, use_cache: bool = True, *,
+                 sampler: str = "host", temperature: float = 1.0, top_k: Optional[int] = None, seed: Optional[int] = None):
         """ref: src/model.py:611-636.  While the sequence still fits the context window the per-layer K/V of the
         tokens seen so far are kept (training layout, [B, ctx, 3C]) and only the new position is computed; once the
         window starts to slide every position embedding shifts, the cache is void, and decoding continues exactly
         as the reference does (full forward on the cropped window).  Dropout is off in both paths only in eval()
-        mode -- like the reference, train() mode samples with dropout through the uncached path."""
+        mode -- like the reference, train() mode samples with dropout through the uncached path.
+        sampler / temperature / top_k / seed: as in _LM.generate.  sampler="device" in eval() mode with use_cache=True replays one
+        captured graph per token (decode.DeviceDecoder): no host work inside the loop."""
+        temperature, top_k = check_sampling_args(sampler, temperature, top_k, self.token_embedding_table.weight.shape[0])
+        kw = dict(sampler=sampler, temperature=temperature, top_k=top_k, seed=seed)
+        if sampler == "device":
+            if not use_cache or self.training:
+                return self._generate_device(idx, max_new_tokens, generator, temperature, top_k, seed)
+            return self._generate_device_cached(idx, max_new_tokens, generator, temperature, top_k, seed)
         if not use_cache or self.training or idx.shape[1] >= self.context_length:
-            return super().generate(idx, max_new_tokens, generator)
+            return super().generate(idx, max_new_tokens, generator, **kw)
         B, t0 = idx.shape
         self._check_ids(idx, None)
+        params = self._host_params(idx.device, temperature, top_k)
         C3 = 3 * self.token_embedding_table.weight.shape[1]
         ws, w_lm = self._decode_weights()
         caches = [torch.zeros((B, self.context_length, C3), dtype=self.act_dtype, device=idx.device) for _ in self.blocks]
         logits = self._prefill(idx.contiguous(), caches, ws, w_lm)      # the whole prompt in one pass
         produced = 0
         while produced < max_new_tokens:
-            probs = ops.softmax_rows(logits)
+            probs = self._probs(logits, params)
             nxt = torch.multinomial(probs.cpu(), num_samples=1, generator=generator).to(idx.device)
             idx = torch.cat((idx, nxt), dim=1)
             produced += 1
@@ -293,9 +389,48 @@ class TransformerLM(_BlocksLM):
                 break
             t = idx.shape[1] - 1
             if t >= self.context_length:                         # window slides: fall back to the reference algorithm
-                return super().generate(idx, max_new_tokens - produced, generator)
+                return super().generate(idx, max_new_tokens - produced, generator, **kw)
             logits = self._decode_step(nxt.contiguous(), t, caches, ws, w_lm)
         return idx
+
+    # ------------------------------------------------------------------ graph-replayed decoding (sampler="device")
+    def __getstate__(self):
+        d = self.__dict__.copy()
+        d.pop("_decoders", None)              # captured graphs and their buffers are rebuilt on demand, never copied or pickled
+        return d
+
+    @torch.no_grad()
+    def _generate_device_cached(self, idx, max_new_tokens, generator, temperature, top_k, seed, graph: bool = True):
+        """eager one-pass prefill, sample, advance; then one step per token on the device position L: the K/V-cached step while
+        L <= ctx, the full-window step after that.  graph=True replays the two captured graphs of decode.DeviceDecoder;
+        graph=False launches the very same steps eagerly."""
+        from .decode import DeviceDecoder
+        ops._chk(idx, "idx", torch.int64, contiguous=False)
+        if idx.dim() != 2 or idx.shape[1] < 1:
+            raise ValueError("idx must be (B, T) with T >= 1")
+        B, t0 = idx.shape
+        total, ctx = t0 + max_new_tokens, self.context_length
+        key = (B, idx.device, self.act_dtype, self.split_bf16)
+        decs = self.__dict__.setdefault("_decoders", {})
+        dec = decs.get(key)
+        if dec is None or dec.cap < total:
+            dec = decs[key] = DeviceDecoder(self, B, idx.device, total)
+        dec.refresh(self)                      # a generate() after an optimizer step sees the new weights
+        if graph:
+            dec.capture()
+        _, state, params = self._decode_begin(idx, max_new_tokens, generator, temperature, top_k, seed, ids=dec.ids)
+        dec.state.copy_(state)
+        dec.params.copy_(params)
+        L = t0
+        if max_new_tokens > 0 and t0 < ctx:
+            logits = self._prefill(idx.contiguous(), dec.caches, dec.ws, dec.w_lm)
+            ops.sample_rows(logits, dec.state, dec.params, ids=dec.ids)
+            ops.state_advance(dec.state)
+            L += 1
+        while L < total:
+            dec.step(cached=L <= ctx, graph=graph)
+            L += 1
+        return dec.ids[:, :total].clone()
 
 
 MODEL_CLASSES = OrderedDict(

@@ -754,6 +754,107 @@ def softmax_rows(logits: Tensor) -> Tensor:
     return probs
 
 
+def new_sample_params(temperature: float, top_k: Optional[int], device) -> Tensor:
+    """device {float inv_temp, int32 top_k} of sample_rows (stored as two int32 bit patterns).  temperature 0 = greedy
+    (inv_temp 0); top_k None / 0 = off.  inv_temp is 1 / temperature rounded to fp32."""
+    import struct
+    inv = 0.0 if temperature == 0 else 1.0 / float(temperature)
+    bits = struct.unpack("<i", struct.pack("<f", inv))[0]
+    return torch.tensor([bits, int(top_k or 0)], dtype=torch.int32, device=device)
+
+
+def sample_rows(logits: Tensor, state: Optional[Tensor] = None, params: Optional[Tensor] = None, *, seed: Optional[int] = None,
+                L: Optional[int] = None, temperature: float = 1.0, top_k: Optional[int] = None, ids: Optional[Tensor] = None,
+                tokens: bool = True, probs: bool = False):
+    """one token per row of fp32 logits [M, V] (dg_sample_rows; include/drakegpt_hip.h states the semantics).
+    state: decode state int32[4] {seed_lo, seed_hi, L, 0} (new_rng_state(seed, device, step=L)); built from seed / L when None.
+    params: new_sample_params(...); built from temperature / top_k when None.
+    ids [B, cap] int64: row m's token is written to ids[m, L] by the kernel (nothing is returned for it); otherwise, with
+    tokens=True, a new int64 [M] tensor is returned.  probs=True also returns the filtered distribution [M, V].
+    Returns tokens, probs, (tokens, probs) or None according to what was asked for."""
+    _chk(logits, "logits", torch.float32, contiguous=False)
+    if logits.dim() != 2:
+        raise RuntimeError("sample_rows: logits must be [M, V]")
+    M, V = logits.shape
+    want_tok = tokens or ids is not None
+    if not want_tok and not probs:
+        raise ValueError("sample_rows: nothing to compute (tokens=False, probs=False)")
+    if params is None:
+        params = new_sample_params(temperature, top_k, logits.device)
+    _chk(params, "params", torch.int32)
+    if params.numel() != 2:
+        raise RuntimeError("sample_rows: params must hold {inv_temp, top_k}")
+    if want_tok:
+        if state is None:
+            if seed is None or L is None:
+                raise ValueError("sample_rows: tokens need a decode state, or seed= and L=")
+            state = new_rng_state(int(seed), logits.device, step=int(L))
+        _chk(state, "state", torch.int32)
+        if state.numel() != 4:
+            raise RuntimeError("sample_rows: state must be int32[4]")
+    out_tok, ld_ids, tok_ptr = None, 0, None
+    if ids is not None:
+        _chk(ids, "ids", torch.int64)
+        if ids.dim() != 2 or ids.shape[0] != M:
+            raise RuntimeError(f"sample_rows: ids must be [M = {M}, capacity]")
+        ld_ids, tok_ptr = ids.shape[1], _p(ids)
+    elif tokens:
+        out_tok = torch.empty((M,), dtype=torch.int64, device=logits.device)
+        tok_ptr = _p(out_tok)
+    p_out = torch.empty((M, V), dtype=torch.float32, device=logits.device) if probs else None
+    check(lib.dg_sample_rows(_p(logits), _ld(logits), M, V, _p(state) if want_tok else None, _p(params), tok_ptr, ld_ids,
+                             _p(p_out), V, _stream()), "dg_sample_rows")
+    if out_tok is not None and probs:
+        return out_tok, p_out
+    return out_tok if out_tok is not None else p_out
+
+
+def embed_window(ids: Tensor, state: Tensor, tok: Tensor, pos: Tensor, mode: int, out: Optional[Tensor] = None) -> Tensor:
+    """the embedding of a decode step with the position L = state[2] read on the device (dg_embed_window).
+    mode 0: [B, C] = tok[ids[:, L-1]] + pos[L-1];  mode 1: [B, Tw, C] = tok[ids[:, L-Tw:L]] + pos, Tw = rows of pos."""
+    _chk(ids, "ids", torch.int64)
+    _chk(state, "state", torch.int32)
+    _chk(tok, "tok", torch.float32)
+    _chk(pos, "pos", torch.float32)
+    if ids.dim() != 2 or state.numel() != 4 or mode not in (0, 1):
+        raise RuntimeError("embed_window: ids must be [B, capacity], state int32[4], mode 0 or 1")
+    B, cap = ids.shape
+    V, Cd = tok.shape
+    Tw = pos.shape[0]
+    if pos.shape[1] != Cd:
+        raise RuntimeError("embed_window: tok and pos widths differ")
+    shape = (B, Cd) if mode == 0 else (B, Tw, Cd)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=ids.device)
+    else:
+        _chk(out, "out", torch.float32)
+        if tuple(out.shape) != shape:
+            raise RuntimeError(f"embed_window: out must be {shape}")
+    check(lib.dg_embed_window(_p(ids), cap, _p(state), _p(tok), _p(pos), _p(out), B, Tw, Cd, V, mode, _stream()), "dg_embed_window")
+    return out
+
+
+def attn_decode_append(row: Tensor, cache: Tensor, state: Tensor, NH: int, H: int, scale: float,
+                       out: Optional[Tensor] = None) -> Tensor:
+    """attn_decode at position t = state[2] - 1 read on the device: row [B, 3*NH*H] (the new token's q/k/v) is written into
+    cache[:, t] and attended over keys 0..t; returns [B, NH*H].  t >= Tcap: nothing happens (out keeps its contents)."""
+    _chk(cache, "cache")
+    _chk(row, "row", cache.dtype)
+    _chk(state, "state", torch.int32)
+    B, Tcap, W = cache.shape
+    if W != 3 * NH * H or tuple(row.shape) != (B, W) or state.numel() != 4:
+        raise RuntimeError("attn_decode_append: cache must be [B, Tcap, 3*NH*H], row [B, 3*NH*H], state int32[4]")
+    if out is None:
+        out = torch.empty((B, NH * H), dtype=cache.dtype, device=cache.device)
+    else:
+        _chk(out, "out", cache.dtype)
+        if tuple(out.shape) != (B, NH * H):
+            raise RuntimeError("attn_decode_append: out must be [B, NH*H]")
+    check(lib.dg_attn_decode_append(_p(row), _p(cache), _p(out), _p(state), B, Tcap, NH, H, float(scale), dt_code(cache.dtype),
+                                    _stream()), "dg_attn_decode_append")
+    return out
+
+
 def adamw_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, hyper: Tensor, rng_state: Tensor, grad_scale: float = 1.0,
                shadow_bf16: Optional[Tensor] = None, n: Optional[int] = None, advance: bool = False, *,
                clip: Optional[Tensor] = None) -> None:

@@ -131,6 +131,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32", "fp8", "bf16x3"])
     ap.add_argument("--model-dir", default="model")
     ap.add_argument("--sample", type=int, default=100)
+    ap.add_argument("--sampler", default="host", choices=["host", "device"], help="who draws the tokens of the sample printed at the "
+                    "end: torch.multinomial on the host CPU generator (the reference's stream), or the GPU sampler kernel (no host "
+                    "work per token)")
+    ap.add_argument("--temperature", type=float, default=1.0, help="sampling temperature of that sample (0 = greedy)")
+    ap.add_argument("--top-k", type=int, default=None, help="keep only the k most likely tokens of that sample (default: off)")
     ap.add_argument("--grad-clip", type=float, default=None, metavar="MAX_NORM",
                     help="clip the gradient to this global 2-norm before every AdamW step (ref: clip_grad_norm_; default: off); each "
                     "evaluation line then also reports the last step's pre-clip norm as grad_norm")
@@ -237,7 +242,10 @@ def main(argv=None):
     model.eval()
     if rank == 0:
         idx = torch.zeros((1, 1), dtype=torch.long, device=device)
-        print(decode(model.generate(idx, max_new_tokens=args.sample)[0].tolist()))
+        sample_kw = {}
+        if (args.sampler, args.temperature, args.top_k) != ("host", 1.0, None):
+            sample_kw = dict(sampler=args.sampler, temperature=args.temperature, top_k=args.top_k)
+        print(decode(model.generate(idx, max_new_tokens=args.sample, **sample_kw)[0].tolist()))
         if not args.no_save:
             os.makedirs(args.model_dir, exist_ok=True)
             path = get_model_path(args.model_dir, args.model, args.scale)

@@ -359,6 +359,40 @@ int dg_attn_bwd_fp8(const void* qkv, const void* out, const void* dout, const fl
 int dg_attn_decode(const void* qkv_cache, void* out, int B, int Tcap, int t, int NH, int H,
                    float scale, int dtype, void* stream);
 
+/* dg_attn_decode with t = L - 1 read from the decode state (4 device uint32 in the rng_state format, {seed_lo, seed_hi, L, 0},
+ * L = current length of the sequence; dg_state_advance does L += 1), so that a captured decode step replays for every token --
+ * ref: src/model.py:625-635.  The new token's q/k/v row arrives in the fixed staging buffer qkv_row [B, 3*NH*H]; the kernel
+ * writes it into qkv_cache[b, t] and attends over keys 0..t with dg_attn_decode's arithmetic and order (fp32 decoding stays
+ * bit-identical to the uncached forward).  L == 0 or L - 1 >= Tcap: nothing is read or written. */
+int dg_attn_decode_append(const void* qkv_row, void* qkv_cache, void* out, const uint32_t* state, int B, int Tcap,
+                          int NH, int H, float scale, int dtype, void* stream);
+
+/* The embedding of a decode step, position read from the decode state -- ref: src/model.py:625 (crop to the context window)
+ * + :595-597.  ids: int64 [B, ld_ids], the sequence so far in columns 0..L-1; pos has Tw rows (the context length).
+ *   mode 0: x[b, :]    = tok[ids[b, L-1]] + pos[L-1]             (one position; 1 <= L <= Tw)
+ *   mode 1: x[b, i, :] = tok[ids[b, L-Tw+i]] + pos[i], i < Tw    (the full sliding window; L >= Tw)
+ * ids are clamped to [0, V) as in dg_embed_fwd.  An L outside the mode's range or beyond ld_ids writes nothing. */
+int dg_embed_window(const int64_t* ids, int64_t ld_ids, const uint32_t* state, const float* tok, const float* pos,
+                    float* x, int B, int Tw, int C, int V, int mode, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Sampling on the device -- ref: src/model.py:625-635: F.softmax at :631 and torch.multinomial at :633, with the temperature
+ * and top-k filter every GPT sampler has.  One token per row of fp32 logits [M, V] (leading dimension ldl; columns V..ldl-1
+ * are never read).  params (device): {float inv_temp, int32 top_k}, read by the kernel so that a captured graph picks up new
+ * settings.  state: the decode state {seed_lo, seed_hi, L, 0}.
+ *   inv_temp > 0:  z_j = logits_j * inv_temp (fp32).   inv_temp == 0: greedy -- the lowest index among the maxima, no random
+ *                  number consumed, probs one-hot.
+ *   top_k == 0 (or >= V): off; else tau = the k-th largest z and every j with z_j >= tau is kept (ties at the threshold are all
+ *                  kept).  -inf logits are never kept and never sampled.
+ *   e_j = exp(z_j - max z) for kept j (the subtraction in fp32, exp and everything after it in fp64), else 0;  S = sum e_j;  p_j = e_j / S.
+ *   u = (h >> 8) * 2^-24,  h = dg_hash_w(dg_site_key(seed_lo, seed_hi, L, DG_SITE_SAMPLE = 0x53414D50), row * DG_WEYL)
+ *   token = the smallest n with sum_{j <= n} e_j > u * S; if rounding leaves none, the last kept index.
+ * Outputs (each nullable, not both): ids int64 -- ld_ids > 0: row m's token goes to ids[m * ld_ids + L] (not written when
+ * L >= ld_ids); ld_ids == 0: to ids[m] -- and probs [M, ldp] fp32, the filtered distribution p.  state may be NULL without ids.
+ * One workgroup per row, no floating-point atomics: the result is a pure function of (logits, state, params, row).  V <= 2^20. */
+int dg_sample_rows(const float* logits, int64_t ldl, int M, int V, const uint32_t* state, const void* params,
+                   int64_t* ids, int64_t ld_ids, float* probs, int64_t ldp, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Cross entropy, mean over rows -- ref: F.cross_entropy at src/model.py:604-607 (K16).
  * loss_rows[m] = logsumexp(logits[m,:]) - logits[m,target[m]].  If dlogits != NULL also writes
