@@ -9,6 +9,9 @@
 //      wave order), S = the last prefix
 //   4. the thread whose prefix interval holds u * S walks its chunk again and writes the token; all threads write probs
 // z and z - max are single fp32 roundings (__fmul_rn / __fsub_rn: never contracted into an fma), so a host restatement can match.
+//   2b. dg_sample_rows_nucleus only (four-word params): min-p keeps e_j >= min_p; top-p finds tau_p by a second radix descent whose
+//      LDS histograms hold INTEGER masses w_j = rint(e_j * 2^40) (64-bit integer atomics: sums do not depend on arrival order).
+//      Neither costs a pass when it is off: min-p alone is one more compare in passes 3 and 4.
 // No floating-point atomics anywhere: tokens and probs are a pure function of (logits, state, params, row).
 // exp and the prefix sums are fp64: with a few terms kept by top-k the errors of an fp32 expf do not average out of S (measured:
 // probs off by 4.5 x 2^-24 at k = 40), and fp64 is cheap here -- a few passes over one row.  The CDF is then exact to ~1e-14.
@@ -17,6 +20,7 @@
 #define DG_SITE_SAMPLE 0x53414D50u      // "SAMP": not of the form 4 * layer + k for any layer a model can have
 
 struct SampleParams { float inv_temp; int32_t top_k; };
+struct SampleParamsEx { float inv_temp; int32_t top_k; float top_p; float min_p; };      // dg_sample_rows_nucleus: the same first two words
 
 __device__ __forceinline__ uint32_t f32_key(float z) {          // a < b  <=>  key(a) < key(b)  (no NaNs)
     const uint32_t b = __float_as_uint(z);
@@ -26,7 +30,8 @@ __device__ __forceinline__ float key_f32(uint32_t k) {
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
 }
 
-template <int NT>
+// EXT: params is a SampleParamsEx and the top-p / min-p stage exists; !EXT is dg_sample_rows as it always was
+template <int NT, bool EXT>
 __global__ __launch_bounds__(NT) void sample_rows_kernel(const float* __restrict__ logits, int64_t ldl, int M, int V,
                                                          const uint32_t* __restrict__ state, const SampleParams* __restrict__ params,
                                                          int64_t* __restrict__ ids, int64_t ld_ids, float* __restrict__ probs,
@@ -38,6 +43,8 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const float* __restrict
     __shared__ uint32_t s_sel[2];          // {key prefix, k still to find below it}
     __shared__ double s_wtot[NW];
     __shared__ int s_owner, s_last;
+    __shared__ unsigned long long s_mass[EXT ? 256 : 1];
+    __shared__ uint32_t s_psel[2];         // {key prefix of tau_p, a bin was found}
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int row = blockIdx.x;
     const float* x = logits + (int64_t)row * ldl;
@@ -117,13 +124,79 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const float* __restrict
         tau = key_f32(s_sel[0]);
     }
 
+    // kept before top-p (K1 of the header): z >= tau, never -inf, and with min-p e >= min_p; e is computed on the way
+    double minp = 0.0; bool use_minp = false;
+    auto kept = [&](float z, double& e) -> bool {
+        if (!(z >= tau && z > -INFINITY)) return false;
+        e = exp((double)__fsub_rn(z, mx));
+        if constexpr (EXT) { if (use_minp && !(e >= minp)) return false; }
+        return true;
+    };
+
+    // ---- pass 2b: tau_p = the lowest z whose mass above it, G(z) = sum { w_i : z_i > z }, is < T = top_p * S1 (as doubles)
+    if constexpr (EXT) {
+        const SampleParamsEx* px = (const SampleParamsEx*)params;
+        const float top_p = px->top_p, min_p = px->min_p;
+        use_minp = min_p > 0.f;
+        minp = (double)fminf(min_p, 1.f);                       // the maximum (e = 1) always stays
+        if (top_p > 0.f && top_p < 1.f) {
+            // The same 4 x 8-bit descent as top-k, over histograms of mass.  A bin holds a kept key iff its mass is > 0 and the
+            // mass above the bin is < T: its highest key with mass has exactly that G.  Keys with w = 0 need no count of their own:
+            // every key below them has w = 0 too, so their G is S1, and (double)S1 > T for any fp32 top_p < 1.
+            // Level 0 sees every element of K1, so its histogram total is S1: no pass of its own.
+            if (tid == 0) { s_psel[0] = 0u; s_psel[1] = 0u; }
+            double T = 0.0; unsigned long long carried = 0ull;      // live in wave 0 only
+            for (int shift = 24; shift >= 0; shift -= 8) {
+                for (int i = tid; i < 256; i += NT) s_mass[i] = 0ull;
+                __syncthreads();
+                const uint32_t prefix = s_psel[0];
+                const uint32_t himask = shift == 24 ? 0u : (0xFFFFFFFFu << (shift + 8));
+                for (int i = tid; i < V; i += NT) {
+                    const float z = __fmul_rn(x[i], sc);
+                    const uint32_t key = f32_key(z);
+                    double e;
+                    if (((key ^ prefix) & himask) == 0u && kept(z, e)) {
+                        const unsigned long long wj = (unsigned long long)rint(e * 0x1p40);
+                        if (wj) atomicAdd(&s_mass[(key >> shift) & 255u], wj);
+                    }
+                }
+                __syncthreads();
+                if (w == 0) {
+                    // lane l owns bins 4l .. 4l + 3; a3 .. a0 = the mass above each of them
+                    const unsigned long long m0 = s_mass[4 * lane], m1 = s_mass[4 * lane + 1], m2 = s_mass[4 * lane + 2],
+                                             m3 = s_mass[4 * lane + 3];
+                    const unsigned long long m = m0 + m1 + m2 + m3;
+                    unsigned long long suf = m;                // inclusive suffix sum over lanes >= lane
+#pragma unroll
+                    for (int o = 1; o < 64; o <<= 1) { const unsigned long long t = __shfl_down(suf, o, 64); if (lane + o < 64) suf += t; }
+                    if (shift == 24) T = (double)top_p * (double)__shfl(suf, 0, 64);
+                    const unsigned long long a3 = carried + (suf - m), a2 = a3 + m3, a1 = a2 + m2, a0 = a1 + m1;
+                    int bin = -1; unsigned long long A = 0ull;  // this lane's lowest bin that holds a kept key
+                    if (m0 && (double)a0 < T) { bin = 4 * lane; A = a0; }
+                    else if (m1 && (double)a1 < T) { bin = 4 * lane + 1; A = a1; }
+                    else if (m2 && (double)a2 < T) { bin = 4 * lane + 2; A = a2; }
+                    else if (m3 && (double)a3 < T) { bin = 4 * lane + 3; A = a3; }
+                    const unsigned long long have = __ballot(bin >= 0);
+                    if (have) {                                 // none: no finite logit in the row -- no filter, as without top-p
+                        const int src = __ffsll(have) - 1;
+                        carried = __shfl(A, src, 64);
+                        if (lane == src) { s_psel[0] = prefix | ((uint32_t)bin << shift); s_psel[1] = 1u; }
+                    }
+                }
+                __syncthreads();
+            }
+            if (s_psel[1]) tau = fmaxf(tau, key_f32(s_psel[0]));
+        }
+    }
+
     // ---- pass 3: chunk sums in index order, fp64, and their scan
     const int chunk = (V + NT - 1) / NT;
     const int j0 = min(tid * chunk, V), j1 = min(j0 + chunk, V);
     double csum = 0.0; int last = -1;
     for (int j = j0; j < j1; ++j) {
         const float z = __fmul_rn(x[j], sc);
-        if (z >= tau && z > -INFINITY) { csum += exp((double)__fsub_rn(z, mx)); last = j; }
+        double e;
+        if (kept(z, e)) { csum += e; last = j; }
     }
     double incl = csum;
 #pragma unroll
@@ -140,7 +213,8 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const float* __restrict
     if (prow) {
         for (int i = tid; i < V; i += NT) {
             const float z = __fmul_rn(x[i], sc);
-            prow[i] = (z >= tau && z > -INFINITY) ? (float)(exp((double)__fsub_rn(z, mx)) / S) : 0.f;
+            double e;
+            prow[i] = kept(z, e) ? (float)(e / S) : 0.f;
         }
     }
     if (!write_tok) return;
@@ -159,15 +233,17 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const float* __restrict
     double run = excl; int tok = last;                         // last: if re-adding from excl rounds below target
     for (int j = j0; j < j1; ++j) {
         const float z = __fmul_rn(x[j], sc);
-        if (z >= tau && z > -INFINITY) {
-            run += exp((double)__fsub_rn(z, mx));
+        double e;
+        if (kept(z, e)) {
+            run += e;
             if (run > target) { tok = j; break; }
         }
     }
     *tok_out = tok;
 }
 
-extern "C" int dg_sample_rows(const float* logits, int64_t ldl, int M, int V, const uint32_t* state, const void* params,
+template <bool EXT>
+static int sample_rows_launch(const float* logits, int64_t ldl, int M, int V, const uint32_t* state, const void* params,
                               int64_t* ids, int64_t ld_ids, float* probs, int64_t ldp, void* stream) {
     if (!logits || !params || M <= 0 || V <= 0 || V > (1 << 20) || ldl < V || ld_ids < 0) return DG_ERR_ARG;
     if (!ids && !probs) return DG_ERR_ARG;
@@ -177,9 +253,19 @@ extern "C" int dg_sample_rows(const float* logits, int64_t ldl, int M, int V, co
     const SampleParams* p = (const SampleParams*)params;
     // a chunk of at most 32 (small rows) or V / 1024 (52 at V = 53248) elements per thread
     if (V <= 8192)
-        hipLaunchKernelGGL(sample_rows_kernel<256>, dim3(M), dim3(256), 0, s, logits, ldl, M, V, state, p, ids, ld_ids, probs, ldp);
+        hipLaunchKernelGGL((sample_rows_kernel<256, EXT>), dim3(M), dim3(256), 0, s, logits, ldl, M, V, state, p, ids, ld_ids, probs, ldp);
     else
-        hipLaunchKernelGGL(sample_rows_kernel<1024>, dim3(M), dim3(1024), 0, s, logits, ldl, M, V, state, p, ids, ld_ids, probs, ldp);
+        hipLaunchKernelGGL((sample_rows_kernel<1024, EXT>), dim3(M), dim3(1024), 0, s, logits, ldl, M, V, state, p, ids, ld_ids, probs, ldp);
     DG_LAUNCH_CHECK();
     return DG_OK;
+}
+
+extern "C" int dg_sample_rows(const float* logits, int64_t ldl, int M, int V, const uint32_t* state, const void* params,
+                              int64_t* ids, int64_t ld_ids, float* probs, int64_t ldp, void* stream) {
+    return sample_rows_launch<false>(logits, ldl, M, V, state, params, ids, ld_ids, probs, ldp, stream);
+}
+
+extern "C" int dg_sample_rows_nucleus(const float* logits, int64_t ldl, int M, int V, const uint32_t* state, const void* params,
+                                      int64_t* ids, int64_t ld_ids, float* probs, int64_t ldp, void* stream) {
+    return sample_rows_launch<true>(logits, ldl, M, V, state, params, ids, ld_ids, probs, ldp, stream);
 }

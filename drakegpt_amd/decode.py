@@ -11,7 +11,8 @@ it, the sampler writes token L into the ids buffer and dg_state_advance moves L 
       (TransformerLM._forward_rows), lm_head on the last row, sample_rows, state_advance
 
 Graphs hold raw pointers, so the decoder owns every operand: staged copies of the weights (refreshed on every generate call),
-the K/V caches, the ids buffer, the state and the sampler parameters.
+the K/V caches, the ids buffer, the state and the sampler parameters (always the four-word block of dg_sample_rows_nucleus:
+temperature, top_k, top_p and min_p change between calls without a new capture).
 """
 from __future__ import annotations
 
@@ -37,7 +38,8 @@ class DeviceDecoder:
         self.cap = max(ctx + 1, (min_cap + 255) // 256 * 256)
         self.ids = torch.zeros((B, self.cap), dtype=torch.int64, device=device)
         self.state = torch.zeros(4, dtype=torch.int32, device=device)
-        self.params = ops.new_sample_params(1.0, None, device)
+        # four words {inv_temp, top_k, top_p, min_p}: the captured sampler is dg_sample_rows_nucleus, whatever the call asks for
+        self.params = ops.new_sample_params(1.0, None, device, top_p=1.0, min_p=0.0)
         self.caches = [torch.zeros((B, ctx, 3 * C), dtype=self.act, device=device) for _ in model.blocks]
         self.row = torch.zeros((B, 3 * C), dtype=self.act, device=device)       # staging: the new token's q/k/v
         self.ws = self.w_lm = self.tok = self.pos = self.lm_bias = None

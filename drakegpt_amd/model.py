@@ -71,6 +71,29 @@ def check_sampling_args(sampler, temperature, top_k, vocab_size: int):
     return t, top_k
 
 
+def check_nucleus_args(top_p, min_p):
+    """the checks of generate()'s top_p / min_p, like check_sampling_args: plain Python, raised before anything touches a
+    device.  Returns (top_p, min_p) as floats, None where left out."""
+    def number(x, name):
+        if isinstance(x, bool):
+            raise ValueError(f"generate: {name} must be a number, got {x!r}")
+        try:
+            return float(x)
+        except (TypeError, ValueError):
+            raise ValueError(f"generate: {name} must be a number, got {x!r}") from None
+    if top_p is not None:
+        p = number(top_p, "top_p")
+        if not (math.isfinite(p) and 0.0 < p <= 1.0):
+            raise ValueError(f"generate: top_p must be in (0, 1] (or None), got {top_p!r}")
+        top_p = p
+    if min_p is not None:
+        p = number(min_p, "min_p")
+        if not 0.0 <= p <= 1.0:
+            raise ValueError(f"generate: min_p must be in [0, 1] (or None), got {min_p!r}")
+        min_p = p
+    return top_p, min_p
+
+
 def draw_seed(generator: Optional[torch.Generator]) -> int:
     """one sampling seed from the CPU generator (the global one unless `generator` is given)"""
     return int(torch.randint(0, 2 ** 62, (1,), generator=generator))
@@ -127,26 +150,32 @@ class _LM(HipModule):
 
     @staticmethod
     def _probs(logits, params):
-        """params None: the plain softmax (the reference's distribution); else the temperature / top-k filtered one"""
+        """params None: the plain softmax (the reference's distribution); else the temperature / top-k / top-p / min-p filtered one"""
         if params is None:
             return ops.softmax_rows(logits)
         return ops.sample_rows(logits, params=params, tokens=False, probs=True)
 
     @staticmethod
-    def _host_params(device, temperature, top_k):
-        return None if temperature == 1.0 and top_k is None else ops.new_sample_params(temperature, top_k, device)
+    def _host_params(device, temperature, top_k, top_p=None, min_p=None):
+        if temperature == 1.0 and top_k is None and top_p is None and min_p is None:
+            return None
+        return ops.new_sample_params(temperature, top_k, device, top_p=top_p, min_p=min_p)
 
     def generate(self, idx, max_new_tokens, generator: Optional[torch.Generator] = None, *, sampler: str = "host",
-                 temperature: float = 1.0, top_k: Optional[int] = None, seed: Optional[int] = None):
+                 temperature: float = 1.0, top_k: Optional[int] = None, seed: Optional[int] = None,
+                 top_p: Optional[float] = None, min_p: Optional[float] = None):
         """ref: src/model.py:611-636.  sampler="host" (default): softmax runs on the GPU; torch.multinomial runs on the host CPU
         generator (the global one unless `generator` is given), as it does in the reference on CPU.  A temperature other than 1
-        (0 = greedy) or a top_k filters the distribution on the GPU first (dg_sample_rows).
+        (0 = greedy) or a top_k filters the distribution on the GPU first (dg_sample_rows); so do top_p (nucleus: the most
+        likely tokens whose mass reaches top_p, ties kept) and min_p (tokens at least min_p times as likely as the best one),
+        applied after top_k (dg_sample_rows_nucleus).
         sampler="device": the tokens are drawn by dg_sample_rows from a counter-based stream keyed by `seed` (drawn once from the
         CPU generator when None) and the sequence length, and never leave the GPU inside the loop."""
         temperature, top_k = check_sampling_args(sampler, temperature, top_k, self.token_embedding_table.weight.shape[0])
+        top_p, min_p = check_nucleus_args(top_p, min_p)
         if sampler == "device":
-            return self._generate_device(idx, max_new_tokens, generator, temperature, top_k, seed)
-        params = self._host_params(idx.device, temperature, top_k)
+            return self._generate_device(idx, max_new_tokens, generator, temperature, top_k, seed, top_p=top_p, min_p=min_p)
+        params = self._host_params(idx.device, temperature, top_k, top_p, min_p)
         for _ in range(max_new_tokens):
             cond = idx if self.context_length is None else idx[:, -self.context_length:]
             probs = self._last_probs(cond.contiguous(), params)
@@ -154,7 +183,7 @@ class _LM(HipModule):
             idx = torch.cat((idx, nxt.to(idx.device)), dim=1)
         return idx
 
-    def _decode_begin(self, idx, max_new_tokens, generator, temperature, top_k, seed, ids=None):
+    def _decode_begin(self, idx, max_new_tokens, generator, temperature, top_k, seed, ids=None, top_p=None, min_p=None):
         """shared start of the device-sampler paths: checks the prompt once, returns (ids buffer, decode state, params)"""
         ops._chk(idx, "idx", torch.int64, contiguous=False)
         if idx.dim() != 2 or idx.shape[1] < 1:
@@ -166,13 +195,14 @@ class _LM(HipModule):
         if ids is None:
             ids = torch.zeros((B, t0 + max_new_tokens), dtype=torch.int64, device=idx.device)
         ids[:, :t0] = idx
-        return ids, ops.new_rng_state(int(seed), idx.device, step=t0), ops.new_sample_params(temperature, top_k, idx.device)
+        params = ops.new_sample_params(temperature, top_k, idx.device, top_p=top_p, min_p=min_p)
+        return ids, ops.new_rng_state(int(seed), idx.device, step=t0), params
 
     @torch.no_grad()
-    def _generate_device(self, idx, max_new_tokens, generator, temperature, top_k, seed):
+    def _generate_device(self, idx, max_new_tokens, generator, temperature, top_k, seed, *, top_p=None, min_p=None):
         """the reference algorithm (full forward on the cropped window per token) with the sampler on the device: the kernel writes
         token L into ids[:, L]; no host copy or sync inside the loop (the ids were range-checked once, sampled ids are in range)."""
-        ids, state, params = self._decode_begin(idx, max_new_tokens, generator, temperature, top_k, seed)
+        ids, state, params = self._decode_begin(idx, max_new_tokens, generator, temperature, top_k, seed, top_p=top_p, min_p=min_p)
         t0, ctx = idx.shape[1], self.context_length
         had = "check_ids" in self.__dict__
         saved = self.check_ids
@@ -356,25 +386,28 @@ class TransformerLM(_BlocksLM):
         return self._forward_rows(x, B, t0, caches, ws, w_lm)
 
     def generate(self, idx, max_new_tokens, generator: Optional[torch.Generator] = None, use_cache: bool = True, *,
-                 sampler: str = "host", temperature: float = 1.0, top_k: Optional[int] = None, seed: Optional[int] = None):
+                 sampler: str = "host", temperature: float = 1.0, top_k: Optional[int] = None, seed: Optional[int] = None,
+                 top_p: Optional[float] = None, min_p: Optional[float] = None):
         """ref: src/model.py:611-636.  While the sequence still fits the context window the per-layer K/V of the
         tokens seen so far are kept (training layout, [B, ctx, 3C]) and only the new position is computed; once the
         window starts to slide every position embedding shifts, the cache is void, and decoding continues exactly
         as the reference does (full forward on the cropped window).  Dropout is off in both paths only in eval()
         mode -- like the reference, train() mode samples with dropout through the uncached path.
-        sampler / temperature / top_k / seed: as in _LM.generate.  sampler="device" in eval() mode with use_cache=True replays one
-        captured graph per token (decode.DeviceDecoder): no host work inside the loop."""
+        sampler / temperature / top_k / seed / top_p / min_p: as in _LM.generate.  sampler="device" in eval() mode with
+        use_cache=True replays one captured graph per token (decode.DeviceDecoder): no host work inside the loop, and the same
+        graphs for every setting of the sampler."""
         temperature, top_k = check_sampling_args(sampler, temperature, top_k, self.token_embedding_table.weight.shape[0])
-        kw = dict(sampler=sampler, temperature=temperature, top_k=top_k, seed=seed)
+        top_p, min_p = check_nucleus_args(top_p, min_p)
+        kw = dict(sampler=sampler, temperature=temperature, top_k=top_k, seed=seed, top_p=top_p, min_p=min_p)
         if sampler == "device":
             if not use_cache or self.training:
-                return self._generate_device(idx, max_new_tokens, generator, temperature, top_k, seed)
-            return self._generate_device_cached(idx, max_new_tokens, generator, temperature, top_k, seed)
+                return self._generate_device(idx, max_new_tokens, generator, temperature, top_k, seed, top_p=top_p, min_p=min_p)
+            return self._generate_device_cached(idx, max_new_tokens, generator, temperature, top_k, seed, top_p=top_p, min_p=min_p)
         if not use_cache or self.training or idx.shape[1] >= self.context_length:
             return super().generate(idx, max_new_tokens, generator, **kw)
         B, t0 = idx.shape
         self._check_ids(idx, None)
-        params = self._host_params(idx.device, temperature, top_k)
+        params = self._host_params(idx.device, temperature, top_k, top_p, min_p)
         C3 = 3 * self.token_embedding_table.weight.shape[1]
         ws, w_lm = self._decode_weights()
         caches = [torch.zeros((B, self.context_length, C3), dtype=self.act_dtype, device=idx.device) for _ in self.blocks]
@@ -400,7 +433,8 @@ class TransformerLM(_BlocksLM):
         return d
 
     @torch.no_grad()
-    def _generate_device_cached(self, idx, max_new_tokens, generator, temperature, top_k, seed, graph: bool = True):
+    def _generate_device_cached(self, idx, max_new_tokens, generator, temperature, top_k, seed, graph: bool = True, *,
+                                top_p=None, min_p=None):
         """eager one-pass prefill, sample, advance; then one step per token on the device position L: the K/V-cached step while
         L <= ctx, the full-window step after that.  graph=True replays the two captured graphs of decode.DeviceDecoder;
         graph=False launches the very same steps eagerly."""
@@ -418,7 +452,9 @@ class TransformerLM(_BlocksLM):
         dec.refresh(self)                      # a generate() after an optimizer step sees the new weights
         if graph:
             dec.capture()
-        _, state, params = self._decode_begin(idx, max_new_tokens, generator, temperature, top_k, seed, ids=dec.ids)
+        # the decoder's block always has four words (filters off: top_p 1, min_p 0), so one capture serves every setting
+        _, state, params = self._decode_begin(idx, max_new_tokens, generator, temperature, top_k, seed, ids=dec.ids,
+                                              top_p=1.0 if top_p is None else top_p, min_p=0.0 if min_p is None else min_p)
         dec.state.copy_(state)
         dec.params.copy_(params)
         L = t0

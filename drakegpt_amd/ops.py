@@ -754,21 +754,32 @@ def softmax_rows(logits: Tensor) -> Tensor:
     return probs
 
 
-def new_sample_params(temperature: float, top_k: Optional[int], device) -> Tensor:
-    """device {float inv_temp, int32 top_k} of sample_rows (stored as two int32 bit patterns).  temperature 0 = greedy
-    (inv_temp 0); top_k None / 0 = off.  inv_temp is 1 / temperature rounded to fp32."""
+def _f32_bits(x: float) -> int:
     import struct
+    return struct.unpack("<i", struct.pack("<f", x))[0]
+
+
+def new_sample_params(temperature: float, top_k: Optional[int], device, *, top_p: Optional[float] = None,
+                      min_p: Optional[float] = None) -> Tensor:
+    """device {float inv_temp, int32 top_k} of sample_rows (stored as two int32 bit patterns).  temperature 0 = greedy
+    (inv_temp 0); top_k None / 0 = off.  inv_temp is 1 / temperature rounded to fp32.
+    With a top_p or a min_p: the four-word block {inv_temp, top_k, float top_p, float min_p} of dg_sample_rows_nucleus
+    (top_p None = 1 = off, min_p None = 0 = off)."""
     inv = 0.0 if temperature == 0 else 1.0 / float(temperature)
-    bits = struct.unpack("<i", struct.pack("<f", inv))[0]
-    return torch.tensor([bits, int(top_k or 0)], dtype=torch.int32, device=device)
+    words = [_f32_bits(inv), int(top_k or 0)]
+    if top_p is not None or min_p is not None:
+        # a top_p below the smallest fp32 must not round to 0, which the kernel takes as "off": it keeps the maximum alone
+        words += [_f32_bits(1.0 if top_p is None else max(float(top_p), 2.0 ** -149)), _f32_bits(0.0 if min_p is None else float(min_p))]
+    return torch.tensor(words, dtype=torch.int32, device=device)
 
 
 def sample_rows(logits: Tensor, state: Optional[Tensor] = None, params: Optional[Tensor] = None, *, seed: Optional[int] = None,
                 L: Optional[int] = None, temperature: float = 1.0, top_k: Optional[int] = None, ids: Optional[Tensor] = None,
-                tokens: bool = True, probs: bool = False):
-    """one token per row of fp32 logits [M, V] (dg_sample_rows; include/drakegpt_hip.h states the semantics).
+                tokens: bool = True, probs: bool = False, top_p: Optional[float] = None, min_p: Optional[float] = None):
+    """one token per row of fp32 logits [M, V] (dg_sample_rows, or dg_sample_rows_nucleus when params has four words;
+    include/drakegpt_hip.h states the semantics).
     state: decode state int32[4] {seed_lo, seed_hi, L, 0} (new_rng_state(seed, device, step=L)); built from seed / L when None.
-    params: new_sample_params(...); built from temperature / top_k when None.
+    params: new_sample_params(...); built from temperature / top_k / top_p / min_p when None.
     ids [B, cap] int64: row m's token is written to ids[m, L] by the kernel (nothing is returned for it); otherwise, with
     tokens=True, a new int64 [M] tensor is returned.  probs=True also returns the filtered distribution [M, V].
     Returns tokens, probs, (tokens, probs) or None according to what was asked for."""
@@ -780,10 +791,12 @@ def sample_rows(logits: Tensor, state: Optional[Tensor] = None, params: Optional
     if not want_tok and not probs:
         raise ValueError("sample_rows: nothing to compute (tokens=False, probs=False)")
     if params is None:
-        params = new_sample_params(temperature, top_k, logits.device)
+        params = new_sample_params(temperature, top_k, logits.device, top_p=top_p, min_p=min_p)
     _chk(params, "params", torch.int32)
-    if params.numel() != 2:
-        raise RuntimeError("sample_rows: params must hold {inv_temp, top_k}")
+    if params.numel() not in (2, 4):
+        raise RuntimeError("sample_rows: params must hold {inv_temp, top_k} or {inv_temp, top_k, top_p, min_p}")
+    entry, name = (lib.dg_sample_rows, "dg_sample_rows") if params.numel() == 2 else (lib.dg_sample_rows_nucleus,
+                                                                                      "dg_sample_rows_nucleus")
     if want_tok:
         if state is None:
             if seed is None or L is None:
@@ -802,8 +815,8 @@ def sample_rows(logits: Tensor, state: Optional[Tensor] = None, params: Optional
         out_tok = torch.empty((M,), dtype=torch.int64, device=logits.device)
         tok_ptr = _p(out_tok)
     p_out = torch.empty((M, V), dtype=torch.float32, device=logits.device) if probs else None
-    check(lib.dg_sample_rows(_p(logits), _ld(logits), M, V, _p(state) if want_tok else None, _p(params), tok_ptr, ld_ids,
-                             _p(p_out), V, _stream()), "dg_sample_rows")
+    check(entry(_p(logits), _ld(logits), M, V, _p(state) if want_tok else None, _p(params), tok_ptr, ld_ids, _p(p_out), V, _stream()),
+          name)
     if out_tok is not None and probs:
         return out_tok, p_out
     return out_tok if out_tok is not None else p_out

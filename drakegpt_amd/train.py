@@ -136,6 +136,10 @@ def build_parser() -> argparse.ArgumentParser:
                     "work per token)")
     ap.add_argument("--temperature", type=float, default=1.0, help="sampling temperature of that sample (0 = greedy)")
     ap.add_argument("--top-k", type=int, default=None, help="keep only the k most likely tokens of that sample (default: off)")
+    ap.add_argument("--top-p", type=float, default=None, help="nucleus filter of that sample: keep the most likely tokens whose mass "
+                    "reaches this share, in (0, 1] (default: off)")
+    ap.add_argument("--min-p", type=float, default=None, help="keep only tokens at least this many times as likely as the best one, "
+                    "in [0, 1] (default: off)")
     ap.add_argument("--grad-clip", type=float, default=None, metavar="MAX_NORM",
                     help="clip the gradient to this global 2-norm before every AdamW step (ref: clip_grad_norm_; default: off); each "
                     "evaluation line then also reports the last step's pre-clip norm as grad_norm")
@@ -243,8 +247,8 @@ def main(argv=None):
     if rank == 0:
         idx = torch.zeros((1, 1), dtype=torch.long, device=device)
         sample_kw = {}
-        if (args.sampler, args.temperature, args.top_k) != ("host", 1.0, None):
-            sample_kw = dict(sampler=args.sampler, temperature=args.temperature, top_k=args.top_k)
+        if (args.sampler, args.temperature, args.top_k, args.top_p, args.min_p) != ("host", 1.0, None, None, None):
+            sample_kw = dict(sampler=args.sampler, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, min_p=args.min_p)
         print(decode(model.generate(idx, max_new_tokens=args.sample, **sample_kw)[0].tolist()))
         if not args.no_save:
             os.makedirs(args.model_dir, exist_ok=True)

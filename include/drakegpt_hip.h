@@ -393,6 +393,24 @@ int dg_embed_window(const int64_t* ids, int64_t ld_ids, const uint32_t* state, c
 int dg_sample_rows(const float* logits, int64_t ldl, int M, int V, const uint32_t* state, const void* params,
                    int64_t* ids, int64_t ld_ids, float* probs, int64_t ldp, void* stream);
 
+/* dg_sample_rows with a top-p (nucleus) and a min-p filter after top-k.  params (device, four words):
+ * {float inv_temp, int32 top_k, float top_p, float min_p}; everything else as dg_sample_rows.  0 < top_p <= 1, 1 = off;
+ * 0 <= min_p <= 1, 0 = off (the kernel takes a top_p outside (0, 1) as off and a min_p above 1 as 1).  Greedy ignores both.
+ *   K0 = the set top-k keeps (z_j >= tau_k, never -inf), e_j = exp((double)(z_j - max z)) as above.
+ *   min-p:  K1 = { j in K0 : e_j >= (double)min_p }.  The maximum has e = 1: K1 is never empty.
+ *   top-p:  integer masses, so that no result depends on a summation order:
+ *             w_j = rint(e_j * 2^40) as uint64 for j in K1, else 0;   S1 = sum w_j  (exact: V <= 2^20 gives S1 <= 2^60);
+ *             G(t) = sum { w_i : i in K1, z_i > t };   T = (double)top_p * (double)S1;
+ *             K = { j in K1 : (double)G(z_j) < T }.
+ *           G depends on j only through z_j and is monotone, so K is a threshold set z_j >= tau_p and ties at the threshold are
+ *           all kept: in a descending sort, the shortest prefix whose mass reaches top_p of the mass left by top-k and min-p,
+ *           plus its ties.
+ *   Then as dg_sample_rows on K: S = sum_{j in K} e_j in fp64 in index order, p_j = e_j / S on K, else 0, the same u and the
+ *   same token rule.  Rows without a finite logit behave as in dg_sample_rows.
+ * With top_p == 1 and min_p == 0 tokens and probs are bit-identical to dg_sample_rows; a filter that is off costs no pass. */
+int dg_sample_rows_nucleus(const float* logits, int64_t ldl, int M, int V, const uint32_t* state, const void* params,
+                           int64_t* ids, int64_t ld_ids, float* probs, int64_t ldp, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Cross entropy, mean over rows -- ref: F.cross_entropy at src/model.py:604-607 (K16).
  * loss_rows[m] = logsumexp(logits[m,:]) - logits[m,target[m]].  If dlogits != NULL also writes

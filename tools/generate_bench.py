@@ -3,13 +3,15 @@
 the reference's inference.py default, N = 1000 new tokens from a one-token prompt.
 
     python tools/generate_bench.py [--sampler host|device] [--precision fp32 bf16] [--batch 1] [--tokens 1000] [--repeats 3]
+                                   [--top-p P] [--min-p P] [--vocab 80]
 
 Two phases are reported separately.  With a one-token prompt the first ctx tokens are made while the sequence still fits the
 window (one prefill, then K/V-cached steps); the rest by the sliding-window algorithm (a full forward per token).  The first
 phase is timed as a call that stops at ctx tokens, the second as the difference between the full call and that one (the
 per-call set-up cancels), each as the median of --repeats calls that alternate between the two lengths.
 --sampler host passes no keyword that an older generate() does not have, so this file also times a commit without the device
-sampler.  One JSON line per precision.
+sampler; --top-p / --min-p are passed only when given, for the same reason.  --vocab widens the vocabulary (50257: the sampler
+at a GPT-2 row).  One JSON line per precision.
 """
 import argparse
 import json
@@ -32,14 +34,21 @@ def main():
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--tokens", type=int, default=1000)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--top-p", type=float, default=None)
+    ap.add_argument("--min-p", type=float, default=None)
+    ap.add_argument("--vocab", type=int, default=80)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("generate_bench needs the GPU: a timing taken anywhere else says nothing")
     cfg = PRESETS["scaled"]
     dev = torch.device("cuda:0")
-    V, C, T, NH, NL = 80, cfg["embedding_dim"], cfg["context_length"], cfg["num_heads"], cfg["num_layers"]
+    V, C, T, NH, NL = args.vocab, cfg["embedding_dim"], cfg["context_length"], cfg["num_heads"], cfg["num_layers"]
     n_cached = min(args.tokens, T)
     kw = {} if args.sampler == "host" else dict(sampler="device", seed=1234)
+    if args.top_p is not None:
+        kw["top_p"] = args.top_p
+    if args.min_p is not None:
+        kw["min_p"] = args.min_p
     for precision in args.precision:
         torch.manual_seed(42)
         m = D.TransformerLM(V, C, T, NH, NL, cfg["dropout"], precision=precision).to(dev).eval()
@@ -62,7 +71,7 @@ def main():
             full.append(timed(args.tokens))
         t_short, t_full = statistics.median(short), statistics.median(full)
         line = {"tool": "generate_bench", "sampler": args.sampler, "precision": precision, "batch": args.batch,
-                "tokens": args.tokens, "ctx": T, "repeats": args.repeats,
+                "vocab": V, "top_p": args.top_p, "min_p": args.min_p, "tokens": args.tokens, "ctx": T, "repeats": args.repeats,
                 "total_s": round(t_full, 4), "total_tok_per_s": round(args.batch * args.tokens / t_full, 1),
                 "cached_tokens": n_cached, "cached_s": round(t_short, 4),
                 "cached_tok_per_s": round(args.batch * n_cached / t_short, 1),
