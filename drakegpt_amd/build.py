@@ -37,6 +37,7 @@ SOURCES = [
     "chain.hip",
     "chain_bwd.hip",
     "grad_clip.hip",
+    "grad_accum.hip",
     "sample.hip",
 ]
 

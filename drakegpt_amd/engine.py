@@ -31,7 +31,7 @@ import torch
 from . import ops
 from . import sublayers as S
 from .model import TransformerLM
-from .optim import check_max_grad_norm
+from .optim import check_accum_steps, check_max_grad_norm
 
 Tensor = torch.Tensor
 ALIGN = 64          # floats: every tensor starts on a 256-byte boundary of the flat buffer
@@ -178,7 +178,7 @@ class TrainEngine:
                  lr: float = 1e-3, betas=(0.9, 0.95), eps: float = 1e-8, weight_decay: float = 1e-2,
                  seed: int = 42, rank: int = 0, world_size: int = 1, process_group=None, use_graph: bool = True,
                  dp_buckets: Optional[int] = None, logits: str = "auto", grad_stream: str = "auto", fp8_dw: Optional[bool] = None,
-                 max_grad_norm: Optional[float] = None):
+                 max_grad_norm: Optional[float] = None, accum_steps: int = 1):
         if not isinstance(model, TransformerLM):
             raise TypeError("TrainEngine drives TransformerLM (the other five models train through the autograd path)")
         p0 = next(model.parameters())
@@ -207,6 +207,11 @@ class TrainEngine:
         self.rank, self.world, self.pg = rank, world_size, process_group
         self.use_graph = use_graph
         self._dp_buckets_arg = dp_buckets
+        # gradient accumulation: accum_steps micro-batches per AdamW step (1: nothing below exists, the step is what it always was)
+        self.accum = check_accum_steps(accum_steps)
+        if self.accum > 1 and dp_buckets is not None and int(dp_buckets) > 1:
+            raise ValueError("accum_steps > 1 uses one gradient exchange per optimizer step (it is amortised over the micro-steps "
+                             "already): dp_buckets > 1 cannot be combined with it")
         import os as _os
         if logits == "auto" and _os.environ.get("DG_LOGITS") in ("fp32", "bf16"):      # A/B runs
             logits = _os.environ["DG_LOGITS"]
@@ -277,6 +282,17 @@ class TrainEngine:
             self.last_grad_norm = self.clip_state[0]          # 0-d view: the pre-clip norm of the latest step
         # dropout stream differs per data-parallel rank; the step word also drives Adam's bias correction
         self.state = ops.new_rng_state(seed + 0x9E3779B97F4A7C15 * rank & 0xFFFFFFFFFFFFFFFF, self.dev, 0)
+        # accum_steps = k > 1: TWO counters.  state[2] becomes the micro-step word (dropout key, staged offset row, fp8 amax slot:
+        # all of them move once per micro-batch; dg_grad_accumulate moves it on), opt_state[2] counts optimizer steps and is
+        # AdamW's t.  gacc holds the sum of the micro-batch gradients, acc_ctl = {j, k, arrival, 0} the position inside the
+        # optimizer step (_j is its host mirror), loss_acc = {sum of the micro losses, their mean after the k-th}.
+        self.gacc = self.acc_ctl = self.opt_state = self.loss_acc = None
+        self._j = 0
+        if self.accum > 1:
+            self.gacc = torch.zeros(self.n_active, dtype=torch.float32, device=self.dev)
+            self.acc_ctl = ops.new_accum_ctl(self.accum, self.dev)
+            self.opt_state = ops.new_rng_state(0, self.dev, 0)
+            self.loss_acc = torch.zeros(2, dtype=torch.float32, device=self.dev)
         # window offsets: a staged block [rows, B] the captured step walks through by itself (row = step word - off_ctl[0],
         # clamped to off_ctl[1] rows); set_offsets() is the one-row form (row 0, off_ctl[1] = 1)
         self.off_block = torch.zeros((self.OFFSET_ROWS, self.B), dtype=torch.int64, device=self.dev)
@@ -333,6 +349,8 @@ class TrainEngine:
         (652 MB / 1.6 GB) -- and not for the 43 MB of the scaled model, whose whole exchange is ~0.4 ms over xGMI while every
         cut costs a graph seam and a less well filled dW launch."""
         import os
+        if self.accum > 1:
+            return 1
         if arg is None and os.environ.get("DG_DP_BUCKETS"):
             arg = int(os.environ["DG_DP_BUCKETS"])
         if not self.grouped_dw or (self.world == 1 and arg is None):
@@ -375,21 +393,28 @@ class TrainEngine:
             n *= d
         return self.flat[off:off + n].view(shape)
 
-    def grad_view(self, key: str) -> Tensor:
+    def grad_view(self, key: str, buf: Optional[Tensor] = None) -> Tensor:
         off, shape = self._region(key)
         n = 1
         for d in shape:
             n *= d
-        return self.gflat[off:off + n].view(shape)
+        return (self.gflat if buf is None else buf)[off:off + n].view(shape)
 
     def named_grads(self) -> Dict[str, Tensor]:
         """the step's gradient as views of the flat buffer, keyed by the reference's parameter names (what `p.grad` holds after
         `loss.backward()` in ref: src/train.py:150; after a data-parallel step: the SUM over ranks).  `ln_f.*` is absent: it never
-        receives a gradient."""
+        receives a gradient.
+        accum_steps = k > 1: views of the accumulator -- the SUM over the micro-batch gradients taken so far in this optimizer
+        step (all k of them after the k-th micro_step(), and over ranks after its exchange); divide by k for the mean gradient
+        the optimizer applied, which is what `p.grad` holds after k x `(loss / k).backward()`."""
         NH, H = self.NH, self.H
         out: Dict[str, Tensor] = {}
+        _gv = self.grad_view
+        if self.accum > 1:
+            def _gv(key):
+                return self.grad_view(key, self.gacc)
         for l in range(self.L):
-            wqkv = self.grad_view(f"{l}.wqkv")
+            wqkv = _gv(f"{l}.wqkv")
             pre = f"blocks.{l}."
             for h in range(NH):
                 out[f"{pre}sa_head.heads.{h}.key.weight"] = wqkv[(NH + h) * H:(NH + h + 1) * H]
@@ -398,10 +423,10 @@ class TrainEngine:
             for ref, key in (("sa_head.proj.weight", "wproj"), ("sa_head.proj.bias", "bproj"), ("ffwd.net.0.weight", "w1"),
                              ("ffwd.net.0.bias", "b1"), ("ffwd.net.2.weight", "w2"), ("ffwd.net.2.bias", "b2"),
                              ("ln1.weight", "ln1w"), ("ln1.bias", "ln1b"), ("ln2.weight", "ln2w"), ("ln2.bias", "ln2b")):
-                out[pre + ref] = self.grad_view(f"{l}.{key}")
-        out["lm_head.weight"], out["lm_head.bias"] = self.grad_view("lm.w"), self.grad_view("lm.b")
-        out["token_embedding_table.weight"] = self.grad_view("tok")
-        out["position_embedding_table.weight"] = self.grad_view("pos")
+                out[pre + ref] = _gv(f"{l}.{key}")
+        out["lm_head.weight"], out["lm_head.bias"] = _gv("lm.w"), _gv("lm.b")
+        out["token_embedding_table.weight"] = _gv("tok")
+        out["position_embedding_table.weight"] = _gv("pos")
         return out
 
     def _alloc_and_adopt(self):
@@ -842,6 +867,25 @@ class TrainEngine:
             segs.append(seg)
         return segs, [r for _, r in plan]
 
+    def _prog_micro(self):
+        """accum_steps > 1: one micro-batch -- the step's forward / backward, then its gradient and loss into the accumulators; that
+        launch also moves the micro-step word on (nothing behind it reads the word)"""
+        self._prog_fwd_bwd()
+        ops.grad_accumulate(self.gacc, self.gflat, self.n_active, self.acc_ctl, self.loss, self.loss_acc, self.state)
+
+    def _prog_update_accum(self):
+        """accum_steps = k > 1: _prog_update on the accumulated gradient -- norm and AdamW on gacc * 1 / (k * world), the mean over
+        micro-batches and ranks, with the optimizer's own step counter as t"""
+        scale = 1.0 / (self.accum * self.world)
+        if self.clip_state is None:
+            ops.adamw_step(self.flat, self.gacc, self.m_, self.v_, self.hyper, self.opt_state, scale,
+                           shadow_bf16=self.shadow, n=self.n_active, advance=True)
+        else:
+            ops.grad_norm(self.gacc, scale, self.clip_state[2:3], self.clip_state, self.norm_work)
+            ops.adamw_step(self.flat, self.gacc, self.m_, self.v_, self.hyper, self.opt_state, scale,
+                           shadow_bf16=self.shadow, n=self.n_active, advance=True, clip=self.clip_state[1:2])
+        self._refresh_transposes()
+
     def _prog_update(self):
         # (the step word moves on inside the AdamW launch: nothing after it reads the word)
         if self.clip_state is None:
@@ -862,7 +906,8 @@ class TrainEngine:
     def _allreduce(self):
         if self._dp():
             import torch.distributed as dist
-            dist.all_reduce(self.gflat, op=dist.ReduceOp.SUM, group=self.pg)     # mean = sum * 1/world in AdamW
+            # mean = sum * 1/world in AdamW (accum_steps > 1: the accumulated gradient, once per optimizer step)
+            dist.all_reduce(self.gflat if self.accum == 1 else self.gacc, op=dist.ReduceOp.SUM, group=self.pg)
 
     def _allreduce_ranges_async(self, ranges, works: list) -> None:
         """start the SUM all-reduce of finished ranges of the flat gradient.  RCCL enqueues it on its own stream behind the work
@@ -874,6 +919,31 @@ class TrainEngine:
                 works.append(dist.all_reduce(self.gflat[lo:hi], op=dist.ReduceOp.SUM, group=self.pg, async_op=True))
 
     # -------------------------------------------------------------------------------- capture
+    def _capture_accum(self):
+        """accum_steps > 1: one micro graph and one update graph in the same pool; the warm-up runs each program once and every
+        buffer and counter it moves is put back"""
+        bufs = (self.flat, self.m_, self.v_, self.state, self.gacc, self.acc_ctl, self.opt_state, self.loss_acc)
+        snap = [b.clone() for b in bufs]
+        j = self._j
+        side = torch.cuda.Stream(device=self.dev)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):       # warm-up: loads every code object and allocates the dW workspaces before capture
+            self._prog_micro()
+            self._prog_update_accum()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize(self.dev)
+        for b, s in zip(bufs, snap):
+            b.copy_(s)
+        self._j = j
+        self.refresh_shadows()
+        torch.cuda.synchronize(self.dev)
+        g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g1):
+            self._prog_micro()
+        with torch.cuda.graph(g2, pool=g1.pool()):
+            self._prog_update_accum()
+        self._graphs = (g1, g2)
+
     def _capture(self):
         snap = (self.flat.clone(), self.m_.clone(), self.v_.clone(), self.state.clone())
         side = torch.cuda.Stream(device=self.dev)
@@ -953,6 +1023,13 @@ class TrainEngine:
         counter, so a training loop is nothing but graph launches between two stagings"""
         if block.dim() != 2 or block.shape[1] != self.B or block.shape[0] < 1:
             raise ValueError(f"stage_offsets: need [n >= 1, B = {self.B}] offsets")
+        if self.accum > 1:
+            # one row per micro-step: optimizer step s after this call consumes rows s * k .. s * k + k - 1
+            if block.shape[0] % self.accum:
+                raise ValueError(f"stage_offsets: {block.shape[0]} rows are no multiple of accum_steps = {self.accum}")
+            if self._j:
+                raise RuntimeError(f"stage_offsets: {self._j} of {self.accum} micro-steps of the current optimizer step are taken; "
+                                   "finish it with micro_step() first")
         if not block.is_cuda:
             self.check_offsets(block)
         n = block.shape[0]
@@ -981,8 +1058,52 @@ class TrainEngine:
         self.x.copy_(x, non_blocking=True)
         self.y.copy_(y, non_blocking=True)
 
+    def micro_step(self) -> Tensor:
+        """one micro-batch on the current offsets / batch: forward, backward, its gradient added into the accumulator; returns the
+        micro-batch's loss (device scalar).  The accum_steps-th call also runs the gradient exchange (one all-reduce of the
+        accumulated gradient) and the optimizer update on the mean gradient.  accum_steps == 1: the same as step()."""
+        if self.accum == 1:
+            return self.step()
+        if self._off_left is not None:
+            if self._off_left <= 0:
+                raise RuntimeError(f"micro_step(): the {self._off_rows} staged offset rows are used up; stage_offsets() or set_offsets() first")
+            self._off_left -= 1
+        if self.use_graph and self._graphs is None:
+            self._capture_accum()
+        if self.use_graph:
+            self._graphs[0].replay()
+        else:
+            self._prog_micro()
+        self._j += 1
+        if self._j == self.accum:
+            self._j = 0
+            self._allreduce()
+            if self.use_graph:
+                self._graphs[1].replay()
+            else:
+                self._prog_update_accum()
+        return self.loss
+
+    def _step_accum(self) -> Tensor:
+        k = self.accum
+        if self.corpus is None or self._off_left is None:
+            raise RuntimeError(f"step() with accum_steps = {k} runs {k} micro-batches and needs {k} staged offset rows "
+                               "(set_corpus + stage_offsets); with batches given by set_batch() / set_offsets() call micro_step() "
+                               "once per batch -- step() would use the same batch for every micro-step")
+        if self._j:
+            raise RuntimeError(f"step(): {self._j} of {k} micro-steps of the current optimizer step are taken; finish it with micro_step()")
+        if self._off_left < k:
+            raise RuntimeError(f"step(): {self._off_left} of the {self._off_rows} staged offset rows are left, one optimizer step "
+                               f"needs {k}; stage_offsets() first")
+        for _ in range(k):
+            self.micro_step()
+        return self.loss_acc[1]
+
     def step(self) -> Tensor:
-        """one training iteration on the current offsets / batch; returns the device loss scalar"""
+        """one training iteration on the current offsets / batch; returns the device loss scalar.  accum_steps = k > 1: k
+        micro-steps on the next k staged offset rows and one optimizer update; returns the mean of their losses."""
+        if self.accum > 1:
+            return self._step_accum()
         if self._off_left is not None:
             if self._off_left <= 0:
                 raise RuntimeError(f"step(): the {self._off_rows} staged offset rows are used up; stage_offsets() or set_offsets() first")
@@ -1096,4 +1217,9 @@ class TrainEngine:
                 raise RuntimeError("dg_gemm_tn_grouped: a split-K hand-over timed out; weight gradients since then are invalid")
 
     def step_count(self) -> int:
+        """optimizer steps taken"""
+        return int((self.state if self.accum == 1 else self.opt_state)[2].item())
+
+    def micro_step_count(self) -> int:
+        """micro-batches run: the word that keys dropout and selects the staged offset row (== step_count() for accum_steps 1)"""
         return int(self.state[2].item())

@@ -916,6 +916,41 @@ def grad_norm(gs, grad_scale: float, max_norm: Tensor, out: Tensor, work: Option
     return out
 
 
+def new_accum_ctl(k: int, device) -> Tensor:
+    """device uint32[4] = {j = 0, k, arrival counter = 0, 0} for grad_accumulate (stored as int32); k = accum_steps is validated here,
+    on the host: the launch itself never looks at it again"""
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1 or k >= (1 << 31):
+        raise ValueError(f"new_accum_ctl: k must be an integer >= 1, got {k!r}")
+    return torch.tensor([0, k, 0, 0], dtype=torch.int32, device=device)
+
+
+def grad_accumulate(acc: Tensor, g: Tensor, n: Optional[int], ctl: Tensor, loss: Optional[Tensor] = None,
+                    loss_out: Optional[Tensor] = None, rng_state: Optional[Tensor] = None) -> None:
+    """one micro-step of gradient accumulation (dg_grad_accumulate): acc[0, n) = g (ctl[0] == 0) or acc + g (one fp32 add per
+    element), loss_out = {running sum of loss, its mean over k on the last micro-step}; the launch moves ctl[0] on to
+    (j + 1) mod k and, given rng_state, its step word to step + 1.  ctl comes from new_accum_ctl(k, device)."""
+    _chk(acc, "acc", torch.float32)
+    _chk(g, "g", torch.float32)
+    _chk(ctl, "ctl", torch.int32)
+    n = acc.numel() if n is None else int(n)
+    if n < 1 or n > acc.numel() or n > g.numel():
+        raise ValueError(f"grad_accumulate: n = {n} does not fit acc ({acc.numel()}) and g ({g.numel()})")
+    if ctl.numel() < 4:
+        raise ValueError("grad_accumulate: ctl needs 4 words {j, k, arrival, 0} (new_accum_ctl)")
+    if (loss is None) != (loss_out is None):
+        raise ValueError("grad_accumulate: loss and loss_out go together")
+    if loss is not None:
+        _chk(loss, "loss", torch.float32)
+        _chk(loss_out, "loss_out", torch.float32)
+        if loss.numel() < 1 or loss_out.numel() < 2:
+            raise ValueError("grad_accumulate: loss needs 1 float, loss_out 2 {sum, mean}")
+    if rng_state is not None:
+        _chk(rng_state, "rng_state", torch.int32)
+        if rng_state.numel() < 4:
+            raise ValueError("grad_accumulate: rng_state needs 4 words")
+    check(lib.dg_grad_accumulate(_p(acc), _p(g), n, _p(ctl), _p(loss), _p(loss_out), _p(rng_state), _stream()), "dg_grad_accumulate")
+
+
 def block_chain_supported(M: int, C: int, dtype: torch.dtype) -> bool:
     """can dg_block_chain_fwd run this shape?  (bf16 operands, C = 384, M % 64 == 0)"""
     return dtype == torch.bfloat16 and bool(lib.dg_block_chain_supported(int(M), int(C)))

@@ -37,6 +37,13 @@ def check_max_grad_norm(v) -> float:
     return f
 
 
+def check_accum_steps(v) -> int:
+    """accum_steps (micro-batches per optimizer step) must be an integer >= 1: no bools, no floats (2.0 is a typo, not a count)"""
+    if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+        raise ValueError(f"accum_steps must be an integer >= 1, got {v!r}")
+    return int(v)
+
+
 class _Flat:
     def __init__(self, params, device):
         self.key = tuple(id(p) for p in params)

@@ -32,6 +32,7 @@ import torch
 from . import dist as ddist
 from .config import DRAKE_VOCAB_SIZE, PARAMS, PRESETS, SCALE_PARAMS, TRAIN
 from .model import MODEL_CLASSES, model_params
+from .optim import check_accum_steps
 from .preprocessing import draw_offsets, encode_text, get_mapper, load_train_val_data, split_train_val
 
 
@@ -95,18 +96,21 @@ def evaluate_loss(train_data, val_data, model, eval_iters, context_length, batch
 
 
 def engine_loop(engine, n_train: int, T: int, B: int, rank: int, world: int, iters: int, eval_interval: int, on_eval, device,
-                generator: Optional[torch.Generator] = None) -> None:
+                generator: Optional[torch.Generator] = None, accum_steps: int = 1) -> None:
     """The training iterations of ref: src/train.py:141-172 on the engine path.  The reference draws one randint(len(data) - T,
     (B,)) per step from the global CPU generator and, every eval_interval steps, 2 * eval_iters more inside evaluate_loss --
     the SAME generator.  Here the offsets of all steps up to the next evaluation are drawn in one go (same draws, same order:
     a stage never crosses an evaluation) and staged in HBM once (TrainEngine.stage_offsets): the captured step finds its own row
     through the device-side step counter, so a step is one graph launch and nothing else.
-    `on_eval(it)` runs after step `it` when (it + 1) % eval_interval == 0."""
+    `on_eval(it)` runs after step `it` when (it + 1) % eval_interval == 0.
+    accum_steps = K > 1 (an engine built with the same accum_steps): an iteration is one optimizer step on K micro-batches; it
+    draws K blocks of B * world offsets, in the order a loop of K get_batch calls would, so a stage holds K * n rows and
+    `iters` / `eval_interval` count optimizer steps."""
     for it in range(iters):
         if it % eval_interval == 0:
             n = min(eval_interval, iters - it)
             engine.stage_offsets(torch.stack([ddist.shard_rows(draw_offsets(n_train, T, B * world, generator), rank, world)
-                                              for _ in range(n)]))
+                                              for _ in range(n * accum_steps)]))
         engine.step()
         if (it + 1) % eval_interval == 0:
             on_eval(it)
@@ -143,11 +147,15 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--grad-clip", type=float, default=None, metavar="MAX_NORM",
                     help="clip the gradient to this global 2-norm before every AdamW step (ref: clip_grad_norm_; default: off); each "
                     "evaluation line then also reports the last step's pre-clip norm as grad_norm")
+    ap.add_argument("--accum-steps", type=int, default=1, metavar="K",
+                    help="gradient accumulation: K micro-batches of batch_size rows per AdamW step (the effective batch is K * "
+                    "batch_size * world_size; --iters and --eval-interval count optimizer steps; default 1)")
     return ap
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    K = check_accum_steps(args.accum_steps)
 
     torch.manual_seed(42)
     if not torch.cuda.is_available():
@@ -192,7 +200,7 @@ def main(argv=None):
     if args.model == "TransformerLM":
         from .engine import TrainEngine
         engine = TrainEngine(model, B, T, lr=base_lr, betas=params["betas"], seed=42, rank=rank, world_size=world, process_group=pg,
-                             max_grad_norm=args.grad_clip)
+                             max_grad_norm=args.grad_clip, accum_steps=K)
         engine.set_corpus(train_dev)
     else:
         # the five earlier-stage models train through the autograd path; their flat-buffer AdamW all-reduces the gradient
@@ -222,7 +230,7 @@ def main(argv=None):
         if rank == 0:
             el = time.perf_counter() - t0
             line = {"step": it + 1, "train_loss": float(losses["train"]), "val_loss": float(losses["val"]), "lr": lr,
-                    "tokens_per_s": (it + 1) * B * T * world / el}
+                    "tokens_per_s": (it + 1) * K * B * T * world / el}
             if args.grad_clip is not None:
                 # the last step's pre-clip norm: the evaluation has synchronised the stream already
                 line["grad_norm"] = float((engine if engine is not None else optimizer).last_grad_norm)
@@ -230,15 +238,24 @@ def main(argv=None):
         model.train()
 
     if engine is not None:
-        engine_loop(engine, len(train_data), T, B, rank, world, args.iters, args.eval_interval, on_eval, device)
+        engine_loop(engine, len(train_data), T, B, rank, world, args.iters, args.eval_interval, on_eval, device, accum_steps=K)
     else:
         from . import ops
         for it in range(args.iters):
-            ix = ddist.shard_rows(draw_offsets(len(train_data), T, B * world, None), rank, world).to(device, non_blocking=True)
-            x, y = ops.batch_gather(train_dev, ix, T)
-            logits, loss = model(x, y)
-            optimizer.zero_grad()
-            loss.backward()
+            if K == 1:
+                ix = ddist.shard_rows(draw_offsets(len(train_data), T, B * world, None), rank, world).to(device, non_blocking=True)
+                x, y = ops.batch_gather(train_dev, ix, T)
+                logits, loss = model(x, y)
+                optimizer.zero_grad()
+                loss.backward()
+            else:
+                # K micro-batches per step: autograd sums (loss / K).backward() into .grad -- the mean gradient over all K
+                optimizer.zero_grad()
+                for _ in range(K):
+                    ix = ddist.shard_rows(draw_offsets(len(train_data), T, B * world, None), rank, world).to(device, non_blocking=True)
+                    x, y = ops.batch_gather(train_dev, ix, T)
+                    logits, loss = model(x, y)
+                    (loss / K).backward()
             optimizer.step()
             if (it + 1) % args.eval_interval == 0:
                 on_eval(it)

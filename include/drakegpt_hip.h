@@ -478,6 +478,22 @@ int dg_adamw_step_clip(float* p, const float* g, float* m, float* v, int64_t n, 
                        float grad_scale, const float* clip_coef, void* shadow_bf16, int advance_step, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Gradient accumulation -- ref: k x `(loss / k).backward()` summing into p.grad between two optimizer.step() calls.  One
+ * streaming pass per micro-step over the flat fp32 gradient g[0, n) of that micro-batch:
+ *   ctl (4 device uint32) = {j, k, arrival counter, 0}: j = micro-step inside the current optimizer step, k = accum_steps >= 1
+ *   j == 0: acc[i] = g[i]  (acc is not read: it never needs a zero fill; 8 B/param)      j > 0: acc[i] = acc[i] + g[i]  (12 B/param)
+ * exactly one fp32 add per element (no scale, no FMA), so acc holds the SUM of the micro-batch gradients: pass
+ * grad_scale = 1 / k (times 1 / world_size) to dg_sumsq / dg_adamw_step for the mean.
+ * loss / loss_out (both given or both NULL; device fp32 [1] / [2]): loss_out[0] = (j == 0 ? loss[0] : loss_out[0] + loss[0]), and on
+ * the last micro-step (j == k - 1) loss_out[1] = loss_out[0] / k, the mean loss of the optimizer step.
+ * The launch moves the counters on itself, like dg_adamw_step's advance: the workgroup that finishes last clears ctl[2], writes
+ * ctl[0] = (j + 1 == k ? 0 : j + 1) and, with rng_state != NULL, rng_state[2] = step + 1 -- the micro-step word that keys dropout,
+ * the staged offset row and the fp8 amax slot (rng_state[3] is not touched).  ctl[2] is zero before and after every launch.
+ * DG_ERR_ARG: NULL acc / g / ctl, n <= 0, one of loss / loss_out alone.  DG_ERR_ALIGN: acc or g not 16-byte aligned. */
+int dg_grad_accumulate(float* acc, const float* g, int64_t n, uint32_t* ctl, const float* loss, float* loss_out,
+                       uint32_t* rng_state, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * The row-local chain of one residual block in ONE launch (bf16 operands, C = 384, M % 64 == 0) -- ref:
  * src/model_component.py:454 (proj) + :505 (x + ...), :506 + :488-489 (LayerNorm 2), :320-325 (FeedForward3), the second
  * residual add, and the NEXT block's :505 LayerNorm 1 + :392-393,404 (its 3 * NH per-head Linears as one packed operand):
