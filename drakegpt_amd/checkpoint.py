@@ -1,0 +1,188 @@
+"""Training-state files: what TrainEngine.state_dict() / the harness write, and the optimizer-format mapping behind them.
+
+Nothing here touches the GPU.  A training state is a nested dict of CPU tensors, ints, floats, strings, lists and None, so the
+file loads with ``torch.load(..., weights_only=True)`` like every other file of this project:
+
+    {"format": "drakegpt_amd.train_state", "version": 1,
+     "model": {...}, "optimizer": {...}, "engine": {...}, "meta": {...}}          # TrainEngine.state_dict()
+
+The harness (drakegpt_amd.train) wraps that in a dict of the same format / version with its own fields beside it.
+
+The optimizer part is torch.optim.AdamW's own format.  The engine keeps Adam's moments in flat buffers whose layout is keyed by
+region ("3.wqkv", "lm.w", "tok", ...: engine._build_layout); ``param_region`` says which rows of which region a reference
+parameter name is, ``region_params`` is its inverse, and ``optimizer_state_from_regions`` / ``regions_from_optimizer_state``
+move whole optimizer states between the two forms."""
+from __future__ import annotations
+
+import os
+import re
+import tempfile
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import torch
+
+Tensor = torch.Tensor
+FORMAT = "drakegpt_amd.train_state"
+VERSION = 1
+
+_BLOCK_KEYS = (("sa_head.proj.weight", "wproj"), ("sa_head.proj.bias", "bproj"), ("ffwd.net.0.weight", "w1"), ("ffwd.net.0.bias", "b1"),
+               ("ffwd.net.2.weight", "w2"), ("ffwd.net.2.bias", "b2"), ("ln1.weight", "ln1w"), ("ln1.bias", "ln1b"),
+               ("ln2.weight", "ln2w"), ("ln2.bias", "ln2b"))
+_TOP_KEYS = (("lm_head.weight", "lm.w"), ("lm_head.bias", "lm.b"), ("token_embedding_table.weight", "tok"),
+             ("position_embedding_table.weight", "pos"), ("ln_f.weight", "lnf.w"), ("ln_f.bias", "lnf.b"))
+_HEAD = re.compile(r"^blocks\.(\d+)\.sa_head\.heads\.(\d+)\.(query|key|value)\.weight$")
+_BLOCK = re.compile(r"^blocks\.(\d+)\.(.+)$")
+_QKV = {"query": 0, "key": 1, "value": 2}          # order of the three groups of NH heads inside a layer's packed [3 NH H, C] operand
+UNTRAINED = ("lnf.w", "lnf.b")                     # regions the optimizer never touches (ln_f: no gradient)
+
+
+# ------------------------------------------------------------------------------------------ names <-> regions
+def param_region(name: str, num_heads: int, head_size: int) -> Tuple[str, Optional[Tuple[int, int]]]:
+    """(region key, rows) of a TransformerLM parameter under the reference's name.  rows is None when the parameter is the whole
+    region, else the [lo, hi) rows of the layer's packed QKV matrix that hold this head's query / key / value weight."""
+    m = _HEAD.match(name)
+    if m:
+        l, h, which = int(m.group(1)), int(m.group(2)), _QKV[m.group(3)]
+        if h >= num_heads:
+            raise KeyError(name)
+        lo = (which * num_heads + h) * head_size
+        return f"{l}.wqkv", (lo, lo + head_size)
+    m = _BLOCK.match(name)
+    if m:
+        for ref, key in _BLOCK_KEYS:
+            if m.group(2) == ref:
+                return f"{int(m.group(1))}.{key}", None
+        raise KeyError(name)
+    for ref, key in _TOP_KEYS:
+        if name == ref:
+            return key, None
+    raise KeyError(name)
+
+
+def region_params(key: str, num_heads: int, head_size: int) -> List[Tuple[str, Optional[Tuple[int, int]]]]:
+    """inverse of param_region: the reference parameter names inside a region, each with its rows (None: the whole region)"""
+    for ref, k in _TOP_KEYS:
+        if key == k:
+            return [(ref, None)]
+    l, _, k = key.partition(".")
+    if not l.isdigit():
+        raise KeyError(key)
+    if k == "wqkv":
+        out = []
+        for which, i in _QKV.items():
+            for h in range(num_heads):
+                lo = (i * num_heads + h) * head_size
+                out.append((f"blocks.{l}.sa_head.heads.{h}.{which}.weight", (lo, lo + head_size)))
+        return out
+    for ref, kk in _BLOCK_KEYS:
+        if k == kk:
+            return [(f"blocks.{l}.{ref}", None)]
+    raise KeyError(key)
+
+
+def _rows(t: Tensor, rows) -> Tensor:
+    return t if rows is None else t[rows[0]:rows[1]]
+
+
+def optimizer_state_from_regions(names: Sequence[str], regions: Dict[str, Tuple[Tensor, Tensor]], num_heads: int, head_size: int,
+                                 step: int, lr: float, betas, eps: float, weight_decay: float) -> dict:
+    """what torch.optim.AdamW(model.parameters(), ...) would save: `names` are model.named_parameters()'s names in order,
+    `regions` maps a region key to its (exp_avg, exp_avg_sq) tensors in the region's own shape.  A parameter whose region is
+    absent from `regions` (ln_f) gets no state entry, as in torch."""
+    state = {}
+    for i, name in enumerate(names):
+        key, rows = param_region(name, num_heads, head_size)
+        if key not in regions:
+            continue
+        m, v = regions[key]
+        state[i] = {"step": torch.tensor(float(step)), "exp_avg": _rows(m, rows).detach().cpu().clone(),
+                    "exp_avg_sq": _rows(v, rows).detach().cpu().clone()}
+    # the group as the installed torch writes it (its set of option keys changes between releases): ask torch itself
+    dummy = [torch.nn.Parameter(torch.zeros(1)) for _ in names]
+    groups = torch.optim.AdamW(dummy, lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps),
+                               weight_decay=float(weight_decay)).state_dict()["param_groups"]
+    return {"state": state, "param_groups": groups}
+
+
+def regions_from_optimizer_state(sd: dict, names: Sequence[str], num_heads: int, head_size: int):
+    """inverse of optimizer_state_from_regions, for a dict written by it, by torch.optim.AdamW or by drakegpt_amd.optim.AdamW
+    over the same model: ({region key: (exp_avg, exp_avg_sq)}, step, {"lr", "betas", "eps", "weight_decay"}).  Raises ValueError
+    if the parameters disagree about the step count, if the state does not fit `names`, or if a packed QKV region is only partly
+    present."""
+    groups = sd["param_groups"]
+    if len(groups) != 1:
+        raise ValueError(f"optimizer state: expected one parameter group, found {len(groups)}")
+    g = groups[0]
+    if list(g["params"]) != list(range(len(names))):
+        raise ValueError(f"optimizer state: the group lists {len(g['params'])} parameters, the model has {len(names)}")
+    state = sd["state"]
+    steps = sorted({int(float(st["step"])) for st in state.values()})
+    if len(steps) > 1:
+        raise ValueError(f"optimizer state: the parameters disagree about the step count: {steps}")
+    parts: Dict[str, list] = {}
+    for i, st in state.items():
+        i = int(i)
+        if not 0 <= i < len(names):
+            raise ValueError(f"optimizer state: entry {i} is outside the model's {len(names)} parameters")
+        key, rows = param_region(names[i], num_heads, head_size)
+        parts.setdefault(key, []).append((rows, st["exp_avg"].detach().cpu().float(), st["exp_avg_sq"].detach().cpu().float()))
+    regions = {}
+    for key, lst in parts.items():
+        if lst[0][0] is None:
+            regions[key] = (lst[0][1].clone(), lst[0][2].clone())
+            continue
+        lst.sort(key=lambda e: e[0][0])
+        if [e[0] for e in lst] != [(k * head_size, (k + 1) * head_size) for k in range(3 * num_heads)]:
+            raise ValueError(f"optimizer state: region {key} needs the query / key / value state of all {num_heads} heads")
+        regions[key] = (torch.cat([e[1] for e in lst]), torch.cat([e[2] for e in lst]))
+    hyper = {"lr": float(g["lr"]), "betas": (float(g["betas"][0]), float(g["betas"][1])), "eps": float(g["eps"]),
+             "weight_decay": float(g["weight_decay"])}
+    return regions, (steps[0] if steps else 0), hyper
+
+
+# ------------------------------------------------------------------------------------------ files
+def check_format(obj, what: str = "training state") -> None:
+    if not isinstance(obj, dict):
+        raise ValueError(f"{what}: expected a dict, found {type(obj).__name__}")
+    for field, own in (("format", FORMAT), ("version", VERSION)):
+        if field not in obj:
+            raise ValueError(f"{what}: missing key {field!r}")
+        if obj[field] != own:
+            raise ValueError(f"{what}: {field} is {obj[field]!r}, this package reads {own!r}")
+
+
+def check_compat(saved_meta: dict, own_meta: dict, what: str = "meta") -> None:
+    """every field of own_meta must be present in saved_meta with the same value; ValueError names the field and both values"""
+    for field, own in own_meta.items():
+        if field not in saved_meta:
+            raise ValueError(f"training state: missing key {what}.{field}")
+        saved = saved_meta[field]
+        if isinstance(own, (tuple, list)):
+            same = isinstance(saved, (tuple, list)) and list(saved) == list(own)
+        else:
+            same = type(saved) is type(own) and saved == own
+        if not same:
+            raise ValueError(f"training state: {what}.{field} differs: saved {saved!r}, this run has {own!r}")
+
+
+def save_train_state(path: str, obj: dict) -> None:
+    """write to a temporary file in the same directory, then os.replace: the previous file stays intact until the new one is
+    complete, and a failure leaves no temporary file behind"""
+    check_format(obj)
+    d = os.path.dirname(os.path.abspath(path))
+    os.makedirs(d, exist_ok=True)
+    fd, tmp = tempfile.mkstemp(dir=d, prefix=os.path.basename(path) + ".", suffix=".tmp")
+    os.close(fd)
+    try:
+        torch.save(obj, tmp)
+        os.replace(tmp, path)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.unlink(tmp)
+        raise
+
+
+def load_train_state(path: str) -> dict:
+    obj = torch.load(path, map_location="cpu", weights_only=True)
+    check_format(obj, f"training state {path}")
+    return obj

@@ -28,6 +28,7 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
+from . import checkpoint as CK
 from . import ops
 from . import sublayers as S
 from .model import TransformerLM
@@ -193,6 +194,8 @@ class TrainEngine:
         self.split_bf16 = bool(getattr(model, "split_bf16", False))
         self.fp8_sites: Dict[str, Tensor] = {}
         self._fp8_seeded = False
+        self._fp8_keep = False      # load_state_dict: the histories are loaded state, a capture warm-up must put them back
+        self._finite_work = None
         self.B = int(batch_size)
         self.T = int(context_length or model.context_length)
         if self.T > model.context_length:
@@ -271,6 +274,7 @@ class TrainEngine:
             self.chain_bwd = False
         self._alloc_and_adopt()
         self.hyper = torch.tensor([lr, betas[0], betas[1], eps, weight_decay], dtype=torch.float32, device=self.dev)
+        self.hyper_host = [float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay)]      # what state_dict() reports
         # global-norm gradient clipping (ref: clip_grad_norm_(model.parameters(), max_norm) before optimizer.step()): the norm of
         # the mean gradient over ranks, gflat[0, n_active) * 1 / world, is computed inside the step and its coefficient applied
         # inside the AdamW launch; gflat / named_grads() keep the unclipped gradient.  clip_state = {total_norm, coef, max_norm, 0}
@@ -281,7 +285,8 @@ class TrainEngine:
             self.norm_work = ops.grad_norm_workspace([self.gflat], self.dev)
             self.last_grad_norm = self.clip_state[0]          # 0-d view: the pre-clip norm of the latest step
         # dropout stream differs per data-parallel rank; the step word also drives Adam's bias correction
-        self.state = ops.new_rng_state(seed + 0x9E3779B97F4A7C15 * rank & 0xFFFFFFFFFFFFFFFF, self.dev, 0)
+        self.seed = int(seed)
+        self.state = ops.new_rng_state(self._rank_seed(self.seed), self.dev, 0)
         # accum_steps = k > 1: TWO counters.  state[2] becomes the micro-step word (dropout key, staged offset row, fp8 amax slot:
         # all of them move once per micro-batch; dg_grad_accumulate moves it on), opt_state[2] counts optimizer steps and is
         # AdamW's t.  gacc holds the sum of the micro-batch gradients, acc_ctl = {j, k, arrival, 0} the position inside the
@@ -314,6 +319,9 @@ class TrainEngine:
         self.keep_logits = False        # parity tests: keep the step's logits [M, V] alive as `last_logits` (also inside a captured graph)
         self.last_logits: Optional[Tensor] = None
         self.refresh_shadows()
+
+    def _rank_seed(self, seed: int) -> int:
+        return seed + 0x9E3779B97F4A7C15 * self.rank & 0xFFFFFFFFFFFFFFFF
 
     # -------------------------------------------------------------------------------- layout
     def _build_layout(self):
@@ -924,6 +932,7 @@ class TrainEngine:
         buffer and counter it moves is put back"""
         bufs = (self.flat, self.m_, self.v_, self.state, self.gacc, self.acc_ctl, self.opt_state, self.loss_acc)
         snap = [b.clone() for b in bufs]
+        hist = self._fp8_snapshot()
         j = self._j
         side = torch.cuda.Stream(device=self.dev)
         side.wait_stream(torch.cuda.current_stream())
@@ -934,6 +943,7 @@ class TrainEngine:
         torch.cuda.synchronize(self.dev)
         for b, s in zip(bufs, snap):
             b.copy_(s)
+        self._fp8_put_back(hist)
         self._j = j
         self.refresh_shadows()
         torch.cuda.synchronize(self.dev)
@@ -946,6 +956,7 @@ class TrainEngine:
 
     def _capture(self):
         snap = (self.flat.clone(), self.m_.clone(), self.v_.clone(), self.state.clone())
+        hist = self._fp8_snapshot()
         side = torch.cuda.Stream(device=self.dev)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):       # warm-up: loads every code object and allocates the dW workspaces before capture
@@ -958,6 +969,7 @@ class TrainEngine:
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize(self.dev)
         self.flat.copy_(snap[0]); self.m_.copy_(snap[1]); self.v_.copy_(snap[2]); self.state.copy_(snap[3])
+        self._fp8_put_back(hist)
         self.refresh_shadows()
         torch.cuda.synchronize(self.dev)
         if not self._dp():
@@ -997,6 +1009,7 @@ class TrainEngine:
         self._graphs = None
 
     def set_lr(self, lr: float):
+        self.hyper_host[0] = float(lr)
         self.hyper[0:1].fill_(float(lr))
 
     def set_max_grad_norm(self, max_norm: float):
@@ -1208,6 +1221,219 @@ class TrainEngine:
             self._eval_graph.replay()
             out[i:i + 1].copy_(self.ev_loss)
         return out
+
+    # -------------------------------------------------------------------------------- training state
+    def _meta(self) -> dict:
+        return {"precision": str(self.model.precision), "vocab_size": int(self.V), "embedding_dim": int(self.C), "num_layers": int(self.L),
+                "num_heads": int(self.NH), "model_context_length": int(self.model.context_length), "batch_size": self.B,
+                "context_length": self.T, "accum_steps": self.accum, "world_size": int(self.world), "dropout": self.p_drop}
+
+    def _param_names(self) -> List[str]:
+        return [n for n, _ in self.model.named_parameters()]
+
+    def _trained_keys(self) -> List[str]:
+        return [k for lay in (self.layA, self.layB, self.layE) for k in lay.entries]
+
+    def _fp8_snapshot(self):
+        """capture warm-up of an engine whose fp8 histories are loaded state: they are put back like flat / m_ / v_ / state (a
+        fresh engine's warm-up SEEDS them, and keeps what it seeded)"""
+        if not (self.fp8 and self._fp8_keep and self._fp8_seeded):
+            return None
+        return {k: v.clone() for k, v in self.fp8_sites.items()}
+
+    def _fp8_put_back(self, snap) -> None:
+        if snap:
+            for k, v in snap.items():
+                self.fp8_sites[k].copy_(v)
+
+    def is_finite(self) -> bool:
+        """are the weights and Adam's moments all finite?  The sum-of-squares launch of the gradient norm over flat, m_ and v_ and
+        one device round trip: ask before a good checkpoint is replaced by a diverged run's."""
+        if self._finite_work is None:
+            self._finite_work = ops.grad_norm_workspace([self.flat, self.m_, self.v_], self.dev)
+        return ops.all_finite([self.flat, self.m_, self.v_], self._finite_work)
+
+    def optimizer_state_dict(self) -> dict:
+        """Adam's state in torch.optim.AdamW's own format, as AdamW(model.parameters(), ...) would save it after step_count()
+        steps (CPU tensors; the per-head query / key / value moments are rows of the packed QKV region; ln_f has no entry;
+        before the first step `state` is empty, as torch's is).  Synchronises."""
+        step = self.step_count()
+        regions = {}
+        if step > 0:
+            m, v = self.m_.cpu(), self.v_.cpu()
+            regions = {k: (self.grad_view(k, m), self.grad_view(k, v)) for k in self._trained_keys()}
+        h = self.hyper_host
+        return CK.optimizer_state_from_regions(self._param_names(), regions, self.NH, self.H, step, h[0], (h[1], h[2]), h[3], h[4])
+
+    def _parse_optimizer_state(self, sd: dict):
+        """validate an optimizer state_dict against this engine; returns (m, v as CPU images of the flat buffers, step, hyper)"""
+        try:
+            regions, step, hyper = CK.regions_from_optimizer_state(sd, self._param_names(), self.NH, self.H)
+        except KeyError as e:
+            raise ValueError(f"optimizer state: missing key {e}") from None
+        keys = self._trained_keys()
+        for k in regions:
+            if k not in keys:
+                raise ValueError(f"optimizer state: {k} is not a trained region of this engine")
+        if step > 0 and set(regions) != set(keys):
+            raise ValueError(f"optimizer state: no moments for {sorted(set(keys) - set(regions))}")
+        m = torch.zeros(self.n_active, dtype=torch.float32)
+        v = torch.zeros(self.n_active, dtype=torch.float32)
+        for k, (rm, rv) in regions.items():
+            shape = self._region(k)[1]
+            if tuple(rm.shape) != shape or tuple(rv.shape) != shape:
+                raise ValueError(f"optimizer state: {k} has shape {tuple(rm.shape)}, this engine's is {shape}")
+            self.grad_view(k, m).copy_(rm)
+            self.grad_view(k, v).copy_(rv)
+        if not 0 <= step < (1 << 32):
+            raise ValueError(f"optimizer state: step count {step} does not fit the device-side step word")
+        return m, v, step, hyper
+
+    def _write_optimizer_state(self, m: Tensor, v: Tensor, step: int, hyper: dict) -> None:
+        self.m_.copy_(m)
+        self.v_.copy_(v)
+        self.hyper_host = [hyper["lr"], hyper["betas"][0], hyper["betas"][1], hyper["eps"], hyper["weight_decay"]]
+        self.hyper.copy_(torch.tensor(self.hyper_host, dtype=torch.float32))
+        word = self.state if self.accum == 1 else self.opt_state
+        word[2:3].copy_(ops.new_rng_state(0, self.dev, step)[2:3])
+
+    @torch.no_grad()
+    def load_optimizer_state_dict(self, sd: dict) -> None:
+        """moments, step count and hyper-parameters from optimizer_state_dict(), torch.optim.AdamW or drakegpt_amd.optim.AdamW over
+        the same model, written in place (captured graphs stay valid).  ValueError if the parameters disagree about the step
+        count or the state does not fit.  accum_steps == 1: the step word also keys dropout and selects the staged offset row,
+        so loading another step count moves those too -- load_state_dict() is the form that keeps every counter consistent."""
+        m, v, step, hyper = self._parse_optimizer_state(sd)
+        self._write_optimizer_state(m, v, step, hyper)
+
+    def state_dict(self) -> dict:
+        """everything a following step reads that an earlier step or call wrote, as CPU tensors and plain values (DESIGN.md
+        section 4 lists every buffer).  Synchronises; not for the hot path.  RuntimeError inside an optimizer step."""
+        if self._j:
+            raise RuntimeError(f"state_dict(): {self._j} of {self.accum} micro-steps of the current optimizer step are taken; finish it "
+                               "with micro_step() first (a half-filled gradient accumulator is not a state to save)")
+        torch.cuda.synchronize(self.dev)
+        used = 0 if self._off_left is None else self._off_rows - self._off_left
+        eng = {"seed": self.seed, "step_word": int(self.state[2].item()) & 0xFFFFFFFF,
+               "opt_step": None if self.accum == 1 else int(self.opt_state[2].item()) & 0xFFFFFFFF,
+               "acc_ctl": None if self.accum == 1 else self.acc_ctl.cpu(),
+               "max_grad_norm": self.max_grad_norm,
+               "offsets": self.off_block[used:self._off_rows].cpu(), "offsets_rows": self._off_rows, "offsets_left": self._off_left,
+               "fp8_seeded": bool(self._fp8_seeded),
+               "fp8_sites": {k: v.cpu() for k, v in self.fp8_sites.items()} if self.fp8 else {}}
+        return {"format": CK.FORMAT, "version": CK.VERSION,
+                "model": {k: v.detach().cpu().clone() for k, v in self.model.state_dict().items()},
+                "optimizer": self.optimizer_state_dict(), "engine": eng, "meta": self._meta()}
+
+    _ENGINE_KEYS = ("seed", "step_word", "opt_step", "acc_ctl", "max_grad_norm", "offsets", "offsets_rows", "offsets_left",
+                    "fp8_seeded", "fp8_sites")
+
+    @torch.no_grad()
+    def load_state_dict(self, sd: dict) -> None:
+        """continue the run state_dict() was taken from: the next step() is the step that run would have taken next.  Everything is
+        validated before anything is written (ValueError names the field and both values; the engine is untouched then), and
+        written in place: the model's Parameters stay views of `flat` and captured graphs stay valid (a staged block larger than
+        the offset buffer is the one exception, as in stage_offsets).  Hyper-parameters follow the file; clipping on / off follows
+        this engine, its threshold the file where both clip.  Every rank loads rank 0's file; the dropout stream is re-derived
+        from the saved seed for this rank.  precision fp8: a rank other than 0 seeds its amax histories afresh."""
+        CK.check_format(sd)
+        for k in ("model", "optimizer", "engine", "meta"):
+            if k not in sd:
+                raise ValueError(f"training state: missing key {k!r}")
+        CK.check_compat(sd["meta"], self._meta())
+        e = sd["engine"]
+        for k in self._ENGINE_KEYS:
+            if k not in e:
+                raise ValueError(f"training state: missing key engine.{k}")
+        own = self.model.state_dict()
+        for k, t in own.items():
+            if k not in sd["model"]:
+                raise ValueError(f"training state: missing key model.{k}")
+            if tuple(sd["model"][k].shape) != tuple(t.shape):
+                raise ValueError(f"training state: model.{k} has shape {tuple(sd['model'][k].shape)}, this model's is {tuple(t.shape)}")
+        for k in sd["model"]:
+            if k not in own:
+                raise ValueError(f"training state: model.{k} is not a tensor of this model")
+        m, v, step, hyper = self._parse_optimizer_state(sd["optimizer"])
+        word = int(e["step_word"])
+        opt_step = word if self.accum == 1 else e["opt_step"]
+        if opt_step is None or int(opt_step) != step:
+            raise ValueError(f"training state: engine step count differs: the engine section says {opt_step!r}, the optimizer state {step}")
+        if self.accum > 1:
+            ctl = e["acc_ctl"]
+            if ctl is None or tuple(ctl.shape) != (4,) or ctl.dtype != torch.int32 or ctl.tolist()[:2] != [0, self.accum]:
+                raise ValueError(f"training state: engine.acc_ctl is {None if ctl is None else ctl.tolist()!r}, this engine needs "
+                                 f"[0, {self.accum}, ...] (saved between two optimizer steps)")
+        left, rows, offs = e["offsets_left"], int(e["offsets_rows"]), e["offsets"]
+        n = 1 if left is None else int(left)
+        if offs.dim() != 2 or offs.dtype != torch.int64 or tuple(offs.shape) != (n, self.B) or not 0 <= n <= max(rows, 1):
+            raise ValueError(f"training state: engine.offsets is {tuple(offs.shape)} {offs.dtype}, expected {(n, self.B)} int64 "
+                             f"({left!r} of {rows} staged rows left)")
+        if self.corpus is not None and n:
+            lo, hi = (int(x) for x in torch.aminmax(offs))
+            if lo < 0 or hi + self.T + 1 > self.corpus.numel():
+                raise ValueError(f"training state: engine.offsets in [{lo}, {hi}] do not fit this engine's corpus of "
+                                 f"{self.corpus.numel()} tokens at T = {self.T}")
+        mgn = e["max_grad_norm"]
+        if mgn is not None and self.clip_state is not None:
+            try:
+                mgn = check_max_grad_norm(mgn)
+            except ValueError as err:
+                raise ValueError(f"training state: engine.{err}") from None
+        sites = None
+        if self.fp8 and self.rank == 0 and e["fp8_seeded"]:
+            sites = e["fp8_sites"]
+            if not self._fp8_seeded:
+                # the histories do not exist before the first execution: run the program once as a fresh engine's warm-up does
+                # (it writes the gradient buffers and the loss: scratch) so that they exist to be written
+                self._fp8_seed_pass()
+            for k, t in self.fp8_sites.items():
+                if k not in sites:
+                    raise ValueError(f"training state: missing key engine.fp8_sites.{k}")
+                if tuple(sites[k].shape) != tuple(t.shape):
+                    raise ValueError(f"training state: engine.fp8_sites.{k} has shape {tuple(sites[k].shape)}, this engine's is {tuple(t.shape)}")
+        # ---- nothing was written up to here (but scratch); from here on nothing fails
+        for k, t in own.items():
+            t.copy_(sd["model"][k])
+        self._write_optimizer_state(m, v, step, hyper)
+        self.seed = int(e["seed"])
+        self.state.copy_(ops.new_rng_state(self._rank_seed(self.seed), self.dev, word))
+        if self.accum > 1:
+            self.opt_state[2:3].copy_(ops.new_rng_state(0, self.dev, step)[2:3])
+            self.acc_ctl.copy_(e["acc_ctl"])
+        self._j = 0
+        if mgn is not None and self.clip_state is not None:
+            self.set_max_grad_norm(mgn)
+        if n > self.off_block.shape[0]:
+            self.off_block = torch.zeros((n, self.B), dtype=torch.int64, device=self.dev)
+            self.offsets = self.off_block[0]
+            self._graphs = None
+        if n:
+            self.off_block[:n].copy_(offs)
+        self.off_ctl.copy_(torch.tensor([word - (1 << 32) if word >= (1 << 31) else word, max(n, 1)], dtype=torch.int32))
+        self._off_rows, self._off_left = (1, None) if left is None else (n if n else rows, n)
+        if self.fp8:
+            if sites is not None:
+                for k, t in self.fp8_sites.items():
+                    t.copy_(sites[k])
+                self._fp8_keep = True
+            elif self._fp8_seeded:
+                # (a rank other than 0, or a file saved before its first step) seed again, as a fresh engine does: the seeding
+                # execution makes new history tensors, so graphs that hold the old ones go
+                self._fp8_seeded, self._fp8_keep = False, False
+                self.fp8_sites.clear()
+                self._graphs = None
+        if self.shadow is not None:      # (the optimizer launch keeps the whole bf16 image current; refresh_shadows() the GEMM weights)
+            ops.cast(self.flat[:self.n_active], torch.bfloat16, out=self.shadow)
+        self.refresh_shadows()
+
+    def _fp8_seed_pass(self) -> None:
+        if self._dp() and self.dp_buckets > 1:
+            for seg in self._prog_segments()[0]:
+                seg()
+        else:
+            self._prog_fwd_bwd()
+        torch.cuda.synchronize(self.dev)
 
     def check_status(self) -> None:
         """raise if a bounded device-side wait of the grouped dW GEMM ever ran out (dg_gemm_tn_grouped: the sticky error word in

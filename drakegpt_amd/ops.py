@@ -916,6 +916,27 @@ def grad_norm(gs, grad_scale: float, max_norm: Tensor, out: Tensor, work: Option
     return out
 
 
+def all_finite(ts, work: Optional[Tensor] = None) -> bool:
+    """True when every element of the fp32 device tensors ts is finite: the fp64 partial sums of squares dg_sumsq_partials
+    leaves (grad_norm's first pass) are finite when every fp32 element under them is.  (The kernel squares in fp32, so a finite
+    element beyond 1.8e19 in magnitude also reads as not finite: as a weight or an Adam moment that is a diverged run too.)
+    One launch per tensor (16-byte aligned, as every flat buffer is), one device round trip; not for the hot path."""
+    ts = [ts] if isinstance(ts, Tensor) else list(ts)
+    for i, t in enumerate(ts):
+        _chk(t, f"ts[{i}]", torch.float32)
+    ts = [t for t in ts if t.numel()]
+    if not ts:
+        return True
+    need = sum(int(lib.dg_sumsq_parts(t.numel())) for t in ts)
+    if work is None or work.dtype != torch.float64 or work.numel() < need:
+        work = torch.empty(need, dtype=torch.float64, device=ts[0].device)
+    base = 0
+    for t in ts:
+        check(lib.dg_sumsq_partials(_p(t), t.numel(), work.data_ptr() + 8 * base, _stream()), "dg_sumsq_partials")
+        base += int(lib.dg_sumsq_parts(t.numel()))
+    return bool(torch.isfinite(work[:base]).all().item())
+
+
 def new_accum_ctl(k: int, device) -> Tensor:
     """device uint32[4] = {j = 0, k, arrival counter = 0, 0} for grad_accumulate (stored as int32); k = accum_steps is validated here,
     on the host: the launch itself never looks at it again"""

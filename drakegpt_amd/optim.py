@@ -154,6 +154,21 @@ class AdamW(torch.optim.Optimizer):
             dist.all_reduce(fl.g, op=dist.ReduceOp.SUM, group=self.process_group)
         return fl
 
+    def is_finite(self) -> bool:
+        """are the parameters and Adam's moments all finite?  (TrainEngine.is_finite for the autograd path: the sum-of-squares
+        launch of the gradient norm over every group's flat buffers -- before a group's first step, over its parameters -- and
+        one device round trip.)  Ask before a good checkpoint is replaced by a diverged run's."""
+        ts = []
+        for gi, group in enumerate(self.param_groups):
+            fl = self._flat.get(gi)
+            held = set(fl.key) if fl is not None else ()
+            if fl is not None:
+                ts += [fl.flat, fl.m, fl.v]
+            ts += [p.detach().float().contiguous().clone() for p in group["params"] if id(p) not in held and p.numel()]
+        if any(not t.is_cuda for t in ts):
+            raise RuntimeError("drakegpt_amd.optim.AdamW updates GPU parameters only (no CPU path)")
+        return ops.all_finite(ts)
+
     # ---- checkpointing: the moments and the step count live in the flat buffers, not in torch's per-parameter `state`; export /
     # import them in torch.optim.AdamW's own format (state[i] = {"step", "exp_avg", "exp_avg_sq"}) so that a resumed run keeps
     # its bias correction and moments, and a state_dict written by torch.optim.AdamW loads here (ref: src/train.py:121)

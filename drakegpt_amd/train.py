@@ -29,6 +29,7 @@ from typing import Optional
 
 import torch
 
+from . import checkpoint as CK
 from . import dist as ddist
 from .config import DRAKE_VOCAB_SIZE, PARAMS, PRESETS, SCALE_PARAMS, TRAIN
 from .model import MODEL_CLASSES, model_params
@@ -96,7 +97,7 @@ def evaluate_loss(train_data, val_data, model, eval_iters, context_length, batch
 
 
 def engine_loop(engine, n_train: int, T: int, B: int, rank: int, world: int, iters: int, eval_interval: int, on_eval, device,
-                generator: Optional[torch.Generator] = None, accum_steps: int = 1) -> None:
+                generator: Optional[torch.Generator] = None, accum_steps: int = 1, start: int = 0) -> None:
     """The training iterations of ref: src/train.py:141-172 on the engine path.  The reference draws one randint(len(data) - T,
     (B,)) per step from the global CPU generator and, every eval_interval steps, 2 * eval_iters more inside evaluate_loss --
     the SAME generator.  Here the offsets of all steps up to the next evaluation are drawn in one go (same draws, same order:
@@ -105,10 +106,12 @@ def engine_loop(engine, n_train: int, T: int, B: int, rank: int, world: int, ite
     `on_eval(it)` runs after step `it` when (it + 1) % eval_interval == 0.
     accum_steps = K > 1 (an engine built with the same accum_steps): an iteration is one optimizer step on K micro-batches; it
     draws K blocks of B * world offsets, in the order a loop of K get_batch calls would, so a stage holds K * n rows and
-    `iters` / `eval_interval` count optimizer steps."""
-    for it in range(iters):
-        if it % eval_interval == 0:
-            n = min(eval_interval, iters - it)
+    `iters` / `eval_interval` count optimizer steps.
+    start > 0: a resumed run -- iterations start .. iters - 1.  Its first stage runs to the next evaluation boundary, which are
+    the rows (and draws) an uninterrupted run would still have had staged there."""
+    for it in range(start, iters):
+        if it % eval_interval == 0 or it == start:
+            n = min(eval_interval - it % eval_interval, iters - it)
             engine.stage_offsets(torch.stack([ddist.shard_rows(draw_offsets(n_train, T, B * world, generator), rank, world)
                                               for _ in range(n * accum_steps)]))
         engine.step()
@@ -150,11 +153,83 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--accum-steps", type=int, default=1, metavar="K",
                     help="gradient accumulation: K micro-batches of batch_size rows per AdamW step (the effective batch is K * "
                     "batch_size * world_size; --iters and --eval-interval count optimizer steps; default 1)")
+    ap.add_argument("--save-every", type=int, default=None, metavar="N",
+                    help="write the full training state (weights, optimizer, counters, generator: everything --resume needs) after "
+                    "the evaluation of every N-th iteration and after the last one; N must be a multiple of --eval-interval "
+                    "(default: off)")
+    ap.add_argument("--state-path", default=None, help="where --save-every writes (default: <model-dir>/<model>[_scaled].state.pt)")
+    ap.add_argument("--resume", default=None, metavar="PATH", help="continue the run whose training state is in PATH; --iters stays "
+                    "the total number of iterations")
     return ap
 
 
+def parse_args(argv=None):
+    """build_parser().parse_args plus the checks that span several flags"""
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.save_every is not None and (args.save_every < 1 or args.save_every % args.eval_interval):
+        ap.error(f"--save-every {args.save_every} must be a positive multiple of --eval-interval {args.eval_interval} (offsets are "
+                 "staged per evaluation interval: the state is written between two stages)")
+    if args.resume is not None and not os.path.isfile(args.resume):
+        ap.error(f"--resume: no training state at {args.resume}")
+    if args.state_path is None:
+        args.state_path = get_model_path(args.model_dir, args.model, args.scale)[:-len(".pt")] + ".state.pt"
+    return args
+
+
+def _to_cpu(obj):
+    if isinstance(obj, torch.Tensor):
+        return obj.detach().cpu()
+    if isinstance(obj, dict):
+        return {k: _to_cpu(v) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return type(obj)(_to_cpu(v) for v in obj)
+    return obj
+
+
+def run_args(args, K: int, world: int) -> dict:
+    """the arguments a resumed run must repeat"""
+    return {"model": args.model, "preset": args.preset, "scale": bool(args.scale), "precision": args.precision, "accum_steps": K,
+            "world_size": world}
+
+
+def save_run_state(path: str, *, next_iteration: int, sched_steps: int, must_match: dict, model, engine=None, optimizer=None,
+                   rank: int = 0, world: int = 1) -> None:
+    """the harness's training state: the engine's state_dict() (autograd path: the model's and optim.AdamW's) and, beside it, the
+    next iteration, the scheduler's count, the global CPU generator and the must-match arguments.  Refuses a diverged run
+    (RuntimeError; the file already there stays as it is).  Rank 0 writes; every rank waits for it."""
+    if not (engine if engine is not None else optimizer).is_finite():
+        raise RuntimeError(f"refusing to save a diverged run: weights or Adam moments are not finite after iteration {next_iteration}; "
+                           f"{path} is left as it was")
+    if rank == 0:
+        obj = {"format": CK.FORMAT, "version": CK.VERSION, "iteration": int(next_iteration), "sched_steps": int(sched_steps),
+               "rng_state": torch.get_rng_state(), "args": dict(must_match),
+               "engine": engine.state_dict() if engine is not None else None,
+               "model": None if engine is not None else {k: v.detach().cpu().clone() for k, v in model.state_dict().items()},
+               "optimizer": None if engine is not None else _to_cpu(optimizer.state_dict())}
+        CK.save_train_state(path, obj)
+    if world > 1:
+        torch.distributed.barrier()
+
+
+def load_run_state(path: str, must_match: dict) -> dict:
+    """read and check a file written by save_run_state; SystemExit names the first argument that differs"""
+    try:
+        st = CK.load_train_state(path)
+        for k in ("iteration", "sched_steps", "rng_state", "args", "engine", "model", "optimizer"):
+            if k not in st:
+                raise ValueError(f"training state {path}: missing key {k!r}")
+    except ValueError as e:
+        raise SystemExit(f"--resume: {e}") from None
+    for field, own in must_match.items():
+        saved = st["args"].get(field, "<absent>")
+        if saved != own:
+            raise SystemExit(f"--resume: {field} differs: {path} was written with {saved!r}, this run has {own!r}")
+    return st
+
+
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     K = check_accum_steps(args.accum_steps)
 
     torch.manual_seed(42)
@@ -208,8 +283,33 @@ def main(argv=None):
         optimizer = AdamW(model.parameters(), lr=base_lr, betas=params["betas"], process_group=pg, world_size=world,
                           max_grad_norm=args.grad_clip)
 
-    model.train()
+    must_match = run_args(args, K, world)
+    start = 0
     sched = {"steps": 0}
+    if args.resume:
+        st = load_run_state(args.resume, must_match)
+        if (st["engine"] is None) != (engine is None):
+            raise SystemExit(f"--resume: {args.resume} does not hold the state of a {args.model} run")
+        try:
+            if engine is not None:
+                engine.load_state_dict(st["engine"])
+            else:
+                model.load_state_dict(st["model"])
+                optimizer.load_state_dict(st["optimizer"])
+        except ValueError as e:
+            raise SystemExit(f"--resume: {e}") from None
+        start, sched["steps"] = int(st["iteration"]), int(st["sched_steps"])
+        if start > args.iters:
+            raise SystemExit(f"--resume: {args.resume} is at iteration {start}, past --iters {args.iters}")
+        torch.set_rng_state(st["rng_state"])          # the generator that draws offsets, evaluation batches and the sample
+        if rank == 0:
+            print(f"resumed {args.resume} at iteration {start}")
+
+    def save_state(next_it):
+        save_run_state(args.state_path, next_iteration=next_it, sched_steps=sched["steps"], must_match=must_match, model=model,
+                       engine=engine, optimizer=None if engine is not None else optimizer, rank=rank, world=world)
+
+    model.train()
     t0 = time.perf_counter()
 
     def on_eval(it):
@@ -230,18 +330,21 @@ def main(argv=None):
         if rank == 0:
             el = time.perf_counter() - t0
             line = {"step": it + 1, "train_loss": float(losses["train"]), "val_loss": float(losses["val"]), "lr": lr,
-                    "tokens_per_s": (it + 1) * K * B * T * world / el}
+                    "tokens_per_s": (it + 1 - start) * K * B * T * world / el}
             if args.grad_clip is not None:
                 # the last step's pre-clip norm: the evaluation has synchronised the stream already
                 line["grad_norm"] = float((engine if engine is not None else optimizer).last_grad_norm)
             print(json.dumps(line), flush=True)
         model.train()
+        if args.save_every and (it + 1) % args.save_every == 0:
+            save_state(it + 1)
 
     if engine is not None:
-        engine_loop(engine, len(train_data), T, B, rank, world, args.iters, args.eval_interval, on_eval, device, accum_steps=K)
+        engine_loop(engine, len(train_data), T, B, rank, world, args.iters, args.eval_interval, on_eval, device, accum_steps=K,
+                    start=start)
     else:
         from . import ops
-        for it in range(args.iters):
+        for it in range(start, args.iters):
             if K == 1:
                 ix = ddist.shard_rows(draw_offsets(len(train_data), T, B * world, None), rank, world).to(device, non_blocking=True)
                 x, y = ops.batch_gather(train_dev, ix, T)
@@ -260,6 +363,8 @@ def main(argv=None):
             if (it + 1) % args.eval_interval == 0:
                 on_eval(it)
 
+    if args.save_every and args.iters % args.save_every:
+        save_state(args.iters)      # before the sample is drawn: a longer run continued from here sees the uninterrupted run's generator
     model.eval()
     if rank == 0:
         idx = torch.zeros((1, 1), dtype=torch.long, device=device)
