@@ -34,6 +34,9 @@ _HEAD = re.compile(r"^blocks\.(\d+)\.sa_head\.heads\.(\d+)\.(query|key|value)\.w
 _BLOCK = re.compile(r"^blocks\.(\d+)\.(.+)$")
 _QKV = {"query": 0, "key": 1, "value": 2}          # order of the three groups of NH heads inside a layer's packed [3 NH H, C] operand
 UNTRAINED = ("lnf.w", "lnf.b")                     # regions the optimizer never touches (ln_f: no gradient)
+# weight-decay groups: the kinds of parameter TrainEngine(no_decay=...) / train --no-decay keep out of weight decay, by region key
+NO_DECAY_KINDS = {"bias": ("bproj", "b1", "b2", "lm.b"), "layernorm": ("ln1w", "ln1b", "ln2w", "ln2b", "lnf.w", "lnf.b"),
+                  "embedding": ("tok", "pos")}
 
 
 # ------------------------------------------------------------------------------------------ names <-> regions
@@ -80,17 +83,51 @@ def region_params(key: str, num_heads: int, head_size: int) -> List[Tuple[str, O
     raise KeyError(key)
 
 
+def check_no_decay(kinds) -> Tuple[str, ...]:
+    """the sorted, de-duplicated kinds of a no_decay collection; ValueError for anything outside NO_DECAY_KINDS"""
+    if isinstance(kinds, str):
+        raise ValueError(f"no_decay must be a collection out of {sorted(NO_DECAY_KINDS)}, got the string {kinds!r}")
+    try:
+        kinds = list(kinds)
+    except TypeError:
+        raise ValueError(f"no_decay must be a collection out of {sorted(NO_DECAY_KINDS)}, got {kinds!r}") from None
+    for k in kinds:
+        if not isinstance(k, str) or k not in NO_DECAY_KINDS:
+            raise ValueError(f"no_decay: {k!r} is not one of {sorted(NO_DECAY_KINDS)}")
+    return tuple(sorted(set(kinds)))
+
+
+def region_no_decay(key: str, kinds) -> bool:
+    """is the region kept out of weight decay under these kinds?  ("3.b1" and "lm.b" are biases, "3.ln1w" a LayerNorm parameter)"""
+    tail = key if key in ("lm.b", "lm.w", "lnf.w", "lnf.b") else key.rpartition(".")[2]
+    return any(tail in NO_DECAY_KINDS[k] for k in kinds)
+
+
+def split_param_names(names: Sequence[str], num_heads: int, head_size: int, kinds) -> Tuple[List[str], List[str]]:
+    """(decayed, not decayed) parameter names, each in model order: the two parameter groups of a torch.optim.AdamW that does
+    what TrainEngine(no_decay=kinds) does"""
+    kinds = check_no_decay(kinds)
+    groups: Tuple[List[str], List[str]] = ([], [])
+    for name in names:
+        groups[region_no_decay(param_region(name, num_heads, head_size)[0], kinds)].append(name)
+    return groups
+
+
 def _rows(t: Tensor, rows) -> Tensor:
     return t if rows is None else t[rows[0]:rows[1]]
 
 
 def optimizer_state_from_regions(names: Sequence[str], regions: Dict[str, Tuple[Tensor, Tensor]], num_heads: int, head_size: int,
-                                 step: int, lr: float, betas, eps: float, weight_decay: float) -> dict:
+                                 step: int, lr: float, betas, eps: float, weight_decay: float, no_decay=()) -> dict:
     """what torch.optim.AdamW(model.parameters(), ...) would save: `names` are model.named_parameters()'s names in order,
     `regions` maps a region key to its (exp_avg, exp_avg_sq) tensors in the region's own shape.  A parameter whose region is
-    absent from `regions` (ln_f) gets no state entry, as in torch."""
+    absent from `regions` (ln_f) gets no state entry, as in torch.
+    no_decay (kinds, see check_no_decay) not empty: what AdamW([{"params": decayed}, {"params": others, "weight_decay": 0.0}], ...)
+    over split_param_names' two lists would save -- torch numbers the parameters group by group."""
+    no_decay = check_no_decay(no_decay)
+    split = split_param_names(names, num_heads, head_size, no_decay) if no_decay else (list(names), [])
     state = {}
-    for i, name in enumerate(names):
+    for i, name in enumerate(split[0] + split[1]):
         key, rows = param_region(name, num_heads, head_size)
         if key not in regions:
             continue
@@ -98,22 +135,38 @@ def optimizer_state_from_regions(names: Sequence[str], regions: Dict[str, Tuple[
         state[i] = {"step": torch.tensor(float(step)), "exp_avg": _rows(m, rows).detach().cpu().clone(),
                     "exp_avg_sq": _rows(v, rows).detach().cpu().clone()}
     # the group as the installed torch writes it (its set of option keys changes between releases): ask torch itself
-    dummy = [torch.nn.Parameter(torch.zeros(1)) for _ in names]
+    dummy = [{"params": [torch.nn.Parameter(torch.zeros(1)) for _ in split[0]]}]
+    if no_decay:
+        dummy.append({"params": [torch.nn.Parameter(torch.zeros(1)) for _ in split[1]], "weight_decay": 0.0})
     groups = torch.optim.AdamW(dummy, lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps),
                                weight_decay=float(weight_decay)).state_dict()["param_groups"]
     return {"state": state, "param_groups": groups}
 
 
-def regions_from_optimizer_state(sd: dict, names: Sequence[str], num_heads: int, head_size: int):
+def regions_from_optimizer_state(sd: dict, names: Sequence[str], num_heads: int, head_size: int, no_decay=()):
     """inverse of optimizer_state_from_regions, for a dict written by it, by torch.optim.AdamW or by drakegpt_amd.optim.AdamW
     over the same model: ({region key: (exp_avg, exp_avg_sq)}, step, {"lr", "betas", "eps", "weight_decay"}).  Raises ValueError
     if the parameters disagree about the step count, if the state does not fit `names`, or if a packed QKV region is only partly
-    present."""
+    present.  no_decay not empty: the dict must hold the two groups of split_param_names (the second with weight_decay 0 and
+    otherwise the first one's options); "weight_decay" is then the first group's."""
+    no_decay = check_no_decay(no_decay)
     groups = sd["param_groups"]
-    if len(groups) != 1:
-        raise ValueError(f"optimizer state: expected one parameter group, found {len(groups)}")
+    if len(groups) != (2 if no_decay else 1):
+        raise ValueError(f"optimizer state: expected {'two parameter groups' if no_decay else 'one parameter group'}, found {len(groups)}")
     g = groups[0]
-    if list(g["params"]) != list(range(len(names))):
+    if no_decay:
+        split = split_param_names(names, num_heads, head_size, no_decay)
+        g1 = groups[1]
+        if list(g["params"]) != list(range(len(split[0]))) or list(g1["params"]) != list(range(len(split[0]), len(names))):
+            raise ValueError(f"optimizer state: the groups list {len(g['params'])} + {len(g1['params'])} parameters, no_decay = "
+                             f"{list(no_decay)} splits the model's {len(names)} into {len(split[0])} + {len(split[1])}")
+        if float(g1["weight_decay"]) != 0.0:
+            raise ValueError(f"optimizer state: the second group has weight_decay {g1['weight_decay']!r}, expected 0")
+        for opt in ("lr", "betas", "eps"):
+            if (tuple(g[opt]) if opt == "betas" else g[opt]) != (tuple(g1[opt]) if opt == "betas" else g1[opt]):
+                raise ValueError(f"optimizer state: the two groups differ in {opt}: {g[opt]!r} and {g1[opt]!r}")
+        names = split[0] + split[1]
+    elif list(g["params"]) != list(range(len(names))):
         raise ValueError(f"optimizer state: the group lists {len(g['params'])} parameters, the model has {len(names)}")
     state = sd["state"]
     steps = sorted({int(float(st["step"])) for st in state.values()})

@@ -889,14 +889,32 @@ extern "C" int dg_softmax_rows(const float* logits, int64_t ldl, float* probs, i
 // one-thread launch for that cost 4 us of the step.)
 // CLIP: the gradient clipping coefficient (dg_grad_norm_finalize) is read from device memory and multiplied into grad_scale once per
 // workgroup; CLIP = false is the unclipped kernel unchanged, and a coefficient of exactly 1 gives the same bits (grad_scale * 1.0f).
-template <bool CLIP>
+// TABLE: lr comes from lr_table[min(step word, lr_table_len - 1)] (a schedule staged in HBM once) instead of hyper[0]; the word is
+// read once per workgroup, where the step word is read.  MASK: no_decay_bits holds one bit per 64-float granule (bit G & 31 of word
+// G >> 5 covers elements [64 G, 64 G + 64)); a set bit makes decay 1.0f for that granule, and p * 1.0f is exact, so those elements
+// get the bits of weight_decay = 0.  A lane's four floats never cross a granule and a wave's 256 floats lie in one bitmap word, so
+// the vector body reads one cached word per wave iteration.  With both false this is the kernel as it was.
+// The existing entries instantiate <CLIP, false, false> with an empty pack: the kernel and its kernel arguments as they were.
+struct AdamwSched { const float* lr_table; int64_t lr_table_len; const uint32_t* no_decay_bits; };
+template <typename... S>
+__device__ __forceinline__ AdamwSched adamw_sched_of(S... s) {
+    if constexpr (sizeof...(S) != 0) return (s, ...);
+    else return AdamwSched{nullptr, 0, nullptr};
+}
+
+template <bool CLIP, bool TABLE, bool MASK, typename... S>   // S: nothing, or one AdamwSched when TABLE or MASK
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                              float* __restrict__ v, int64_t n, const float* __restrict__ hyper,
                              uint32_t* rng_state, float grad_scale,
-                             bf16_t* __restrict__ shadow, int advance, const float* __restrict__ clip_coef) {
+                             bf16_t* __restrict__ shadow, int advance, const float* __restrict__ clip_coef, S... sched) {
+    static_assert(sizeof...(S) == ((TABLE || MASK) ? 1 : 0), "the schedule arguments go with TABLE or MASK");
+    const AdamwSched sc = adamw_sched_of(sched...);
+    const float* __restrict__ lr_table = sc.lr_table;
+    const uint32_t* __restrict__ no_decay_bits = sc.no_decay_bits;
     if (CLIP) grad_scale *= clip_coef[0];
-    const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4];
+    const float lr0 = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4];
     const uint32_t step_now = rng_state[2];
+    const float lr = TABLE ? lr_table[(int64_t)step_now < sc.lr_table_len - 1 ? (int64_t)step_now : sc.lr_table_len - 1] : lr0;
     const float t = (float)(step_now + 1u);
     const float bc1 = 1.f - powf(b1, t);
     const float bc2 = 1.f - powf(b2, t);
@@ -908,10 +926,14 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
     int64_t n4 = n / 4;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gs) {
         f32x4 pp = ((f32x4*)p)[i], gg = ((const f32x4*)g)[i], mm = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
+        float dec = decay;
+        if (MASK) {                                              // granule = i >> 4 (16 lanes of four floats)
+            if ((no_decay_bits[i >> 9] >> ((unsigned)(i >> 4) & 31u)) & 1u) dec = 1.f;
+        }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float gj = gg[j] * grad_scale;
-            float pj = pp[j] * decay;
+            float pj = pp[j] * dec;
             float mj = mm[j] + (gj - mm[j]) * (1.f - b1);          // lerp, as torch does
             float vj = vv[j] * b2 + (1.f - b2) * gj * gj;
             float denom = sqrtf(vj) * inv_sqrt_bc2 + eps;
@@ -931,8 +953,12 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
         }
     }
     for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gs) {
+        float dec = decay;
+        if (MASK) {
+            if ((no_decay_bits[i >> 11] >> ((unsigned)(i >> 6) & 31u)) & 1u) dec = 1.f;
+        }
         float gj = g[i] * grad_scale;
-        float pj = p[i] * decay;
+        float pj = p[i] * dec;
         float mj = m[i] + (gj - m[i]) * (1.f - b1);
         float vj = v[i] * b2 + (1.f - b2) * gj * gj;
         float denom = sqrtf(vj) * inv_sqrt_bc2 + eps;
@@ -952,18 +978,23 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
     }
 }
 
+static unsigned adamw_grid(int64_t n) {
+    unsigned grid = (unsigned)((n / 4 + 255) / 256);
+    if (grid == 0) grid = 1;
+    if (grid > 2048) grid = 2048;
+    return grid;
+}
+
 static int adamw_launch(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, uint32_t* rng_state,
                         float grad_scale, const float* clip_coef, void* shadow_bf16, int advance_step, void* stream) {
     if (!p || !g || !m || !v || !hyper || !rng_state || n <= 0) return DG_ERR_ARG;
     if (!dg_aligned16(p) || !dg_aligned16(g) || !dg_aligned16(m) || !dg_aligned16(v)) return DG_ERR_ALIGN;
-    unsigned grid = (unsigned)((n / 4 + 255) / 256);
-    if (grid == 0) grid = 1;
-    if (grid > 2048) grid = 2048;
+    const unsigned grid = adamw_grid(n);
     if (clip_coef)
-        hipLaunchKernelGGL(adamw_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, hyper, rng_state, grad_scale,
+        hipLaunchKernelGGL((adamw_kernel<true, false, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, hyper, rng_state, grad_scale,
                            (bf16_t*)shadow_bf16, advance_step, clip_coef);
     else
-        hipLaunchKernelGGL(adamw_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, hyper, rng_state, grad_scale,
+        hipLaunchKernelGGL((adamw_kernel<false, false, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, hyper, rng_state, grad_scale,
                            (bf16_t*)shadow_bf16, advance_step, (const float*)nullptr);
     DG_LAUNCH_CHECK();
     return DG_OK;
@@ -978,6 +1009,30 @@ extern "C" int dg_adamw_step_clip(float* p, const float* g, float* m, float* v, 
                                   float grad_scale, const float* clip_coef, void* shadow_bf16, int advance_step, void* stream) {
     if (!clip_coef) return DG_ERR_ARG;
     return adamw_launch(p, g, m, v, n, hyper, rng_state, grad_scale, clip_coef, shadow_bf16, advance_step, stream);
+}
+
+extern "C" int dg_adamw_step_sched(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, uint32_t* rng_state,
+                                   float grad_scale, const float* clip_coef, const float* lr_table, int64_t lr_table_len,
+                                   const uint32_t* no_decay_bits, void* shadow_bf16, int advance_step, void* stream) {
+    if (!p || !g || !m || !v || !hyper || !rng_state || n <= 0) return DG_ERR_ARG;
+    if (lr_table ? lr_table_len < 1 : lr_table_len != 0) return DG_ERR_ARG;
+    if (!dg_aligned16(p) || !dg_aligned16(g) || !dg_aligned16(m) || !dg_aligned16(v)) return DG_ERR_ALIGN;
+    const unsigned grid = adamw_grid(n);
+    const AdamwSched sc{lr_table, lr_table_len, no_decay_bits};
+#define LAUNCH(CLIP, TABLE, MASK) hipLaunchKernelGGL((adamw_kernel<CLIP, TABLE, MASK, AdamwSched>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, hyper, rng_state, grad_scale, (bf16_t*)shadow_bf16, advance_step, clip_coef, sc)
+    switch ((clip_coef ? 4 : 0) | (lr_table ? 2 : 0) | (no_decay_bits ? 1 : 0)) {
+        case 0: return adamw_launch(p, g, m, v, n, hyper, rng_state, grad_scale, nullptr, shadow_bf16, advance_step, stream);
+        case 1: LAUNCH(false, false, true); break;
+        case 2: LAUNCH(false, true, false); break;
+        case 3: LAUNCH(false, true, true); break;
+        case 4: return adamw_launch(p, g, m, v, n, hyper, rng_state, grad_scale, clip_coef, shadow_bf16, advance_step, stream);
+        case 5: LAUNCH(true, false, true); break;
+        case 6: LAUNCH(true, true, false); break;
+        default: LAUNCH(true, true, true); break;
+    }
+#undef LAUNCH
+    DG_LAUNCH_CHECK();
+    return DG_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

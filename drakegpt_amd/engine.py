@@ -30,6 +30,7 @@ import torch
 
 from . import checkpoint as CK
 from . import ops
+from . import schedules as SCH
 from . import sublayers as S
 from .model import TransformerLM
 from .optim import check_accum_steps, check_max_grad_norm
@@ -179,7 +180,8 @@ class TrainEngine:
                  lr: float = 1e-3, betas=(0.9, 0.95), eps: float = 1e-8, weight_decay: float = 1e-2,
                  seed: int = 42, rank: int = 0, world_size: int = 1, process_group=None, use_graph: bool = True,
                  dp_buckets: Optional[int] = None, logits: str = "auto", grad_stream: str = "auto", fp8_dw: Optional[bool] = None,
-                 max_grad_norm: Optional[float] = None, accum_steps: int = 1):
+                 max_grad_norm: Optional[float] = None, accum_steps: int = 1, lr_schedule=None, schedule_steps: Optional[int] = None,
+                 no_decay=()):
         if not isinstance(model, TransformerLM):
             raise TypeError("TrainEngine drives TransformerLM (the other five models train through the autograd path)")
         p0 = next(model.parameters())
@@ -212,6 +214,12 @@ class TrainEngine:
         self._dp_buckets_arg = dp_buckets
         # gradient accumulation: accum_steps micro-batches per AdamW step (1: nothing below exists, the step is what it always was)
         self.accum = check_accum_steps(accum_steps)
+        # (validated before anything is allocated) the learning-rate table of lr_schedule -- a sequence, a 1-D tensor, or a callable
+        # s -> lr with schedule_steps entries -- and the kinds of parameter kept out of weight decay
+        self.lr_table_host = None if lr_schedule is None else SCH.as_table(lr_schedule, schedule_steps)
+        if lr_schedule is None and schedule_steps is not None:
+            raise ValueError("schedule_steps goes with lr_schedule")
+        self.no_decay = CK.check_no_decay(no_decay)
         if self.accum > 1 and dp_buckets is not None and int(dp_buckets) > 1:
             raise ValueError("accum_steps > 1 uses one gradient exchange per optimizer step (it is amortised over the micro-steps "
                              "already): dp_buckets > 1 cannot be combined with it")
@@ -275,6 +283,19 @@ class TrainEngine:
         self._alloc_and_adopt()
         self.hyper = torch.tensor([lr, betas[0], betas[1], eps, weight_decay], dtype=torch.float32, device=self.dev)
         self.hyper_host = [float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay)]      # what state_dict() reports
+        # lr_schedule: AdamW finds its rate in a table staged here once, by its own step word (dg_adamw_step_sched): hyper[0] is
+        # not read then.  The table's address and length are launch arguments of the captured graph: set_lr_schedule() replaces
+        # values, never the tensor.  no_decay: one bit per 64-float granule of flat[0, n_active); a region's alignment gap
+        # belongs to its last granule (the gap holds zeros, decayed or not).
+        self.lr_table = None if self.lr_table_host is None else self.lr_table_host.to(self.dev)
+        self.no_decay_bits = None
+        if self.no_decay:
+            self.no_decay_bits = ops.new_no_decay_bits(self._no_decay_ranges(), self.n_active, self.dev)
+        # what _prog_update / _prog_update_accum add to their ops.adamw_step call: nothing for an engine with neither, whose call is
+        # the one it always was, argument for argument
+        self._sched_kw = {}
+        if self.lr_table is not None or self.no_decay_bits is not None:
+            self._sched_kw = {"lr_table": self.lr_table, "no_decay_bits": self.no_decay_bits}
         # global-norm gradient clipping (ref: clip_grad_norm_(model.parameters(), max_norm) before optimizer.step()): the norm of
         # the mean gradient over ranks, gflat[0, n_active) * 1 / world, is computed inside the step and its coefficient applied
         # inside the AdamW launch; gflat / named_grads() keep the unclipped gradient.  clip_state = {total_norm, coef, max_norm, 0}
@@ -386,6 +407,18 @@ class TrainEngine:
             plan.append((list(range(hi_layer - 1, lo_layer - 1, -1)), ranges))
             hi_layer = lo_layer
         return plan
+
+    def _no_decay_ranges(self):
+        """[lo, hi) element ranges of flat[0, n_active) that self.no_decay keeps out of weight decay: whole granules"""
+        out = []
+        for k in self._trained_keys():
+            if CK.region_no_decay(k, self.no_decay):
+                off, shape = self._region(k)
+                n = 1
+                for d in shape:
+                    n *= d
+                out.append((off, min(_round(off + n), self.n_active)))
+        return out
 
     def _region(self, key: str):
         for lay, base in ((self.layA, self.offA), (self.layB, self.offB), (self.layE, self.offE), (self.layZ, self.offZ)):
@@ -887,25 +920,25 @@ class TrainEngine:
         scale = 1.0 / (self.accum * self.world)
         if self.clip_state is None:
             ops.adamw_step(self.flat, self.gacc, self.m_, self.v_, self.hyper, self.opt_state, scale,
-                           shadow_bf16=self.shadow, n=self.n_active, advance=True)
+                           shadow_bf16=self.shadow, n=self.n_active, advance=True, **self._sched_kw)
         else:
             ops.grad_norm(self.gacc, scale, self.clip_state[2:3], self.clip_state, self.norm_work)
             ops.adamw_step(self.flat, self.gacc, self.m_, self.v_, self.hyper, self.opt_state, scale,
-                           shadow_bf16=self.shadow, n=self.n_active, advance=True, clip=self.clip_state[1:2])
+                           shadow_bf16=self.shadow, n=self.n_active, advance=True, clip=self.clip_state[1:2], **self._sched_kw)
         self._refresh_transposes()
 
     def _prog_update(self):
         # (the step word moves on inside the AdamW launch: nothing after it reads the word)
         if self.clip_state is None:
             ops.adamw_step(self.flat, self.gflat, self.m_, self.v_, self.hyper, self.state, 1.0 / self.world,
-                           shadow_bf16=self.shadow, n=self.n_active, advance=True)
+                           shadow_bf16=self.shadow, n=self.n_active, advance=True, **self._sched_kw)
         else:
             # the gradient is final here on every path (the data-parallel optimizer graph runs after the exchange): norm of the mean
             # over ranks, then AdamW on g * coef.  The alignment gaps of gflat are zero (no producer writes them), so the norm
             # over the whole active range is the norm over the parameters.
             ops.grad_norm(self.gflat, 1.0 / self.world, self.clip_state[2:3], self.clip_state, self.norm_work)
             ops.adamw_step(self.flat, self.gflat, self.m_, self.v_, self.hyper, self.state, 1.0 / self.world,
-                           shadow_bf16=self.shadow, n=self.n_active, advance=True, clip=self.clip_state[1:2])
+                           shadow_bf16=self.shadow, n=self.n_active, advance=True, clip=self.clip_state[1:2], **self._sched_kw)
         self._refresh_transposes()
 
     def _dp(self) -> bool:
@@ -1009,8 +1042,30 @@ class TrainEngine:
         self._graphs = None
 
     def set_lr(self, lr: float):
+        if self.lr_table is not None:
+            raise RuntimeError("set_lr: this engine follows a learning-rate schedule (TrainEngine(..., lr_schedule=...)); "
+                               "set_lr_schedule() replaces its values")
         self.hyper_host[0] = float(lr)
         self.hyper[0:1].fill_(float(lr))
+
+    def set_lr_schedule(self, values, schedule_steps: Optional[int] = None):
+        """new values for the staged table, from the next step on (a device copy: captured graphs stay valid).  The table's
+        length is fixed at construction: ValueError for another one, RuntimeError on an engine built without a schedule."""
+        if self.lr_table is None:
+            raise RuntimeError("set_lr_schedule: this engine was built without a schedule (TrainEngine(..., lr_schedule=...))")
+        table = SCH.as_table(values, schedule_steps)
+        if table.numel() != self.lr_table.numel():
+            raise ValueError(f"set_lr_schedule: the new schedule has {table.numel()} entries, this engine's table has "
+                             f"{self.lr_table.numel()} (the length is fixed at construction)")
+        self.lr_table_host = table
+        self.lr_table.copy_(table)
+
+    def current_lr(self) -> float:
+        """the rate the next optimizer step uses: table[min(step_count(), len - 1)], or the constant rate without a schedule.
+        Synchronises on an engine with a schedule."""
+        if self.lr_table_host is None:
+            return self.hyper_host[0]
+        return float(self.lr_table_host[min(self.step_count(), self.lr_table_host.numel() - 1)])
 
     def set_max_grad_norm(self, max_norm: float):
         """a new clipping threshold for the following steps (a device write: captured graphs stay valid)"""
@@ -1263,12 +1318,14 @@ class TrainEngine:
             m, v = self.m_.cpu(), self.v_.cpu()
             regions = {k: (self.grad_view(k, m), self.grad_view(k, v)) for k in self._trained_keys()}
         h = self.hyper_host
-        return CK.optimizer_state_from_regions(self._param_names(), regions, self.NH, self.H, step, h[0], (h[1], h[2]), h[3], h[4])
+        lr = h[0] if self.lr_table_host is None else float(self.lr_table_host[min(step, self.lr_table_host.numel() - 1)])
+        return CK.optimizer_state_from_regions(self._param_names(), regions, self.NH, self.H, step, lr, (h[1], h[2]), h[3], h[4],
+                                               no_decay=self.no_decay)
 
     def _parse_optimizer_state(self, sd: dict):
         """validate an optimizer state_dict against this engine; returns (m, v as CPU images of the flat buffers, step, hyper)"""
         try:
-            regions, step, hyper = CK.regions_from_optimizer_state(sd, self._param_names(), self.NH, self.H)
+            regions, step, hyper = CK.regions_from_optimizer_state(sd, self._param_names(), self.NH, self.H, no_decay=self.no_decay)
         except KeyError as e:
             raise ValueError(f"optimizer state: missing key {e}") from None
         keys = self._trained_keys()
@@ -1320,7 +1377,8 @@ class TrainEngine:
                "max_grad_norm": self.max_grad_norm,
                "offsets": self.off_block[used:self._off_rows].cpu(), "offsets_rows": self._off_rows, "offsets_left": self._off_left,
                "fp8_seeded": bool(self._fp8_seeded),
-               "fp8_sites": {k: v.cpu() for k, v in self.fp8_sites.items()} if self.fp8 else {}}
+               "fp8_sites": {k: v.cpu() for k, v in self.fp8_sites.items()} if self.fp8 else {},
+               "lr_table": None if self.lr_table_host is None else self.lr_table_host.clone(), "no_decay": list(self.no_decay)}
         return {"format": CK.FORMAT, "version": CK.VERSION,
                 "model": {k: v.detach().cpu().clone() for k, v in self.model.state_dict().items()},
                 "optimizer": self.optimizer_state_dict(), "engine": eng, "meta": self._meta()}
@@ -1354,6 +1412,22 @@ class TrainEngine:
         for k in sd["model"]:
             if k not in own:
                 raise ValueError(f"training state: model.{k} is not a tensor of this model")
+        # (a file written before schedules and decay groups existed has neither key: no schedule, no groups)
+        table, groups = e.get("lr_table"), e.get("no_decay") or []
+        own_len = None if self.lr_table_host is None else self.lr_table_host.numel()
+        if table is not None and (not isinstance(table, Tensor) or table.dim() != 1 or table.dtype != torch.float32):
+            raise ValueError("training state: engine.lr_table is not a 1-D float32 tensor")
+        saved_len = None if table is None else table.numel()
+        if saved_len != own_len:
+            raise ValueError(f"training state: engine.lr_table differs: saved {saved_len!r} entries, this engine's schedule has "
+                             f"{own_len!r} (None: no schedule)")
+        if table is not None:
+            try:
+                table = SCH.as_table(table)
+            except ValueError as err:
+                raise ValueError(f"training state: engine.lr_table: {err}") from None
+        if sorted(groups) != list(self.no_decay):
+            raise ValueError(f"training state: engine.no_decay differs: saved {sorted(groups)!r}, this engine has {list(self.no_decay)!r}")
         m, v, step, hyper = self._parse_optimizer_state(sd["optimizer"])
         word = int(e["step_word"])
         opt_step = word if self.accum == 1 else e["opt_step"]
@@ -1396,6 +1470,9 @@ class TrainEngine:
         for k, t in own.items():
             t.copy_(sd["model"][k])
         self._write_optimizer_state(m, v, step, hyper)
+        if table is not None:
+            self.lr_table_host = table
+            self.lr_table.copy_(table)
         self.seed = int(e["seed"])
         self.state.copy_(ops.new_rng_state(self._rank_seed(self.seed), self.dev, word))
         if self.accum > 1:

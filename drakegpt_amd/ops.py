@@ -870,13 +870,33 @@ def attn_decode_append(row: Tensor, cache: Tensor, state: Tensor, NH: int, H: in
 
 def adamw_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, hyper: Tensor, rng_state: Tensor, grad_scale: float = 1.0,
                shadow_bf16: Optional[Tensor] = None, n: Optional[int] = None, advance: bool = False, *,
-               clip: Optional[Tensor] = None) -> None:
+               clip: Optional[Tensor] = None, lr_table: Optional[Tensor] = None, no_decay_bits: Optional[Tensor] = None) -> None:
     """advance: the launch also moves the step word of rng_state on (what state_advance does, without its launch).
     clip: a device fp32 scalar, the clipping coefficient written by grad_norm (out[1:2]); the step then applies g * grad_scale * coef
-    (dg_adamw_step_clip) and g itself stays unclipped.  None: dg_adamw_step, unchanged."""
+    (dg_adamw_step_clip) and g itself stays unclipped.  None: dg_adamw_step, unchanged.
+    lr_table: a device fp32 vector; the update uses lr_table[min(step word, len - 1)] instead of hyper[0].
+    no_decay_bits: the bitmap of new_no_decay_bits(ranges, n, device); elements of a set granule see weight_decay = 0.
+    Either of the two takes the launch to dg_adamw_step_sched; with both None the calls are the ones above, unchanged."""
     for t, nm in ((p, "p"), (g, "g"), (m, "m"), (v, "v"), (hyper, "hyper")):
         _chk(t, nm, torch.float32)
     n = p.numel() if n is None else n
+    if lr_table is not None or no_decay_bits is not None:
+        if n < 1 or any(n > t.numel() for t in (p, g, m, v)):
+            raise ValueError(f"adamw_step: n = {n} does not fit p, g, m, v")
+        if lr_table is not None:
+            _chk(lr_table, "lr_table", torch.float32)
+            if lr_table.dim() != 1 or lr_table.numel() < 1:
+                raise ValueError("adamw_step: lr_table must be a 1-D tensor with at least one entry")
+        if no_decay_bits is not None:
+            _chk(no_decay_bits, "no_decay_bits", torch.int32)
+            if no_decay_bits.numel() < no_decay_words(n):
+                raise ValueError(f"adamw_step: no_decay_bits needs {no_decay_words(n)} words for n = {n}, got {no_decay_bits.numel()}")
+        if clip is not None:
+            _chk(clip, "clip", torch.float32)
+        check(lib.dg_adamw_step_sched(_p(p), _p(g), _p(m), _p(v), n, _p(hyper), _p(rng_state), float(grad_scale), _p(clip), _p(lr_table),
+                                      0 if lr_table is None else lr_table.numel(), _p(no_decay_bits), _p(shadow_bf16), int(advance),
+                                      _stream()), "dg_adamw_step_sched")
+        return
     if clip is None:
         check(lib.dg_adamw_step(_p(p), _p(g), _p(m), _p(v), n, _p(hyper), _p(rng_state), float(grad_scale), _p(shadow_bf16), int(advance),
                                 _stream()), "dg_adamw_step")
@@ -884,6 +904,33 @@ def adamw_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, hyper: Tensor, rng_st
     _chk(clip, "clip", torch.float32)
     check(lib.dg_adamw_step_clip(_p(p), _p(g), _p(m), _p(v), n, _p(hyper), _p(rng_state), float(grad_scale), _p(clip), _p(shadow_bf16),
                                  int(advance), _stream()), "dg_adamw_step_clip")
+
+
+NO_DECAY_GRANULE = 64   # floats per bit of the no-decay bitmap: ALIGN of engine.py and _ALIGN of optim.py
+
+
+def no_decay_words(n: int) -> int:
+    """uint32 words of the no-decay bitmap over n floats: ceil(ceil(n / 64) / 32)"""
+    return ((n + NO_DECAY_GRANULE - 1) // NO_DECAY_GRANULE + 31) // 32
+
+
+def new_no_decay_bits(ranges, n: int, device) -> Tensor:
+    """the bitmap dg_adamw_step_sched reads (uint32 words stored as int32 bit patterns): bit (G & 31) of word (G >> 5) is set
+    when the granule of elements [64 G, 64 G + 64) lies in one of the [lo, hi) element ranges.  A range has to start on a granule
+    and end on one or at n: half a granule cannot be kept out of weight decay."""
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"new_no_decay_bits: n must be an integer >= 1, got {n!r}")
+    words = [0] * no_decay_words(n)
+    for lo, hi in ranges:
+        lo, hi = int(lo), int(hi)
+        if not 0 <= lo <= hi <= n:
+            raise ValueError(f"new_no_decay_bits: range [{lo}, {hi}) does not lie in [0, {n})")
+        if lo % NO_DECAY_GRANULE or (hi % NO_DECAY_GRANULE and hi != n):
+            raise ValueError(f"new_no_decay_bits: range [{lo}, {hi}) must start on a multiple of {NO_DECAY_GRANULE} and end on one or at n = {n}")
+        for G in range(lo // NO_DECAY_GRANULE, (hi + NO_DECAY_GRANULE - 1) // NO_DECAY_GRANULE):
+            words[G >> 5] |= 1 << (G & 31)
+    words = [w - (1 << 32) if w >= (1 << 31) else w for w in words]
+    return torch.tensor(words, dtype=torch.int32, device=device)
 
 
 def grad_norm_workspace(gs, device) -> Tensor:

@@ -17,6 +17,11 @@ state_dict checkpoint (:181-183).  Differences, on purpose:
 is used everywhere (batch shape and learning rates too), flags are real booleans, wandb is replaced
 by JSON lines on stdout, and without --data a synthetic uniform char corpus stands in for the
 Kaggle download.
+
+Added beside the reference's loop, all off by default: --grad-clip, --accum-steps, --save-every / --resume, and --lr-schedule /
+--warmup-steps / --min-lr / --no-decay: a rate per optimizer step over --iters steps (looked up on the GPU from a table on the
+engine path, set as group["lr"] on the autograd path) and parameters kept out of weight decay.  The default `reference`
+schedule is the CyclicLR stepped at evaluations described above.
 """
 from __future__ import annotations
 
@@ -31,6 +36,7 @@ import torch
 
 from . import checkpoint as CK
 from . import dist as ddist
+from . import schedules
 from .config import DRAKE_VOCAB_SIZE, PARAMS, PRESETS, SCALE_PARAMS, TRAIN
 from .model import MODEL_CLASSES, model_params
 from .optim import check_accum_steps
@@ -58,6 +64,21 @@ def build_model(model_name: str, scale: bool, params: dict, scale_params: dict, 
     }[model_name]
     model = MODEL_CLASSES[model_name](**cfg, precision=precision).to(device)
     return model, cfg, params
+
+
+def no_decay_groups(model, kinds):
+    """two torch-style parameter groups for the autograd path: everything else, then (weight_decay 0) the parameters `kinds`
+    keeps out of weight decay -- by module type: Linear biases, LayerNorm weights and biases, Embedding tables"""
+    kinds = CK.check_no_decay(kinds)
+    types = {"bias": torch.nn.Linear, "layernorm": torch.nn.LayerNorm, "embedding": torch.nn.Embedding}
+    skip = set()
+    for mod in model.modules():
+        for kind in kinds:
+            if isinstance(mod, types[kind]):
+                ps = [mod.bias] if kind == "bias" else list(mod.parameters(recurse=False))
+                skip.update(id(p) for p in ps if p is not None)
+    ps = list(model.parameters())
+    return [{"params": [p for p in ps if id(p) not in skip]}, {"params": [p for p in ps if id(p) in skip], "weight_decay": 0.0}]
 
 
 def get_model_path(dir, model_name: str, scale: bool) -> str:
@@ -120,6 +141,29 @@ def engine_loop(engine, n_train: int, T: int, B: int, rank: int, world: int, ite
     engine.check_status()         # end of the run: a timed-out dW hand-over must not end in a saved checkpoint
 
 
+LR_SCHEDULES = ("reference", "constant", "warmup-cosine", "warmup-linear", "cyclic")
+
+
+def _no_decay_arg(text: str):
+    """--no-decay bias,layernorm -> ("bias", "layernorm")"""
+    try:
+        return CK.check_no_decay([k.strip() for k in text.split(",") if k.strip()])
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
+def lr_values(args, base_lr: float, max_lr: float):
+    """the rate of every optimizer step 0 .. --iters - 1 under --lr-schedule (None for `reference`, which is stepped at evaluations)"""
+    if args.lr_schedule == "reference":
+        return None
+    if args.lr_schedule == "constant":
+        return schedules.constant(base_lr, max(int(args.iters), 1))
+    if args.lr_schedule == "cyclic":
+        return schedules.cyclic(base_lr, max_lr, 5, max(int(args.iters), 1))
+    form = schedules.warmup_cosine if args.lr_schedule == "warmup-cosine" else schedules.warmup_linear
+    return form(max_lr, args.warmup_steps, args.iters, args.min_lr)
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="Train a DrakeGPT language model on MI355X")
     ap.add_argument("--model", default="TransformerLM", choices=list(MODEL_CLASSES))
@@ -153,6 +197,18 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--accum-steps", type=int, default=1, metavar="K",
                     help="gradient accumulation: K micro-batches of batch_size rows per AdamW step (the effective batch is K * "
                     "batch_size * world_size; --iters and --eval-interval count optimizer steps; default 1)")
+    ap.add_argument("--lr-schedule", default="reference", choices=list(LR_SCHEDULES),
+                    help="reference (default): the reference's CyclicLR(base_lr, max_lr, step_size_up=5), stepped once per evaluation.  "
+                    "The others give every optimizer step its own rate over --iters steps, looked up on the GPU from a table staged "
+                    "once: constant (the preset's base_lr), warmup-cosine / warmup-linear (--warmup-steps of linear warm-up to the "
+                    "preset's max_lr, then a cosine / a straight line down to --min-lr at the last step), cyclic (that CyclicLR "
+                    "stepped after every optimizer step)")
+    ap.add_argument("--warmup-steps", type=int, default=0, metavar="N", help="warm-up steps of warmup-cosine / warmup-linear: step s "
+                    "< N trains at max_lr * (s + 1) / N (default 0; --iters must exceed N + 1)")
+    ap.add_argument("--min-lr", type=float, default=0.0, metavar="X", help="the rate warmup-cosine / warmup-linear end on (default 0)")
+    ap.add_argument("--no-decay", type=_no_decay_arg, default=(), metavar="KINDS",
+                    help="comma-separated kinds of parameter kept out of weight decay: bias (every Linear bias), layernorm (LayerNorm "
+                    "weights and biases), embedding (the token and position tables); default: none, every parameter decays")
     ap.add_argument("--save-every", type=int, default=None, metavar="N",
                     help="write the full training state (weights, optimizer, counters, generator: everything --resume needs) after "
                     "the evaluation of every N-th iteration and after the last one; N must be a multiple of --eval-interval "
@@ -167,6 +223,13 @@ def parse_args(argv=None):
     """build_parser().parse_args plus the checks that span several flags"""
     ap = build_parser()
     args = ap.parse_args(argv)
+    if args.lr_schedule not in ("warmup-cosine", "warmup-linear") and (args.warmup_steps != 0 or args.min_lr != 0.0):
+        ap.error(f"--warmup-steps and --min-lr go with --lr-schedule warmup-cosine or warmup-linear, not {args.lr_schedule}")
+    if args.lr_schedule != "reference":
+        try:
+            lr_values(args, 1.0, 1.0)          # (the rates come from the preset later: the shape is checked here)
+        except ValueError as e:
+            ap.error(f"--lr-schedule {args.lr_schedule}: {e} (total is --iters, warmup is --warmup-steps)")
     if args.save_every is not None and (args.save_every < 1 or args.save_every % args.eval_interval):
         ap.error(f"--save-every {args.save_every} must be a positive multiple of --eval-interval {args.eval_interval} (offsets are "
                  "staged per evaluation interval: the state is written between two stages)")
@@ -188,9 +251,15 @@ def _to_cpu(obj):
 
 
 def run_args(args, K: int, world: int) -> dict:
-    """the arguments a resumed run must repeat"""
+    """the arguments a resumed run must repeat (RUN_ARG_DEFAULTS: those a file written before they existed ran with)"""
     return {"model": args.model, "preset": args.preset, "scale": bool(args.scale), "precision": args.precision, "accum_steps": K,
-            "world_size": world}
+            "world_size": world, "lr_schedule": args.lr_schedule, "warmup_steps": int(args.warmup_steps), "min_lr": float(args.min_lr),
+            "no_decay": list(args.no_decay),
+            # the table's length: the step count the schedule was laid out over
+            "schedule_iters": None if args.lr_schedule == "reference" else int(args.iters)}
+
+
+RUN_ARG_DEFAULTS = {"lr_schedule": "reference", "warmup_steps": 0, "min_lr": 0.0, "no_decay": [], "schedule_iters": None}
 
 
 def save_run_state(path: str, *, next_iteration: int, sched_steps: int, must_match: dict, model, engine=None, optimizer=None,
@@ -222,7 +291,7 @@ def load_run_state(path: str, must_match: dict) -> dict:
     except ValueError as e:
         raise SystemExit(f"--resume: {e}") from None
     for field, own in must_match.items():
-        saved = st["args"].get(field, "<absent>")
+        saved = st["args"].get(field, RUN_ARG_DEFAULTS.get(field, "<absent>"))
         if saved != own:
             raise SystemExit(f"--resume: {field} differs: {path} was written with {saved!r}, this run has {own!r}")
     return st
@@ -271,17 +340,24 @@ def main(argv=None):
     B, T = params["batch_size"], params["context_length"]
     base_lr, max_lr = params["base_lr"], params["max_lr"]
 
+    table = lr_values(args, base_lr, max_lr)          # one rate per optimizer step, or None: the reference's CyclicLR at evaluations
+
     engine = None
     if args.model == "TransformerLM":
         from .engine import TrainEngine
         engine = TrainEngine(model, B, T, lr=base_lr, betas=params["betas"], seed=42, rank=rank, world_size=world, process_group=pg,
-                             max_grad_norm=args.grad_clip, accum_steps=K)
+                             max_grad_norm=args.grad_clip, accum_steps=K, lr_schedule=table, no_decay=args.no_decay)
         engine.set_corpus(train_dev)
     else:
         # the five earlier-stage models train through the autograd path; their flat-buffer AdamW all-reduces the gradient
         from .optim import AdamW
-        optimizer = AdamW(model.parameters(), lr=base_lr, betas=params["betas"], process_group=pg, world_size=world,
+        groups = model.parameters()
+        if args.no_decay:
+            groups = no_decay_groups(model, args.no_decay)
+        optimizer = AdamW(groups, lr=base_lr, betas=params["betas"], process_group=pg, world_size=world,
                           max_grad_norm=args.grad_clip)
+        if table is not None:
+            table = schedules.as_table(table).tolist()          # the fp32 values the engine's table would hold
 
     must_match = run_args(args, K, world)
     start = 0
@@ -321,12 +397,16 @@ def main(argv=None):
             engine.check_status()
         losses = evaluate_loss(train_dev, val_dev, model, args.eval_iters, T, B, device, engine=engine)
         sched["steps"] += 1
-        lr = cyclic_lr(sched["steps"], base_lr, max_lr)
-        if engine is not None:
-            engine.set_lr(lr)
+        if table is not None:
+            # a per-step schedule: nothing to set here; report the rate of the next step
+            lr = engine.current_lr() if engine is not None else table[min(it + 1, len(table) - 1)]
         else:
-            for g in optimizer.param_groups:
-                g["lr"] = lr
+            lr = cyclic_lr(sched["steps"], base_lr, max_lr)
+            if engine is not None:
+                engine.set_lr(lr)
+            else:
+                for g in optimizer.param_groups:
+                    g["lr"] = lr
         if rank == 0:
             el = time.perf_counter() - t0
             line = {"step": it + 1, "train_loss": float(losses["train"]), "val_loss": float(losses["val"]), "lr": lr,
@@ -345,6 +425,9 @@ def main(argv=None):
     else:
         from . import ops
         for it in range(start, args.iters):
+            if table is not None:
+                for g in optimizer.param_groups:
+                    g["lr"] = table[min(it, len(table) - 1)]
             if K == 1:
                 ix = ddist.shard_rows(draw_offsets(len(train_data), T, B * world, None), rank, world).to(device, non_blocking=True)
                 x, y = ops.batch_gather(train_dev, ix, T)

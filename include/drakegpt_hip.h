@@ -478,6 +478,23 @@ int dg_adamw_step_clip(float* p, const float* g, float* m, float* v, int64_t n, 
                        float grad_scale, const float* clip_coef, void* shadow_bf16, int advance_step, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Per-step learning rate and weight-decay groups inside the AdamW launch -- ref: torch.optim.lr_scheduler stepped after every
+ * optimizer.step(), and torch.optim.AdamW over two parameter groups of which one has weight_decay = 0.
+ *   s = rng_state.step (read once per workgroup, before any arrival),  t = s + 1
+ *   lr_table (device fp32 [lr_table_len], lr_table_len >= 1; may be NULL with lr_table_len == 0):
+ *     lr = lr_table[min(s, lr_table_len - 1)]  instead of hyper[0]: past the end of the table its last entry holds.
+ *   no_decay_bits (device uint32 [ceil(ceil(n / 64) / 32)]; may be NULL): bit (G & 31) of word (G >> 5) covers the granule of
+ *     elements [64 G, 64 G + 64).  A set bit: p *= 1.0f for those elements instead of p *= 1 - lr*wd, which is exact, so they
+ *     get the bits dg_adamw_step gives with weight_decay = 0; every other element gets the bits it gets without a bitmap.
+ *   clip_coef (device fp32 [1]; may be NULL): as in dg_adamw_step_clip.
+ * With all three NULL the result is dg_adamw_step's, bit for bit; the lr that was used is written nowhere (the host knows the
+ * table and the step).  One extra cached word per wave iteration (256 floats); no LDS, no further atomics.
+ * DG_ERR_ARG: what dg_adamw_step refuses, a NULL lr_table with lr_table_len != 0, an lr_table with lr_table_len < 1. */
+int dg_adamw_step_sched(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, uint32_t* rng_state,
+                        float grad_scale, const float* clip_coef, const float* lr_table, int64_t lr_table_len,
+                        const uint32_t* no_decay_bits, void* shadow_bf16, int advance_step, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Gradient accumulation -- ref: k x `(loss / k).backward()` summing into p.grad between two optimizer.step() calls.  One
  * streaming pass per micro-step over the flat fp32 gradient g[0, n) of that micro-batch:
  *   ctl (4 device uint32) = {j, k, arrival counter, 0}: j = micro-step inside the current optimizer step, k = accum_steps >= 1
