@@ -270,6 +270,63 @@ def assert_rowwise_each(got: Tensor, ref: Tensor, group: int, bounds: Tensor, na
 
 
 # --------------------------------------------------------------------------------------
+# decode attention: one query (position t) against a K/V cache kept in the training layout
+# --------------------------------------------------------------------------------------
+def decode_attention_fp64(cache: Tensor, t: int, B: int, Tcap: int, NH: int, H: int, scale: Optional[float] = None,
+                          row: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """out[b, h] = softmax(q_t . K[0..t]^T * scale) . V[0..t] over a cache [B, Tcap, 3*NH*H] (row = position, q | k | v thirds,
+    heads inside a third).  ``row`` [B, 3*NH*H]: row t is replaced by it first (the append form: the new token's q/k/v arrive
+    in a staging row).  Rows > t are never touched (they may hold NaN).  Returns out [B, NH*H] and P [B, NH, t+1], fp64."""
+    assert tuple(cache.shape) == (B, Tcap, 3 * NH * H) and 0 <= t < Tcap, (tuple(cache.shape), t)
+    c = cache.detach().cpu().reshape(B, Tcap, 3, NH, H)
+    n = t + 1 if row is None else t                                       # (the thirds are converted one by one: 50 MB caches)
+    q, k, v = f64(c[:, t, 0]), f64(c[:, :n, 1]), f64(c[:, :n, 2])         # (B, NH, H), (B, n, NH, H) twice
+    if row is not None:
+        r = f64(row).reshape(B, 3, NH, H)
+        q, k, v = r[:, 0], torch.cat([k, r[:, 1:2]], 1), torch.cat([v, r[:, 2:3]], 1)
+    scale = H ** -0.5 if scale is None else scale
+    P = torch.softmax(torch.einsum("bhd,bjhd->bhj", q, k) * scale, -1)
+    return torch.einsum("bhj,bjhd->bhd", P, v).reshape(B, NH * H), P
+
+
+def spotlight_decode_inputs(B: int, Tcap: int, NH: int, H: int, t: int, j_star: int, seed: int, dtype: torch.dtype) -> Tensor:
+    """A randn cache [B, Tcap, 3*NH*H] in ``dtype`` whose key j_star holds about half of query t's probability in every (b, h):
+    k[b, j_star, h] = c * q / |q| with c solved in fp64 so that its score equals the log-sum-exp of the other keys' scores.
+    At t = 8191 a randn key holds ~1e-4 of the mass and a kernel that drops it (or reads a stale row in its place) stays inside
+    a bf16 bound; with the spotlight on that key the same kernel is wrong by O(1).
+    The condition 0.25 <= P[b, h, j_star] <= 0.75 is asserted on the fp64 reference of the ROUNDED inputs: a condition on the
+    operands, not a measurement."""
+    assert 1 <= t < Tcap and 0 <= j_star <= t, (t, j_star, Tcap)
+    g = torch.Generator().manual_seed(seed)
+    cache = torch.randn((B, Tcap, 3 * NH * H), generator=g).to(dtype)
+    c = cache.view(B, Tcap, 3, NH, H)
+    scale = H ** -0.5
+    q = f64(c[:, t, 0])                                                   # (B, NH, H)
+    s = torch.einsum("bhd,bjhd->bhj", q, f64(c[:, :t + 1, 1])) * scale
+    s[:, :, j_star] = float("-inf")
+    qn = q.norm(dim=-1, keepdim=True)
+    key = q / qn * (torch.logsumexp(s, -1, keepdim=True) / (qn * scale))  # score of the key = lse of the others
+    cache.view(B, Tcap, 3, NH, H)[:, j_star, 1] = key.to(dtype)
+    P = decode_attention_fp64(cache, t, B, Tcap, NH, H)[1][:, :, j_star]
+    assert 0.25 <= P.min().item() and P.max().item() <= 0.75, (P.min().item(), P.max().item())
+    return cache
+
+
+DECODE_TOL_FP32 = 2e-5                     # the suite's fp32 attention-forward tolerance (tests/test_gpu_ops.py)
+# bf16: the decode kernels compute in fp32 and round only the stored output, which moves every element by at most 2^-8 |x|,
+# hence a (b, head) group by at most 2^-8 of its norm; the fp32 arithmetic in front of it gets the fp32 tolerance
+DECODE_TOL_BF16 = BF16_RN + DECODE_TOL_FP32
+
+
+def assert_decode_output(got: Tensor, ref: Tensor, H: int, dtype: torch.dtype, name: str = "") -> float:
+    """a decode-attention output [B, NH*H] against decode_attention_fp64: finite, and every (b, head) group within the bound
+    of its dtype.  Returns the worst group."""
+    if not bool(torch.isfinite(f64(got)).all()):
+        raise AssertionError(f"{name}: {int((~torch.isfinite(f64(got))).sum())} non-finite elements")
+    return assert_rowwise(got, ref, H, DECODE_TOL_BF16 if dtype == torch.bfloat16 else DECODE_TOL_FP32, name)
+
+
+# --------------------------------------------------------------------------------------
 # planted defects (host tensors only): what the localized checks must catch
 # --------------------------------------------------------------------------------------
 def plant(x: Tensor, kind: str, group: int) -> Tensor:

@@ -260,3 +260,88 @@ def test_assert_within_rounding_counts_and_locates():
     got[0, 0] = float("inf")
     with pytest.raises(AssertionError, match="9 of 6144"):
         P.assert_within_rounding(got, ref, 0.0, 1, "x")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# decode attention: the reference, the spotlight inputs, and the defects the checks of tests/test_gpu_decode.py must refuse
+# ---------------------------------------------------------------------------------------------------------------------
+def test_decode_reference_is_row_t_of_the_causal_reference():
+    B, Tcap, NH, H, t = 2, 40, 3, 8, 29
+    g = torch.Generator().manual_seed(3)
+    cache = torch.randn(B, Tcap, 3 * NH * H, generator=g)
+    cache[:, t + 1:] = float("nan")                          # rows past t are not read
+    out, Pr = P.decode_attention_fp64(cache, t, B, Tcap, NH, H)
+    full = P.attention_fp64(cache[:, :t + 1].reshape(B * (t + 1), -1), None, B, t + 1, NH, H)
+    assert (out - full["out"].view(B, t + 1, NH * H)[:, t]).abs().max().item() < 1e-13
+    assert (Pr - full["P"][:, :, t]).abs().max().item() < 1e-14 and (Pr.sum(-1) - 1).abs().max().item() < 1e-14
+    # the append form: row t comes from the staging row, whatever the cache holds there
+    stale = cache.clone()
+    stale[:, t] = float("nan")
+    out2, P2 = P.decode_attention_fp64(stale, t, B, Tcap, NH, H, row=cache[:, t])
+    assert torch.equal(out2, out) and torch.equal(P2, Pr)
+    out3, _ = P.decode_attention_fp64(cache, t, B, Tcap, NH, H, scale=0.3)
+    assert not torch.allclose(out3, out)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, bf])
+@pytest.mark.parametrize("Tcap,H,t,j_star", [(70, 8, 1, 0), (70, 8, 69, 64), (131, 96, 130, 130), (1024, 64, 1023, 1022)])
+def test_spotlight_key_holds_half_of_the_mass(dtype, Tcap, H, t, j_star):
+    B, NH = 2, 3
+    cache = P.spotlight_decode_inputs(B, Tcap, NH, H, t, j_star, 5, dtype)
+    assert cache.dtype == dtype and tuple(cache.shape) == (B, Tcap, 3 * NH * H)
+    _, Pr = P.decode_attention_fp64(cache, t, B, Tcap, NH, H)
+    assert (Pr[:, :, j_star] - 0.5).abs().max().item() < 0.05
+    # only the key row's k third differs from the plain draw of the same seed
+    plain = torch.randn((B, Tcap, 3 * NH * H), generator=torch.Generator().manual_seed(5)).to(dtype)
+    diff = (cache != plain).view(B, Tcap, 3, NH * H)
+    assert bool(diff[:, j_star, 1].any()) and int(diff.sum()) == int(diff[:, j_star, 1].sum())
+
+
+DECODE_DEFECTS = ("key_t_left_out", "stale_row_t", "one_key_too_many", "v_of_next_head", "last_group_unwritten", "first_lane_round_only")
+
+
+@pytest.mark.parametrize("defect", DECODE_DEFECTS)
+def test_planted_decode_defect_is_refused(defect):
+    """(B, NH, H, t) = (3, 3, 96, 130), spotlight on key t; the emulated kernel output is the fp64 result of the defective
+    algorithm rounded as a bf16 kernel stores it (P.rb), judged by the helper and bound the GPU tests use"""
+    B, NH, H, t, Tcap = 3, 3, 96, 130, 132
+    good = P.spotlight_decode_inputs(B, Tcap, NH, H, t, t, 9, bf)
+    good[:, t + 1:] = float("nan")                           # poisoned like the GPU tests' caches
+    row = good[:, t].clone()
+    stale = good.clone()
+    stale[:, t] = torch.randn(B, 3 * NH * H, generator=torch.Generator().manual_seed(10)).to(bf)   # what an earlier call left there
+    ref, _ = P.decode_attention_fp64(stale, t, B, Tcap, NH, H, row=row)
+    assert torch.equal(ref, P.decode_attention_fp64(good, t, B, Tcap, NH, H)[0])
+    P.assert_decode_output(P.rb(ref), ref, H, bf, "undamaged")
+    P.assert_decode_output(ref.float(), ref, H, torch.float32, "undamaged fp32")
+
+    def heads(c):
+        return c.view(B, Tcap, 3, NH, H)
+
+    def attend(keys):                                        # query t over the given key positions only
+        q = heads(good)[:, t, 0].double()
+        k, v = heads(good)[:, keys, 1].double(), heads(good)[:, keys, 2].double()
+        w = torch.softmax(torch.einsum("bhd,bjhd->bhj", q, k) * H ** -0.5, -1)
+        return torch.einsum("bhj,bjhd->bhd", w, v).reshape(B, NH * H)
+
+    assert (attend(slice(0, t + 1)) - ref).abs().max().item() < 1e-13
+    if defect == "key_t_left_out":
+        bad = attend(slice(0, t))
+    elif defect == "stale_row_t":
+        bad = P.decode_attention_fp64(stale, t, B, Tcap, NH, H)[0]
+    elif defect == "one_key_too_many":                       # the poisoned row t + 1
+        bad = attend(slice(0, t + 2))
+        assert not torch.isfinite(bad).any()
+    elif defect == "v_of_next_head":
+        c = good.clone()
+        heads(c)[:, :t + 1, 2, 1] = heads(good)[:, :t + 1, 2, 2]
+        bad = P.decode_attention_fp64(c, t, B, Tcap, NH, H)[0]
+    elif defect == "last_group_unwritten":
+        bad = ref.clone()
+        bad[B - 1, (NH - 1) * H:] = 55.0                     # the guard fill of the GPU tests
+    elif defect == "first_lane_round_only":                  # keys j >= 64 never visited
+        bad = attend(slice(0, 64))
+    with pytest.raises(AssertionError, match="non-finite" if defect == "one_key_too_many" else "worst group"):
+        P.assert_decode_output(P.rb(bad), ref, H, bf, defect)
+    with pytest.raises(AssertionError):
+        P.assert_decode_output(bad.float(), ref, H, torch.float32, defect)
