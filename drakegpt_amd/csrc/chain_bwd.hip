@@ -14,8 +14,8 @@
 // operand of W1's weight gradient), g / g2 (dY operands of W2's / Wproj's), the gradient stream dx / dx2, do, and the partial rows of
 // every bias / LayerNorm gradient on the way (b1 = column sums of df, b2 / bproj = column sums of g / g2, dgamma / dbeta of both
 // LayerNorms) -- here TWO partial rows per workgroup (one per wave row: no cross-wave exchange), i.e. 2 x blocks rows for
-// dg_reduce_partials.  The LayerNorm backward consumes the dX GEMM's fp32 accumulators directly (the separate launches round them
-// to bf16 in between).
+// dg_reduce_partials.  The LayerNorm backward takes the dX GEMM's accumulators rounded to bf16 in registers, as the separate dX
+// launch hands them over (x-hat crosses the row-sum exchange as bf16 too); the hidden values are never stored.
 //
 // MODE 0: everything above (between the attention backward of block l and that of block l-1); 1: the second half only (top of the
 // stack: g arrives from the loss head's dropout backward); 2: the first half only (block 0: g is the token-table operand, no

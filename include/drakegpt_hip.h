@@ -561,7 +561,7 @@ int dg_pack_chain_weights_batched(const int64_t* desc, int n_desc, int total_sta
  * operands of the weight gradients), dx1 / dx2 (the bf16 gradient stream), dout (the attention backward's input) and the
  * partial rows of b1 (column sums of df), b2 / bproj (column sums of g1 / g2) and both LayerNorms' dgamma / dbeta: TWO rows
  * per 64-row block, row 2 * block + {0, 1} at `part_stride` floats (2 * M / 64 rows for dg_reduce_partials).  The LayerNorm
- * backward consumes the dX GEMM's fp32 accumulators (the separate launches round them to bf16 in between).  The four weight
+ * backward takes the dX GEMM's accumulators rounded to bf16 in registers (what the separate dX launch hands over).  The four weight
  * operands are the W^T shadows ([in, out] bf16) PACKED by dg_pack_chain_weights (wqkvT: N = C, K = 3C; w2T: N = 4C, K = C;
  * w1T: N = C, K = 4C; wprojT: N = C, K = C).  sign_bits: dg_gemm_nt's layout for an [M, 4C] output.
  * mode 0: everything above (dresid2 is dx1: pass the same pointer).  mode 1 (top of the stack): the second half only, g1

@@ -102,10 +102,8 @@ def assert_within_rounding(got: Tensor, ref: Tensor, envelope, ulps: float = 1.0
                              f"(32 x 32 tile ({row // TILE}, {col // TILE}), 8-element chunk {col // 8} of row {row}): "
                              f"got {g.reshape(-1)[flat].item():.6g}, ref {r.reshape(-1)[flat].item():.6g}, "
                              f"allowed {bound.reshape(-1)[flat].item():.3g}")
-    sel = err if where is None else err[where.cpu()]
-    bsel = bound if where is None else bound[where.cpu()]
-    ok = bsel > 0
-    return (sel[ok] / bsel[ok]).max().item() if bool(ok.any()) else 0.0
+    ok = bound > 0 if where is None else (bound > 0) & where.cpu()           # (masked, not gathered: these tensors reach 50 M elements)
+    return torch.where(ok, err / bound, torch.zeros_like(err)).max().item() if r.numel() else 0.0
 
 
 def gemm_envelope(A: Tensor, B: Tensor, K: Optional[int] = None, bias: Optional[Tensor] = None, resid: Optional[Tensor] = None,
@@ -133,6 +131,67 @@ def mask_margin(pre: Tensor, envelope: Tensor, max_share: float = 1e-3) -> Tenso
     share = 1.0 - decided.double().mean().item()
     assert share < max_share, f"{share:.2e} of the pre-activations lie within the envelope of zero"
     return decided
+
+
+def rounding_margin(value: Tensor, envelope: Tensor, max_share: float = 1e-3) -> Tuple[Tensor, float]:
+    """the analogue of mask_margin for a value a kernel rounds to bf16 and never stores (the dX GEMM outputs in front of the chain's
+    LayerNorm backward): where the fp64 value lies within ``envelope`` of a bf16 rounding boundary (the midpoint of two neighbours),
+    the kernel's fp32 value may round to the other neighbour, one bf16 ulp away from rb(value).  Returns the per-element allowance --
+    one ulp of the value's binade where the rounding is undecided, zero elsewhere -- and the undecided share, which must stay below
+    ``max_share`` (a condition on the operands and the envelope, not a measurement of a kernel).
+    Where the envelope is no longer small against the ulp (4 e >= ulp: a sum that cancels to almost nothing) the fp32 value v' may
+    lie several ulps away: |rb(v') - rb(v)| <= |v' - v| + ulp(v') / 2 + ulp(v) / 2 with ulp(v') <= 2^-7 (|v| + e), hence < 2 (e + ulp)."""
+    v, e = f64(value), f64(envelope)
+    r = rb(v)
+    ulp = 2.0 ** (torch.floor(torch.log2(v.abs().clamp_min(2.0 ** -126))) - 7)       # spacing of bf16 in the value's binade
+    # distance to the nearest rounding boundary: the midpoints sit half an ulp from the rounded value
+    dist = (ulp / 2 - (v - r).abs()).abs()
+    undecided = dist <= e
+    share = undecided.double().mean().item()
+    assert share < max_share, f"{share:.2e} of the hidden values lie within the envelope of a bf16 rounding boundary"
+    return torch.where(undecided, torch.where(4 * e < ulp, ulp, 2 * (e + ulp)), torch.zeros_like(ulp)), share
+
+
+# --------------------------------------------------------------------------------------
+# LayerNorm: fp64 reference and the envelope of an fp32 evaluation
+# --------------------------------------------------------------------------------------
+def layernorm_fp64(x: Tensor, w: Tensor, b: Tensor, eps: float = 1e-5):
+    """y, mean, std, xhat of a row-wise LayerNorm in fp64 (mean / std [M, 1])"""
+    xd = x.double()
+    mean = xd.mean(1, keepdim=True)
+    var = ((xd - mean) ** 2).mean(1, keepdim=True)
+    std = (var + eps).sqrt()
+    xhat = (xd - mean) / std
+    return xhat * w.double() + b.double(), mean, std, xhat
+
+
+def layernorm_envelope(mean: Tensor, std: Tensor, xhat: Tensor, w: Tensor) -> Tensor:
+    """y = gamma * (x - mean) / std + beta in fp32.  The row mean carries one fp32 rounding of a number of size |mean|
+    (2^-24 |mean|; the factor 4 covers the summation), x - mean one of its own (2^-24 |x - mean|, and |x - mean| / std = |xhat|), so
+    xhat moves by at most 4 * 2^-24 * (|mean| / std + 1) * max|xhat| and y by |gamma| times that; what follows (rstd, the multiply-add)
+    is a couple of fp32 ulps of the result: the 2^-23 |ref| term of the caller."""
+    return 4 * 2.0 ** -24 * (mean.abs() / std + 1) * w.double().abs() * xhat.abs().amax(1, keepdim=True).clamp_min(2.0 ** -24)
+
+
+def assert_layernorm_stats(mu: Tensor, rs: Tensor, x: Tensor, mean: Tensor, std: Tensor, xhat: Tensor, name: str = "") -> Tuple[float, float]:
+    """the stored row statistics of an fp32 LayerNorm against layernorm_fp64 of the same rows; returns (mean, rstd) error / bound.
+    mean: within 4 fp32 roundings of the size of the partial sums it is made of.  On rows with |mean| >> spread (the offset rows
+    of tests/test_gpu_conditioning.py) that size is |mean| itself; in general no partial sum of x / C exceeds the row's mean |x|
+    (>= |mean|, equal up to spread / |mean| on offset rows), which is what is used here -- a row whose mean happens to cancel
+    to 1e-6 still carries the roundings of summands of size 1.  rstd: (mean error / std) relative, plus two fp32 ulps."""
+    mu, rs = f64(mu).view(-1), f64(rs).view(-1)
+    mean, std, amax = f64(mean).view(-1), f64(std).view(-1), f64(xhat).abs().amax(1)
+    size = f64(x).abs().mean(1)
+    out = []
+    for what, err, bound in (("mean", (mu - mean).abs(), 4 * 2.0 ** -24 * size),
+                             ("rstd", (rs * std - 1).abs(), 4 * 2.0 ** -24 * (mean.abs() / std + 1) * amax + 2.0 ** -22)):
+        bad = ~(err <= bound)
+        if bool(bad.any()):
+            row = int(torch.where(bad, torch.nan_to_num(err / bound, nan=float("inf")), torch.zeros_like(err)).argmax())
+            raise AssertionError(f"{name} {what}: {int(bad.sum())} of {err.numel()} rows outside the bound; worst row {row} (64-row block {row // 64}, "
+                                 f"32-row tile {row // TILE}): error {err[row].item():.3g}, allowed {bound[row].item():.3g}")
+        out.append((err / bound).max().item())
+    return out[0], out[1]
 
 
 def single_rounding_envelope(value: Tensor, n: int) -> float:

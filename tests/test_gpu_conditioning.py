@@ -134,21 +134,8 @@ def _ln_rows(kind, M, C, g):
     raise ValueError(kind)
 
 
-def _ln_fp64(x, w, b, eps=1e-5):
-    xd = x.double()
-    mean = xd.mean(1, keepdim=True)
-    var = ((xd - mean) ** 2).mean(1, keepdim=True)
-    std = (var + eps).sqrt()
-    xhat = (xd - mean) / std
-    return xhat * w.double() + b.double(), mean, std, xhat
-
-
-def _ln_envelope(mean, std, xhat, w):
-    """y = gamma * (x - mean) / std + beta in fp32.  The row mean carries one fp32 rounding of a number of size |mean|
-    (2^-24 |mean|; the factor 4 covers the summation), x - mean one of its own (2^-24 |x - mean|, and |x - mean| / std = |xhat|), so
-    xhat moves by at most 4 * 2^-24 * (|mean| / std + 1) * max|xhat| and y by |gamma| times that; what follows (rstd, the multiply-add)
-    is a couple of fp32 ulps of the result: the 2^-23 |ref| term of the caller."""
-    return 4 * 2.0 ** -24 * (mean.abs() / std + 1) * w.double().abs() * xhat.abs().amax(1, keepdim=True).clamp_min(2.0 ** -24)
+# the fp64 LayerNorm and the envelope of its fp32 evaluation: shared with tests/test_gpu_chain_parity.py
+from oracle.parity import layernorm_envelope as _ln_envelope, layernorm_fp64 as _ln_fp64  # noqa: E402
 
 
 @pytest.mark.parametrize("C", [384, 1024, 100])

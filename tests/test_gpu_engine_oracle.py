@@ -51,6 +51,9 @@ def test_scaled_bf16_graph_step_with_dropout_matches_oracle(dev):
     eng.keep_logits = True
     # the dispatch bench.py gets: grouped dW with the one-hot token problem, fused LN backward, colsum epilogue, sign bits
     assert eng.grouped_dw and eng.onehot is not None and eng.last_block_act and eng.stream_dtype == torch.bfloat16
+    # ... and the forward chain (dg_block_chain_fwd modes 2 / 0 / 1) between the attention calls, the separate backward launches:
+    # what this test compares with the oracle is what the benchmark times
+    assert eng.chain_full and not eng.chain_bwd
     assert ops.layernorm_bwd_fused_supported(C) and ops.gemm_nt_colsum_rows(torch.bfloat16, B * T, 4 * C, C) > 0
     assert ops.gemm_nt_sign_bits_supported(torch.bfloat16, 4 * C, C)
     g = torch.Generator().manual_seed(3)

@@ -894,7 +894,7 @@ def test_engine_minimal_shapes(dev):
 
 
 @pytest.mark.parametrize("mode", [0, 1, 2, 3, 4])
-@pytest.mark.parametrize("M,p", [(64, 0.0), (4160, 0.2), (16384, 0.2)])
+@pytest.mark.parametrize("M,p", [(64, 0.0), (4160, 0.2), (16384, 0.2), ("cus+1", 0.2)])
 def test_block_chain_kernel_equals_the_launches_it_replaces(dev, mode, M, p):
     """dg_block_chain_fwd (round 3): the row-local chain of a residual block -- proj + residual, LayerNorm 2, FFN1 (ReLU, sign
     bits), FFN2 + residual, the next block's LayerNorm 1 and packed QKV (ref: src/model_component.py:454,505-506,320-325,392-393,
@@ -903,10 +903,12 @@ def test_block_chain_kernel_equals_the_launches_it_replaces(dev, mode, M, p):
     bits are IDENTICAL (same MFMA sequence per element, same hash), the row statistics differ by an fp32 rounding (four 96-column
     partials combined with Chan's formula instead of one wave-wide sum), hence an occasional bf16 ulp in the LayerNorm outputs
     and what follows them.  One block (M = 64), several blocks per workgroup (M = 16384 > 256 x 64 is not: 4160 = 65 blocks on
-    256 CUs is), every mode."""
+    256 CUs is; "cus+1": 64 x (the device's CU count + 1) rows, the same on any CU count), every mode."""
     ops = _ops()
     from drakegpt_amd import sublayers as S
     C = 384
+    if M == "cus+1":
+        M = 64 * (torch.cuda.get_device_properties(dev).multi_processor_count + 1)
     assert ops.block_chain_supported(M, C, torch.bfloat16) and not ops.block_chain_supported(M + 8, C, torch.bfloat16)
     assert not ops.block_chain_supported(M, 768, torch.bfloat16)
     g = torch.Generator().manual_seed(M + mode)

@@ -345,3 +345,107 @@ def test_planted_decode_defect_is_refused(defect):
         P.assert_decode_output(P.rb(bad), ref, H, bf, defect)
     with pytest.raises(AssertionError):
         P.assert_decode_output(bad.float(), ref, H, torch.float32, defect)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the block chain: the stage checks of tests/test_gpu_chain_parity.py on a CPU stand-in (tests/chain_model.py)
+# ---------------------------------------------------------------------------------------------------------------------
+import os  # noqa: E402
+import sys  # noqa: E402
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import chain_model as CM  # noqa: E402
+
+CHAIN_OLD_TOL = 3e-4                           # the whole-tensor ratio of test_block_chain_kernel_equals_the_launches_it_replaces
+_CHAIN = {}
+
+
+def _chain_case(M, mode, p):
+    key = (M, mode, p)
+    if key not in _CHAIN:
+        op = CM.fwd_operands(M, M + mode)
+        _CHAIN[key] = (op, CM.fwd_standin(op, mode, p))
+    return _CHAIN[key]
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2, 3, 4])
+@pytest.mark.parametrize("M,p", [(64, 0.0), (64, 0.2), (320, 0.0), (320, 0.2)])
+def test_chain_standin_stays_inside_every_stage_bound(M, mode, p):
+    """the envelopes are not vacuous: fp64 rounded at the kernel's store points passes every stage, and the roundings alone
+    use a visible part of the bf16 stages' bounds"""
+    op, good = _chain_case(M, mode, p)
+    use = CM.check_fwd(good, op, mode, p, mask=good.get("mask"), grid=2)
+    assert use and all(0 <= u <= 1 for u in use.values()), use
+    for k in ("h2", "f", "h1", "qkv"):
+        assert k not in use or use[k] > 0.3, (k, use[k])
+
+
+@pytest.mark.parametrize("M", [64, 320])
+def test_chain_operand_recipe_leaves_few_signs_undecided(M):
+    """mask_margin's cap (1e-3) is a condition on the operands: the recipe meets it with a wide margin on the fp64 reference alone"""
+    op, good = _chain_case(M, 0, 0.2)
+    pre = good["h2"].double() @ op["w1"].double().T + op["b1"].double()
+    decided = P.mask_margin(pre, P.gemm_envelope(good["h2"], op["w1"], CM.C, op["b1"]))
+    assert 1.0 - decided.double().mean().item() < 5e-4
+
+
+# defects the old comparison (ratio of the whole tensor against the clean result at 3e-4; up to max(2, bytes / 100000) differing
+# sign-bit bytes) lets through at M = 320
+CHAIN_OLD_CHECK_MISSES = {"decided_sign_bit_flipped"}
+
+
+@pytest.mark.parametrize("defect", CM.FWD_DEFECTS)
+def test_planted_chain_defect_is_refused_at_its_stage(defect):
+    M, mode, p = 320, 0, 0.2
+    op, good = _chain_case(M, mode, p)
+    bad = CM.fwd_standin(op, mode, p, defect=defect, cus=2)
+    assert any(not torch.equal(bad[k], good[k]) for k in good)
+    with pytest.raises(AssertionError, match=CM.FWD_DEFECT_STAGE[defect] + r":.*\[64-row block \d+: workgroup \d+, round \d+"):
+        CM.check_fwd(bad, op, mode, p, mask=bad["mask"], grid=2)
+    flipped = int((bad["mask"] != good["mask"]).sum())
+    old_passes = all(P.rel(bad[k], good[k]) < CHAIN_OLD_TOL for k in good if k != "mask") and flipped <= 2
+    assert old_passes == (defect in CHAIN_OLD_CHECK_MISSES), (defect, {k: P.rel(bad[k], good[k]) for k in good}, flipped)
+
+
+def _chain_bwd_case(M, mode, p):
+    key = ("bwd", M, mode, p)
+    if key not in _CHAIN:
+        op = CM.bwd_operands(M, 7 * M + mode)
+        _CHAIN[key] = (op,) + CM.bwd_standin(op, mode, p)
+    return _CHAIN[key]
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2])
+@pytest.mark.parametrize("M,p", [(64, 0.0), (64, 0.2), (320, 0.2)])
+def test_chain_bwd_standin_stays_inside_every_stage_bound(M, mode, p):
+    op, good, parts = _chain_bwd_case(M, mode, p)
+    use = CM.check_bwd(good, parts, op, mode, p, op["mask"])
+    assert use and all(0 <= u <= 1 for u in use.values()), use
+    for k in ("dx1", "g1", "dx2", "g2", "df", "dout"):                    # the stand-in's own roundings use a visible part of each bound
+        assert k not in use or use[k] > 0.2, (k, use[k])
+
+
+@pytest.mark.parametrize("defect", CM.BWD_DEFECTS)
+def test_planted_chain_bwd_defect_is_refused_at_its_stage(defect):
+    M, mode, p = 320, 0, 0.2
+    op, good, parts = _chain_bwd_case(M, mode, p)
+    bad, bad_parts = CM.bwd_standin(op, mode, p, defect=defect)
+    assert any(not torch.equal(bad[k], good[k]) for k in good) or not torch.equal(bad_parts, parts)
+    with pytest.raises(AssertionError, match=CM.BWD_DEFECT_STAGE[defect] + ".*(row|block) "):
+        CM.check_bwd(bad, bad_parts, op, mode, p, op["mask"])
+
+
+def test_rounding_margin_marks_values_near_a_bf16_rounding_boundary():
+    # bf16 neighbours of 1.0 upwards: 1, 1 + 2^-7; the boundary between them is 1 + 2^-8
+    v = torch.tensor([1.0, 1.0 + 2.0 ** -8 - 1e-6, 1.0 + 2.0 ** -8 + 1e-6, 1.0 + 2.0 ** -8 - 1e-3, -(2.0 + 2.0 ** -7) + 1e-7, 0.75], dtype=torch.float64)
+    allow, share = P.rounding_margin(v, torch.full_like(v, 1e-5), max_share=1.0)
+    assert allow.tolist() == [0.0, 2.0 ** -7, 2.0 ** -7, 0.0, 2.0 ** -6, 0.0] and abs(share - 0.5) < 1e-12
+    with pytest.raises(AssertionError, match="rounding boundary"):
+        P.rounding_margin(v, torch.full_like(v, 1e-5))
+    # what the margin is for: a value computed in fp32 rounds to rb(v) or, only where it is marked, to the neighbour one ulp away
+    g = torch.Generator().manual_seed(0)
+    A, B = torch.randn(256, 384, generator=g).to(bf), (torch.randn(384, 384, generator=g) * 384 ** -0.5).to(bf)
+    exact = A.double() @ B.double().T
+    allow, share = P.rounding_margin(exact, P.gemm_envelope(A, B, 384), max_share=1.0)
+    diff = ((A.float() @ B.float().T).to(bf).double() - P.rb(exact)).abs()
+    assert bool((diff <= allow).all()) and 0 < share < 1
