@@ -4,11 +4,36 @@
 // 1024-thread workgroup per row that keeps the whole row in registers, so the logits are read from HBM exactly once.
 // Algorithmic bytes per row: V*4 read (+ V*sizeof(dlogits) written when training).
 #include "common.h"
+#include <float.h>
 
-template <typename TD, typename TL = float>
+// Loss options, a compile-time switch of every kernel below: the kernels end in a parameter pack `O... o` that is either empty (the
+// plain mean NLL: the code and the kernel arguments it always had) or one CeOpt (OPT below):
+// label smoothing eps in [0, 1) and the z-loss coefficient zeta >= 0.  Per row, with lse = mx + log s and p = softmax(x):
+//   objective  l   = lse - (1 - eps) x_t - (eps / V) sum_{i < V} x_i + zeta lse^2
+//   gradient   g_i = grad_scale (p_i (1 + 2 zeta lse) - (1 - eps) [i == t] - eps / V)
+// The cross-entropy part is evaluated as log s + (1 - eps)(mx - x_t) + (eps / V) sum_{i < V} (mx - x_i): every term is non-negative
+// and nothing rounds at the size of mx (see the comment in cross_entropy_row_bf16_kernel).  The sum runs over the V logits only:
+// neither the -inf that fills padding lanes nor the memory of columns V .. ldl - 1 enters it.  With zeta > 0 a gradient row sums to
+// 2 zeta lse grad_scale, not to zero.
+struct CeOpt { float eps, zeta; };
+__device__ __forceinline__ CeOpt ce_opt() { return CeOpt{0.f, 0.f}; }
+__device__ __forceinline__ CeOpt ce_opt(CeOpt opt) { return opt; }
+__device__ __forceinline__ float ce_objective(float mx, float logs, float xt, float sd, int V, CeOpt opt) {
+    const float lse = mx + logs;
+    return logs + (1.f - opt.eps) * (mx - xt) + opt.eps / (float)V * sd + opt.zeta * lse * lse;
+}
+// p_i enters the gradient times 1 + 2 zeta lse; the target's one-hot weighs 1 - eps; every column gives up eps / V
+__device__ __forceinline__ float ce_pscale(float mx, float logs, CeOpt opt) { return 1.f + 2.f * opt.zeta * (mx + logs); }
+__device__ __forceinline__ float ce_grad(float p, bool hot, float unif, CeOpt opt, float grad_scale) {
+    return (p - (hot ? 1.f - opt.eps : 0.f) - unif) * grad_scale;
+}
+
+template <typename TD, typename TL = float, typename... O>
 __global__ void cross_entropy_kernel(const TL* __restrict__ logits, int64_t ldl, const int64_t* __restrict__ targets,
                                      float* __restrict__ loss_rows, TD* __restrict__ dlogits, int64_t ldd,
-                                     float grad_scale, const float* __restrict__ gs_dev, int M, int V) {
+                                     float grad_scale, const float* __restrict__ gs_dev, int M, int V, O... o) {
+    constexpr bool OPT = sizeof...(O) != 0;
+    const CeOpt opt = ce_opt(o...);
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (row >= M) return;
@@ -16,20 +41,26 @@ __global__ void cross_entropy_kernel(const TL* __restrict__ logits, int64_t ldl,
     float mx = -INFINITY;
     for (int i = lane; i < V; i += 64) mx = fmaxf(mx, (float)x[i]);
     mx = wave_max(mx);
-    float s = 0.f;
-    for (int i = lane; i < V; i += 64) s += expf((float)x[i] - mx);
+    float s = 0.f, sd = 0.f;
+    for (int i = lane; i < V; i += 64) {
+        s += expf((float)x[i] - mx);
+        if (OPT) sd += mx - (float)x[i];
+    }
     s = wave_sum(s);
+    if (OPT) sd = wave_sum(sd);
     int64_t t = targets[row];
     t = t < 0 ? 0 : (t >= V ? V - 1 : t);
     const float lse = mx + logf(s);
-    if (lane == 0) loss_rows[row] = lse - (float)x[t];
+    if (lane == 0) loss_rows[row] = OPT ? ce_objective(mx, logf(s), (float)x[t], sd, V, opt) : lse - (float)x[t];
     if (dlogits) {
         TD* d = dlogits + (int64_t)row * ldd;
-        const float inv = 1.f / s;
+        const float inv = OPT ? ce_pscale(mx, logf(s), opt) / s : 1.f / s;
+        const float unif = OPT ? opt.eps / (float)V : 0.f;
         if (gs_dev) grad_scale *= gs_dev[0];
         for (int i = lane; i < (int)ldd; i += 64) {
             float g = 0.f;
-            if (i < V) g = (expf((float)x[i] - mx) * inv - (i == (int)t ? 1.f : 0.f)) * grad_scale;
+            if (i < V) g = OPT ? ce_grad(expf((float)x[i] - mx) * inv, i == (int)t, unif, opt, grad_scale)
+                               : (expf((float)x[i] - mx) * inv - (i == (int)t ? 1.f : 0.f)) * grad_scale;
             d[i] = from_f32<TD>(g);
         }
     }
@@ -38,10 +69,12 @@ __global__ void cross_entropy_kernel(const TL* __restrict__ logits, int64_t ldl,
 
 // Small vocabularies (V <= 128: the character-level model): 16 lanes per row, four rows per wave, the row held in registers
 // (the wave-per-row kernel above left 3/4 of its lanes idle at V = 80 and read the row three times: 12 us for 8 MB).
-template <typename TD>
+template <typename TD, typename... O>
 __global__ __launch_bounds__(256) void cross_entropy_small_kernel(const float* __restrict__ logits, int64_t ldl, const int64_t* __restrict__ targets,
                                                                   float* __restrict__ loss_rows, TD* __restrict__ dlogits, int64_t ldd,
-                                                                  float grad_scale, const float* __restrict__ gs_dev, int M, int V) {
+                                                                  float grad_scale, const float* __restrict__ gs_dev, int M, int V, O... o) {
+    constexpr bool OPT = sizeof...(O) != 0;
+    const CeOpt opt = ce_opt(o...);
     const int sub = threadIdx.x & 15;
     const int row = blockIdx.x * 16 + (threadIdx.x >> 4);
     const bool ok = row < M;
@@ -56,23 +89,32 @@ __global__ __launch_bounds__(256) void cross_entropy_small_kernel(const float* _
     }
 #pragma unroll
     for (int o = 8; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    float s = 0.f;
+    float s = 0.f, sd = 0.f;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) { v[k] = expf(v[k] - mx); s += v[k]; }
+    for (int k = 0; k < 8; ++k) {
+        if (OPT && sub + 16 * k < V) sd += mx - v[k];            // (the -inf of a padding lane stays out)
+        v[k] = expf(v[k] - mx); s += v[k];
+    }
 #pragma unroll
-    for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    for (int sh = 8; sh > 0; sh >>= 1) s += __shfl_xor(s, sh, 64);
+    if (OPT) {
+#pragma unroll
+        for (int sh = 8; sh > 0; sh >>= 1) sd += __shfl_xor(sd, sh, 64);
+    }
     if (!ok) return;
     int64_t t = targets[row];
     t = t < 0 ? 0 : (t >= V ? V - 1 : t);
-    if (sub == 0) loss_rows[row] = mx + logf(s) - x[t];
+    if (sub == 0) loss_rows[row] = OPT ? ce_objective(mx, logf(s), x[t], sd, V, opt) : mx + logf(s) - x[t];
     if (dlogits) {
         TD* d = dlogits + (int64_t)row * ldd;
-        const float inv = 1.f / s;
+        const float inv = OPT ? ce_pscale(mx, logf(s), opt) / s : 1.f / s;
+        const float unif = OPT ? opt.eps / (float)V : 0.f;
         if (gs_dev) grad_scale *= gs_dev[0];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int i = sub + 16 * k;
-            if (i < (int)ldd) d[i] = from_f32<TD>(i < V ? (v[k] * inv - (i == (int)t ? 1.f : 0.f)) * grad_scale : 0.f);
+            if (i < (int)ldd) d[i] = from_f32<TD>(i >= V ? 0.f : OPT ? ce_grad(v[k] * inv, i == (int)t, unif, opt, grad_scale)
+                                                                     : (v[k] * inv - (i == (int)t ? 1.f : 0.f)) * grad_scale);
         }
     }
 }
@@ -89,10 +131,12 @@ struct CeFuse {
 };
 #define CEF_THREADS 1024                  // 64 row groups of 16 lanes: a 64-row share of the batch is in flight at once
 #define CEF_RG (CEF_THREADS / 16)
-template <typename TD>
+template <typename TD, typename... O>
 __global__ __launch_bounds__(CEF_THREADS) void cross_entropy_small_fused_kernel(const float* __restrict__ logits, int64_t ldl, const int64_t* __restrict__ targets,
                                                                         float* __restrict__ loss_rows, TD* __restrict__ dlogits, int64_t ldd,
-                                                                        float grad_scale, int M, int V, CeFuse fz) {
+                                                                        float grad_scale, int M, int V, CeFuse fz, O... o) {
+    constexpr bool OPT = sizeof...(O) != 0;
+    const CeOpt opt = ce_opt(o...);
     __shared__ float red[CEF_RG][128];
     __shared__ float lred[CEF_RG];
     __shared__ unsigned last_flag;
@@ -117,22 +161,32 @@ __global__ __launch_bounds__(CEF_THREADS) void cross_entropy_small_fused_kernel(
         }
 #pragma unroll
         for (int o = 8; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-        float s = 0.f;
+        float s = 0.f, sd = 0.f;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) { v[k] = expf(v[k] - mx); s += v[k]; }
+        for (int k = 0; k < 8; ++k) {
+            if (OPT && sub + 16 * k < V) sd += mx - v[k];            // (the -inf of a padding lane stays out)
+            v[k] = expf(v[k] - mx); s += v[k];
+        }
 #pragma unroll
-        for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        for (int sh = 8; sh > 0; sh >>= 1) s += __shfl_xor(s, sh, 64);
+        if (OPT) {
+#pragma unroll
+            for (int sh = 8; sh > 0; sh >>= 1) sd += __shfl_xor(sd, sh, 64);
+        }
         if (!ok) continue;
         int64_t t = targets[row];
         t = t < 0 ? 0 : (t >= V ? V - 1 : t);
-        const float lr = mx + logf(s) - x[t];
+        const float lr = OPT ? ce_objective(mx, logf(s), x[t], sd, V, opt) : mx + logf(s) - x[t];
         if (sub == 0) { loss_rows[row] = lr; lsum += lr; }
         TD* d = dlogits + (int64_t)row * ldd;
-        const float inv = 1.f / s;
+        const float inv = OPT ? ce_pscale(mx, logf(s), opt) / s : 1.f / s;
+        const float unif = OPT ? opt.eps / (float)V : 0.f;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int i = sub + 16 * k;
-            const float gk = i < V ? (v[k] * inv - (i == (int)t ? 1.f : 0.f)) * grad_scale : 0.f;
+            // (with zeta > 0 a row no longer sums to zero: cacc stays the column sum of exactly what is written)
+            const float gk = i >= V ? 0.f : OPT ? ce_grad(v[k] * inv, i == (int)t, unif, opt, grad_scale)
+                                                : (v[k] * inv - (i == (int)t ? 1.f : 0.f)) * grad_scale;
             cacc[k] += gk;
             if (i < (int)ldd) d[i] = from_f32<TD>(gk);
         }
@@ -179,11 +233,14 @@ __global__ __launch_bounds__(CEF_THREADS) void cross_entropy_small_fused_kernel(
 // TL: logits type.  bf16 logits (the engine at the GPT-2 vocabulary: 0.82 GB instead of 1.65 GB written by lm_head and read here)
 // may be overwritten IN PLACE by their own gradient (dlogits == logits, ldd == ldl): a workgroup holds its whole row in
 // registers before it stores anything.
-template <typename TD, typename TL = float>
+template <typename TD, typename TL = float, typename... O>
 __global__ __launch_bounds__(CE_BLOCK) void cross_entropy_row_kernel(const TL* logits, int64_t ldl, const int64_t* __restrict__ targets,
                                                                       float* __restrict__ loss_rows, TD* dlogits, int64_t ldd,   // (may alias)
-                                                                      float grad_scale, const float* __restrict__ gs_dev, int M, int V) {
+                                                                      float grad_scale, const float* __restrict__ gs_dev, int M, int V, O... o) {
+    constexpr bool OPT = sizeof...(O) != 0;
+    const CeOpt opt = ce_opt(o...);
     __shared__ float red[16];
+    __shared__ float red2[OPT ? 16 : 1];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int row = blockIdx.x;
     const TL* x = logits + (int64_t)row * ldl;
@@ -205,27 +262,37 @@ __global__ __launch_bounds__(CE_BLOCK) void cross_entropy_row_kernel(const TL* l
 #pragma unroll
     for (int k = 1; k < 16; ++k) mx = fmaxf(mx, red[k]);
     __syncthreads();
-    float s = 0.f;
+    float s = 0.f, sd = 0.f;
 #pragma unroll
     for (int k = 0; k < CE_MAXK; ++k) {
+        if (OPT && k * CE_BLOCK + tid < V) sd += mx - v[k];      // (the -inf of a padding lane stays out)
         v[k] = expf(v[k] - mx);                          // exp(-inf) = 0 for the padding
         s += v[k];
     }
     s = wave_sum(s);
+    if (OPT) sd = wave_sum(sd);
     if (lane == 0) red[w] = s;
+    if (OPT && lane == 0) red2[w] = sd;
     __syncthreads();
     s = red[0];
 #pragma unroll
     for (int k = 1; k < 16; ++k) s += red[k];             // fixed order
-    if (tid == 0) loss_rows[row] = mx + logf(s) - xt;
+    if (OPT) {
+        sd = red2[0];
+#pragma unroll
+        for (int k = 1; k < 16; ++k) sd += red2[k];
+    }
+    if (tid == 0) loss_rows[row] = OPT ? ce_objective(mx, logf(s), xt, sd, V, opt) : mx + logf(s) - xt;
     if (dlogits) {
         TD* d = dlogits + (int64_t)row * ldd;
-        const float inv = 1.f / s;
+        const float inv = OPT ? ce_pscale(mx, logf(s), opt) / s : 1.f / s;
+        const float unif = OPT ? opt.eps / (float)V : 0.f;
         if (gs_dev) grad_scale *= gs_dev[0];
 #pragma unroll
         for (int k = 0; k < CE_MAXK; ++k) {
             const int i = k * CE_BLOCK + tid;
-            if (i < (int)ldd) d[i] = from_f32<TD>(i < V ? (v[k] * inv - (i == (int)t ? 1.f : 0.f)) * grad_scale : 0.f);
+            if (i < (int)ldd) d[i] = from_f32<TD>(i >= V ? 0.f : OPT ? ce_grad(v[k] * inv, i == (int)t, unif, opt, grad_scale)
+                                                                     : (v[k] * inv - (i == (int)t ? 1.f : 0.f)) * grad_scale);
         }
     }
 }
@@ -248,11 +315,17 @@ __device__ __forceinline__ float ce_exp_fast(float x, float mxl) { return __buil
 // q8 (nullable; round 3, precision "fp8"): the gradient a second time as OCP e5m2 with the A-PRIORI scale q8_scale = 57344 /
 // grad_scale (|softmax - onehot| <= 1, so |dlogits| <= grad_scale: no amax pass, no history) -- the A operand of lm_head's fp8 dX
 // GEMM and the dY operand of its fp8 dW; columns V .. ldq8 - 1 are written as zeros (the dX contraction runs over the padded width).
+// With label smoothing alone the bound stands (|p_i - eps / V| < 1, |p_t - (1 - eps) - eps / V| < 1); with zeta > 0 it does not (a row
+// sums to 2 zeta lse grad_scale), so the launcher gives q8 to the options only at zeta = 0.
+template <typename... O>
 __global__ __launch_bounds__(CE_BLOCK, 8) void cross_entropy_row_bf16_kernel(const bf16_t* logits, int64_t ldl, const int64_t* __restrict__ targets,
                                                                               float* __restrict__ loss_rows, bf16_t* dlogits, int64_t ldd,
                                                                               float grad_scale, const float* __restrict__ gs_dev, int M, int V,
-                                                                              unsigned char* __restrict__ q8, int64_t ldq8, float q8_scale) {
+                                                                              unsigned char* __restrict__ q8, int64_t ldq8, float q8_scale, O... o) {
+    constexpr bool OPT = sizeof...(O) != 0;
+    const CeOpt opt = ce_opt(o...);
     __shared__ float red[16];
+    __shared__ float red2[OPT ? 16 : 1];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int row = blockIdx.x;
     const bf16_t* x = logits + (int64_t)row * ldl;
@@ -280,29 +353,40 @@ __global__ __launch_bounds__(CE_BLOCK, 8) void cross_entropy_row_bf16_kernel(con
     for (int k = 1; k < 16; ++k) mx = fmaxf(mx, red[k]);
     __syncthreads();
     const float mxl = mx * CE_LOG2E;
-    float s = 0.f;
+    float s = 0.f, sd = 0.f;
 #pragma unroll
     for (int j = 0; j < CE_MAXC; ++j) {
         const int c = tid + CE_BLOCK * j;
         if (c < nchunk && c * 8 < V) {
 #pragma unroll
             for (int e = 0; e < 8; ++e)
-                if (c * 8 + e < V) s += ce_exp_fast((float)q[j][e], mxl);
+                if (c * 8 + e < V) {
+                    s += ce_exp_fast((float)q[j][e], mxl);
+                    if (OPT) sd += mx - (float)q[j][e];
+                }
         }
     }
     s = wave_sum(s);
+    if (OPT) sd = wave_sum(sd);
     if (lane == 0) red[w] = s;
+    if (OPT && lane == 0) red2[w] = sd;
     __syncthreads();
     s = red[0];
 #pragma unroll
     for (int k = 1; k < 16; ++k) s += red[k];             // fixed order
+    if (OPT) {
+        sd = red2[0];
+#pragma unroll
+        for (int k = 1; k < 16; ++k) sd += red2[k];
+    }
     // (mx - xt first: exact for bf16 logits within 2^16 of each other, so a target at the row maximum gives logf(s) itself.  mx + logf(s)
     // rounds at the size of mx -- 2^-24 |mx| = 1.2e-4 at |mx| = 2000 -- on top of the 2^-24 |mx| that the rounding of mx log2(e) already
     // costs through ce_exp_fast: tests/test_gpu_conditioning.py, logit range 2000)
-    if (tid == 0) loss_rows[row] = (mx - xt) + logf(s);
+    if (tid == 0) loss_rows[row] = OPT ? ce_objective(mx, logf(s), xt, sd, V, opt) : (mx - xt) + logf(s);
     if (dlogits) {
         bf16_t* d = dlogits + (int64_t)row * ldd;
-        const float inv = 1.f / s;
+        const float inv = OPT ? ce_pscale(mx, logf(s), opt) / s : 1.f / s;
+        const float unif = OPT ? opt.eps / (float)V : 0.f;
         if (gs_dev) grad_scale *= gs_dev[0];
         const int dchunk = (int)(ldd / 8);
 #pragma unroll
@@ -314,7 +398,8 @@ __global__ __launch_bounds__(CE_BLOCK, 8) void cross_entropy_row_bf16_kernel(con
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const int i = c * 8 + e;
-                    gv[e] = i < V ? (ce_exp_fast((float)q[j][e], mxl) * inv - (i == (int)t ? 1.f : 0.f)) * grad_scale : 0.f;
+                    gv[e] = i >= V ? 0.f : OPT ? ce_grad(ce_exp_fast((float)q[j][e], mxl) * inv, i == (int)t, unif, opt, grad_scale)
+                                               : (ce_exp_fast((float)q[j][e], mxl) * inv - (i == (int)t ? 1.f : 0.f)) * grad_scale;
                     o[e] = (bf16_t)gv[e];
                 }
                 *(bf16x8*)(d + c * 8) = o;
@@ -332,28 +417,60 @@ __global__ __launch_bounds__(CE_BLOCK, 8) void cross_entropy_row_bf16_kernel(con
     }
 }
 
+// O... opt: nothing (the three old entry points: the instantiations they always launched) or one CeOpt
+template <typename... O>
 static int ce_launch(const void* logits_v, int logits_dtype, int64_t ldl, const int64_t* targets, float* loss_rows,
                      void* dlogits, int64_t ldd, int dtype, float grad_scale, const float* grad_scale_dev, int M, int V,
-                     unsigned char* q8, int64_t ldq8, float q8_scale, void* stream);
+                     unsigned char* q8, int64_t ldq8, float q8_scale, void* stream, O... opt);
+
+// eps in [0, 1), zeta >= 0, both finite (a NaN fails every comparison)
+static bool ce_opt_ok(float eps, float zeta) { return eps >= 0.f && eps < 1.f && zeta >= 0.f && zeta <= FLT_MAX; }
 
 extern "C" int dg_cross_entropy(const void* logits_v, int logits_dtype, int64_t ldl, const int64_t* targets, float* loss_rows,
                                 void* dlogits, int64_t ldd, int dtype, float grad_scale, const float* grad_scale_dev, int M, int V, void* stream) {
-    return ce_launch(logits_v, logits_dtype, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, grad_scale_dev, M, V, nullptr, 0, 0.f, stream);
+    return ce_launch(logits_v, logits_dtype, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, grad_scale_dev, M, V, nullptr, 0, 0.f,
+                            stream);
+}
+
+extern "C" int dg_cross_entropy_smooth(const void* logits_v, int logits_dtype, int64_t ldl, const int64_t* targets, float* loss_rows,
+                                       void* dlogits, int64_t ldd, int dtype, float grad_scale, const float* grad_scale_dev, int M, int V,
+                                       float label_smoothing, float z_loss, void* stream) {
+    if (!ce_opt_ok(label_smoothing, z_loss)) return DG_ERR_ARG;
+    if (label_smoothing == 0.f && z_loss == 0.f)
+        return dg_cross_entropy(logits_v, logits_dtype, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, grad_scale_dev, M, V, stream);
+    return ce_launch(logits_v, logits_dtype, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, grad_scale_dev, M, V, nullptr, 0, 0.f,
+                           stream, CeOpt{label_smoothing, z_loss});
 }
 
 // bf16 logits (the whole-row kernel, 16-byte accesses) with the gradient ALSO as e5m2: dlogits_fp8 [M, ld8] = e5m2(dlogits * 57344 /
 // grad_scale), dequantisation factor grad_scale / 57344 (a constant the caller knows); ld8 % 16 == 0, ld8 >= V, columns beyond V zero
-extern "C" int dg_cross_entropy_fp8(const void* logits, int64_t ldl, const int64_t* targets, float* loss_rows, void* dlogits, int64_t ldd,
-                                    float grad_scale, int M, int V, void* dlogits_fp8, int64_t ld8, void* stream) {
+static int ce_fp8_check(const void* logits, int64_t ldl, const void* dlogits, int64_t ldd, float grad_scale, int V, const void* dlogits_fp8, int64_t ld8) {
     if (!dlogits || !dlogits_fp8 || ld8 < V || ld8 % 16 || ld8 > ldd || !dg_aligned16(dlogits_fp8) || !(grad_scale > 0.f)) return DG_ERR_ARG;
     if (ldl % 8 || ldd % 8 || !dg_aligned16(logits) || !dg_aligned16(dlogits) || (int64_t)((V + 7) / 8) * 8 > ldl) return DG_ERR_ALIGN;
-    return ce_launch(logits, DG_BF16, ldl, targets, loss_rows, dlogits, ldd, DG_BF16, grad_scale, nullptr, M, V, (unsigned char*)dlogits_fp8, ld8,
-                     57344.f / grad_scale, stream);
+    return DG_OK;
 }
 
+extern "C" int dg_cross_entropy_fp8(const void* logits, int64_t ldl, const int64_t* targets, float* loss_rows, void* dlogits, int64_t ldd,
+                                    float grad_scale, int M, int V, void* dlogits_fp8, int64_t ld8, void* stream) {
+    if (const int e = ce_fp8_check(logits, ldl, dlogits, ldd, grad_scale, V, dlogits_fp8, ld8)) return e;
+    return ce_launch(logits, DG_BF16, ldl, targets, loss_rows, dlogits, ldd, DG_BF16, grad_scale, nullptr, M, V, (unsigned char*)dlogits_fp8, ld8,
+                            57344.f / grad_scale, stream);
+}
+
+// label smoothing only: |g_i| <= grad_scale, on which the a-priori scale rests, does not survive a z-loss
+extern "C" int dg_cross_entropy_fp8_smooth(const void* logits, int64_t ldl, const int64_t* targets, float* loss_rows, void* dlogits, int64_t ldd,
+                                           float grad_scale, int M, int V, void* dlogits_fp8, int64_t ld8, float label_smoothing, void* stream) {
+    if (!ce_opt_ok(label_smoothing, 0.f)) return DG_ERR_ARG;
+    if (label_smoothing == 0.f) return dg_cross_entropy_fp8(logits, ldl, targets, loss_rows, dlogits, ldd, grad_scale, M, V, dlogits_fp8, ld8, stream);
+    if (const int e = ce_fp8_check(logits, ldl, dlogits, ldd, grad_scale, V, dlogits_fp8, ld8)) return e;
+    return ce_launch(logits, DG_BF16, ldl, targets, loss_rows, dlogits, ldd, DG_BF16, grad_scale, nullptr, M, V, (unsigned char*)dlogits_fp8, ld8,
+                           57344.f / grad_scale, stream, CeOpt{label_smoothing, 0.f});
+}
+
+template <typename... O>
 static int ce_launch(const void* logits_v, int logits_dtype, int64_t ldl, const int64_t* targets, float* loss_rows,
                      void* dlogits, int64_t ldd, int dtype, float grad_scale, const float* grad_scale_dev, int M, int V,
-                     unsigned char* q8, int64_t ldq8, float q8_scale, void* stream) {
+                     unsigned char* q8, int64_t ldq8, float q8_scale, void* stream, O... opt) {
     if (!logits_v || !targets || !loss_rows || M <= 0 || V <= 0 || ldl < V) return DG_ERR_ARG;
     if (dlogits && ldd < V) return DG_ERR_ARG;
     if (logits_dtype != DG_F32 && logits_dtype != DG_BF16) return DG_ERR_DTYPE;
@@ -367,11 +484,11 @@ static int ce_launch(const void* logits_v, int logits_dtype, int64_t ldl, const 
                          (int64_t)((V + 7) / 8) * 8 <= ldl && w <= (int64_t)CE_BLOCK * CE_MAXC * 8;
         if (q8 && !vec) return DG_ERR_ARG;
         if (vec)
-            hipLaunchKernelGGL(cross_entropy_row_bf16_kernel, dim3(M), dim3(CE_BLOCK), 0, (hipStream_t)stream, (const bf16_t*)logits_v, ldl,
-                               targets, loss_rows, (bf16_t*)dlogits, ldd, grad_scale, grad_scale_dev, M, V, q8, ldq8, q8_scale);
+            hipLaunchKernelGGL((cross_entropy_row_bf16_kernel<O...>), dim3(M), dim3(CE_BLOCK), 0, (hipStream_t)stream, (const bf16_t*)logits_v, ldl,
+                               targets, loss_rows, (bf16_t*)dlogits, ldd, grad_scale, grad_scale_dev, M, V, q8, ldq8, q8_scale, opt...);
         else
-            hipLaunchKernelGGL((cross_entropy_row_kernel<bf16_t, bf16_t>), dim3(M), dim3(CE_BLOCK), 0, (hipStream_t)stream, (const bf16_t*)logits_v, ldl,
-                               targets, loss_rows, (bf16_t*)dlogits, ldd, grad_scale, grad_scale_dev, M, V);
+            hipLaunchKernelGGL((cross_entropy_row_kernel<bf16_t, bf16_t, O...>), dim3(M), dim3(CE_BLOCK), 0, (hipStream_t)stream, (const bf16_t*)logits_v, ldl,
+                               targets, loss_rows, (bf16_t*)dlogits, ldd, grad_scale, grad_scale_dev, M, V, opt...);
         DG_LAUNCH_CHECK();
         return DG_OK;
     }
@@ -382,35 +499,36 @@ static int ce_launch(const void* logits_v, int logits_dtype, int64_t ldl, const 
     const int64_t width = dlogits && ldd > V ? ldd : V;
     if (width <= 128) {
         if (dtype == DG_BF16)
-            hipLaunchKernelGGL(cross_entropy_small_kernel<bf16_t>, dim3((M + 15) / 16), block, 0, s, logits, ldl, targets, loss_rows, (bf16_t*)dlogits, ldd, grad_scale, grad_scale_dev, M, V);
+            hipLaunchKernelGGL((cross_entropy_small_kernel<bf16_t, O...>), dim3((M + 15) / 16), block, 0, s, logits, ldl, targets, loss_rows, (bf16_t*)dlogits, ldd, grad_scale, grad_scale_dev, M, V, opt...);
         else if (dtype == DG_F32)
-            hipLaunchKernelGGL(cross_entropy_small_kernel<float>, dim3((M + 15) / 16), block, 0, s, logits, ldl, targets, loss_rows, (float*)dlogits, ldd, grad_scale, grad_scale_dev, M, V);
+            hipLaunchKernelGGL((cross_entropy_small_kernel<float, O...>), dim3((M + 15) / 16), block, 0, s, logits, ldl, targets, loss_rows, (float*)dlogits, ldd, grad_scale, grad_scale_dev, M, V, opt...);
         else return DG_ERR_DTYPE;
         DG_LAUNCH_CHECK();
         return DG_OK;
     }
     if (V > 4096 && width <= (int64_t)CE_BLOCK * CE_MAXK) {
         if (dtype == DG_BF16)
-            hipLaunchKernelGGL(cross_entropy_row_kernel<bf16_t>, dim3(M), dim3(CE_BLOCK), 0, s, logits, ldl, targets, loss_rows, (bf16_t*)dlogits, ldd, grad_scale, grad_scale_dev, M, V);
+            hipLaunchKernelGGL((cross_entropy_row_kernel<bf16_t, float, O...>), dim3(M), dim3(CE_BLOCK), 0, s, logits, ldl, targets, loss_rows, (bf16_t*)dlogits, ldd, grad_scale, grad_scale_dev, M, V, opt...);
         else if (dtype == DG_F32)
-            hipLaunchKernelGGL(cross_entropy_row_kernel<float>, dim3(M), dim3(CE_BLOCK), 0, s, logits, ldl, targets, loss_rows, (float*)dlogits, ldd, grad_scale, grad_scale_dev, M, V);
+            hipLaunchKernelGGL((cross_entropy_row_kernel<float, float, O...>), dim3(M), dim3(CE_BLOCK), 0, s, logits, ldl, targets, loss_rows, (float*)dlogits, ldd, grad_scale, grad_scale_dev, M, V, opt...);
         else return DG_ERR_DTYPE;
         DG_LAUNCH_CHECK();
         return DG_OK;
     }
     if (dtype == DG_BF16)
-        hipLaunchKernelGGL(cross_entropy_kernel<bf16_t>, grid, block, 0, s, logits, ldl, targets, loss_rows, (bf16_t*)dlogits, ldd, grad_scale, grad_scale_dev, M, V);
+        hipLaunchKernelGGL((cross_entropy_kernel<bf16_t, float, O...>), grid, block, 0, s, logits, ldl, targets, loss_rows, (bf16_t*)dlogits, ldd, grad_scale, grad_scale_dev, M, V, opt...);
     else if (dtype == DG_F32)
-        hipLaunchKernelGGL(cross_entropy_kernel<float>, grid, block, 0, s, logits, ldl, targets, loss_rows, (float*)dlogits, ldd, grad_scale, grad_scale_dev, M, V);
+        hipLaunchKernelGGL((cross_entropy_kernel<float, float, O...>), grid, block, 0, s, logits, ldl, targets, loss_rows, (float*)dlogits, ldd, grad_scale, grad_scale_dev, M, V, opt...);
     else return DG_ERR_DTYPE;
     DG_LAUNCH_CHECK();
     return DG_OK;
 }
 
 
-extern "C" int dg_cross_entropy_fused(const float* logits, int64_t ldl, const int64_t* targets, float* loss_rows, void* dlogits, int64_t ldd,
-                                      int dtype, float grad_scale, int M, int V, float* colsum_part, int64_t part_stride, int n_partials,
-                                      float* loss_part, uint32_t* loss_counter, float* loss_out, float loss_scale, void* stream) {
+template <typename... O>
+static int ce_fused_launch(const float* logits, int64_t ldl, const int64_t* targets, float* loss_rows, void* dlogits, int64_t ldd,
+                           int dtype, float grad_scale, int M, int V, float* colsum_part, int64_t part_stride, int n_partials,
+                           float* loss_part, uint32_t* loss_counter, float* loss_out, float loss_scale, void* stream, O... opt) {
     if (!logits || !targets || !loss_rows || !dlogits || M <= 0 || V <= 0 || ldl < V || ldd < V) return DG_ERR_ARG;
     if (ldd > 128 || n_partials <= 0 || n_partials > 2048) return DG_ERR_ARG;         // rows in registers; shares summed out of 8 KB of LDS
     if (colsum_part && part_stride < V) return DG_ERR_ARG;
@@ -419,10 +537,29 @@ extern "C" int dg_cross_entropy_fused(const float* logits, int64_t ldl, const in
     const CeFuse fz{colsum_part, part_stride, rows_per, loss_part, (unsigned*)loss_counter, loss_out, loss_scale};
     hipStream_t s = (hipStream_t)stream;
     if (dtype == DG_BF16)
-        hipLaunchKernelGGL(cross_entropy_small_fused_kernel<bf16_t>, dim3(n_partials), dim3(CEF_THREADS), 0, s, logits, ldl, targets, loss_rows, (bf16_t*)dlogits, ldd, grad_scale, M, V, fz);
+        hipLaunchKernelGGL((cross_entropy_small_fused_kernel<bf16_t, O...>), dim3(n_partials), dim3(CEF_THREADS), 0, s, logits, ldl, targets, loss_rows, (bf16_t*)dlogits, ldd, grad_scale, M, V, fz, opt...);
     else if (dtype == DG_F32)
-        hipLaunchKernelGGL(cross_entropy_small_fused_kernel<float>, dim3(n_partials), dim3(CEF_THREADS), 0, s, logits, ldl, targets, loss_rows, (float*)dlogits, ldd, grad_scale, M, V, fz);
+        hipLaunchKernelGGL((cross_entropy_small_fused_kernel<float, O...>), dim3(n_partials), dim3(CEF_THREADS), 0, s, logits, ldl, targets, loss_rows, (float*)dlogits, ldd, grad_scale, M, V, fz, opt...);
     else return DG_ERR_DTYPE;
     DG_LAUNCH_CHECK();
     return DG_OK;
+}
+
+extern "C" int dg_cross_entropy_fused(const float* logits, int64_t ldl, const int64_t* targets, float* loss_rows, void* dlogits, int64_t ldd,
+                                      int dtype, float grad_scale, int M, int V, float* colsum_part, int64_t part_stride, int n_partials,
+                                      float* loss_part, uint32_t* loss_counter, float* loss_out, float loss_scale, void* stream) {
+    return ce_fused_launch(logits, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, M, V, colsum_part, part_stride, n_partials,
+                                  loss_part, loss_counter, loss_out, loss_scale, stream);
+}
+
+extern "C" int dg_cross_entropy_fused_smooth(const float* logits, int64_t ldl, const int64_t* targets, float* loss_rows, void* dlogits, int64_t ldd,
+                                             int dtype, float grad_scale, int M, int V, float* colsum_part, int64_t part_stride, int n_partials,
+                                             float* loss_part, uint32_t* loss_counter, float* loss_out, float loss_scale,
+                                             float label_smoothing, float z_loss, void* stream) {
+    if (!ce_opt_ok(label_smoothing, z_loss)) return DG_ERR_ARG;
+    if (label_smoothing == 0.f && z_loss == 0.f)
+        return dg_cross_entropy_fused(logits, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, M, V, colsum_part, part_stride, n_partials,
+                                      loss_part, loss_counter, loss_out, loss_scale, stream);
+    return ce_fused_launch(logits, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, M, V, colsum_part, part_stride, n_partials,
+                                 loss_part, loss_counter, loss_out, loss_scale, stream, CeOpt{label_smoothing, z_loss});
 }

@@ -181,7 +181,7 @@ class TrainEngine:
                  seed: int = 42, rank: int = 0, world_size: int = 1, process_group=None, use_graph: bool = True,
                  dp_buckets: Optional[int] = None, logits: str = "auto", grad_stream: str = "auto", fp8_dw: Optional[bool] = None,
                  max_grad_norm: Optional[float] = None, accum_steps: int = 1, lr_schedule=None, schedule_steps: Optional[int] = None,
-                 no_decay=()):
+                 no_decay=(), label_smoothing: float = 0.0, z_loss: float = 0.0):
         if not isinstance(model, TransformerLM):
             raise TypeError("TrainEngine drives TransformerLM (the other five models train through the autograd path)")
         p0 = next(model.parameters())
@@ -220,6 +220,11 @@ class TrainEngine:
         if lr_schedule is None and schedule_steps is not None:
             raise ValueError("schedule_steps goes with lr_schedule")
         self.no_decay = CK.check_no_decay(no_decay)
+        # the training objective's options (label smoothing, z-loss: inside the loss-head kernels): what every training program
+        # adds to its loss-head call -- nothing for a default engine, whose calls are the ones they always were.  eval_loss /
+        # eval_losses stay the plain cross entropy.
+        self.label_smoothing, self.z_loss = ops.check_loss_options(label_smoothing, z_loss)
+        self._loss_kw = {k: v for k, v in (("label_smoothing", self.label_smoothing), ("z_loss", self.z_loss)) if v != 0.0}
         if self.accum > 1 and dp_buckets is not None and int(dp_buckets) > 1:
             raise ValueError("accum_steps > 1 uses one gradient exchange per optimizer step (it is amortised over the micro-steps "
                              "already): dp_buckets > 1 cannot be combined with it")
@@ -281,6 +286,11 @@ class TrainEngine:
         if self.dp_buckets > 1:
             self.chain_bwd = False
         self._alloc_and_adopt()
+        if self.fp8_head and self.z_loss > 0.0:
+            # the loss kernel's e5m2 gradient copy is scaled a priori by 57344 M: |dlogits| <= 1 / M, which label smoothing
+            # keeps and a z-loss does not (a gradient row sums to 2 z_loss lse / M)
+            raise ValueError("z_loss > 0 cannot be combined with the fp8 loss head (precision 'fp8' at a large vocabulary): its "
+                             "e5m2 gradient scale rests on |dlogits| <= 1 / M; label_smoothing can")
         self.hyper = torch.tensor([lr, betas[0], betas[1], eps, weight_decay], dtype=torch.float32, device=self.dev)
         self.hyper_host = [float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay)]      # what state_dict() reports
         # lr_schedule: AdamW finds its rate in a table staged here once, by its own step word (dg_adamw_step_sched): hyper[0] is
@@ -699,6 +709,7 @@ class TrainEngine:
         return x, saved
 
     def _head(self, run: S.Run, h: Tensor, y_idx: Optional[Tensor], want_grad: bool, saved, M: int):
+        okw = self._loss_kw if want_grad else {}        # the objective's options: training programs only, evaluation stays plain
         if self.bf16_logits and y_idx is not None and not self.keep_logits:
             # large vocabulary: lm_head writes bf16 logits into the buffer that becomes dlogits -- the cross-entropy kernel holds
             # a whole row in registers and overwrites it in place with its gradient (1.65 GB less written and 0.82 GB less read
@@ -715,13 +726,13 @@ class TrainEngine:
                 logits = ops.gemm_nt(xq, wq, self.act, scale_a=xs, scale_b=ws, bias=self.param_view("lm.b"), out=buf[:, :self.V])
                 if want_grad and M == self.M:
                     q8 = torch.empty((M, buf.shape[1]), dtype=S.E5M2, device=self.dev)
-                    rows = ops.cross_entropy_fp8(logits, y_idx.view(M), self.V, buf, 1.0 / M, q8)
+                    rows = ops.cross_entropy_fp8(logits, y_idx.view(M), self.V, buf, 1.0 / M, q8, **okw)      # (z_loss: refused at construction)
                     buf.dg_q8 = (q8, self.dl_scale)
                 else:
-                    rows = ops.cross_entropy(logits, y_idx.view(M), self.V, dlogits=buf if want_grad else None, grad_scale=1.0 / M)
+                    rows = ops.cross_entropy(logits, y_idx.view(M), self.V, dlogits=buf if want_grad else None, grad_scale=1.0 / M, **okw)
                 return None, rows, (saved, h, buf)
             logits, (xa,) = S.linear_fwd(run, h, self.param_view("lm.w"), self.param_view("lm.b"), out=buf[:, :self.V])
-            rows = ops.cross_entropy(logits, y_idx.view(M), self.V, dlogits=buf if want_grad else None, grad_scale=1.0 / M)
+            rows = ops.cross_entropy(logits, y_idx.view(M), self.V, dlogits=buf if want_grad else None, grad_scale=1.0 / M, **okw)
             return None, rows, (saved, xa, buf)
         logits, (xa,) = S.linear_fwd(run, h, self.param_view("lm.w"), self.param_view("lm.b"), pad_rows=True)
         if y_idx is None:
@@ -733,9 +744,9 @@ class TrainEngine:
                 # small vocabulary: the loss head in one launch -- gradient rows, the lm_head bias partials and the mean loss
                 part, stride, n = FlatSink(self).vector("lm.b", self.V)
                 rows = ops.cross_entropy_fused(logits, y_idx.view(M), self.V, dlogits, 1.0 / M, part, stride, n, self.loss_scratch,
-                                               self.loss, 1.0 / M)
+                                               self.loss, 1.0 / M, **okw)
                 return logits, rows, (saved, xa, dlogits, True)
-        rows = ops.cross_entropy(logits, y_idx.view(M), self.V, dlogits=dlogits, grad_scale=1.0 / M)
+        rows = ops.cross_entropy(logits, y_idx.view(M), self.V, dlogits=dlogits, grad_scale=1.0 / M, **okw)
         return logits, rows, (saved, xa, dlogits)
 
     def _backward_begin(self, run: S.Run, x_idx: Tensor, ctx) -> dict:
@@ -1278,10 +1289,23 @@ class TrainEngine:
         return out
 
     # -------------------------------------------------------------------------------- training state
+    _LOSS_FIELDS = ("label_smoothing", "z_loss")
+
     def _meta(self) -> dict:
-        return {"precision": str(self.model.precision), "vocab_size": int(self.V), "embedding_dim": int(self.C), "num_layers": int(self.L),
+        meta = {"precision": str(self.model.precision), "vocab_size": int(self.V), "embedding_dim": int(self.C), "num_layers": int(self.L),
                 "num_heads": int(self.NH), "model_context_length": int(self.model.context_length), "batch_size": self.B,
                 "context_length": self.T, "accum_steps": self.accum, "world_size": int(self.world), "dropout": self.p_drop}
+        meta.update(self._loss_kw)      # only where set: a default engine writes and accepts exactly the files it always did
+        return meta
+
+    def _check_meta(self, saved: dict) -> None:
+        """CK.check_compat on the fields every engine has; the loss options in both directions (a field absent on either side reads
+        as 0.0: a smoothed state is refused by a default engine as much as the reverse)"""
+        CK.check_compat(saved, {k: v for k, v in self._meta().items() if k not in self._LOSS_FIELDS})
+        for field in self._LOSS_FIELDS:
+            theirs, own = saved.get(field, 0.0), self._loss_kw.get(field, 0.0)
+            if isinstance(theirs, bool) or not isinstance(theirs, (int, float)) or float(theirs) != own:
+                raise ValueError(f"training state: meta.{field} differs: saved {theirs!r}, this run has {own!r}")
 
     def _param_names(self) -> List[str]:
         return [n for n, _ in self.model.named_parameters()]
@@ -1398,7 +1422,7 @@ class TrainEngine:
         for k in ("model", "optimizer", "engine", "meta"):
             if k not in sd:
                 raise ValueError(f"training state: missing key {k!r}")
-        CK.check_compat(sd["meta"], self._meta())
+        self._check_meta(sd["meta"])
         e = sd["engine"]
         for k in self._ENGINE_KEYS:
             if k not in e:

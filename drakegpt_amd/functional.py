@@ -127,13 +127,15 @@ class LinearFn(torch.autograd.Function):
 
 
 class CrossEntropyFn(torch.autograd.Function):
-    """mean cross entropy over the rows of logits [M,V] (ref: src/model.py:606-607)"""
+    """mean cross entropy over the rows of logits [M,V] (ref: src/model.py:606-607); with label_smoothing / z_loss the mean of
+    the row objectives of ops.cross_entropy"""
 
     @staticmethod
-    def forward(ctx, logits: Tensor, targets: Tensor):
+    def forward(ctx, logits: Tensor, targets: Tensor, label_smoothing: float = 0.0, z_loss: float = 0.0):
         M, V = logits.shape
         logits = logits.contiguous()
-        rows = ops.cross_entropy(logits, targets, V)
+        ctx.opts = dict(zip(("label_smoothing", "z_loss"), ops.check_loss_options(label_smoothing, z_loss)))
+        rows = ops.cross_entropy(logits, targets, V, **ctx.opts)
         loss = ops.reduce_sum(rows, 1.0 / M)
         ctx.save_for_backward(logits, targets)
         return loss
@@ -145,8 +147,8 @@ class CrossEntropyFn(torch.autograd.Function):
         dlogits = torch.empty_like(logits)
         rows = torch.empty((M,), dtype=torch.float32, device=logits.device)
         ops.cross_entropy(logits, targets, V, dlogits=dlogits, grad_scale=1.0 / M,
-                          grad_scale_dev=dloss.contiguous().to(torch.float32), loss_rows=rows)
-        return dlogits, None
+                          grad_scale_dev=dloss.contiguous().to(torch.float32), loss_rows=rows, **ctx.opts)
+        return dlogits, None, None, None
 
 
 def embed(idx, tok, pos):
@@ -165,5 +167,5 @@ def linear(x, w, b, act):
     return LinearFn.apply(x, w, b, act)
 
 
-def cross_entropy(logits, targets):
-    return CrossEntropyFn.apply(logits, targets)
+def cross_entropy(logits, targets, label_smoothing=0.0, z_loss=0.0):
+    return CrossEntropyFn.apply(logits, targets, label_smoothing, z_loss)

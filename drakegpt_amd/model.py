@@ -130,6 +130,21 @@ class _LM(HipModule):
         if targets is not None:
             ops.check_ids(targets, V if not hasattr(self, "lm_head") else self.lm_head.weight.shape[0], "targets")
 
+    # the training objective's options: plain attributes, not part of the state_dict; forward applies them in train() mode only
+    label_smoothing = 0.0
+    z_loss = 0.0
+
+    def set_loss_options(self, label_smoothing=0.0, z_loss=0.0):
+        """label smoothing (F.cross_entropy's label_smoothing) and the z-loss coefficient (z_loss * logsumexp^2 per row) of
+        the loss forward(idx, targets) returns in train() mode; in eval() it stays the plain cross entropy, the reference's metric"""
+        self.label_smoothing, self.z_loss = ops.check_loss_options(label_smoothing, z_loss)
+        return self
+
+    def _loss(self, logits, targets):
+        if self.training:
+            return HF.cross_entropy(logits, targets, self.label_smoothing, self.z_loss)
+        return HF.cross_entropy(logits, targets)
+
     def forward(self, idx, targets=None):
         if idx.dim() != 2:
             raise ValueError("idx must be (B, T)")
@@ -140,7 +155,7 @@ class _LM(HipModule):
             return logits, None
         B, T, V = logits.shape
         logits = logits.view(B * T, V)
-        loss = HF.cross_entropy(logits, targets.reshape(B * T))
+        loss = self._loss(logits, targets.reshape(B * T))
         return logits, loss
 
     @torch.no_grad()
@@ -236,7 +251,7 @@ class BigramLM(_LM):
             return logits, None
         B, T, V = logits.shape
         logits = logits.view(B * T, V)
-        return logits, HF.cross_entropy(logits, targets.reshape(B * T))
+        return logits, self._loss(logits, targets.reshape(B * T))
 
 
 class SingleHeadAttentionLM(_LM):

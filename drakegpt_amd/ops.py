@@ -8,6 +8,7 @@ validated on the host before a launch -- a kernel that faults can reset the GPU.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional
 
 import torch
@@ -674,8 +675,31 @@ def attn_decode(cache: Tensor, t: int, NH: int, H: int, scale: float) -> Tensor:
     return out
 
 
+def check_loss_options(label_smoothing=0.0, z_loss=0.0):
+    """the checks of the two loss options, plain Python, raised before anything touches a device: label_smoothing in [0, 1)
+    (F.cross_entropy's label_smoothing), z_loss >= 0 and finite (the coefficient of logsumexp^2).  Returns both as floats."""
+    out = []
+    for name, x in (("label_smoothing", label_smoothing), ("z_loss", z_loss)):
+        if isinstance(x, bool):
+            raise ValueError(f"{name} must be a number, got {x!r}")
+        try:
+            out.append(float(x))
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be a number, got {x!r}") from None
+    eps, zeta = out
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing!r}")
+    if not (math.isfinite(zeta) and zeta >= 0.0):
+        raise ValueError(f"z_loss must be finite and >= 0, got {z_loss!r}")
+    return eps, zeta
+
+
 def cross_entropy(logits: Tensor, targets: Tensor, V: int, dlogits: Optional[Tensor] = None, grad_scale: float = 1.0,
-                  grad_scale_dev: Optional[Tensor] = None, loss_rows: Optional[Tensor] = None) -> Tensor:
+                  grad_scale_dev: Optional[Tensor] = None, loss_rows: Optional[Tensor] = None, *,
+                  label_smoothing: float = 0.0, z_loss: float = 0.0) -> Tensor:
+    """per-row objective (and, with dlogits, its gradient times grad_scale): the plain NLL, or with label_smoothing / z_loss
+    lse - (1 - eps) x_t - (eps / V) sum x + z_loss lse^2 (dg_cross_entropy_smooth)"""
+    eps, zeta = check_loss_options(label_smoothing, z_loss)
     _chk(logits, "logits", contiguous=False)              # fp32, or bf16 (large vocabularies: dlogits may then BE logits)
     if logits.dtype not in (torch.float32, torch.bfloat16):
         raise TypeError("cross_entropy: logits must be float32 or bfloat16")
@@ -687,22 +711,33 @@ def cross_entropy(logits: Tensor, targets: Tensor, V: int, dlogits: Optional[Ten
     if dlogits is not None:
         _chk(dlogits, "dlogits", contiguous=False)
         ldd, dcode = _ld(dlogits), dt_code(dlogits.dtype)
-    check(lib.dg_cross_entropy(_p(logits), dt_code(logits.dtype), _ld(logits), _p(targets), _p(loss_rows), _p(dlogits), ldd, dcode, float(grad_scale),
-                               _p(grad_scale_dev), M, V, _stream()), "dg_cross_entropy")
+    if eps == 0.0 and zeta == 0.0:
+        check(lib.dg_cross_entropy(_p(logits), dt_code(logits.dtype), _ld(logits), _p(targets), _p(loss_rows), _p(dlogits), ldd, dcode, float(grad_scale),
+                                   _p(grad_scale_dev), M, V, _stream()), "dg_cross_entropy")
+    else:
+        check(lib.dg_cross_entropy_smooth(_p(logits), dt_code(logits.dtype), _ld(logits), _p(targets), _p(loss_rows), _p(dlogits), ldd, dcode,
+                                          float(grad_scale), _p(grad_scale_dev), M, V, eps, zeta, _stream()), "dg_cross_entropy_smooth")
     return loss_rows
 
 
-def cross_entropy_fp8(logits: Tensor, targets: Tensor, V: int, dlogits: Tensor, grad_scale: float, dlogits_fp8: Tensor) -> Tensor:
+def cross_entropy_fp8(logits: Tensor, targets: Tensor, V: int, dlogits: Tensor, grad_scale: float, dlogits_fp8: Tensor, *,
+                      label_smoothing: float = 0.0) -> Tensor:
     """cross_entropy on bf16 logits (gradient in bf16, possibly in place) that also writes the gradient as e5m2 with the a-priori
-    scale 57344 / grad_scale into dlogits_fp8 [M, ld8 >= V] (pad columns zeroed); dequantisation factor: grad_scale / 57344"""
+    scale 57344 / grad_scale into dlogits_fp8 [M, ld8 >= V] (pad columns zeroed); dequantisation factor: grad_scale / 57344.
+    label_smoothing keeps |dlogits| <= grad_scale, on which that scale rests; a z-loss does not, so there is no z_loss here."""
+    eps, _ = check_loss_options(label_smoothing, 0.0)
     _chk(logits, "logits", torch.bfloat16, contiguous=False)
     _chk(targets, "targets", torch.int64)
     _chk(dlogits, "dlogits", torch.bfloat16, contiguous=False)
     _chk(dlogits_fp8, "dlogits_fp8", torch.float8_e5m2, contiguous=False)
     M = logits.shape[0]
     loss_rows = torch.empty((M,), dtype=torch.float32, device=logits.device)
-    check(lib.dg_cross_entropy_fp8(_p(logits), _ld(logits), _p(targets), _p(loss_rows), _p(dlogits), _ld(dlogits), float(grad_scale), M, V,
-                                   _p(dlogits_fp8), _ld(dlogits_fp8), _stream()), "dg_cross_entropy_fp8")
+    if eps == 0.0:
+        check(lib.dg_cross_entropy_fp8(_p(logits), _ld(logits), _p(targets), _p(loss_rows), _p(dlogits), _ld(dlogits), float(grad_scale), M, V,
+                                       _p(dlogits_fp8), _ld(dlogits_fp8), _stream()), "dg_cross_entropy_fp8")
+    else:
+        check(lib.dg_cross_entropy_fp8_smooth(_p(logits), _ld(logits), _p(targets), _p(loss_rows), _p(dlogits), _ld(dlogits), float(grad_scale), M, V,
+                                              _p(dlogits_fp8), _ld(dlogits_fp8), eps, _stream()), "dg_cross_entropy_fp8_smooth")
     return loss_rows
 
 
@@ -712,10 +747,12 @@ def cross_entropy_fused_supported(logits: Tensor, dlogits: Tensor, n_partials: i
 
 def cross_entropy_fused(logits: Tensor, targets: Tensor, V: int, dlogits: Tensor, grad_scale: float, colsum_part: Optional[Tensor],
                         part_stride: int, n_partials: int, loss_scratch: Optional[Tensor], loss_out: Optional[Tensor], loss_scale: float,
-                        loss_rows: Optional[Tensor] = None) -> Tensor:
+                        loss_rows: Optional[Tensor] = None, *, label_smoothing: float = 0.0, z_loss: float = 0.0) -> Tensor:
     """cross_entropy + column-sum partials of dlogits (n_partials rows of part_stride floats) + loss_out = loss_scale * sum(rows)
     in one launch (V <= 128).  loss_scratch: fp32 [n_partials + 1], its LAST word the arrival counter (zero before the first
-    launch; the kernel leaves it at zero).  Returns the per-row losses."""
+    launch; the kernel leaves it at zero).  Returns the per-row losses (with label_smoothing / z_loss: the per-row objectives,
+    and partials that no longer add up to zero once z_loss > 0)."""
+    eps, zeta = check_loss_options(label_smoothing, z_loss)
     _chk(logits, "logits", torch.float32, contiguous=False)
     _chk(targets, "targets", torch.int64)
     _chk(dlogits, "dlogits", contiguous=False)
@@ -731,10 +768,13 @@ def cross_entropy_fused(logits: Tensor, targets: Tensor, V: int, dlogits: Tensor
         if loss_scratch.numel() < n_partials + 1:
             raise ValueError("cross_entropy_fused: loss_scratch needs n_partials + 1 words")
         cnt = loss_scratch.data_ptr() + 4 * n_partials
-    check(lib.dg_cross_entropy_fused(_p(logits), _ld(logits), _p(targets), _p(loss_rows), _p(dlogits), _ld(dlogits), dt_code(dlogits.dtype),
-                                     float(grad_scale), M, V, _p(colsum_part), part_stride, n_partials,
-                                     _p(loss_scratch) if loss_out is not None else None, cnt, _p(loss_out), float(loss_scale), _stream()),
-          "dg_cross_entropy_fused")
+    head = (_p(logits), _ld(logits), _p(targets), _p(loss_rows), _p(dlogits), _ld(dlogits), dt_code(dlogits.dtype),
+            float(grad_scale), M, V, _p(colsum_part), part_stride, n_partials,
+            _p(loss_scratch) if loss_out is not None else None, cnt, _p(loss_out), float(loss_scale))
+    if eps == 0.0 and zeta == 0.0:
+        check(lib.dg_cross_entropy_fused(*head, _stream()), "dg_cross_entropy_fused")
+    else:
+        check(lib.dg_cross_entropy_fused_smooth(*head, eps, zeta, _stream()), "dg_cross_entropy_fused_smooth")
     return loss_rows
 
 

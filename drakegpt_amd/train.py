@@ -21,7 +21,8 @@ Kaggle download.
 Added beside the reference's loop, all off by default: --grad-clip, --accum-steps, --save-every / --resume, and --lr-schedule /
 --warmup-steps / --min-lr / --no-decay: a rate per optimizer step over --iters steps (looked up on the GPU from a table on the
 engine path, set as group["lr"] on the autograd path) and parameters kept out of weight decay.  The default `reference`
-schedule is the CyclicLR stepped at evaluations described above.
+schedule is the CyclicLR stepped at evaluations described above.  --label-smoothing / --z-loss set the training objective
+(inside the loss-head kernels, both paths); evaluation lines keep the plain cross entropy.
 """
 from __future__ import annotations
 
@@ -39,6 +40,7 @@ from . import dist as ddist
 from . import schedules
 from .config import DRAKE_VOCAB_SIZE, PARAMS, PRESETS, SCALE_PARAMS, TRAIN
 from .model import MODEL_CLASSES, model_params
+from .ops import check_loss_options
 from .optim import check_accum_steps
 from .preprocessing import draw_offsets, encode_text, get_mapper, load_train_val_data, split_train_val
 
@@ -209,6 +211,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--no-decay", type=_no_decay_arg, default=(), metavar="KINDS",
                     help="comma-separated kinds of parameter kept out of weight decay: bias (every Linear bias), layernorm (LayerNorm "
                     "weights and biases), embedding (the token and position tables); default: none, every parameter decays")
+    ap.add_argument("--label-smoothing", type=float, default=0.0, metavar="E",
+                    help="label smoothing of the training objective, in [0, 1) (F.cross_entropy's label_smoothing; default 0: off).  "
+                    "Evaluation lines keep reporting the plain cross entropy")
+    ap.add_argument("--z-loss", type=float, default=0.0, metavar="Z",
+                    help="add Z * logsumexp(logits)^2 per row to the training objective (default 0: off; not with the fp8 loss head: "
+                    "--precision fp8 at a large vocabulary)")
     ap.add_argument("--save-every", type=int, default=None, metavar="N",
                     help="write the full training state (weights, optimizer, counters, generator: everything --resume needs) after "
                     "the evaluation of every N-th iteration and after the last one; N must be a multiple of --eval-interval "
@@ -230,6 +238,10 @@ def parse_args(argv=None):
             lr_values(args, 1.0, 1.0)          # (the rates come from the preset later: the shape is checked here)
         except ValueError as e:
             ap.error(f"--lr-schedule {args.lr_schedule}: {e} (total is --iters, warmup is --warmup-steps)")
+    try:
+        args.label_smoothing, args.z_loss = check_loss_options(args.label_smoothing, args.z_loss)
+    except ValueError as e:
+        ap.error(f"--label-smoothing / --z-loss: {e}")
     if args.save_every is not None and (args.save_every < 1 or args.save_every % args.eval_interval):
         ap.error(f"--save-every {args.save_every} must be a positive multiple of --eval-interval {args.eval_interval} (offsets are "
                  "staged per evaluation interval: the state is written between two stages)")
@@ -254,12 +266,13 @@ def run_args(args, K: int, world: int) -> dict:
     """the arguments a resumed run must repeat (RUN_ARG_DEFAULTS: those a file written before they existed ran with)"""
     return {"model": args.model, "preset": args.preset, "scale": bool(args.scale), "precision": args.precision, "accum_steps": K,
             "world_size": world, "lr_schedule": args.lr_schedule, "warmup_steps": int(args.warmup_steps), "min_lr": float(args.min_lr),
-            "no_decay": list(args.no_decay),
+            "no_decay": list(args.no_decay), "label_smoothing": float(args.label_smoothing), "z_loss": float(args.z_loss),
             # the table's length: the step count the schedule was laid out over
             "schedule_iters": None if args.lr_schedule == "reference" else int(args.iters)}
 
 
-RUN_ARG_DEFAULTS = {"lr_schedule": "reference", "warmup_steps": 0, "min_lr": 0.0, "no_decay": [], "schedule_iters": None}
+RUN_ARG_DEFAULTS = {"lr_schedule": "reference", "warmup_steps": 0, "min_lr": 0.0, "no_decay": [], "schedule_iters": None,
+                    "label_smoothing": 0.0, "z_loss": 0.0}
 
 
 def save_run_state(path: str, *, next_iteration: int, sched_steps: int, must_match: dict, model, engine=None, optimizer=None,
@@ -346,11 +359,13 @@ def main(argv=None):
     if args.model == "TransformerLM":
         from .engine import TrainEngine
         engine = TrainEngine(model, B, T, lr=base_lr, betas=params["betas"], seed=42, rank=rank, world_size=world, process_group=pg,
-                             max_grad_norm=args.grad_clip, accum_steps=K, lr_schedule=table, no_decay=args.no_decay)
+                             max_grad_norm=args.grad_clip, accum_steps=K, lr_schedule=table, no_decay=args.no_decay,
+                             label_smoothing=args.label_smoothing, z_loss=args.z_loss)
         engine.set_corpus(train_dev)
     else:
         # the five earlier-stage models train through the autograd path; their flat-buffer AdamW all-reduces the gradient
         from .optim import AdamW
+        model.set_loss_options(args.label_smoothing, args.z_loss)      # (train() mode only: evaluate_loss runs in eval())
         groups = model.parameters()
         if args.no_decay:
             groups = no_decay_groups(model, args.no_decay)

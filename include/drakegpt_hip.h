@@ -439,6 +439,23 @@ int dg_cross_entropy_fp8(const void* logits, int64_t ldl, const int64_t* targets
 int dg_cross_entropy_fused(const float* logits, int64_t ldl, const int64_t* targets, float* loss_rows, void* dlogits, int64_t ldd,
                            int dtype, float grad_scale, int M, int V, float* colsum_part, int64_t part_stride, int n_partials,
                            float* loss_part, uint32_t* loss_counter, float* loss_out, float loss_scale, void* stream);
+/* The three entry points above with the two knobs of a training objective: label smoothing eps = label_smoothing in [0, 1)
+ * (F.cross_entropy(label_smoothing=)) and the z-loss zeta = z_loss >= 0.  Per row, lse = logsumexp(logits[m,:]), p = softmax, t the target:
+ *   loss_rows[m] = lse - (1 - eps) x_t - (eps / V) sum_{i < V} x_i + zeta lse^2
+ *   dlogits[m,n] = grad_scale (p_n (1 + 2 zeta lse) - (1 - eps) [n == t] - eps / V),   columns V .. ldd - 1 zero
+ * The sum runs over the V logits only, whatever columns V .. ldl - 1 hold.  With zeta > 0 a gradient row sums to 2 zeta lse grad_scale;
+ * the fused head's column-sum partials are the sums of what was written and loss_out = loss_scale * sum of loss_rows.  The e5m2
+ * copy's a-priori scale needs |dlogits| <= grad_scale, which label smoothing keeps and a z-loss does not: the fp8 entry takes
+ * label_smoothing only.  Values outside the ranges (or not finite): DG_ERR_ARG.  Both at 0: the old entry point, bit for bit. */
+int dg_cross_entropy_smooth(const void* logits, int logits_dtype, int64_t ldl, const int64_t* targets, float* loss_rows,
+                            void* dlogits, int64_t ldd, int dtype, float grad_scale, const float* grad_scale_dev, int M, int V,
+                            float label_smoothing, float z_loss, void* stream);
+int dg_cross_entropy_fp8_smooth(const void* logits, int64_t ldl, const int64_t* targets, float* loss_rows, void* dlogits, int64_t ldd,
+                                float grad_scale, int M, int V, void* dlogits_fp8, int64_t ld8, float label_smoothing, void* stream);
+int dg_cross_entropy_fused_smooth(const float* logits, int64_t ldl, const int64_t* targets, float* loss_rows, void* dlogits, int64_t ldd,
+                                  int dtype, float grad_scale, int M, int V, float* colsum_part, int64_t part_stride, int n_partials,
+                                  float* loss_part, uint32_t* loss_counter, float* loss_out, float loss_scale,
+                                  float label_smoothing, float z_loss, void* stream);
 /* out[0] = scale * sum_i x[i] (single workgroup, fixed order). */
 int dg_reduce_sum(const float* x, int64_t n, float scale, float* out, void* stream);
 
