@@ -218,6 +218,43 @@ def check_compat(saved_meta: dict, own_meta: dict, what: str = "meta") -> None:
             raise ValueError(f"training state: {what}.{field} differs: saved {saved!r}, this run has {own!r}")
 
 
+def check_ema_meta(saved_meta: dict, own: bool) -> None:
+    """whether a moving average of the weights is kept must agree in both directions: meta["ema"] is written (True) only by an
+    engine that keeps one, so a file from before it existed reads as off"""
+    saved = saved_meta.get("ema", False)
+    if not isinstance(saved, bool) or saved != bool(own):
+        raise ValueError(f"training state: meta.ema differs: saved {saved!r}, this run has {bool(own)!r}")
+
+
+def check_ema_state(section, own: bool, n: int):
+    """the "ema" section of an engine / optimizer state ({"decay", "warmup", "values"}) against a run that keeps an average (own)
+    of n floats or does not; returns None or (decay, warmup, values).  ValueError names the field."""
+    from .ops import check_ema_options
+    if (section is not None) != bool(own):
+        raise ValueError(f"training state: engine.ema differs: saved {'present' if section is not None else None!r}, this run has "
+                         f"{'a moving average' if own else None!r}")
+    if section is None:
+        return None
+    if not isinstance(section, dict):
+        raise ValueError(f"training state: engine.ema is a {type(section).__name__}, expected a dict")
+    for k in ("decay", "warmup", "values"):
+        if k not in section:
+            raise ValueError(f"training state: missing key engine.ema.{k}")
+    if not isinstance(section["warmup"], bool):
+        raise ValueError(f"training state: engine.ema.warmup is {section['warmup']!r}, expected a bool")
+    try:
+        decay = check_ema_options(section["decay"], section["warmup"])
+    except ValueError as err:
+        raise ValueError(f"training state: engine.ema.decay: {err}") from None
+    if decay is None:
+        raise ValueError("training state: engine.ema.decay is None")
+    values = section["values"]
+    if not isinstance(values, Tensor) or values.dtype != torch.float32 or tuple(values.shape) != (n,):
+        raise ValueError(f"training state: engine.ema.values is {getattr(values, 'dtype', type(values).__name__)} "
+                         f"{tuple(getattr(values, 'shape', ()))}, expected float32 {(n,)}")
+    return decay, section["warmup"], values
+
+
 def save_train_state(path: str, obj: dict) -> None:
     """write to a temporary file in the same directory, then os.replace: the previous file stays intact until the new one is
     complete, and a failure leaves no temporary file behind"""

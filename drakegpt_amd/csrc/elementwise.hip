@@ -902,13 +902,38 @@ __device__ __forceinline__ AdamwSched adamw_sched_of(S... s) {
     else return AdamwSched{nullptr, 0, nullptr};
 }
 
-template <bool CLIP, bool TABLE, bool MASK, typename... S>   // S: nothing, or one AdamwSched when TABLE or MASK
+// EMA (S = AdamwSched, AdamwEma): one more 16 B/lane stream, ema = ema + (p_new - ema) * (1 - d_s) on the weight this thread has
+// just stored (step word 0: ema = p_new, the buffer is not read).  {decay, warmup} come from device memory (a captured graph picks
+// up a new decay); d_s and 1 - d_s are computed once per workgroup, where the step word is read.  The three operations are rounded
+// one by one (adamw_ema_lerp: contraction is off inside it, so the multiply and the add never become an FMA), so three fp32
+// operations on the host give the same bits.  Without it the kernel, its instantiations and its kernel arguments are the ones they were.
+struct AdamwEma { float* ema; const float* ema_hyper; };
+__device__ __forceinline__ float adamw_ema_lerp(float e, float p, float w) {
+#pragma clang fp contract(off)
+    const float d = p - e;
+    const float t = d * w;
+    return e + t;
+}
+__device__ __forceinline__ float adamw_ema_weight(const float* __restrict__ ema_hyper, uint32_t step) {
+#pragma clang fp contract(off)
+    float d = ema_hyper[0];
+    if (ema_hyper[1] != 0.f) d = fminf(d, ((float)step + 1.f) / ((float)step + 10.f));      // (correctly rounded: hipcc's default)
+    return 1.f - d;
+}
+__device__ __forceinline__ AdamwSched adamw_sched_of(AdamwSched sc, AdamwEma) { return sc; }
+__device__ __forceinline__ AdamwEma adamw_ema_of(AdamwSched, AdamwEma ea) { return ea; }
+template <typename... S>
+__device__ __forceinline__ AdamwEma adamw_ema_of(S...) { return AdamwEma{nullptr, nullptr}; }
+
+template <bool CLIP, bool TABLE, bool MASK, typename... S>   // S: nothing; one AdamwSched when TABLE or MASK; AdamwSched, AdamwEma
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                              float* __restrict__ v, int64_t n, const float* __restrict__ hyper,
                              uint32_t* rng_state, float grad_scale,
                              bf16_t* __restrict__ shadow, int advance, const float* __restrict__ clip_coef, S... sched) {
-    static_assert(sizeof...(S) == ((TABLE || MASK) ? 1 : 0), "the schedule arguments go with TABLE or MASK");
+    constexpr bool EMA = sizeof...(S) == 2;
+    static_assert(EMA || sizeof...(S) == ((TABLE || MASK) ? 1 : 0), "the schedule arguments go with TABLE or MASK");
     const AdamwSched sc = adamw_sched_of(sched...);
+    const AdamwEma ea = adamw_ema_of(sched...);
     const float* __restrict__ lr_table = sc.lr_table;
     const uint32_t* __restrict__ no_decay_bits = sc.no_decay_bits;
     if (CLIP) grad_scale *= clip_coef[0];
@@ -922,6 +947,9 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
     const float inv_sqrt_bc2 = 1.f / sqrtf(bc2);
     const float decay = 1.f - lr * wd;
     const bool shadow_vec = (((uintptr_t)shadow) & 7) == 0;
+    float* __restrict__ ema = ea.ema;
+    float ema_w = 0.f;
+    if (EMA) ema_w = adamw_ema_weight(ea.ema_hyper, step_now);
     int64_t gs = (int64_t)gridDim.x * blockDim.x;
     int64_t n4 = n / 4;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gs) {
@@ -941,6 +969,15 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
             pp[j] = pj; mm[j] = mj; vv[j] = vj;
         }
         ((f32x4*)p)[i] = pp; ((f32x4*)m)[i] = mm; ((f32x4*)v)[i] = vv;
+        if (EMA) {
+            f32x4 ee = pp;
+            if (step_now != 0u) {
+                ee = ((f32x4*)ema)[i];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) ee[j] = adamw_ema_lerp(ee[j], pp[j], ema_w);
+            }
+            ((f32x4*)ema)[i] = ee;
+        }
         if (shadow) {                                            // one 8-byte store (shadow + 4 i is 8-byte aligned with p)
             bf16x4 sh;
 #pragma unroll
@@ -965,6 +1002,14 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
         pj -= step_size * (mj / denom);
         p[i] = pj; m[i] = mj; v[i] = vj;
         if (shadow) shadow[i] = (bf16_t)pj;
+        if (EMA) {
+            float ej = pj;
+            if (step_now != 0u) {
+                ej = ema[i];
+                ej = adamw_ema_lerp(ej, pj, ema_w);
+            }
+            ema[i] = ej;
+        }
     }
     if (advance) {
         __syncthreads();                                   // (every wave of this workgroup has read the step word long ago)
@@ -1031,6 +1076,55 @@ extern "C" int dg_adamw_step_sched(float* p, const float* g, float* m, float* v,
         default: LAUNCH(true, true, true); break;
     }
 #undef LAUNCH
+    DG_LAUNCH_CHECK();
+    return DG_OK;
+}
+
+extern "C" int dg_adamw_step_ema(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, uint32_t* rng_state,
+                                 float grad_scale, const float* clip_coef, const float* lr_table, int64_t lr_table_len,
+                                 const uint32_t* no_decay_bits, void* shadow_bf16, int advance_step, float* ema, const float* ema_hyper,
+                                 void* stream) {
+    if (!p || !g || !m || !v || !hyper || !rng_state || !ema || !ema_hyper || n <= 0) return DG_ERR_ARG;
+    if (lr_table ? lr_table_len < 1 : lr_table_len != 0) return DG_ERR_ARG;
+    if (!dg_aligned16(p) || !dg_aligned16(g) || !dg_aligned16(m) || !dg_aligned16(v) || !dg_aligned16(ema)) return DG_ERR_ALIGN;
+    const unsigned grid = adamw_grid(n);
+    const AdamwSched sc{lr_table, lr_table_len, no_decay_bits};
+    const AdamwEma ea{ema, ema_hyper};
+#define LAUNCH(CLIP, TABLE, MASK) hipLaunchKernelGGL((adamw_kernel<CLIP, TABLE, MASK, AdamwSched, AdamwEma>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, hyper, rng_state, grad_scale, (bf16_t*)shadow_bf16, advance_step, clip_coef, sc, ea)
+    switch ((clip_coef ? 4 : 0) | (lr_table ? 2 : 0) | (no_decay_bits ? 1 : 0)) {
+        case 0: LAUNCH(false, false, false); break;
+        case 1: LAUNCH(false, false, true); break;
+        case 2: LAUNCH(false, true, false); break;
+        case 3: LAUNCH(false, true, true); break;
+        case 4: LAUNCH(true, false, false); break;
+        case 5: LAUNCH(true, false, true); break;
+        case 6: LAUNCH(true, true, false); break;
+        default: LAUNCH(true, true, true); break;
+    }
+#undef LAUNCH
+    DG_LAUNCH_CHECK();
+    return DG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// exchange two fp32 buffers in one streaming launch (TrainEngine.ema_weights: weights <-> their moving average)
+__global__ void swap_f32_kernel(float* __restrict__ a, float* __restrict__ b, int64_t n) {
+    const int64_t gs = (int64_t)gridDim.x * blockDim.x;
+    const int64_t n4 = n / 4;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gs) {
+        const f32x4 x = ((f32x4*)a)[i], y = ((f32x4*)b)[i];
+        ((f32x4*)a)[i] = y; ((f32x4*)b)[i] = x;
+    }
+    for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gs) {
+        const float x = a[i], y = b[i];
+        a[i] = y; b[i] = x;
+    }
+}
+
+extern "C" int dg_swap_f32(float* a, float* b, int64_t n, void* stream) {
+    if (!a || !b || n <= 0) return DG_ERR_ARG;
+    if (!dg_aligned16(a) || !dg_aligned16(b)) return DG_ERR_ALIGN;
+    hipLaunchKernelGGL(swap_f32_kernel, dim3(adamw_grid(n)), dim3(256), 0, (hipStream_t)stream, a, b, n);
     DG_LAUNCH_CHECK();
     return DG_OK;
 }

@@ -24,6 +24,7 @@ MI355X-first layout (288 GB HBM: keep everything resident, nothing is re-packed 
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -181,7 +182,8 @@ class TrainEngine:
                  seed: int = 42, rank: int = 0, world_size: int = 1, process_group=None, use_graph: bool = True,
                  dp_buckets: Optional[int] = None, logits: str = "auto", grad_stream: str = "auto", fp8_dw: Optional[bool] = None,
                  max_grad_norm: Optional[float] = None, accum_steps: int = 1, lr_schedule=None, schedule_steps: Optional[int] = None,
-                 no_decay=(), label_smoothing: float = 0.0, z_loss: float = 0.0):
+                 no_decay=(), label_smoothing: float = 0.0, z_loss: float = 0.0, ema_decay: Optional[float] = None,
+                 ema_warmup: bool = False):
         if not isinstance(model, TransformerLM):
             raise TypeError("TrainEngine drives TransformerLM (the other five models train through the autograd path)")
         p0 = next(model.parameters())
@@ -225,6 +227,9 @@ class TrainEngine:
         # eval_losses stay the plain cross entropy.
         self.label_smoothing, self.z_loss = ops.check_loss_options(label_smoothing, z_loss)
         self._loss_kw = {k: v for k, v in (("label_smoothing", self.label_smoothing), ("z_loss", self.z_loss)) if v != 0.0}
+        # an exponential moving average of the weights, moved on inside the AdamW launch (None: no average, nothing below exists)
+        self.ema_decay = ops.check_ema_options(ema_decay, ema_warmup)
+        self.ema_warmup = bool(ema_warmup)
         if self.accum > 1 and dp_buckets is not None and int(dp_buckets) > 1:
             raise ValueError("accum_steps > 1 uses one gradient exchange per optimizer step (it is amortised over the micro-steps "
                              "already): dp_buckets > 1 cannot be combined with it")
@@ -306,6 +311,17 @@ class TrainEngine:
         self._sched_kw = {}
         if self.lr_table is not None or self.no_decay_bits is not None:
             self._sched_kw = {"lr_table": self.lr_table, "no_decay_bits": self.no_decay_bits}
+        # ema_decay: ema = flat[0, n_active) as the launch has just written it, averaged by AdamW's own step word (opt_state under
+        # accumulation: once per optimizer step); the first step overwrites it.  ema_hyper = {decay, warmup} is read on the device:
+        # set_ema_decay() writes it, captured graphs stay valid.  _ema_kw is what the two update programs add to their
+        # ops.adamw_step call: nothing for an engine without it, whose call is the one it always was.
+        self.ema = self.ema_hyper = None
+        self._ema_kw = {}
+        self._in_ema = False          # inside `with ema_weights()`: flat holds the average, ema the weights
+        if self.ema_decay is not None:
+            self.ema = self.flat[:self.n_active].clone()
+            self.ema_hyper = ops.new_ema_hyper(self.ema_decay, self.ema_warmup, self.dev)
+            self._ema_kw = {"ema": self.ema, "ema_hyper": self.ema_hyper}
         # global-norm gradient clipping (ref: clip_grad_norm_(model.parameters(), max_norm) before optimizer.step()): the norm of
         # the mean gradient over ranks, gflat[0, n_active) * 1 / world, is computed inside the step and its coefficient applied
         # inside the AdamW launch; gflat / named_grads() keep the unclipped gradient.  clip_state = {total_norm, coef, max_norm, 0}
@@ -931,25 +947,27 @@ class TrainEngine:
         scale = 1.0 / (self.accum * self.world)
         if self.clip_state is None:
             ops.adamw_step(self.flat, self.gacc, self.m_, self.v_, self.hyper, self.opt_state, scale,
-                           shadow_bf16=self.shadow, n=self.n_active, advance=True, **self._sched_kw)
+                           shadow_bf16=self.shadow, n=self.n_active, advance=True, **self._sched_kw, **self._ema_kw)
         else:
             ops.grad_norm(self.gacc, scale, self.clip_state[2:3], self.clip_state, self.norm_work)
             ops.adamw_step(self.flat, self.gacc, self.m_, self.v_, self.hyper, self.opt_state, scale,
-                           shadow_bf16=self.shadow, n=self.n_active, advance=True, clip=self.clip_state[1:2], **self._sched_kw)
+                           shadow_bf16=self.shadow, n=self.n_active, advance=True, clip=self.clip_state[1:2], **self._sched_kw,
+                           **self._ema_kw)
         self._refresh_transposes()
 
     def _prog_update(self):
         # (the step word moves on inside the AdamW launch: nothing after it reads the word)
         if self.clip_state is None:
             ops.adamw_step(self.flat, self.gflat, self.m_, self.v_, self.hyper, self.state, 1.0 / self.world,
-                           shadow_bf16=self.shadow, n=self.n_active, advance=True, **self._sched_kw)
+                           shadow_bf16=self.shadow, n=self.n_active, advance=True, **self._sched_kw, **self._ema_kw)
         else:
             # the gradient is final here on every path (the data-parallel optimizer graph runs after the exchange): norm of the mean
             # over ranks, then AdamW on g * coef.  The alignment gaps of gflat are zero (no producer writes them), so the norm
             # over the whole active range is the norm over the parameters.
             ops.grad_norm(self.gflat, 1.0 / self.world, self.clip_state[2:3], self.clip_state, self.norm_work)
             ops.adamw_step(self.flat, self.gflat, self.m_, self.v_, self.hyper, self.state, 1.0 / self.world,
-                           shadow_bf16=self.shadow, n=self.n_active, advance=True, clip=self.clip_state[1:2], **self._sched_kw)
+                           shadow_bf16=self.shadow, n=self.n_active, advance=True, clip=self.clip_state[1:2], **self._sched_kw,
+                           **self._ema_kw)
         self._refresh_transposes()
 
     def _dp(self) -> bool:
@@ -975,6 +993,8 @@ class TrainEngine:
         """accum_steps > 1: one micro graph and one update graph in the same pool; the warm-up runs each program once and every
         buffer and counter it moves is put back"""
         bufs = (self.flat, self.m_, self.v_, self.state, self.gacc, self.acc_ctl, self.opt_state, self.loss_acc)
+        if self.ema is not None:
+            bufs += (self.ema,)
         snap = [b.clone() for b in bufs]
         hist = self._fp8_snapshot()
         j = self._j
@@ -1000,6 +1020,7 @@ class TrainEngine:
 
     def _capture(self):
         snap = (self.flat.clone(), self.m_.clone(), self.v_.clone(), self.state.clone())
+        ema_snap = None if self.ema is None else self.ema.clone()
         hist = self._fp8_snapshot()
         side = torch.cuda.Stream(device=self.dev)
         side.wait_stream(torch.cuda.current_stream())
@@ -1013,6 +1034,8 @@ class TrainEngine:
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize(self.dev)
         self.flat.copy_(snap[0]); self.m_.copy_(snap[1]); self.v_.copy_(snap[2]); self.state.copy_(snap[3])
+        if ema_snap is not None:
+            self.ema.copy_(ema_snap)
         self._fp8_put_back(hist)
         self.refresh_shadows()
         torch.cuda.synchronize(self.dev)
@@ -1085,6 +1108,76 @@ class TrainEngine:
         self.max_grad_norm = check_max_grad_norm(max_norm)
         self.clip_state[2:3].fill_(self.max_grad_norm)
 
+    # ---- the moving average of the weights (TrainEngine(ema_decay=...))
+    def _refuse_in_ema(self, what: str) -> None:
+        if self._in_ema:
+            raise RuntimeError(f"{what} inside `with ema_weights()`: the weights are swapped with their moving average; leave the "
+                               "context first")
+
+    def _need_ema(self, what: str) -> None:
+        if self.ema is None:
+            raise RuntimeError(f"{what}: this engine was built without a moving average (TrainEngine(..., ema_decay=...))")
+
+    def set_ema_decay(self, decay: float):
+        """a new decay for the following optimizer steps (a device write: captured graphs stay valid)"""
+        self._need_ema("set_ema_decay")
+        d = ops.check_ema_options(decay, self.ema_warmup)
+        if d is None:
+            raise ValueError("set_ema_decay: the decay must be a number in (0, 1); an engine cannot drop its moving average")
+        self.ema_decay = d
+        self.ema_hyper[0:1].fill_(d)
+
+    def ema_view(self, key: str) -> Tensor:
+        """the moving average of one trained region, a view of `ema` (as param_view is a view of `flat`)"""
+        self._need_ema("ema_view")
+        return self.grad_view(key, self.ema)
+
+    def ema_state_dict(self) -> dict:
+        """the moving average in the model's state_dict() format, as CPU tensors: loads into a plain TransformerLM.  The per-head
+        query / key / value entries are rows of the packed QKV region (the mapping of optimizer_state_dict); tensors the engine
+        does not train (ln_f) are the model's.  Synchronises."""
+        self._need_ema("ema_state_dict")
+        self._refuse_in_ema("ema_state_dict()")
+        img = self.ema.cpu()
+        out = {}
+        for name, t in self.model.state_dict().items():
+            try:
+                key, rows = CK.param_region(name, self.NH, self.H)
+            except KeyError:
+                key = None
+            if key is None or key in CK.UNTRAINED:
+                out[name] = t.detach().cpu().clone()
+            else:
+                out[name] = CK._rows(self.grad_view(key, img), rows).clone()
+        return out
+
+    def _swap_ema(self) -> None:
+        ops.swap_(self.flat, self.ema, self.n_active)
+        if self.shadow is not None:      # (the optimizer launch keeps the whole bf16 image current; refresh_shadows() the GEMM weights)
+            lo = self.layA.size
+            ops.cast(self.flat[lo:self.n_active], torch.bfloat16, out=self.shadow[lo:])
+        self.refresh_shadows()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """`with engine.ema_weights():` -- evaluate, sample or export the averaged weights.  On entry the weights and their moving
+        average change places (one dg_swap_f32 launch) and every weight-derived copy is rebuilt from them (refresh_shadows); the
+        model's Parameters are views of `flat` and captured graphs hold its address, so eval_loss, eval_losses, model.generate and
+        model.state_dict() all see the average.  On exit the same again: the derived copies are functions of the weights alone,
+        so training continues bit for bit.  Inside, whatever would train on or save the swapped buffers raises RuntimeError."""
+        self._need_ema("ema_weights")
+        self._refuse_in_ema("ema_weights()")
+        if self._j:
+            raise RuntimeError(f"ema_weights(): {self._j} of {self.accum} micro-steps of the current optimizer step are taken; finish "
+                               "it with micro_step() first")
+        self._swap_ema()
+        self._in_ema = True
+        try:
+            yield self
+        finally:
+            self._in_ema = False
+            self._swap_ema()
+
     def set_offsets(self, ix: Tensor):
         """window offsets of THIS rank's rows for the next step (drawn by the host CPU generator, ref: preprocessing.py:43)"""
         if self._off_rows != 1:
@@ -1141,6 +1234,7 @@ class TrainEngine:
         """one micro-batch on the current offsets / batch: forward, backward, its gradient added into the accumulator; returns the
         micro-batch's loss (device scalar).  The accum_steps-th call also runs the gradient exchange (one all-reduce of the
         accumulated gradient) and the optimizer update on the mean gradient.  accum_steps == 1: the same as step()."""
+        self._refuse_in_ema("micro_step()")
         if self.accum == 1:
             return self.step()
         if self._off_left is not None:
@@ -1181,6 +1275,7 @@ class TrainEngine:
     def step(self) -> Tensor:
         """one training iteration on the current offsets / batch; returns the device loss scalar.  accum_steps = k > 1: k
         micro-steps on the next k staged offset rows and one optimizer update; returns the mean of their losses."""
+        self._refuse_in_ema("step()")
         if self.accum > 1:
             return self._step_accum()
         if self._off_left is not None:
@@ -1296,12 +1391,15 @@ class TrainEngine:
                 "num_heads": int(self.NH), "model_context_length": int(self.model.context_length), "batch_size": self.B,
                 "context_length": self.T, "accum_steps": self.accum, "world_size": int(self.world), "dropout": self.p_drop}
         meta.update(self._loss_kw)      # only where set: a default engine writes and accepts exactly the files it always did
+        if self.ema is not None:
+            meta["ema"] = True
         return meta
 
     def _check_meta(self, saved: dict) -> None:
         """CK.check_compat on the fields every engine has; the loss options in both directions (a field absent on either side reads
         as 0.0: a smoothed state is refused by a default engine as much as the reverse)"""
-        CK.check_compat(saved, {k: v for k, v in self._meta().items() if k not in self._LOSS_FIELDS})
+        CK.check_compat(saved, {k: v for k, v in self._meta().items() if k not in self._LOSS_FIELDS and k != "ema"})
+        CK.check_ema_meta(saved, self.ema is not None)
         for field in self._LOSS_FIELDS:
             theirs, own = saved.get(field, 0.0), self._loss_kw.get(field, 0.0)
             if isinstance(theirs, bool) or not isinstance(theirs, (int, float)) or float(theirs) != own:
@@ -1384,12 +1482,14 @@ class TrainEngine:
         the same model, written in place (captured graphs stay valid).  ValueError if the parameters disagree about the step
         count or the state does not fit.  accum_steps == 1: the step word also keys dropout and selects the staged offset row,
         so loading another step count moves those too -- load_state_dict() is the form that keeps every counter consistent."""
+        self._refuse_in_ema("load_optimizer_state_dict()")
         m, v, step, hyper = self._parse_optimizer_state(sd)
         self._write_optimizer_state(m, v, step, hyper)
 
     def state_dict(self) -> dict:
         """everything a following step reads that an earlier step or call wrote, as CPU tensors and plain values (DESIGN.md
         section 4 lists every buffer).  Synchronises; not for the hot path.  RuntimeError inside an optimizer step."""
+        self._refuse_in_ema("state_dict()")
         if self._j:
             raise RuntimeError(f"state_dict(): {self._j} of {self.accum} micro-steps of the current optimizer step are taken; finish it "
                                "with micro_step() first (a half-filled gradient accumulator is not a state to save)")
@@ -1403,6 +1503,8 @@ class TrainEngine:
                "fp8_seeded": bool(self._fp8_seeded),
                "fp8_sites": {k: v.cpu() for k, v in self.fp8_sites.items()} if self.fp8 else {},
                "lr_table": None if self.lr_table_host is None else self.lr_table_host.clone(), "no_decay": list(self.no_decay)}
+        if self.ema is not None:
+            eng["ema"] = {"decay": self.ema_decay, "warmup": self.ema_warmup, "values": self.ema.cpu()}
         return {"format": CK.FORMAT, "version": CK.VERSION,
                 "model": {k: v.detach().cpu().clone() for k, v in self.model.state_dict().items()},
                 "optimizer": self.optimizer_state_dict(), "engine": eng, "meta": self._meta()}
@@ -1418,6 +1520,7 @@ class TrainEngine:
         the offset buffer is the one exception, as in stage_offsets).  Hyper-parameters follow the file; clipping on / off follows
         this engine, its threshold the file where both clip.  Every rank loads rank 0's file; the dropout stream is re-derived
         from the saved seed for this rank.  precision fp8: a rank other than 0 seeds its amax histories afresh."""
+        self._refuse_in_ema("load_state_dict()")
         CK.check_format(sd)
         for k in ("model", "optimizer", "engine", "meta"):
             if k not in sd:
@@ -1452,6 +1555,7 @@ class TrainEngine:
                 raise ValueError(f"training state: engine.lr_table: {err}") from None
         if sorted(groups) != list(self.no_decay):
             raise ValueError(f"training state: engine.no_decay differs: saved {sorted(groups)!r}, this engine has {list(self.no_decay)!r}")
+        ema_sd = CK.check_ema_state(e.get("ema"), self.ema is not None, self.n_active)
         m, v, step, hyper = self._parse_optimizer_state(sd["optimizer"])
         word = int(e["step_word"])
         opt_step = word if self.accum == 1 else e["opt_step"]
@@ -1497,6 +1601,10 @@ class TrainEngine:
         if table is not None:
             self.lr_table_host = table
             self.lr_table.copy_(table)
+        if ema_sd is not None:
+            self.ema_decay, self.ema_warmup = ema_sd[0], ema_sd[1]
+            self.ema_hyper.copy_(torch.tensor([self.ema_decay, 1.0 if self.ema_warmup else 0.0], dtype=torch.float32))
+            self.ema.copy_(ema_sd[2])
         self.seed = int(e["seed"])
         self.state.copy_(ops.new_rng_state(self._rank_seed(self.seed), self.dev, word))
         if self.accum > 1:

@@ -908,31 +908,57 @@ def attn_decode_append(row: Tensor, cache: Tensor, state: Tensor, NH: int, H: in
     return out
 
 
+def _check_adamw_indexing(n: int, streams: dict, lr_table, no_decay_bits, clip) -> None:
+    """what dg_adamw_step_sched / dg_adamw_step_ema index and the library cannot check: n against every stream, the table's shape,
+    the bitmap's length"""
+    if n < 1 or any(n > t.numel() for t in streams.values()):
+        raise ValueError(f"adamw_step: n = {n} does not fit {', '.join(streams)}")
+    if lr_table is not None:
+        _chk(lr_table, "lr_table", torch.float32)
+        if lr_table.dim() != 1 or lr_table.numel() < 1:
+            raise ValueError("adamw_step: lr_table must be a 1-D tensor with at least one entry")
+    if no_decay_bits is not None:
+        _chk(no_decay_bits, "no_decay_bits", torch.int32)
+        if no_decay_bits.numel() < no_decay_words(n):
+            raise ValueError(f"adamw_step: no_decay_bits needs {no_decay_words(n)} words for n = {n}, got {no_decay_bits.numel()}")
+    if clip is not None:
+        _chk(clip, "clip", torch.float32)
+
+
 def adamw_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, hyper: Tensor, rng_state: Tensor, grad_scale: float = 1.0,
                shadow_bf16: Optional[Tensor] = None, n: Optional[int] = None, advance: bool = False, *,
-               clip: Optional[Tensor] = None, lr_table: Optional[Tensor] = None, no_decay_bits: Optional[Tensor] = None) -> None:
+               clip: Optional[Tensor] = None, lr_table: Optional[Tensor] = None, no_decay_bits: Optional[Tensor] = None,
+               ema: Optional[Tensor] = None, ema_hyper: Optional[Tensor] = None) -> None:
     """advance: the launch also moves the step word of rng_state on (what state_advance does, without its launch).
     clip: a device fp32 scalar, the clipping coefficient written by grad_norm (out[1:2]); the step then applies g * grad_scale * coef
     (dg_adamw_step_clip) and g itself stays unclipped.  None: dg_adamw_step, unchanged.
     lr_table: a device fp32 vector; the update uses lr_table[min(step word, len - 1)] instead of hyper[0].
     no_decay_bits: the bitmap of new_no_decay_bits(ranges, n, device); elements of a set granule see weight_decay = 0.
-    Either of the two takes the launch to dg_adamw_step_sched; with both None the calls are the ones above, unchanged."""
+    Either of the two takes the launch to dg_adamw_step_sched; with both None the calls are the ones above, unchanged.
+    ema (with ema_hyper = new_ema_hyper(decay, warmup, device)): the launch also moves this moving average of the weights on
+    (dg_adamw_step_ema: ema += (p_new - ema) * (1 - d_s) by the step word it reads; step word 0: ema = p_new); p, m, v, the shadow
+    and the state words are the ones the launch without it writes.  None: the calls above, unchanged."""
     for t, nm in ((p, "p"), (g, "g"), (m, "m"), (v, "v"), (hyper, "hyper")):
         _chk(t, nm, torch.float32)
     n = p.numel() if n is None else n
+    if ema is None and ema_hyper is not None:
+        raise ValueError("adamw_step: ema_hyper goes with ema")
+    if ema is not None:
+        if ema_hyper is None:
+            raise ValueError("adamw_step: ema needs ema_hyper (new_ema_hyper)")
+        _chk(ema, "ema", torch.float32)
+        _chk(ema_hyper, "ema_hyper", torch.float32)
+        _check_adamw_indexing(n, {"p": p, "g": g, "m": m, "v": v, "ema": ema}, lr_table, no_decay_bits, clip)
+        if ema_hyper.numel() < 2:
+            raise ValueError("adamw_step: ema_hyper needs 2 floats {decay, warmup} (new_ema_hyper)")
+        if shadow_bf16 is not None and shadow_bf16.numel() < n:
+            raise ValueError(f"adamw_step: shadow_bf16 holds {shadow_bf16.numel()} elements, n = {n}")
+        check(lib.dg_adamw_step_ema(_p(p), _p(g), _p(m), _p(v), n, _p(hyper), _p(rng_state), float(grad_scale), _p(clip), _p(lr_table),
+                                    0 if lr_table is None else lr_table.numel(), _p(no_decay_bits), _p(shadow_bf16), int(advance),
+                                    _p(ema), _p(ema_hyper), _stream()), "dg_adamw_step_ema")
+        return
     if lr_table is not None or no_decay_bits is not None:
-        if n < 1 or any(n > t.numel() for t in (p, g, m, v)):
-            raise ValueError(f"adamw_step: n = {n} does not fit p, g, m, v")
-        if lr_table is not None:
-            _chk(lr_table, "lr_table", torch.float32)
-            if lr_table.dim() != 1 or lr_table.numel() < 1:
-                raise ValueError("adamw_step: lr_table must be a 1-D tensor with at least one entry")
-        if no_decay_bits is not None:
-            _chk(no_decay_bits, "no_decay_bits", torch.int32)
-            if no_decay_bits.numel() < no_decay_words(n):
-                raise ValueError(f"adamw_step: no_decay_bits needs {no_decay_words(n)} words for n = {n}, got {no_decay_bits.numel()}")
-        if clip is not None:
-            _chk(clip, "clip", torch.float32)
+        _check_adamw_indexing(n, {"p": p, "g": g, "m": m, "v": v}, lr_table, no_decay_bits, clip)
         check(lib.dg_adamw_step_sched(_p(p), _p(g), _p(m), _p(v), n, _p(hyper), _p(rng_state), float(grad_scale), _p(clip), _p(lr_table),
                                       0 if lr_table is None else lr_table.numel(), _p(no_decay_bits), _p(shadow_bf16), int(advance),
                                       _stream()), "dg_adamw_step_sched")
@@ -944,6 +970,48 @@ def adamw_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, hyper: Tensor, rng_st
     _chk(clip, "clip", torch.float32)
     check(lib.dg_adamw_step_clip(_p(p), _p(g), _p(m), _p(v), n, _p(hyper), _p(rng_state), float(grad_scale), _p(clip), _p(shadow_bf16),
                                  int(advance), _stream()), "dg_adamw_step_clip")
+
+
+def check_ema_options(decay=None, warmup=False):
+    """the checks of the two EMA options, plain Python, raised before anything touches a device: decay None (no moving average) or
+    a number with 0 < decay < 1 (no bools, no NaN); warmup (d_s = min(decay, (s + 1) / (s + 10))) goes with a decay.  Returns the
+    decay as None or a float."""
+    if decay is None:
+        if warmup:
+            raise ValueError("ema_warmup goes with ema_decay")
+        return None
+    if isinstance(decay, bool):
+        raise ValueError(f"ema_decay must be a number in (0, 1), got {decay!r}")
+    try:
+        d = float(decay)
+    except (TypeError, ValueError):
+        raise ValueError(f"ema_decay must be a number in (0, 1), got {decay!r}") from None
+    if not 0.0 < d < 1.0:          # (NaN fails both comparisons)
+        raise ValueError(f"ema_decay must be a number in (0, 1), got {decay!r}")
+    if float(torch.tensor(d, dtype=torch.float32)) >= 1.0:
+        raise ValueError(f"ema_decay {decay!r} rounds to 1 in fp32: the average would never move")
+    return d
+
+
+def new_ema_hyper(decay, warmup, device) -> Tensor:
+    """device fp32 {decay, warmup != 0} for adamw_step(ema=...): read by the launch, so writing it changes the decay of a captured graph"""
+    d = check_ema_options(decay, warmup)
+    if d is None:
+        raise ValueError("new_ema_hyper: ema_decay is None")
+    return torch.tensor([d, 1.0 if warmup else 0.0], dtype=torch.float32, device=device)
+
+
+def swap_(a: Tensor, b: Tensor, n: Optional[int] = None) -> None:
+    """exchange the first n elements (default: all) of two fp32 buffers in one launch (dg_swap_f32)"""
+    _chk(a, "a", torch.float32)
+    _chk(b, "b", torch.float32)
+    n = min(a.numel(), b.numel()) if n is None else int(n)
+    if n < 1 or n > a.numel() or n > b.numel():
+        raise ValueError(f"swap_: n = {n} does not fit a ({a.numel()}) and b ({b.numel()})")
+    lo, hi = sorted((a.data_ptr(), b.data_ptr()))
+    if lo + 4 * n > hi:
+        raise ValueError("swap_: a and b overlap")
+    check(lib.dg_swap_f32(_p(a), _p(b), n, _stream()), "dg_swap_f32")
 
 
 NO_DECAY_GRANULE = 64   # floats per bit of the no-decay bitmap: ALIGN of engine.py and _ALIGN of optim.py

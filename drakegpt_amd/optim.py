@@ -13,9 +13,15 @@ max_grad_norm: global-norm clipping, ``torch.nn.utils.clip_grad_norm_(model.para
 over every parameter group, on the mean gradient over ranks.  ``step()`` then copies (and all-reduces) every group's gradient
 first, computes one norm over all groups' flat gradients on the GPU and updates every group with the same coefficient, which the
 AdamW launch applies: ``p.grad`` keeps the unclipped gradient (clip_grad_norm_ clips it in place).  ``last_grad_norm`` is the
-pre-clip norm of the latest step, a device scalar."""
+pre-clip norm of the latest step, a device scalar.
+
+ema_decay (with ema_warmup): an exponential moving average of the weights, one flat buffer per parameter group, moved on inside the
+AdamW launch by the group's own step count (the recurrence of ``AveragedModel(model, multi_avg_fn=get_ema_multi_avg_fn(d))``
+updated after every ``step()``).  ``with optimizer.ema_weights():`` swaps the weights with their average for evaluation, sampling
+or ``model.state_dict()``; ``state_dict()`` carries the averages under a top-level ``"ema"`` key (only when on)."""
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import Optional
 
@@ -60,6 +66,7 @@ class _Flat:
         self.hyper = torch.zeros(5, dtype=torch.float32, device=device)
         self.hyper_host = None
         self.gviews = [self.g[o:o + p.numel()].view(p.shape) for o, p in zip(self.offsets, params)]
+        self.ema = self.ema_hyper = None                         # AdamW(ema_decay=...): the moving average of flat, {decay, warmup}
 
     def view(self, buf, i, p):
         return buf[self.offsets[i]:self.offsets[i] + p.numel()].view(p.shape)
@@ -67,8 +74,12 @@ class _Flat:
 
 class AdamW(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, *, process_group=None, world_size: int = 1,
-                 max_grad_norm: Optional[float] = None):
+                 max_grad_norm: Optional[float] = None, ema_decay: Optional[float] = None, ema_warmup: bool = False):
         self.max_grad_norm = None if max_grad_norm is None else check_max_grad_norm(max_grad_norm)
+        self.ema_decay = ops.check_ema_options(ema_decay, ema_warmup)
+        self.ema_warmup = bool(ema_warmup)
+        self._ema_hyper = {}            # device -> {decay, warmup} there, made with the first flat group on that device
+        self._in_ema = False
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.process_group, self.world_size = process_group, int(world_size)
         self._flat = {}
@@ -97,11 +108,60 @@ class AdamW(torch.optim.Optimizer):
                 j = carry[id(p)]
                 fl.view(fl.m, i, p).copy_(old.m[old.offsets[j]:old.offsets[j] + p.numel()].view(p.shape))
                 fl.view(fl.v, i, p).copy_(old.v[old.offsets[j]:old.offsets[j] + p.numel()].view(p.shape))
+        if self.ema_decay is not None:
+            fl.ema = fl.flat.clone()                             # defined before the first step, which overwrites it (step word 0)
+            if old is not None and old.ema is not None:          # the set of trained parameters changed: keep their averages
+                for i, p in enumerate(params):
+                    if id(p) in carry:
+                        j = carry[id(p)]
+                        fl.view(fl.ema, i, p).copy_(old.ema[old.offsets[j]:old.offsets[j] + p.numel()].view(p.shape))
+            if dev not in self._ema_hyper:
+                self._ema_hyper[dev] = ops.new_ema_hyper(self.ema_decay, self.ema_warmup, dev)
+            fl.ema_hyper = self._ema_hyper[dev]
         self._flat[gi] = fl
         return fl
 
+    def _ema_kw(self, fl: _Flat) -> dict:
+        """what step() adds to its ops.adamw_step call: nothing without ema_decay, where the call is the one it always was"""
+        return {} if fl.ema is None else {"ema": fl.ema, "ema_hyper": fl.ema_hyper}
+
+    def set_ema_decay(self, decay: float) -> None:
+        if self.ema_decay is None:
+            raise RuntimeError("set_ema_decay: this optimizer was built without a moving average (AdamW(..., ema_decay=...))")
+        d = ops.check_ema_options(decay, self.ema_warmup)
+        if d is None:
+            raise ValueError("set_ema_decay: the decay must be a number in (0, 1)")
+        self.ema_decay = d
+        for t in self._ema_hyper.values():
+            t[0:1].fill_(d)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """`with optimizer.ema_weights():` -- the parameters hold their moving average inside (one dg_swap_f32 launch per flat
+        group on entry, one on exit: the parameters are views of the flat buffers); step(), state_dict() and load_state_dict()
+        raise RuntimeError inside.  Groups that have not taken a step yet have no average: their parameters stay as they are."""
+        if self.ema_decay is None:
+            raise RuntimeError("ema_weights: this optimizer was built without a moving average (AdamW(..., ema_decay=...))")
+        self._refuse_in_ema("ema_weights()")
+        flats = [fl for fl in self._flat.values() if fl.ema is not None]
+        for fl in flats:
+            ops.swap_(fl.flat, fl.ema)
+        self._in_ema = True
+        try:
+            yield self
+        finally:
+            self._in_ema = False
+            for fl in flats:
+                ops.swap_(fl.flat, fl.ema)
+
+    def _refuse_in_ema(self, what: str) -> None:
+        if self._in_ema:
+            raise RuntimeError(f"{what} inside `with ema_weights()`: the weights are swapped with their moving average; leave the "
+                               "context first")
+
     @torch.no_grad()
     def step(self, closure=None):
+        self._refuse_in_ema("step()")
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -111,7 +171,7 @@ class AdamW(torch.optim.Optimizer):
             for gi, group in enumerate(self.param_groups):
                 fl = self._gather(gi, group)
                 if fl is not None:
-                    ops.adamw_step(fl.flat, fl.g, fl.m, fl.v, fl.hyper, fl.t, grad_scale=scale, advance=True)
+                    ops.adamw_step(fl.flat, fl.g, fl.m, fl.v, fl.hyper, fl.t, grad_scale=scale, advance=True, **self._ema_kw(fl))
             return loss
         # clipping: every group's (all-reduced) gradient first, then ONE norm over all of them, then every group's update with it
         flats = [fl for fl in (self._gather(gi, group) for gi, group in enumerate(self.param_groups)) if fl is not None]
@@ -130,7 +190,8 @@ class AdamW(torch.optim.Optimizer):
             self._norm_work = (key, ops.grad_norm_workspace([fl.g for fl in flats], dev))
         ops.grad_norm([fl.g for fl in flats], scale, self._clip[2:3], self._clip, self._norm_work[1])
         for fl in flats:
-            ops.adamw_step(fl.flat, fl.g, fl.m, fl.v, fl.hyper, fl.t, grad_scale=scale, advance=True, clip=self._clip[1:2])
+            ops.adamw_step(fl.flat, fl.g, fl.m, fl.v, fl.hyper, fl.t, grad_scale=scale, advance=True, clip=self._clip[1:2],
+                           **self._ema_kw(fl))
         return loss
 
     def _gather(self, gi: int, group) -> Optional[_Flat]:
@@ -173,8 +234,10 @@ class AdamW(torch.optim.Optimizer):
     # import them in torch.optim.AdamW's own format (state[i] = {"step", "exp_avg", "exp_avg_sq"}) so that a resumed run keeps
     # its bias correction and moments, and a state_dict written by torch.optim.AdamW loads here (ref: src/train.py:121)
     def state_dict(self):
+        self._refuse_in_ema("state_dict()")
         sd = super().state_dict()                   # param_groups with indices; `state` is empty (nothing lives there)
         state, base = {}, 0
+        ema = {}
         for gi, group in enumerate(self.param_groups):
             fl = self._flat.get(gi)
             if fl is not None:
@@ -187,14 +250,44 @@ class AdamW(torch.optim.Optimizer):
                         continue
                     state[idx[pid]] = {"step": torch.tensor(t), "exp_avg": fl.view(fl.m, i, p).detach().clone(),
                                        "exp_avg_sq": fl.view(fl.v, i, p).detach().clone()}
+                    if fl.ema is not None:
+                        ema[idx[pid]] = fl.view(fl.ema, i, p).detach().clone()
             base += len(group["params"])
         sd["state"] = state
+        if self.ema_decay is not None:              # only when on: without it the dict is torch.optim.AdamW's, key for key
+            sd["ema"] = {"decay": self.ema_decay, "warmup": self.ema_warmup, "values": ema}
         return sd
 
     @torch.no_grad()
     def load_state_dict(self, state_dict):
+        self._refuse_in_ema("load_state_dict()")
         state = state_dict.get("state", {})
+        ema = state_dict.get("ema")
+        if (ema is not None) != (self.ema_decay is not None):
+            raise ValueError(f"optimizer state: ema differs: saved {'present' if ema is not None else None!r}, this optimizer has "
+                             f"ema_decay = {self.ema_decay!r}")
+        if ema is not None:
+            for k in ("decay", "warmup", "values"):
+                if k not in ema:
+                    raise ValueError(f"optimizer state: missing key ema.{k}")
+            decay = ops.check_ema_options(ema["decay"], bool(ema["warmup"]))
+            if decay is None or sorted(int(i) for i in ema["values"]) != sorted(int(i) for i in state):
+                raise ValueError("optimizer state: ema.values must hold one average per parameter that has Adam moments")
+            # what the loop below refuses, found before the file's decay is taken over: a refused load leaves the options as they were
+            base = 0
+            for group in self.param_groups:
+                idx = [base + j for j in range(len(group["params"])) if (base + j) in state]
+                if any(not group["params"][i - base].is_cuda for i in idx):
+                    raise RuntimeError("drakegpt_amd.optim.AdamW updates GPU parameters only (no CPU path)")
+                steps = sorted({int(float(state[i]["step"])) for i in idx})
+                if len(steps) > 1:
+                    raise ValueError("drakegpt_amd.optim.AdamW keeps ONE step count per parameter group; the state holds " + str(steps))
+                base += len(group["params"])
         super().load_state_dict({"state": {}, "param_groups": state_dict["param_groups"]})
+        if ema is not None:
+            self.ema_decay, self.ema_warmup = decay, bool(ema["warmup"])
+            for t in self._ema_hyper.values():
+                t.copy_(torch.tensor([decay, 1.0 if self.ema_warmup else 0.0], dtype=torch.float32))
         base = 0
         for gi, group in enumerate(self.param_groups):
             have = [(j, p) for j, p in enumerate(group["params"]) if (base + j) in state]
@@ -209,6 +302,8 @@ class AdamW(torch.optim.Optimizer):
                     st = state[base + j]
                     fl.view(fl.m, i, p).copy_(st["exp_avg"].to(p.device, torch.float32))
                     fl.view(fl.v, i, p).copy_(st["exp_avg_sq"].to(p.device, torch.float32))
+                    if ema is not None:
+                        fl.view(fl.ema, i, p).copy_(ema["values"][base + j].to(p.device, torch.float32))
                     steps.add(int(float(st["step"])))
                 if len(steps) != 1:
                     raise ValueError("drakegpt_amd.optim.AdamW keeps ONE step count per parameter group; the state holds " + str(sorted(steps)))

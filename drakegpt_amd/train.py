@@ -22,11 +22,15 @@ Added beside the reference's loop, all off by default: --grad-clip, --accum-step
 --warmup-steps / --min-lr / --no-decay: a rate per optimizer step over --iters steps (looked up on the GPU from a table on the
 engine path, set as group["lr"] on the autograd path) and parameters kept out of weight decay.  The default `reference`
 schedule is the CyclicLR stepped at evaluations described above.  --label-smoothing / --z-loss set the training objective
-(inside the loss-head kernels, both paths); evaluation lines keep the plain cross entropy.
+(inside the loss-head kernels, both paths); evaluation lines keep the plain cross entropy.  --ema-decay [--ema-warmup] keeps an
+exponential moving average of the weights inside the AdamW launch (both paths): every evaluation line gains val_loss_ema (the
+averaged weights on val_loss's own batches), the final sample is drawn from the average and it is saved as <name>.ema.pt beside
+the raw checkpoint.
 """
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import math
 import os
@@ -40,7 +44,7 @@ from . import dist as ddist
 from . import schedules
 from .config import DRAKE_VOCAB_SIZE, PARAMS, PRESETS, SCALE_PARAMS, TRAIN
 from .model import MODEL_CLASSES, model_params
-from .ops import check_loss_options
+from .ops import check_ema_options, check_loss_options
 from .optim import check_accum_steps
 from .preprocessing import draw_offsets, encode_text, get_mapper, load_train_val_data, split_train_val
 
@@ -99,22 +103,35 @@ def cyclic_lr(step_count: int, base_lr: float, max_lr: float, step_size_up: int 
 
 
 @torch.no_grad()
-def evaluate_loss(train_data, val_data, model, eval_iters, context_length, batch_size, device, engine=None, generator=None):
-    """ref: src/train.py:61-75.  `model` must be in eval mode; batches are drawn as get_batch does."""
+def evaluate_loss(train_data, val_data, model, eval_iters, context_length, batch_size, device, engine=None, generator=None,
+                  drawn=None, offsets=None):
+    """ref: src/train.py:61-75.  `model` must be in eval mode; batches are drawn as get_batch does.
+    drawn: a dict that receives the window offsets of every split, [eval_iters, batch_size].  offsets: such a dict -- the splits
+    it names are evaluated, on those offsets, and nothing is drawn (--ema-decay: the averaged weights on val_loss's batches)."""
     from . import ops
     out = {}
     for name, data in (("train", train_data), ("val", val_data)):
+        if offsets is not None and name not in offsets:
+            continue
+        given = None if offsets is None else offsets[name]
         if engine is not None and data.is_cuda:
             # same draws in the same order as the loop below, staged once; the engine replays a captured forward per batch
-            offs = torch.stack([draw_offsets(len(data), context_length, batch_size, generator) for _ in range(eval_iters)])
+            offs = given if given is not None else torch.stack([draw_offsets(len(data), context_length, batch_size, generator)
+                                                                for _ in range(eval_iters)])
+            if drawn is not None:
+                drawn[name] = offs
             out[name] = engine.eval_losses(data, offs.to(device)).mean().cpu()
             continue
         losses = torch.zeros(eval_iters)
+        rows = []
         for it in range(eval_iters):
-            ix = draw_offsets(len(data), context_length, batch_size, generator).to(device)
+            rows.append(given[it] if given is not None else draw_offsets(len(data), context_length, batch_size, generator))
+            ix = rows[-1].to(device)
             x, y = ops.batch_gather(data, ix, context_length)
             loss = engine.eval_loss(x, y) if engine is not None else model(x, y)[1]
             losses[it] = loss.item()
+        if drawn is not None:
+            drawn[name] = torch.stack(rows)
         out[name] = losses.mean()
     return out
 
@@ -217,6 +234,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--z-loss", type=float, default=0.0, metavar="Z",
                     help="add Z * logsumexp(logits)^2 per row to the training objective (default 0: off; not with the fp8 loss head: "
                     "--precision fp8 at a large vocabulary)")
+    ap.add_argument("--ema-decay", type=float, default=None, metavar="D",
+                    help="keep an exponential moving average of the weights, ema += (w - ema) * (1 - D) after every optimizer step, "
+                    "in (0, 1) (default: off).  Evaluation lines gain val_loss_ema, the final sample is drawn from the average and "
+                    "it is saved as <name>.ema.pt beside the checkpoint")
+    ap.add_argument("--ema-warmup", action="store_true", help="with --ema-decay: step s averages with min(D, (s + 1) / (s + 10))")
     ap.add_argument("--save-every", type=int, default=None, metavar="N",
                     help="write the full training state (weights, optimizer, counters, generator: everything --resume needs) after "
                     "the evaluation of every N-th iteration and after the last one; N must be a multiple of --eval-interval "
@@ -242,6 +264,10 @@ def parse_args(argv=None):
         args.label_smoothing, args.z_loss = check_loss_options(args.label_smoothing, args.z_loss)
     except ValueError as e:
         ap.error(f"--label-smoothing / --z-loss: {e}")
+    try:
+        args.ema_decay = check_ema_options(args.ema_decay, args.ema_warmup)
+    except ValueError as e:
+        ap.error(f"--ema-decay / --ema-warmup: {e}")
     if args.save_every is not None and (args.save_every < 1 or args.save_every % args.eval_interval):
         ap.error(f"--save-every {args.save_every} must be a positive multiple of --eval-interval {args.eval_interval} (offsets are "
                  "staged per evaluation interval: the state is written between two stages)")
@@ -267,12 +293,13 @@ def run_args(args, K: int, world: int) -> dict:
     return {"model": args.model, "preset": args.preset, "scale": bool(args.scale), "precision": args.precision, "accum_steps": K,
             "world_size": world, "lr_schedule": args.lr_schedule, "warmup_steps": int(args.warmup_steps), "min_lr": float(args.min_lr),
             "no_decay": list(args.no_decay), "label_smoothing": float(args.label_smoothing), "z_loss": float(args.z_loss),
+            "ema_decay": None if args.ema_decay is None else float(args.ema_decay), "ema_warmup": bool(args.ema_warmup),
             # the table's length: the step count the schedule was laid out over
             "schedule_iters": None if args.lr_schedule == "reference" else int(args.iters)}
 
 
 RUN_ARG_DEFAULTS = {"lr_schedule": "reference", "warmup_steps": 0, "min_lr": 0.0, "no_decay": [], "schedule_iters": None,
-                    "label_smoothing": 0.0, "z_loss": 0.0}
+                    "label_smoothing": 0.0, "z_loss": 0.0, "ema_decay": None, "ema_warmup": False}
 
 
 def save_run_state(path: str, *, next_iteration: int, sched_steps: int, must_match: dict, model, engine=None, optimizer=None,
@@ -360,7 +387,8 @@ def main(argv=None):
         from .engine import TrainEngine
         engine = TrainEngine(model, B, T, lr=base_lr, betas=params["betas"], seed=42, rank=rank, world_size=world, process_group=pg,
                              max_grad_norm=args.grad_clip, accum_steps=K, lr_schedule=table, no_decay=args.no_decay,
-                             label_smoothing=args.label_smoothing, z_loss=args.z_loss)
+                             label_smoothing=args.label_smoothing, z_loss=args.z_loss,
+                             **({} if args.ema_decay is None else {"ema_decay": args.ema_decay, "ema_warmup": args.ema_warmup}))
         engine.set_corpus(train_dev)
     else:
         # the five earlier-stage models train through the autograd path; their flat-buffer AdamW all-reduces the gradient
@@ -370,7 +398,8 @@ def main(argv=None):
         if args.no_decay:
             groups = no_decay_groups(model, args.no_decay)
         optimizer = AdamW(groups, lr=base_lr, betas=params["betas"], process_group=pg, world_size=world,
-                          max_grad_norm=args.grad_clip)
+                          max_grad_norm=args.grad_clip,
+                          **({} if args.ema_decay is None else {"ema_decay": args.ema_decay, "ema_warmup": args.ema_warmup}))
         if table is not None:
             table = schedules.as_table(table).tolist()          # the fp32 values the engine's table would hold
 
@@ -400,6 +429,8 @@ def main(argv=None):
         save_run_state(args.state_path, next_iteration=next_it, sched_steps=sched["steps"], must_match=must_match, model=model,
                        engine=engine, optimizer=None if engine is not None else optimizer, rank=rank, world=world)
 
+    averaged = (engine if engine is not None else optimizer).ema_weights if args.ema_decay is not None else None
+
     model.train()
     t0 = time.perf_counter()
 
@@ -410,7 +441,14 @@ def main(argv=None):
             # grouped dW GEMM's sticky error word costs nothing.  Raises (-> non-zero exit) if a hand-over ever timed out:
             # every weight gradient since then is suspect, and the losses would still look plausible.
             engine.check_status()
-        losses = evaluate_loss(train_dev, val_dev, model, args.eval_iters, T, B, device, engine=engine)
+        drawn = {}
+        losses = evaluate_loss(train_dev, val_dev, model, args.eval_iters, T, B, device, engine=engine, drawn=drawn)
+        if averaged is not None:
+            # the averaged weights on val_loss's own batches: nothing more is drawn from the host generator, so the run's
+            # train_loss / val_loss / lr are those of the run without --ema-decay
+            with averaged():
+                losses["val_ema"] = evaluate_loss(train_dev, val_dev, model, args.eval_iters, T, B, device, engine=engine,
+                                                  offsets={"val": drawn["val"]})["val"]
         sched["steps"] += 1
         if table is not None:
             # a per-step schedule: nothing to set here; report the rate of the next step
@@ -426,6 +464,8 @@ def main(argv=None):
             el = time.perf_counter() - t0
             line = {"step": it + 1, "train_loss": float(losses["train"]), "val_loss": float(losses["val"]), "lr": lr,
                     "tokens_per_s": (it + 1 - start) * K * B * T * world / el}
+            if averaged is not None:
+                line["val_loss_ema"] = float(losses["val_ema"])
             if args.grad_clip is not None:
                 # the last step's pre-clip norm: the evaluation has synchronised the stream already
                 line["grad_norm"] = float((engine if engine is not None else optimizer).last_grad_norm)
@@ -469,10 +509,17 @@ def main(argv=None):
         sample_kw = {}
         if (args.sampler, args.temperature, args.top_k, args.top_p, args.min_p) != ("host", 1.0, None, None, None):
             sample_kw = dict(sampler=args.sampler, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, min_p=args.min_p)
-        print(decode(model.generate(idx, max_new_tokens=args.sample, **sample_kw)[0].tolist()))
+        path = get_model_path(args.model_dir, args.model, args.scale)
+        # --ema-decay: the sample comes from the averaged weights, which are saved beside the raw checkpoint in its format
+        with (averaged() if averaged is not None else contextlib.nullcontext()):
+            print(decode(model.generate(idx, max_new_tokens=args.sample, **sample_kw)[0].tolist()))
+            if averaged is not None and not args.no_save:
+                os.makedirs(args.model_dir, exist_ok=True)
+                ema_path = path[:-len(".pt")] + ".ema.pt"
+                torch.save({k: v.detach().cpu().clone() for k, v in model.state_dict().items()}, ema_path)
+                print(f"saved {ema_path}")
         if not args.no_save:
             os.makedirs(args.model_dir, exist_ok=True)
-            path = get_model_path(args.model_dir, args.model, args.scale)
             torch.save({k: v.detach().cpu().clone() for k, v in model.state_dict().items()}, path)
             print(f"saved {path}")
     if world > 1:

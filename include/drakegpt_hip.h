@@ -512,6 +512,24 @@ int dg_adamw_step_sched(float* p, const float* g, float* m, float* v, int64_t n,
                         const uint32_t* no_decay_bits, void* shadow_bf16, int advance_step, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Exponential moving average of the weights inside the AdamW launch.
+ * dg_adamw_step_ema: dg_adamw_step_sched (same arguments, same p, m, v, shadow and state words, bit for bit, for every
+ * combination of clip_coef / lr_table / no_decay_bits) which also updates ema (n floats, 16-byte aligned) from the weight the
+ * same thread has just stored.  ema_hyper = device fp32 {decay, warmup}, read from device memory (a captured graph picks up a
+ * new decay without recapture).  With s the step word the launch reads (before any advance):
+ *     d_s = decay, or, if warmup != 0, min(decay, ((float)s + 1) / ((float)s + 10))          w = 1.0f - d_s
+ *     s == 0:  ema[i] = p_new[i]                         (ema is not read: it may hold anything)
+ *     s >  0:  ema[i] = ema[i] + (p_new[i] - ema[i]) * w (three separately rounded fp32 operations, never an FMA)
+ * One more 16 B/lane stream (8 B/param); d_s and w once per workgroup; no LDS, no further atomics.
+ * DG_ERR_ARG: what dg_adamw_step_sched refuses, a NULL ema, a NULL ema_hyper.  DG_ERR_ALIGN: also a misaligned ema.
+ * dg_swap_f32: exchanges a[0, n) and b[0, n) (two distinct buffers, both 16-byte aligned) in one streaming launch. */
+int dg_adamw_step_ema(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, uint32_t* rng_state,
+                      float grad_scale, const float* clip_coef, const float* lr_table, int64_t lr_table_len,
+                      const uint32_t* no_decay_bits, void* shadow_bf16, int advance_step, float* ema, const float* ema_hyper,
+                      void* stream);
+int dg_swap_f32(float* a, float* b, int64_t n, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Gradient accumulation -- ref: k x `(loss / k).backward()` summing into p.grad between two optimizer.step() calls.  One
  * streaming pass per micro-step over the flat fp32 gradient g[0, n) of that micro-batch:
  *   ctl (4 device uint32) = {j, k, arrival counter, 0}: j = micro-step inside the current optimizer step, k = accum_steps >= 1
