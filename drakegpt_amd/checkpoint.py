@@ -113,8 +113,9 @@ def split_param_names(names: Sequence[str], num_heads: int, head_size: int, kind
     return groups
 
 
-def _rows(t: Tensor, rows) -> Tensor:
-    return t if rows is None else t[rows[0]:rows[1]]
+def rows(t: Tensor, span) -> Tensor:
+    """the part of a region's tensor that param_region's second result names (None: all of it)"""
+    return t if span is None else t[span[0]:span[1]]
 
 
 def optimizer_state_from_regions(names: Sequence[str], regions: Dict[str, Tuple[Tensor, Tensor]], num_heads: int, head_size: int,
@@ -128,12 +129,12 @@ def optimizer_state_from_regions(names: Sequence[str], regions: Dict[str, Tuple[
     split = split_param_names(names, num_heads, head_size, no_decay) if no_decay else (list(names), [])
     state = {}
     for i, name in enumerate(split[0] + split[1]):
-        key, rows = param_region(name, num_heads, head_size)
+        key, span = param_region(name, num_heads, head_size)
         if key not in regions:
             continue
         m, v = regions[key]
-        state[i] = {"step": torch.tensor(float(step)), "exp_avg": _rows(m, rows).detach().cpu().clone(),
-                    "exp_avg_sq": _rows(v, rows).detach().cpu().clone()}
+        state[i] = {"step": torch.tensor(float(step)), "exp_avg": rows(m, span).detach().cpu().clone(),
+                    "exp_avg_sq": rows(v, span).detach().cpu().clone()}
     # the group as the installed torch writes it (its set of option keys changes between releases): ask torch itself
     dummy = [{"params": [torch.nn.Parameter(torch.zeros(1)) for _ in split[0]]}]
     if no_decay:

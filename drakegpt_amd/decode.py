@@ -21,6 +21,7 @@ import weakref
 import torch
 
 from . import ops
+from .engine import capture_after_warmup
 
 
 class DeviceDecoder:
@@ -91,27 +92,18 @@ class DeviceDecoder:
     # ------------------------------------------------------------------ capture / replay
     @torch.no_grad()
     def capture(self) -> None:
-        """capture both steps once (as TrainEngine._capture does: warm-up on a side stream first, which loads every code object and
-        fills the allocator; the state word is restored afterwards).  A warm-up step writes cache row L - 1 and ids[:, L]: both are
-        rewritten by the real step at that L before anything reads them."""
+        """capture both steps once, each after a warm-up run at its own position (engine.capture_after_warmup; the state word is put
+        back in between).  A warm-up step writes cache row L - 1 and ids[:, L]: both are rewritten by the real step at that L before
+        anything reads them."""
         if self.graphs is not None:
             return
         model = self._mref()
         graphs = []
         for L, fn in ((1, self._step_cached), (self.ctx, lambda: self._step_window(model))):
-            self.state.copy_(ops.new_rng_state(0, self.device, step=L))
-            side = torch.cuda.Stream(device=self.device)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                fn()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize(self.device)
-            self.state.copy_(ops.new_rng_state(0, self.device, step=L))
-            torch.cuda.synchronize(self.device)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                fn()
-            graphs.append(g)
+            def position(L=L):
+                self.state.copy_(ops.new_rng_state(0, self.device, step=L))
+            position()
+            graphs += capture_after_warmup(self.device, [fn], position)
         self.graphs = tuple(graphs)
 
     def step(self, cached: bool, graph: bool = True) -> None:

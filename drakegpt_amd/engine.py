@@ -2,7 +2,8 @@
 
 One step = ref: src/train.py:143-151 (get_batch -> forward -> zero_grad -> backward -> AdamW.step)
 run as hand-sequenced HIP kernels with no autograd, captured once into a hipGraph and replayed:
-Python issues the step's 100 kernel launches (L = 6) once, at capture time, and one graph launch per step afterwards.
+Python issues the step's library calls (66 for the scaled preset in bf16, L = 6: tests/golden/step_launches.json) once, at capture
+time, and one graph launch per step afterwards.
 
 MI355X-first layout (288 GB HBM: keep everything resident, nothing is re-packed per step):
   * ONE flat fp32 master buffer holds every parameter; the model's nn.Parameters (reference
@@ -21,10 +22,19 @@ MI355X-first layout (288 GB HBM: keep everything resident, nothing is re-packed 
   * data parallel: the flat gradient is all-reduced (RCCL via torch.distributed) between the
     backward graph and the optimizer graph -- or, bucketed, range by range while the next layer group's
     backward graph runs (_dp_plan); ln_f is outside the reduced range on every rank.
+
+The step is described once, by _step_programs(): the backward programs in order (_prog_fwd_bwd; or _prog_micro, accum_steps
+times; or the layer-group segments of _prog_segments), each with the exchange behind it, and the update program _prog_update.
+_run() executes that description -- the programs themselves, or their graphs' replay -- for step() and micro_step();
+_capture() warms the same programs up and captures them through capture_after_warmup(), which eval_losses and the device
+decoder use too.
 """
 from __future__ import annotations
 
 import contextlib
+import functools
+import math
+import os
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -51,17 +61,35 @@ class _Layout:
 
     def add(self, key: str, shape) -> int:
         off = self.size
-        n = 1
-        for d in shape:
-            n *= d
         self.entries[key] = (off, tuple(shape))
-        self.size = off + _round(n)
+        self.size = off + _round(math.prod(shape))
         return off
 
 
-def _os_env(name: str, default: str) -> str:
-    import os
-    return os.environ.get(name, default)
+WHOLE = "whole"     # the exchange behind a backward program: one synchronous all-reduce of the whole gradient buffer
+
+
+def capture_after_warmup(dev, progs, restore=None) -> tuple:
+    """one hipGraph per program, all in the first one's memory pool (activations may cross from one program to the next).  The
+    programs first run once on a side stream -- that loads every code object and makes every allocation a capture could not --
+    and restore(), if given, puts back what that run moved before the capture starts."""
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for prog in progs:
+            prog()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize(dev)
+    if restore is not None:
+        restore()
+        torch.cuda.synchronize(dev)
+    graphs = []
+    for prog in progs:
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, pool=graphs[0].pool() if graphs else None):
+            prog()
+        graphs.append(g)
+    return tuple(graphs)
 
 
 class ShadowWeights:
@@ -233,18 +261,17 @@ class TrainEngine:
         if self.accum > 1 and dp_buckets is not None and int(dp_buckets) > 1:
             raise ValueError("accum_steps > 1 uses one gradient exchange per optimizer step (it is amortised over the micro-steps "
                              "already): dp_buckets > 1 cannot be combined with it")
-        import os as _os
-        if logits == "auto" and _os.environ.get("DG_LOGITS") in ("fp32", "bf16"):      # A/B runs
-            logits = _os.environ["DG_LOGITS"]
-        if grad_stream == "auto" and _os.environ.get("DG_GRAD_STREAM") in ("fp32", "bf16"):
-            grad_stream = _os.environ["DG_GRAD_STREAM"]
+        env = os.environ.get
+        if logits == "auto" and env("DG_LOGITS") in ("fp32", "bf16"):      # A/B runs
+            logits = env("DG_LOGITS")
+        if grad_stream == "auto" and env("DG_GRAD_STREAM") in ("fp32", "bf16"):
+            grad_stream = env("DG_GRAD_STREAM")
         if grad_stream not in ("auto", "fp32", "bf16"):
             raise ValueError("grad_stream must be 'auto', 'fp32' or 'bf16'")
         # The gradient that flows down the residual branch (dresid -> dx of every LayerNorm backward).  bf16 / fp8 modes keep it
         # in bf16 ("auto"): it is rounded once per sub-layer like every other activation gradient of those modes, and every
         # LayerNorm backward moves 75 MB instead of 100 MB.  The forward residual stream stays fp32 in every mode.
-        _C = model.token_embedding_table.weight.shape[1]
-        _can = self.act == torch.bfloat16 and ops.layernorm_bwd_fused_supported(_C) and self.M % 64 == 0
+        _can = self.act == torch.bfloat16 and ops.layernorm_bwd_fused_supported(self.C) and self.M % 64 == 0
         if grad_stream == "bf16" and not _can:
             raise ValueError("a bf16 gradient stream needs the bf16 / fp8 precision and the fused LayerNorm backward")
         self.stream_dtype = torch.bfloat16 if (_can and grad_stream != "fp32") else torch.float32
@@ -252,9 +279,8 @@ class TrainEngine:
             raise ValueError("logits must be 'auto', 'fp32' or 'bf16'")
         # logits as bf16 (in-place gradient): by default only where they are big enough to matter -- the GPT-2 vocabulary --
         # and never in the fp32 parity mode; "fp32" keeps what the module path returns (tests compare the two)
-        V_ = model.token_embedding_table.weight.shape[0]
-        self.bf16_logits = self.act == torch.bfloat16 and 4096 < V_ <= 53248 and logits != "fp32" if logits != "bf16" else True
-        if self.bf16_logits and (self.act != torch.bfloat16 or not (4096 < V_ <= 53248)):
+        self.bf16_logits = self.act == torch.bfloat16 and 4096 < self.V <= 53248 and logits != "fp32" if logits != "bf16" else True
+        if self.bf16_logits and (self.act != torch.bfloat16 or not (4096 < self.V <= 53248)):
             raise ValueError("bf16 logits need the bf16 / fp8 precision and a vocabulary of 4097 .. 53248 (the whole-row kernel)")
         g = S.granule(self.act)
         if self.C % g or (self.NH * self.H) % g:
@@ -264,27 +290,27 @@ class TrainEngine:
         # bf16: every dW of the step comes from ONE grouped GEMM at the end of backward, written straight into the
         # flat gradient (no split-K slabs); fp32 parity mode keeps the per-matrix split-K path
         self.grouped_dw = self.act == torch.bfloat16 and self.M % 64 == 0
-        # LayerNorm inside the epilogue of the GEMM that produces its input (dg_block_chain_fwd modes 3 / 4: proj + residual + LN2,
-        # FFN2 + residual + the next block's LN1): bf16 mode at the width the kernel is built for.  OFF by default (DG_CHAIN_LN=1 turns
-        # it on): measured inside the captured step (round 3, same box) proj + LN2 24.7 us against 17.4 + 8.8, FFN2 + LN1' 44.2 us
-        # against 33.5 + 8.8, plus 7.8 us for the packed-weight refresh: 2.558 vs 2.528 ms per step (DESIGN.md section 4.5)
-        # precision "fp8": the weight gradients of the block Linears on the fp8 copies of their operands (DG_FP8_DW=0: bf16 dW, A/B)
-        self.last_block_act = _os.environ.get("DG_LAST_BLOCK_ACT", "1") != "0"      # 0: fp32 output + cast launch (A/B runs)
+        self.last_block_act = env("DG_LAST_BLOCK_ACT", "1") != "0"      # 0: fp32 output + cast launch (A/B runs)
         self.fp8_head = False       # (set in _alloc_and_adopt: precision fp8 at a large vocabulary)
-        self.fp8_dw = self.fp8 and (_os.environ.get("DG_FP8_DW", "1") != "0" if fp8_dw is None else bool(fp8_dw))
+        # precision "fp8": the weight gradients of the block Linears on the fp8 copies of their operands (DG_FP8_DW=0: bf16 dW, A/B)
+        self.fp8_dw = self.fp8 and (env("DG_FP8_DW", "1") != "0" if fp8_dw is None else bool(fp8_dw))
         # Everything between two attention calls as ONE launch per layer (dg_block_chain_fwd modes 2 / 0 / 1; forward launches per block
         # 7 -> 2): the default where the kernel exists (bf16, C = 384, M % 64 == 0); DG_CHAIN=0 keeps the separate launches (A/B).
         # Same box, headline configuration: 2.507 -> 2.403 ms per step.
-        self.chain_full = (_os.environ.get("DG_CHAIN", "1") != "0" and not self.fp8 and self.NH * self.H == self.C and self.last_block_act
+        self.chain_full = (env("DG_CHAIN", "1") != "0" and not self.fp8 and self.NH * self.H == self.C and self.last_block_act
                            and ops.block_chain_supported(self.M, self.C, self.act))
-        self.chain_warm = _os.environ.get("DG_CHAIN_WARM", "0") == "1"
+        self.chain_warm = env("DG_CHAIN_WARM", "0") == "1"
         # The same for the backward pass (dg_block_chain_bwd: dX-QKV + LayerNorm-1 backward of block l, dX-FFN2 / dX-FFN1 / LayerNorm-2
         # backward / dX-proj of block l - 1 in one launch; backward launches per block 8 -> 3).  Needs the bf16 gradient stream and one
         # gradient exchange (a chain straddles two blocks: no layer-group seams).  Opt-in (DG_CHAIN_BWD=1) until it beats the separate launches
         # inside the step (first measurement: 136 vs 128.5 us per layer).
-        self.chain_bwd = (_os.environ.get("DG_CHAIN_BWD", "0") == "1" and self.chain_full and self.stream_dtype == torch.bfloat16
+        self.chain_bwd = (env("DG_CHAIN_BWD", "0") == "1" and self.chain_full and self.stream_dtype == torch.bfloat16
                           and ops.block_chain_bwd_supported(self.M, self.C, self.act))
-        self.chain_ln = (_os.environ.get("DG_CHAIN_LN", "0") == "1" and not self.fp8 and self.NH * self.H == self.C
+        # LayerNorm inside the epilogue of the GEMM that produces its input (dg_block_chain_fwd modes 3 / 4: proj + residual + LN2,
+        # FFN2 + residual + the next block's LN1): bf16 mode at the width the kernel is built for.  OFF by default (DG_CHAIN_LN=1 turns
+        # it on): measured inside the captured step (round 3, same box) proj + LN2 24.7 us against 17.4 + 8.8, FFN2 + LN1' 44.2 us
+        # against 33.5 + 8.8, plus 7.8 us for the packed-weight refresh: 2.558 vs 2.528 ms per step (DESIGN.md section 4.5)
+        self.chain_ln = (env("DG_CHAIN_LN", "0") == "1" and not self.fp8 and self.NH * self.H == self.C
                          and ops.block_chain_supported(self.M, self.C, self.act))
         self._build_layout()
         self.dp_buckets = self._choose_buckets(self._dp_buckets_arg)
@@ -306,14 +332,14 @@ class TrainEngine:
         self.no_decay_bits = None
         if self.no_decay:
             self.no_decay_bits = ops.new_no_decay_bits(self._no_decay_ranges(), self.n_active, self.dev)
-        # what _prog_update / _prog_update_accum add to their ops.adamw_step call: nothing for an engine with neither, whose call is
-        # the one it always was, argument for argument
+        # what _prog_update adds to its ops.adamw_step call: nothing for an engine with neither, whose call is the one it always
+        # was, argument for argument
         self._sched_kw = {}
         if self.lr_table is not None or self.no_decay_bits is not None:
             self._sched_kw = {"lr_table": self.lr_table, "no_decay_bits": self.no_decay_bits}
         # ema_decay: ema = flat[0, n_active) as the launch has just written it, averaged by AdamW's own step word (opt_state under
         # accumulation: once per optimizer step); the first step overwrites it.  ema_hyper = {decay, warmup} is read on the device:
-        # set_ema_decay() writes it, captured graphs stay valid.  _ema_kw is what the two update programs add to their
+        # set_ema_decay() writes it, captured graphs stay valid.  _ema_kw is what _prog_update adds to its
         # ops.adamw_step call: nothing for an engine without it, whose call is the one it always was.
         self.ema = self.ema_hyper = None
         self._ema_kw = {}
@@ -403,7 +429,6 @@ class TrainEngine:
         when the gradient is large enough for the exchange to matter against the step -- >= 128 MB, i.e. the GPT-2 shapes
         (652 MB / 1.6 GB) -- and not for the 43 MB of the scaled model, whose whole exchange is ~0.4 ms over xGMI while every
         cut costs a graph seam and a less well filled dW launch."""
-        import os
         if self.accum > 1:
             return 1
         if arg is None and os.environ.get("DG_DP_BUCKETS"):
@@ -417,7 +442,7 @@ class TrainEngine:
     def _dp_plan(self):
         """[(layers of the group, in backward order; [(lo, hi) ranges of the flat gradient that are final after the group])].
         Region A is laid out layer 0 .. L-1 then lm_head, so a group's weight gradients are ONE contiguous range; the first group
-        also carries lm_head.weight (its dW problem is the first one recorded), the last group the biases / LayerNorm vectors
+        also carries lm_head's weight (its dW problem is the first one recorded), the last group the biases / LayerNorm vectors
         and the embeddings (B | E: contiguous, final only after the last LayerNorm backward and the embedding backward)."""
         nb, L = self.dp_buckets, self.L
         per = (L + nb - 1) // nb
@@ -440,10 +465,7 @@ class TrainEngine:
         for k in self._trained_keys():
             if CK.region_no_decay(k, self.no_decay):
                 off, shape = self._region(k)
-                n = 1
-                for d in shape:
-                    n *= d
-                out.append((off, min(_round(off + n), self.n_active)))
+                out.append((off, min(_round(off + math.prod(shape)), self.n_active)))
         return out
 
     def _region(self, key: str):
@@ -455,17 +477,11 @@ class TrainEngine:
 
     def param_view(self, key: str) -> Tensor:
         off, shape = self._region(key)
-        n = 1
-        for d in shape:
-            n *= d
-        return self.flat[off:off + n].view(shape)
+        return self.flat[off:off + math.prod(shape)].view(shape)
 
     def grad_view(self, key: str, buf: Optional[Tensor] = None) -> Tensor:
         off, shape = self._region(key)
-        n = 1
-        for d in shape:
-            n *= d
-        return (self.gflat if buf is None else buf)[off:off + n].view(shape)
+        return (self.gflat if buf is None else buf)[off:off + math.prod(shape)].view(shape)
 
     def named_grads(self) -> Dict[str, Tensor]:
         """the step's gradient as views of the flat buffer, keyed by the reference's parameter names (what `p.grad` holds after
@@ -474,26 +490,12 @@ class TrainEngine:
         accum_steps = k > 1: views of the accumulator -- the SUM over the micro-batch gradients taken so far in this optimizer
         step (all k of them after the k-th micro_step(), and over ranks after its exchange); divide by k for the mean gradient
         the optimizer applied, which is what `p.grad` holds after k x `(loss / k).backward()`."""
-        NH, H = self.NH, self.H
+        buf = self.gflat if self.accum == 1 else self.gacc
         out: Dict[str, Tensor] = {}
-        _gv = self.grad_view
-        if self.accum > 1:
-            def _gv(key):
-                return self.grad_view(key, self.gacc)
-        for l in range(self.L):
-            wqkv = _gv(f"{l}.wqkv")
-            pre = f"blocks.{l}."
-            for h in range(NH):
-                out[f"{pre}sa_head.heads.{h}.key.weight"] = wqkv[(NH + h) * H:(NH + h + 1) * H]
-                out[f"{pre}sa_head.heads.{h}.query.weight"] = wqkv[h * H:(h + 1) * H]
-                out[f"{pre}sa_head.heads.{h}.value.weight"] = wqkv[(2 * NH + h) * H:(2 * NH + h + 1) * H]
-            for ref, key in (("sa_head.proj.weight", "wproj"), ("sa_head.proj.bias", "bproj"), ("ffwd.net.0.weight", "w1"),
-                             ("ffwd.net.0.bias", "b1"), ("ffwd.net.2.weight", "w2"), ("ffwd.net.2.bias", "b2"),
-                             ("ln1.weight", "ln1w"), ("ln1.bias", "ln1b"), ("ln2.weight", "ln2w"), ("ln2.bias", "ln2b")):
-                out[pre + ref] = _gv(f"{l}.{key}")
-        out["lm_head.weight"], out["lm_head.bias"] = _gv("lm.w"), _gv("lm.b")
-        out["token_embedding_table.weight"] = _gv("tok")
-        out["position_embedding_table.weight"] = _gv("pos")
+        for name, _ in self.model.named_parameters():
+            key, rows = CK.param_region(name, self.NH, self.H)
+            if key not in CK.UNTRAINED:
+                out[name] = CK.rows(self.grad_view(key, buf), rows)
         return out
 
     def _alloc_and_adopt(self):
@@ -503,7 +505,8 @@ class TrainEngine:
         self.gflat = torch.zeros(self.n_active, dtype=torch.float32, device=dev)
         self.m_ = torch.zeros(self.n_active, dtype=torch.float32, device=dev)
         self.v_ = torch.zeros(self.n_active, dtype=torch.float32, device=dev)
-        self.tn_workspaces: Dict[int, Tensor] = {}      # split-K workspace of the grouped dW GEMM, one per launch group
+        # split-K workspaces of the grouped dW GEMM, one per (launch group, kind: bf16 / fp8 operands)
+        self.tn_workspaces: Dict[Tuple[int, int], Tensor] = {}
         self.small_dw: Dict[str, Tuple[Tensor, int]] = {}
         # one-hot rows of the batch (bf16 [M, V rounded up to 8]): rewritten by every forward, read by the grouped dW GEMM
         self.onehot = None
@@ -523,35 +526,12 @@ class TrainEngine:
         if self.chain_bwd:
             self.Gv = max(self.Gv, 2 * (self.M // 64))            # dg_block_chain_bwd: two partial rows per 64-row block
         self.vparts = torch.zeros((self.Gv, self.layB.size), dtype=torch.float32, device=dev)
-        NH, H = self.NH, self.H
-
-        def adopt(param: torch.nn.Parameter, view: Tensor):
-            view.copy_(param.data)
-            param.data = view
-
         with torch.no_grad():
-            for l, blk in enumerate(m.blocks):
-                wqkv = self.param_view(f"{l}.wqkv")
-                for h, head in enumerate(blk.sa_head.heads):
-                    adopt(head.query.weight, wqkv[h * H:(h + 1) * H])
-                    adopt(head.key.weight, wqkv[(NH + h) * H:(NH + h + 1) * H])
-                    adopt(head.value.weight, wqkv[(2 * NH + h) * H:(2 * NH + h + 1) * H])
-                adopt(blk.sa_head.proj.weight, self.param_view(f"{l}.wproj"))
-                adopt(blk.sa_head.proj.bias, self.param_view(f"{l}.bproj"))
-                adopt(blk.ffwd.net[0].weight, self.param_view(f"{l}.w1"))
-                adopt(blk.ffwd.net[0].bias, self.param_view(f"{l}.b1"))
-                adopt(blk.ffwd.net[2].weight, self.param_view(f"{l}.w2"))
-                adopt(blk.ffwd.net[2].bias, self.param_view(f"{l}.b2"))
-                adopt(blk.ln1.weight, self.param_view(f"{l}.ln1w"))
-                adopt(blk.ln1.bias, self.param_view(f"{l}.ln1b"))
-                adopt(blk.ln2.weight, self.param_view(f"{l}.ln2w"))
-                adopt(blk.ln2.bias, self.param_view(f"{l}.ln2b"))
-            adopt(m.lm_head.weight, self.param_view("lm.w"))
-            adopt(m.lm_head.bias, self.param_view("lm.b"))
-            adopt(m.token_embedding_table.weight, self.param_view("tok"))
-            adopt(m.position_embedding_table.weight, self.param_view("pos"))
-            adopt(m.ln_f.weight, self.param_view("lnf.w"))
-            adopt(m.ln_f.bias, self.param_view("lnf.b"))
+            for name, param in m.named_parameters():
+                key, rows = CK.param_region(name, self.NH, self.H)
+                view = CK.rows(self.param_view(key), rows)
+                view.copy_(param.data)
+                param.data = view
         # GEMM operand shadows
         self.weights = ShadowWeights()
         self.shadow = None
@@ -568,7 +548,7 @@ class TrainEngine:
             self.wt8_flat = torch.zeros(self.wt_flat.numel(), dtype=S.E4M3, device=dev)
             # lm_head joins when its two contraction lengths suit the fp8 K step: K = C forward, K = V padded (50257 -> 50304 = 393 x
             # 128) in the dX direction; a char-level vocabulary (80 -> 128 columns of padding) stays bf16
-            self.fp8_head = (_os_env("DG_FP8_HEAD", "1") != "0" and self.bf16_logits and S.fp8_k_ok(self.C) and S.fp8_k_ok(S.k_pad(self.V, self.act))
+            self.fp8_head = (os.environ.get("DG_FP8_HEAD", "1") != "0" and self.bf16_logits and S.fp8_k_ok(self.C) and S.fp8_k_ok(S.k_pad(self.V, self.act))
                              and self.last_block_act)
             n_fp8 = sum(1 for key in self.layA.entries if key != "lm.w" or self.fp8_head)
             self.wscale_f = torch.ones(n_fp8, dtype=torch.float32, device=dev)
@@ -578,7 +558,7 @@ class TrainEngine:
         self._pack_pairs = []
         self._packT_pairs = []
         self._u8_pairs = []
-        self.fp8_wt8 = self.fp8 and _os_env("DG_FP8_WT8", "1") != "0"
+        self.fp8_wt8 = self.fp8 and os.environ.get("DG_FP8_WT8", "1") != "0"
         for key, (off, shape) in self.layA.entries.items():
             W = self.param_view(key)
             n = shape[0] * shape[1]
@@ -876,14 +856,6 @@ class TrainEngine:
             ops.reduce_partials(self.slabs, self.layA.size, self.S, self.gflat[self.offA:], self.layA.size)
         ops.reduce_partials(self.vparts, self.layB.size, self.Gv, self.gflat[self.offB:], self.layB.size)
 
-    def _backward(self, run: S.Run, x_idx: Tensor, ctx):
-        st = self._backward_begin(run, x_idx, ctx)
-        if self.chain_bwd and x_idx.numel() == self.M:
-            self._backward_layers_chain(st)
-        else:
-            self._backward_layers(st, reversed(range(self.L)))
-        self._backward_end(st)
-
     def _train_run(self) -> S.Run:
         """per-step runtime configuration of the training program.  fp8: every quantisation site keeps its amax history in
         self.fp8_sites (one-pass delayed scaling); the first execution (the eager warm-up before capture, or the first eager
@@ -893,47 +865,45 @@ class TrainEngine:
             self._fp8_seeded = True
         return S.Run(act=self.act, rng=self.state if self.p_drop > 0.0 else None, weights=self.weights, fp8=self.fp8, split=self.split_bf16,
                      fp8_sites=self.fp8_sites if self.fp8 else None, fp8_seed=seed, step_word=self.state, stream=self.stream_dtype,
-                     fp8_only=self.fp8 and self.fp8_dw and self.grouped_dw and _os_env("DG_FP8_ONLY", "1") != "0")
+                     fp8_only=self.fp8 and self.fp8_dw and self.grouped_dw and os.environ.get("DG_FP8_ONLY", "1") != "0")
 
-    def _prog_fwd_bwd(self):
-        """gather the batch, forward, backward, reduce the gradient partials"""
+    def _prog_front(self) -> dict:
+        """gather the batch, forward, the loss, lm_head's backward: the step up to the backward pass of the residual blocks"""
         run = self._train_run()
         logits, rows, ctx = self._forward(run, self.x, self.y, True, gather=self.corpus is not None)
         if self.keep_logits:
             self.last_logits = logits
         if len(ctx) == 3:
             ops.reduce_sum(rows, 1.0 / self.M, out=self.loss)
-        self._backward(run, self.x, ctx)
+        return self._backward_begin(run, self.x, ctx)
+
+    def _prog_fwd_bwd(self):
+        """gather the batch, forward, backward, reduce the gradient partials"""
+        st = self._prog_front()
+        if self.chain_bwd:
+            self._backward_layers_chain(st)
+        else:
+            self._backward_layers(st, reversed(range(self.L)))
+        self._backward_end(st)
 
     def _prog_segments(self):
-        """the same step cut at the layer-group boundaries of _dp_plan(): segment k ends with the grouped dW launch of its
-        group, after which the group's range of the flat gradient is final and its all-reduce can start"""
+        """[(segment, ranges)]: the same step cut at the layer-group boundaries of _dp_plan().  Segment k ends with the grouped dW
+        launch of its group, after which the group's ranges of the flat gradient are final and their all-reduce can start"""
         plan = self._dp_plan()
         st = {}
 
-        def first():
-            run = self._train_run()
-            logits, rows, ctx = self._forward(run, self.x, self.y, True, gather=self.corpus is not None)
-            if self.keep_logits:
-                self.last_logits = logits
-            if len(ctx) == 3:
-                ops.reduce_sum(rows, 1.0 / self.M, out=self.loss)
-            st.clear()
-            st.update(self._backward_begin(run, self.x, ctx))
+        def seg(k, layers):
+            if k == 0:
+                st.clear()
+                st.update(self._prog_front())
+            self._backward_layers(st, layers)
+            if k == len(plan) - 1:
+                self._backward_end(st, group=k)
+                st.clear()                      # release the activations (they live in the graph pool anyway)
+            else:
+                st["sink"].flush(k)
 
-        segs = []
-        for k, (layers, _) in enumerate(plan):
-            def seg(k=k, layers=layers):
-                if k == 0:
-                    first()
-                self._backward_layers(st, layers)
-                if k == len(plan) - 1:
-                    self._backward_end(st, group=k)
-                    st.clear()                      # release the activations (they live in the graph pool anyway)
-                else:
-                    st["sink"].flush(k)
-            segs.append(seg)
-        return segs, [r for _, r in plan]
+        return [(functools.partial(seg, k, layers), ranges) for k, (layers, ranges) in enumerate(plan)]
 
     def _prog_micro(self):
         """accum_steps > 1: one micro-batch -- the step's forward / backward, then its gradient and loss into the accumulators; that
@@ -941,130 +911,120 @@ class TrainEngine:
         self._prog_fwd_bwd()
         ops.grad_accumulate(self.gacc, self.gflat, self.n_active, self.acc_ctl, self.loss, self.loss_acc, self.state)
 
-    def _prog_update_accum(self):
-        """accum_steps = k > 1: _prog_update on the accumulated gradient -- norm and AdamW on gacc * 1 / (k * world), the mean over
-        micro-batches and ranks, with the optimizer's own step counter as t"""
-        scale = 1.0 / (self.accum * self.world)
-        if self.clip_state is None:
-            ops.adamw_step(self.flat, self.gacc, self.m_, self.v_, self.hyper, self.opt_state, scale,
-                           shadow_bf16=self.shadow, n=self.n_active, advance=True, **self._sched_kw, **self._ema_kw)
-        else:
-            ops.grad_norm(self.gacc, scale, self.clip_state[2:3], self.clip_state, self.norm_work)
-            ops.adamw_step(self.flat, self.gacc, self.m_, self.v_, self.hyper, self.opt_state, scale,
-                           shadow_bf16=self.shadow, n=self.n_active, advance=True, clip=self.clip_state[1:2], **self._sched_kw,
-                           **self._ema_kw)
-        self._refresh_transposes()
-
     def _prog_update(self):
-        # (the step word moves on inside the AdamW launch: nothing after it reads the word)
-        if self.clip_state is None:
-            ops.adamw_step(self.flat, self.gflat, self.m_, self.v_, self.hyper, self.state, 1.0 / self.world,
-                           shadow_bf16=self.shadow, n=self.n_active, advance=True, **self._sched_kw, **self._ema_kw)
-        else:
-            # the gradient is final here on every path (the data-parallel optimizer graph runs after the exchange): norm of the mean
-            # over ranks, then AdamW on g * coef.  The alignment gaps of gflat are zero (no producer writes them), so the norm
-            # over the whole active range is the norm over the parameters.
-            ops.grad_norm(self.gflat, 1.0 / self.world, self.clip_state[2:3], self.clip_state, self.norm_work)
-            ops.adamw_step(self.flat, self.gflat, self.m_, self.v_, self.hyper, self.state, 1.0 / self.world,
-                           shadow_bf16=self.shadow, n=self.n_active, advance=True, clip=self.clip_state[1:2], **self._sched_kw,
-                           **self._ema_kw)
+        """norm (if clipping), AdamW, W^T refresh.  The gradient is final here on every path (the data-parallel update runs after
+        the exchange): gflat * 1 / world, the mean over ranks, with the step word as t -- or, accum_steps = k > 1, gacc * 1 /
+        (k * world), the mean over micro-batches and ranks, with the optimizer's own counter.  The word moves on inside the AdamW
+        launch: nothing after it reads the word."""
+        grad, word = (self.gflat, self.state) if self.accum == 1 else (self.gacc, self.opt_state)
+        scale = 1.0 / (self.accum * self.world)
+        clip = {}
+        if self.clip_state is not None:
+            # AdamW on g * coef.  The alignment gaps of the gradient buffer are zero (no producer writes them), so the norm over
+            # the whole active range is the norm over the parameters.
+            ops.grad_norm(grad, scale, self.clip_state[2:3], self.clip_state, self.norm_work)
+            clip = {"clip": self.clip_state[1:2]}
+        ops.adamw_step(self.flat, grad, self.m_, self.v_, self.hyper, word, scale, shadow_bf16=self.shadow, n=self.n_active,
+                       advance=True, **clip, **self._sched_kw, **self._ema_kw)
         self._refresh_transposes()
 
+    # -------------------------------------------------------------------------------- the step: description, capture, run
     def _dp(self) -> bool:
         return self.world > 1 or self.force_dp_path
 
-    def _allreduce(self):
-        if self._dp():
-            import torch.distributed as dist
-            # mean = sum * 1/world in AdamW (accum_steps > 1: the accumulated gradient, once per optimizer step)
-            dist.all_reduce(self.gflat if self.accum == 1 else self.gacc, op=dist.ReduceOp.SUM, group=self.pg)
+    def _step_programs(self):
+        """the optimizer step as ([(backward program, the exchange behind it)], update program).  The exchange is None, WHOLE, or
+        the [(lo, hi)] ranges of the flat gradient a layer group has finished (all-reduced asynchronously beside the next group).
+        accum_steps = k: the micro program k times, the exchange behind the last.  Everything that runs a step -- eagerly, as the
+        warm-up before capture, to seed the fp8 histories, captured -- runs this."""
+        if self._dp() and self.dp_buckets > 1:
+            backward = self._prog_segments()
+        elif self.accum > 1:
+            backward = [(self._prog_micro, None)] * (self.accum - 1) + [(self._prog_micro, WHOLE)]
+        else:
+            backward = [(self._prog_fwd_bwd, WHOLE)]
+        return backward, self._prog_update
 
-    def _allreduce_ranges_async(self, ranges, works: list) -> None:
-        """start the SUM all-reduce of finished ranges of the flat gradient.  RCCL enqueues it on its own stream behind the work
-        already submitted to the current stream (the segment that produced the ranges) and it then runs beside the next
-        segment; `works` are joined before the optimizer graph."""
-        if self._dp():
-            import torch.distributed as dist
-            for lo, hi in ranges:
-                works.append(dist.all_reduce(self.gflat[lo:hi], op=dist.ReduceOp.SUM, group=self.pg, async_op=True))
-
-    # -------------------------------------------------------------------------------- capture
-    def _capture_accum(self):
-        """accum_steps > 1: one micro graph and one update graph in the same pool; the warm-up runs each program once and every
-        buffer and counter it moves is put back"""
-        bufs = (self.flat, self.m_, self.v_, self.state, self.gacc, self.acc_ctl, self.opt_state, self.loss_acc)
-        if self.ema is not None:
-            bufs += (self.ema,)
+    def _snapshot(self):
+        """copy every buffer and counter the step's programs move; returns the call that puts them back"""
+        bufs = [self.flat, self.m_, self.v_, self.state]
+        bufs += [b for b in (self.ema, self.gacc, self.acc_ctl, self.opt_state, self.loss_acc) if b is not None]
         snap = [b.clone() for b in bufs]
-        hist = self._fp8_snapshot()
-        j = self._j
-        side = torch.cuda.Stream(device=self.dev)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):       # warm-up: loads every code object and allocates the dW workspaces before capture
-            self._prog_micro()
-            self._prog_update_accum()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize(self.dev)
-        for b, s in zip(bufs, snap):
-            b.copy_(s)
-        self._fp8_put_back(hist)
-        self._j = j
-        self.refresh_shadows()
-        torch.cuda.synchronize(self.dev)
-        g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g1):
-            self._prog_micro()
-        with torch.cuda.graph(g2, pool=g1.pool()):
-            self._prog_update_accum()
-        self._graphs = (g1, g2)
+
+        def put_back():
+            for b, c in zip(bufs, snap):
+                b.copy_(c)
+        return put_back
 
     def _capture(self):
-        snap = (self.flat.clone(), self.m_.clone(), self.v_.clone(), self.state.clone())
-        ema_snap = None if self.ema is None else self.ema.clone()
-        hist = self._fp8_snapshot()
-        side = torch.cuda.Stream(device=self.dev)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):       # warm-up: loads every code object and allocates the dW workspaces before capture
-            if self._dp() and self.dp_buckets > 1:
-                for seg in self._prog_segments()[0]:
-                    seg()
-            else:
-                self._prog_fwd_bwd()
-            self._prog_update()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize(self.dev)
-        self.flat.copy_(snap[0]); self.m_.copy_(snap[1]); self.v_.copy_(snap[2]); self.state.copy_(snap[3])
-        if ema_snap is not None:
-            self.ema.copy_(ema_snap)
-        self._fp8_put_back(hist)
-        self.refresh_shadows()
-        torch.cuda.synchronize(self.dev)
-        if not self._dp():
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._prog_fwd_bwd()
-                self._prog_update()
-            self._graphs = (g,)
-        elif self.dp_buckets > 1:
-            # one graph per layer group + the optimizer graph, all in one memory pool (activations cross the seams)
-            segs, self._seg_ranges = self._prog_segments()
-            graphs = []
-            for seg in segs:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=graphs[0].pool() if graphs else None):
-                    seg()
-                graphs.append(g)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=graphs[0].pool()):
-                self._prog_update()
-            self._graphs = tuple(graphs) + (g,)
+        """one graph per distinct program of the step, all in one pool (the multi-rank step and accumulation: the exchange runs
+        between replays) -- or the whole step in ONE graph: a single process with accum_steps 1.  The warm-up runs every program
+        once, in step order; what it moved is put back before the capture.  Sets _graphs and _replay: the step description with
+        every program replaced by its graph's replay (the one-graph step: no backward stages, the whole step in the update slot)."""
+        backward, update = self._step_programs()
+        progs = list(dict.fromkeys(p for p, _ in backward)) + [update]
+        one_graph = not self._dp() and self.accum == 1
+        if one_graph:
+            def whole_step(parts=tuple(progs)):
+                for p in parts:
+                    p()
+            progs = [whole_step]
+        put_back, hist = self._snapshot(), self._fp8_snapshot()
+
+        def restore():
+            put_back()
+            self._fp8_put_back(hist)
+            self.refresh_shadows()
+
+        self._graphs = capture_after_warmup(self.dev, progs, restore)
+        if one_graph:
+            self._replay = [], self._graphs[0].replay
         else:
-            g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g1):
-                self._prog_fwd_bwd()
-            with torch.cuda.graph(g2, pool=g1.pool()):
-                self._prog_update()
-            self._graphs = (g1, g2)
+            replay = dict(zip(progs, (g.replay for g in self._graphs)))
+            self._replay = [(replay[p], exchange) for p, exchange in backward], replay[update]
+
+    def _exchange(self, exchange, works: list) -> None:
+        """the SUM all-reduce behind a backward program; the mean is the 1 / world inside AdamW.  WHOLE: the whole gradient buffer
+        (accum_steps > 1: the accumulated gradient, once per optimizer step), synchronously.  Ranges: each one asynchronously --
+        RCCL enqueues it on its own stream behind the work already submitted to the current stream (the segment that produced
+        the ranges) and it then runs beside the next segment; `works` are joined before the update."""
+        import torch.distributed as dist
+        if exchange is WHOLE:
+            dist.all_reduce(self.gflat if self.accum == 1 else self.gacc, op=dist.ReduceOp.SUM, group=self.pg)
+        else:
+            for lo, hi in exchange:
+                works.append(dist.all_reduce(self.gflat[lo:hi], op=dist.ReduceOp.SUM, group=self.pg, async_op=True))
+
+    def _run(self, lo: Optional[int] = None, hi: Optional[int] = None) -> None:
+        """run the backward stages [lo, hi) of the step (default: all of them) -- the programs themselves, or (use_graph) their
+        graphs' replay -- and, behind the step's last stage, the exchange's join and the update"""
+        if not self.use_graph:
+            backward, update = self._step_programs()
+        else:
+            if self._graphs is None:
+                self._capture()
+            backward, update = self._replay
+        stages = backward[lo:hi]
+        last = hi is None or hi >= len(backward)
+        dp = last and self._dp()
+        whole = dp and stages[-1][1] is WHOLE           # (only ever behind the step's last backward stage)
+        ev = self._timing_events(3) if (dp and self.use_graph and self.accum == 1) else None
+        works = []
+        for prog, exchange in stages:
+            prog()
+            if dp and isinstance(exchange, list):
+                self._exchange(exchange, works)
+        if ev: ev[1].record()
+        if whole:
+            self._exchange(WHOLE, works)
+        for w in works:
+            w.wait()                    # stream-level join with the RCCL stream (no host block with the nccl backend)
+        if ev: ev[2].record()
+        if last:
+            update()
+        if ev:
+            self._timing_done(ev, ("backward_graphs", "exposed_exchange", "optimizer_graph") if self.dp_buckets > 1 else
+                              ("backward_graph", "exchange", "optimizer_graph"))
 
     # -------------------------------------------------------------------------------- public
     def set_corpus(self, data: Tensor):
@@ -1148,7 +1108,7 @@ class TrainEngine:
             if key is None or key in CK.UNTRAINED:
                 out[name] = t.detach().cpu().clone()
             else:
-                out[name] = CK._rows(self.grad_view(key, img), rows).clone()
+                out[name] = CK.rows(self.grad_view(key, img), rows).clone()
         return out
 
     def _swap_ema(self) -> None:
@@ -1205,15 +1165,24 @@ class TrainEngine:
         if not block.is_cuda:
             self.check_offsets(block)
         n = block.shape[0]
+        self._grow_offsets(n)
+        self.off_block[:n].copy_(block, non_blocking=block.is_cuda)
+        self.off_ctl[0:1].copy_(self.state[2:3])          # device-side: row = step word - step word now
+        self.off_ctl[1:2].fill_(n)
+        self._off_rows, self._off_left = n, n
+
+    def _grow_offsets(self, n: int) -> None:
         if n > self.off_block.shape[0]:
             # a larger block buffer is a new address: captured graphs go (and with them the view set_offsets writes)
             self.off_block = torch.zeros((n, self.B), dtype=torch.int64, device=self.dev)
             self.offsets = self.off_block[0]
             self._graphs = None
-        self.off_block[:n].copy_(block, non_blocking=block.is_cuda)
-        self.off_ctl[0:1].copy_(self.state[2:3])          # device-side: row = step word - step word now
-        self.off_ctl[1:2].fill_(n)
-        self._off_rows, self._off_left = n, n
+
+    def _take_offset_rows(self, what: str, n: int = 1) -> None:
+        if self._off_left is not None:
+            if self._off_left <= 0:
+                raise RuntimeError(f"{what}: the {self._off_rows} staged offset rows are used up; stage_offsets() or set_offsets() first")
+            self._off_left -= n
 
     def check_offsets(self, ix: Tensor):
         """window offsets must leave room for T + 1 tokens (ref: randint(len(data) - context_length), src/preprocessing.py:43);
@@ -1237,90 +1206,29 @@ class TrainEngine:
         self._refuse_in_ema("micro_step()")
         if self.accum == 1:
             return self.step()
-        if self._off_left is not None:
-            if self._off_left <= 0:
-                raise RuntimeError(f"micro_step(): the {self._off_rows} staged offset rows are used up; stage_offsets() or set_offsets() first")
-            self._off_left -= 1
-        if self.use_graph and self._graphs is None:
-            self._capture_accum()
-        if self.use_graph:
-            self._graphs[0].replay()
-        else:
-            self._prog_micro()
-        self._j += 1
-        if self._j == self.accum:
-            self._j = 0
-            self._allreduce()
-            if self.use_graph:
-                self._graphs[1].replay()
-            else:
-                self._prog_update_accum()
+        self._take_offset_rows("micro_step()")
+        self._run(self._j, self._j + 1)
+        self._j = (self._j + 1) % self.accum
         return self.loss
-
-    def _step_accum(self) -> Tensor:
-        k = self.accum
-        if self.corpus is None or self._off_left is None:
-            raise RuntimeError(f"step() with accum_steps = {k} runs {k} micro-batches and needs {k} staged offset rows "
-                               "(set_corpus + stage_offsets); with batches given by set_batch() / set_offsets() call micro_step() "
-                               "once per batch -- step() would use the same batch for every micro-step")
-        if self._j:
-            raise RuntimeError(f"step(): {self._j} of {k} micro-steps of the current optimizer step are taken; finish it with micro_step()")
-        if self._off_left < k:
-            raise RuntimeError(f"step(): {self._off_left} of the {self._off_rows} staged offset rows are left, one optimizer step "
-                               f"needs {k}; stage_offsets() first")
-        for _ in range(k):
-            self.micro_step()
-        return self.loss_acc[1]
 
     def step(self) -> Tensor:
         """one training iteration on the current offsets / batch; returns the device loss scalar.  accum_steps = k > 1: k
         micro-steps on the next k staged offset rows and one optimizer update; returns the mean of their losses."""
         self._refuse_in_ema("step()")
-        if self.accum > 1:
-            return self._step_accum()
-        if self._off_left is not None:
-            if self._off_left <= 0:
-                raise RuntimeError(f"step(): the {self._off_rows} staged offset rows are used up; stage_offsets() or set_offsets() first")
-            self._off_left -= 1
-        if not self.use_graph:
-            if self._dp() and self.dp_buckets > 1:
-                segs, ranges = self._prog_segments()
-                works = []
-                for seg, r in zip(segs, ranges):
-                    seg()
-                    self._allreduce_ranges_async(r, works)
-                for w in works:
-                    w.wait()
-            else:
-                self._prog_fwd_bwd()
-                self._allreduce()
-            self._prog_update()
-            return self.loss
-        if self._graphs is None:
-            self._capture()
-        if not self._dp():
-            self._graphs[0].replay()
-        elif self.dp_buckets > 1:
-            works = []
-            ev = self._timing_events(3)
-            for g, r in zip(self._graphs[:-1], self._seg_ranges):
-                g.replay()
-                self._allreduce_ranges_async(r, works)
-            if ev: ev[1].record()
-            for w in works:
-                w.wait()                    # stream-level join with the RCCL stream (no host block with the nccl backend)
-            if ev: ev[2].record()
-            self._graphs[-1].replay()
-            self._timing_done(ev, ("backward_graphs", "exposed_exchange", "optimizer_graph"))
-        else:
-            ev = self._timing_events(3)
-            self._graphs[0].replay()
-            if ev: ev[1].record()
-            self._allreduce()
-            if ev: ev[2].record()
-            self._graphs[1].replay()
-            self._timing_done(ev, ("backward_graph", "exchange", "optimizer_graph"))
-        return self.loss
+        k = self.accum
+        if k > 1:
+            if self.corpus is None or self._off_left is None:
+                raise RuntimeError(f"step() with accum_steps = {k} runs {k} micro-batches and needs {k} staged offset rows "
+                                   "(set_corpus + stage_offsets); with batches given by set_batch() / set_offsets() call micro_step() "
+                                   "once per batch -- step() would use the same batch for every micro-step")
+            if self._j:
+                raise RuntimeError(f"step(): {self._j} of {k} micro-steps of the current optimizer step are taken; finish it with micro_step()")
+            if self._off_left < k:
+                raise RuntimeError(f"step(): {self._off_left} of the {self._off_rows} staged offset rows are left, one optimizer step "
+                                   f"needs {k}; stage_offsets() first")
+        self._take_offset_rows("step()", k)
+        self._run()
+        return self.loss if k == 1 else self.loss_acc[1]
 
     def _timing_events(self, n: int):
         if not self.debug_timing:
@@ -1367,16 +1275,7 @@ class TrainEngine:
                 run = S.Run(act=self.act, rng=None, weights=self.weights, fp8=self.fp8, split=self.split_bf16)
                 _, rows, _ = self._forward(run, self.ev_x, self.ev_y, False)
                 ops.reduce_sum(rows, 1.0 / rows.numel(), out=self.ev_loss)
-            side = torch.cuda.Stream(device=self.dev)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):       # warm-up outside capture
-                prog()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize(self.dev)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                prog()
-            self._eval_graph = g
+            self._eval_graph, = capture_after_warmup(self.dev, [prog])
         for i in range(n):
             ops.batch_gather(data, offsets[i], self.T, self.ev_x, self.ev_y)
             self._eval_graph.replay()
@@ -1586,9 +1485,16 @@ class TrainEngine:
         if self.fp8 and self.rank == 0 and e["fp8_seeded"]:
             sites = e["fp8_sites"]
             if not self._fp8_seeded:
-                # the histories do not exist before the first execution: run the program once as a fresh engine's warm-up does
-                # (it writes the gradient buffers and the loss: scratch) so that they exist to be written
-                self._fp8_seed_pass()
+                # the histories do not exist before the first execution: run the step's backward programs once, as a fresh engine's
+                # warm-up does, so that they exist to be written.  accum_steps 1: that writes the gradient buffers and the loss,
+                # scratch.  accum_steps > 1: the micro program's accumulate launch also moves gacc, acc_ctl, loss_acc and the
+                # micro-step word, which are put back
+                put_back = self._snapshot() if self.accum > 1 else None
+                for prog in dict.fromkeys(p for p, _ in self._step_programs()[0]):
+                    prog()
+                if put_back is not None:
+                    put_back()
+                torch.cuda.synchronize(self.dev)
             for k, t in self.fp8_sites.items():
                 if k not in sites:
                     raise ValueError(f"training state: missing key engine.fp8_sites.{k}")
@@ -1613,10 +1519,7 @@ class TrainEngine:
         self._j = 0
         if mgn is not None and self.clip_state is not None:
             self.set_max_grad_norm(mgn)
-        if n > self.off_block.shape[0]:
-            self.off_block = torch.zeros((n, self.B), dtype=torch.int64, device=self.dev)
-            self.offsets = self.off_block[0]
-            self._graphs = None
+        self._grow_offsets(n)
         if n:
             self.off_block[:n].copy_(offs)
         self.off_ctl.copy_(torch.tensor([word - (1 << 32) if word >= (1 << 31) else word, max(n, 1)], dtype=torch.int32))
@@ -1635,14 +1538,6 @@ class TrainEngine:
         if self.shadow is not None:      # (the optimizer launch keeps the whole bf16 image current; refresh_shadows() the GEMM weights)
             ops.cast(self.flat[:self.n_active], torch.bfloat16, out=self.shadow)
         self.refresh_shadows()
-
-    def _fp8_seed_pass(self) -> None:
-        if self._dp() and self.dp_buckets > 1:
-            for seg in self._prog_segments()[0]:
-                seg()
-        else:
-            self._prog_fwd_bwd()
-        torch.cuda.synchronize(self.dev)
 
     def check_status(self) -> None:
         """raise if a bounded device-side wait of the grouped dW GEMM ever ran out (dg_gemm_tn_grouped: the sticky error word in
