@@ -34,6 +34,8 @@
 //     E (LayerNorm pieces)   the four wave columns' partial row statistics are in the scratch (the unused activation part of the
 //                            NEXT stage's buffer), between barrier b_last and b_last + 1
 //     END                    block done: LDS may be refilled for the next block of this workgroup
+// The per-column vectors of the epilogues (biases, gamma, beta) ride with the stages into activation parts that are free at that moment
+// and are read from LDS (see PER-COLUMN VECTORS in the kernel); the loaders walk the stages matrix by matrix (see `seg`).
 #include "common.h"
 #include <stdlib.h>
 
@@ -103,14 +105,25 @@ __global__ __launch_bounds__(768) void block_chain_fwd_kernel(ChainP p) {
         for (int i = 0; i < grp * p.stagger; ++i) __builtin_amdgcn_s_sleep(1);
     }
 
-    // DMA pieces per loader wave and stage.  FFN2 inside a longer chain: 6 + 1 (K = 32 of the hidden block in the ring's activation
+    // DMA pieces per loader wave and stage (`issue` returns the count; the counted waits are sums of what it returned): six of weights
+    // + activations + per-column vectors.  FFN2 inside a longer chain: 6 + 1 (K = 32 of the hidden block in the ring's activation
     // part).  MODE 4 (FFN2 alone): the resident-A region is free, so the hidden block streams through IT as six slots of whole
     // 128-byte-row K = 64 tiles (full cache lines from memory that is cold inside the step; half lines cost 46 instead of 33 us):
     // even stages carry 2 more pieces, odd stages none.
-    auto n_of = [&](int s) -> int {
-        if (MODE == 4) return (s & 1) ? 6 : 8;
-        return (HAS_FFN2 && s >= O_FFN2 && s < Q0) ? 7 : 6;
-    };
+    //
+    // PER-COLUMN VECTORS.  The bias / gamma / beta an epilogue needs ride into the ring's activation parts that are free at that moment
+    // (only FFN2 stages of modes 0 / 1 carry an activation piece), as extra LDS-DMA pieces of the stage the epilogue's last pipeline
+    // barrier publishes -- every such stage sits in buffer 0 -- so the epilogue reads them with ds_read_b128 (lgkmcnt: no wait behind
+    // its own global stores) instead of from L2:
+    //     bias (bproj / b1 chunk / b2)   buffer 0, activation part + 2048 (the LayerNorm scratch keeps the low 2 KB), natural order:
+    //                                    one piece, lanes 0-23 of loader wave w carry columns 96 w .. 96 w + 95
+    //     gamma | beta                   buffer 1, activation part + 0, one stage LATER (the loaders wait for it in front of E):
+    //                                    one piece, wave w: [gamma 96 w .. + 95 | beta 96 w .. + 95] = 768 B, lanes 0-23 | 24-47
+    // Modes 0 / 1: proj's vectors with stages 12 / 13, b1 chunk c < 3 with stage 24 + 12 c, FFN2's (mode 0) with Q0 / Q0 + 1.  b1 chunk 3
+    // and mode 1's b2 have no home (the four FFN2 stages in flight fill every activation part) and stay global loads.  Modes 2 / 3 / 4
+    // never use the activation parts: all of an epilogue's vectors ride with stage 0.  FFN2 overwrites the parts, so every block
+    // re-stages them.
+    constexpr int VEC_BIAS = 0 * CH_STAGE + CH_STAGE_B + 2048, VEC_GB = 1 * CH_STAGE + CH_STAGE_B;
     // does a LayerNorm epilogue follow stage s (the last K step of proj / FFN2)?
     auto ln_after = [&](int s) -> bool { return (HAS_PROJ && s == O_FFN1 - 1) || (LN_FFN2 && s == Q0 - 1); };
 
@@ -129,29 +142,71 @@ __global__ __launch_bounds__(768) void block_chain_fwd_kernel(ChainP p) {
         for (int blk = blockIdx.x; blk < p.n_blocks; blk += gridDim.x) {
             const int64_t row0 = (int64_t)blk * CH_ROWS;
             const char* fblk = (const char*)p.f + row0 * (int64_t)(4 * C * 2);
-            auto issue = [&](int s) {
-                if (p.dbg == 3 && s >= CH_NST) return;
-                const char* src;
-                if (HAS_PROJ && s < O_FFN1) src = p.wproj + (int64_t)s * CH_STAGE_B;
-                else if (HAS_FFN1 && s < O_FFN2) src = p.w1 + (int64_t)(s - O_FFN1) * CH_STAGE_B;
-                else if (HAS_FFN2 && s < Q0) src = p.w2 + (int64_t)(s - O_FFN2) * CH_STAGE_B;
-                else src = p.wqkv + (int64_t)(s - Q0) * CH_STAGE_B;
-                char* buf = lds + (s & (CH_NST - 1)) * CH_STAGE;
-#pragma unroll
-                for (int i = 0; i < 6; ++i)
-                    __builtin_amdgcn_global_load_lds((gptr_t)(src + voff + i * 1024), (lptr_t)(buf + lw * 6144 + i * 1024), 16, 0, 0);
-                if (MODE == 4) {
-                    if (!(s & 1)) {                                       // K = 64 tile u = s / 2 of the hidden block -> slot u % 6 (standard image)
-                        const int u = s >> 1;
-#pragma unroll
-                        for (int j = 0; j < 2; ++j) {
-                            const int pr = lw * 2 + j;
-                            const char* src = fblk + (int64_t)(pr * 8 + prow) * (4 * C * 2) + u * 128 + ((slot ^ prow) << 4);
-                            __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(lds + CH_ARES + (u % 6) * 8192 + pr * 1024), 16, 0, 0);
-                        }
-                    }
-                } else if (HAS_FFN2 && s >= O_FFN2 && s < Q0)
+            // per-column vectors: every loader wave issues each piece, so the counted waits are the same for all four (the lane id
+            // through an opaque copy, as in the epilogues: the addresses are made here, not carried across the stage loop)
+            auto vec1 = [&](const float* v) {
+                int l = lane; asm volatile("" : "+v"(l));
+                if (l < 24) __builtin_amdgcn_global_load_lds((gptr_t)(v + lw * 96 + l * 4), (lptr_t)(lds + VEC_BIAS + lw * 384), 16, 0, 0);
+            };
+            auto vec2 = [&](const float* gm, const float* bt) {
+                int l = lane; asm volatile("" : "+v"(l));
+                if (l < 48)
+                    __builtin_amdgcn_global_load_lds((gptr_t)(l < 24 ? gm + lw * 96 + l * 4 : bt + lw * 96 + (l - 24) * 4),
+                                                     (lptr_t)(lds + VEC_GB + lw * 768), 16, 0, 0);
+            };
+            // the activation pieces of FFN2's stage s: one (mode 4: two with an even stage, none with an odd one)
+            auto issue_a = [&](int s, char* buf) {
+                if (MODE != 4) {
                     __builtin_amdgcn_global_load_lds((gptr_t)(fblk + (s - O_FFN2) * 64 + aoff), (lptr_t)(buf + CH_STAGE_B + lw * 1024), 16, 0, 0);
+                    return;
+                }
+                if (s & 1) return;
+                const int u = s >> 1;                                     // K = 64 tile u = s / 2 of the hidden block -> slot u % 6 (standard image)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int pr = lw * 2 + j;
+                    const char* src = fblk + (int64_t)(pr * 8 + prow) * (4 * C * 2) + u * 128 + ((slot ^ prow) << 4);
+                    __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(lds + CH_ARES + (u % 6) * 8192 + pr * 1024), 16, 0, 0);
+                }
+            };
+            // returns the pieces of stage s per loader wave: a constant for a literal s, so that the counted waits fold (under the
+            // ablation dbg == 3 nothing is in flight and any wait passes)
+            auto issue = [&](int s) -> int {
+                const bool off = p.dbg == 3 && s >= CH_NST;
+                int n = 6;
+                const char* src;
+                char* buf = lds + (s & (CH_NST - 1)) * CH_STAGE;
+                if (HAS_PROJ && s < O_FFN1) src = p.wproj + (int64_t)s * CH_STAGE_B;
+                else if (HAS_FFN1 && s < O_FFN2) {
+                    const int r = s - O_FFN1;
+                    src = p.w1 + (int64_t)r * CH_STAGE_B;
+                    if (r == 0) { if (!off) vec1(p.bproj); ++n; }         // proj's epilogue runs behind barrier O_FFN1 - 1
+                    else if (r == 1) { if (!off) vec2(p.ln2w, p.ln2b); ++n; }
+                    else if (r == KS || r == 2 * KS || r == 3 * KS) { if (!off) vec1(p.b1 + (r / KS - 1) * C); ++n; }      // FFN1 chunks 0-2
+                } else if (HAS_FFN2 && s < Q0) {
+                    src = p.w2 + (int64_t)(s - O_FFN2) * CH_STAGE_B;
+                    n += MODE != 4 ? 1 : (s & 1) ? 0 : 2;
+                    if (!off) issue_a(s, buf);
+                } else {
+                    src = p.wqkv + (int64_t)(s - Q0) * CH_STAGE_B;
+                    if (MODE == 0 && s == Q0) { if (!off) vec1(p.b2); ++n; }      // FFN2's epilogue runs behind barrier Q0 - 1
+                    else if (MODE == 0 && s == Q0 + 1) { if (!off) vec2(p.ln1w, p.ln1b); ++n; }
+                }
+                // (Stages with a literal index: left to itself the compiler makes one 64-bit lane address per piece of all of them up
+                // front and spills them by the hundred.  One opaque uniform base per stage.)
+                asm volatile("" : "+s"(src));
+                if (!off) {
+#pragma unroll
+                    for (int i = 0; i < 6; ++i)
+                        __builtin_amdgcn_global_load_lds((gptr_t)(src + voff + i * 1024), (lptr_t)(buf + lw * 6144 + i * 1024), 16, 0, 0);
+                }
+                if ((MODE == 2 || MODE == 3 || MODE == 4) && s == 0) {    // these modes never use the activation parts
+                    if (MODE == 3) { vec1(p.bproj); ++n; }
+                    if (MODE == 4) { vec1(p.b2); ++n; }
+                    if (MODE == 3) vec2(p.ln2w, p.ln2b); else vec2(p.ln1w, p.ln1b);
+                    ++n;
+                }
+                return n;
             };
             if (HAS_PROJ) {
                 // the block's attention output -> resident A (6 K-tiles x 8 pieces; standard 128-byte-row image)
@@ -163,9 +218,16 @@ __global__ __launch_bounds__(768) void block_chain_fwd_kernel(ChainP p) {
                     __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(lds + CH_ARES + tile * 8192 + pr * 1024), 16, 0, 0);
                 }
             }
-            for (int s = 0; s < CH_NST; ++s) issue(s);
-            if (MODE == 2) __builtin_amdgcn_s_barrier();                  // E of the head's LayerNorm (the MFMA waves' prologue)
-            ch_wait_vm(n_of(1) + n_of(2) + n_of(3));                      // stages 1..3 may fly; resident A + stage 0 landed
+            issue(0);
+            const int n1 = issue(1);
+            // n_prev + n_last: the pieces of the two stages issued last.  In front of barrier b these are stages b + 2 and b + 3, so
+            // waiting for all but that many says stage b + 1 has landed (past the block's end a stage that does not exist counts 0)
+            int n_prev = issue(2), n_last = issue(3);
+            if (MODE == 2) {                                              // E of the head's LayerNorm (the MFMA waves' prologue):
+                ch_wait_vm(n1 + n_prev + n_last);                         // its gamma / beta ride with stage 0
+                __builtin_amdgcn_s_barrier();
+            }
+            ch_wait_vm(n1 + n_prev + n_last);                             // stages 1..3 may fly; resident A + stage 0 landed
             __builtin_amdgcn_s_barrier();                                 // P
             if (p.dbg == 5) {                                             // ablation: the loaders do nothing but keep the barrier sequence
                 for (int b = 0; b + 1 < S; ++b) {
@@ -176,14 +238,59 @@ __global__ __launch_bounds__(768) void block_chain_fwd_kernel(ChainP p) {
                 __builtin_amdgcn_s_barrier();
                 continue;
             }
-            for (int b = 0; b + 1 < S; ++b) {
-                int fly = 0;
-                if (b + 2 < S) fly += n_of(b + 2);
-                if (b + 3 < S) fly += n_of(b + 3);
-                ch_wait_vm(fly);                                          // stage b+1 landed
+            // Barrier b = s - 4 and the stage s issued behind it, matrix by matrix.  Every instruction of a loader wave takes an issue
+            // slot from the MFMA waves of its SIMD (the K loops lost 5 % when the stage loop decoded every stage's piece, vectors and
+            // piece count at run time), so what is special sits in the first stages of a matrix -- the vectors, the E barrier of the
+            // LayerNorm in front (behind barrier lo - 1, i.e. stage lo + 3), piece counts that differ from the matrix' own -- and these six
+            // are unrolled with a literal stage index; the rest of the matrix is a loop of one wait, one barrier and the stage's pieces
+            // on a running base.
+            auto adv = [&](int b, int n_issued) {                         // b's E barrier, if any, follows the issue (see `issue`)
+                n_prev = n_last;
+                n_last = n_issued;
+                if (ln_after(b)) {                                        // E: gamma / beta ride with stage b + 2 (issued two barriers ago)
+                    ch_wait_vm(n_prev + n_last);                          // all but stages b + 3 and b + 4 have landed
+                    __builtin_amdgcn_s_barrier();
+                }
+            };
+            auto seg = [&](int lo, int hi, const char* w, bool ffn2) {    // stages lo .. hi - 1 = the matrix w, behind barriers lo - 4 .. hi - 5
+#pragma unroll
+                for (int k = 0; k < 6; ++k) {
+                    const int s = lo + k;
+                    if (s < CH_NST) continue;                             // (issued in front of P)
+                    ch_wait_vm(n_prev + n_last);                          // stage s - 3 landed
+                    __builtin_amdgcn_s_barrier();                         // b = s - 4
+                    adv(s - CH_NST, issue(s));
+                }
+                const char* base = w + (int64_t)6 * CH_STAGE_B;
+#pragma nounroll
+                for (int s = lo + 6; s < hi; ++s, base += CH_STAGE_B) {
+                    // the two stages in flight are plain stages of this matrix: 6 + 6, FFN2 7 + 7 (mode 4: 8 + 6)
+                    if (ffn2) asm volatile("s_waitcnt vmcnt(14)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+                    __builtin_amdgcn_s_barrier();                         // b = s - 4
+                    if (p.dbg == 3) continue;
+                    char* buf = lds + (s & (CH_NST - 1)) * CH_STAGE;
+                    const char* src = base;
+                    asm volatile("" : "+s"(src));
+#pragma unroll
+                    for (int i = 0; i < 6; ++i)
+                        __builtin_amdgcn_global_load_lds((gptr_t)(src + voff + i * 1024), (lptr_t)(buf + lw * 6144 + i * 1024), 16, 0, 0);
+                    if (ffn2) issue_a(s, buf);
+                }
+                n_prev = ffn2 ? (MODE == 4 ? 8 : 7) : 6;                  // stages hi - 2 and hi - 1 (mode 4: hi is even)
+                n_last = ffn2 ? (MODE == 4 ? 6 : 7) : 6;
+            };
+            if (HAS_PROJ) seg(0, O_FFN1, p.wproj, false);
+            if (HAS_FFN1) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) seg(O_FFN1 + c * KS, O_FFN1 + (c + 1) * KS, p.w1 + (int64_t)c * KS * CH_STAGE_B, false);
+            }
+            if (HAS_FFN2) seg(O_FFN2, Q0, p.w2, true);
+            if (HAS_QKV) seg(Q0, S, p.wqkv, false);
+#pragma unroll
+            for (int b = S - CH_NST; b + 1 < S; ++b) {                    // the last three barriers: nothing left to issue
+                ch_wait_vm(n_prev + n_last);                              // stage b + 1 landed
                 __builtin_amdgcn_s_barrier();                             // b
-                if (b + CH_NST < S) issue(b + CH_NST);
-                if (ln_after(b)) __builtin_amdgcn_s_barrier();            // E
+                adv(b, 0);
             }
             if (ln_after(S - 1)) __builtin_amdgcn_s_barrier();            // E of a LayerNorm behind the block's last stage (modes 3, 4)
             __builtin_amdgcn_s_barrier();                                 // END
@@ -274,8 +381,8 @@ __global__ __launch_bounds__(768) void block_chain_fwd_kernel(ChainP p) {
     // LayerNorm of the 64 x C block whose values the MFMA waves hold as xv[i][q][8] (row i*16 + fr of wave row wm, the lane's 24
     // columns): per wave column a (mean, M2) pair over its 96 columns, combined across the four wave columns through `scratch`
     // (Chan's formula: exact), then y = (x - mean) rstd gamma + beta as bf16 to global memory and into the resident A image.
-    auto layernorm = [&](float (&xv)[2][3][8], float* scratch, int64_t row0, const float* gamma, const float* beta, float* mean_o,
-                         float* rstd_o, bf16_t* y) {
+    // gamma / beta come from LDS (VEC_GB: delivered by the loaders, known landed behind E).
+    auto layernorm = [&](float (&xv)[2][3][8], float* scratch, int64_t row0, float* mean_o, float* rstd_o, bf16_t* y) {
         const int lo = opaque_lane(), fr = lo & 15, fg = lo >> 4, col_l = wn * 96 + (fg & 1) * 16 + (fg >> 1) * 8;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -311,11 +418,12 @@ __global__ __launch_bounds__(768) void block_chain_fwd_kernel(ChainP p) {
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
             const int col = col_l + 32 * q;
-            // (gamma / beta of block q + 1 requested ahead, like the residual operands: 2 us SLOWER per LayerNorm piece -- 32 more
-            // live registers and ten spills; requested for block 0 only, in front of the exchange barrier: ten spills again, for all
-            // three blocks there: sixty.  The plain form it is: three L2 round trips, ~4 000 of this epilogue's 19 500 cycles)
-            const f32x4 g0 = *(const f32x4*)(gamma + col), g1 = *(const f32x4*)(gamma + col + 4);
-            const f32x4 b0 = *(const f32x4*)(beta + col), b1 = *(const f32x4*)(beta + col + 4);
+            // (From global memory these were three dependent L2 round trips, ~4 000 of this epilogue's 19 500 cycles, each queued
+            // behind the stores of the group before on the in-order vmcnt; requesting them ahead into registers spilled 10-60.  From
+            // LDS: the 16 lanes of an fg group read one address, the four groups disjoint 32-byte segments of the wave column's 768 B.)
+            const char* gb = lds + VEC_GB + wn * 768 + (col - wn * 96) * 4;
+            const f32x4 g0 = *(const f32x4*)gb, g1 = *(const f32x4*)(gb + 16);
+            const f32x4 b0 = *(const f32x4*)(gb + 384), b1 = *(const f32x4*)(gb + 400);
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 bf16x8 o;
@@ -331,12 +439,14 @@ __global__ __launch_bounds__(768) void block_chain_fwd_kernel(ChainP p) {
         }
     };
     // bias + dropout + residual epilogue of proj / FFN2 -> xv (and the fp32 / bf16 stream in global memory)
+    // (`bias` == nullptr: the bias sits in LDS at VEC_BIAS, published by the piece's last pipeline barrier)
     auto residual_epilogue = [&](float (&xv)[2][3][8], int64_t row0, const float* bias, const float* res, uint32_t key, float* out32, bf16_t* out16) {
         const int lo = opaque_lane(), fr = lo & 15, fg = lo >> 4, col_l = wn * 96 + (fg & 1) * 16 + (fg >> 1) * 8;
         f32x4 bq[2][2], r[2][2][2];                                       // [q & 1]: block q + 1 is requested before block q is computed
         auto request = [&](int q) {
             const int col = col_l + 32 * q;
-            bq[q & 1][0] = *(const f32x4*)(bias + col); bq[q & 1][1] = *(const f32x4*)(bias + col + 4);
+            if (bias) { bq[q & 1][0] = *(const f32x4*)(bias + col); bq[q & 1][1] = *(const f32x4*)(bias + col + 4); }
+            else { bq[q & 1][0] = *(const f32x4*)(lds + VEC_BIAS + col * 4); bq[q & 1][1] = *(const f32x4*)(lds + VEC_BIAS + col * 4 + 16); }
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const float* rp = res + row0 * C + mad24(wm * 32 + i * 16 + fr, C, col);
@@ -420,7 +530,7 @@ __global__ __launch_bounds__(768) void block_chain_fwd_kernel(ChainP p) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { xv[i][q][e] = a[e]; xv[i][q][4 + e] = b[e]; }
                 }
-            layernorm(xv, (float*)(lds + 0 * CH_STAGE + CH_STAGE_B), row0, p.ln1w, p.ln1b, p.mean1, p.rstd1, p.h1);
+            layernorm(xv, (float*)(lds + 0 * CH_STAGE + CH_STAGE_B), row0, p.mean1, p.rstd1, p.h1);
         }
         __builtin_amdgcn_s_barrier();                                     // P
         // one GEMM piece = NSTEP K steps entering with (fa0, fb0) loaded for its first step; `ring_a`: A operand from the ring.
@@ -485,8 +595,8 @@ __global__ __launch_bounds__(768) void block_chain_fwd_kernel(ChainP p) {
             if (p.dbg == 4 || p.dbg == 5) __builtin_amdgcn_s_barrier();
             else {
                 float xv[2][3][8];
-                residual_epilogue(xv, row0, p.bproj, p.x, key_proj, p.x1, nullptr);
-                layernorm(xv, (float*)(lds + (g & (CH_NST - 1)) * CH_STAGE + CH_STAGE_B), row0, p.ln2w, p.ln2b, p.mean2, p.rstd2, p.h2);
+                residual_epilogue(xv, row0, nullptr, p.x, key_proj, p.x1, nullptr);
+                layernorm(xv, (float*)(lds + (g & (CH_NST - 1)) * CH_STAGE + CH_STAGE_B), row0, p.mean2, p.rstd2, p.h2);
             }
         }
         stamp(2);
@@ -501,10 +611,13 @@ __global__ __launch_bounds__(768) void block_chain_fwd_kernel(ChainP p) {
                 const int tile_lo = (blk >> 1) * (4 * C / 192) + c * 2 + (wn >> 1);
                 const int wv = (((blk & 1) * 2 + wm) * 2 + (wn & 1));
                 f32x4 bq[3][2];                                           // every bias load in front of the first store
+                // chunks 0-2: from LDS (VEC_BIAS, with the next chunk's first stage).  Chunk 3 runs while FFN2's first stages, which
+                // fill every activation part, are in flight: from global memory
 #pragma unroll
                 for (int q = 0; q < 3; ++q) {
-                    const int col = c * C + col_l + 32 * q;
-                    bq[q][0] = *(const f32x4*)(p.b1 + col); bq[q][1] = *(const f32x4*)(p.b1 + col + 4);
+                    const int col = col_l + 32 * q;
+                    if (c < 3) { bq[q][0] = *(const f32x4*)(lds + VEC_BIAS + col * 4); bq[q][1] = *(const f32x4*)(lds + VEC_BIAS + col * 4 + 16); }
+                    else { bq[q][0] = *(const f32x4*)(p.b1 + c * C + col); bq[q][1] = *(const f32x4*)(p.b1 + c * C + col + 4); }
                 }
 #pragma unroll
                 for (int q = 0; q < 3; ++q) {
@@ -538,9 +651,9 @@ __global__ __launch_bounds__(768) void block_chain_fwd_kernel(ChainP p) {
             if (p.dbg == 4 || p.dbg == 5) { if (LN_FFN2) __builtin_amdgcn_s_barrier(); }
             else {
                 float xv[2][3][8];
-                residual_epilogue(xv, row0, p.b2, p.x1, key_ffn, MODE != 1 ? p.x2 : nullptr, p.x2b);
+                residual_epilogue(xv, row0, MODE == 1 ? p.b2 : nullptr, p.x1, key_ffn, MODE != 1 ? p.x2 : nullptr, p.x2b);
                 if (LN_FFN2)
-                    layernorm(xv, (float*)(lds + (g & (CH_NST - 1)) * CH_STAGE + CH_STAGE_B), row0, p.ln1w, p.ln1b, p.mean1, p.rstd1, p.h1);
+                    layernorm(xv, (float*)(lds + (g & (CH_NST - 1)) * CH_STAGE + CH_STAGE_B), row0, p.mean1, p.rstd1, p.h1);
             }
         }
         stamp(12);
@@ -579,6 +692,10 @@ __global__ __launch_bounds__(768) void block_chain_fwd_kernel(ChainP p) {
 // loaders stream them: stage k = (column chunk c = k / (K / 32), K step t = k % (K / 32)); inside a stage 192 lines of 128 B,
 // physical 16-byte slot s of line j holds logical slot ls = s ^ (j & 7): row c * 384 + j + 192 * (ls >> 2), columns
 // t * 32 + 8 * (ls & 3) .. + 7.  One workgroup per stage; desc rows = {src, dst, N, K, first stage of the matrix in the grid, ld}.
+// A stage takes 64 of the 128 bytes of a source line, K step t + 1 of the same column chunk the other 64: where K / 32 is even the two
+// workgroups of a stage pair (t even, t + 1) share the PAIR's work by lines instead -- each packs 96 lines of both stages, 16 lanes per
+// line = rows j and j + 192 as whole 128-byte source lines and one whole packed line of each stage -- so that every source line is
+// read once (63.8 -> 42.5 MB per refresh of the step's weights).  The grid and the packed image are the same.
 struct PackOne { const unsigned short* src; unsigned short* dst; int N, K; int64_t ld; };
 __global__ __launch_bounds__(256) void pack_chain_kernel(const int64_t* __restrict__ desc, int n_desc, PackOne one) {
     const unsigned short* src = one.src;
@@ -595,6 +712,18 @@ __global__ __launch_bounds__(256) void pack_chain_kernel(const int64_t* __restri
         k = (int)((int64_t)blockIdx.x - D[4]);
     }
     const int KT = K / 32, c = k / KT, t = k % KT;
+    if (!(KT & 1)) {                                                      // (pairs never straddle a column chunk or a matrix: k even <=> t even)
+        const int half = t & 1, t0 = t - half;
+        const int64_t k0 = k - half;
+#pragma unroll
+        for (int u = 0; u < 6; ++u) {
+            const int idx = threadIdx.x + 256 * u, line = 96 * half + (idx >> 4), hi = (idx >> 3) & 1, j = idx & 7;
+            const int slot = (hi * 4 + (j & 3)) ^ (line & 7);
+            const int row = c * 384 + line + 192 * hi, col = t0 * 32 + 8 * j;
+            *(u32x4*)(dst + ((k0 + (j >> 2)) * 1536 + line * 8 + slot) * 8) = *(const u32x4*)(src + (int64_t)row * ld + col);
+        }
+        return;
+    }
 #pragma unroll
     for (int u = 0; u < 6; ++u) {
         const int idx = threadIdx.x + 256 * u, line = idx >> 3, slot = idx & 7, ls = slot ^ (line & 7);

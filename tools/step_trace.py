@@ -4,6 +4,8 @@
 import csv, sys, collections
 rows = list(csv.DictReader(open(sys.argv[1])))
 rows.sort(key=lambda r: int(r['Start_Timestamp']))
+for r in rows:                                     # newer rocprofv3 demangles: "void adamw_kernel<false, ..."
+    r['Kernel_Name'] = r['Kernel_Name'][5:] if r['Kernel_Name'].startswith('void ') else r['Kernel_Name']
 idx = [i for i, r in enumerate(rows) if r['Kernel_Name'].startswith('adamw')]
 seq = rows[idx[-2] + 1:idx[-1] + 1]
 agg = collections.OrderedDict()
