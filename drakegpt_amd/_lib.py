@@ -156,7 +156,11 @@ SIGNATURES = {
     "dg_cross_entropy_smooth": [_vp, _i, _i64, _vp, _vp, _vp, _i64, _i, _f, _vp, _i, _i, _f, _f, _vp],
     "dg_cross_entropy_fp8_smooth": [_vp, _i64, _vp, _vp, _vp, _i64, _f, _i, _i, _vp, _i64, _f, _vp],
     "dg_cross_entropy_fused_smooth": [_vp, _i64, _vp, _vp, _vp, _i64, _i, _f, _i, _i, _vp, _i64, _i, _vp, _vp, _vp, _f, _f, _f, _vp],
+    "dg_ce_count_valid": [_vp, _i, _i64, _vp, _vp],
+    "dg_cross_entropy_ignore": [_vp, _i, _i64, _vp, _vp, _vp, _i64, _i, _f, _vp, _i, _i, _f, _f, _i64, _vp, _vp],
+    "dg_cross_entropy_fused_ignore": [_vp, _i64, _vp, _vp, _vp, _i64, _i, _f, _i, _i, _vp, _i64, _i, _vp, _vp, _vp, _f, _f, _f, _i64, _vp, _vp],
     "dg_reduce_sum": [_vp, _i64, _f, _vp, _vp],
+    "dg_reduce_sum_scaled": [_vp, _i64, _f, _vp, _vp, _vp],
     "dg_softmax_rows": [_vp, _i64, _vp, _i64, _i, _i, _vp],
     "dg_adamw_step": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _f, _vp, _i, _vp],
     "dg_sumsq_parts": [_i64],

@@ -16,8 +16,26 @@
 // neither the -inf that fills padding lanes nor the memory of columns V .. ldl - 1 enters it.  With zeta > 0 a gradient row sums to
 // 2 zeta lse grad_scale, not to zero.
 struct CeOpt { float eps, zeta; };
+// ignore_index, a second member the pack may end in (IGN below; alone or behind a CeOpt): a row whose target equals ignore_index is
+// left out -- its loss_rows entry and its dlogits row (padding columns included, and in place over its own logits) are STORED as
+// exact zeros, and its target is recognised before any logit is read, a wave- / workgroup-uniform exit in the wave-per-row and
+// workgroup-per-row kernels.  The other rows' gradients are scaled by inv_count[0] = 1 / N, N the number of rows that count, which
+// only the device knows (dg_ce_count_valid writes it); the mean of loss_rows takes the same factor (dg_reduce_sum_scaled, or the
+// fused kernel's last workgroup).  N = 0: inv_count is +inf, nothing is multiplied by it, every gradient row is zeros.
+// The ignore forms without a CeOpt write the row loss as log s + (mx - x_t), the order the options use (nothing rounds at the size of mx:
+// logits shifted by +1000 keep 1e-6); the plain instantiations keep mx + log s - x_t, the code they always had.
+struct CeIgn { int64_t ignore_index; const float* inv_count; };
+template <typename T, typename... O> struct ce_has { static constexpr bool value = false; };
+template <typename T, typename U, typename... O> struct ce_has<T, U, O...> { static constexpr bool value = ce_has<T, O...>::value; };
+template <typename T, typename... O> struct ce_has<T, T, O...> { static constexpr bool value = true; };
 __device__ __forceinline__ CeOpt ce_opt() { return CeOpt{0.f, 0.f}; }
 __device__ __forceinline__ CeOpt ce_opt(CeOpt opt) { return opt; }
+__device__ __forceinline__ CeOpt ce_opt(CeIgn) { return CeOpt{0.f, 0.f}; }
+__device__ __forceinline__ CeOpt ce_opt(CeOpt opt, CeIgn) { return opt; }
+__device__ __forceinline__ CeIgn ce_ign() { return CeIgn{0, nullptr}; }
+__device__ __forceinline__ CeIgn ce_ign(CeOpt) { return CeIgn{0, nullptr}; }
+__device__ __forceinline__ CeIgn ce_ign(CeIgn ign) { return ign; }
+__device__ __forceinline__ CeIgn ce_ign(CeOpt, CeIgn ign) { return ign; }
 __device__ __forceinline__ float ce_objective(float mx, float logs, float xt, float sd, int V, CeOpt opt) {
     const float lse = mx + logs;
     return logs + (1.f - opt.eps) * (mx - xt) + opt.eps / (float)V * sd + opt.zeta * lse * lse;
@@ -32,11 +50,18 @@ template <typename TD, typename TL = float, typename... O>
 __global__ void cross_entropy_kernel(const TL* __restrict__ logits, int64_t ldl, const int64_t* __restrict__ targets,
                                      float* __restrict__ loss_rows, TD* __restrict__ dlogits, int64_t ldd,
                                      float grad_scale, const float* __restrict__ gs_dev, int M, int V, O... o) {
-    constexpr bool OPT = sizeof...(O) != 0;
+    constexpr bool OPT = ce_has<CeOpt, O...>::value, IGN = ce_has<CeIgn, O...>::value;
     const CeOpt opt = ce_opt(o...);
+    const CeIgn ign = ce_ign(o...);
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (row >= M) return;
+    if (IGN && targets[row] == ign.ignore_index) {           // (wave-uniform: no logit of the row is read)
+        if (lane == 0) loss_rows[row] = 0.f;
+        if (dlogits)
+            for (int i = lane; i < (int)ldd; i += 64) dlogits[(int64_t)row * ldd + i] = from_f32<TD>(0.f);
+        return;
+    }
     const TL* x = logits + (int64_t)row * ldl;
     float mx = -INFINITY;
     for (int i = lane; i < V; i += 64) mx = fmaxf(mx, (float)x[i]);
@@ -51,12 +76,13 @@ __global__ void cross_entropy_kernel(const TL* __restrict__ logits, int64_t ldl,
     int64_t t = targets[row];
     t = t < 0 ? 0 : (t >= V ? V - 1 : t);
     const float lse = mx + logf(s);
-    if (lane == 0) loss_rows[row] = OPT ? ce_objective(mx, logf(s), (float)x[t], sd, V, opt) : lse - (float)x[t];
+    if (lane == 0) loss_rows[row] = OPT ? ce_objective(mx, logf(s), (float)x[t], sd, V, opt) : IGN ? logf(s) + (mx - (float)x[t]) : lse - (float)x[t];
     if (dlogits) {
         TD* d = dlogits + (int64_t)row * ldd;
         const float inv = OPT ? ce_pscale(mx, logf(s), opt) / s : 1.f / s;
         const float unif = OPT ? opt.eps / (float)V : 0.f;
         if (gs_dev) grad_scale *= gs_dev[0];
+        if (IGN) grad_scale *= ign.inv_count[0];
         for (int i = lane; i < (int)ldd; i += 64) {
             float g = 0.f;
             if (i < V) g = OPT ? ce_grad(expf((float)x[i] - mx) * inv, i == (int)t, unif, opt, grad_scale)
@@ -73,18 +99,21 @@ template <typename TD, typename... O>
 __global__ __launch_bounds__(256) void cross_entropy_small_kernel(const float* __restrict__ logits, int64_t ldl, const int64_t* __restrict__ targets,
                                                                   float* __restrict__ loss_rows, TD* __restrict__ dlogits, int64_t ldd,
                                                                   float grad_scale, const float* __restrict__ gs_dev, int M, int V, O... o) {
-    constexpr bool OPT = sizeof...(O) != 0;
+    constexpr bool OPT = ce_has<CeOpt, O...>::value, IGN = ce_has<CeIgn, O...>::value;
     const CeOpt opt = ce_opt(o...);
+    const CeIgn ign = ce_ign(o...);
     const int sub = threadIdx.x & 15;
     const int row = blockIdx.x * 16 + (threadIdx.x >> 4);
     const bool ok = row < M;
     const float* x = logits + (int64_t)(ok ? row : 0) * ldl;
+    // an ignored row keeps its 16 lanes in the shuffles below on zeros that it never loaded, and stores zeros
+    const bool skip = IGN && ok && targets[row] == ign.ignore_index;
     float v[8];
     float mx = -INFINITY;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         const int i = sub + 16 * k;
-        v[k] = i < V ? x[i] : -INFINITY;
+        v[k] = i < V ? (IGN && skip ? 0.f : x[i]) : -INFINITY;
         mx = fmaxf(mx, v[k]);
     }
 #pragma unroll
@@ -102,14 +131,24 @@ __global__ __launch_bounds__(256) void cross_entropy_small_kernel(const float* _
         for (int sh = 8; sh > 0; sh >>= 1) sd += __shfl_xor(sd, sh, 64);
     }
     if (!ok) return;
+    if (IGN && skip) {
+        if (sub == 0) loss_rows[row] = 0.f;
+        if (dlogits) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if (sub + 16 * k < (int)ldd) dlogits[(int64_t)row * ldd + sub + 16 * k] = from_f32<TD>(0.f);
+        }
+        return;
+    }
     int64_t t = targets[row];
     t = t < 0 ? 0 : (t >= V ? V - 1 : t);
-    if (sub == 0) loss_rows[row] = OPT ? ce_objective(mx, logf(s), x[t], sd, V, opt) : mx + logf(s) - x[t];
+    if (sub == 0) loss_rows[row] = OPT ? ce_objective(mx, logf(s), x[t], sd, V, opt) : IGN ? logf(s) + (mx - x[t]) : mx + logf(s) - x[t];
     if (dlogits) {
         TD* d = dlogits + (int64_t)row * ldd;
         const float inv = OPT ? ce_pscale(mx, logf(s), opt) / s : 1.f / s;
         const float unif = OPT ? opt.eps / (float)V : 0.f;
         if (gs_dev) grad_scale *= gs_dev[0];
+        if (IGN) grad_scale *= ign.inv_count[0];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int i = sub + 16 * k;
@@ -135,8 +174,9 @@ template <typename TD, typename... O>
 __global__ __launch_bounds__(CEF_THREADS) void cross_entropy_small_fused_kernel(const float* __restrict__ logits, int64_t ldl, const int64_t* __restrict__ targets,
                                                                         float* __restrict__ loss_rows, TD* __restrict__ dlogits, int64_t ldd,
                                                                         float grad_scale, int M, int V, CeFuse fz, O... o) {
-    constexpr bool OPT = sizeof...(O) != 0;
+    constexpr bool OPT = ce_has<CeOpt, O...>::value, IGN = ce_has<CeIgn, O...>::value;
     const CeOpt opt = ce_opt(o...);
+    const CeIgn ign = ce_ign(o...);
     __shared__ float red[CEF_RG][128];
     __shared__ float lred[CEF_RG];
     __shared__ unsigned last_flag;
@@ -147,16 +187,20 @@ __global__ __launch_bounds__(CEF_THREADS) void cross_entropy_small_fused_kernel(
 #pragma unroll
     for (int k = 0; k < 8; ++k) cacc[k] = 0.f;
     float lsum = 0.f;
+    if (IGN) grad_scale *= ign.inv_count[0];
     for (int r0 = m_begin; r0 < m_end; r0 += CEF_RG) {            // (uniform trip count: the shuffles below need every lane)
         const int row = r0 + rg;
         const bool ok = row < m_end;
         const float* x = logits + (int64_t)(ok ? row : m_begin) * ldl;
+        // an ignored row group stays in the trip and in the shuffles on zeros that it never loaded: it stores zeros and adds
+        // nothing to the column sums or to the loss share
+        const bool skip = IGN && ok && targets[row] == ign.ignore_index;
         float v[8];
         float mx = -INFINITY;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int i = sub + 16 * k;
-            v[k] = i < V ? x[i] : -INFINITY;
+            v[k] = i < V ? (IGN && skip ? 0.f : x[i]) : -INFINITY;
             mx = fmaxf(mx, v[k]);
         }
 #pragma unroll
@@ -174,9 +218,16 @@ __global__ __launch_bounds__(CEF_THREADS) void cross_entropy_small_fused_kernel(
             for (int sh = 8; sh > 0; sh >>= 1) sd += __shfl_xor(sd, sh, 64);
         }
         if (!ok) continue;
+        if (IGN && skip) {
+            if (sub == 0) loss_rows[row] = 0.f;
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if (sub + 16 * k < (int)ldd) dlogits[(int64_t)row * ldd + sub + 16 * k] = from_f32<TD>(0.f);
+            continue;
+        }
         int64_t t = targets[row];
         t = t < 0 ? 0 : (t >= V ? V - 1 : t);
-        const float lr = OPT ? ce_objective(mx, logf(s), x[t], sd, V, opt) : mx + logf(s) - x[t];
+        const float lr = OPT ? ce_objective(mx, logf(s), x[t], sd, V, opt) : IGN ? logf(s) + (mx - x[t]) : mx + logf(s) - x[t];
         if (sub == 0) { loss_rows[row] = lr; lsum += lr; }
         TD* d = dlogits + (int64_t)row * ldd;
         const float inv = OPT ? ce_pscale(mx, logf(s), opt) / s : 1.f / s;
@@ -223,7 +274,7 @@ __global__ __launch_bounds__(CEF_THREADS) void cross_entropy_small_fused_kernel(
     if (tid == 0) {
         float tot = 0.f;
         for (int i = 0; i < (int)gridDim.x; ++i) tot += sh[i];
-        fz.loss_out[0] = tot * fz.loss_scale;
+        fz.loss_out[0] = IGN ? tot * (fz.loss_scale * ign.inv_count[0]) : tot * fz.loss_scale;
         __hip_atomic_store(fz.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
@@ -237,16 +288,23 @@ template <typename TD, typename TL = float, typename... O>
 __global__ __launch_bounds__(CE_BLOCK) void cross_entropy_row_kernel(const TL* logits, int64_t ldl, const int64_t* __restrict__ targets,
                                                                       float* __restrict__ loss_rows, TD* dlogits, int64_t ldd,   // (may alias)
                                                                       float grad_scale, const float* __restrict__ gs_dev, int M, int V, O... o) {
-    constexpr bool OPT = sizeof...(O) != 0;
+    constexpr bool OPT = ce_has<CeOpt, O...>::value, IGN = ce_has<CeIgn, O...>::value;
     const CeOpt opt = ce_opt(o...);
+    const CeIgn ign = ce_ign(o...);
     __shared__ float red[16];
     __shared__ float red2[OPT ? 16 : 1];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int row = blockIdx.x;
     const TL* x = logits + (int64_t)row * ldl;
+    int64_t t = targets[row];
+    if (IGN && t == ign.ignore_index) {                  // (workgroup-uniform, before any load of the row and any barrier)
+        if (tid == 0) loss_rows[row] = 0.f;
+        if (dlogits)
+            for (int i = tid; i < (int)ldd; i += CE_BLOCK) dlogits[(int64_t)row * ldd + i] = from_f32<TD>(0.f);
+        return;
+    }
     float v[CE_MAXK];
     float mx = -INFINITY;
-    int64_t t = targets[row];
     t = t < 0 ? 0 : (t >= V ? V - 1 : t);
     const float xt = (float)x[t];                        // before any store of this row (in-place gradient)
 #pragma unroll
@@ -282,12 +340,13 @@ __global__ __launch_bounds__(CE_BLOCK) void cross_entropy_row_kernel(const TL* l
 #pragma unroll
         for (int k = 1; k < 16; ++k) sd += red2[k];
     }
-    if (tid == 0) loss_rows[row] = OPT ? ce_objective(mx, logf(s), xt, sd, V, opt) : mx + logf(s) - xt;
+    if (tid == 0) loss_rows[row] = OPT ? ce_objective(mx, logf(s), xt, sd, V, opt) : IGN ? logf(s) + (mx - xt) : mx + logf(s) - xt;
     if (dlogits) {
         TD* d = dlogits + (int64_t)row * ldd;
         const float inv = OPT ? ce_pscale(mx, logf(s), opt) / s : 1.f / s;
         const float unif = OPT ? opt.eps / (float)V : 0.f;
         if (gs_dev) grad_scale *= gs_dev[0];
+        if (IGN) grad_scale *= ign.inv_count[0];
 #pragma unroll
         for (int k = 0; k < CE_MAXK; ++k) {
             const int i = k * CE_BLOCK + tid;
@@ -322,14 +381,25 @@ __global__ __launch_bounds__(CE_BLOCK, 8) void cross_entropy_row_bf16_kernel(con
                                                                               float* __restrict__ loss_rows, bf16_t* dlogits, int64_t ldd,
                                                                               float grad_scale, const float* __restrict__ gs_dev, int M, int V,
                                                                               unsigned char* __restrict__ q8, int64_t ldq8, float q8_scale, O... o) {
-    constexpr bool OPT = sizeof...(O) != 0;
+    constexpr bool OPT = ce_has<CeOpt, O...>::value, IGN = ce_has<CeIgn, O...>::value;
     const CeOpt opt = ce_opt(o...);
+    const CeIgn ign = ce_ign(o...);
     __shared__ float red[16];
     __shared__ float red2[OPT ? 16 : 1];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int row = blockIdx.x;
     const bf16_t* x = logits + (int64_t)row * ldl;
     int64_t t = targets[row];
+    if (IGN && t == ign.ignore_index) {                  // (workgroup-uniform, before any load of the row and any barrier; never with q8)
+        if (tid == 0) loss_rows[row] = 0.f;
+        if (dlogits) {
+            bf16x8 z;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) z[e] = (bf16_t)0.f;
+            for (int c = tid; c < (int)(ldd / 8); c += CE_BLOCK) *(bf16x8*)(dlogits + (int64_t)row * ldd + c * 8) = z;
+        }
+        return;
+    }
     t = t < 0 ? 0 : (t >= V ? V - 1 : t);
     const float xt = (float)x[t];                        // before any store of this row (in-place gradient)
     const int nchunk = (int)((dlogits && ldd > V ? ldd : (int64_t)V) + 7) / 8;      // chunks that exist in memory (ldl >= that * 8)
@@ -388,6 +458,7 @@ __global__ __launch_bounds__(CE_BLOCK, 8) void cross_entropy_row_bf16_kernel(con
         const float inv = OPT ? ce_pscale(mx, logf(s), opt) / s : 1.f / s;
         const float unif = OPT ? opt.eps / (float)V : 0.f;
         if (gs_dev) grad_scale *= gs_dev[0];
+        if (IGN) grad_scale *= ign.inv_count[0];
         const int dchunk = (int)(ldd / 8);
 #pragma unroll
         for (int j = 0; j < CE_MAXC; ++j) {
@@ -417,7 +488,7 @@ __global__ __launch_bounds__(CE_BLOCK, 8) void cross_entropy_row_bf16_kernel(con
     }
 }
 
-// O... opt: nothing (the three old entry points: the instantiations they always launched) or one CeOpt
+// O... opt: nothing (the three old entry points: the instantiations they always launched), one CeOpt, one CeIgn, or a CeOpt and a CeIgn
 template <typename... O>
 static int ce_launch(const void* logits_v, int logits_dtype, int64_t ldl, const int64_t* targets, float* loss_rows,
                      void* dlogits, int64_t ldd, int dtype, float grad_scale, const float* grad_scale_dev, int M, int V,
@@ -473,6 +544,7 @@ static int ce_launch(const void* logits_v, int logits_dtype, int64_t ldl, const 
                      unsigned char* q8, int64_t ldq8, float q8_scale, void* stream, O... opt) {
     if (!logits_v || !targets || !loss_rows || M <= 0 || V <= 0 || ldl < V) return DG_ERR_ARG;
     if (dlogits && ldd < V) return DG_ERR_ARG;
+    if (ce_has<CeIgn, O...>::value && q8) return DG_ERR_ARG;      // (the e5m2 scale rests on |dlogits| <= 1 / M: see dg_cross_entropy_fp8)
     if (logits_dtype != DG_F32 && logits_dtype != DG_BF16) return DG_ERR_DTYPE;
     if (logits_dtype == DG_BF16) {
         // bf16 logits: the whole-row kernel only (its in-place form is what they exist for); gradient in bf16
@@ -562,4 +634,59 @@ extern "C" int dg_cross_entropy_fused_smooth(const float* logits, int64_t ldl, c
                                       loss_part, loss_counter, loss_out, loss_scale, stream);
     return ce_fused_launch(logits, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, M, V, colsum_part, part_stride, n_partials,
                                  loss_part, loss_counter, loss_out, loss_scale, stream, CeOpt{label_smoothing, z_loss});
+}
+
+// {(float)N, 1.0f / (float)N}, N the number of targets that are not ignore_index: one workgroup, an integer sum (no order to fix), the
+// reciprocal one correctly rounded fp32 division (+inf at N = 0).  Everything the ignore forms below need to know about the batch.
+__global__ __launch_bounds__(1024) void ce_count_valid_kernel(const int64_t* __restrict__ targets, int M, int64_t ignore_index, float* __restrict__ out) {
+    __shared__ int red[16];
+    int n = 0;
+    for (int i = threadIdx.x; i < M; i += 1024) n += targets[i] != ignore_index ? 1 : 0;
+#pragma unroll
+    for (int sh = 32; sh > 0; sh >>= 1) n += __shfl_xor(n, sh, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int tot = 0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) tot += red[k];
+        const float nf = (float)tot;
+        out[0] = nf;
+        out[1] = __fdiv_rn(1.0f, nf);
+    }
+}
+
+extern "C" int dg_ce_count_valid(const int64_t* targets, int M, int64_t ignore_index, float* out, void* stream) {
+    if (!targets || !out || M <= 0) return DG_ERR_ARG;
+    hipLaunchKernelGGL(ce_count_valid_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, targets, M, ignore_index, out);
+    DG_LAUNCH_CHECK();
+    return DG_OK;
+}
+
+// rows whose target equals ignore_index left out; inv_count: device, 1 / N (the second word of dg_ce_count_valid's output).  With both
+// options zero the kernels are instantiated with the CeIgn alone.
+extern "C" int dg_cross_entropy_ignore(const void* logits_v, int logits_dtype, int64_t ldl, const int64_t* targets, float* loss_rows,
+                                       void* dlogits, int64_t ldd, int dtype, float grad_scale, const float* grad_scale_dev, int M, int V,
+                                       float label_smoothing, float z_loss, int64_t ignore_index, const float* inv_count, void* stream) {
+    if (!ce_opt_ok(label_smoothing, z_loss) || !inv_count) return DG_ERR_ARG;
+    const CeIgn ign{ignore_index, inv_count};
+    if (label_smoothing == 0.f && z_loss == 0.f)
+        return ce_launch(logits_v, logits_dtype, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, grad_scale_dev, M, V, nullptr, 0, 0.f,
+                         stream, ign);
+    return ce_launch(logits_v, logits_dtype, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, grad_scale_dev, M, V, nullptr, 0, 0.f,
+                     stream, CeOpt{label_smoothing, z_loss}, ign);
+}
+
+// loss_out = loss_scale * inv_count[0] * sum(rows); the column-sum partials hold the rows that count only
+extern "C" int dg_cross_entropy_fused_ignore(const float* logits, int64_t ldl, const int64_t* targets, float* loss_rows, void* dlogits, int64_t ldd,
+                                             int dtype, float grad_scale, int M, int V, float* colsum_part, int64_t part_stride, int n_partials,
+                                             float* loss_part, uint32_t* loss_counter, float* loss_out, float loss_scale,
+                                             float label_smoothing, float z_loss, int64_t ignore_index, const float* inv_count, void* stream) {
+    if (!ce_opt_ok(label_smoothing, z_loss) || !inv_count) return DG_ERR_ARG;
+    const CeIgn ign{ignore_index, inv_count};
+    if (label_smoothing == 0.f && z_loss == 0.f)
+        return ce_fused_launch(logits, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, M, V, colsum_part, part_stride, n_partials,
+                               loss_part, loss_counter, loss_out, loss_scale, stream, ign);
+    return ce_fused_launch(logits, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, M, V, colsum_part, part_stride, n_partials,
+                           loss_part, loss_counter, loss_out, loss_scale, stream, CeOpt{label_smoothing, z_loss}, ign);
 }

@@ -211,7 +211,7 @@ class TrainEngine:
                  dp_buckets: Optional[int] = None, logits: str = "auto", grad_stream: str = "auto", fp8_dw: Optional[bool] = None,
                  max_grad_norm: Optional[float] = None, accum_steps: int = 1, lr_schedule=None, schedule_steps: Optional[int] = None,
                  no_decay=(), label_smoothing: float = 0.0, z_loss: float = 0.0, ema_decay: Optional[float] = None,
-                 ema_warmup: bool = False):
+                 ema_warmup: bool = False, ignore_index: Optional[int] = None):
         if not isinstance(model, TransformerLM):
             raise TypeError("TrainEngine drives TransformerLM (the other five models train through the autograd path)")
         p0 = next(model.parameters())
@@ -255,6 +255,11 @@ class TrainEngine:
         # eval_losses stay the plain cross entropy.
         self.label_smoothing, self.z_loss = ops.check_loss_options(label_smoothing, z_loss)
         self._loss_kw = {k: v for k, v in (("label_smoothing", self.label_smoothing), ("z_loss", self.z_loss)) if v != 0.0}
+        # ignore_index (F.cross_entropy's; None: off, nothing below exists): a property of the targets, so it holds in every program
+        # with a loss head, evaluation included.  token_count = {N, 1 / N} of the batch the last loss head saw, written by one
+        # count launch right before it; the head's gradient scale is then 1.0 and the 1 / N comes from the device.
+        self.ignore_index = ops.check_loss_options(ignore_index=ignore_index)[2]
+        self.token_count = None if self.ignore_index is None else torch.zeros(2, dtype=torch.float32, device=self.dev)
         # an exponential moving average of the weights, moved on inside the AdamW launch (None: no average, nothing below exists)
         self.ema_decay = ops.check_ema_options(ema_decay, ema_warmup)
         self.ema_warmup = bool(ema_warmup)
@@ -322,6 +327,10 @@ class TrainEngine:
             # keeps and a z-loss does not (a gradient row sums to 2 z_loss lse / M)
             raise ValueError("z_loss > 0 cannot be combined with the fp8 loss head (precision 'fp8' at a large vocabulary): its "
                              "e5m2 gradient scale rests on |dlogits| <= 1 / M; label_smoothing can")
+        if self.fp8_head and self.ignore_index is not None:
+            raise ValueError("ignore_index cannot be combined with the fp8 loss head (precision 'fp8' at a large vocabulary): its "
+                             "e5m2 gradient scale rests on |dlogits| <= 1 / M, and with ignored rows the bound is 1 / N, which "
+                             "only the device knows")
         self.hyper = torch.tensor([lr, betas[0], betas[1], eps, weight_decay], dtype=torch.float32, device=self.dev)
         self.hyper_host = [float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay)]      # what state_dict() reports
         # lr_schedule: AdamW finds its rate in a table staged here once, by its own step word (dg_adamw_step_sched): hyper[0] is
@@ -706,6 +715,13 @@ class TrainEngine:
 
     def _head(self, run: S.Run, h: Tensor, y_idx: Optional[Tensor], want_grad: bool, saved, M: int):
         okw = self._loss_kw if want_grad else {}        # the objective's options: training programs only, evaluation stays plain
+        gs = 1.0 / M
+        if self.ignore_index is not None and y_idx is not None:
+            # the targets' option, in training and evaluation alike: count the rows that count (after the gather that may have
+            # drawn them), hand the kernels 1 / N on the device
+            ops.count_valid(y_idx.view(M), self.ignore_index, out=self.token_count)
+            okw = dict(okw, ignore_index=self.ignore_index, inv_count=self.token_count[1:])
+            gs = 1.0
         if self.bf16_logits and y_idx is not None and not self.keep_logits:
             # large vocabulary: lm_head writes bf16 logits into the buffer that becomes dlogits -- the cross-entropy kernel holds
             # a whole row in registers and overwrites it in place with its gradient (1.65 GB less written and 0.82 GB less read
@@ -722,13 +738,13 @@ class TrainEngine:
                 logits = ops.gemm_nt(xq, wq, self.act, scale_a=xs, scale_b=ws, bias=self.param_view("lm.b"), out=buf[:, :self.V])
                 if want_grad and M == self.M:
                     q8 = torch.empty((M, buf.shape[1]), dtype=S.E5M2, device=self.dev)
-                    rows = ops.cross_entropy_fp8(logits, y_idx.view(M), self.V, buf, 1.0 / M, q8, **okw)      # (z_loss: refused at construction)
+                    rows = ops.cross_entropy_fp8(logits, y_idx.view(M), self.V, buf, gs, q8, **okw)      # (z_loss, ignore_index: refused at construction)
                     buf.dg_q8 = (q8, self.dl_scale)
                 else:
-                    rows = ops.cross_entropy(logits, y_idx.view(M), self.V, dlogits=buf if want_grad else None, grad_scale=1.0 / M, **okw)
+                    rows = ops.cross_entropy(logits, y_idx.view(M), self.V, dlogits=buf if want_grad else None, grad_scale=gs, **okw)
                 return None, rows, (saved, h, buf)
             logits, (xa,) = S.linear_fwd(run, h, self.param_view("lm.w"), self.param_view("lm.b"), out=buf[:, :self.V])
-            rows = ops.cross_entropy(logits, y_idx.view(M), self.V, dlogits=buf if want_grad else None, grad_scale=1.0 / M, **okw)
+            rows = ops.cross_entropy(logits, y_idx.view(M), self.V, dlogits=buf if want_grad else None, grad_scale=gs, **okw)
             return None, rows, (saved, xa, buf)
         logits, (xa,) = S.linear_fwd(run, h, self.param_view("lm.w"), self.param_view("lm.b"), pad_rows=True)
         if y_idx is None:
@@ -739,10 +755,10 @@ class TrainEngine:
             if M == self.M and ops.cross_entropy_fused_supported(logits, dlogits, self.G):
                 # small vocabulary: the loss head in one launch -- gradient rows, the lm_head bias partials and the mean loss
                 part, stride, n = FlatSink(self).vector("lm.b", self.V)
-                rows = ops.cross_entropy_fused(logits, y_idx.view(M), self.V, dlogits, 1.0 / M, part, stride, n, self.loss_scratch,
-                                               self.loss, 1.0 / M, **okw)
+                rows = ops.cross_entropy_fused(logits, y_idx.view(M), self.V, dlogits, gs, part, stride, n, self.loss_scratch,
+                                               self.loss, gs, **okw)
                 return logits, rows, (saved, xa, dlogits, True)
-        rows = ops.cross_entropy(logits, y_idx.view(M), self.V, dlogits=dlogits, grad_scale=1.0 / M, **okw)
+        rows = ops.cross_entropy(logits, y_idx.view(M), self.V, dlogits=dlogits, grad_scale=gs, **okw)
         return logits, rows, (saved, xa, dlogits)
 
     def _backward_begin(self, run: S.Run, x_idx: Tensor, ctx) -> dict:
@@ -867,6 +883,17 @@ class TrainEngine:
                      fp8_sites=self.fp8_sites if self.fp8 else None, fp8_seed=seed, step_word=self.state, stream=self.stream_dtype,
                      fp8_only=self.fp8 and self.fp8_dw and self.grouped_dw and os.environ.get("DG_FP8_ONLY", "1") != "0")
 
+    def _mean_rows(self, rows: Tensor, out: Optional[Tensor] = None) -> Tensor:
+        """the mean of a loss head's rows: over all of them, or with ignore_index over the N that count (the count it just left)"""
+        if self.ignore_index is None:
+            return ops.reduce_sum(rows, 1.0 / rows.numel(), out=out)
+        return ops.reduce_sum(rows, 1.0, out=out, scale_dev=self.token_count[1:])
+
+    @property
+    def last_token_count(self) -> Optional[Tensor]:
+        """ignore_index: N, the targets that counted in the last loss head that ran (0-d device view; reading it synchronises)"""
+        return None if self.token_count is None else self.token_count[0]
+
     def _prog_front(self) -> dict:
         """gather the batch, forward, the loss, lm_head's backward: the step up to the backward pass of the residual blocks"""
         run = self._train_run()
@@ -874,7 +901,7 @@ class TrainEngine:
         if self.keep_logits:
             self.last_logits = logits
         if len(ctx) == 3:
-            ops.reduce_sum(rows, 1.0 / self.M, out=self.loss)
+            self._mean_rows(rows, self.loss)
         return self._backward_begin(run, self.x, ctx)
 
     def _prog_fwd_bwd(self):
@@ -1195,7 +1222,10 @@ class TrainEngine:
     def set_batch(self, x: Tensor, y: Tensor):
         """token / target ids of this rank's rows, given directly (ids are validated here; the captured step never checks)"""
         ops.check_ids(x, self.V, "x")
-        ops.check_ids(y, self.V, "y")
+        if self.ignore_index is None:
+            ops.check_ids(y, self.V, "y")
+        else:
+            ops.check_ids(y, self.V, "y", allow=self.ignore_index)
         self.x.copy_(x, non_blocking=True)
         self.y.copy_(y, non_blocking=True)
 
@@ -1249,7 +1279,7 @@ class TrainEngine:
         """forward only, dropout off (ref: evaluate_loss, src/train.py:61-75)"""
         run = S.Run(act=self.act, rng=None, weights=self.weights, fp8=self.fp8, split=self.split_bf16)
         _, rows, _ = self._forward(run, x, y, False)
-        return ops.reduce_sum(rows, 1.0 / rows.numel())
+        return self._mean_rows(rows)
 
     @torch.no_grad()
     def eval_losses(self, data: Tensor, offsets: Tensor) -> Tensor:
@@ -1274,7 +1304,7 @@ class TrainEngine:
             def prog():
                 run = S.Run(act=self.act, rng=None, weights=self.weights, fp8=self.fp8, split=self.split_bf16)
                 _, rows, _ = self._forward(run, self.ev_x, self.ev_y, False)
-                ops.reduce_sum(rows, 1.0 / rows.numel(), out=self.ev_loss)
+                self._mean_rows(rows, self.ev_loss)
             self._eval_graph, = capture_after_warmup(self.dev, [prog])
         for i in range(n):
             ops.batch_gather(data, offsets[i], self.T, self.ev_x, self.ev_y)
@@ -1290,6 +1320,8 @@ class TrainEngine:
                 "num_heads": int(self.NH), "model_context_length": int(self.model.context_length), "batch_size": self.B,
                 "context_length": self.T, "accum_steps": self.accum, "world_size": int(self.world), "dropout": self.p_drop}
         meta.update(self._loss_kw)      # only where set: a default engine writes and accepts exactly the files it always did
+        if self.ignore_index is not None:
+            meta["ignore_index"] = self.ignore_index
         if self.ema is not None:
             meta["ema"] = True
         return meta
@@ -1297,12 +1329,15 @@ class TrainEngine:
     def _check_meta(self, saved: dict) -> None:
         """CK.check_compat on the fields every engine has; the loss options in both directions (a field absent on either side reads
         as 0.0: a smoothed state is refused by a default engine as much as the reverse)"""
-        CK.check_compat(saved, {k: v for k, v in self._meta().items() if k not in self._LOSS_FIELDS and k != "ema"})
+        CK.check_compat(saved, {k: v for k, v in self._meta().items() if k not in self._LOSS_FIELDS and k not in ("ema", "ignore_index")})
         CK.check_ema_meta(saved, self.ema is not None)
         for field in self._LOSS_FIELDS:
             theirs, own = saved.get(field, 0.0), self._loss_kw.get(field, 0.0)
             if isinstance(theirs, bool) or not isinstance(theirs, (int, float)) or float(theirs) != own:
                 raise ValueError(f"training state: meta.{field} differs: saved {theirs!r}, this run has {own!r}")
+        theirs = saved.get("ignore_index")
+        if isinstance(theirs, bool) or not (theirs is None or isinstance(theirs, int)) or theirs != self.ignore_index:
+            raise ValueError(f"training state: meta.ignore_index differs: saved {theirs!r}, this run has {self.ignore_index!r}")
 
     def _param_names(self) -> List[str]:
         return [n for n, _ in self.model.named_parameters()]

@@ -128,15 +128,25 @@ class LinearFn(torch.autograd.Function):
 
 class CrossEntropyFn(torch.autograd.Function):
     """mean cross entropy over the rows of logits [M,V] (ref: src/model.py:606-607); with label_smoothing / z_loss the mean of
-    the row objectives of ops.cross_entropy"""
+    the row objectives of ops.cross_entropy; with ignore_index the mean over the rows whose target is not ignore_index, counted
+    once on the device in forward (no sync) and reused in backward"""
 
     @staticmethod
-    def forward(ctx, logits: Tensor, targets: Tensor, label_smoothing: float = 0.0, z_loss: float = 0.0):
+    def forward(ctx, logits: Tensor, targets: Tensor, label_smoothing: float = 0.0, z_loss: float = 0.0, ignore_index=None):
         M, V = logits.shape
         logits = logits.contiguous()
-        ctx.opts = dict(zip(("label_smoothing", "z_loss"), ops.check_loss_options(label_smoothing, z_loss)))
-        rows = ops.cross_entropy(logits, targets, V, **ctx.opts)
-        loss = ops.reduce_sum(rows, 1.0 / M)
+        eps, zeta, ign = ops.check_loss_options(label_smoothing, z_loss, ignore_index)
+        ctx.opts = {"label_smoothing": eps, "z_loss": zeta}
+        ctx.inv_count = None
+        if ign is None:
+            rows = ops.cross_entropy(logits, targets, V, **ctx.opts)
+            loss = ops.reduce_sum(rows, 1.0 / M)
+        else:
+            targets = targets.contiguous()
+            ctx.opts["ignore_index"] = ign
+            ctx.inv_count = ops.count_valid(targets, ign)[1:]
+            rows = ops.cross_entropy(logits, targets, V, inv_count=ctx.inv_count, **ctx.opts)
+            loss = ops.reduce_sum(rows, 1.0, scale_dev=ctx.inv_count)
         ctx.save_for_backward(logits, targets)
         return loss
 
@@ -146,9 +156,9 @@ class CrossEntropyFn(torch.autograd.Function):
         M, V = logits.shape
         dlogits = torch.empty_like(logits)
         rows = torch.empty((M,), dtype=torch.float32, device=logits.device)
-        ops.cross_entropy(logits, targets, V, dlogits=dlogits, grad_scale=1.0 / M,
-                          grad_scale_dev=dloss.contiguous().to(torch.float32), loss_rows=rows, **ctx.opts)
-        return dlogits, None, None, None
+        ops.cross_entropy(logits, targets, V, dlogits=dlogits, grad_scale=1.0 / M if ctx.inv_count is None else 1.0,
+                          grad_scale_dev=dloss.contiguous().to(torch.float32), loss_rows=rows, inv_count=ctx.inv_count, **ctx.opts)
+        return dlogits, None, None, None, None
 
 
 def embed(idx, tok, pos):
@@ -167,5 +177,5 @@ def linear(x, w, b, act):
     return LinearFn.apply(x, w, b, act)
 
 
-def cross_entropy(logits, targets, label_smoothing=0.0, z_loss=0.0):
-    return CrossEntropyFn.apply(logits, targets, label_smoothing, z_loss)
+def cross_entropy(logits, targets, label_smoothing=0.0, z_loss=0.0, ignore_index=None):
+    return CrossEntropyFn.apply(logits, targets, label_smoothing, z_loss, ignore_index)

@@ -128,22 +128,25 @@ class _LM(HipModule):
         V = self.token_embedding_table.weight.shape[0]
         ops.check_ids(idx, V, "idx")
         if targets is not None:
-            ops.check_ids(targets, V if not hasattr(self, "lm_head") else self.lm_head.weight.shape[0], "targets")
+            ops.check_ids(targets, V if not hasattr(self, "lm_head") else self.lm_head.weight.shape[0], "targets", allow=self.ignore_index)
 
     # the training objective's options: plain attributes, not part of the state_dict; forward applies them in train() mode only
     label_smoothing = 0.0
     z_loss = 0.0
+    ignore_index = None
 
-    def set_loss_options(self, label_smoothing=0.0, z_loss=0.0):
+    def set_loss_options(self, label_smoothing=0.0, z_loss=0.0, ignore_index=None):
         """label smoothing (F.cross_entropy's label_smoothing) and the z-loss coefficient (z_loss * logsumexp^2 per row) of
-        the loss forward(idx, targets) returns in train() mode; in eval() it stays the plain cross entropy, the reference's metric"""
-        self.label_smoothing, self.z_loss = ops.check_loss_options(label_smoothing, z_loss)
+        the loss forward(idx, targets) returns in train() mode; in eval() it stays the plain cross entropy, the reference's metric.
+        ignore_index (F.cross_entropy's ignore_index; None: off, -100: the reference's behaviour) describes the targets, not the
+        objective: a target equal to it is left out of the mean, in train() and in eval()."""
+        self.label_smoothing, self.z_loss, self.ignore_index = ops.check_loss_options(label_smoothing, z_loss, ignore_index)
         return self
 
     def _loss(self, logits, targets):
         if self.training:
-            return HF.cross_entropy(logits, targets, self.label_smoothing, self.z_loss)
-        return HF.cross_entropy(logits, targets)
+            return HF.cross_entropy(logits, targets, self.label_smoothing, self.z_loss, self.ignore_index)
+        return HF.cross_entropy(logits, targets, ignore_index=self.ignore_index)
 
     def forward(self, idx, targets=None):
         if idx.dim() != 2:

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import numbers
 from typing import Optional
 
 import torch
@@ -56,13 +57,17 @@ def _ld(t: Tensor) -> int:
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
 
 
-def check_ids(ids: Tensor, n: int, what: str) -> None:
-    """raise IndexError unless 0 <= ids < n -- what nn.Embedding / F.cross_entropy do in the reference (ref: src/model.py:595,
+def check_ids(ids: Tensor, n: int, what: str, allow: Optional[int] = None) -> None:
+    """raise IndexError unless 0 <= ids < n (or ids == allow: the targets' ignore_index) -- what nn.Embedding / F.cross_entropy do in the reference (ref: src/model.py:595,
     606).  The kernels clamp ids so that a bad one can never fault the GPU, which would otherwise turn a tokenizer / vocabulary
     mismatch into a plausible loss on aliased ids.  One device round trip: call it where ids ENTER (module forward, set_corpus,
     set_batch), never inside a captured step."""
     if ids.numel() == 0:
         return
+    if allow is not None and not 0 <= allow < n:
+        ids = ids[ids != allow]
+        if ids.numel() == 0:
+            return
     lo, hi = torch.aminmax(ids)
     lo, hi = int(lo), int(hi)
     if lo < 0 or hi >= n:
@@ -675,9 +680,22 @@ def attn_decode(cache: Tensor, t: int, NH: int, H: int, scale: float) -> Tensor:
     return out
 
 
-def check_loss_options(label_smoothing=0.0, z_loss=0.0):
-    """the checks of the two loss options, plain Python, raised before anything touches a device: label_smoothing in [0, 1)
-    (F.cross_entropy's label_smoothing), z_loss >= 0 and finite (the coefficient of logsumexp^2).  Returns both as floats."""
+_NO_IGNORE = object()
+
+
+def check_loss_options(label_smoothing=0.0, z_loss=0.0, ignore_index=_NO_IGNORE):
+    """the checks of the loss options, plain Python, raised before anything touches a device: label_smoothing in [0, 1)
+    (F.cross_entropy's label_smoothing), z_loss >= 0 and finite (the coefficient of logsumexp^2).  Returns both as floats.
+    Called with ignore_index (F.cross_entropy's ignore_index: None, or an int that fits int64 -- never a bool or a float) it checks
+    that too and returns all three."""
+    if ignore_index is not _NO_IGNORE:
+        if ignore_index is not None:
+            if isinstance(ignore_index, bool) or not isinstance(ignore_index, numbers.Integral):
+                raise ValueError(f"ignore_index must be None or an int, got {ignore_index!r}")
+            ignore_index = int(ignore_index)
+            if not -(1 << 63) <= ignore_index < (1 << 63):
+                raise ValueError(f"ignore_index must fit int64, got {ignore_index!r}")
+        return (*check_loss_options(label_smoothing, z_loss), ignore_index)
     out = []
     for name, x in (("label_smoothing", label_smoothing), ("z_loss", z_loss)):
         if isinstance(x, bool):
@@ -696,10 +714,14 @@ def check_loss_options(label_smoothing=0.0, z_loss=0.0):
 
 def cross_entropy(logits: Tensor, targets: Tensor, V: int, dlogits: Optional[Tensor] = None, grad_scale: float = 1.0,
                   grad_scale_dev: Optional[Tensor] = None, loss_rows: Optional[Tensor] = None, *,
-                  label_smoothing: float = 0.0, z_loss: float = 0.0) -> Tensor:
+                  label_smoothing: float = 0.0, z_loss: float = 0.0, ignore_index: Optional[int] = None,
+                  inv_count: Optional[Tensor] = None) -> Tensor:
     """per-row objective (and, with dlogits, its gradient times grad_scale): the plain NLL, or with label_smoothing / z_loss
-    lse - (1 - eps) x_t - (eps / V) sum x + z_loss lse^2 (dg_cross_entropy_smooth)"""
-    eps, zeta = check_loss_options(label_smoothing, z_loss)
+    lse - (1 - eps) x_t - (eps / V) sum x + z_loss lse^2 (dg_cross_entropy_smooth).  With ignore_index a row whose target equals it
+    gets a zero objective and a zero gradient row, and the other gradient rows are also scaled by inv_count[0], the device's 1 / N
+    (count_valid(targets, ignore_index)[1:]; dg_cross_entropy_ignore)."""
+    eps, zeta, ignore_index = check_loss_options(label_smoothing, z_loss, ignore_index)
+    _chk_inv_count("cross_entropy", ignore_index, inv_count)
     _chk(logits, "logits", contiguous=False)              # fp32, or bf16 (large vocabularies: dlogits may then BE logits)
     if logits.dtype not in (torch.float32, torch.bfloat16):
         raise TypeError("cross_entropy: logits must be float32 or bfloat16")
@@ -711,7 +733,11 @@ def cross_entropy(logits: Tensor, targets: Tensor, V: int, dlogits: Optional[Ten
     if dlogits is not None:
         _chk(dlogits, "dlogits", contiguous=False)
         ldd, dcode = _ld(dlogits), dt_code(dlogits.dtype)
-    if eps == 0.0 and zeta == 0.0:
+    if ignore_index is not None:
+        check(lib.dg_cross_entropy_ignore(_p(logits), dt_code(logits.dtype), _ld(logits), _p(targets), _p(loss_rows), _p(dlogits), ldd, dcode,
+                                          float(grad_scale), _p(grad_scale_dev), M, V, eps, zeta, ignore_index, _p(inv_count), _stream()),
+              "dg_cross_entropy_ignore")
+    elif eps == 0.0 and zeta == 0.0:
         check(lib.dg_cross_entropy(_p(logits), dt_code(logits.dtype), _ld(logits), _p(targets), _p(loss_rows), _p(dlogits), ldd, dcode, float(grad_scale),
                                    _p(grad_scale_dev), M, V, _stream()), "dg_cross_entropy")
     else:
@@ -721,10 +747,14 @@ def cross_entropy(logits: Tensor, targets: Tensor, V: int, dlogits: Optional[Ten
 
 
 def cross_entropy_fp8(logits: Tensor, targets: Tensor, V: int, dlogits: Tensor, grad_scale: float, dlogits_fp8: Tensor, *,
-                      label_smoothing: float = 0.0) -> Tensor:
+                      label_smoothing: float = 0.0, ignore_index: Optional[int] = None) -> Tensor:
     """cross_entropy on bf16 logits (gradient in bf16, possibly in place) that also writes the gradient as e5m2 with the a-priori
     scale 57344 / grad_scale into dlogits_fp8 [M, ld8 >= V] (pad columns zeroed); dequantisation factor: grad_scale / 57344.
-    label_smoothing keeps |dlogits| <= grad_scale, on which that scale rests; a z-loss does not, so there is no z_loss here."""
+    label_smoothing keeps |dlogits| <= grad_scale, on which that scale rests; a z-loss does not, so there is no z_loss here; with
+    ignore_index the bound would be the device's 1 / N, so that is refused too."""
+    if ignore_index is not None:
+        raise ValueError("cross_entropy_fp8 takes no ignore_index: its e5m2 gradient scale rests on |dlogits| <= grad_scale = 1 / M, and "
+                         "with ignored rows the bound is 1 / N, which only the device knows")
     eps, _ = check_loss_options(label_smoothing, 0.0)
     _chk(logits, "logits", torch.bfloat16, contiguous=False)
     _chk(targets, "targets", torch.int64)
@@ -747,12 +777,15 @@ def cross_entropy_fused_supported(logits: Tensor, dlogits: Tensor, n_partials: i
 
 def cross_entropy_fused(logits: Tensor, targets: Tensor, V: int, dlogits: Tensor, grad_scale: float, colsum_part: Optional[Tensor],
                         part_stride: int, n_partials: int, loss_scratch: Optional[Tensor], loss_out: Optional[Tensor], loss_scale: float,
-                        loss_rows: Optional[Tensor] = None, *, label_smoothing: float = 0.0, z_loss: float = 0.0) -> Tensor:
+                        loss_rows: Optional[Tensor] = None, *, label_smoothing: float = 0.0, z_loss: float = 0.0,
+                        ignore_index: Optional[int] = None, inv_count: Optional[Tensor] = None) -> Tensor:
     """cross_entropy + column-sum partials of dlogits (n_partials rows of part_stride floats) + loss_out = loss_scale * sum(rows)
     in one launch (V <= 128).  loss_scratch: fp32 [n_partials + 1], its LAST word the arrival counter (zero before the first
     launch; the kernel leaves it at zero).  Returns the per-row losses (with label_smoothing / z_loss: the per-row objectives,
-    and partials that no longer add up to zero once z_loss > 0)."""
-    eps, zeta = check_loss_options(label_smoothing, z_loss)
+    and partials that no longer add up to zero once z_loss > 0).  With ignore_index: as in cross_entropy, the partials hold the
+    rows that count and loss_out = loss_scale * inv_count[0] * sum(rows)."""
+    eps, zeta, ignore_index = check_loss_options(label_smoothing, z_loss, ignore_index)
+    _chk_inv_count("cross_entropy_fused", ignore_index, inv_count)
     _chk(logits, "logits", torch.float32, contiguous=False)
     _chk(targets, "targets", torch.int64)
     _chk(dlogits, "dlogits", contiguous=False)
@@ -771,17 +804,52 @@ def cross_entropy_fused(logits: Tensor, targets: Tensor, V: int, dlogits: Tensor
     head = (_p(logits), _ld(logits), _p(targets), _p(loss_rows), _p(dlogits), _ld(dlogits), dt_code(dlogits.dtype),
             float(grad_scale), M, V, _p(colsum_part), part_stride, n_partials,
             _p(loss_scratch) if loss_out is not None else None, cnt, _p(loss_out), float(loss_scale))
-    if eps == 0.0 and zeta == 0.0:
+    if ignore_index is not None:
+        check(lib.dg_cross_entropy_fused_ignore(*head, eps, zeta, ignore_index, _p(inv_count), _stream()), "dg_cross_entropy_fused_ignore")
+    elif eps == 0.0 and zeta == 0.0:
         check(lib.dg_cross_entropy_fused(*head, _stream()), "dg_cross_entropy_fused")
     else:
         check(lib.dg_cross_entropy_fused_smooth(*head, eps, zeta, _stream()), "dg_cross_entropy_fused_smooth")
     return loss_rows
 
 
-def reduce_sum(x: Tensor, scale: float, out: Optional[Tensor] = None) -> Tensor:
+def _chk_inv_count(what: str, ignore_index, inv_count) -> None:
+    if ignore_index is None:
+        if inv_count is not None:
+            raise ValueError(f"{what}: inv_count without ignore_index")
+        return
+    if inv_count is None:
+        raise ValueError(f"{what}: ignore_index needs inv_count, the device's 1 / N (count_valid(targets, ignore_index)[1:])")
+    _chk(inv_count, "inv_count", torch.float32)
+    if inv_count.numel() < 1:
+        raise ValueError(f"{what}: inv_count is empty")
+
+
+def count_valid(targets: Tensor, ignore_index: int, out: Optional[Tensor] = None) -> Tensor:
+    """fp32 [2] = {N, 1 / N}, N the number of targets that are not ignore_index (dg_ce_count_valid: one small launch, no sync)"""
+    _, _, ignore_index = check_loss_options(ignore_index=ignore_index)
+    if ignore_index is None:
+        raise ValueError("count_valid: ignore_index must be an int")
+    _chk(targets, "targets", torch.int64)
+    if out is None:
+        out = torch.empty((2,), dtype=torch.float32, device=targets.device)
+    else:
+        _chk(out, "out", torch.float32)
+        if out.numel() < 2:
+            raise ValueError("count_valid: out needs two words")
+    check(lib.dg_ce_count_valid(_p(targets), targets.numel(), ignore_index, _p(out), _stream()), "dg_ce_count_valid")
+    return out
+
+
+def reduce_sum(x: Tensor, scale: float, out: Optional[Tensor] = None, scale_dev: Optional[Tensor] = None) -> Tensor:
+    """out = scale * sum(x); with scale_dev (fp32, on the device) out = scale * scale_dev[0] * sum(x), the same order"""
     _chk(x, "x", torch.float32)
     if out is None:
         out = torch.empty((), dtype=torch.float32, device=x.device)
+    if scale_dev is not None:
+        _chk(scale_dev, "scale_dev", torch.float32)
+        check(lib.dg_reduce_sum_scaled(_p(x), x.numel(), float(scale), _p(scale_dev), _p(out), _stream()), "dg_reduce_sum_scaled")
+        return out
     check(lib.dg_reduce_sum(_p(x), x.numel(), float(scale), _p(out), _stream()), "dg_reduce_sum")
     return out
 

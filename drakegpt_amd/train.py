@@ -234,6 +234,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--z-loss", type=float, default=0.0, metavar="Z",
                     help="add Z * logsumexp(logits)^2 per row to the training objective (default 0: off; not with the fp8 loss head: "
                     "--precision fp8 at a large vocabulary)")
+    ap.add_argument("--ignore-token", type=int, default=None, metavar="ID",
+                    help="leave every position whose target is token ID out of the loss, in training and in the evaluation lines; each "
+                    "batch's mean is over the targets that remain (F.cross_entropy's ignore_index; default: off).  A resumed run must "
+                    "repeat it; not with the fp8 loss head (--precision fp8 at a large vocabulary)")
     ap.add_argument("--ema-decay", type=float, default=None, metavar="D",
                     help="keep an exponential moving average of the weights, ema += (w - ema) * (1 - D) after every optimizer step, "
                     "in (0, 1) (default: off).  Evaluation lines gain val_loss_ema, the final sample is drawn from the average and "
@@ -265,6 +269,10 @@ def parse_args(argv=None):
     except ValueError as e:
         ap.error(f"--label-smoothing / --z-loss: {e}")
     try:
+        args.ignore_token = check_loss_options(ignore_index=args.ignore_token)[2]
+    except ValueError as e:
+        ap.error(f"--ignore-token: {e}")
+    try:
         args.ema_decay = check_ema_options(args.ema_decay, args.ema_warmup)
     except ValueError as e:
         ap.error(f"--ema-decay / --ema-warmup: {e}")
@@ -295,7 +303,9 @@ def run_args(args, K: int, world: int) -> dict:
             "no_decay": list(args.no_decay), "label_smoothing": float(args.label_smoothing), "z_loss": float(args.z_loss),
             "ema_decay": None if args.ema_decay is None else float(args.ema_decay), "ema_warmup": bool(args.ema_warmup),
             # the table's length: the step count the schedule was laid out over
-            "schedule_iters": None if args.lr_schedule == "reference" else int(args.iters)}
+            "schedule_iters": None if args.lr_schedule == "reference" else int(args.iters),
+            # (only where set: a run without it writes the file it always wrote; load_run_state compares it in both directions)
+            **({} if getattr(args, "ignore_token", None) is None else {"ignore_token": int(args.ignore_token)})}
 
 
 RUN_ARG_DEFAULTS = {"lr_schedule": "reference", "warmup_steps": 0, "min_lr": 0.0, "no_decay": [], "schedule_iters": None,
@@ -334,6 +344,9 @@ def load_run_state(path: str, must_match: dict) -> dict:
         saved = st["args"].get(field, RUN_ARG_DEFAULTS.get(field, "<absent>"))
         if saved != own:
             raise SystemExit(f"--resume: {field} differs: {path} was written with {saved!r}, this run has {own!r}")
+    saved, own = st["args"].get("ignore_token"), must_match.get("ignore_token")
+    if saved != own:
+        raise SystemExit(f"--resume: ignore_token differs: {path} was written with {saved!r}, this run has {own!r}")
     return st
 
 
@@ -388,12 +401,14 @@ def main(argv=None):
         engine = TrainEngine(model, B, T, lr=base_lr, betas=params["betas"], seed=42, rank=rank, world_size=world, process_group=pg,
                              max_grad_norm=args.grad_clip, accum_steps=K, lr_schedule=table, no_decay=args.no_decay,
                              label_smoothing=args.label_smoothing, z_loss=args.z_loss,
+                             **({} if args.ignore_token is None else {"ignore_index": args.ignore_token}),
                              **({} if args.ema_decay is None else {"ema_decay": args.ema_decay, "ema_warmup": args.ema_warmup}))
         engine.set_corpus(train_dev)
     else:
         # the five earlier-stage models train through the autograd path; their flat-buffer AdamW all-reduces the gradient
         from .optim import AdamW
-        model.set_loss_options(args.label_smoothing, args.z_loss)      # (train() mode only: evaluate_loss runs in eval())
+        # (smoothing / z-loss in train() mode only: evaluate_loss runs in eval(); the ignored token in both)
+        model.set_loss_options(args.label_smoothing, args.z_loss, **({} if args.ignore_token is None else {"ignore_index": args.ignore_token}))
         groups = model.parameters()
         if args.no_decay:
             groups = no_decay_groups(model, args.no_decay)

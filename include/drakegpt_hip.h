@@ -456,8 +456,30 @@ int dg_cross_entropy_fused_smooth(const float* logits, int64_t ldl, const int64_
                                   int dtype, float grad_scale, int M, int V, float* colsum_part, int64_t part_stride, int n_partials,
                                   float* loss_part, uint32_t* loss_counter, float* loss_out, float loss_scale,
                                   float label_smoothing, float z_loss, void* stream);
+/* ignore_index (F.cross_entropy(ignore_index=)): rows whose target equals ignore_index -- any int64, inside [0, V) or not -- are
+ * left out, and the mean is taken over the N rows that remain.
+ *   dg_ce_count_valid: out[0] = (float)N, out[1] = 1.0f / (float)N (one correctly rounded fp32 division; +inf at N = 0), N = #{m <
+ *   M : targets[m] != ignore_index}.  One launch of one workgroup, an integer sum, no host involvement: safe under graph capture.
+ *   dg_cross_entropy_ignore / dg_cross_entropy_fused_ignore: dg_cross_entropy_smooth / dg_cross_entropy_fused_smooth with
+ *     loss_rows[m] = keep_m l_m                            (an ignored row: exactly 0)
+ *     dlogits[m,n] = keep_m g_mn grad_scale inv_count[0]   (an ignored row: STORED as zeros, columns V .. ldd - 1 included, in place too)
+ *   l, g the row objective and gradient above, inv_count a device pointer to 1 / N (out + 1 of dg_ce_count_valid; NULL: DG_ERR_ARG).
+ *   An ignored row is recognised from its target before any of its logits is read.  The fused head's column-sum partials hold the
+ *   rows that count and loss_out = loss_scale * inv_count[0] * sum of loss_rows; elsewhere dg_reduce_sum_scaled gives the mean.
+ *   Targets that are neither ignore_index nor in [0, V) are clamped as in every entry above.  N = 0: the mean is NaN (0 * inf, as
+ *   torch's) and every gradient row is zeros (torch's are NaN).  There is no fp8 form: the e5m2 scale rests on |dlogits| <= 1 / M. */
+int dg_ce_count_valid(const int64_t* targets, int M, int64_t ignore_index, float* out, void* stream);
+int dg_cross_entropy_ignore(const void* logits, int logits_dtype, int64_t ldl, const int64_t* targets, float* loss_rows,
+                            void* dlogits, int64_t ldd, int dtype, float grad_scale, const float* grad_scale_dev, int M, int V,
+                            float label_smoothing, float z_loss, int64_t ignore_index, const float* inv_count, void* stream);
+int dg_cross_entropy_fused_ignore(const float* logits, int64_t ldl, const int64_t* targets, float* loss_rows, void* dlogits, int64_t ldd,
+                                  int dtype, float grad_scale, int M, int V, float* colsum_part, int64_t part_stride, int n_partials,
+                                  float* loss_part, uint32_t* loss_counter, float* loss_out, float loss_scale,
+                                  float label_smoothing, float z_loss, int64_t ignore_index, const float* inv_count, void* stream);
 /* out[0] = scale * sum_i x[i] (single workgroup, fixed order). */
 int dg_reduce_sum(const float* x, int64_t n, float scale, float* out, void* stream);
+/* out[0] = scale * scale_dev[0] * sum_i x[i]: dg_reduce_sum's order, one more factor read on the device. */
+int dg_reduce_sum_scaled(const float* x, int64_t n, float scale, const float* scale_dev, float* out, void* stream);
 
 /* probs = softmax(logits) row-wise, fp32 -- ref: F.softmax at src/model.py:631 (generate). */
 int dg_softmax_rows(const float* logits, int64_t ldl, float* probs, int64_t ldp, int M, int V,
