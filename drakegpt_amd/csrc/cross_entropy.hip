@@ -5,6 +5,7 @@
 // Algorithmic bytes per row: V*4 read (+ V*sizeof(dlogits) written when training).
 #include "common.h"
 #include <float.h>
+#include <type_traits>
 
 // Loss options, a compile-time switch of every kernel below: the kernels end in a parameter pack `O... o` that is either empty (the
 // plain mean NLL: the code and the kernel arguments it always had) or one CeOpt (OPT below):
@@ -22,8 +23,6 @@ struct CeOpt { float eps, zeta; };
 // workgroup-per-row kernels.  The other rows' gradients are scaled by inv_count[0] = 1 / N, N the number of rows that count, which
 // only the device knows (dg_ce_count_valid writes it); the mean of loss_rows takes the same factor (dg_reduce_sum_scaled, or the
 // fused kernel's last workgroup).  N = 0: inv_count is +inf, nothing is multiplied by it, every gradient row is zeros.
-// The ignore forms without a CeOpt write the row loss as log s + (mx - x_t), the order the options use (nothing rounds at the size of mx:
-// logits shifted by +1000 keep 1e-6); the plain instantiations keep mx + log s - x_t, the code they always had.
 struct CeIgn { int64_t ignore_index; const float* inv_count; };
 template <typename T, typename... O> struct ce_has { static constexpr bool value = false; };
 template <typename T, typename U, typename... O> struct ce_has<T, U, O...> { static constexpr bool value = ce_has<T, O...>::value; };
@@ -36,32 +35,65 @@ __device__ __forceinline__ CeIgn ce_ign() { return CeIgn{0, nullptr}; }
 __device__ __forceinline__ CeIgn ce_ign(CeOpt) { return CeIgn{0, nullptr}; }
 __device__ __forceinline__ CeIgn ce_ign(CeIgn ign) { return ign; }
 __device__ __forceinline__ CeIgn ce_ign(CeOpt, CeIgn ign) { return ign; }
+
+// The pack resolved: every kernel opens with `const CePack<O...> p{ce_opt(o...), ce_ign(o...)}` and hands p.OPT, p.IGN, p.opt and p.ign to
+// the row math below, which takes and returns values.
+template <typename... O> struct CePack {
+    static constexpr bool OPT = ce_has<CeOpt, O...>::value, IGN = ce_has<CeIgn, O...>::value;
+    CeOpt opt;
+    CeIgn ign;
+};
+// The row loss from mx, logs = log s, xt = x_t and sd = sum_{i < V} (mx - x_i) (read under OPT only).  The plain instantiations keep
+// mx + log s - x_t, the code they always had.  The ignore forms without a CeOpt write log s + (mx - x_t), the order the options use
+// (nothing rounds at the size of mx: logits shifted by +1000 keep 1e-6).  The bf16 whole-row kernel has an order of its own.
 __device__ __forceinline__ float ce_objective(float mx, float logs, float xt, float sd, int V, CeOpt opt) {
     const float lse = mx + logs;
     return logs + (1.f - opt.eps) * (mx - xt) + opt.eps / (float)V * sd + opt.zeta * lse * lse;
 }
+template <bool OPT, bool IGN>
+__device__ __forceinline__ float ce_row_loss(float mx, float logs, float xt, float sd, int V, CeOpt opt) {
+    return OPT ? ce_objective(mx, logs, xt, sd, V, opt) : IGN ? logs + (mx - xt) : mx + logs - xt;
+}
+// The gradient element is (e_i inv - (1 - eps) [i == t] - unif) scale with e_i = exp(x_i - mx), inv = ce_inv(), unif = ce_unif():
 // p_i enters the gradient times 1 + 2 zeta lse; the target's one-hot weighs 1 - eps; every column gives up eps / V
 __device__ __forceinline__ float ce_pscale(float mx, float logs, CeOpt opt) { return 1.f + 2.f * opt.zeta * (mx + logs); }
-__device__ __forceinline__ float ce_grad(float p, bool hot, float unif, CeOpt opt, float grad_scale) {
-    return (p - (hot ? 1.f - opt.eps : 0.f) - unif) * grad_scale;
+template <bool OPT> __device__ __forceinline__ float ce_inv(float mx, float logs, float s, CeOpt opt) {
+    return OPT ? ce_pscale(mx, logs, opt) / s : 1.f / s;
+}
+template <bool OPT> __device__ __forceinline__ float ce_unif(int V, CeOpt opt) { return OPT ? opt.eps / (float)V : 0.f; }
+template <bool OPT> __device__ __forceinline__ float ce_grad(float p, bool hot, float unif, CeOpt opt, float grad_scale) {
+    return OPT ? (p - (hot ? 1.f - opt.eps : 0.f) - unif) * grad_scale : (p - (hot ? 1.f : 0.f)) * grad_scale;
+}
+__device__ __forceinline__ int64_t ce_clamp_target(int64_t t, int V) { return t < 0 ? 0 : (t >= V ? V - 1 : t); }
+// An ignored row: loss 0 and, where there is a gradient, exact zeros over all ldd columns of its row; the thread stores columns
+// first, first + stride, ...  The 16-byte form for bf16x8 rows follows.  (The two rows-in-registers kernels store their <= 8 columns
+// per lane unrolled, the fused one inside its row loop.)
+template <typename TD>
+__device__ __forceinline__ void ce_zero_row(float* loss_rows, TD* dlogits, int64_t ldd, int row, int first, int stride) {
+    if (first == 0) loss_rows[row] = 0.f;
+    if (dlogits)
+        for (int i = first; i < (int)ldd; i += stride) dlogits[(int64_t)row * ldd + i] = from_f32<TD>(0.f);
+}
+__device__ __forceinline__ void ce_zero_row_x8(float* loss_rows, bf16_t* dlogits, int64_t ldd, int row, int first, int stride) {
+    if (first == 0) loss_rows[row] = 0.f;
+    if (!dlogits) return;
+    bf16x8 z;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) z[e] = (bf16_t)0.f;
+    for (int c = first; c < (int)(ldd / 8); c += stride) *(bf16x8*)(dlogits + (int64_t)row * ldd + c * 8) = z;
 }
 
 template <typename TD, typename TL = float, typename... O>
 __global__ void cross_entropy_kernel(const TL* __restrict__ logits, int64_t ldl, const int64_t* __restrict__ targets,
                                      float* __restrict__ loss_rows, TD* __restrict__ dlogits, int64_t ldd,
                                      float grad_scale, const float* __restrict__ gs_dev, int M, int V, O... o) {
-    constexpr bool OPT = ce_has<CeOpt, O...>::value, IGN = ce_has<CeIgn, O...>::value;
-    const CeOpt opt = ce_opt(o...);
-    const CeIgn ign = ce_ign(o...);
+    const CePack<O...> p{ce_opt(o...), ce_ign(o...)};
+    constexpr bool OPT = p.OPT, IGN = p.IGN;
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (row >= M) return;
-    if (IGN && targets[row] == ign.ignore_index) {           // (wave-uniform: no logit of the row is read)
-        if (lane == 0) loss_rows[row] = 0.f;
-        if (dlogits)
-            for (int i = lane; i < (int)ldd; i += 64) dlogits[(int64_t)row * ldd + i] = from_f32<TD>(0.f);
-        return;
-    }
+    if (IGN && targets[row] == p.ign.ignore_index)           // (wave-uniform: no logit of the row is read)
+        return ce_zero_row(loss_rows, dlogits, ldd, row, lane, 64);
     const TL* x = logits + (int64_t)row * ldl;
     float mx = -INFINITY;
     for (int i = lane; i < V; i += 64) mx = fmaxf(mx, (float)x[i]);
@@ -73,20 +105,16 @@ __global__ void cross_entropy_kernel(const TL* __restrict__ logits, int64_t ldl,
     }
     s = wave_sum(s);
     if (OPT) sd = wave_sum(sd);
-    int64_t t = targets[row];
-    t = t < 0 ? 0 : (t >= V ? V - 1 : t);
-    const float lse = mx + logf(s);
-    if (lane == 0) loss_rows[row] = OPT ? ce_objective(mx, logf(s), (float)x[t], sd, V, opt) : IGN ? logf(s) + (mx - (float)x[t]) : lse - (float)x[t];
+    const int64_t t = ce_clamp_target(targets[row], V);
+    if (lane == 0) loss_rows[row] = ce_row_loss<OPT, IGN>(mx, logf(s), (float)x[t], sd, V, p.opt);
     if (dlogits) {
         TD* d = dlogits + (int64_t)row * ldd;
-        const float inv = OPT ? ce_pscale(mx, logf(s), opt) / s : 1.f / s;
-        const float unif = OPT ? opt.eps / (float)V : 0.f;
+        const float inv = ce_inv<OPT>(mx, logf(s), s, p.opt), unif = ce_unif<OPT>(V, p.opt);
         if (gs_dev) grad_scale *= gs_dev[0];
-        if (IGN) grad_scale *= ign.inv_count[0];
+        if (IGN) grad_scale *= p.ign.inv_count[0];
         for (int i = lane; i < (int)ldd; i += 64) {
             float g = 0.f;
-            if (i < V) g = OPT ? ce_grad(expf((float)x[i] - mx) * inv, i == (int)t, unif, opt, grad_scale)
-                               : (expf((float)x[i] - mx) * inv - (i == (int)t ? 1.f : 0.f)) * grad_scale;
+            if (i < V) g = ce_grad<OPT>(expf((float)x[i] - mx) * inv, i == (int)t, unif, p.opt, grad_scale);
             d[i] = from_f32<TD>(g);
         }
     }
@@ -95,19 +123,21 @@ __global__ void cross_entropy_kernel(const TL* __restrict__ logits, int64_t ldl,
 
 // Small vocabularies (V <= 128: the character-level model): 16 lanes per row, four rows per wave, the row held in registers
 // (the wave-per-row kernel above left 3/4 of its lanes idle at V = 80 and read the row three times: 12 us for 8 MB).
+// Its 16-lane row body (load, max, shuffle, exp, sum, shuffle) stands again in the fused kernel below, on purpose: as one function,
+// whether it returns a struct or fills references, the compiler orders the operands of the sums differently and, in the forms with a
+// CeOpt, turns selects into branches -- all 16 instantiations come out as other code.
 template <typename TD, typename... O>
 __global__ __launch_bounds__(256) void cross_entropy_small_kernel(const float* __restrict__ logits, int64_t ldl, const int64_t* __restrict__ targets,
                                                                   float* __restrict__ loss_rows, TD* __restrict__ dlogits, int64_t ldd,
                                                                   float grad_scale, const float* __restrict__ gs_dev, int M, int V, O... o) {
-    constexpr bool OPT = ce_has<CeOpt, O...>::value, IGN = ce_has<CeIgn, O...>::value;
-    const CeOpt opt = ce_opt(o...);
-    const CeIgn ign = ce_ign(o...);
+    const CePack<O...> p{ce_opt(o...), ce_ign(o...)};
+    constexpr bool OPT = p.OPT, IGN = p.IGN;
     const int sub = threadIdx.x & 15;
     const int row = blockIdx.x * 16 + (threadIdx.x >> 4);
     const bool ok = row < M;
     const float* x = logits + (int64_t)(ok ? row : 0) * ldl;
     // an ignored row keeps its 16 lanes in the shuffles below on zeros that it never loaded, and stores zeros
-    const bool skip = IGN && ok && targets[row] == ign.ignore_index;
+    const bool skip = IGN && ok && targets[row] == p.ign.ignore_index;
     float v[8];
     float mx = -INFINITY;
 #pragma unroll
@@ -140,20 +170,17 @@ __global__ __launch_bounds__(256) void cross_entropy_small_kernel(const float* _
         }
         return;
     }
-    int64_t t = targets[row];
-    t = t < 0 ? 0 : (t >= V ? V - 1 : t);
-    if (sub == 0) loss_rows[row] = OPT ? ce_objective(mx, logf(s), x[t], sd, V, opt) : IGN ? logf(s) + (mx - x[t]) : mx + logf(s) - x[t];
+    const int64_t t = ce_clamp_target(targets[row], V);
+    if (sub == 0) loss_rows[row] = ce_row_loss<OPT, IGN>(mx, logf(s), x[t], sd, V, p.opt);
     if (dlogits) {
         TD* d = dlogits + (int64_t)row * ldd;
-        const float inv = OPT ? ce_pscale(mx, logf(s), opt) / s : 1.f / s;
-        const float unif = OPT ? opt.eps / (float)V : 0.f;
+        const float inv = ce_inv<OPT>(mx, logf(s), s, p.opt), unif = ce_unif<OPT>(V, p.opt);
         if (gs_dev) grad_scale *= gs_dev[0];
-        if (IGN) grad_scale *= ign.inv_count[0];
+        if (IGN) grad_scale *= p.ign.inv_count[0];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int i = sub + 16 * k;
-            if (i < (int)ldd) d[i] = from_f32<TD>(i >= V ? 0.f : OPT ? ce_grad(v[k] * inv, i == (int)t, unif, opt, grad_scale)
-                                                                     : (v[k] * inv - (i == (int)t ? 1.f : 0.f)) * grad_scale);
+            if (i < (int)ldd) d[i] = from_f32<TD>(i >= V ? 0.f : ce_grad<OPT>(v[k] * inv, i == (int)t, unif, p.opt, grad_scale));
         }
     }
 }
@@ -174,9 +201,8 @@ template <typename TD, typename... O>
 __global__ __launch_bounds__(CEF_THREADS) void cross_entropy_small_fused_kernel(const float* __restrict__ logits, int64_t ldl, const int64_t* __restrict__ targets,
                                                                         float* __restrict__ loss_rows, TD* __restrict__ dlogits, int64_t ldd,
                                                                         float grad_scale, int M, int V, CeFuse fz, O... o) {
-    constexpr bool OPT = ce_has<CeOpt, O...>::value, IGN = ce_has<CeIgn, O...>::value;
-    const CeOpt opt = ce_opt(o...);
-    const CeIgn ign = ce_ign(o...);
+    const CePack<O...> p{ce_opt(o...), ce_ign(o...)};
+    constexpr bool OPT = p.OPT, IGN = p.IGN;
     __shared__ float red[CEF_RG][128];
     __shared__ float lred[CEF_RG];
     __shared__ unsigned last_flag;
@@ -187,14 +213,14 @@ __global__ __launch_bounds__(CEF_THREADS) void cross_entropy_small_fused_kernel(
 #pragma unroll
     for (int k = 0; k < 8; ++k) cacc[k] = 0.f;
     float lsum = 0.f;
-    if (IGN) grad_scale *= ign.inv_count[0];
+    if (IGN) grad_scale *= p.ign.inv_count[0];
     for (int r0 = m_begin; r0 < m_end; r0 += CEF_RG) {            // (uniform trip count: the shuffles below need every lane)
         const int row = r0 + rg;
         const bool ok = row < m_end;
         const float* x = logits + (int64_t)(ok ? row : m_begin) * ldl;
         // an ignored row group stays in the trip and in the shuffles on zeros that it never loaded: it stores zeros and adds
         // nothing to the column sums or to the loss share
-        const bool skip = IGN && ok && targets[row] == ign.ignore_index;
+        const bool skip = IGN && ok && targets[row] == p.ign.ignore_index;
         float v[8];
         float mx = -INFINITY;
 #pragma unroll
@@ -225,19 +251,16 @@ __global__ __launch_bounds__(CEF_THREADS) void cross_entropy_small_fused_kernel(
                 if (sub + 16 * k < (int)ldd) dlogits[(int64_t)row * ldd + sub + 16 * k] = from_f32<TD>(0.f);
             continue;
         }
-        int64_t t = targets[row];
-        t = t < 0 ? 0 : (t >= V ? V - 1 : t);
-        const float lr = OPT ? ce_objective(mx, logf(s), x[t], sd, V, opt) : IGN ? logf(s) + (mx - x[t]) : mx + logf(s) - x[t];
+        const int64_t t = ce_clamp_target(targets[row], V);
+        const float lr = ce_row_loss<OPT, IGN>(mx, logf(s), x[t], sd, V, p.opt);
         if (sub == 0) { loss_rows[row] = lr; lsum += lr; }
         TD* d = dlogits + (int64_t)row * ldd;
-        const float inv = OPT ? ce_pscale(mx, logf(s), opt) / s : 1.f / s;
-        const float unif = OPT ? opt.eps / (float)V : 0.f;
+        const float inv = ce_inv<OPT>(mx, logf(s), s, p.opt), unif = ce_unif<OPT>(V, p.opt);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int i = sub + 16 * k;
             // (with zeta > 0 a row no longer sums to zero: cacc stays the column sum of exactly what is written)
-            const float gk = i >= V ? 0.f : OPT ? ce_grad(v[k] * inv, i == (int)t, unif, opt, grad_scale)
-                                                : (v[k] * inv - (i == (int)t ? 1.f : 0.f)) * grad_scale;
+            const float gk = i >= V ? 0.f : ce_grad<OPT>(v[k] * inv, i == (int)t, unif, p.opt, grad_scale);
             cacc[k] += gk;
             if (i < (int)ldd) d[i] = from_f32<TD>(gk);
         }
@@ -274,13 +297,41 @@ __global__ __launch_bounds__(CEF_THREADS) void cross_entropy_small_fused_kernel(
     if (tid == 0) {
         float tot = 0.f;
         for (int i = 0; i < (int)gridDim.x; ++i) tot += sh[i];
-        fz.loss_out[0] = IGN ? tot * (fz.loss_scale * ign.inv_count[0]) : tot * fz.loss_scale;
+        fz.loss_out[0] = IGN ? tot * (fz.loss_scale * p.ign.inv_count[0]) : tot * fz.loss_scale;
         __hip_atomic_store(fz.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
 #define CE_BLOCK 1024
 #define CE_MAXK 52                    // values per thread (128-VGPR budget at 16 waves per workgroup): rows up to 53248 logits
+// The reductions of the two whole-row kernels over the 16 waves of a workgroup, once every wave's leader has stored its value to red
+// (and, under OPT, its sd to red2).  The leaders' stores stay in the kernels: as part of these helpers their basic blocks land in front
+// of the unrolled load loop and the kernels come out one or two instructions longer.
+// The maximum: its second barrier frees red for the sums.
+__device__ __forceinline__ float ce_block_max(const float* red) {
+    __syncthreads();
+    float mx = red[0];
+#pragma unroll
+    for (int k = 1; k < 16; ++k) mx = fmaxf(mx, red[k]);
+    __syncthreads();
+    return mx;
+}
+// s and sd together: one store phase, ONE barrier, then both sums, red2 touched only under OPT.  (Two phases with a barrier each took
+// the CeOpt forms, which sit at the register limit, from 16 to 176 bytes of scratch.)
+struct CeSums { float s, sd; };
+template <bool OPT> __device__ __forceinline__ CeSums ce_block_sums(const float* red, const float* red2) {
+    __syncthreads();
+    float s = red[0], sd = 0.f;
+#pragma unroll
+    for (int k = 1; k < 16; ++k) s += red[k];             // fixed order
+    if (OPT) {
+        sd = red2[0];
+#pragma unroll
+        for (int k = 1; k < 16; ++k) sd += red2[k];
+    }
+    return CeSums{s, sd};
+}
+
 // TL: logits type.  bf16 logits (the engine at the GPT-2 vocabulary: 0.82 GB instead of 1.65 GB written by lm_head and read here)
 // may be overwritten IN PLACE by their own gradient (dlogits == logits, ldd == ldl): a workgroup holds its whole row in
 // registers before it stores anything.
@@ -288,24 +339,19 @@ template <typename TD, typename TL = float, typename... O>
 __global__ __launch_bounds__(CE_BLOCK) void cross_entropy_row_kernel(const TL* logits, int64_t ldl, const int64_t* __restrict__ targets,
                                                                       float* __restrict__ loss_rows, TD* dlogits, int64_t ldd,   // (may alias)
                                                                       float grad_scale, const float* __restrict__ gs_dev, int M, int V, O... o) {
-    constexpr bool OPT = ce_has<CeOpt, O...>::value, IGN = ce_has<CeIgn, O...>::value;
-    const CeOpt opt = ce_opt(o...);
-    const CeIgn ign = ce_ign(o...);
+    const CePack<O...> p{ce_opt(o...), ce_ign(o...)};
+    constexpr bool OPT = p.OPT, IGN = p.IGN;
     __shared__ float red[16];
     __shared__ float red2[OPT ? 16 : 1];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int row = blockIdx.x;
     const TL* x = logits + (int64_t)row * ldl;
     int64_t t = targets[row];
-    if (IGN && t == ign.ignore_index) {                  // (workgroup-uniform, before any load of the row and any barrier)
-        if (tid == 0) loss_rows[row] = 0.f;
-        if (dlogits)
-            for (int i = tid; i < (int)ldd; i += CE_BLOCK) dlogits[(int64_t)row * ldd + i] = from_f32<TD>(0.f);
-        return;
-    }
+    if (IGN && t == p.ign.ignore_index)                  // (workgroup-uniform, before any load of the row and any barrier)
+        return ce_zero_row(loss_rows, dlogits, ldd, row, tid, CE_BLOCK);
     float v[CE_MAXK];
     float mx = -INFINITY;
-    t = t < 0 ? 0 : (t >= V ? V - 1 : t);
+    t = ce_clamp_target(t, V);
     const float xt = (float)x[t];                        // before any store of this row (in-place gradient)
 #pragma unroll
     for (int k = 0; k < CE_MAXK; ++k) {
@@ -315,11 +361,7 @@ __global__ __launch_bounds__(CE_BLOCK) void cross_entropy_row_kernel(const TL* l
     }
     mx = wave_max(mx);
     if (lane == 0) red[w] = mx;
-    __syncthreads();
-    mx = red[0];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) mx = fmaxf(mx, red[k]);
-    __syncthreads();
+    mx = ce_block_max(red);
     float s = 0.f, sd = 0.f;
 #pragma unroll
     for (int k = 0; k < CE_MAXK; ++k) {
@@ -331,27 +373,18 @@ __global__ __launch_bounds__(CE_BLOCK) void cross_entropy_row_kernel(const TL* l
     if (OPT) sd = wave_sum(sd);
     if (lane == 0) red[w] = s;
     if (OPT && lane == 0) red2[w] = sd;
-    __syncthreads();
-    s = red[0];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) s += red[k];             // fixed order
-    if (OPT) {
-        sd = red2[0];
-#pragma unroll
-        for (int k = 1; k < 16; ++k) sd += red2[k];
-    }
-    if (tid == 0) loss_rows[row] = OPT ? ce_objective(mx, logf(s), xt, sd, V, opt) : IGN ? logf(s) + (mx - xt) : mx + logf(s) - xt;
+    const CeSums sums = ce_block_sums<OPT>(red, red2);
+    s = sums.s; sd = sums.sd;
+    if (tid == 0) loss_rows[row] = ce_row_loss<OPT, IGN>(mx, logf(s), xt, sd, V, p.opt);
     if (dlogits) {
         TD* d = dlogits + (int64_t)row * ldd;
-        const float inv = OPT ? ce_pscale(mx, logf(s), opt) / s : 1.f / s;
-        const float unif = OPT ? opt.eps / (float)V : 0.f;
+        const float inv = ce_inv<OPT>(mx, logf(s), s, p.opt), unif = ce_unif<OPT>(V, p.opt);
         if (gs_dev) grad_scale *= gs_dev[0];
-        if (IGN) grad_scale *= ign.inv_count[0];
+        if (IGN) grad_scale *= p.ign.inv_count[0];
 #pragma unroll
         for (int k = 0; k < CE_MAXK; ++k) {
             const int i = k * CE_BLOCK + tid;
-            if (i < (int)ldd) d[i] = from_f32<TD>(i >= V ? 0.f : OPT ? ce_grad(v[k] * inv, i == (int)t, unif, opt, grad_scale)
-                                                                     : (v[k] * inv - (i == (int)t ? 1.f : 0.f)) * grad_scale);
+            if (i < (int)ldd) d[i] = from_f32<TD>(i >= V ? 0.f : ce_grad<OPT>(v[k] * inv, i == (int)t, unif, p.opt, grad_scale));
         }
     }
 }
@@ -381,26 +414,17 @@ __global__ __launch_bounds__(CE_BLOCK, 8) void cross_entropy_row_bf16_kernel(con
                                                                               float* __restrict__ loss_rows, bf16_t* dlogits, int64_t ldd,
                                                                               float grad_scale, const float* __restrict__ gs_dev, int M, int V,
                                                                               unsigned char* __restrict__ q8, int64_t ldq8, float q8_scale, O... o) {
-    constexpr bool OPT = ce_has<CeOpt, O...>::value, IGN = ce_has<CeIgn, O...>::value;
-    const CeOpt opt = ce_opt(o...);
-    const CeIgn ign = ce_ign(o...);
+    const CePack<O...> p{ce_opt(o...), ce_ign(o...)};
+    constexpr bool OPT = p.OPT, IGN = p.IGN;
     __shared__ float red[16];
     __shared__ float red2[OPT ? 16 : 1];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int row = blockIdx.x;
     const bf16_t* x = logits + (int64_t)row * ldl;
     int64_t t = targets[row];
-    if (IGN && t == ign.ignore_index) {                  // (workgroup-uniform, before any load of the row and any barrier; never with q8)
-        if (tid == 0) loss_rows[row] = 0.f;
-        if (dlogits) {
-            bf16x8 z;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) z[e] = (bf16_t)0.f;
-            for (int c = tid; c < (int)(ldd / 8); c += CE_BLOCK) *(bf16x8*)(dlogits + (int64_t)row * ldd + c * 8) = z;
-        }
-        return;
-    }
-    t = t < 0 ? 0 : (t >= V ? V - 1 : t);
+    if (IGN && t == p.ign.ignore_index)                  // (workgroup-uniform, before any load of the row and any barrier; never with q8)
+        return ce_zero_row_x8(loss_rows, dlogits, ldd, row, tid, CE_BLOCK);
+    t = ce_clamp_target(t, V);
     const float xt = (float)x[t];                        // before any store of this row (in-place gradient)
     const int nchunk = (int)((dlogits && ldd > V ? ldd : (int64_t)V) + 7) / 8;      // chunks that exist in memory (ldl >= that * 8)
     bf16x8 q[CE_MAXC];
@@ -417,11 +441,7 @@ __global__ __launch_bounds__(CE_BLOCK, 8) void cross_entropy_row_bf16_kernel(con
     }
     mx = wave_max(mx);
     if (lane == 0) red[w] = mx;
-    __syncthreads();
-    mx = red[0];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) mx = fmaxf(mx, red[k]);
-    __syncthreads();
+    mx = ce_block_max(red);
     const float mxl = mx * CE_LOG2E;
     float s = 0.f, sd = 0.f;
 #pragma unroll
@@ -440,25 +460,17 @@ __global__ __launch_bounds__(CE_BLOCK, 8) void cross_entropy_row_bf16_kernel(con
     if (OPT) sd = wave_sum(sd);
     if (lane == 0) red[w] = s;
     if (OPT && lane == 0) red2[w] = sd;
-    __syncthreads();
-    s = red[0];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) s += red[k];             // fixed order
-    if (OPT) {
-        sd = red2[0];
-#pragma unroll
-        for (int k = 1; k < 16; ++k) sd += red2[k];
-    }
+    const CeSums sums = ce_block_sums<OPT>(red, red2);
+    s = sums.s; sd = sums.sd;
     // (mx - xt first: exact for bf16 logits within 2^16 of each other, so a target at the row maximum gives logf(s) itself.  mx + logf(s)
     // rounds at the size of mx -- 2^-24 |mx| = 1.2e-4 at |mx| = 2000 -- on top of the 2^-24 |mx| that the rounding of mx log2(e) already
     // costs through ce_exp_fast: tests/test_gpu_conditioning.py, logit range 2000)
-    if (tid == 0) loss_rows[row] = OPT ? ce_objective(mx, logf(s), xt, sd, V, opt) : (mx - xt) + logf(s);
+    if (tid == 0) loss_rows[row] = OPT ? ce_objective(mx, logf(s), xt, sd, V, p.opt) : (mx - xt) + logf(s);
     if (dlogits) {
         bf16_t* d = dlogits + (int64_t)row * ldd;
-        const float inv = OPT ? ce_pscale(mx, logf(s), opt) / s : 1.f / s;
-        const float unif = OPT ? opt.eps / (float)V : 0.f;
+        const float inv = ce_inv<OPT>(mx, logf(s), s, p.opt), unif = ce_unif<OPT>(V, p.opt);
         if (gs_dev) grad_scale *= gs_dev[0];
-        if (IGN) grad_scale *= ign.inv_count[0];
+        if (IGN) grad_scale *= p.ign.inv_count[0];
         const int dchunk = (int)(ldd / 8);
 #pragma unroll
         for (int j = 0; j < CE_MAXC; ++j) {
@@ -469,8 +481,7 @@ __global__ __launch_bounds__(CE_BLOCK, 8) void cross_entropy_row_bf16_kernel(con
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const int i = c * 8 + e;
-                    gv[e] = i >= V ? 0.f : OPT ? ce_grad(ce_exp_fast((float)q[j][e], mxl) * inv, i == (int)t, unif, opt, grad_scale)
-                                               : (ce_exp_fast((float)q[j][e], mxl) * inv - (i == (int)t ? 1.f : 0.f)) * grad_scale;
+                    gv[e] = i >= V ? 0.f : ce_grad<OPT>(ce_exp_fast((float)q[j][e], mxl) * inv, i == (int)t, unif, p.opt, grad_scale);
                     o[e] = (bf16_t)gv[e];
                 }
                 *(bf16x8*)(d + c * 8) = o;
@@ -488,156 +499,8 @@ __global__ __launch_bounds__(CE_BLOCK, 8) void cross_entropy_row_bf16_kernel(con
     }
 }
 
-// O... opt: nothing (the three old entry points: the instantiations they always launched), one CeOpt, one CeIgn, or a CeOpt and a CeIgn
-template <typename... O>
-static int ce_launch(const void* logits_v, int logits_dtype, int64_t ldl, const int64_t* targets, float* loss_rows,
-                     void* dlogits, int64_t ldd, int dtype, float grad_scale, const float* grad_scale_dev, int M, int V,
-                     unsigned char* q8, int64_t ldq8, float q8_scale, void* stream, O... opt);
-
-// eps in [0, 1), zeta >= 0, both finite (a NaN fails every comparison)
-static bool ce_opt_ok(float eps, float zeta) { return eps >= 0.f && eps < 1.f && zeta >= 0.f && zeta <= FLT_MAX; }
-
-extern "C" int dg_cross_entropy(const void* logits_v, int logits_dtype, int64_t ldl, const int64_t* targets, float* loss_rows,
-                                void* dlogits, int64_t ldd, int dtype, float grad_scale, const float* grad_scale_dev, int M, int V, void* stream) {
-    return ce_launch(logits_v, logits_dtype, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, grad_scale_dev, M, V, nullptr, 0, 0.f,
-                            stream);
-}
-
-extern "C" int dg_cross_entropy_smooth(const void* logits_v, int logits_dtype, int64_t ldl, const int64_t* targets, float* loss_rows,
-                                       void* dlogits, int64_t ldd, int dtype, float grad_scale, const float* grad_scale_dev, int M, int V,
-                                       float label_smoothing, float z_loss, void* stream) {
-    if (!ce_opt_ok(label_smoothing, z_loss)) return DG_ERR_ARG;
-    if (label_smoothing == 0.f && z_loss == 0.f)
-        return dg_cross_entropy(logits_v, logits_dtype, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, grad_scale_dev, M, V, stream);
-    return ce_launch(logits_v, logits_dtype, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, grad_scale_dev, M, V, nullptr, 0, 0.f,
-                           stream, CeOpt{label_smoothing, z_loss});
-}
-
-// bf16 logits (the whole-row kernel, 16-byte accesses) with the gradient ALSO as e5m2: dlogits_fp8 [M, ld8] = e5m2(dlogits * 57344 /
-// grad_scale), dequantisation factor grad_scale / 57344 (a constant the caller knows); ld8 % 16 == 0, ld8 >= V, columns beyond V zero
-static int ce_fp8_check(const void* logits, int64_t ldl, const void* dlogits, int64_t ldd, float grad_scale, int V, const void* dlogits_fp8, int64_t ld8) {
-    if (!dlogits || !dlogits_fp8 || ld8 < V || ld8 % 16 || ld8 > ldd || !dg_aligned16(dlogits_fp8) || !(grad_scale > 0.f)) return DG_ERR_ARG;
-    if (ldl % 8 || ldd % 8 || !dg_aligned16(logits) || !dg_aligned16(dlogits) || (int64_t)((V + 7) / 8) * 8 > ldl) return DG_ERR_ALIGN;
-    return DG_OK;
-}
-
-extern "C" int dg_cross_entropy_fp8(const void* logits, int64_t ldl, const int64_t* targets, float* loss_rows, void* dlogits, int64_t ldd,
-                                    float grad_scale, int M, int V, void* dlogits_fp8, int64_t ld8, void* stream) {
-    if (const int e = ce_fp8_check(logits, ldl, dlogits, ldd, grad_scale, V, dlogits_fp8, ld8)) return e;
-    return ce_launch(logits, DG_BF16, ldl, targets, loss_rows, dlogits, ldd, DG_BF16, grad_scale, nullptr, M, V, (unsigned char*)dlogits_fp8, ld8,
-                            57344.f / grad_scale, stream);
-}
-
-// label smoothing only: |g_i| <= grad_scale, on which the a-priori scale rests, does not survive a z-loss
-extern "C" int dg_cross_entropy_fp8_smooth(const void* logits, int64_t ldl, const int64_t* targets, float* loss_rows, void* dlogits, int64_t ldd,
-                                           float grad_scale, int M, int V, void* dlogits_fp8, int64_t ld8, float label_smoothing, void* stream) {
-    if (!ce_opt_ok(label_smoothing, 0.f)) return DG_ERR_ARG;
-    if (label_smoothing == 0.f) return dg_cross_entropy_fp8(logits, ldl, targets, loss_rows, dlogits, ldd, grad_scale, M, V, dlogits_fp8, ld8, stream);
-    if (const int e = ce_fp8_check(logits, ldl, dlogits, ldd, grad_scale, V, dlogits_fp8, ld8)) return e;
-    return ce_launch(logits, DG_BF16, ldl, targets, loss_rows, dlogits, ldd, DG_BF16, grad_scale, nullptr, M, V, (unsigned char*)dlogits_fp8, ld8,
-                           57344.f / grad_scale, stream, CeOpt{label_smoothing, 0.f});
-}
-
-template <typename... O>
-static int ce_launch(const void* logits_v, int logits_dtype, int64_t ldl, const int64_t* targets, float* loss_rows,
-                     void* dlogits, int64_t ldd, int dtype, float grad_scale, const float* grad_scale_dev, int M, int V,
-                     unsigned char* q8, int64_t ldq8, float q8_scale, void* stream, O... opt) {
-    if (!logits_v || !targets || !loss_rows || M <= 0 || V <= 0 || ldl < V) return DG_ERR_ARG;
-    if (dlogits && ldd < V) return DG_ERR_ARG;
-    if (ce_has<CeIgn, O...>::value && q8) return DG_ERR_ARG;      // (the e5m2 scale rests on |dlogits| <= 1 / M: see dg_cross_entropy_fp8)
-    if (logits_dtype != DG_F32 && logits_dtype != DG_BF16) return DG_ERR_DTYPE;
-    if (logits_dtype == DG_BF16) {
-        // bf16 logits: the whole-row kernel only (its in-place form is what they exist for); gradient in bf16
-        const int64_t w = dlogits && ldd > V ? ldd : V;
-        if (w > (int64_t)CE_BLOCK * CE_MAXK) return DG_ERR_ARG;
-        if (dlogits && dtype != DG_BF16) return DG_ERR_DTYPE;
-        if (dlogits == logits_v && ldd != ldl) return DG_ERR_ARG;
-        const bool vec = ldl % 8 == 0 && dg_aligned16(logits_v) && (!dlogits || (ldd % 8 == 0 && dg_aligned16(dlogits))) &&
-                         (int64_t)((V + 7) / 8) * 8 <= ldl && w <= (int64_t)CE_BLOCK * CE_MAXC * 8;
-        if (q8 && !vec) return DG_ERR_ARG;
-        if (vec)
-            hipLaunchKernelGGL((cross_entropy_row_bf16_kernel<O...>), dim3(M), dim3(CE_BLOCK), 0, (hipStream_t)stream, (const bf16_t*)logits_v, ldl,
-                               targets, loss_rows, (bf16_t*)dlogits, ldd, grad_scale, grad_scale_dev, M, V, q8, ldq8, q8_scale, opt...);
-        else
-            hipLaunchKernelGGL((cross_entropy_row_kernel<bf16_t, bf16_t, O...>), dim3(M), dim3(CE_BLOCK), 0, (hipStream_t)stream, (const bf16_t*)logits_v, ldl,
-                               targets, loss_rows, (bf16_t*)dlogits, ldd, grad_scale, grad_scale_dev, M, V, opt...);
-        DG_LAUNCH_CHECK();
-        return DG_OK;
-    }
-    const float* logits = (const float*)logits_v;
-    if (dlogits == logits_v) return DG_ERR_ARG;          // in place only with bf16 logits
-    dim3 grid((M + 3) / 4), block(256);
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t width = dlogits && ldd > V ? ldd : V;
-    if (width <= 128) {
-        if (dtype == DG_BF16)
-            hipLaunchKernelGGL((cross_entropy_small_kernel<bf16_t, O...>), dim3((M + 15) / 16), block, 0, s, logits, ldl, targets, loss_rows, (bf16_t*)dlogits, ldd, grad_scale, grad_scale_dev, M, V, opt...);
-        else if (dtype == DG_F32)
-            hipLaunchKernelGGL((cross_entropy_small_kernel<float, O...>), dim3((M + 15) / 16), block, 0, s, logits, ldl, targets, loss_rows, (float*)dlogits, ldd, grad_scale, grad_scale_dev, M, V, opt...);
-        else return DG_ERR_DTYPE;
-        DG_LAUNCH_CHECK();
-        return DG_OK;
-    }
-    if (V > 4096 && width <= (int64_t)CE_BLOCK * CE_MAXK) {
-        if (dtype == DG_BF16)
-            hipLaunchKernelGGL((cross_entropy_row_kernel<bf16_t, float, O...>), dim3(M), dim3(CE_BLOCK), 0, s, logits, ldl, targets, loss_rows, (bf16_t*)dlogits, ldd, grad_scale, grad_scale_dev, M, V, opt...);
-        else if (dtype == DG_F32)
-            hipLaunchKernelGGL((cross_entropy_row_kernel<float, float, O...>), dim3(M), dim3(CE_BLOCK), 0, s, logits, ldl, targets, loss_rows, (float*)dlogits, ldd, grad_scale, grad_scale_dev, M, V, opt...);
-        else return DG_ERR_DTYPE;
-        DG_LAUNCH_CHECK();
-        return DG_OK;
-    }
-    if (dtype == DG_BF16)
-        hipLaunchKernelGGL((cross_entropy_kernel<bf16_t, float, O...>), grid, block, 0, s, logits, ldl, targets, loss_rows, (bf16_t*)dlogits, ldd, grad_scale, grad_scale_dev, M, V, opt...);
-    else if (dtype == DG_F32)
-        hipLaunchKernelGGL((cross_entropy_kernel<float, float, O...>), grid, block, 0, s, logits, ldl, targets, loss_rows, (float*)dlogits, ldd, grad_scale, grad_scale_dev, M, V, opt...);
-    else return DG_ERR_DTYPE;
-    DG_LAUNCH_CHECK();
-    return DG_OK;
-}
-
-
-template <typename... O>
-static int ce_fused_launch(const float* logits, int64_t ldl, const int64_t* targets, float* loss_rows, void* dlogits, int64_t ldd,
-                           int dtype, float grad_scale, int M, int V, float* colsum_part, int64_t part_stride, int n_partials,
-                           float* loss_part, uint32_t* loss_counter, float* loss_out, float loss_scale, void* stream, O... opt) {
-    if (!logits || !targets || !loss_rows || !dlogits || M <= 0 || V <= 0 || ldl < V || ldd < V) return DG_ERR_ARG;
-    if (ldd > 128 || n_partials <= 0 || n_partials > 2048) return DG_ERR_ARG;         // rows in registers; shares summed out of 8 KB of LDS
-    if (colsum_part && part_stride < V) return DG_ERR_ARG;
-    if ((loss_out != nullptr) != (loss_part != nullptr) || (loss_out != nullptr) != (loss_counter != nullptr)) return DG_ERR_ARG;
-    const int rows_per = (M + n_partials - 1) / n_partials;
-    const CeFuse fz{colsum_part, part_stride, rows_per, loss_part, (unsigned*)loss_counter, loss_out, loss_scale};
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == DG_BF16)
-        hipLaunchKernelGGL((cross_entropy_small_fused_kernel<bf16_t, O...>), dim3(n_partials), dim3(CEF_THREADS), 0, s, logits, ldl, targets, loss_rows, (bf16_t*)dlogits, ldd, grad_scale, M, V, fz, opt...);
-    else if (dtype == DG_F32)
-        hipLaunchKernelGGL((cross_entropy_small_fused_kernel<float, O...>), dim3(n_partials), dim3(CEF_THREADS), 0, s, logits, ldl, targets, loss_rows, (float*)dlogits, ldd, grad_scale, M, V, fz, opt...);
-    else return DG_ERR_DTYPE;
-    DG_LAUNCH_CHECK();
-    return DG_OK;
-}
-
-extern "C" int dg_cross_entropy_fused(const float* logits, int64_t ldl, const int64_t* targets, float* loss_rows, void* dlogits, int64_t ldd,
-                                      int dtype, float grad_scale, int M, int V, float* colsum_part, int64_t part_stride, int n_partials,
-                                      float* loss_part, uint32_t* loss_counter, float* loss_out, float loss_scale, void* stream) {
-    return ce_fused_launch(logits, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, M, V, colsum_part, part_stride, n_partials,
-                                  loss_part, loss_counter, loss_out, loss_scale, stream);
-}
-
-extern "C" int dg_cross_entropy_fused_smooth(const float* logits, int64_t ldl, const int64_t* targets, float* loss_rows, void* dlogits, int64_t ldd,
-                                             int dtype, float grad_scale, int M, int V, float* colsum_part, int64_t part_stride, int n_partials,
-                                             float* loss_part, uint32_t* loss_counter, float* loss_out, float loss_scale,
-                                             float label_smoothing, float z_loss, void* stream) {
-    if (!ce_opt_ok(label_smoothing, z_loss)) return DG_ERR_ARG;
-    if (label_smoothing == 0.f && z_loss == 0.f)
-        return dg_cross_entropy_fused(logits, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, M, V, colsum_part, part_stride, n_partials,
-                                      loss_part, loss_counter, loss_out, loss_scale, stream);
-    return ce_fused_launch(logits, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, M, V, colsum_part, part_stride, n_partials,
-                                 loss_part, loss_counter, loss_out, loss_scale, stream, CeOpt{label_smoothing, z_loss});
-}
-
 // {(float)N, 1.0f / (float)N}, N the number of targets that are not ignore_index: one workgroup, an integer sum (no order to fix), the
-// reciprocal one correctly rounded fp32 division (+inf at N = 0).  Everything the ignore forms below need to know about the batch.
+// reciprocal one correctly rounded fp32 division (+inf at N = 0).  Everything the ignore forms need to know about the batch.
 __global__ __launch_bounds__(1024) void ce_count_valid_kernel(const int64_t* __restrict__ targets, int M, int64_t ignore_index, float* __restrict__ out) {
     __shared__ int red[16];
     int n = 0;
@@ -656,25 +519,141 @@ __global__ __launch_bounds__(1024) void ce_count_valid_kernel(const int64_t* __r
     }
 }
 
-extern "C" int dg_ce_count_valid(const int64_t* targets, int M, int64_t ignore_index, float* out, void* stream) {
-    if (!targets || !out || M <= 0) return DG_ERR_ARG;
-    hipLaunchKernelGGL(ce_count_valid_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, targets, M, ignore_index, out);
+// ---------------------------------------------------------------------------------------------
+// Host side.  The one place that chooses the pack: launch() with nothing (both options zero, no ign: the plain kernels), a CeOpt, a
+// CeIgn (both options zero: the CeIgn alone), or a CeOpt and a CeIgn.
+// eps in [0, 1), zeta >= 0, both finite (a NaN fails every comparison)
+static bool ce_opt_ok(float eps, float zeta) { return eps >= 0.f && eps < 1.f && zeta >= 0.f && zeta <= FLT_MAX; }
+template <typename F> static int ce_with_options(float eps, float zeta, const CeIgn* ign, F&& launch) {
+    if (!ce_opt_ok(eps, zeta) || (ign && !ign->inv_count)) return DG_ERR_ARG;
+    const bool plain = eps == 0.f && zeta == 0.f;
+    if (ign) return plain ? launch(*ign) : launch(CeOpt{eps, zeta}, *ign);
+    return plain ? launch() : launch(CeOpt{eps, zeta});
+}
+// The gradient's type: launch(d) with dlogits as a bf16_t* or a float*, whichever dtype names
+template <typename F> static int ce_with_grad_type(int dtype, void* dlogits, F&& launch) {
+    if (dtype == DG_BF16) launch((bf16_t*)dlogits);
+    else if (dtype == DG_F32) launch((float*)dlogits);
+    else return DG_ERR_DTYPE;
     DG_LAUNCH_CHECK();
     return DG_OK;
 }
+template <typename P> using ce_pointee = std::remove_pointer_t<P>;
 
-// rows whose target equals ignore_index left out; inv_count: device, 1 / N (the second word of dg_ce_count_valid's output).  With both
-// options zero the kernels are instantiated with the CeIgn alone.
+// ign: null, or the CeIgn of an _ignore entry point; q8: null but for the _fp8 entry points
+static int ce_rows(const void* logits_v, int logits_dtype, int64_t ldl, const int64_t* targets, float* loss_rows, void* dlogits, int64_t ldd,
+                   int dtype, float grad_scale, const float* grad_scale_dev, int M, int V, unsigned char* q8, int64_t ldq8, float q8_scale,
+                   float eps, float zeta, const CeIgn* ign, void* stream) {
+    return ce_with_options(eps, zeta, ign, [&](auto... opt) -> int {
+        if (!logits_v || !targets || !loss_rows || M <= 0 || V <= 0 || ldl < V) return DG_ERR_ARG;
+        if (dlogits && ldd < V) return DG_ERR_ARG;
+        if (ign && q8) return DG_ERR_ARG;                    // (the e5m2 scale rests on |dlogits| <= 1 / M: see dg_cross_entropy_fp8)
+        if (logits_dtype != DG_F32 && logits_dtype != DG_BF16) return DG_ERR_DTYPE;
+        hipStream_t s = (hipStream_t)stream;
+        const int64_t width = dlogits && ldd > V ? ldd : V;
+        if (logits_dtype == DG_BF16) {
+            // bf16 logits: the whole-row kernel only (its in-place form is what they exist for); gradient in bf16
+            if (width > (int64_t)CE_BLOCK * CE_MAXK) return DG_ERR_ARG;
+            if (dlogits && dtype != DG_BF16) return DG_ERR_DTYPE;
+            if (dlogits == logits_v && ldd != ldl) return DG_ERR_ARG;
+            const bool vec = ldl % 8 == 0 && dg_aligned16(logits_v) && (!dlogits || (ldd % 8 == 0 && dg_aligned16(dlogits))) &&
+                             (int64_t)((V + 7) / 8) * 8 <= ldl && width <= (int64_t)CE_BLOCK * CE_MAXC * 8;
+            if (q8 && !vec) return DG_ERR_ARG;
+            if (vec)
+                hipLaunchKernelGGL((cross_entropy_row_bf16_kernel<decltype(opt)...>), dim3(M), dim3(CE_BLOCK), 0, s, (const bf16_t*)logits_v, ldl,
+                                   targets, loss_rows, (bf16_t*)dlogits, ldd, grad_scale, grad_scale_dev, M, V, q8, ldq8, q8_scale, opt...);
+            else
+                hipLaunchKernelGGL((cross_entropy_row_kernel<bf16_t, bf16_t, decltype(opt)...>), dim3(M), dim3(CE_BLOCK), 0, s, (const bf16_t*)logits_v,
+                                   ldl, targets, loss_rows, (bf16_t*)dlogits, ldd, grad_scale, grad_scale_dev, M, V, opt...);
+            DG_LAUNCH_CHECK();
+            return DG_OK;
+        }
+        const float* logits = (const float*)logits_v;
+        if (dlogits == logits_v) return DG_ERR_ARG;          // in place only with bf16 logits
+        return ce_with_grad_type(dtype, dlogits, [&](auto* d) {
+            using TD = ce_pointee<decltype(d)>;
+            if (width <= 128)
+                hipLaunchKernelGGL((cross_entropy_small_kernel<TD, decltype(opt)...>), dim3((M + 15) / 16), dim3(256), 0, s, logits, ldl, targets, loss_rows,
+                                   d, ldd, grad_scale, grad_scale_dev, M, V, opt...);
+            else if (V > 4096 && width <= (int64_t)CE_BLOCK * CE_MAXK)
+                hipLaunchKernelGGL((cross_entropy_row_kernel<TD, float, decltype(opt)...>), dim3(M), dim3(CE_BLOCK), 0, s, logits, ldl, targets, loss_rows,
+                                   d, ldd, grad_scale, grad_scale_dev, M, V, opt...);
+            else
+                hipLaunchKernelGGL((cross_entropy_kernel<TD, float, decltype(opt)...>), dim3((M + 3) / 4), dim3(256), 0, s, logits, ldl, targets, loss_rows,
+                                   d, ldd, grad_scale, grad_scale_dev, M, V, opt...);
+        });
+    });
+}
+
+static int ce_fused(const float* logits, int64_t ldl, const int64_t* targets, float* loss_rows, void* dlogits, int64_t ldd, int dtype, float grad_scale,
+                    int M, int V, float* colsum_part, int64_t part_stride, int n_partials, float* loss_part, uint32_t* loss_counter, float* loss_out,
+                    float loss_scale, float eps, float zeta, const CeIgn* ign, void* stream) {
+    return ce_with_options(eps, zeta, ign, [&](auto... opt) -> int {
+        if (!logits || !targets || !loss_rows || !dlogits || M <= 0 || V <= 0 || ldl < V || ldd < V) return DG_ERR_ARG;
+        if (ldd > 128 || n_partials <= 0 || n_partials > 2048) return DG_ERR_ARG;     // rows in registers; shares summed out of 8 KB of LDS
+        if (colsum_part && part_stride < V) return DG_ERR_ARG;
+        if ((loss_out != nullptr) != (loss_part != nullptr) || (loss_out != nullptr) != (loss_counter != nullptr)) return DG_ERR_ARG;
+        const int rows_per = (M + n_partials - 1) / n_partials;
+        const CeFuse fz{colsum_part, part_stride, rows_per, loss_part, (unsigned*)loss_counter, loss_out, loss_scale};
+        return ce_with_grad_type(dtype, dlogits, [&](auto* d) {
+            hipLaunchKernelGGL((cross_entropy_small_fused_kernel<ce_pointee<decltype(d)>, decltype(opt)...>), dim3(n_partials), dim3(CEF_THREADS), 0,
+                               (hipStream_t)stream, logits, ldl, targets, loss_rows, d, ldd, grad_scale, M, V, fz, opt...);
+        });
+    });
+}
+
+extern "C" int dg_cross_entropy(const void* logits_v, int logits_dtype, int64_t ldl, const int64_t* targets, float* loss_rows,
+                                void* dlogits, int64_t ldd, int dtype, float grad_scale, const float* grad_scale_dev, int M, int V, void* stream) {
+    return ce_rows(logits_v, logits_dtype, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, grad_scale_dev, M, V, nullptr, 0, 0.f, 0.f, 0.f,
+                   nullptr, stream);
+}
+
+extern "C" int dg_cross_entropy_smooth(const void* logits_v, int logits_dtype, int64_t ldl, const int64_t* targets, float* loss_rows,
+                                       void* dlogits, int64_t ldd, int dtype, float grad_scale, const float* grad_scale_dev, int M, int V,
+                                       float label_smoothing, float z_loss, void* stream) {
+    return ce_rows(logits_v, logits_dtype, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, grad_scale_dev, M, V, nullptr, 0, 0.f,
+                   label_smoothing, z_loss, nullptr, stream);
+}
+
+// rows whose target equals ignore_index left out; inv_count: device, 1 / N (the second word of dg_ce_count_valid's output)
 extern "C" int dg_cross_entropy_ignore(const void* logits_v, int logits_dtype, int64_t ldl, const int64_t* targets, float* loss_rows,
                                        void* dlogits, int64_t ldd, int dtype, float grad_scale, const float* grad_scale_dev, int M, int V,
                                        float label_smoothing, float z_loss, int64_t ignore_index, const float* inv_count, void* stream) {
-    if (!ce_opt_ok(label_smoothing, z_loss) || !inv_count) return DG_ERR_ARG;
     const CeIgn ign{ignore_index, inv_count};
-    if (label_smoothing == 0.f && z_loss == 0.f)
-        return ce_launch(logits_v, logits_dtype, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, grad_scale_dev, M, V, nullptr, 0, 0.f,
-                         stream, ign);
-    return ce_launch(logits_v, logits_dtype, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, grad_scale_dev, M, V, nullptr, 0, 0.f,
-                     stream, CeOpt{label_smoothing, z_loss}, ign);
+    return ce_rows(logits_v, logits_dtype, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, grad_scale_dev, M, V, nullptr, 0, 0.f,
+                   label_smoothing, z_loss, &ign, stream);
+}
+
+// bf16 logits (the whole-row kernel, 16-byte accesses) with the gradient ALSO as e5m2: dlogits_fp8 [M, ld8] = e5m2(dlogits * 57344 /
+// grad_scale), dequantisation factor grad_scale / 57344 (a constant the caller knows); ld8 % 16 == 0, ld8 >= V, columns beyond V zero.
+// Label smoothing only: |g_i| <= grad_scale, on which the a-priori scale rests, does not survive a z-loss
+extern "C" int dg_cross_entropy_fp8_smooth(const void* logits, int64_t ldl, const int64_t* targets, float* loss_rows, void* dlogits, int64_t ldd,
+                                           float grad_scale, int M, int V, void* dlogits_fp8, int64_t ld8, float label_smoothing, void* stream) {
+    if (!ce_opt_ok(label_smoothing, 0.f)) return DG_ERR_ARG;
+    if (!dlogits || !dlogits_fp8 || ld8 < V || ld8 % 16 || ld8 > ldd || !dg_aligned16(dlogits_fp8) || !(grad_scale > 0.f)) return DG_ERR_ARG;
+    if (ldl % 8 || ldd % 8 || !dg_aligned16(logits) || !dg_aligned16(dlogits) || (int64_t)((V + 7) / 8) * 8 > ldl) return DG_ERR_ALIGN;
+    return ce_rows(logits, DG_BF16, ldl, targets, loss_rows, dlogits, ldd, DG_BF16, grad_scale, nullptr, M, V, (unsigned char*)dlogits_fp8, ld8,
+                   57344.f / grad_scale, label_smoothing, 0.f, nullptr, stream);
+}
+
+extern "C" int dg_cross_entropy_fp8(const void* logits, int64_t ldl, const int64_t* targets, float* loss_rows, void* dlogits, int64_t ldd,
+                                    float grad_scale, int M, int V, void* dlogits_fp8, int64_t ld8, void* stream) {
+    return dg_cross_entropy_fp8_smooth(logits, ldl, targets, loss_rows, dlogits, ldd, grad_scale, M, V, dlogits_fp8, ld8, 0.f, stream);
+}
+
+extern "C" int dg_cross_entropy_fused(const float* logits, int64_t ldl, const int64_t* targets, float* loss_rows, void* dlogits, int64_t ldd,
+                                      int dtype, float grad_scale, int M, int V, float* colsum_part, int64_t part_stride, int n_partials,
+                                      float* loss_part, uint32_t* loss_counter, float* loss_out, float loss_scale, void* stream) {
+    return ce_fused(logits, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, M, V, colsum_part, part_stride, n_partials, loss_part, loss_counter,
+                    loss_out, loss_scale, 0.f, 0.f, nullptr, stream);
+}
+
+extern "C" int dg_cross_entropy_fused_smooth(const float* logits, int64_t ldl, const int64_t* targets, float* loss_rows, void* dlogits, int64_t ldd,
+                                             int dtype, float grad_scale, int M, int V, float* colsum_part, int64_t part_stride, int n_partials,
+                                             float* loss_part, uint32_t* loss_counter, float* loss_out, float loss_scale,
+                                             float label_smoothing, float z_loss, void* stream) {
+    return ce_fused(logits, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, M, V, colsum_part, part_stride, n_partials, loss_part, loss_counter,
+                    loss_out, loss_scale, label_smoothing, z_loss, nullptr, stream);
 }
 
 // loss_out = loss_scale * inv_count[0] * sum(rows); the column-sum partials hold the rows that count only
@@ -682,11 +661,14 @@ extern "C" int dg_cross_entropy_fused_ignore(const float* logits, int64_t ldl, c
                                              int dtype, float grad_scale, int M, int V, float* colsum_part, int64_t part_stride, int n_partials,
                                              float* loss_part, uint32_t* loss_counter, float* loss_out, float loss_scale,
                                              float label_smoothing, float z_loss, int64_t ignore_index, const float* inv_count, void* stream) {
-    if (!ce_opt_ok(label_smoothing, z_loss) || !inv_count) return DG_ERR_ARG;
     const CeIgn ign{ignore_index, inv_count};
-    if (label_smoothing == 0.f && z_loss == 0.f)
-        return ce_fused_launch(logits, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, M, V, colsum_part, part_stride, n_partials,
-                               loss_part, loss_counter, loss_out, loss_scale, stream, ign);
-    return ce_fused_launch(logits, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, M, V, colsum_part, part_stride, n_partials,
-                           loss_part, loss_counter, loss_out, loss_scale, stream, CeOpt{label_smoothing, z_loss}, ign);
+    return ce_fused(logits, ldl, targets, loss_rows, dlogits, ldd, dtype, grad_scale, M, V, colsum_part, part_stride, n_partials, loss_part, loss_counter,
+                    loss_out, loss_scale, label_smoothing, z_loss, &ign, stream);
+}
+
+extern "C" int dg_ce_count_valid(const int64_t* targets, int M, int64_t ignore_index, float* out, void* stream) {
+    if (!targets || !out || M <= 0) return DG_ERR_ARG;
+    hipLaunchKernelGGL(ce_count_valid_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, targets, M, ignore_index, out);
+    DG_LAUNCH_CHECK();
+    return DG_OK;
 }

@@ -834,8 +834,13 @@ extern "C" int dg_reduce_partials(const float* partials, int64_t stride, int n_p
 }
 
 // ---------------------------------------------------------------------------------------------
-// out[0] = scale * sum x   (one workgroup of 1024; fixed tree => deterministic)
-__global__ void reduce_sum_kernel(const float* __restrict__ x, int64_t n, float scale, float* __restrict__ out) {
+// out[0] = scale * sum x   (one workgroup of 1024; fixed tree => deterministic).  With the pack `const float* scale_dev` one more
+// factor that only the device knows, out[0] = scale * scale_dev[0] * sum x (the 1 / N of dg_ce_count_valid: the mean over the rows
+// that count); the empty pack leaves the plain kernel its arguments and its code.
+__device__ __forceinline__ float reduce_sum_factor(float scale) { return scale; }
+__device__ __forceinline__ float reduce_sum_factor(float scale, const float* scale_dev) { return scale * scale_dev[0]; }
+template <typename... S>
+__global__ void reduce_sum_kernel(const float* __restrict__ x, int64_t n, float scale, S... scale_dev, float* __restrict__ out) {
     __shared__ float red[16];
     float s = 0.f;
     for (int64_t i = threadIdx.x; i < n; i += 1024) s += x[i];
@@ -845,36 +850,20 @@ __global__ void reduce_sum_kernel(const float* __restrict__ x, int64_t n, float 
     if (threadIdx.x < 64) {
         float t = threadIdx.x < 16 ? red[threadIdx.x] : 0.f;
         t = wave_sum(t);
-        if (threadIdx.x == 0) out[0] = t * scale;
+        if (threadIdx.x == 0) out[0] = t * reduce_sum_factor(scale, scale_dev...);
     }
 }
 
 extern "C" int dg_reduce_sum(const float* x, int64_t n, float scale, float* out, void* stream) {
     if (!x || !out || n <= 0) return DG_ERR_ARG;
-    hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, x, n, scale, out);
+    hipLaunchKernelGGL(reduce_sum_kernel<>, dim3(1), dim3(1024), 0, (hipStream_t)stream, x, n, scale, out);
     DG_LAUNCH_CHECK();
     return DG_OK;
 }
 
-// out[0] = scale * scale_dev[0] * sum x: the same workgroup, the same tree, one more factor that only the device knows (the 1 / N of
-// dg_ce_count_valid: the mean over the rows that count)
-__global__ void reduce_sum_scaled_kernel(const float* __restrict__ x, int64_t n, float scale, const float* __restrict__ scale_dev, float* __restrict__ out) {
-    __shared__ float red[16];
-    float s = 0.f;
-    for (int64_t i = threadIdx.x; i < n; i += 1024) s += x[i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        float t = threadIdx.x < 16 ? red[threadIdx.x] : 0.f;
-        t = wave_sum(t);
-        if (threadIdx.x == 0) out[0] = t * (scale * scale_dev[0]);
-    }
-}
-
 extern "C" int dg_reduce_sum_scaled(const float* x, int64_t n, float scale, const float* scale_dev, float* out, void* stream) {
     if (!x || !out || !scale_dev || n <= 0) return DG_ERR_ARG;
-    hipLaunchKernelGGL(reduce_sum_scaled_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, x, n, scale, scale_dev, out);
+    hipLaunchKernelGGL(reduce_sum_kernel<const float* __restrict__>, dim3(1), dim3(1024), 0, (hipStream_t)stream, x, n, scale, scale_dev, out);
     DG_LAUNCH_CHECK();
     return DG_OK;
 }

@@ -712,6 +712,50 @@ def check_loss_options(label_smoothing=0.0, z_loss=0.0, ignore_index=_NO_IGNORE)
     return eps, zeta
 
 
+def _chk_inv_count(what: str, ignore_index, inv_count) -> None:
+    if ignore_index is None:
+        if inv_count is not None:
+            raise ValueError(f"{what}: inv_count without ignore_index")
+        return
+    if inv_count is None:
+        raise ValueError(f"{what}: ignore_index needs inv_count, the device's 1 / N (count_valid(targets, ignore_index)[1:])")
+    _chk(inv_count, "inv_count", torch.float32)
+    if inv_count.numel() < 1:
+        raise ValueError(f"{what}: inv_count is empty")
+
+
+def _ce_tensors(logits: Tensor, targets: Tensor, dlogits: Optional[Tensor], loss_rows: Optional[Tensor], logits_dtype=None, dlogits_dtype=None,
+                need_dlogits: bool = True):
+    """what the cross_entropy* functions share: the tensor checks and the loss_rows allocation.  Returns M, loss_rows and the
+    leading dimension and dtype code of dlogits (0, DG_F32 without one)."""
+    _chk(logits, "logits", logits_dtype, contiguous=False)  # fp32, or bf16 (large vocabularies: dlogits may then BE logits)
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("cross_entropy: logits must be float32 or bfloat16")
+    _chk(targets, "targets", torch.int64)
+    M = logits.shape[0]
+    if loss_rows is None:
+        loss_rows = torch.empty((M,), dtype=torch.float32, device=logits.device)
+    ldd, dcode = 0, DG_F32
+    if dlogits is not None or need_dlogits:
+        _chk(dlogits, "dlogits", dlogits_dtype, contiguous=False)
+        ldd, dcode = _ld(dlogits), dt_code(dlogits.dtype)
+    return M, loss_rows, ldd, dcode
+
+
+def _ce_call(base: str, head: tuple, eps: float, zeta: Optional[float] = None, ignore_index: Optional[int] = None,
+             inv_count: Optional[Tensor] = None) -> None:
+    """base(*head), base_smooth(*head, eps[, zeta]) or base_ignore(*head, eps, zeta, ignore_index, inv_count), each with the stream last:
+    the plain entry point when every option is zero.  zeta None: an entry point that has no z-loss."""
+    opts = (eps,) if zeta is None else (eps, zeta)
+    if ignore_index is not None:
+        name, tail = base + "_ignore", (*opts, ignore_index, _p(inv_count))
+    elif any(opts):
+        name, tail = base + "_smooth", opts
+    else:
+        name, tail = base, ()
+    check(getattr(lib, name)(*head, *tail, _stream()), name)
+
+
 def cross_entropy(logits: Tensor, targets: Tensor, V: int, dlogits: Optional[Tensor] = None, grad_scale: float = 1.0,
                   grad_scale_dev: Optional[Tensor] = None, loss_rows: Optional[Tensor] = None, *,
                   label_smoothing: float = 0.0, z_loss: float = 0.0, ignore_index: Optional[int] = None,
@@ -722,27 +766,9 @@ def cross_entropy(logits: Tensor, targets: Tensor, V: int, dlogits: Optional[Ten
     (count_valid(targets, ignore_index)[1:]; dg_cross_entropy_ignore)."""
     eps, zeta, ignore_index = check_loss_options(label_smoothing, z_loss, ignore_index)
     _chk_inv_count("cross_entropy", ignore_index, inv_count)
-    _chk(logits, "logits", contiguous=False)              # fp32, or bf16 (large vocabularies: dlogits may then BE logits)
-    if logits.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError("cross_entropy: logits must be float32 or bfloat16")
-    _chk(targets, "targets", torch.int64)
-    M = logits.shape[0]
-    if loss_rows is None:
-        loss_rows = torch.empty((M,), dtype=torch.float32, device=logits.device)
-    ldd, dcode = 0, DG_F32
-    if dlogits is not None:
-        _chk(dlogits, "dlogits", contiguous=False)
-        ldd, dcode = _ld(dlogits), dt_code(dlogits.dtype)
-    if ignore_index is not None:
-        check(lib.dg_cross_entropy_ignore(_p(logits), dt_code(logits.dtype), _ld(logits), _p(targets), _p(loss_rows), _p(dlogits), ldd, dcode,
-                                          float(grad_scale), _p(grad_scale_dev), M, V, eps, zeta, ignore_index, _p(inv_count), _stream()),
-              "dg_cross_entropy_ignore")
-    elif eps == 0.0 and zeta == 0.0:
-        check(lib.dg_cross_entropy(_p(logits), dt_code(logits.dtype), _ld(logits), _p(targets), _p(loss_rows), _p(dlogits), ldd, dcode, float(grad_scale),
-                                   _p(grad_scale_dev), M, V, _stream()), "dg_cross_entropy")
-    else:
-        check(lib.dg_cross_entropy_smooth(_p(logits), dt_code(logits.dtype), _ld(logits), _p(targets), _p(loss_rows), _p(dlogits), ldd, dcode,
-                                          float(grad_scale), _p(grad_scale_dev), M, V, eps, zeta, _stream()), "dg_cross_entropy_smooth")
+    M, loss_rows, ldd, dcode = _ce_tensors(logits, targets, dlogits, loss_rows, need_dlogits=False)
+    _ce_call("dg_cross_entropy", (_p(logits), dt_code(logits.dtype), _ld(logits), _p(targets), _p(loss_rows), _p(dlogits), ldd, dcode,
+                                  float(grad_scale), _p(grad_scale_dev), M, V), eps, zeta, ignore_index, inv_count)
     return loss_rows
 
 
@@ -756,18 +782,10 @@ def cross_entropy_fp8(logits: Tensor, targets: Tensor, V: int, dlogits: Tensor, 
         raise ValueError("cross_entropy_fp8 takes no ignore_index: its e5m2 gradient scale rests on |dlogits| <= grad_scale = 1 / M, and "
                          "with ignored rows the bound is 1 / N, which only the device knows")
     eps, _ = check_loss_options(label_smoothing, 0.0)
-    _chk(logits, "logits", torch.bfloat16, contiguous=False)
-    _chk(targets, "targets", torch.int64)
-    _chk(dlogits, "dlogits", torch.bfloat16, contiguous=False)
+    M, loss_rows, ldd, _ = _ce_tensors(logits, targets, dlogits, None, torch.bfloat16, torch.bfloat16)
     _chk(dlogits_fp8, "dlogits_fp8", torch.float8_e5m2, contiguous=False)
-    M = logits.shape[0]
-    loss_rows = torch.empty((M,), dtype=torch.float32, device=logits.device)
-    if eps == 0.0:
-        check(lib.dg_cross_entropy_fp8(_p(logits), _ld(logits), _p(targets), _p(loss_rows), _p(dlogits), _ld(dlogits), float(grad_scale), M, V,
-                                       _p(dlogits_fp8), _ld(dlogits_fp8), _stream()), "dg_cross_entropy_fp8")
-    else:
-        check(lib.dg_cross_entropy_fp8_smooth(_p(logits), _ld(logits), _p(targets), _p(loss_rows), _p(dlogits), _ld(dlogits), float(grad_scale), M, V,
-                                              _p(dlogits_fp8), _ld(dlogits_fp8), eps, _stream()), "dg_cross_entropy_fp8_smooth")
+    _ce_call("dg_cross_entropy_fp8", (_p(logits), _ld(logits), _p(targets), _p(loss_rows), _p(dlogits), ldd, float(grad_scale), M, V,
+                                      _p(dlogits_fp8), _ld(dlogits_fp8)), eps)
     return loss_rows
 
 
@@ -786,12 +804,7 @@ def cross_entropy_fused(logits: Tensor, targets: Tensor, V: int, dlogits: Tensor
     rows that count and loss_out = loss_scale * inv_count[0] * sum(rows)."""
     eps, zeta, ignore_index = check_loss_options(label_smoothing, z_loss, ignore_index)
     _chk_inv_count("cross_entropy_fused", ignore_index, inv_count)
-    _chk(logits, "logits", torch.float32, contiguous=False)
-    _chk(targets, "targets", torch.int64)
-    _chk(dlogits, "dlogits", contiguous=False)
-    M = logits.shape[0]
-    if loss_rows is None:
-        loss_rows = torch.empty((M,), dtype=torch.float32, device=logits.device)
+    M, loss_rows, ldd, dcode = _ce_tensors(logits, targets, dlogits, loss_rows, torch.float32)
     if colsum_part is not None:
         _chk(colsum_part, "colsum_part", torch.float32, contiguous=False)
     cnt = None
@@ -801,28 +814,10 @@ def cross_entropy_fused(logits: Tensor, targets: Tensor, V: int, dlogits: Tensor
         if loss_scratch.numel() < n_partials + 1:
             raise ValueError("cross_entropy_fused: loss_scratch needs n_partials + 1 words")
         cnt = loss_scratch.data_ptr() + 4 * n_partials
-    head = (_p(logits), _ld(logits), _p(targets), _p(loss_rows), _p(dlogits), _ld(dlogits), dt_code(dlogits.dtype),
-            float(grad_scale), M, V, _p(colsum_part), part_stride, n_partials,
-            _p(loss_scratch) if loss_out is not None else None, cnt, _p(loss_out), float(loss_scale))
-    if ignore_index is not None:
-        check(lib.dg_cross_entropy_fused_ignore(*head, eps, zeta, ignore_index, _p(inv_count), _stream()), "dg_cross_entropy_fused_ignore")
-    elif eps == 0.0 and zeta == 0.0:
-        check(lib.dg_cross_entropy_fused(*head, _stream()), "dg_cross_entropy_fused")
-    else:
-        check(lib.dg_cross_entropy_fused_smooth(*head, eps, zeta, _stream()), "dg_cross_entropy_fused_smooth")
+    _ce_call("dg_cross_entropy_fused", (_p(logits), _ld(logits), _p(targets), _p(loss_rows), _p(dlogits), ldd, dcode, float(grad_scale), M, V,
+                                        _p(colsum_part), part_stride, n_partials, _p(loss_scratch) if loss_out is not None else None, cnt,
+                                        _p(loss_out), float(loss_scale)), eps, zeta, ignore_index, inv_count)
     return loss_rows
-
-
-def _chk_inv_count(what: str, ignore_index, inv_count) -> None:
-    if ignore_index is None:
-        if inv_count is not None:
-            raise ValueError(f"{what}: inv_count without ignore_index")
-        return
-    if inv_count is None:
-        raise ValueError(f"{what}: ignore_index needs inv_count, the device's 1 / N (count_valid(targets, ignore_index)[1:])")
-    _chk(inv_count, "inv_count", torch.float32)
-    if inv_count.numel() < 1:
-        raise ValueError(f"{what}: inv_count is empty")
 
 
 def count_valid(targets: Tensor, ignore_index: int, out: Optional[Tensor] = None) -> Tensor:
