@@ -170,6 +170,8 @@ SIGNATURES = {
     "dg_adamw_step_sched": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _f, _vp, _vp, _i64, _vp, _vp, _i, _vp],
     "dg_adamw_step_ema": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _f, _vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp],
     "dg_swap_f32": [_vp, _vp, _i64, _vp],
+    "dg_grad_norm_finalize_guard": [_vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp],
+    "dg_adamw_step_guard": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _f, _vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp],
     "dg_grad_accumulate": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
     "dg_block_chain_supported": [_i, _i],
     "dg_block_chain_fwd": [C.POINTER(BlockChainArgs), _vp],

@@ -256,6 +256,54 @@ def check_ema_state(section, own: bool, n: int):
     return decay, section["warmup"], values
 
 
+def check_guard_meta(saved_meta: dict, own: bool) -> None:
+    """meta["update_guard"] is written (True) only by an engine with the update guard on.  A guarded file is refused by an engine
+    without the guard (its data word and its optimizer word may differ, and that engine has one word); an unguarded file loads
+    into a guarded engine (the guard can be turned on mid-run), as does a guarded file."""
+    saved = saved_meta.get("update_guard", False)
+    if not isinstance(saved, bool):
+        raise ValueError(f"training state: meta.update_guard is {saved!r}, expected a bool")
+    if saved and not own:
+        raise ValueError(f"training state: meta.update_guard differs: saved {saved!r}, this run has {bool(own)!r} (the file keeps "
+                         "a data word and an optimizer word that may differ; load it into an engine with the update guard on)")
+
+
+def check_guard_state(section, saved_meta: dict, own: bool, step_word: int):
+    """the "guard" section of an engine state ({"skipped", "consecutive", "limit", "opt_step"}) against a run with the update
+    guard on (own) or off; returns None (own off) or (opt_step, skipped, consecutive, limit, restore_limit).  An unguarded file
+    into a guarded run: opt_step = step_word (None is returned for it: the caller knows its own word), counters 0, the run keeps
+    its limit.  ValueError names the field."""
+    from .ops import check_guard_options
+    check_guard_meta(saved_meta, own)
+    saved = bool(saved_meta.get("update_guard", False))
+    if saved != (section is not None):
+        raise ValueError(f"training state: engine.guard is {'present' if section is not None else None!r}, meta.update_guard says {saved!r}")
+    if not own:
+        return None
+    if section is None:
+        return None, 0, 0, None, False
+    if not isinstance(section, dict):
+        raise ValueError(f"training state: engine.guard is a {type(section).__name__}, expected a dict")
+    for k in ("skipped", "consecutive", "limit", "opt_step"):
+        if k not in section:
+            raise ValueError(f"training state: missing key engine.guard.{k}")
+    vals = []
+    for k in ("opt_step", "skipped", "consecutive"):
+        x = section[k]
+        if isinstance(x, bool) or not isinstance(x, int) or not 0 <= x < (1 << 32):
+            raise ValueError(f"training state: engine.guard.{k} is {x!r}, expected an integer in [0, 2^32)")
+        vals.append(x)
+    if vals[2] > vals[1]:
+        raise ValueError(f"training state: engine.guard.consecutive is {vals[2]}, more than engine.guard.skipped = {vals[1]}")
+    if vals[0] > step_word:
+        raise ValueError(f"training state: engine.guard.opt_step is {vals[0]}, more than engine.step_word = {step_word}")
+    try:
+        check_guard_options(True, section["limit"])
+    except ValueError as err:
+        raise ValueError(f"training state: engine.guard.limit: {err}") from None
+    return vals[0], vals[1], vals[2], section["limit"], True
+
+
 def save_train_state(path: str, obj: dict) -> None:
     """write to a temporary file in the same directory, then os.replace: the previous file stays intact until the new one is
     complete, and a failure leaves no temporary file behind"""

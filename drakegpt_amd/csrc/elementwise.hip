@@ -937,15 +937,38 @@ __device__ __forceinline__ AdamwEma adamw_ema_of(AdamwSched, AdamwEma ea) { retu
 template <typename... S>
 __device__ __forceinline__ AdamwEma adamw_ema_of(S...) { return AdamwEma{nullptr, nullptr}; }
 
-template <bool CLIP, bool TABLE, bool MASK, typename... S>   // S: nothing; one AdamwSched when TABLE or MASK; AdamwSched, AdamwEma
+// GUARD (S = AdamwSched, AdamwEma, AdamwGuard<EMA>): the update guard of dg_grad_norm_finalize_guard.  Every workgroup reads
+// guard[0] once, where it reads the step word.  0: the update is skipped -- neither streaming loop runs (no load or store of p / g /
+// m / v / ema / shadow: a skipped step costs a launch, not a pass over HBM) and the workgroup goes straight to the arrival counter.
+// The last workgroup to arrive clears the counter, moves data_state[2] (if given: the word that keys dropout, the staged offset row
+// and the fp8 amax slot) on in either case, and the optimizer's own step word only when the update was applied: bias correction,
+// the LR-table index and the EMA warm-up stand still over a skipped step.  Nobody waits for anybody: the same fetch-add, no spin.
+// 1: the body below as it is, so the bits of the unguarded launch.  EMA is a compile-time member here (ema may be NULL at the
+// entry); without the third pack member the kernel, its instantiations and its kernel arguments are the ones they were.
+template <bool EMA_>
+struct AdamwGuard { const uint32_t* guard; uint32_t* data_state; };
+template <typename... S> struct AdamwPack { static constexpr bool guard = false, ema = sizeof...(S) == 2; };
+template <bool EMA_> struct AdamwPack<AdamwSched, AdamwEma, AdamwGuard<EMA_>> { static constexpr bool guard = true, ema = EMA_; };
+template <bool EMA_>
+__device__ __forceinline__ AdamwSched adamw_sched_of(AdamwSched sc, AdamwEma, AdamwGuard<EMA_>) { return sc; }
+template <bool EMA_>
+__device__ __forceinline__ AdamwEma adamw_ema_of(AdamwSched, AdamwEma ea, AdamwGuard<EMA_>) { return ea; }
+template <bool EMA_>
+__device__ __forceinline__ AdamwGuard<EMA_> adamw_guard_of(AdamwSched, AdamwEma, AdamwGuard<EMA_> gd) { return gd; }
+template <typename... S>
+__device__ __forceinline__ AdamwGuard<false> adamw_guard_of(S...) { return AdamwGuard<false>{nullptr, nullptr}; }
+
+template <bool CLIP, bool TABLE, bool MASK, typename... S>   // S: nothing; one AdamwSched when TABLE or MASK; AdamwSched, AdamwEma; + AdamwGuard
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                              float* __restrict__ v, int64_t n, const float* __restrict__ hyper,
                              uint32_t* rng_state, float grad_scale,
                              bf16_t* __restrict__ shadow, int advance, const float* __restrict__ clip_coef, S... sched) {
-    constexpr bool EMA = sizeof...(S) == 2;
-    static_assert(EMA || sizeof...(S) == ((TABLE || MASK) ? 1 : 0), "the schedule arguments go with TABLE or MASK");
+    constexpr bool EMA = AdamwPack<S...>::ema;
+    constexpr bool GUARD = AdamwPack<S...>::guard;
+    static_assert(EMA || GUARD || sizeof...(S) == ((TABLE || MASK) ? 1 : 0), "the schedule arguments go with TABLE or MASK");
     const AdamwSched sc = adamw_sched_of(sched...);
     const AdamwEma ea = adamw_ema_of(sched...);
+    const auto gd = adamw_guard_of(sched...);
     const float* __restrict__ lr_table = sc.lr_table;
     const uint32_t* __restrict__ no_decay_bits = sc.no_decay_bits;
     if (CLIP) grad_scale *= clip_coef[0];
@@ -962,6 +985,11 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
     float* __restrict__ ema = ea.ema;
     float ema_w = 0.f;
     if (EMA) ema_w = adamw_ema_weight(ea.ema_hyper, step_now);
+    bool applied = true;
+    if constexpr (GUARD) {
+        applied = gd.guard[0] != 0u;
+        if (!applied) n = 0;                                     // a skipped update: both loops below are empty
+    }
     int64_t gs = (int64_t)gridDim.x * blockDim.x;
     int64_t n4 = n / 4;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gs) {
@@ -1029,7 +1057,13 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
             const unsigned prev = __hip_atomic_fetch_add(rng_state + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (prev == gridDim.x - 1) {
                 __hip_atomic_store(rng_state + 3, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(rng_state + 2, step_now + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if constexpr (GUARD) {
+                    if (gd.data_state)
+                        __hip_atomic_store(gd.data_state + 2, gd.data_state[2] + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (applied) __hip_atomic_store(rng_state + 2, step_now + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                } else {
+                    __hip_atomic_store(rng_state + 2, step_now + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
             }
         }
     }
@@ -1112,6 +1146,41 @@ extern "C" int dg_adamw_step_ema(float* p, const float* g, float* m, float* v, i
         case 5: LAUNCH(true, false, true); break;
         case 6: LAUNCH(true, true, false); break;
         default: LAUNCH(true, true, true); break;
+    }
+#undef LAUNCH
+    DG_LAUNCH_CHECK();
+    return DG_OK;
+}
+
+extern "C" int dg_adamw_step_guard(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, uint32_t* rng_state,
+                                   float grad_scale, const float* clip_coef, const float* lr_table, int64_t lr_table_len,
+                                   const uint32_t* no_decay_bits, void* shadow_bf16, int advance_step, float* ema, const float* ema_hyper,
+                                   const uint32_t* guard, uint32_t* data_state, void* stream) {
+    if (!p || !g || !m || !v || !hyper || !rng_state || !guard || n <= 0) return DG_ERR_ARG;
+    if ((ema == nullptr) != (ema_hyper == nullptr) || data_state == rng_state) return DG_ERR_ARG;
+    if (lr_table ? lr_table_len < 1 : lr_table_len != 0) return DG_ERR_ARG;
+    if (!dg_aligned16(p) || !dg_aligned16(g) || !dg_aligned16(m) || !dg_aligned16(v) || (ema && !dg_aligned16(ema))) return DG_ERR_ALIGN;
+    const unsigned grid = adamw_grid(n);
+    const AdamwSched sc{lr_table, lr_table_len, no_decay_bits};
+    const AdamwEma ea{ema, ema_hyper};
+#define LAUNCH(CLIP, TABLE, MASK, EMA) hipLaunchKernelGGL((adamw_kernel<CLIP, TABLE, MASK, AdamwSched, AdamwEma, AdamwGuard<EMA>>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, hyper, rng_state, grad_scale, (bf16_t*)shadow_bf16, advance_step, clip_coef, sc, ea, AdamwGuard<EMA>{guard, data_state})
+    switch ((ema ? 8 : 0) | (clip_coef ? 4 : 0) | (lr_table ? 2 : 0) | (no_decay_bits ? 1 : 0)) {
+        case 0: LAUNCH(false, false, false, false); break;
+        case 1: LAUNCH(false, false, true, false); break;
+        case 2: LAUNCH(false, true, false, false); break;
+        case 3: LAUNCH(false, true, true, false); break;
+        case 4: LAUNCH(true, false, false, false); break;
+        case 5: LAUNCH(true, false, true, false); break;
+        case 6: LAUNCH(true, true, false, false); break;
+        case 7: LAUNCH(true, true, true, false); break;
+        case 8: LAUNCH(false, false, false, true); break;
+        case 9: LAUNCH(false, false, true, true); break;
+        case 10: LAUNCH(false, true, false, true); break;
+        case 11: LAUNCH(false, true, true, true); break;
+        case 12: LAUNCH(true, false, false, true); break;
+        case 13: LAUNCH(true, false, true, true); break;
+        case 14: LAUNCH(true, true, false, true); break;
+        default: LAUNCH(true, true, true, true); break;
     }
 #undef LAUNCH
     DG_LAUNCH_CHECK();

@@ -60,8 +60,18 @@ __global__ __launch_bounds__(DG_SUMSQ_WG) void sumsq_partials_kernel(const float
 
 // total_norm = grad_scale * sqrt(sum), rounded to fp32 once; coef as torch evaluates it in fp32:
 // clamp(max_norm / (total_norm + 1e-6), max = 1) -- a NaN norm gives a NaN coefficient (the comparison below keeps it)
+// G = FinalizeGuard, the update guard: the same workgroup, the same sum and the same {total_norm, coef} bits (max_norm may then be
+// null: no coefficient is written), and the decision whether the optimizer update of this step is applied, in
+// guard = {apply, total skipped, consecutive skipped, spare}:
+//   apply = total_norm <= limit[0] && (loss == nullptr || isfinite(loss[0]))
+// A NaN or Inf norm fails the comparison against any finite limit (FLT_MAX guards non-finite gradients alone; +inf would let an
+// Inf norm through).  sumsq_partials_kernel squares in fp32, so a finite element beyond 1.8e19 in magnitude gives an Inf norm and
+// reads as non-finite too.  Thread 0 moves the counters with plain stores; dg_adamw_step_guard reads guard[0] in the next launch.
+// With an empty pack this is the kernel as it was, instruction for instruction.
+struct FinalizeGuard { const float* limit; const float* loss; uint32_t* guard; };
+template <typename... G>
 __global__ __launch_bounds__(DG_SUMSQ_WG) void grad_norm_finalize_kernel(const double* __restrict__ part, int n_parts, float grad_scale,
-                                                                         const float* __restrict__ max_norm, float* __restrict__ out) {
+                                                                         const float* __restrict__ max_norm, float* __restrict__ out, G... gd) {
     __shared__ double red[DG_SUMSQ_WG / 64];
     double acc = 0.0;
     for (int i0 = 0; i0 < n_parts; i0 += 8 * DG_SUMSQ_WG) {        // 8 independent loads in flight per lane, then a fixed-order sum
@@ -77,9 +87,23 @@ __global__ __launch_bounds__(DG_SUMSQ_WG) void grad_norm_finalize_kernel(const d
     const double s = block_sum_f64(acc, red);
     if (threadIdx.x == 0) {
         const float total = (float)(sqrt(s) * (double)grad_scale);
-        const float c = max_norm[0] / (total + 1e-6f);
-        out[0] = total;
-        out[1] = c > 1.f ? 1.f : c;
+        if constexpr (sizeof...(G) == 0) {
+            const float c = max_norm[0] / (total + 1e-6f);
+            out[0] = total;
+            out[1] = c > 1.f ? 1.f : c;
+        } else {
+            const FinalizeGuard fg = (gd, ...);
+            out[0] = total;
+            if (max_norm) {
+                const float c = max_norm[0] / (total + 1e-6f);
+                out[1] = c > 1.f ? 1.f : c;
+            }
+            bool apply = total <= fg.limit[0];
+            if (fg.loss) apply = apply && isfinite(fg.loss[0]);
+            fg.guard[0] = apply ? 1u : 0u;
+            fg.guard[1] += apply ? 0u : 1u;
+            fg.guard[2] = apply ? 0u : fg.guard[2] + 1u;
+        }
     }
 }
 
@@ -95,7 +119,16 @@ extern "C" int dg_sumsq_partials(const float* g, int64_t n, double* part, void* 
 
 extern "C" int dg_grad_norm_finalize(const double* part, int n_parts, float grad_scale, const float* max_norm, float* out, void* stream) {
     if (!part || !max_norm || !out || n_parts <= 0) return DG_ERR_ARG;
-    hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(DG_SUMSQ_WG), 0, (hipStream_t)stream, part, n_parts, grad_scale, max_norm, out);
+    hipLaunchKernelGGL(grad_norm_finalize_kernel<>, dim3(1), dim3(DG_SUMSQ_WG), 0, (hipStream_t)stream, part, n_parts, grad_scale, max_norm, out);
+    DG_LAUNCH_CHECK();
+    return DG_OK;
+}
+
+extern "C" int dg_grad_norm_finalize_guard(const double* part, int n_parts, float grad_scale, const float* max_norm, float* out,
+                                           const float* limit, const float* loss, uint32_t* guard, void* stream) {
+    if (!part || !out || !limit || !guard || n_parts <= 0) return DG_ERR_ARG;
+    hipLaunchKernelGGL(grad_norm_finalize_kernel<FinalizeGuard>, dim3(1), dim3(DG_SUMSQ_WG), 0, (hipStream_t)stream, part, n_parts, grad_scale, max_norm,
+                       out, FinalizeGuard{limit, loss, guard});
     DG_LAUNCH_CHECK();
     return DG_OK;
 }

@@ -211,7 +211,17 @@ class TrainEngine:
                  dp_buckets: Optional[int] = None, logits: str = "auto", grad_stream: str = "auto", fp8_dw: Optional[bool] = None,
                  max_grad_norm: Optional[float] = None, accum_steps: int = 1, lr_schedule=None, schedule_steps: Optional[int] = None,
                  no_decay=(), label_smoothing: float = 0.0, z_loss: float = 0.0, ema_decay: Optional[float] = None,
-                 ema_warmup: bool = False, ignore_index: Optional[int] = None):
+                 ema_warmup: bool = False, ignore_index: Optional[int] = None, skip_nonfinite: bool = False,
+                 skip_grad_norm: Optional[float] = None):
+        """skip_nonfinite / skip_grad_norm: the update guard (off by default).  The optimizer update of a
+        step is applied only if the global gradient norm is at most skip_grad_norm (skip_nonfinite alone: if it is finite) and the
+        step's loss is finite; otherwise it is skipped on the device, inside the same captured graph, with no host sync.  A skipped
+        step leaves weights, moments, the bf16 shadow, every weight-derived copy, the moving average and the optimizer's step word
+        (bias correction, LR-table index, EMA warm-up) untouched, bit for bit, while the data side (dropout key, staged offset
+        row, fp8 amax slot, micro-step counter) moves on to the next batch.  The sum of squares is taken in fp32: a gradient
+        element beyond 1.8e19 in magnitude reads as non-finite.  With more than one rank the decision rests on the all-reduced
+        gradient alone (the same on every rank); a rank's own loss is not consulted.  precision fp8: weights, moments and
+        checkpoints stay clean, but an amax history that has itself gone NaN is not healed (its scale stays NaN on purpose)."""
         if not isinstance(model, TransformerLM):
             raise TypeError("TrainEngine drives TransformerLM (the other five models train through the autograd path)")
         p0 = next(model.parameters())
@@ -263,6 +273,9 @@ class TrainEngine:
         # an exponential moving average of the weights, moved on inside the AdamW launch (None: no average, nothing below exists)
         self.ema_decay = ops.check_ema_options(ema_decay, ema_warmup)
         self.ema_warmup = bool(ema_warmup)
+        # the update guard (off: nothing of it exists): whether it is on, and the norm limit as given (None: non-finite only)
+        self.guard_on, _guard_limit = ops.check_guard_options(skip_nonfinite, skip_grad_norm)
+        self.skip_grad_norm = None if skip_grad_norm is None else _guard_limit
         if self.accum > 1 and dp_buckets is not None and int(dp_buckets) > 1:
             raise ValueError("accum_steps > 1 uses one gradient exchange per optimizer step (it is amortised over the micro-steps "
                              "already): dp_buckets > 1 cannot be combined with it")
@@ -366,6 +379,22 @@ class TrainEngine:
             self.clip_state = torch.tensor([0.0, 1.0, self.max_grad_norm, 0.0], dtype=torch.float32, device=self.dev)
             self.norm_work = ops.grad_norm_workspace([self.gflat], self.dev)
             self.last_grad_norm = self.clip_state[0]          # 0-d view: the pre-clip norm of the latest step
+        # the update guard: guard = {apply, total skipped, consecutive skipped, spare}, written by the finalize launch of the norm
+        # (which then runs with or without clipping) and read by every workgroup of the AdamW launch; guard_limit is read on the
+        # device (set_skip_grad_norm() writes it: captured graphs stay valid).  norm_out = {total_norm, coef} is clip_state where
+        # the engine clips.  _guard_kw is what _prog_update adds to its ops.adamw_step call: nothing for an engine without the
+        # guard, whose call is the one it always was.
+        self.guard = self.guard_limit = self.norm_out = None
+        self._guard_kw = {}
+        if self.guard_on:
+            self.guard = ops.new_update_guard(self.dev)
+            self.guard_limit = torch.tensor([_guard_limit], dtype=torch.float32, device=self.dev)
+            self.norm_out = self.clip_state
+            if self.clip_state is None:
+                self.norm_out = torch.zeros(2, dtype=torch.float32, device=self.dev)
+                self.norm_work = ops.grad_norm_workspace([self.gflat], self.dev)
+                self.last_grad_norm = self.norm_out[0]
+            self._guard_kw = {"guard": self.guard}
         # dropout stream differs per data-parallel rank; the step word also drives Adam's bias correction
         self.seed = int(seed)
         self.state = ops.new_rng_state(self._rank_seed(self.seed), self.dev, 0)
@@ -380,6 +409,12 @@ class TrainEngine:
             self.acc_ctl = ops.new_accum_ctl(self.accum, self.dev)
             self.opt_state = ops.new_rng_state(0, self.dev, 0)
             self.loss_acc = torch.zeros(2, dtype=torch.float32, device=self.dev)
+        elif self.guard_on:
+            # the guard with accum_steps 1: the same two words.  state[2] stays the data word (it moves every step: the AdamW
+            # launch writes it through data_state), opt_state[2] is Adam's t and counts applied updates.  (accum_steps > 1:
+            # dg_grad_accumulate already moves the data word.)
+            self.opt_state = ops.new_rng_state(0, self.dev, 0)
+            self._guard_kw["data_state"] = self.state
         # window offsets: a staged block [rows, B] the captured step walks through by itself (row = step word - off_ctl[0],
         # clamped to off_ctl[1] rows); set_offsets() is the one-row form (row 0, off_ctl[1] = 1)
         self.off_block = torch.zeros((self.OFFSET_ROWS, self.B), dtype=torch.int64, device=self.dev)
@@ -939,20 +974,30 @@ class TrainEngine:
         ops.grad_accumulate(self.gacc, self.gflat, self.n_active, self.acc_ctl, self.loss, self.loss_acc, self.state)
 
     def _prog_update(self):
-        """norm (if clipping), AdamW, W^T refresh.  The gradient is final here on every path (the data-parallel update runs after
+        """norm (if clipping or guarded), AdamW, W^T refresh.  The gradient is final here on every path (the data-parallel update runs after
         the exchange): gflat * 1 / world, the mean over ranks, with the step word as t -- or, accum_steps = k > 1, gacc * 1 /
         (k * world), the mean over micro-batches and ranks, with the optimizer's own counter.  The word moves on inside the AdamW
         launch: nothing after it reads the word."""
-        grad, word = (self.gflat, self.state) if self.accum == 1 else (self.gacc, self.opt_state)
+        grad = self.gflat if self.accum == 1 else self.gacc
+        word = self.state if self.opt_state is None else self.opt_state
         scale = 1.0 / (self.accum * self.world)
         clip = {}
-        if self.clip_state is not None:
+        if self.guard is not None:
+            # the guard: the norm's two launches with or without clipping; the finalize launch also decides whether AdamW applies
+            # the update (norm <= limit, and -- one rank -- the step's loss finite: under accumulation the running sum of the micro
+            # losses).  With more ranks the all-reduced gradient alone decides, so that every rank decides the same.
+            loss = None if self.world > 1 else (self.loss if self.accum == 1 else self.loss_acc[0:1])
+            ops.grad_norm(grad, scale, None if self.clip_state is None else self.clip_state[2:3], self.norm_out, self.norm_work,
+                          guard=self.guard, limit=self.guard_limit, loss=loss)
+            if self.clip_state is not None:
+                clip = {"clip": self.clip_state[1:2]}
+        elif self.clip_state is not None:
             # AdamW on g * coef.  The alignment gaps of the gradient buffer are zero (no producer writes them), so the norm over
             # the whole active range is the norm over the parameters.
             ops.grad_norm(grad, scale, self.clip_state[2:3], self.clip_state, self.norm_work)
             clip = {"clip": self.clip_state[1:2]}
         ops.adamw_step(self.flat, grad, self.m_, self.v_, self.hyper, word, scale, shadow_bf16=self.shadow, n=self.n_active,
-                       advance=True, **clip, **self._sched_kw, **self._ema_kw)
+                       advance=True, **clip, **self._sched_kw, **self._ema_kw, **self._guard_kw)
         self._refresh_transposes()
 
     # -------------------------------------------------------------------------------- the step: description, capture, run
@@ -975,7 +1020,7 @@ class TrainEngine:
     def _snapshot(self):
         """copy every buffer and counter the step's programs move; returns the call that puts them back"""
         bufs = [self.flat, self.m_, self.v_, self.state]
-        bufs += [b for b in (self.ema, self.gacc, self.acc_ctl, self.opt_state, self.loss_acc) if b is not None]
+        bufs += [b for b in (self.ema, self.gacc, self.acc_ctl, self.opt_state, self.loss_acc, self.guard) if b is not None]
         snap = [b.clone() for b in bufs]
 
         def put_back():
@@ -1094,6 +1139,36 @@ class TrainEngine:
             raise RuntimeError("set_max_grad_norm: this engine was built without clipping (TrainEngine(..., max_grad_norm=...))")
         self.max_grad_norm = check_max_grad_norm(max_norm)
         self.clip_state[2:3].fill_(self.max_grad_norm)
+
+    # ---- the update guard (TrainEngine(skip_nonfinite=..., skip_grad_norm=...))
+    def _need_guard(self, what: str) -> None:
+        if self.guard is None:
+            raise RuntimeError(f"{what}: this engine was built without the update guard (TrainEngine(..., skip_nonfinite=True) or "
+                               "skip_grad_norm=...)")
+
+    def set_skip_grad_norm(self, limit: Optional[float]):
+        """a new norm limit for the following steps, or None for non-finite gradients only (a device write: captured graphs stay
+        valid)"""
+        self._need_guard("set_skip_grad_norm")
+        staged = ops.check_guard_options(True, limit)[1]
+        self.skip_grad_norm = None if limit is None else staged
+        self.guard_limit.fill_(staged)
+
+    @property
+    def last_step_applied(self) -> Optional[Tensor]:
+        """1 if the latest optimizer step applied its update, 0 if the guard skipped it (0-d device view; reading it synchronises;
+        None without the guard)"""
+        return None if self.guard is None else self.guard[0]
+
+    def skipped_steps(self) -> int:
+        """optimizer steps the guard has skipped so far.  Synchronises."""
+        self._need_guard("skipped_steps")
+        return int(self.guard[1].item()) & 0xFFFFFFFF
+
+    def consecutive_skips(self) -> int:
+        """optimizer steps skipped in a row up to the latest one (0 after an applied update).  Synchronises."""
+        self._need_guard("consecutive_skips")
+        return int(self.guard[2].item()) & 0xFFFFFFFF
 
     # ---- the moving average of the weights (TrainEngine(ema_decay=...); DESIGN.md section 4.12)
     def _refuse_in_ema(self, what: str) -> None:
@@ -1324,13 +1399,16 @@ class TrainEngine:
             meta["ignore_index"] = self.ignore_index
         if self.ema is not None:
             meta["ema"] = True
+        if self.guard is not None:
+            meta["update_guard"] = True
         return meta
 
     def _check_meta(self, saved: dict) -> None:
         """CK.check_compat on the fields every engine has; the loss options in both directions (a field absent on either side reads
         as 0.0: a smoothed state is refused by a default engine as much as the reverse)"""
-        CK.check_compat(saved, {k: v for k, v in self._meta().items() if k not in self._LOSS_FIELDS and k not in ("ema", "ignore_index")})
+        CK.check_compat(saved, {k: v for k, v in self._meta().items() if k not in self._LOSS_FIELDS and k not in ("ema", "ignore_index", "update_guard")})
         CK.check_ema_meta(saved, self.ema is not None)
+        CK.check_guard_meta(saved, self.guard is not None)
         for field in self._LOSS_FIELDS:
             theirs, own = saved.get(field, 0.0), self._loss_kw.get(field, 0.0)
             if isinstance(theirs, bool) or not isinstance(theirs, (int, float)) or float(theirs) != own:
@@ -1407,7 +1485,7 @@ class TrainEngine:
         self.v_.copy_(v)
         self.hyper_host = [hyper["lr"], hyper["betas"][0], hyper["betas"][1], hyper["eps"], hyper["weight_decay"]]
         self.hyper.copy_(torch.tensor(self.hyper_host, dtype=torch.float32))
-        word = self.state if self.accum == 1 else self.opt_state
+        word = self.state if self.opt_state is None else self.opt_state
         word[2:3].copy_(ops.new_rng_state(0, self.dev, step)[2:3])
 
     @torch.no_grad()
@@ -1439,6 +1517,9 @@ class TrainEngine:
                "lr_table": None if self.lr_table_host is None else self.lr_table_host.clone(), "no_decay": list(self.no_decay)}
         if self.ema is not None:
             eng["ema"] = {"decay": self.ema_decay, "warmup": self.ema_warmup, "values": self.ema.cpu()}
+        if self.guard is not None:      # only where on: a default engine writes exactly the files it always did
+            eng["guard"] = {"skipped": self.skipped_steps(), "consecutive": self.consecutive_skips(), "limit": self.skip_grad_norm,
+                            "opt_step": int(self.opt_state[2].item()) & 0xFFFFFFFF}
         return {"format": CK.FORMAT, "version": CK.VERSION,
                 "model": {k: v.detach().cpu().clone() for k, v in self.model.state_dict().items()},
                 "optimizer": self.optimizer_state_dict(), "engine": eng, "meta": self._meta()}
@@ -1452,7 +1533,9 @@ class TrainEngine:
         validated before anything is written (ValueError names the field and both values; the engine is untouched then), and
         written in place: the model's Parameters stay views of `flat` and captured graphs stay valid (a staged block larger than
         the offset buffer is the one exception, as in stage_offsets).  Hyper-parameters follow the file; clipping on / off follows
-        this engine, its threshold the file where both clip.  Every rank loads rank 0's file; the dropout stream is re-derived
+        this engine, its threshold the file where both clip.  The update guard: a file written with it restores both step words,
+        both counters and the limit; a file written without it loads into a guarded engine (the optimizer word starts at the
+        step word, the counters at 0); a guarded file is refused by an engine without the guard.  Every rank loads rank 0's file; the dropout stream is re-derived
         from the saved seed for this rank.  precision fp8: a rank other than 0 seeds its amax histories afresh."""
         self._refuse_in_ema("load_state_dict()")
         CK.check_format(sd)
@@ -1493,6 +1576,14 @@ class TrainEngine:
         m, v, step, hyper = self._parse_optimizer_state(sd["optimizer"])
         word = int(e["step_word"])
         opt_step = word if self.accum == 1 else e["opt_step"]
+        # the update guard: a guarded file restores both words, both counters and the limit; an unguarded file into a guarded
+        # engine starts the optimizer word at the step word and the counters at 0 (the guard can be turned on mid-run); a guarded
+        # file into an engine without the guard was refused by _check_meta
+        guard_sd = CK.check_guard_state(e.get("guard"), sd["meta"], self.guard is not None, word)
+        if guard_sd is not None and guard_sd[4]:
+            if self.accum > 1 and e["opt_step"] != guard_sd[0]:
+                raise ValueError(f"training state: engine.guard.opt_step is {guard_sd[0]}, engine.opt_step {e['opt_step']!r}")
+            opt_step = guard_sd[0]
         if opt_step is None or int(opt_step) != step:
             raise ValueError(f"training state: engine step count differs: the engine section says {opt_step!r}, the optimizer state {step}")
         if self.accum > 1:
@@ -1548,9 +1639,16 @@ class TrainEngine:
             self.ema.copy_(ema_sd[2])
         self.seed = int(e["seed"])
         self.state.copy_(ops.new_rng_state(self._rank_seed(self.seed), self.dev, word))
-        if self.accum > 1:
+        if self.opt_state is not None:
             self.opt_state[2:3].copy_(ops.new_rng_state(0, self.dev, step)[2:3])
+        if self.accum > 1:
             self.acc_ctl.copy_(e["acc_ctl"])
+        if guard_sd is not None:
+            # (apply, the latest decision, follows from the consecutive count)
+            self.guard.copy_(torch.tensor([0 if guard_sd[2] else 1, *(x - (1 << 32) if x >= (1 << 31) else x for x in guard_sd[1:3]), 0],
+                                          dtype=torch.int32))
+            if guard_sd[4]:
+                self.set_skip_grad_norm(guard_sd[3])
         self._j = 0
         if mgn is not None and self.clip_state is not None:
             self.set_max_grad_norm(mgn)
@@ -1582,8 +1680,8 @@ class TrainEngine:
                 raise RuntimeError("dg_gemm_tn_grouped: a split-K hand-over timed out; weight gradients since then are invalid")
 
     def step_count(self) -> int:
-        """optimizer steps taken"""
-        return int((self.state if self.accum == 1 else self.opt_state)[2].item())
+        """optimizer steps taken (with the update guard: updates applied)"""
+        return int((self.state if self.opt_state is None else self.opt_state)[2].item())
 
     def micro_step_count(self) -> int:
         """micro-batches run: the word that keys dropout and selects the staged offset row (== step_count() for accum_steps 1)"""

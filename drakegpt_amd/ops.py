@@ -991,7 +991,8 @@ def _check_adamw_indexing(n: int, streams: dict, lr_table, no_decay_bits, clip) 
 def adamw_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, hyper: Tensor, rng_state: Tensor, grad_scale: float = 1.0,
                shadow_bf16: Optional[Tensor] = None, n: Optional[int] = None, advance: bool = False, *,
                clip: Optional[Tensor] = None, lr_table: Optional[Tensor] = None, no_decay_bits: Optional[Tensor] = None,
-               ema: Optional[Tensor] = None, ema_hyper: Optional[Tensor] = None) -> None:
+               ema: Optional[Tensor] = None, ema_hyper: Optional[Tensor] = None, guard: Optional[Tensor] = None,
+               data_state: Optional[Tensor] = None) -> None:
     """advance: the launch also moves the step word of rng_state on (what state_advance does, without its launch).
     clip: a device fp32 scalar, the clipping coefficient written by grad_norm (out[1:2]); the step then applies g * grad_scale * coef
     (dg_adamw_step_clip) and g itself stays unclipped.  None: dg_adamw_step, unchanged.
@@ -1000,12 +1001,44 @@ def adamw_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, hyper: Tensor, rng_st
     Either of the two takes the launch to dg_adamw_step_sched; with both None the calls are the ones above, unchanged.
     ema (with ema_hyper = new_ema_hyper(decay, warmup, device)): the launch also moves this moving average of the weights on
     (dg_adamw_step_ema: ema += (p_new - ema) * (1 - d_s) by the step word it reads; step word 0: ema = p_new); p, m, v, the shadow
-    and the state words are the ones the launch without it writes.  None: the calls above, unchanged."""
+    and the state words are the ones the launch without it writes.  None: the calls above, unchanged.
+    guard: the update guard grad_norm(guard=...) has just written (new_update_guard); the launch goes to dg_adamw_step_guard, with
+    any of the operands above.  guard[0] == 1: the bits of the launch without it.  guard[0] == 0: the update is skipped -- no buffer
+    is read or written and rng_state's step word stays.  data_state (with guard and advance): a second 4-word state whose step word
+    the launch moves on in either case (the data side of a training step: dropout key, staged offset row, fp8 amax slot).
+    None: the calls above, unchanged."""
     for t, nm in ((p, "p"), (g, "g"), (m, "m"), (v, "v"), (hyper, "hyper")):
         _chk(t, nm, torch.float32)
     n = p.numel() if n is None else n
     if ema is None and ema_hyper is not None:
         raise ValueError("adamw_step: ema_hyper goes with ema")
+    if guard is None and data_state is not None:
+        raise ValueError("adamw_step: data_state goes with guard")
+    if guard is not None:
+        if ema is not None and ema_hyper is None:
+            raise ValueError("adamw_step: ema needs ema_hyper (new_ema_hyper)")
+        _chk(guard, "guard", torch.int32)
+        _chk(rng_state, "rng_state", torch.int32)
+        if guard.numel() < 4 or rng_state.numel() < 4:
+            raise ValueError("adamw_step: guard and rng_state need 4 words each (new_update_guard, new_rng_state)")
+        streams = {"p": p, "g": g, "m": m, "v": v}
+        if ema is not None:
+            _chk(ema, "ema", torch.float32)
+            _chk(ema_hyper, "ema_hyper", torch.float32)
+            if ema_hyper.numel() < 2:
+                raise ValueError("adamw_step: ema_hyper needs 2 floats {decay, warmup} (new_ema_hyper)")
+            streams["ema"] = ema
+        _check_adamw_indexing(n, streams, lr_table, no_decay_bits, clip)
+        if shadow_bf16 is not None and shadow_bf16.numel() < n:
+            raise ValueError(f"adamw_step: shadow_bf16 holds {shadow_bf16.numel()} elements, n = {n}")
+        if data_state is not None:
+            _chk(data_state, "data_state", torch.int32)
+            if data_state.numel() < 4 or data_state.data_ptr() == rng_state.data_ptr():
+                raise ValueError("adamw_step: data_state needs 4 words of its own (not rng_state)")
+        check(lib.dg_adamw_step_guard(_p(p), _p(g), _p(m), _p(v), n, _p(hyper), _p(rng_state), float(grad_scale), _p(clip), _p(lr_table),
+                                      0 if lr_table is None else lr_table.numel(), _p(no_decay_bits), _p(shadow_bf16), int(advance),
+                                      _p(ema), _p(ema_hyper), _p(guard), _p(data_state), _stream()), "dg_adamw_step_guard")
+        return
     if ema is not None:
         if ema_hyper is None:
             raise ValueError("adamw_step: ema needs ema_hyper (new_ema_hyper)")
@@ -1109,15 +1142,63 @@ def grad_norm_workspace(gs, device) -> Tensor:
     return torch.empty(sum(int(lib.dg_sumsq_parts(g.numel())) for g in gs), dtype=torch.float64, device=device)
 
 
-def grad_norm(gs, grad_scale: float, max_norm: Tensor, out: Tensor, work: Optional[Tensor] = None) -> Tensor:
+GUARD_NONFINITE_LIMIT = float(torch.finfo(torch.float32).max)   # the limit that guards non-finite gradients alone (+inf would pass an Inf norm)
+
+
+def check_guard_options(skip_nonfinite=False, skip_grad_norm=None):
+    """the checks of the two update-guard options, plain Python, raised before anything touches a device: skip_nonfinite a bool;
+    skip_grad_norm None or a finite number > 0 (no bools, no NaN), the largest global gradient norm whose update is applied.
+    skip_grad_norm implies skip_nonfinite (a non-finite norm fails the comparison too).  Returns (on, limit): whether the guard
+    is on, and the fp32 limit to stage (None when off; FLT_MAX with skip_nonfinite alone)."""
+    if not isinstance(skip_nonfinite, bool):
+        raise ValueError(f"skip_nonfinite must be a bool, got {skip_nonfinite!r}")
+    if skip_grad_norm is None:
+        return skip_nonfinite, (GUARD_NONFINITE_LIMIT if skip_nonfinite else None)
+    if isinstance(skip_grad_norm, bool):
+        raise ValueError(f"skip_grad_norm must be a finite number > 0 or None, got {skip_grad_norm!r}")
+    try:
+        f = float(skip_grad_norm)
+    except (TypeError, ValueError):
+        raise ValueError(f"skip_grad_norm must be a finite number > 0 or None, got {skip_grad_norm!r}") from None
+    if not (0.0 < f < math.inf):          # (NaN fails both comparisons)
+        raise ValueError(f"skip_grad_norm must be a finite number > 0 or None, got {skip_grad_norm!r}")
+    return True, min(f, GUARD_NONFINITE_LIMIT)
+
+
+def new_update_guard(device) -> Tensor:
+    """device uint32[4] = {apply = 1, total skipped = 0, consecutive skipped = 0, spare} for grad_norm(guard=...) and
+    adamw_step(guard=...) (stored as int32)"""
+    return torch.tensor([1, 0, 0, 0], dtype=torch.int32, device=device)
+
+
+def grad_norm(gs, grad_scale: float, max_norm: Optional[Tensor], out: Tensor, work: Optional[Tensor] = None, *,
+              guard: Optional[Tensor] = None, limit: Optional[Tensor] = None, loss: Optional[Tensor] = None) -> Tensor:
     """global 2-norm of the flat fp32 gradients gs (a tensor or a list of them: one norm over all) times grad_scale, and the
     clipping coefficient -- the norm and coef of torch.nn.utils.clip_grad_norm_(params, max_norm) (norm_type 2), without touching
     the gradients.  Writes out[0] = total_norm, out[1] = min(1, max_norm / (total_norm + 1e-6)); max_norm is a device fp32 scalar.
-    One dg_sumsq_partials launch per buffer and one dg_grad_norm_finalize launch; the result is bitwise reproducible."""
+    One dg_sumsq_partials launch per buffer and one dg_grad_norm_finalize launch; the result is bitwise reproducible.
+    guard (new_update_guard) with limit (a device fp32 scalar) and optionally loss (a device fp32 scalar): the finalize launch is
+    dg_grad_norm_finalize_guard -- the same out bits, and guard = {apply, total skipped, consecutive skipped}: apply = total_norm
+    <= limit and loss is finite.  max_norm may then be None (no clipping: out[1] is not written).  The sum of squares is taken in
+    fp32, so an element beyond 1.8e19 in magnitude reads as non-finite (as in all_finite).  Without guard: the calls as they were."""
     gs = [gs] if isinstance(gs, Tensor) else list(gs)
     for i, g in enumerate(gs):
         _chk(g, f"gs[{i}]", torch.float32)
-    _chk(max_norm, "max_norm", torch.float32)
+    if guard is None:
+        if limit is not None or loss is not None:
+            raise ValueError("grad_norm: limit and loss go with guard")
+        _chk(max_norm, "max_norm", torch.float32)
+    else:
+        if limit is None:
+            raise ValueError("grad_norm: guard needs limit (a device fp32 scalar)")
+        _chk(guard, "guard", torch.int32)
+        if guard.numel() < 4:
+            raise ValueError("grad_norm: guard needs 4 words {apply, skipped, consecutive, spare} (new_update_guard)")
+        for t, nm in ((max_norm, "max_norm"), (limit, "limit"), (loss, "loss")):
+            if t is not None:
+                _chk(t, nm, torch.float32)
+                if t.numel() < 1:
+                    raise ValueError(f"grad_norm: {nm} needs 1 float")
     _chk(out, "out", torch.float32)
     if out.numel() < 2:
         raise ValueError("grad_norm: out needs 2 floats {total_norm, coef}")
@@ -1130,7 +1211,11 @@ def grad_norm(gs, grad_scale: float, max_norm: Tensor, out: Tensor, work: Option
     for g, k in zip(gs, parts):
         check(lib.dg_sumsq_partials(_p(g), g.numel(), work.data_ptr() + 8 * base, _stream()), "dg_sumsq_partials")
         base += k
-    check(lib.dg_grad_norm_finalize(_p(work), base, float(grad_scale), _p(max_norm), _p(out), _stream()), "dg_grad_norm_finalize")
+    if guard is None:
+        check(lib.dg_grad_norm_finalize(_p(work), base, float(grad_scale), _p(max_norm), _p(out), _stream()), "dg_grad_norm_finalize")
+    else:
+        check(lib.dg_grad_norm_finalize_guard(_p(work), base, float(grad_scale), _p(max_norm), _p(out), _p(limit), _p(loss), _p(guard),
+                                              _stream()), "dg_grad_norm_finalize_guard")
     return out
 
 

@@ -18,7 +18,14 @@ pre-clip norm of the latest step, a device scalar.
 ema_decay (with ema_warmup): an exponential moving average of the weights, one flat buffer per parameter group, moved on inside the
 AdamW launch by the group's own step count (the recurrence of ``AveragedModel(model, multi_avg_fn=get_ema_multi_avg_fn(d))``
 updated after every ``step()``).  ``with optimizer.ema_weights():`` swaps the weights with their average for evaluation, sampling
-or ``model.state_dict()``; ``state_dict()`` carries the averages under a top-level ``"ema"`` key (only when on)."""
+or ``model.state_dict()``; ``state_dict()`` carries the averages under a top-level ``"ema"`` key (only when on).
+
+skip_nonfinite / skip_grad_norm: the update guard (``torch.amp.GradScaler``'s found_inf skip, decided on the GPU with no host sync).
+One norm is taken over all groups' flat gradients, with or without clipping; every group's AdamW launch reads the same guard word
+and, when the norm is not finite (or above ``skip_grad_norm``), touches nothing: no group's parameters, moments, average or step
+count move.  The sum of squares is taken in fp32, so a gradient element beyond 1.8e19 in magnitude reads as non-finite.
+``last_step_applied`` is the latest decision (a device scalar), ``skipped_steps()`` the count; ``state_dict()`` carries a top-level
+``"guard"`` key (only when on)."""
 from __future__ import annotations
 
 import contextlib
@@ -74,12 +81,17 @@ class _Flat:
 
 class AdamW(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, *, process_group=None, world_size: int = 1,
-                 max_grad_norm: Optional[float] = None, ema_decay: Optional[float] = None, ema_warmup: bool = False):
+                 max_grad_norm: Optional[float] = None, ema_decay: Optional[float] = None, ema_warmup: bool = False,
+                 skip_nonfinite: bool = False, skip_grad_norm: Optional[float] = None):
         self.max_grad_norm = None if max_grad_norm is None else check_max_grad_norm(max_grad_norm)
         self.ema_decay = ops.check_ema_options(ema_decay, ema_warmup)
         self.ema_warmup = bool(ema_warmup)
         self._ema_hyper = {}            # device -> {decay, warmup} there, made with the first flat group on that device
         self._in_ema = False
+        self.guard_on, self._guard_limit_host = ops.check_guard_options(skip_nonfinite, skip_grad_norm)
+        self.skip_grad_norm = None if skip_grad_norm is None else self._guard_limit_host
+        self._guard = self._guard_limit = None      # device {apply, skipped, consecutive, spare} and the fp32 limit (after the first step)
+        self._guard_loaded = None                   # counters of a loaded state_dict, written with the first step's allocation
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.process_group, self.world_size = process_group, int(world_size)
         self._flat = {}
@@ -91,6 +103,37 @@ class AdamW(torch.optim.Optimizer):
     def last_grad_norm(self) -> Optional[torch.Tensor]:
         """pre-clip global gradient norm of the latest step (0-d device tensor; None without clipping or before the first step)"""
         return None if self._clip is None else self._clip[0]
+
+    @property
+    def last_step_applied(self) -> Optional[torch.Tensor]:
+        """1 if the latest step() applied its update, 0 if the guard skipped it (0-d device tensor; None without the guard or before
+        the first step)"""
+        return None if self._guard is None else self._guard[0]
+
+    def skipped_steps(self) -> int:
+        """steps the guard has skipped so far.  Synchronises."""
+        if not self.guard_on:
+            raise RuntimeError("skipped_steps: this optimizer was built without the update guard (AdamW(..., skip_nonfinite=True))")
+        if self._guard is None:
+            return 0 if self._guard_loaded is None else self._guard_loaded[0]
+        return int(self._guard[1].item()) & 0xFFFFFFFF
+
+    def consecutive_skips(self) -> int:
+        """steps skipped in a row up to the latest one (0 after an applied update).  Synchronises."""
+        if not self.guard_on:
+            raise RuntimeError("consecutive_skips: this optimizer was built without the update guard (AdamW(..., skip_nonfinite=True))")
+        if self._guard is None:
+            return 0 if self._guard_loaded is None else self._guard_loaded[1]
+        return int(self._guard[2].item()) & 0xFFFFFFFF
+
+    def set_skip_grad_norm(self, limit: Optional[float]) -> None:
+        """a new norm limit for the following steps, or None for non-finite gradients only"""
+        if not self.guard_on:
+            raise RuntimeError("set_skip_grad_norm: this optimizer was built without the update guard (AdamW(..., skip_nonfinite=True))")
+        self._guard_limit_host = ops.check_guard_options(True, limit)[1]
+        self.skip_grad_norm = None if limit is None else self._guard_limit_host
+        if self._guard_limit is not None:
+            self._guard_limit.fill_(self._guard_limit_host)
 
     def _adopt(self, gi: int, params) -> _Flat:
         old = self._flat.get(gi)
@@ -167,13 +210,14 @@ class AdamW(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         scale = 1.0 / self.world_size if self.world_size > 1 else 1.0
-        if self.max_grad_norm is None:
+        if self.max_grad_norm is None and not self.guard_on:
             for gi, group in enumerate(self.param_groups):
                 fl = self._gather(gi, group)
                 if fl is not None:
                     ops.adamw_step(fl.flat, fl.g, fl.m, fl.v, fl.hyper, fl.t, grad_scale=scale, advance=True, **self._ema_kw(fl))
             return loss
-        # clipping: every group's (all-reduced) gradient first, then ONE norm over all of them, then every group's update with it
+        # clipping / the guard: every group's (all-reduced) gradient first, then ONE norm over all of them, then every group's
+        # update with its coefficient / its decision
         flats = [fl for fl in (self._gather(gi, group) for gi, group in enumerate(self.param_groups)) if fl is not None]
         if not flats:
             return loss
@@ -181,17 +225,33 @@ class AdamW(torch.optim.Optimizer):
         if self._clip is None or self._clip.device != dev:
             self._clip = torch.tensor([0.0, 1.0, 0.0, 0.0], dtype=torch.float32, device=dev)
             self._clip_host = None
-        if self._clip_host != self.max_grad_norm:
+        if self.max_grad_norm is not None and self._clip_host != self.max_grad_norm:
             self.max_grad_norm = check_max_grad_norm(self.max_grad_norm)
             self._clip[2:3].fill_(self.max_grad_norm)
             self._clip_host = self.max_grad_norm
         key = tuple(fl.n for fl in flats)
         if self._norm_work is None or self._norm_work[0] != key or self._norm_work[1].device != dev:
             self._norm_work = (key, ops.grad_norm_workspace([fl.g for fl in flats], dev))
-        ops.grad_norm([fl.g for fl in flats], scale, self._clip[2:3], self._clip, self._norm_work[1])
+        clip = {} if self.max_grad_norm is None else {"clip": self._clip[1:2]}
+        guard_norm, guard_step = {}, {}
+        if self.guard_on:
+            if self._guard is None or self._guard.device != dev:
+                old = self._guard
+                self._guard = ops.new_update_guard(dev)
+                self._guard_limit = torch.tensor([self._guard_limit_host], dtype=torch.float32, device=dev)
+                if old is not None:
+                    self._guard.copy_(old)
+                elif self._guard_loaded is not None:
+                    sk, cons = self._guard_loaded
+                    self._guard.copy_(torch.tensor([0 if cons else 1, sk, cons, 0], dtype=torch.int32))
+                self._guard_loaded = None
+            guard_norm = {"guard": self._guard, "limit": self._guard_limit}
+            guard_step = {"guard": self._guard}
+        ops.grad_norm([fl.g for fl in flats], scale, None if self.max_grad_norm is None else self._clip[2:3], self._clip,
+                      self._norm_work[1], **guard_norm)
         for fl in flats:
-            ops.adamw_step(fl.flat, fl.g, fl.m, fl.v, fl.hyper, fl.t, grad_scale=scale, advance=True, clip=self._clip[1:2],
-                           **self._ema_kw(fl))
+            ops.adamw_step(fl.flat, fl.g, fl.m, fl.v, fl.hyper, fl.t, grad_scale=scale, advance=True, **clip, **self._ema_kw(fl),
+                           **guard_step)
         return loss
 
     def _gather(self, gi: int, group) -> Optional[_Flat]:
@@ -256,6 +316,8 @@ class AdamW(torch.optim.Optimizer):
         sd["state"] = state
         if self.ema_decay is not None:              # only when on: without it the dict is torch.optim.AdamW's, key for key
             sd["ema"] = {"decay": self.ema_decay, "warmup": self.ema_warmup, "values": ema}
+        if self.guard_on:                           # only when on, too
+            sd["guard"] = {"skipped": self.skipped_steps(), "consecutive": self.consecutive_skips(), "limit": self.skip_grad_norm}
         return sd
 
     @torch.no_grad()
@@ -283,7 +345,23 @@ class AdamW(torch.optim.Optimizer):
                 if len(steps) > 1:
                     raise ValueError("drakegpt_amd.optim.AdamW keeps ONE step count per parameter group; the state holds " + str(steps))
                 base += len(group["params"])
+        guard = state_dict.get("guard")
+        if guard is not None and not self.guard_on:
+            raise ValueError("optimizer state: guard differs: saved present, this optimizer has the update guard off")
+        if guard is not None:
+            for k in ("skipped", "consecutive", "limit"):
+                if k not in guard:
+                    raise ValueError(f"optimizer state: missing key guard.{k}")
+            for k in ("skipped", "consecutive"):
+                if isinstance(guard[k], bool) or not isinstance(guard[k], int) or not 0 <= guard[k] < (1 << 31):
+                    raise ValueError(f"optimizer state: guard.{k} is {guard[k]!r}, expected an integer >= 0")
+            ops.check_guard_options(True, guard["limit"])
         super().load_state_dict({"state": {}, "param_groups": state_dict["param_groups"]})
+        if self.guard_on:      # (a file without the section: the guard was turned on mid-run, the counters start at 0)
+            self._guard = self._guard_limit = None
+            self._guard_loaded = (guard["skipped"], guard["consecutive"]) if guard is not None else None
+            if guard is not None:
+                self.set_skip_grad_norm(guard["limit"])
         if ema is not None:
             self.ema_decay, self.ema_warmup = decay, bool(ema["warmup"])
             for t in self._ema_hyper.values():

@@ -25,7 +25,12 @@ schedule is the CyclicLR stepped at evaluations described above.  --label-smooth
 (inside the loss-head kernels, both paths); evaluation lines keep the plain cross entropy.  --ema-decay [--ema-warmup] keeps an
 exponential moving average of the weights inside the AdamW launch (both paths): every evaluation line gains val_loss_ema (the
 averaged weights on val_loss's own batches), the final sample is drawn from the average and it is saved as <name>.ema.pt beside
-the raw checkpoint.
+the raw checkpoint.  --skip-nonfinite / --skip-grad-norm X turn the update guard on (both paths): a step whose global gradient
+norm is not finite (or above X), or -- engine path -- whose loss is not finite, skips its optimizer update on the GPU and the run
+goes on with the next batch; evaluation lines gain "skipped", and a run that has skipped more than --max-consecutive-skips updates
+in a row ends with a RuntimeError (checked where the harness synchronises anyway: at evaluation lines and before a save).  The
+staged per-step LR table follows applied updates (a skipped step does not use up an entry); the `reference` schedule and the
+autograd path's per-iteration rates keep counting iterations.
 """
 from __future__ import annotations
 
@@ -44,7 +49,7 @@ from . import dist as ddist
 from . import schedules
 from .config import DRAKE_VOCAB_SIZE, PARAMS, PRESETS, SCALE_PARAMS, TRAIN
 from .model import MODEL_CLASSES, model_params
-from .ops import check_ema_options, check_loss_options
+from .ops import check_ema_options, check_guard_options, check_loss_options
 from .optim import check_accum_steps
 from .preprocessing import draw_offsets, encode_text, get_mapper, load_train_val_data, split_train_val
 
@@ -243,6 +248,15 @@ def build_parser() -> argparse.ArgumentParser:
                     "in (0, 1) (default: off).  Evaluation lines gain val_loss_ema, the final sample is drawn from the average and "
                     "it is saved as <name>.ema.pt beside the checkpoint")
     ap.add_argument("--ema-warmup", action="store_true", help="with --ema-decay: step s averages with min(D, (s + 1) / (s + 10))")
+    ap.add_argument("--skip-nonfinite", action="store_true",
+                    help="the update guard: skip the optimizer update of a step whose gradient norm (engine path: or loss) is not "
+                    "finite, on the GPU, and go on with the next batch (default: off).  Evaluation lines gain skipped")
+    ap.add_argument("--skip-grad-norm", type=float, default=None, metavar="X",
+                    help="the update guard with a limit: also skip a step whose global gradient norm exceeds X (implies "
+                    "--skip-nonfinite; default: off)")
+    ap.add_argument("--max-consecutive-skips", type=int, default=25, metavar="N",
+                    help="with the update guard: end the run (RuntimeError) once more than N updates in a row were skipped, checked at "
+                    "evaluation lines and before a save (default 25)")
     ap.add_argument("--save-every", type=int, default=None, metavar="N",
                     help="write the full training state (weights, optimizer, counters, generator: everything --resume needs) after "
                     "the evaluation of every N-th iteration and after the last one; N must be a multiple of --eval-interval "
@@ -276,6 +290,12 @@ def parse_args(argv=None):
         args.ema_decay = check_ema_options(args.ema_decay, args.ema_warmup)
     except ValueError as e:
         ap.error(f"--ema-decay / --ema-warmup: {e}")
+    try:
+        args.skip_nonfinite = check_guard_options(bool(args.skip_nonfinite), args.skip_grad_norm)[0]
+    except ValueError as e:
+        ap.error(f"--skip-nonfinite / --skip-grad-norm: {e}")
+    if args.max_consecutive_skips < 0:
+        ap.error(f"--max-consecutive-skips {args.max_consecutive_skips} must be >= 0")
     if args.save_every is not None and (args.save_every < 1 or args.save_every % args.eval_interval):
         ap.error(f"--save-every {args.save_every} must be a positive multiple of --eval-interval {args.eval_interval} (offsets are "
                  "staged per evaluation interval: the state is written between two stages)")
@@ -395,6 +415,8 @@ def main(argv=None):
 
     table = lr_values(args, base_lr, max_lr)          # one rate per optimizer step, or None: the reference's CyclicLR at evaluations
 
+    # the update guard's two options: nothing for a run without the flags, whose constructors get the arguments they always got
+    guard_kw = {"skip_nonfinite": True, "skip_grad_norm": args.skip_grad_norm} if args.skip_nonfinite else {}
     engine = None
     if args.model == "TransformerLM":
         from .engine import TrainEngine
@@ -402,6 +424,7 @@ def main(argv=None):
                              max_grad_norm=args.grad_clip, accum_steps=K, lr_schedule=table, no_decay=args.no_decay,
                              label_smoothing=args.label_smoothing, z_loss=args.z_loss,
                              **({} if args.ignore_token is None else {"ignore_index": args.ignore_token}),
+                             **guard_kw,
                              **({} if args.ema_decay is None else {"ema_decay": args.ema_decay, "ema_warmup": args.ema_warmup}))
         engine.set_corpus(train_dev)
     else:
@@ -413,7 +436,7 @@ def main(argv=None):
         if args.no_decay:
             groups = no_decay_groups(model, args.no_decay)
         optimizer = AdamW(groups, lr=base_lr, betas=params["betas"], process_group=pg, world_size=world,
-                          max_grad_norm=args.grad_clip,
+                          max_grad_norm=args.grad_clip, **guard_kw,
                           **({} if args.ema_decay is None else {"ema_decay": args.ema_decay, "ema_warmup": args.ema_warmup}))
         if table is not None:
             table = schedules.as_table(table).tolist()          # the fp32 values the engine's table would hold
@@ -440,7 +463,17 @@ def main(argv=None):
         if rank == 0:
             print(f"resumed {args.resume} at iteration {start}")
 
+    def check_skips(it):
+        """the guard's run of skipped updates, read where the host has synchronised anyway: a gradient that never recovers ends the
+        run instead of idling through the remaining iterations"""
+        n = (engine if engine is not None else optimizer).consecutive_skips()
+        if n > args.max_consecutive_skips:
+            raise RuntimeError(f"the update guard skipped {n} optimizer updates in a row up to iteration {it} (--max-consecutive-skips "
+                               f"{args.max_consecutive_skips}): the gradient does not recover")
+
     def save_state(next_it):
+        if args.skip_nonfinite:
+            check_skips(next_it)
         save_run_state(args.state_path, next_iteration=next_it, sched_steps=sched["steps"], must_match=must_match, model=model,
                        engine=engine, optimizer=None if engine is not None else optimizer, rank=rank, world=world)
 
@@ -464,6 +497,8 @@ def main(argv=None):
             with averaged():
                 losses["val_ema"] = evaluate_loss(train_dev, val_dev, model, args.eval_iters, T, B, device, engine=engine,
                                                   offsets={"val": drawn["val"]})["val"]
+        if args.skip_nonfinite:
+            check_skips(it + 1)
         sched["steps"] += 1
         if table is not None:
             # a per-step schedule: nothing to set here; report the rate of the next step
@@ -484,6 +519,8 @@ def main(argv=None):
             if args.grad_clip is not None:
                 # the last step's pre-clip norm: the evaluation has synchronised the stream already
                 line["grad_norm"] = float((engine if engine is not None else optimizer).last_grad_norm)
+            if args.skip_nonfinite:
+                line["skipped"] = (engine if engine is not None else optimizer).skipped_steps()
             print(json.dumps(line), flush=True)
         model.train()
         if args.save_every and (it + 1) % args.save_every == 0:

@@ -552,6 +552,33 @@ int dg_adamw_step_ema(float* p, const float* g, float* m, float* v, int64_t n, c
 int dg_swap_f32(float* a, float* b, int64_t n, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Update guard -- ref: torch.amp.GradScaler's found_inf skip of optimizer.step(), and "skip the batch on a gradient spike":
+ * the decision whether a step's update is applied is taken on the device, and a skipped update costs a launch.
+ *   guard (4 device uint32) = {apply, total skipped, consecutive skipped, spare}
+ * dg_grad_norm_finalize_guard: dg_grad_norm_finalize (the same workgroup, the same fixed-order fp64 sum, the same out[0] bits, and
+ *   with max_norm != NULL the same out[1] bits; max_norm == NULL: out[1] is not written), which also writes
+ *     guard[0] = apply = total_norm <= limit[0] && (loss == NULL || isfinite(loss[0]))
+ *     guard[1] += !apply;   guard[2] = apply ? 0 : guard[2] + 1
+ *   limit is a device fp32 scalar: FLT_MAX guards non-finite gradients alone (a NaN or Inf norm fails the comparison; +inf would
+ *   let an Inf norm through).  dg_sumsq_partials squares in fp32, so a finite element beyond 1.8e19 in magnitude reads as
+ *   non-finite as well.  DG_ERR_ARG: NULL part / out / limit / guard, n_parts <= 0.
+ * dg_adamw_step_guard: dg_adamw_step_ema's arguments with ema (and ema_hyper, together), lr_table, no_decay_bits and clip_coef
+ *   each NULL or not, plus guard and data_state (4 device uint32, may be NULL; not rng_state itself).
+ *     guard[0] != 0: p, m, v, shadow, ema and rng_state[2] get the bits the unguarded entry with the same operands gives.
+ *     guard[0] == 0: none of p / g / m / v / ema / shadow is read or written, and rng_state[2] stays: bias correction, the
+ *       lr_table index and the EMA warm-up stand still.
+ *   With advance_step != 0 and data_state != NULL the launch writes data_state[2] + 1 in either case: the word that keys
+ *   dropout, the staged offset row and the fp8 amax slot moves on over a skipped update.  Every workgroup reads guard[0] once and
+ *   registers at rng_state[3] (zero before and after every launch); the last one to arrive writes the words; nobody waits.
+ *   DG_ERR_ARG: what dg_adamw_step_sched refuses, a NULL guard, one of ema / ema_hyper alone, data_state == rng_state. */
+int dg_grad_norm_finalize_guard(const double* part, int n_parts, float grad_scale, const float* max_norm, float* out,
+                                const float* limit, const float* loss, uint32_t* guard, void* stream);
+int dg_adamw_step_guard(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, uint32_t* rng_state,
+                        float grad_scale, const float* clip_coef, const float* lr_table, int64_t lr_table_len,
+                        const uint32_t* no_decay_bits, void* shadow_bf16, int advance_step, float* ema, const float* ema_hyper,
+                        const uint32_t* guard, uint32_t* data_state, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Gradient accumulation -- ref: k x `(loss / k).backward()` summing into p.grad between two optimizer.step() calls.  One
  * streaming pass per micro-step over the flat fp32 gradient g[0, n) of that micro-batch:
  *   ctl (4 device uint32) = {j, k, arrival counter, 0}: j = micro-step inside the current optimizer step, k = accum_steps >= 1
