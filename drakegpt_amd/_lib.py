@@ -105,6 +105,10 @@ class TnProblem(C.Structure):
 
 _vp, _i, _i64, _f, _u32 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint32
 
+# the five AdamW entries: p, g, m, v, n, hyper, rng_state, grad_scale, then each entry's own tail (ops.adamw_step builds its call the same way)
+_ADAMW = [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _f]
+_ADAMW_SCHED = [_vp, _vp, _i64, _vp, _vp, _i]         # clip_coef, lr_table, lr_table_len, no_decay_bits, shadow_bf16, advance_step
+
 # name -> argtypes; every entry of include/drakegpt_hip.h (tests/test_abi.py checks the two agree)
 SIGNATURES = {
     "dg_version": [],
@@ -162,16 +166,16 @@ SIGNATURES = {
     "dg_reduce_sum": [_vp, _i64, _f, _vp, _vp],
     "dg_reduce_sum_scaled": [_vp, _i64, _f, _vp, _vp, _vp],
     "dg_softmax_rows": [_vp, _i64, _vp, _i64, _i, _i, _vp],
-    "dg_adamw_step": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _f, _vp, _i, _vp],
+    "dg_adamw_step": _ADAMW + [_vp, _i, _vp],
     "dg_sumsq_parts": [_i64],
     "dg_sumsq_partials": [_vp, _i64, _vp, _vp],
     "dg_grad_norm_finalize": [_vp, _i, _f, _vp, _vp, _vp],
-    "dg_adamw_step_clip": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _f, _vp, _vp, _i, _vp],
-    "dg_adamw_step_sched": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _f, _vp, _vp, _i64, _vp, _vp, _i, _vp],
-    "dg_adamw_step_ema": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _f, _vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp],
+    "dg_adamw_step_clip": _ADAMW + [_vp, _vp, _i, _vp],
+    "dg_adamw_step_sched": _ADAMW + _ADAMW_SCHED + [_vp],
+    "dg_adamw_step_ema": _ADAMW + _ADAMW_SCHED + [_vp, _vp, _vp],
     "dg_swap_f32": [_vp, _vp, _i64, _vp],
     "dg_grad_norm_finalize_guard": [_vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp],
-    "dg_adamw_step_guard": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _f, _vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp],
+    "dg_adamw_step_guard": _ADAMW + _ADAMW_SCHED + [_vp, _vp, _vp, _vp, _vp],
     "dg_grad_accumulate": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
     "dg_block_chain_supported": [_i, _i],
     "dg_block_chain_fwd": [C.POINTER(BlockChainArgs), _vp],

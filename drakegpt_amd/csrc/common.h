@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/drakegpt_hip.h"
 
 typedef __bf16 bf16_t;
@@ -22,6 +23,20 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     } while (0)
 
 static inline bool dg_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+
+// ---------------------------------------------------------------------------------------------
+// Optional kernel arguments: a kernel template that ends in a parameter pack `O... o` of distinct plain structs takes each option as
+// one more kernel argument; an instantiation without the option has neither the argument nor a trace of it in its symbol.
+// dg_pack_has<T, O...>::value says whether the pack holds a T; dg_pack_get(fallback, o...) is the pack's member of type T, or the
+// fallback (AdamW in elementwise.hip, the loss head in cross_entropy.hip).
+template <typename T, typename... O> struct dg_pack_has { static constexpr bool value = false; };
+template <typename T, typename U, typename... O> struct dg_pack_has<T, U, O...> { static constexpr bool value = dg_pack_has<T, O...>::value; };
+template <typename T, typename... O> struct dg_pack_has<T, T, O...> { static constexpr bool value = true; };
+template <typename T> __host__ __device__ __forceinline__ T dg_pack_get(T fallback) { return fallback; }
+template <typename T, typename U, typename... O> __host__ __device__ __forceinline__ T dg_pack_get(T fallback, U first, O... rest) {
+    if constexpr (std::is_same_v<T, U>) return first;
+    else return dg_pack_get(fallback, rest...);
+}
 
 // ---------------------------------------------------------------------------------------------
 // dropout stream: stateless hash of (seed, step, site, element index).  oracle/rng_ref.py

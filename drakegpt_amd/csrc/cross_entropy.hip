@@ -24,24 +24,13 @@ struct CeOpt { float eps, zeta; };
 // only the device knows (dg_ce_count_valid writes it); the mean of loss_rows takes the same factor (dg_reduce_sum_scaled, or the
 // fused kernel's last workgroup).  N = 0: inv_count is +inf, nothing is multiplied by it, every gradient row is zeros.
 struct CeIgn { int64_t ignore_index; const float* inv_count; };
-template <typename T, typename... O> struct ce_has { static constexpr bool value = false; };
-template <typename T, typename U, typename... O> struct ce_has<T, U, O...> { static constexpr bool value = ce_has<T, O...>::value; };
-template <typename T, typename... O> struct ce_has<T, T, O...> { static constexpr bool value = true; };
-__device__ __forceinline__ CeOpt ce_opt() { return CeOpt{0.f, 0.f}; }
-__device__ __forceinline__ CeOpt ce_opt(CeOpt opt) { return opt; }
-__device__ __forceinline__ CeOpt ce_opt(CeIgn) { return CeOpt{0.f, 0.f}; }
-__device__ __forceinline__ CeOpt ce_opt(CeOpt opt, CeIgn) { return opt; }
-__device__ __forceinline__ CeIgn ce_ign() { return CeIgn{0, nullptr}; }
-__device__ __forceinline__ CeIgn ce_ign(CeOpt) { return CeIgn{0, nullptr}; }
-__device__ __forceinline__ CeIgn ce_ign(CeIgn ign) { return ign; }
-__device__ __forceinline__ CeIgn ce_ign(CeOpt, CeIgn ign) { return ign; }
-
-// The pack resolved: every kernel opens with `const CePack<O...> p{ce_opt(o...), ce_ign(o...)}` and hands p.OPT, p.IGN, p.opt and p.ign to
-// the row math below, which takes and returns values.
+// The pack resolved (dg_pack_has / dg_pack_get of common.h): every kernel opens with `const CePack<O...> p(o...)` and hands p.OPT, p.IGN,
+// p.opt and p.ign to the row math below, which takes and returns values.  An absent CeOpt reads as both options zero.
 template <typename... O> struct CePack {
-    static constexpr bool OPT = ce_has<CeOpt, O...>::value, IGN = ce_has<CeIgn, O...>::value;
+    static constexpr bool OPT = dg_pack_has<CeOpt, O...>::value, IGN = dg_pack_has<CeIgn, O...>::value;
     CeOpt opt;
     CeIgn ign;
+    __device__ __forceinline__ explicit CePack(O... o) : opt(dg_pack_get(CeOpt{0.f, 0.f}, o...)), ign(dg_pack_get(CeIgn{0, nullptr}, o...)) {}
 };
 // The row loss from mx, logs = log s, xt = x_t and sd = sum_{i < V} (mx - x_i) (read under OPT only).  The plain instantiations keep
 // mx + log s - x_t, the code they always had.  The ignore forms without a CeOpt write log s + (mx - x_t), the order the options use
@@ -87,7 +76,7 @@ template <typename TD, typename TL = float, typename... O>
 __global__ void cross_entropy_kernel(const TL* __restrict__ logits, int64_t ldl, const int64_t* __restrict__ targets,
                                      float* __restrict__ loss_rows, TD* __restrict__ dlogits, int64_t ldd,
                                      float grad_scale, const float* __restrict__ gs_dev, int M, int V, O... o) {
-    const CePack<O...> p{ce_opt(o...), ce_ign(o...)};
+    const CePack<O...> p(o...);
     constexpr bool OPT = p.OPT, IGN = p.IGN;
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -130,7 +119,7 @@ template <typename TD, typename... O>
 __global__ __launch_bounds__(256) void cross_entropy_small_kernel(const float* __restrict__ logits, int64_t ldl, const int64_t* __restrict__ targets,
                                                                   float* __restrict__ loss_rows, TD* __restrict__ dlogits, int64_t ldd,
                                                                   float grad_scale, const float* __restrict__ gs_dev, int M, int V, O... o) {
-    const CePack<O...> p{ce_opt(o...), ce_ign(o...)};
+    const CePack<O...> p(o...);
     constexpr bool OPT = p.OPT, IGN = p.IGN;
     const int sub = threadIdx.x & 15;
     const int row = blockIdx.x * 16 + (threadIdx.x >> 4);
@@ -201,7 +190,7 @@ template <typename TD, typename... O>
 __global__ __launch_bounds__(CEF_THREADS) void cross_entropy_small_fused_kernel(const float* __restrict__ logits, int64_t ldl, const int64_t* __restrict__ targets,
                                                                         float* __restrict__ loss_rows, TD* __restrict__ dlogits, int64_t ldd,
                                                                         float grad_scale, int M, int V, CeFuse fz, O... o) {
-    const CePack<O...> p{ce_opt(o...), ce_ign(o...)};
+    const CePack<O...> p(o...);
     constexpr bool OPT = p.OPT, IGN = p.IGN;
     __shared__ float red[CEF_RG][128];
     __shared__ float lred[CEF_RG];
@@ -339,7 +328,7 @@ template <typename TD, typename TL = float, typename... O>
 __global__ __launch_bounds__(CE_BLOCK) void cross_entropy_row_kernel(const TL* logits, int64_t ldl, const int64_t* __restrict__ targets,
                                                                       float* __restrict__ loss_rows, TD* dlogits, int64_t ldd,   // (may alias)
                                                                       float grad_scale, const float* __restrict__ gs_dev, int M, int V, O... o) {
-    const CePack<O...> p{ce_opt(o...), ce_ign(o...)};
+    const CePack<O...> p(o...);
     constexpr bool OPT = p.OPT, IGN = p.IGN;
     __shared__ float red[16];
     __shared__ float red2[OPT ? 16 : 1];
@@ -414,7 +403,7 @@ __global__ __launch_bounds__(CE_BLOCK, 8) void cross_entropy_row_bf16_kernel(con
                                                                               float* __restrict__ loss_rows, bf16_t* dlogits, int64_t ldd,
                                                                               float grad_scale, const float* __restrict__ gs_dev, int M, int V,
                                                                               unsigned char* __restrict__ q8, int64_t ldq8, float q8_scale, O... o) {
-    const CePack<O...> p{ce_opt(o...), ce_ign(o...)};
+    const CePack<O...> p(o...);
     constexpr bool OPT = p.OPT, IGN = p.IGN;
     __shared__ float red[16];
     __shared__ float red2[OPT ? 16 : 1];

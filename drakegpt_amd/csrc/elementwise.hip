@@ -894,32 +894,51 @@ extern "C" int dg_softmax_rows(const float* logits, int64_t ldl, float* probs, i
 }
 
 // ---------------------------------------------------------------------------------------------
-// AdamW over a flat buffer (ref: src/train.py:121,151).  16 B/lane streams: reads p,g,m,v and
-// writes p,m,v = 28 B/param (+2 B for the bf16 shadow).
-// advance: the step word moves on inside this launch -- every workgroup reads it first thing and registers at an arrival
-// counter (word 3 of the state) when it is done; the last one to arrive writes step + 1 and clears the counter.  (A separate
-// one-thread launch for that cost 4 us of the step.)
-// CLIP: the gradient clipping coefficient (dg_grad_norm_finalize) is read from device memory and multiplied into grad_scale once per
-// workgroup; CLIP = false is the unclipped kernel unchanged, and a coefficient of exactly 1 gives the same bits (grad_scale * 1.0f).
-// TABLE: lr comes from lr_table[min(step word, lr_table_len - 1)] (a schedule staged in HBM once) instead of hyper[0]; the word is
-// read once per workgroup, where the step word is read.  MASK: no_decay_bits holds one bit per 64-float granule (bit G & 31 of word
-// G >> 5 covers elements [64 G, 64 G + 64)); a set bit makes decay 1.0f for that granule, and p * 1.0f is exact, so those elements
-// get the bits of weight_decay = 0.  A lane's four floats never cross a granule and a wave's 256 floats lie in one bitmap word, so
-// the vector body reads one cached word per wave iteration.  With both false this is the kernel as it was.
-// The existing entries instantiate <CLIP, false, false> with an empty pack: the kernel and its kernel arguments as they were.
+// AdamW over a flat buffer (ref: src/train.py:121,151).  16 B/lane streams: reads p,g,m,v and writes p,m,v = 28 B/param (+2 B for
+// the bf16 shadow, +8 B for the moving average).  One kernel template; every option is compile-time, and an instantiation without an
+// option carries neither its code nor its kernel argument.  <CLIP, TABLE, MASK> are template flags; the schedule's operands, the
+// average and the guard travel in the trailing pack S (dg_pack_get of common.h), which is one of
+//     nothing | AdamwSched | AdamwSched, AdamwEma | AdamwSched, AdamwEma, AdamwGuard<EMA>
+// (adamw_dispatch below is the one place that chooses).  What every workgroup reads once, first thing: hyper, the step word
+// rng_state[2], and with CLIP the coefficient, with TABLE the table entry, with an average {decay, warmup}, with a guard guard[0].
+//   advance  the step word moves on inside this launch: a workgroup that is done registers at an arrival counter (word 3 of the
+//            state); the last one to arrive writes step + 1 and clears the counter.  The same fetch-add for all, nobody waits.
+//   CLIP     grad_scale is multiplied by clip_coef[0] (dg_grad_norm_finalize's, in device memory).  A coefficient of exactly 1 gives
+//            the bits of CLIP = false (grad_scale * 1.0f).
+//   TABLE    lr = lr_table[min(step word, lr_table_len - 1)] (a schedule staged in HBM once) instead of hyper[0].
+//   MASK     no_decay_bits holds one bit per 64-float granule (bit G & 31 of word G >> 5 covers elements [64 G, 64 G + 64)); a set bit
+//            makes decay 1.0f for that granule, and p * 1.0f is exact: the bits of weight_decay = 0.  A lane's four floats never cross
+//            a granule and a wave's 256 floats lie in one bitmap word, so the vector loop reads one cached word per wave trip.
+//   EMA      one more 16 B/lane stream: ema = ema + (p_new - ema) * (1 - d_s) on the weight this thread has just stored; at step word
+//            0 ema = p_new and the buffer is not read.  d_s and 1 - d_s are computed once per workgroup from {decay, warmup} in device
+//            memory (a captured graph picks up a new decay).  The three operations are rounded one by one (adamw_ema_lerp:
+//            contraction is off inside it), so three fp32 operations on the host give the same bits.
+//   GUARD    the update guard of dg_grad_norm_finalize_guard.  guard[0] == 0: the update is skipped -- neither loop runs (no load or
+//            store of p / g / m / v / ema / shadow: a skipped step costs a launch, not a pass over HBM).  The last workgroup to arrive
+//            moves data_state[2] on (if given: the word that keys dropout, the staged offset row and the fp8 amax slot) in either
+//            case, and the optimizer's own step word only when the update was applied: bias correction, the table index and the
+//            average's warm-up stand still over a skipped step.  guard[0] == 1: the bits of the launch without a guard.  Whether
+//            there is an average is a template flag of the guard (ema may be NULL at that entry).
 struct AdamwSched { const float* lr_table; int64_t lr_table_len; const uint32_t* no_decay_bits; };
-template <typename... S>
-__device__ __forceinline__ AdamwSched adamw_sched_of(S... s) {
-    if constexpr (sizeof...(S) != 0) return (s, ...);
-    else return AdamwSched{nullptr, 0, nullptr};
-}
-
-// EMA (S = AdamwSched, AdamwEma): one more 16 B/lane stream, ema = ema + (p_new - ema) * (1 - d_s) on the weight this thread has
-// just stored (step word 0: ema = p_new, the buffer is not read).  {decay, warmup} come from device memory (a captured graph picks
-// up a new decay); d_s and 1 - d_s are computed once per workgroup, where the step word is read.  The three operations are rounded
-// one by one (adamw_ema_lerp: contraction is off inside it, so the multiply and the add never become an FMA), so three fp32
-// operations on the host give the same bits.  Without it the kernel, its instantiations and its kernel arguments are the ones they were.
 struct AdamwEma { float* ema; const float* ema_hyper; };
+template <bool EMA_> struct AdamwGuard { const uint32_t* guard; uint32_t* data_state; };
+template <typename... S> struct AdamwPack { static constexpr bool guard = false, ema = sizeof...(S) == 2; };
+template <bool EMA_> struct AdamwPack<AdamwSched, AdamwEma, AdamwGuard<EMA_>> { static constexpr bool guard = true, ema = EMA_; };
+
+// what one launch applies to every element
+struct AdamwCoef { float grad_scale, b1, b2, eps, step_size, inv_sqrt_bc2; };
+struct AdamwElem { float p, m, v; };
+// The update of one element, from values to values.  The gradient comes first on purpose: callers pass g[i], p[i], m[i], v[i], loads in
+// the order of this list, and with p ahead of g the scalar loop fuses the other product of v * b2 + (1 - b2) * g * g into its FMA.
+__device__ __forceinline__ AdamwElem adamw_elem(float g, float p, float m, float v, float dec, const AdamwCoef& c) {
+    const float gj = g * c.grad_scale;
+    float pj = p * dec;
+    const float mj = m + (gj - m) * (1.f - c.b1);              // lerp, as torch does
+    const float vj = v * c.b2 + (1.f - c.b2) * gj * gj;
+    const float denom = sqrtf(vj) * c.inv_sqrt_bc2 + c.eps;
+    pj -= c.step_size * (mj / denom);
+    return AdamwElem{pj, mj, vj};
+}
 __device__ __forceinline__ float adamw_ema_lerp(float e, float p, float w) {
 #pragma clang fp contract(off)
     const float d = p - e;
@@ -932,33 +951,40 @@ __device__ __forceinline__ float adamw_ema_weight(const float* __restrict__ ema_
     if (ema_hyper[1] != 0.f) d = fminf(d, ((float)step + 1.f) / ((float)step + 10.f));      // (correctly rounded: hipcc's default)
     return 1.f - d;
 }
-__device__ __forceinline__ AdamwSched adamw_sched_of(AdamwSched sc, AdamwEma) { return sc; }
-__device__ __forceinline__ AdamwEma adamw_ema_of(AdamwSched, AdamwEma ea) { return ea; }
-template <typename... S>
-__device__ __forceinline__ AdamwEma adamw_ema_of(S...) { return AdamwEma{nullptr, nullptr}; }
+// The decay factor of the W floats at element i * W: 1.0f where the granule's bit is set (granule = element >> 6, 32 granules per word)
+template <int W>
+__device__ __forceinline__ float adamw_decay_at(const uint32_t* __restrict__ no_decay_bits, int64_t i, float decay) {
+    constexpr int LOG = W == 4 ? 2 : 0;
+    return ((no_decay_bits[i >> (11 - LOG)] >> ((unsigned)(i >> (6 - LOG)) & 31u)) & 1u) ? 1.f : decay;
+}
+// The average over the W new weights at element i * W: a lane's f32x4 (W = 4) or one float of the tail (W = 1).  Step word 0: the
+// average starts at p_new and its buffer is not read.
+template <int W> using adamw_f32 = float __attribute__((ext_vector_type(W)));
+template <int W>
+__device__ __forceinline__ void adamw_ema_update(float* __restrict__ ema, int64_t i, adamw_f32<W> p_new, uint32_t step_now, float ema_w) {
+    adamw_f32<W> ee = p_new;
+    if (step_now != 0u) {
+        ee = ((adamw_f32<W>*)ema)[i];
+#pragma unroll
+        for (int j = 0; j < W; ++j) ee[j] = adamw_ema_lerp(ee[j], p_new[j], ema_w);
+    }
+    ((adamw_f32<W>*)ema)[i] = ee;
+}
+// The bf16 copy of the same W weights: one store (W = 4: 8 bytes, where the shadow is 8-byte aligned as p is), else one per element
+template <int W>
+__device__ __forceinline__ void adamw_shadow_store(bf16_t* __restrict__ shadow, int64_t i, adamw_f32<W> p_new, bool shadow_vec) {
+    typedef bf16_t bf16xw __attribute__((ext_vector_type(W)));
+    bf16xw sh;
+#pragma unroll
+    for (int j = 0; j < W; ++j) sh[j] = (bf16_t)p_new[j];
+    if (W == 1 || shadow_vec) *(bf16xw*)(shadow + i * W) = sh;
+    else {
+#pragma unroll
+        for (int j = 0; j < W; ++j) shadow[i * W + j] = sh[j];
+    }
+}
 
-// GUARD (S = AdamwSched, AdamwEma, AdamwGuard<EMA>): the update guard of dg_grad_norm_finalize_guard.  Every workgroup reads
-// guard[0] once, where it reads the step word.  0: the update is skipped -- neither streaming loop runs (no load or store of p / g /
-// m / v / ema / shadow: a skipped step costs a launch, not a pass over HBM) and the workgroup goes straight to the arrival counter.
-// The last workgroup to arrive clears the counter, moves data_state[2] (if given: the word that keys dropout, the staged offset row
-// and the fp8 amax slot) on in either case, and the optimizer's own step word only when the update was applied: bias correction,
-// the LR-table index and the EMA warm-up stand still over a skipped step.  Nobody waits for anybody: the same fetch-add, no spin.
-// 1: the body below as it is, so the bits of the unguarded launch.  EMA is a compile-time member here (ema may be NULL at the
-// entry); without the third pack member the kernel, its instantiations and its kernel arguments are the ones they were.
-template <bool EMA_>
-struct AdamwGuard { const uint32_t* guard; uint32_t* data_state; };
-template <typename... S> struct AdamwPack { static constexpr bool guard = false, ema = sizeof...(S) == 2; };
-template <bool EMA_> struct AdamwPack<AdamwSched, AdamwEma, AdamwGuard<EMA_>> { static constexpr bool guard = true, ema = EMA_; };
-template <bool EMA_>
-__device__ __forceinline__ AdamwSched adamw_sched_of(AdamwSched sc, AdamwEma, AdamwGuard<EMA_>) { return sc; }
-template <bool EMA_>
-__device__ __forceinline__ AdamwEma adamw_ema_of(AdamwSched, AdamwEma ea, AdamwGuard<EMA_>) { return ea; }
-template <bool EMA_>
-__device__ __forceinline__ AdamwGuard<EMA_> adamw_guard_of(AdamwSched, AdamwEma, AdamwGuard<EMA_> gd) { return gd; }
-template <typename... S>
-__device__ __forceinline__ AdamwGuard<false> adamw_guard_of(S...) { return AdamwGuard<false>{nullptr, nullptr}; }
-
-template <bool CLIP, bool TABLE, bool MASK, typename... S>   // S: nothing; one AdamwSched when TABLE or MASK; AdamwSched, AdamwEma; + AdamwGuard
+template <bool CLIP, bool TABLE, bool MASK, typename... S>
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                              float* __restrict__ v, int64_t n, const float* __restrict__ hyper,
                              uint32_t* rng_state, float grad_scale,
@@ -966,9 +992,9 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
     constexpr bool EMA = AdamwPack<S...>::ema;
     constexpr bool GUARD = AdamwPack<S...>::guard;
     static_assert(EMA || GUARD || sizeof...(S) == ((TABLE || MASK) ? 1 : 0), "the schedule arguments go with TABLE or MASK");
-    const AdamwSched sc = adamw_sched_of(sched...);
-    const AdamwEma ea = adamw_ema_of(sched...);
-    const auto gd = adamw_guard_of(sched...);
+    const AdamwSched sc = dg_pack_get(AdamwSched{nullptr, 0, nullptr}, sched...);
+    const AdamwEma ea = dg_pack_get(AdamwEma{nullptr, nullptr}, sched...);
+    const auto gd = dg_pack_get(AdamwGuard<EMA>{nullptr, nullptr}, sched...);
     const float* __restrict__ lr_table = sc.lr_table;
     const uint32_t* __restrict__ no_decay_bits = sc.no_decay_bits;
     if (CLIP) grad_scale *= clip_coef[0];
@@ -978,8 +1004,7 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
     const float t = (float)(step_now + 1u);
     const float bc1 = 1.f - powf(b1, t);
     const float bc2 = 1.f - powf(b2, t);
-    const float step_size = lr / bc1;
-    const float inv_sqrt_bc2 = 1.f / sqrtf(bc2);
+    const AdamwCoef co{grad_scale, b1, b2, eps, lr / bc1, 1.f / sqrtf(bc2)};
     const float decay = 1.f - lr * wd;
     const bool shadow_vec = (((uintptr_t)shadow) & 7) == 0;
     float* __restrict__ ema = ea.ema;
@@ -994,62 +1019,22 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
     int64_t n4 = n / 4;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gs) {
         f32x4 pp = ((f32x4*)p)[i], gg = ((const f32x4*)g)[i], mm = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
-        float dec = decay;
-        if (MASK) {                                              // granule = i >> 4 (16 lanes of four floats)
-            if ((no_decay_bits[i >> 9] >> ((unsigned)(i >> 4) & 31u)) & 1u) dec = 1.f;
-        }
+        const float dec = MASK ? adamw_decay_at<4>(no_decay_bits, i, decay) : decay;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            float gj = gg[j] * grad_scale;
-            float pj = pp[j] * dec;
-            float mj = mm[j] + (gj - mm[j]) * (1.f - b1);          // lerp, as torch does
-            float vj = vv[j] * b2 + (1.f - b2) * gj * gj;
-            float denom = sqrtf(vj) * inv_sqrt_bc2 + eps;
-            pj -= step_size * (mj / denom);
-            pp[j] = pj; mm[j] = mj; vv[j] = vj;
+            const AdamwElem e = adamw_elem(gg[j], pp[j], mm[j], vv[j], dec, co);
+            pp[j] = e.p; mm[j] = e.m; vv[j] = e.v;
         }
         ((f32x4*)p)[i] = pp; ((f32x4*)m)[i] = mm; ((f32x4*)v)[i] = vv;
-        if (EMA) {
-            f32x4 ee = pp;
-            if (step_now != 0u) {
-                ee = ((f32x4*)ema)[i];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) ee[j] = adamw_ema_lerp(ee[j], pp[j], ema_w);
-            }
-            ((f32x4*)ema)[i] = ee;
-        }
-        if (shadow) {                                            // one 8-byte store (shadow + 4 i is 8-byte aligned with p)
-            bf16x4 sh;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) sh[j] = (bf16_t)pp[j];
-            if (shadow_vec) *(bf16x4*)(shadow + i * 4) = sh;
-            else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) shadow[i * 4 + j] = sh[j];
-            }
-        }
+        if (EMA) adamw_ema_update<4>(ema, i, pp, step_now, ema_w);
+        if (shadow) adamw_shadow_store<4>(shadow, i, pp, shadow_vec);
     }
     for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gs) {
-        float dec = decay;
-        if (MASK) {
-            if ((no_decay_bits[i >> 11] >> ((unsigned)(i >> 6) & 31u)) & 1u) dec = 1.f;
-        }
-        float gj = g[i] * grad_scale;
-        float pj = p[i] * dec;
-        float mj = m[i] + (gj - m[i]) * (1.f - b1);
-        float vj = v[i] * b2 + (1.f - b2) * gj * gj;
-        float denom = sqrtf(vj) * inv_sqrt_bc2 + eps;
-        pj -= step_size * (mj / denom);
-        p[i] = pj; m[i] = mj; v[i] = vj;
-        if (shadow) shadow[i] = (bf16_t)pj;
-        if (EMA) {
-            float ej = pj;
-            if (step_now != 0u) {
-                ej = ema[i];
-                ej = adamw_ema_lerp(ej, pj, ema_w);
-            }
-            ema[i] = ej;
-        }
+        const float dec = MASK ? adamw_decay_at<1>(no_decay_bits, i, decay) : decay;
+        const AdamwElem e = adamw_elem(g[i], p[i], m[i], v[i], dec, co);
+        p[i] = e.p; m[i] = e.m; v[i] = e.v;
+        if (shadow) adamw_shadow_store<1>(shadow, i, e.p, shadow_vec);
+        if (EMA) adamw_ema_update<1>(ema, i, e.p, step_now, ema_w);
     }
     if (advance) {
         __syncthreads();                                   // (every wave of this workgroup has read the step word long ago)
@@ -1060,10 +1045,8 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                 if constexpr (GUARD) {
                     if (gd.data_state)
                         __hip_atomic_store(gd.data_state + 2, gd.data_state[2] + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (applied) __hip_atomic_store(rng_state + 2, step_now + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                } else {
-                    __hip_atomic_store(rng_state + 2, step_now + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
+                if (applied) __hip_atomic_store(rng_state + 2, step_now + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
     }
@@ -1076,115 +1059,87 @@ static unsigned adamw_grid(int64_t n) {
     return grid;
 }
 
-static int adamw_launch(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, uint32_t* rng_state,
-                        float grad_scale, const float* clip_coef, void* shadow_bf16, int advance_step, void* stream) {
-    if (!p || !g || !m || !v || !hyper || !rng_state || n <= 0) return DG_ERR_ARG;
-    if (!dg_aligned16(p) || !dg_aligned16(g) || !dg_aligned16(m) || !dg_aligned16(v)) return DG_ERR_ALIGN;
-    const unsigned grid = adamw_grid(n);
-    if (clip_coef)
-        hipLaunchKernelGGL((adamw_kernel<true, false, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, hyper, rng_state, grad_scale,
-                           (bf16_t*)shadow_bf16, advance_step, clip_coef);
-    else
-        hipLaunchKernelGGL((adamw_kernel<false, false, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, hyper, rng_state, grad_scale,
-                           (bf16_t*)shadow_bf16, advance_step, (const float*)nullptr);
+// Host side.  Every argument of the widest entry; an entry that does not take one leaves it zero.
+struct AdamwCall {
+    float* p; const float* g; float* m; float* v; int64_t n; const float* hyper; uint32_t* rng_state; float grad_scale;
+    void* shadow_bf16; int advance_step; void* stream;
+    const float* clip_coef; const float* lr_table; int64_t lr_table_len; const uint32_t* no_decay_bits;      // _clip; _sched and up
+    float* ema; const float* ema_hyper;                                                                      // _ema and up
+    const uint32_t* guard; uint32_t* data_state;                                                             // _guard
+};
+enum AdamwFamily { ADAMW_STEP, ADAMW_CLIP, ADAMW_SCHED, ADAMW_EMA, ADAMW_GUARD };      // the entry: what it requires, which pack it launches
+
+// every refusal of every entry: DG_ERR_ARG is decided before DG_ERR_ALIGN
+static int adamw_check(const AdamwCall& c, AdamwFamily family) {
+    if (!c.p || !c.g || !c.m || !c.v || !c.hyper || !c.rng_state || c.n <= 0) return DG_ERR_ARG;
+    if (family == ADAMW_CLIP && !c.clip_coef) return DG_ERR_ARG;
+    if (family == ADAMW_EMA && (!c.ema || !c.ema_hyper)) return DG_ERR_ARG;
+    if (family == ADAMW_GUARD && (!c.guard || (c.ema == nullptr) != (c.ema_hyper == nullptr) || c.data_state == c.rng_state)) return DG_ERR_ARG;
+    if (c.lr_table ? c.lr_table_len < 1 : c.lr_table_len != 0) return DG_ERR_ARG;
+    if (!dg_aligned16(c.p) || !dg_aligned16(c.g) || !dg_aligned16(c.m) || !dg_aligned16(c.v) || (c.ema && !dg_aligned16(c.ema))) return DG_ERR_ALIGN;
+    return DG_OK;
+}
+
+// f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...) for the runtime flags b0, b1, ...
+template <typename F> static void adamw_with_flags(F&& f) { f(); }
+template <typename F, typename... B> static void adamw_with_flags(F&& f, bool b, B... rest) {
+    if (b) adamw_with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else adamw_with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+
+// The one place that chooses the instantiation.  _ema and _guard always carry their whole pack; _sched carries AdamwSched when there is
+// a table or a bitmap and is otherwise, like the two entries before it, <CLIP, false, false> with an empty pack.
+static int adamw_dispatch(const AdamwCall& c, AdamwFamily family) {
+    const int rc = adamw_check(c, family);
+    if (rc != DG_OK) return rc;
+    const AdamwSched sc{c.lr_table, c.lr_table_len, c.no_decay_bits};
+    const AdamwEma ea{c.ema, c.ema_hyper};
+    adamw_with_flags([&](auto clip, auto table, auto mask, auto avg) {
+        constexpr bool CLIP = decltype(clip)::value, TABLE = decltype(table)::value, MASK = decltype(mask)::value, EMA = decltype(avg)::value;
+        auto launch = [&](auto... pack) {
+            hipLaunchKernelGGL((adamw_kernel<CLIP, TABLE, MASK, decltype(pack)...>), dim3(adamw_grid(c.n)), dim3(256), 0, (hipStream_t)c.stream, c.p, c.g,
+                               c.m, c.v, c.n, c.hyper, c.rng_state, c.grad_scale, (bf16_t*)c.shadow_bf16, c.advance_step, c.clip_coef, pack...);
+        };
+        if (family == ADAMW_GUARD) launch(sc, ea, AdamwGuard<EMA>{c.guard, c.data_state});
+        else if (family == ADAMW_EMA) launch(sc, ea);
+        else if constexpr (TABLE || MASK) launch(sc);
+        else launch();
+    }, c.clip_coef != nullptr, c.lr_table != nullptr, c.no_decay_bits != nullptr, c.ema != nullptr);
     DG_LAUNCH_CHECK();
     return DG_OK;
 }
 
 extern "C" int dg_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper,
                              uint32_t* rng_state, float grad_scale, void* shadow_bf16, int advance_step, void* stream) {
-    return adamw_launch(p, g, m, v, n, hyper, rng_state, grad_scale, nullptr, shadow_bf16, advance_step, stream);
+    return adamw_dispatch(AdamwCall{p, g, m, v, n, hyper, rng_state, grad_scale, shadow_bf16, advance_step, stream}, ADAMW_STEP);
 }
 
 extern "C" int dg_adamw_step_clip(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, uint32_t* rng_state,
                                   float grad_scale, const float* clip_coef, void* shadow_bf16, int advance_step, void* stream) {
-    if (!clip_coef) return DG_ERR_ARG;
-    return adamw_launch(p, g, m, v, n, hyper, rng_state, grad_scale, clip_coef, shadow_bf16, advance_step, stream);
+    return adamw_dispatch(AdamwCall{p, g, m, v, n, hyper, rng_state, grad_scale, shadow_bf16, advance_step, stream, clip_coef}, ADAMW_CLIP);
 }
 
 extern "C" int dg_adamw_step_sched(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, uint32_t* rng_state,
                                    float grad_scale, const float* clip_coef, const float* lr_table, int64_t lr_table_len,
                                    const uint32_t* no_decay_bits, void* shadow_bf16, int advance_step, void* stream) {
-    if (!p || !g || !m || !v || !hyper || !rng_state || n <= 0) return DG_ERR_ARG;
-    if (lr_table ? lr_table_len < 1 : lr_table_len != 0) return DG_ERR_ARG;
-    if (!dg_aligned16(p) || !dg_aligned16(g) || !dg_aligned16(m) || !dg_aligned16(v)) return DG_ERR_ALIGN;
-    const unsigned grid = adamw_grid(n);
-    const AdamwSched sc{lr_table, lr_table_len, no_decay_bits};
-#define LAUNCH(CLIP, TABLE, MASK) hipLaunchKernelGGL((adamw_kernel<CLIP, TABLE, MASK, AdamwSched>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, hyper, rng_state, grad_scale, (bf16_t*)shadow_bf16, advance_step, clip_coef, sc)
-    switch ((clip_coef ? 4 : 0) | (lr_table ? 2 : 0) | (no_decay_bits ? 1 : 0)) {
-        case 0: return adamw_launch(p, g, m, v, n, hyper, rng_state, grad_scale, nullptr, shadow_bf16, advance_step, stream);
-        case 1: LAUNCH(false, false, true); break;
-        case 2: LAUNCH(false, true, false); break;
-        case 3: LAUNCH(false, true, true); break;
-        case 4: return adamw_launch(p, g, m, v, n, hyper, rng_state, grad_scale, clip_coef, shadow_bf16, advance_step, stream);
-        case 5: LAUNCH(true, false, true); break;
-        case 6: LAUNCH(true, true, false); break;
-        default: LAUNCH(true, true, true); break;
-    }
-#undef LAUNCH
-    DG_LAUNCH_CHECK();
-    return DG_OK;
+    return adamw_dispatch(AdamwCall{p, g, m, v, n, hyper, rng_state, grad_scale, shadow_bf16, advance_step, stream, clip_coef, lr_table,
+                                    lr_table_len, no_decay_bits}, ADAMW_SCHED);
 }
 
 extern "C" int dg_adamw_step_ema(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, uint32_t* rng_state,
                                  float grad_scale, const float* clip_coef, const float* lr_table, int64_t lr_table_len,
                                  const uint32_t* no_decay_bits, void* shadow_bf16, int advance_step, float* ema, const float* ema_hyper,
                                  void* stream) {
-    if (!p || !g || !m || !v || !hyper || !rng_state || !ema || !ema_hyper || n <= 0) return DG_ERR_ARG;
-    if (lr_table ? lr_table_len < 1 : lr_table_len != 0) return DG_ERR_ARG;
-    if (!dg_aligned16(p) || !dg_aligned16(g) || !dg_aligned16(m) || !dg_aligned16(v) || !dg_aligned16(ema)) return DG_ERR_ALIGN;
-    const unsigned grid = adamw_grid(n);
-    const AdamwSched sc{lr_table, lr_table_len, no_decay_bits};
-    const AdamwEma ea{ema, ema_hyper};
-#define LAUNCH(CLIP, TABLE, MASK) hipLaunchKernelGGL((adamw_kernel<CLIP, TABLE, MASK, AdamwSched, AdamwEma>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, hyper, rng_state, grad_scale, (bf16_t*)shadow_bf16, advance_step, clip_coef, sc, ea)
-    switch ((clip_coef ? 4 : 0) | (lr_table ? 2 : 0) | (no_decay_bits ? 1 : 0)) {
-        case 0: LAUNCH(false, false, false); break;
-        case 1: LAUNCH(false, false, true); break;
-        case 2: LAUNCH(false, true, false); break;
-        case 3: LAUNCH(false, true, true); break;
-        case 4: LAUNCH(true, false, false); break;
-        case 5: LAUNCH(true, false, true); break;
-        case 6: LAUNCH(true, true, false); break;
-        default: LAUNCH(true, true, true); break;
-    }
-#undef LAUNCH
-    DG_LAUNCH_CHECK();
-    return DG_OK;
+    return adamw_dispatch(AdamwCall{p, g, m, v, n, hyper, rng_state, grad_scale, shadow_bf16, advance_step, stream, clip_coef, lr_table,
+                                    lr_table_len, no_decay_bits, ema, ema_hyper}, ADAMW_EMA);
 }
 
 extern "C" int dg_adamw_step_guard(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, uint32_t* rng_state,
                                    float grad_scale, const float* clip_coef, const float* lr_table, int64_t lr_table_len,
                                    const uint32_t* no_decay_bits, void* shadow_bf16, int advance_step, float* ema, const float* ema_hyper,
                                    const uint32_t* guard, uint32_t* data_state, void* stream) {
-    if (!p || !g || !m || !v || !hyper || !rng_state || !guard || n <= 0) return DG_ERR_ARG;
-    if ((ema == nullptr) != (ema_hyper == nullptr) || data_state == rng_state) return DG_ERR_ARG;
-    if (lr_table ? lr_table_len < 1 : lr_table_len != 0) return DG_ERR_ARG;
-    if (!dg_aligned16(p) || !dg_aligned16(g) || !dg_aligned16(m) || !dg_aligned16(v) || (ema && !dg_aligned16(ema))) return DG_ERR_ALIGN;
-    const unsigned grid = adamw_grid(n);
-    const AdamwSched sc{lr_table, lr_table_len, no_decay_bits};
-    const AdamwEma ea{ema, ema_hyper};
-#define LAUNCH(CLIP, TABLE, MASK, EMA) hipLaunchKernelGGL((adamw_kernel<CLIP, TABLE, MASK, AdamwSched, AdamwEma, AdamwGuard<EMA>>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, hyper, rng_state, grad_scale, (bf16_t*)shadow_bf16, advance_step, clip_coef, sc, ea, AdamwGuard<EMA>{guard, data_state})
-    switch ((ema ? 8 : 0) | (clip_coef ? 4 : 0) | (lr_table ? 2 : 0) | (no_decay_bits ? 1 : 0)) {
-        case 0: LAUNCH(false, false, false, false); break;
-        case 1: LAUNCH(false, false, true, false); break;
-        case 2: LAUNCH(false, true, false, false); break;
-        case 3: LAUNCH(false, true, true, false); break;
-        case 4: LAUNCH(true, false, false, false); break;
-        case 5: LAUNCH(true, false, true, false); break;
-        case 6: LAUNCH(true, true, false, false); break;
-        case 7: LAUNCH(true, true, true, false); break;
-        case 8: LAUNCH(false, false, false, true); break;
-        case 9: LAUNCH(false, false, true, true); break;
-        case 10: LAUNCH(false, true, false, true); break;
-        case 11: LAUNCH(false, true, true, true); break;
-        case 12: LAUNCH(true, false, false, true); break;
-        case 13: LAUNCH(true, false, true, true); break;
-        case 14: LAUNCH(true, true, false, true); break;
-        default: LAUNCH(true, true, true, true); break;
-    }
-#undef LAUNCH
-    DG_LAUNCH_CHECK();
-    return DG_OK;
+    return adamw_dispatch(AdamwCall{p, g, m, v, n, hyper, rng_state, grad_scale, shadow_bf16, advance_step, stream, clip_coef, lr_table,
+                                    lr_table_len, no_decay_bits, ema, ema_hyper, guard, data_state}, ADAMW_GUARD);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -67,7 +67,9 @@ __global__ __launch_bounds__(DG_SUMSQ_WG) void sumsq_partials_kernel(const float
 // A NaN or Inf norm fails the comparison against any finite limit (FLT_MAX guards non-finite gradients alone; +inf would let an
 // Inf norm through).  sumsq_partials_kernel squares in fp32, so a finite element beyond 1.8e19 in magnitude gives an Inf norm and
 // reads as non-finite too.  Thread 0 moves the counters with plain stores; dg_adamw_step_guard reads guard[0] in the next launch.
-// With an empty pack this is the kernel as it was, instruction for instruction.
+// The pack is empty or one FinalizeGuard; the coefficient is written once for both.  The guard is taken with the fold `(gd, ...)`,
+// not with dg_pack_get: copied straight from the kernel argument its pointers count as never clobbered and guard[1] is read with a
+// scalar load, through the getter it is not.
 struct FinalizeGuard { const float* limit; const float* loss; uint32_t* guard; };
 template <typename... G>
 __global__ __launch_bounds__(DG_SUMSQ_WG) void grad_norm_finalize_kernel(const double* __restrict__ part, int n_parts, float grad_scale,
@@ -87,17 +89,14 @@ __global__ __launch_bounds__(DG_SUMSQ_WG) void grad_norm_finalize_kernel(const d
     const double s = block_sum_f64(acc, red);
     if (threadIdx.x == 0) {
         const float total = (float)(sqrt(s) * (double)grad_scale);
-        if constexpr (sizeof...(G) == 0) {
+        constexpr bool GUARD = sizeof...(G) != 0;
+        out[0] = total;
+        if (!GUARD || max_norm) {
             const float c = max_norm[0] / (total + 1e-6f);
-            out[0] = total;
             out[1] = c > 1.f ? 1.f : c;
-        } else {
+        }
+        if constexpr (GUARD) {
             const FinalizeGuard fg = (gd, ...);
-            out[0] = total;
-            if (max_norm) {
-                const float c = max_norm[0] / (total + 1e-6f);
-                out[1] = c > 1.f ? 1.f : c;
-            }
             bool apply = total <= fg.limit[0];
             if (fg.loss) apply = apply && isfinite(fg.loss[0]);
             fg.guard[0] = apply ? 1u : 0u;

@@ -354,15 +354,15 @@ class TrainEngine:
         self.no_decay_bits = None
         if self.no_decay:
             self.no_decay_bits = ops.new_no_decay_bits(self._no_decay_ranges(), self.n_active, self.dev)
-        # what _prog_update adds to its ops.adamw_step call: nothing for an engine with neither, whose call is the one it always
-        # was, argument for argument
+        # what _prog_update adds to its ops.adamw_step call: nothing for an engine with neither, which then passes no keyword but
+        # `clip` (a stand-in for ops.adamw_step that knows no other keeps working).  ops.adamw_step routes by what it is given.
         self._sched_kw = {}
         if self.lr_table is not None or self.no_decay_bits is not None:
             self._sched_kw = {"lr_table": self.lr_table, "no_decay_bits": self.no_decay_bits}
         # ema_decay: ema = flat[0, n_active) as the launch has just written it, averaged by AdamW's own step word (opt_state under
         # accumulation: once per optimizer step); the first step overwrites it.  ema_hyper = {decay, warmup} is read on the device:
         # set_ema_decay() writes it, captured graphs stay valid.  _ema_kw is what _prog_update adds to its
-        # ops.adamw_step call: nothing for an engine without it, whose call is the one it always was.
+        # ops.adamw_step call: nothing for an engine without it (as _sched_kw).
         self.ema = self.ema_hyper = None
         self._ema_kw = {}
         self._in_ema = False          # inside `with ema_weights()`: flat holds the average, ema the weights
@@ -383,7 +383,7 @@ class TrainEngine:
         # (which then runs with or without clipping) and read by every workgroup of the AdamW launch; guard_limit is read on the
         # device (set_skip_grad_norm() writes it: captured graphs stay valid).  norm_out = {total_norm, coef} is clip_state where
         # the engine clips.  _guard_kw is what _prog_update adds to its ops.adamw_step call: nothing for an engine without the
-        # guard, whose call is the one it always was.
+        # guard (as _sched_kw).
         self.guard = self.guard_limit = self.norm_out = None
         self._guard_kw = {}
         if self.guard_on:

@@ -971,42 +971,26 @@ def attn_decode_append(row: Tensor, cache: Tensor, state: Tensor, NH: int, H: in
     return out
 
 
-def _check_adamw_indexing(n: int, streams: dict, lr_table, no_decay_bits, clip) -> None:
-    """what dg_adamw_step_sched / dg_adamw_step_ema index and the library cannot check: n against every stream, the table's shape,
-    the bitmap's length"""
-    if n < 1 or any(n > t.numel() for t in streams.values()):
-        raise ValueError(f"adamw_step: n = {n} does not fit {', '.join(streams)}")
-    if lr_table is not None:
-        _chk(lr_table, "lr_table", torch.float32)
-        if lr_table.dim() != 1 or lr_table.numel() < 1:
-            raise ValueError("adamw_step: lr_table must be a 1-D tensor with at least one entry")
-    if no_decay_bits is not None:
-        _chk(no_decay_bits, "no_decay_bits", torch.int32)
-        if no_decay_bits.numel() < no_decay_words(n):
-            raise ValueError(f"adamw_step: no_decay_bits needs {no_decay_words(n)} words for n = {n}, got {no_decay_bits.numel()}")
-    if clip is not None:
-        _chk(clip, "clip", torch.float32)
-
-
 def adamw_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, hyper: Tensor, rng_state: Tensor, grad_scale: float = 1.0,
                shadow_bf16: Optional[Tensor] = None, n: Optional[int] = None, advance: bool = False, *,
                clip: Optional[Tensor] = None, lr_table: Optional[Tensor] = None, no_decay_bits: Optional[Tensor] = None,
                ema: Optional[Tensor] = None, ema_hyper: Optional[Tensor] = None, guard: Optional[Tensor] = None,
                data_state: Optional[Tensor] = None) -> None:
-    """advance: the launch also moves the step word of rng_state on (what state_advance does, without its launch).
+    """One fused AdamW launch over the first n elements (default: all) of the flat buffers.  The entry is the first of
+    dg_adamw_step_guard / _ema / _sched / _clip / dg_adamw_step that takes everything given; an operand that is None costs nothing.
+    advance: the launch also moves the step word of rng_state on (what state_advance does, without its launch).
     clip: a device fp32 scalar, the clipping coefficient written by grad_norm (out[1:2]); the step then applies g * grad_scale * coef
-    (dg_adamw_step_clip) and g itself stays unclipped.  None: dg_adamw_step, unchanged.
+    and g itself stays unclipped.
     lr_table: a device fp32 vector; the update uses lr_table[min(step word, len - 1)] instead of hyper[0].
     no_decay_bits: the bitmap of new_no_decay_bits(ranges, n, device); elements of a set granule see weight_decay = 0.
-    Either of the two takes the launch to dg_adamw_step_sched; with both None the calls are the ones above, unchanged.
     ema (with ema_hyper = new_ema_hyper(decay, warmup, device)): the launch also moves this moving average of the weights on
-    (dg_adamw_step_ema: ema += (p_new - ema) * (1 - d_s) by the step word it reads; step word 0: ema = p_new); p, m, v, the shadow
-    and the state words are the ones the launch without it writes.  None: the calls above, unchanged.
-    guard: the update guard grad_norm(guard=...) has just written (new_update_guard); the launch goes to dg_adamw_step_guard, with
-    any of the operands above.  guard[0] == 1: the bits of the launch without it.  guard[0] == 0: the update is skipped -- no buffer
-    is read or written and rng_state's step word stays.  data_state (with guard and advance): a second 4-word state whose step word
-    the launch moves on in either case (the data side of a training step: dropout key, staged offset row, fp8 amax slot).
-    None: the calls above, unchanged."""
+    (ema += (p_new - ema) * (1 - d_s) by the step word it reads; step word 0: ema = p_new); p, m, v, the shadow and the state words
+    are the ones the launch without it writes.
+    guard: the update guard grad_norm(guard=...) has just written (new_update_guard).  guard[0] == 1: the bits of the launch without
+    it.  guard[0] == 0: the update is skipped -- no buffer is read or written and rng_state's step word stays.  data_state (with
+    guard and advance): a second 4-word state whose step word the launch moves on in either case (the data side of a training
+    step: dropout key, staged offset row, fp8 amax slot)."""
+    # the checks, every one for every entry: what the library indexes and cannot check itself
     for t, nm in ((p, "p"), (g, "g"), (m, "m"), (v, "v"), (hyper, "hyper")):
         _chk(t, nm, torch.float32)
     n = p.numel() if n is None else n
@@ -1014,58 +998,44 @@ def adamw_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, hyper: Tensor, rng_st
         raise ValueError("adamw_step: ema_hyper goes with ema")
     if guard is None and data_state is not None:
         raise ValueError("adamw_step: data_state goes with guard")
-    if guard is not None:
-        if ema is not None and ema_hyper is None:
-            raise ValueError("adamw_step: ema needs ema_hyper (new_ema_hyper)")
-        _chk(guard, "guard", torch.int32)
-        _chk(rng_state, "rng_state", torch.int32)
-        if guard.numel() < 4 or rng_state.numel() < 4:
-            raise ValueError("adamw_step: guard and rng_state need 4 words each (new_update_guard, new_rng_state)")
-        streams = {"p": p, "g": g, "m": m, "v": v}
-        if ema is not None:
-            _chk(ema, "ema", torch.float32)
-            _chk(ema_hyper, "ema_hyper", torch.float32)
-            if ema_hyper.numel() < 2:
-                raise ValueError("adamw_step: ema_hyper needs 2 floats {decay, warmup} (new_ema_hyper)")
-            streams["ema"] = ema
-        _check_adamw_indexing(n, streams, lr_table, no_decay_bits, clip)
-        if shadow_bf16 is not None and shadow_bf16.numel() < n:
-            raise ValueError(f"adamw_step: shadow_bf16 holds {shadow_bf16.numel()} elements, n = {n}")
-        if data_state is not None:
-            _chk(data_state, "data_state", torch.int32)
-            if data_state.numel() < 4 or data_state.data_ptr() == rng_state.data_ptr():
-                raise ValueError("adamw_step: data_state needs 4 words of its own (not rng_state)")
-        check(lib.dg_adamw_step_guard(_p(p), _p(g), _p(m), _p(v), n, _p(hyper), _p(rng_state), float(grad_scale), _p(clip), _p(lr_table),
-                                      0 if lr_table is None else lr_table.numel(), _p(no_decay_bits), _p(shadow_bf16), int(advance),
-                                      _p(ema), _p(ema_hyper), _p(guard), _p(data_state), _stream()), "dg_adamw_step_guard")
-        return
+    if ema is not None and ema_hyper is None:
+        raise ValueError("adamw_step: ema needs ema_hyper (new_ema_hyper)")
+    streams = {"p": p, "g": g, "m": m, "v": v}
+    _chk(rng_state, "rng_state", torch.int32)
+    for t, nm, dtype in ((guard, "guard", torch.int32), (ema, "ema", torch.float32), (ema_hyper, "ema_hyper", torch.float32),
+                         (lr_table, "lr_table", torch.float32), (no_decay_bits, "no_decay_bits", torch.int32), (clip, "clip", torch.float32),
+                         (data_state, "data_state", torch.int32)):
+        if t is not None:
+            _chk(t, nm, dtype)
+    if rng_state.numel() < 4 or (guard is not None and guard.numel() < 4):
+        raise ValueError("adamw_step: guard and rng_state need 4 words each (new_update_guard, new_rng_state)")
     if ema is not None:
-        if ema_hyper is None:
-            raise ValueError("adamw_step: ema needs ema_hyper (new_ema_hyper)")
-        _chk(ema, "ema", torch.float32)
-        _chk(ema_hyper, "ema_hyper", torch.float32)
-        _check_adamw_indexing(n, {"p": p, "g": g, "m": m, "v": v, "ema": ema}, lr_table, no_decay_bits, clip)
         if ema_hyper.numel() < 2:
             raise ValueError("adamw_step: ema_hyper needs 2 floats {decay, warmup} (new_ema_hyper)")
-        if shadow_bf16 is not None and shadow_bf16.numel() < n:
-            raise ValueError(f"adamw_step: shadow_bf16 holds {shadow_bf16.numel()} elements, n = {n}")
-        check(lib.dg_adamw_step_ema(_p(p), _p(g), _p(m), _p(v), n, _p(hyper), _p(rng_state), float(grad_scale), _p(clip), _p(lr_table),
-                                    0 if lr_table is None else lr_table.numel(), _p(no_decay_bits), _p(shadow_bf16), int(advance),
-                                    _p(ema), _p(ema_hyper), _stream()), "dg_adamw_step_ema")
-        return
-    if lr_table is not None or no_decay_bits is not None:
-        _check_adamw_indexing(n, {"p": p, "g": g, "m": m, "v": v}, lr_table, no_decay_bits, clip)
-        check(lib.dg_adamw_step_sched(_p(p), _p(g), _p(m), _p(v), n, _p(hyper), _p(rng_state), float(grad_scale), _p(clip), _p(lr_table),
-                                      0 if lr_table is None else lr_table.numel(), _p(no_decay_bits), _p(shadow_bf16), int(advance),
-                                      _stream()), "dg_adamw_step_sched")
-        return
-    if clip is None:
-        check(lib.dg_adamw_step(_p(p), _p(g), _p(m), _p(v), n, _p(hyper), _p(rng_state), float(grad_scale), _p(shadow_bf16), int(advance),
-                                _stream()), "dg_adamw_step")
-        return
-    _chk(clip, "clip", torch.float32)
-    check(lib.dg_adamw_step_clip(_p(p), _p(g), _p(m), _p(v), n, _p(hyper), _p(rng_state), float(grad_scale), _p(clip), _p(shadow_bf16),
-                                 int(advance), _stream()), "dg_adamw_step_clip")
+        streams["ema"] = ema
+    if n < 1 or any(n > t.numel() for t in streams.values()):
+        raise ValueError(f"adamw_step: n = {n} does not fit {', '.join(streams)}")
+    if lr_table is not None and (lr_table.dim() != 1 or lr_table.numel() < 1):
+        raise ValueError("adamw_step: lr_table must be a 1-D tensor with at least one entry")
+    if no_decay_bits is not None and no_decay_bits.numel() < no_decay_words(n):
+        raise ValueError(f"adamw_step: no_decay_bits needs {no_decay_words(n)} words for n = {n}, got {no_decay_bits.numel()}")
+    if shadow_bf16 is not None and shadow_bf16.numel() < n:
+        raise ValueError(f"adamw_step: shadow_bf16 holds {shadow_bf16.numel()} elements, n = {n}")
+    if data_state is not None and (data_state.numel() < 4 or data_state.data_ptr() == rng_state.data_ptr()):
+        raise ValueError("adamw_step: data_state needs 4 words of its own (not rng_state)")
+    # the route: the first entry that takes everything given; each entry's arguments are the shared prefix, its own tail, the stream
+    sched = (_p(clip), _p(lr_table), 0 if lr_table is None else lr_table.numel(), _p(no_decay_bits), _p(shadow_bf16), int(advance))
+    if guard is not None:
+        entry, tail = "dg_adamw_step_guard", sched + (_p(ema), _p(ema_hyper), _p(guard), _p(data_state))
+    elif ema is not None:
+        entry, tail = "dg_adamw_step_ema", sched + (_p(ema), _p(ema_hyper))
+    elif lr_table is not None or no_decay_bits is not None:
+        entry, tail = "dg_adamw_step_sched", sched
+    elif clip is not None:
+        entry, tail = "dg_adamw_step_clip", (_p(clip), _p(shadow_bf16), int(advance))
+    else:
+        entry, tail = "dg_adamw_step", (_p(shadow_bf16), int(advance))
+    check(getattr(lib, entry)(_p(p), _p(g), _p(m), _p(v), n, _p(hyper), _p(rng_state), float(grad_scale), *tail, _stream()), entry)
 
 
 def check_ema_options(decay=None, warmup=False):

@@ -165,7 +165,7 @@ class AdamW(torch.optim.Optimizer):
         return fl
 
     def _ema_kw(self, fl: _Flat) -> dict:
-        """what step() adds to its ops.adamw_step call: nothing without ema_decay, where the call is the one it always was"""
+        """what step() adds to its ops.adamw_step call: nothing without ema_decay (ops.adamw_step routes by what it is given)"""
         return {} if fl.ema is None else {"ema": fl.ema, "ema_hyper": fl.ema_hyper}
 
     def set_ema_decay(self, decay: float) -> None:

@@ -493,7 +493,9 @@ int dg_softmax_rows(const float* logits, int64_t ldl, float* probs, int64_t ldp,
  * hyper (device): {lr, beta1, beta2, eps, weight_decay}.  grad_scale multiplies g first
  * (1/world_size after a sum all-reduce).  Optionally refreshes a bf16 shadow copy of p.
  * advance_step != 0: the launch also does dg_state_advance -- the workgroup that finishes last writes step + 1 (word 3 of
- * rng_state is its arrival counter: zero before and after every launch). */
+ * rng_state is its arrival counter: zero before and after every launch).
+ * dg_adamw_step and the four dg_adamw_step_* entries below are one kernel template, one argument check and one dispatch: each
+ * entry names what it requires and which optional operands it takes, and every one decides DG_ERR_ARG before DG_ERR_ALIGN. */
 int dg_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper,
                   uint32_t* rng_state, float grad_scale, void* shadow_bf16, int advance_step, void* stream);
 
