@@ -12,6 +12,11 @@
 //   2b. dg_sample_rows_nucleus only (four-word params): min-p keeps e_j >= min_p; top-p finds tau_p by a second radix descent whose
 //      LDS histograms hold INTEGER masses w_j = rint(e_j * 2^40) (64-bit integer atomics: sums do not depend on arrival order).
 //      Neither costs a pass when it is off: min-p alone is one more compare in passes 3 and 4.
+//   0. dg_sample_rows_control only: every pass reads y_i in the place of the logit -- the repetition / presence / frequency
+//      penalties on the row's token counts and the logit bias, four single fp32 roundings, recomputed by each pass from
+//      (logit, count, bias) (no scratch row: the three operands are L2-resident like the row itself).  The thread that writes the
+//      token also does counts[row, token] += 1 and, at a stop token, lengths[row] = L + 1; a row that arrives finished writes pad_id
+//      and returns before it reads a logit.
 // No floating-point atomics anywhere: tokens and probs are a pure function of (logits, state, params, row).
 // exp and the prefix sums are fp64: with a few terms kept by top-k the errors of an fp32 expf do not average out of S (measured:
 // probs off by 4.5 x 2^-24 at k = 40), and fp64 is cheap here -- a few passes over one row.  The CDF is then exact to ~1e-14.
@@ -21,6 +26,14 @@
 
 struct SampleParams { float inv_temp; int32_t top_k; };
 struct SampleParamsEx { float inv_temp; int32_t top_k; float top_p; float min_p; };      // dg_sample_rows_nucleus: the same first two words
+// dg_sample_rows_control: the 16-word control block (device) and the launch arguments that come with it
+struct SampleControl {
+    float inv_rep, rep, presence, frequency;
+    int32_t use_bias, n_stop, pad_id, reserved;
+    int32_t stop[DG_SAMPLE_MAX_STOP];
+};
+struct SampleCtlArgs { const SampleControl* control; const float* bias; int32_t* counts; int64_t ldc; int32_t* lengths; };
+struct SampleNoCtl {};
 
 __device__ __forceinline__ uint32_t f32_key(float z) {          // a < b  <=>  key(a) < key(b)  (no NaNs)
     const uint32_t b = __float_as_uint(z);
@@ -30,12 +43,27 @@ __device__ __forceinline__ float key_f32(uint32_t k) {
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
 }
 
+// The adjustment of dg_sample_rows_control: four fp32 roundings, one instruction each.  Contraction is off for the whole function --
+// left on, x * inv_rep - presence becomes one fma with a single rounding, which no host restatement reproduces.
+__device__ __forceinline__ float adjust_logit(float x, int32_t c, float inv_rep, float rep, float presence, float frequency,
+                                              const float* __restrict__ bias, int i) {
+#pragma clang fp contract(off)
+    float y = x;
+    if (c > 0) y = y > 0.f ? y * inv_rep : y * rep;
+    y = y - (c > 0 ? presence : 0.f);
+    const float f = frequency * (float)c;
+    y = y - f;
+    if (bias) y = y + bias[i];
+    return y;
+}
+
 // EXT: params is a SampleParamsEx and the top-p / min-p stage exists; !EXT is dg_sample_rows as it always was
-template <int NT, bool EXT>
+// CTL: dg_sample_rows_control -- `ctl` holds the control block, bias, counts and lengths; !CTL: an empty struct, no code
+template <int NT, bool EXT, bool CTL = false>
 __global__ __launch_bounds__(NT) void sample_rows_kernel(const float* __restrict__ logits, int64_t ldl, int M, int V,
                                                          const uint32_t* __restrict__ state, const SampleParams* __restrict__ params,
                                                          int64_t* __restrict__ ids, int64_t ld_ids, float* __restrict__ probs,
-                                                         int64_t ldp) {
+                                                         int64_t ldp, std::conditional_t<CTL, SampleCtlArgs, SampleNoCtl> ctl) {
     constexpr int NW = NT / 64;
     __shared__ float s_mx[NW];
     __shared__ int s_ix[NW];
@@ -54,10 +82,30 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const float* __restrict
     const bool greedy = !(inv_temp > 0.f);
     const float sc = greedy ? 1.f : inv_temp;
 
+    // ---- pass 0 (CTL): finished rows leave here; everything below reads zat(i) = y_i * sc in the place of logit_i * sc
+    float inv_rep = 1.f, rpen = 1.f, presence = 0.f, frequency = 0.f;
+    const float* bias = nullptr; int32_t* crow = nullptr;
+    if constexpr (CTL) {
+        if (ctl.lengths && ids && ld_ids > 0 && ctl.lengths[row] != 0) {          // uniform per workgroup, before any barrier
+            const uint32_t Lf = state[2];
+            if (tid == 0 && (int64_t)Lf < ld_ids) ids[(int64_t)row * ld_ids + Lf] = (int64_t)ctl.control->pad_id;
+            return;
+        }
+        inv_rep = ctl.control->inv_rep; rpen = ctl.control->rep;
+        presence = ctl.control->presence; frequency = ctl.control->frequency;
+        if (ctl.control->use_bias != 0) bias = ctl.bias;
+        if (ctl.counts) crow = ctl.counts + (int64_t)row * ctl.ldc;
+    }
+    auto zat = [&](int i) -> float {
+        float y = x[i];
+        if constexpr (CTL) y = adjust_logit(y, crow ? crow[i] : 0, inv_rep, rpen, presence, frequency, bias, i);
+        return __fmul_rn(y, sc);
+    };
+
     // ---- pass 1: max and the lowest index that attains it
     float mx = -INFINITY; int ix = V;
     for (int i = tid; i < V; i += NT) {
-        const float z = __fmul_rn(x[i], sc);
+        const float z = zat(i);
         if (ix == V || z > mx) { mx = z; ix = i; }              // strict: a thread keeps the lowest of its equal maxima
     }
 #pragma unroll
@@ -78,9 +126,21 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const float* __restrict
     const uint32_t L = state ? state[2] : 0u;
     const bool write_tok = ids != nullptr && (ld_ids == 0 || (int64_t)L < ld_ids);
     int64_t* tok_out = ids ? (ld_ids == 0 ? ids + row : ids + (int64_t)row * ld_ids + L) : nullptr;
+    // the one thread that has the token writes it and (CTL) keeps the row's books: every read of counts is behind it by then
+    auto emit = [&](int tok) {
+        *tok_out = tok;
+        if constexpr (CTL) {
+            if (crow) crow[tok] = crow[tok] + 1;
+            if (ctl.lengths && ld_ids > 0) {
+                const int ns = min(ctl.control->n_stop, DG_SAMPLE_MAX_STOP);
+                for (int q = 0; q < ns; ++q)
+                    if (ctl.control->stop[q] == tok) { ctl.lengths[row] = (int32_t)(L + 1u); break; }
+            }
+        }
+    };
 
     if (greedy) {
-        if (tid == 0 && write_tok) *tok_out = ix;
+        if (tid == 0 && write_tok) emit(ix);
         if (prow) for (int i = tid; i < V; i += NT) prow[i] = i == ix ? 1.f : 0.f;
         return;
     }
@@ -96,7 +156,7 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const float* __restrict
             const uint32_t prefix = s_sel[0];
             const uint32_t himask = shift == 24 ? 0u : (0xFFFFFFFFu << (shift + 8));
             for (int i = tid; i < V; i += NT) {
-                const uint32_t key = f32_key(__fmul_rn(x[i], sc));
+                const uint32_t key = f32_key(zat(i));
                 if (((key ^ prefix) & himask) == 0u) atomicAdd(&s_hist[(key >> shift) & 255u], 1);
             }
             __syncthreads();
@@ -152,7 +212,7 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const float* __restrict
                 const uint32_t prefix = s_psel[0];
                 const uint32_t himask = shift == 24 ? 0u : (0xFFFFFFFFu << (shift + 8));
                 for (int i = tid; i < V; i += NT) {
-                    const float z = __fmul_rn(x[i], sc);
+                    const float z = zat(i);
                     const uint32_t key = f32_key(z);
                     double e;
                     if (((key ^ prefix) & himask) == 0u && kept(z, e)) {
@@ -194,7 +254,7 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const float* __restrict
     const int j0 = min(tid * chunk, V), j1 = min(j0 + chunk, V);
     double csum = 0.0; int last = -1;
     for (int j = j0; j < j1; ++j) {
-        const float z = __fmul_rn(x[j], sc);
+        const float z = zat(j);
         double e;
         if (kept(z, e)) { csum += e; last = j; }
     }
@@ -212,7 +272,7 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const float* __restrict
 
     if (prow) {
         for (int i = tid; i < V; i += NT) {
-            const float z = __fmul_rn(x[i], sc);
+            const float z = zat(i);
             double e;
             prow[i] = kept(z, e) ? (float)(e / S) : 0.f;
         }
@@ -226,36 +286,42 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const float* __restrict
     __syncthreads();
     const int owner = s_owner;
     if (owner == NT) {                                         // rounding (or an empty / non-finite row) left no such n
-        if (tid == 0) { const int l = s_last; *tok_out = l >= 0 ? l : ix; }
+        if (tid == 0) { const int l = s_last; emit(l >= 0 ? l : ix); }
         return;
     }
     if (tid != owner) return;
     double run = excl; int tok = last;                         // last: if re-adding from excl rounds below target
     for (int j = j0; j < j1; ++j) {
-        const float z = __fmul_rn(x[j], sc);
+        const float z = zat(j);
         double e;
         if (kept(z, e)) {
             run += e;
             if (run > target) { tok = j; break; }
         }
     }
-    *tok_out = tok;
+    emit(tok);
 }
 
-template <bool EXT>
+template <bool EXT, bool CTL = false>
 static int sample_rows_launch(const float* logits, int64_t ldl, int M, int V, const uint32_t* state, const void* params,
-                              int64_t* ids, int64_t ld_ids, float* probs, int64_t ldp, void* stream) {
+                              int64_t* ids, int64_t ld_ids, float* probs, int64_t ldp, void* stream,
+                              std::conditional_t<CTL, SampleCtlArgs, SampleNoCtl> ctl = {}) {
     if (!logits || !params || M <= 0 || V <= 0 || V > (1 << 20) || ldl < V || ld_ids < 0) return DG_ERR_ARG;
     if (!ids && !probs) return DG_ERR_ARG;
     if (ids && !state) return DG_ERR_ARG;
     if (probs && ldp < V) return DG_ERR_ARG;
+    if constexpr (CTL) {
+        if (!ctl.control) return DG_ERR_ARG;
+        if (ctl.counts && ctl.ldc < V) return DG_ERR_ARG;
+        if (ctl.lengths && (!ids || ld_ids == 0)) return DG_ERR_ARG;
+    }
     hipStream_t s = (hipStream_t)stream;
     const SampleParams* p = (const SampleParams*)params;
     // a chunk of at most 32 (small rows) or V / 1024 (52 at V = 53248) elements per thread
     if (V <= 8192)
-        hipLaunchKernelGGL((sample_rows_kernel<256, EXT>), dim3(M), dim3(256), 0, s, logits, ldl, M, V, state, p, ids, ld_ids, probs, ldp);
+        hipLaunchKernelGGL((sample_rows_kernel<256, EXT, CTL>), dim3(M), dim3(256), 0, s, logits, ldl, M, V, state, p, ids, ld_ids, probs, ldp, ctl);
     else
-        hipLaunchKernelGGL((sample_rows_kernel<1024, EXT>), dim3(M), dim3(1024), 0, s, logits, ldl, M, V, state, p, ids, ld_ids, probs, ldp);
+        hipLaunchKernelGGL((sample_rows_kernel<1024, EXT, CTL>), dim3(M), dim3(1024), 0, s, logits, ldl, M, V, state, p, ids, ld_ids, probs, ldp, ctl);
     DG_LAUNCH_CHECK();
     return DG_OK;
 }
@@ -268,4 +334,37 @@ extern "C" int dg_sample_rows(const float* logits, int64_t ldl, int M, int V, co
 extern "C" int dg_sample_rows_nucleus(const float* logits, int64_t ldl, int M, int V, const uint32_t* state, const void* params,
                                       int64_t* ids, int64_t ld_ids, float* probs, int64_t ldp, void* stream) {
     return sample_rows_launch<true>(logits, ldl, M, V, state, params, ids, ld_ids, probs, ldp, stream);
+}
+
+extern "C" int dg_sample_rows_control(const float* logits, int64_t ldl, int M, int V, const uint32_t* state, const void* params,
+                                      int64_t* ids, int64_t ld_ids, float* probs, int64_t ldp, const void* control,
+                                      const float* bias, int32_t* counts, int64_t ldc, int32_t* lengths, void* stream) {
+    return sample_rows_launch<true, true>(logits, ldl, M, V, state, params, ids, ld_ids, probs, ldp, stream,
+                                          SampleCtlArgs{(const SampleControl*)control, bias, counts, ldc, lengths});
+}
+
+// counts[m, clamp(ids[m, j])] += 1 for j < n: one workgroup per row; !accumulate zeroes the row's V counts first, and the barrier
+// of that same workgroup orders the zeroes before its own atomics -- no grid-wide ordering is needed
+__global__ __launch_bounds__(256) void token_counts_kernel(const int64_t* __restrict__ ids, int64_t ld_ids, int n, int V,
+                                                           int32_t* __restrict__ counts, int64_t ldc, int accumulate) {
+    const int row = blockIdx.x;
+    int32_t* crow = counts + (int64_t)row * ldc;
+    if (!accumulate) {
+        for (int i = threadIdx.x; i < V; i += 256) crow[i] = 0;
+        __syncthreads();
+    }
+    const int64_t* irow = ids + (int64_t)row * ld_ids;
+    for (int j = threadIdx.x; j < n; j += 256) {
+        int64_t v = irow[j];
+        v = v < 0 ? 0 : (v >= V ? V - 1 : v);
+        atomicAdd(&crow[v], 1);
+    }
+}
+
+extern "C" int dg_token_counts(const int64_t* ids, int64_t ld_ids, int M, int n, int V, int32_t* counts, int64_t ldc,
+                               int accumulate, void* stream) {
+    if (!ids || !counts || M <= 0 || n < 0 || V <= 0 || ld_ids < n || ldc < V) return DG_ERR_ARG;
+    hipLaunchKernelGGL(token_counts_kernel, dim3(M), dim3(256), 0, (hipStream_t)stream, ids, ld_ids, n, V, counts, ldc, accumulate);
+    DG_LAUNCH_CHECK();
+    return DG_OK;
 }

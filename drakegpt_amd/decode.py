@@ -13,6 +13,11 @@ it, the sampler writes token L into the ids buffer and dg_state_advance moves L 
 Graphs hold raw pointers, so the decoder owns every operand: staged copies of the weights (refreshed on every generate call),
 the K/V caches, the ids buffer, the state and the sampler parameters (always the four-word block of dg_sample_rows_nucleus:
 temperature, top_k, top_p and min_p change between calls without a new capture).
+
+A call with a penalty, a logit bias or a stop token replays a second pair of graphs, captured on the first such call: the same
+two chains ending in dg_sample_rows_control.  Its operands are the decoder's too -- the 16-word control block, bias [V], the
+token counts [B, V] that the kernel keeps up to date and lengths [B], the rows' "finished" state that the next replay honours --
+and every call that uses them rewrites all four first.  A call without controls replays the first pair, as it always did.
 """
 from __future__ import annotations
 
@@ -45,6 +50,15 @@ class DeviceDecoder:
         self.row = torch.zeros((B, 3 * C), dtype=self.act, device=device)       # staging: the new token's q/k/v
         self.ws = self.w_lm = self.tok = self.pos = self.lm_bias = None
         self.graphs = None
+        # the operands of dg_sample_rows_control, the tail of the second pair of graphs (captured on the first call that asks for a
+        # penalty, a bias or a stop token): every call that uses them rewrites all four first (set_controls)
+        V = model.token_embedding_table.weight.shape[0]
+        self.control = ops.new_sample_control(device=device)
+        self.bias = torch.zeros(V, dtype=torch.float32, device=device)
+        self.counts = torch.zeros((B, V), dtype=torch.int32, device=device)
+        self.lengths = torch.zeros(B, dtype=torch.int32, device=device)
+        self.graphs_control = None
+        self._controls = False                 # which tail a step launches: set by capture() / step() / tail() around the step
 
     # ------------------------------------------------------------------ operands
     @torch.no_grad()
@@ -65,9 +79,30 @@ class DeviceDecoder:
                 d.copy_(s)
 
     # ------------------------------------------------------------------ the two steps
+    @torch.no_grad()
+    def set_controls(self, control, bias, t0: int) -> None:
+        """the start of a call with controls: the new block, the bias (a CPU tensor or None: zeros, and the block's use_bias is 0),
+        the counts of the prompt ids[:, :t0] and all rows running -- nothing is inherited from the previous call"""
+        self.control.copy_(control)
+        if bias is None:
+            self.bias.zero_()
+        else:
+            self.bias.copy_(bias)
+        ops.token_counts(self.ids, t0, self.counts.shape[1], self.counts)
+        self.lengths.zero_()
+
     def _tail(self, logits) -> None:
-        ops.sample_rows(logits, self.state, self.params, ids=self.ids)
+        if self._controls:
+            ops.sample_rows(logits, self.state, self.params, ids=self.ids, control=self.control, bias=self.bias, counts=self.counts,
+                            lengths=self.lengths)
+        else:
+            ops.sample_rows(logits, self.state, self.params, ids=self.ids)
         ops.state_advance(self.state)
+
+    def tail(self, logits, controls: bool = False) -> None:
+        """sample and advance on eager logits (the prefill's last row)"""
+        self._controls = controls
+        self._tail(logits)
 
     def _step_cached(self) -> None:
         """TransformerLM._decode_step at the device position L - 1"""
@@ -91,12 +126,14 @@ class DeviceDecoder:
 
     # ------------------------------------------------------------------ capture / replay
     @torch.no_grad()
-    def capture(self) -> None:
+    def capture(self, controls: bool = False) -> None:
         """capture both steps once, each after a warm-up run at its own position (engine.capture_after_warmup; the state word is put
         back in between).  A warm-up step writes cache row L - 1 and ids[:, L]: both are rewritten by the real step at that L before
-        anything reads them."""
-        if self.graphs is not None:
+        anything reads them.  controls=True: the second pair, the same steps ending in dg_sample_rows_control; its warm-up also
+        touches counts and lengths, which set_controls rewrites before every use."""
+        if (self.graphs_control if controls else self.graphs) is not None:
             return
+        self._controls = controls
         model = self._mref()
         graphs = []
         for L, fn in ((1, self._step_cached), (self.ctx, lambda: self._step_window(model))):
@@ -104,11 +141,15 @@ class DeviceDecoder:
                 self.state.copy_(ops.new_rng_state(0, self.device, step=L))
             position()
             graphs += capture_after_warmup(self.device, [fn], position)
-        self.graphs = tuple(graphs)
+        if controls:
+            self.graphs_control = tuple(graphs)
+        else:
+            self.graphs = tuple(graphs)
 
-    def step(self, cached: bool, graph: bool = True) -> None:
+    def step(self, cached: bool, graph: bool = True, controls: bool = False) -> None:
+        self._controls = controls
         if graph:
-            self.graphs[0 if cached else 1].replay()
+            (self.graphs_control if controls else self.graphs)[0 if cached else 1].replay()
         elif cached:
             self._step_cached()
         else:

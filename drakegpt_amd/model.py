@@ -19,11 +19,13 @@ Reference quirks kept on purpose:
 from __future__ import annotations
 
 import math
+import numbers
 from collections import OrderedDict
 from typing import Optional
 
 import torch
 import torch.nn as nn
+from torch import Tensor
 
 from . import functional as HF
 from . import ops
@@ -94,6 +96,123 @@ def check_nucleus_args(top_p, min_p):
     return top_p, min_p
 
 
+def check_control_args(repetition_penalty, presence_penalty, frequency_penalty, logit_bias, stop_tokens, pad_token, stop_poll,
+                       vocab_size: int):
+    """the checks of generate()'s penalties, logit_bias and stop tokens, like check_nucleus_args: plain Python, raised before
+    anything touches a device.  Returns None when every control is off, else a dict: rep / presence / frequency (floats), bias
+    (a CPU fp32 tensor [V] or None), stop (a tuple of ints), pad (int), poll (int), adjust (bool: a penalty or a bias is on)."""
+    V = int(vocab_size)
+
+    def number(x, name):
+        if isinstance(x, bool):
+            raise ValueError(f"generate: {name} must be a number, got {x!r}")
+        try:
+            return float(x)
+        except (TypeError, ValueError):
+            raise ValueError(f"generate: {name} must be a number, got {x!r}") from None
+
+    def token(x, name):
+        if isinstance(x, bool) or not isinstance(x, numbers.Integral):
+            raise ValueError(f"generate: {name} must be an integer token id, got {x!r}")
+        if not 0 <= int(x) < V:
+            raise ValueError(f"generate: {name} must be in [0, {V}), got {x!r}")
+        return int(x)
+
+    rep = number(repetition_penalty, "repetition_penalty")
+    if not (math.isfinite(rep) and rep > 0.0):
+        raise ValueError(f"generate: repetition_penalty must be finite and > 0, got {repetition_penalty!r}")
+    presence = number(presence_penalty, "presence_penalty")
+    frequency = number(frequency_penalty, "frequency_penalty")
+    if not (math.isfinite(presence) and math.isfinite(frequency)):
+        raise ValueError("generate: presence_penalty and frequency_penalty must be finite")
+    if isinstance(stop_poll, bool) or not isinstance(stop_poll, numbers.Integral) or stop_poll < 1:
+        raise ValueError(f"generate: stop_poll must be an integer >= 1, got {stop_poll!r}")
+    bias = None
+    if logit_bias is not None:
+        if isinstance(logit_bias, dict):
+            bias = torch.zeros(V, dtype=torch.float32)
+            for k, v in logit_bias.items():
+                bias[token(k, "a logit_bias token")] = number(v, "a logit_bias value")
+        else:
+            try:
+                bias = torch.as_tensor(logit_bias).detach().to(device="cpu", dtype=torch.float32)
+            except (TypeError, ValueError, RuntimeError):
+                raise ValueError("generate: logit_bias must be a {token: value} dict or a sequence of vocab_size numbers") from None
+            if bias.dim() != 1 or bias.numel() != V:
+                raise ValueError(f"generate: a logit_bias sequence must have vocab_size = {V} entries, got {tuple(bias.shape)}")
+            bias = bias.clone()
+        if bool(torch.isnan(bias).any()) or bool((bias == math.inf).any()):
+            raise ValueError("generate: logit_bias values must be finite or -inf (a ban)")
+        if bool((bias == -math.inf).all()):
+            raise ValueError("generate: logit_bias bans every token")
+    stop = ()
+    if stop_tokens is not None:
+        if isinstance(stop_tokens, numbers.Integral) and not isinstance(stop_tokens, bool):
+            seq = [stop_tokens]
+        else:
+            try:
+                seq = list(stop_tokens)
+            except TypeError:
+                raise ValueError(f"generate: stop_tokens must be an int or a sequence of ints, got {stop_tokens!r}") from None
+        stop = tuple(token(t, "a stop token") for t in seq)
+        if not 1 <= len(stop) <= ops.SAMPLE_MAX_STOP or len(set(stop)) != len(stop):
+            raise ValueError(f"generate: stop_tokens must be 1 to {ops.SAMPLE_MAX_STOP} distinct token ids, got {stop_tokens!r}")
+    if pad_token is not None and not stop:
+        raise ValueError("generate: pad_token needs stop_tokens")
+    pad = token(pad_token, "pad_token") if pad_token is not None else (stop[0] if stop else 0)
+    adjust = not (rep == 1.0 and presence == 0.0 and frequency == 0.0 and bias is None)       # do the logits change at all
+    if not adjust and not stop:
+        return None
+    return dict(rep=rep, presence=presence, frequency=frequency, bias=bias, stop=stop, pad=pad, poll=int(stop_poll), adjust=adjust)
+
+
+def new_control_block(ctl: dict, device) -> Tensor:
+    """check_control_args' dict as the device block of dg_sample_rows_control"""
+    return ops.new_sample_control(repetition_penalty=ctl["rep"], presence_penalty=ctl["presence"], frequency_penalty=ctl["frequency"],
+                                  stop_tokens=ctl["stop"], pad_token=ctl["pad"], use_bias=ctl["bias"] is not None, device=device)
+
+
+def all_rows_finished(lengths: Tensor) -> bool:
+    """the stop-token poll: one device-to-host read of lengths [B]"""
+    return bool((lengths != 0).all())
+
+
+def trim_to_longest(ids: Tensor, lengths: Optional[Tensor], total: int) -> Tensor:
+    """ids[:, :n], n = the longest row: a row's final length (stop token included), `total` for a row still running"""
+    if lengths is None:
+        return ids[:, :total]
+    n = lengths.cpu()
+    return ids[:, :int(torch.where(n == 0, torch.full_like(n, total), n).max())]
+
+
+class _ControlOperands:
+    """what one generate() call with controls hands to ops.sample_rows: the control block, the bias, the token counts of the whole
+    sequence so far (prompt included, beyond the context window too) and, for the device sampler with stop tokens, lengths"""
+
+    def __init__(self, ctl: dict, idx: Tensor, V: int, lengths: bool):
+        self.stop, self.pad, self.poll, self.adjust = ctl["stop"], ctl["pad"], ctl["poll"], ctl["adjust"]
+        self.V = V
+        self.control = new_control_block(ctl, idx.device)
+        self.counts = ops.token_counts(idx, idx.shape[1], V)
+        self.bias = None if ctl["bias"] is None else ctl["bias"].to(idx.device)
+        self.lengths = torch.zeros(idx.shape[0], dtype=torch.int32, device=idx.device) if lengths and self.stop else None
+        self.finished = torch.zeros(idx.shape[0], dtype=torch.bool)          # the host sampler's own stop state
+
+    def kw(self) -> dict:
+        return dict(control=self.control, bias=self.bias, counts=self.counts, lengths=self.lengths)
+
+    def host_token(self, nxt: Tensor) -> Tensor:
+        """the host sampler's stop rule on the drawn column nxt [B, 1] (CPU): finished rows get pad_token, a row that draws a stop
+        token keeps it and is finished from the next position on"""
+        if self.stop:
+            nxt = torch.where(self.finished[:, None], torch.full_like(nxt, self.pad), nxt)
+            self.finished = self.finished | torch.isin(nxt[:, 0], torch.tensor(self.stop))
+        return nxt
+
+    def host_done(self) -> bool:
+        return bool(self.stop) and bool(self.finished.all())
+
+
 def draw_seed(generator: Optional[torch.Generator]) -> int:
     """one sampling seed from the CPU generator (the global one unless `generator` is given)"""
     return int(torch.randint(0, 2 ** 62, (1,), generator=generator))
@@ -162,43 +281,82 @@ class _LM(HipModule):
         return logits, loss
 
     @torch.no_grad()
-    def _last_probs(self, idx, params=None):
+    def _last_probs(self, idx, params=None, cs=None):
         logits, _ = self(idx)
-        return self._probs(logits[:, -1, :], params)
+        return self._probs(logits[:, -1, :], params, cs)
 
     @staticmethod
-    def _probs(logits, params):
-        """params None: the plain softmax (the reference's distribution); else the temperature / top-k / top-p / min-p filtered one"""
+    def _probs(logits, params, cs=None):
+        """params None: the plain softmax (the reference's distribution); else the temperature / top-k / top-p / min-p filtered one;
+        with cs (a _ControlOperands) the penalties and the bias are applied by the same kernel, which only reads the counts.
+        Stop tokens alone change no distribution: the call a run without them makes, so the tokens before a stop are its tokens"""
+        if cs is not None and cs.adjust:
+            return ops.sample_rows(logits, params=params, tokens=False, probs=True, control=cs.control, bias=cs.bias, counts=cs.counts)
         if params is None:
             return ops.softmax_rows(logits)
         return ops.sample_rows(logits, params=params, tokens=False, probs=True)
 
     @staticmethod
-    def _host_params(device, temperature, top_k, top_p=None, min_p=None):
+    def _host_params(device, temperature, top_k, top_p=None, min_p=None, ctl=None):
+        if ctl is not None and ctl["adjust"]:             # dg_sample_rows_control takes the four-word block
+            return ops.new_sample_params(temperature, top_k, device, top_p=1.0 if top_p is None else top_p,
+                                         min_p=0.0 if min_p is None else min_p)
         if temperature == 1.0 and top_k is None and top_p is None and min_p is None:
             return None
         return ops.new_sample_params(temperature, top_k, device, top_p=top_p, min_p=min_p)
 
+    @staticmethod
+    def _host_draw(probs, generator, idx, cs):
+        """one column from the CPU generator (one multinomial per step, controls or not), appended to idx and counted"""
+        nxt = torch.multinomial(probs.cpu(), num_samples=1, generator=generator)
+        if cs is not None:
+            nxt = cs.host_token(nxt)
+        nxt = nxt.to(idx.device)
+        idx = torch.cat((idx, nxt), dim=1)
+        if cs is not None and cs.adjust:
+            ops.token_counts(nxt, 1, cs.V, cs.counts, accumulate=True)
+        return idx, nxt
+
     def generate(self, idx, max_new_tokens, generator: Optional[torch.Generator] = None, *, sampler: str = "host",
                  temperature: float = 1.0, top_k: Optional[int] = None, seed: Optional[int] = None,
-                 top_p: Optional[float] = None, min_p: Optional[float] = None):
+                 top_p: Optional[float] = None, min_p: Optional[float] = None, repetition_penalty: float = 1.0,
+                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, stop_tokens=None,
+                 pad_token: Optional[int] = None, stop_poll: int = 64):
         """ref: src/model.py:611-636.  sampler="host" (default): softmax runs on the GPU; torch.multinomial runs on the host CPU
         generator (the global one unless `generator` is given), as it does in the reference on CPU.  A temperature other than 1
         (0 = greedy) or a top_k filters the distribution on the GPU first (dg_sample_rows); so do top_p (nucleus: the most
         likely tokens whose mass reaches top_p, ties kept) and min_p (tokens at least min_p times as likely as the best one),
         applied after top_k (dg_sample_rows_nucleus).
         sampler="device": the tokens are drawn by dg_sample_rows from a counter-based stream keyed by `seed` (drawn once from the
-        CPU generator when None) and the sequence length, and never leave the GPU inside the loop."""
-        temperature, top_k = check_sampling_args(sampler, temperature, top_k, self.token_embedding_table.weight.shape[0])
+        CPU generator when None) and the sequence length, and never leave the GPU inside the loop.
+        Controls, all off by default, applied to the logits before the temperature (dg_sample_rows_control):
+        repetition_penalty (CTRL / HF: a seen token's logit is divided by it when positive, multiplied when not),
+        presence_penalty (subtracted once from a seen token) and frequency_penalty (subtracted per occurrence) act on the token
+        counts of the WHOLE sequence so far -- the prompt included, also what has left the context window, as HF's processors
+        see input_ids.  logit_bias: a {token: value} dict or vocab_size values added to the logits; -inf bans a token.
+        stop_tokens (an int or up to 8): a row that draws one keeps it, every later position of that row is pad_token (default: the
+        first stop token), and the result (B, t0 + n), n <= max_new_tokens, is trimmed to the longest row; before its stop a row
+        has the tokens of the same call without stop_tokens.  With the device sampler the host looks at the rows' state every
+        stop_poll tokens (the only sync; the result does not depend on it)."""
+        V = self.token_embedding_table.weight.shape[0]
+        temperature, top_k = check_sampling_args(sampler, temperature, top_k, V)
         top_p, min_p = check_nucleus_args(top_p, min_p)
+        ctl = check_control_args(repetition_penalty, presence_penalty, frequency_penalty, logit_bias, stop_tokens, pad_token,
+                                 stop_poll, V)
         if sampler == "device":
-            return self._generate_device(idx, max_new_tokens, generator, temperature, top_k, seed, top_p=top_p, min_p=min_p)
-        params = self._host_params(idx.device, temperature, top_k, top_p, min_p)
+            return self._generate_device(idx, max_new_tokens, generator, temperature, top_k, seed, top_p=top_p, min_p=min_p, ctl=ctl)
+        params = self._host_params(idx.device, temperature, top_k, top_p, min_p, ctl)
+        cs = None if ctl is None else _ControlOperands(ctl, idx, V, lengths=False)
+        return self._generate_host(idx, max_new_tokens, generator, params, cs)
+
+    def _generate_host(self, idx, max_new_tokens, generator, params, cs=None):
+        """the reference loop: full forward on the cropped window per token, one multinomial on the CPU generator per token"""
         for _ in range(max_new_tokens):
             cond = idx if self.context_length is None else idx[:, -self.context_length:]
-            probs = self._last_probs(cond.contiguous(), params)
-            nxt = torch.multinomial(probs.cpu(), num_samples=1, generator=generator)
-            idx = torch.cat((idx, nxt.to(idx.device)), dim=1)
+            probs = self._last_probs(cond.contiguous(), params, cs)
+            idx, _ = self._host_draw(probs, generator, idx, cs)
+            if cs is not None and cs.host_done():
+                break
         return idx
 
     def _decode_begin(self, idx, max_new_tokens, generator, temperature, top_k, seed, ids=None, top_p=None, min_p=None):
@@ -217,11 +375,16 @@ class _LM(HipModule):
         return ids, ops.new_rng_state(int(seed), idx.device, step=t0), params
 
     @torch.no_grad()
-    def _generate_device(self, idx, max_new_tokens, generator, temperature, top_k, seed, *, top_p=None, min_p=None):
+    def _generate_device(self, idx, max_new_tokens, generator, temperature, top_k, seed, *, top_p=None, min_p=None, ctl=None):
         """the reference algorithm (full forward on the cropped window per token) with the sampler on the device: the kernel writes
-        token L into ids[:, L]; no host copy or sync inside the loop (the ids were range-checked once, sampled ids are in range)."""
+        token L into ids[:, L]; no host copy or sync inside the loop (the ids were range-checked once, sampled ids are in range).
+        With stop tokens the host reads the rows' lengths every ctl["poll"] tokens and leaves once every row is finished."""
+        if ctl is not None:
+            top_p, min_p = 1.0 if top_p is None else top_p, 0.0 if min_p is None else min_p
         ids, state, params = self._decode_begin(idx, max_new_tokens, generator, temperature, top_k, seed, top_p=top_p, min_p=min_p)
         t0, ctx = idx.shape[1], self.context_length
+        cs = None if ctl is None else _ControlOperands(ctl, idx, self.token_embedding_table.weight.shape[0], lengths=True)
+        kw = {} if cs is None else cs.kw()
         had = "check_ids" in self.__dict__
         saved = self.check_ids
         self.check_ids = False
@@ -229,14 +392,16 @@ class _LM(HipModule):
             for L in range(t0, t0 + max_new_tokens):
                 lo = 0 if ctx is None else max(0, L - ctx)
                 logits, _ = self(ids[:, lo:L].contiguous())
-                ops.sample_rows(logits[:, -1, :], state, params, ids=ids)
+                ops.sample_rows(logits[:, -1, :], state, params, ids=ids, **kw)
                 ops.state_advance(state)
+                if cs is not None and cs.lengths is not None and (L + 1 - t0) % cs.poll == 0 and all_rows_finished(cs.lengths):
+                    break
         finally:
             if had:
                 self.check_ids = saved
             else:
                 del self.check_ids
-        return ids
+        return ids if cs is None else trim_to_longest(ids, cs.lengths, t0 + max_new_tokens)
 
 
 class BigramLM(_LM):
@@ -405,42 +570,51 @@ class TransformerLM(_BlocksLM):
 
     def generate(self, idx, max_new_tokens, generator: Optional[torch.Generator] = None, use_cache: bool = True, *,
                  sampler: str = "host", temperature: float = 1.0, top_k: Optional[int] = None, seed: Optional[int] = None,
-                 top_p: Optional[float] = None, min_p: Optional[float] = None):
+                 top_p: Optional[float] = None, min_p: Optional[float] = None, repetition_penalty: float = 1.0,
+                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, stop_tokens=None,
+                 pad_token: Optional[int] = None, stop_poll: int = 64):
         """ref: src/model.py:611-636.  While the sequence still fits the context window the per-layer K/V of the
         tokens seen so far are kept (training layout, [B, ctx, 3C]) and only the new position is computed; once the
         window starts to slide every position embedding shifts, the cache is void, and decoding continues exactly
         as the reference does (full forward on the cropped window).  Dropout is off in both paths only in eval()
         mode -- like the reference, train() mode samples with dropout through the uncached path.
-        sampler / temperature / top_k / seed / top_p / min_p: as in _LM.generate.  sampler="device" in eval() mode with
+        sampler / temperature / top_k / seed / top_p / min_p and the controls (repetition_penalty, presence_penalty,
+        frequency_penalty, logit_bias, stop_tokens, pad_token, stop_poll; counts cover the whole sequence so far, prompt
+        included and beyond the context window): as in _LM.generate.  sampler="device" in eval() mode with
         use_cache=True replays one captured graph per token (decode.DeviceDecoder): no host work inside the loop, and the same
-        graphs for every setting of the sampler."""
-        temperature, top_k = check_sampling_args(sampler, temperature, top_k, self.token_embedding_table.weight.shape[0])
+        graphs for every setting of the sampler; a call with any control replays a second pair of graphs, captured once, whose
+        sampler is dg_sample_rows_control."""
+        V = self.token_embedding_table.weight.shape[0]
+        temperature, top_k = check_sampling_args(sampler, temperature, top_k, V)
         top_p, min_p = check_nucleus_args(top_p, min_p)
-        kw = dict(sampler=sampler, temperature=temperature, top_k=top_k, seed=seed, top_p=top_p, min_p=min_p)
+        ctl = check_control_args(repetition_penalty, presence_penalty, frequency_penalty, logit_bias, stop_tokens, pad_token,
+                                 stop_poll, V)
         if sampler == "device":
             if not use_cache or self.training:
-                return self._generate_device(idx, max_new_tokens, generator, temperature, top_k, seed, top_p=top_p, min_p=min_p)
-            return self._generate_device_cached(idx, max_new_tokens, generator, temperature, top_k, seed, top_p=top_p, min_p=min_p)
+                return self._generate_device(idx, max_new_tokens, generator, temperature, top_k, seed, top_p=top_p, min_p=min_p, ctl=ctl)
+            return self._generate_device_cached(idx, max_new_tokens, generator, temperature, top_k, seed, top_p=top_p, min_p=min_p,
+                                                ctl=ctl)
+        params = self._host_params(idx.device, temperature, top_k, top_p, min_p, ctl)
         if not use_cache or self.training or idx.shape[1] >= self.context_length:
-            return super().generate(idx, max_new_tokens, generator, **kw)
+            cs = None if ctl is None else _ControlOperands(ctl, idx, V, lengths=False)
+            return self._generate_host(idx, max_new_tokens, generator, params, cs)
         B, t0 = idx.shape
         self._check_ids(idx, None)
-        params = self._host_params(idx.device, temperature, top_k, top_p, min_p)
+        cs = None if ctl is None else _ControlOperands(ctl, idx, V, lengths=False)
         C3 = 3 * self.token_embedding_table.weight.shape[1]
         ws, w_lm = self._decode_weights()
         caches = [torch.zeros((B, self.context_length, C3), dtype=self.act_dtype, device=idx.device) for _ in self.blocks]
         logits = self._prefill(idx.contiguous(), caches, ws, w_lm)      # the whole prompt in one pass
         produced = 0
         while produced < max_new_tokens:
-            probs = self._probs(logits, params)
-            nxt = torch.multinomial(probs.cpu(), num_samples=1, generator=generator).to(idx.device)
-            idx = torch.cat((idx, nxt), dim=1)
+            probs = self._probs(logits, params, cs)
+            idx, nxt = self._host_draw(probs, generator, idx, cs)
             produced += 1
-            if produced == max_new_tokens:
+            if produced == max_new_tokens or (cs is not None and cs.host_done()):
                 break
             t = idx.shape[1] - 1
             if t >= self.context_length:                         # window slides: fall back to the reference algorithm
-                return super().generate(idx, max_new_tokens - produced, generator, **kw)
+                return self._generate_host(idx, max_new_tokens - produced, generator, params, cs)
             logits = self._decode_step(nxt.contiguous(), t, caches, ws, w_lm)
         return idx
 
@@ -452,10 +626,12 @@ class TransformerLM(_BlocksLM):
 
     @torch.no_grad()
     def _generate_device_cached(self, idx, max_new_tokens, generator, temperature, top_k, seed, graph: bool = True, *,
-                                top_p=None, min_p=None):
+                                top_p=None, min_p=None, ctl=None):
         """eager one-pass prefill, sample, advance; then one step per token on the device position L: the K/V-cached step while
         L <= ctx, the full-window step after that.  graph=True replays the two captured graphs of decode.DeviceDecoder;
-        graph=False launches the very same steps eagerly."""
+        graph=False launches the very same steps eagerly.  ctl (check_control_args' dict): the steps end in
+        dg_sample_rows_control on the decoder's counts / lengths / bias / control block, and graph=True replays the decoder's
+        second pair of graphs; with stop tokens the host reads lengths every ctl["poll"] tokens."""
         from .decode import DeviceDecoder
         ops._chk(idx, "idx", torch.int64, contiguous=False)
         if idx.dim() != 2 or idx.shape[1] < 1:
@@ -468,23 +644,28 @@ class TransformerLM(_BlocksLM):
         if dec is None or dec.cap < total:
             dec = decs[key] = DeviceDecoder(self, B, idx.device, total)
         dec.refresh(self)                      # a generate() after an optimizer step sees the new weights
+        controls = ctl is not None
         if graph:
-            dec.capture()
+            dec.capture(controls)
         # the decoder's block always has four words (filters off: top_p 1, min_p 0), so one capture serves every setting
         _, state, params = self._decode_begin(idx, max_new_tokens, generator, temperature, top_k, seed, ids=dec.ids,
                                               top_p=1.0 if top_p is None else top_p, min_p=0.0 if min_p is None else min_p)
         dec.state.copy_(state)
         dec.params.copy_(params)
+        if controls:
+            dec.set_controls(new_control_block(ctl, idx.device), ctl["bias"], t0)
+        poll = ctl["poll"] if controls and ctl["stop"] else 0
         L = t0
         if max_new_tokens > 0 and t0 < ctx:
             logits = self._prefill(idx.contiguous(), dec.caches, dec.ws, dec.w_lm)
-            ops.sample_rows(logits, dec.state, dec.params, ids=dec.ids)
-            ops.state_advance(dec.state)
+            dec.tail(logits, controls)
             L += 1
         while L < total:
-            dec.step(cached=L <= ctx, graph=graph)
+            if poll and L > t0 and (L - t0) % poll == 0 and all_rows_finished(dec.lengths):
+                break
+            dec.step(cached=L <= ctx, graph=graph, controls=controls)
             L += 1
-        return dec.ids[:, :total].clone()
+        return trim_to_longest(dec.ids, dec.lengths if poll else None, total).clone()
 
 
 MODEL_CLASSES = OrderedDict(

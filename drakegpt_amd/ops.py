@@ -876,11 +876,54 @@ def new_sample_params(temperature: float, top_k: Optional[int], device, *, top_p
     return torch.tensor(words, dtype=torch.int32, device=device)
 
 
+SAMPLE_MAX_STOP = 8          # DG_SAMPLE_MAX_STOP
+SAMPLE_CONTROL_WORDS = 16
+
+
+def new_sample_control(*, repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
+                       stop_tokens=(), pad_token: Optional[int] = None, use_bias: bool = False, device=None) -> Tensor:
+    """the 16-word control block of dg_sample_rows_control as int32 bit patterns: {float inv_rep, float rep, float presence,
+    float frequency, int32 use_bias, int32 n_stop, int32 pad_id, 0, int32 stop[8]}.  inv_rep is 1 / rep rounded to fp32 once,
+    here; pad_token None = the first stop token (0 without one); unused stop slots hold -1."""
+    stop = [int(t) for t in stop_tokens]
+    if len(stop) > SAMPLE_MAX_STOP:
+        raise ValueError(f"new_sample_control: at most {SAMPLE_MAX_STOP} stop tokens, got {len(stop)}")
+    rep = float(repetition_penalty)
+    pad = int(pad_token) if pad_token is not None else (stop[0] if stop else 0)
+    words = [_f32_bits(1.0 / rep), _f32_bits(rep), _f32_bits(float(presence_penalty)), _f32_bits(float(frequency_penalty)),
+             int(bool(use_bias)), len(stop), pad, 0] + stop + [-1] * (SAMPLE_MAX_STOP - len(stop))
+    return torch.tensor(words, dtype=torch.int32, device=device)
+
+
+def token_counts(ids: Tensor, n: int, V: int, counts: Optional[Tensor] = None, accumulate: bool = False) -> Tensor:
+    """int32 [M, V] (or the given counts [M, >= V]): how often each token occurs in ids[m, :n] (dg_token_counts; ids int64 [M, cap],
+    rows may be strided, clamped to [0, V) as the embedding does).  accumulate=False zeroes the counts first."""
+    _chk(ids, "ids", torch.int64, contiguous=False)
+    if ids.dim() != 2 or ids.stride(1) != 1 or not 0 <= n <= ids.shape[1]:
+        raise RuntimeError("token_counts: ids must be [M, capacity >= n] with unit column stride")
+    M = ids.shape[0]
+    if counts is None:
+        if accumulate:
+            raise ValueError("token_counts: accumulate=True needs counts")
+        counts = torch.empty((M, V), dtype=torch.int32, device=ids.device)
+    _chk(counts, "counts", torch.int32, contiguous=False)
+    if counts.dim() != 2 or counts.shape[0] != M or counts.shape[1] < V or counts.stride(1) != 1:
+        raise RuntimeError(f"token_counts: counts must be int32 [M = {M}, >= V = {V}]")
+    check(lib.dg_token_counts(_p(ids), max(_ld(ids), n), M, int(n), int(V), _p(counts), _ld(counts), int(bool(accumulate)), _stream()),
+          "dg_token_counts")
+    return counts
+
+
 def sample_rows(logits: Tensor, state: Optional[Tensor] = None, params: Optional[Tensor] = None, *, seed: Optional[int] = None,
                 L: Optional[int] = None, temperature: float = 1.0, top_k: Optional[int] = None, ids: Optional[Tensor] = None,
-                tokens: bool = True, probs: bool = False, top_p: Optional[float] = None, min_p: Optional[float] = None):
+                tokens: bool = True, probs: bool = False, top_p: Optional[float] = None, min_p: Optional[float] = None,
+                control: Optional[Tensor] = None, bias: Optional[Tensor] = None, counts: Optional[Tensor] = None,
+                lengths: Optional[Tensor] = None):
     """one token per row of fp32 logits [M, V] (dg_sample_rows, or dg_sample_rows_nucleus when params has four words;
     include/drakegpt_hip.h states the semantics).
+    control: new_sample_control(...) -- dg_sample_rows_control: penalties on counts int32 [M, >= V] (the kernel adds the token
+    it writes), bias fp32 [V] (read when the block's use_bias is set), lengths int32 [M] (stop tokens; needs ids).  The
+    parameter block built here then always has four words.  Without control: bias / counts / lengths are refused.
     state: decode state int32[4] {seed_lo, seed_hi, L, 0} (new_rng_state(seed, device, step=L)); built from seed / L when None.
     params: new_sample_params(...); built from temperature / top_k / top_p / min_p when None.
     ids [B, cap] int64: row m's token is written to ids[m, L] by the kernel (nothing is returned for it); otherwise, with
@@ -893,9 +936,29 @@ def sample_rows(logits: Tensor, state: Optional[Tensor] = None, params: Optional
     want_tok = tokens or ids is not None
     if not want_tok and not probs:
         raise ValueError("sample_rows: nothing to compute (tokens=False, probs=False)")
+    if control is None and (bias is not None or counts is not None or lengths is not None):
+        raise ValueError("sample_rows: bias / counts / lengths need control=new_sample_control(...)")
     if params is None:
+        if control is not None:
+            top_p, min_p = 1.0 if top_p is None else top_p, 0.0 if min_p is None else min_p
         params = new_sample_params(temperature, top_k, logits.device, top_p=top_p, min_p=min_p)
     _chk(params, "params", torch.int32)
+    if control is not None:
+        _chk(control, "control", torch.int32)
+        if control.numel() != SAMPLE_CONTROL_WORDS or params.numel() != 4:
+            raise RuntimeError("sample_rows: control must hold 16 words and comes with the four-word params")
+        if bias is not None:
+            _chk(bias, "bias", torch.float32)
+            if bias.numel() != V:
+                raise RuntimeError(f"sample_rows: bias must be fp32 [V = {V}]")
+        if counts is not None:
+            _chk(counts, "counts", torch.int32, contiguous=False)
+            if counts.dim() != 2 or counts.shape[0] != M or counts.shape[1] < V or counts.stride(1) != 1:
+                raise RuntimeError(f"sample_rows: counts must be int32 [M = {M}, >= V = {V}]")
+        if lengths is not None:
+            _chk(lengths, "lengths", torch.int32)
+            if lengths.numel() != M or ids is None:
+                raise RuntimeError(f"sample_rows: lengths must be int32 [M = {M}] and needs ids=")
     if params.numel() not in (2, 4):
         raise RuntimeError("sample_rows: params must hold {inv_temp, top_k} or {inv_temp, top_k, top_p, min_p}")
     entry, name = (lib.dg_sample_rows, "dg_sample_rows") if params.numel() == 2 else (lib.dg_sample_rows_nucleus,
@@ -918,8 +981,14 @@ def sample_rows(logits: Tensor, state: Optional[Tensor] = None, params: Optional
         out_tok = torch.empty((M,), dtype=torch.int64, device=logits.device)
         tok_ptr = _p(out_tok)
     p_out = torch.empty((M, V), dtype=torch.float32, device=logits.device) if probs else None
-    check(entry(_p(logits), _ld(logits), M, V, _p(state) if want_tok else None, _p(params), tok_ptr, ld_ids, _p(p_out), V, _stream()),
-          name)
+    if control is not None:
+        ldc = 0 if counts is None else _ld(counts)
+        check(lib.dg_sample_rows_control(_p(logits), _ld(logits), M, V, _p(state) if want_tok else None, _p(params), tok_ptr, ld_ids,
+                                         _p(p_out), V, _p(control), _p(bias), _p(counts), ldc, _p(lengths), _stream()),
+              "dg_sample_rows_control")
+    else:
+        check(entry(_p(logits), _ld(logits), M, V, _p(state) if want_tok else None, _p(params), tok_ptr, ld_ids, _p(p_out), V, _stream()),
+              name)
     if out_tok is not None and probs:
         return out_tok, p_out
     return out_tok if out_tok is not None else p_out

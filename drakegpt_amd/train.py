@@ -215,6 +215,14 @@ def build_parser() -> argparse.ArgumentParser:
                     "reaches this share, in (0, 1] (default: off)")
     ap.add_argument("--min-p", type=float, default=None, help="keep only tokens at least this many times as likely as the best one, "
                     "in [0, 1] (default: off)")
+    ap.add_argument("--repetition-penalty", type=float, default=1.0, metavar="R", help="of that sample: divide (multiply, when "
+                    "negative) the logit of every token already in the sequence by R (default 1: off)")
+    ap.add_argument("--presence-penalty", type=float, default=0.0, metavar="A", help="subtract A from the logit of every token "
+                    "already in the sequence (default 0: off)")
+    ap.add_argument("--frequency-penalty", type=float, default=0.0, metavar="F", help="subtract F per earlier occurrence of a token "
+                    "from its logit (default 0: off)")
+    ap.add_argument("--stop-token", type=int, action="append", default=None, metavar="ID", help="end the sample at this token id "
+                    "(repeatable, up to 8; default: none)")
     ap.add_argument("--grad-clip", type=float, default=None, metavar="MAX_NORM",
                     help="clip the gradient to this global 2-norm before every AdamW step (ref: clip_grad_norm_; default: off); each "
                     "evaluation line then also reports the last step's pre-clip norm as grad_norm")
@@ -561,6 +569,9 @@ def main(argv=None):
         sample_kw = {}
         if (args.sampler, args.temperature, args.top_k, args.top_p, args.min_p) != ("host", 1.0, None, None, None):
             sample_kw = dict(sampler=args.sampler, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, min_p=args.min_p)
+        if (args.repetition_penalty, args.presence_penalty, args.frequency_penalty, args.stop_token) != (1.0, 0.0, 0.0, None):
+            sample_kw.update(repetition_penalty=args.repetition_penalty, presence_penalty=args.presence_penalty,
+                             frequency_penalty=args.frequency_penalty, stop_tokens=args.stop_token)
         path = get_model_path(args.model_dir, args.model, args.scale)
         # --ema-decay: the sample comes from the averaged weights, which are saved beside the raw checkpoint in its format
         with (averaged() if averaged is not None else contextlib.nullcontext()):

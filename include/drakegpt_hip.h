@@ -411,6 +411,42 @@ int dg_sample_rows(const float* logits, int64_t ldl, int M, int V, const uint32_
 int dg_sample_rows_nucleus(const float* logits, int64_t ldl, int M, int V, const uint32_t* state, const void* params,
                            int64_t* ids, int64_t ld_ids, float* probs, int64_t ldp, void* stream);
 
+/* dg_sample_rows_nucleus with repetition / presence / frequency penalties, a logit bias and stop tokens.  control (device, 16
+ * 32-bit words, read by the kernel so that one captured graph serves every setting):
+ *   {float inv_rep, float rep, float presence, float frequency, int32 use_bias, int32 n_stop, int32 pad_id, int32 reserved,
+ *    int32 stop[DG_SAMPLE_MAX_STOP]}
+ * bias: fp32 [V], read only when use_bias != 0.  counts: int32 [M, ldc], ldc >= V, nullable: counts[m, j] = how often token j
+ * occurs in row m's sequence so far, prompt included.  lengths: int32 [M], nullable: 0 = the row is running, else its final
+ * length, stop token included.
+ *   Every place where dg_sample_rows reads logits_i reads y_i instead; with c = counts[m, i] (0 without counts) each line is one
+ *   fp32 rounding, in this order:
+ *     y = c > 0 ? (x > 0 ? x * inv_rep : x * rep) : x      repetition penalty (CTRL, HF's repetition_penalty); inv_rep is
+ *                                                          fp32(1 / rep) made on the host: a correctly rounded product that
+ *                                                          numpy restates bit for bit, within one rounding of HF's x / rep
+ *     y = y - (c > 0 ? presence : 0)
+ *     y = y - frequency * (float)c
+ *     y = use_bias ? y + bias[i] : y                       a bias of -inf bans the token
+ *   Greedy, top-k, min-p, top-p, the fp64 sums, u, the token rule and the rows without a finite entry: as in
+ *   dg_sample_rows_nucleus on y.  With rep = inv_rep = 1, presence = frequency = 0 and use_bias = 0, y == x bit for bit.
+ * Only where the token t of row m is written (ids given, L < ld_ids or ld_ids == 0), the thread that writes it also does
+ *   counts[m, t] += 1 (one workgroup per row: a plain load, add and store), and with lengths and ld_ids > 0:
+ *   lengths[m] = L + 1 if t is one of stop[0 .. min(n_stop, DG_SAMPLE_MAX_STOP)).
+ * A row that arrives with lengths[m] != 0 is finished: pad_id goes to ids[m, L] (L < ld_ids), no logit is read, counts and
+ * lengths stay as they are (and its row of probs, if asked for, is not written).  With probs and no ids, counts is only read.
+ * Refused: a NULL control, counts with ldc < V, lengths without ids or with ld_ids == 0, and what dg_sample_rows_nucleus
+ * refuses.  No floating-point atomics: a pure function of (logits, state, params, control, bias, counts, lengths, row). */
+#define DG_SAMPLE_MAX_STOP 8
+int dg_sample_rows_control(const float* logits, int64_t ldl, int M, int V, const uint32_t* state, const void* params,
+                           int64_t* ids, int64_t ld_ids, float* probs, int64_t ldp, const void* control,
+                           const float* bias, int32_t* counts, int64_t ldc, int32_t* lengths, void* stream);
+
+/* Token counts for dg_sample_rows_control: counts[m, clamp(ids[m * ld_ids + j])] += 1 for j < n (n <= ld_ids), ids clamped to
+ * [0, V) as in dg_embed_fwd.  accumulate == 0: row m's V counts are zeroed first.  One workgroup per row (its own barrier
+ * orders the zeroes before the increments), integer atomics: the result does not depend on an order.  counts: int32 [M, ldc],
+ * ldc >= V; columns V..ldc-1 are never touched.  n == 0 with accumulate == 0 just zeroes. */
+int dg_token_counts(const int64_t* ids, int64_t ld_ids, int M, int n, int V, int32_t* counts, int64_t ldc,
+                    int accumulate, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Cross entropy, mean over rows -- ref: F.cross_entropy at src/model.py:604-607 (K16).
  * loss_rows[m] = logsumexp(logits[m,:]) - logits[m,target[m]].  If dlogits != NULL also writes

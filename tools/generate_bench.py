@@ -4,6 +4,7 @@ the reference's inference.py default, N = 1000 new tokens from a one-token promp
 
     python tools/generate_bench.py [--sampler host|device] [--precision fp32 bf16] [--batch 1] [--tokens 1000] [--repeats 3]
                                    [--top-p P] [--min-p P] [--vocab 80]
+                                   [--repetition-penalty R] [--presence-penalty A] [--frequency-penalty F]
 
 Two phases are reported separately.  With a one-token prompt the first ctx tokens are made while the sequence still fits the
 window (one prefill, then K/V-cached steps); the rest by the sliding-window algorithm (a full forward per token).  The first
@@ -11,7 +12,8 @@ phase is timed as a call that stops at ctx tokens, the second as the difference 
 per-call set-up cancels), each as the median of --repeats calls that alternate between the two lengths.
 --sampler host passes no keyword that an older generate() does not have, so this file also times a commit without the device
 sampler; --top-p / --min-p are passed only when given, for the same reason.  --vocab widens the vocabulary (50257: the sampler
-at a GPT-2 row).  One JSON line per precision.
+at a GPT-2 row).  The three penalty flags are passed only when given too: with one of them the device sampler replays the
+decoder's second pair of graphs (dg_sample_rows_control).  One JSON line per precision.
 """
 import argparse
 import json
@@ -37,6 +39,9 @@ def main():
     ap.add_argument("--top-p", type=float, default=None)
     ap.add_argument("--min-p", type=float, default=None)
     ap.add_argument("--vocab", type=int, default=80)
+    ap.add_argument("--repetition-penalty", type=float, default=None)
+    ap.add_argument("--presence-penalty", type=float, default=None)
+    ap.add_argument("--frequency-penalty", type=float, default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("generate_bench needs the GPU: a timing taken anywhere else says nothing")
@@ -49,6 +54,9 @@ def main():
         kw["top_p"] = args.top_p
     if args.min_p is not None:
         kw["min_p"] = args.min_p
+    for name in ("repetition_penalty", "presence_penalty", "frequency_penalty"):
+        if getattr(args, name) is not None:
+            kw[name] = getattr(args, name)
     for precision in args.precision:
         torch.manual_seed(42)
         m = D.TransformerLM(V, C, T, NH, NL, cfg["dropout"], precision=precision).to(dev).eval()
@@ -71,7 +79,8 @@ def main():
             full.append(timed(args.tokens))
         t_short, t_full = statistics.median(short), statistics.median(full)
         line = {"tool": "generate_bench", "sampler": args.sampler, "precision": precision, "batch": args.batch,
-                "vocab": V, "top_p": args.top_p, "min_p": args.min_p, "tokens": args.tokens, "ctx": T, "repeats": args.repeats,
+                "vocab": V, "top_p": args.top_p, "min_p": args.min_p, "repetition_penalty": args.repetition_penalty,
+                "presence_penalty": args.presence_penalty, "frequency_penalty": args.frequency_penalty, "tokens": args.tokens, "ctx": T, "repeats": args.repeats,
                 "total_s": round(t_full, 4), "total_tok_per_s": round(args.batch * args.tokens / t_full, 1),
                 "cached_tokens": n_cached, "cached_s": round(t_short, 4),
                 "cached_tok_per_s": round(args.batch * n_cached / t_short, 1),
