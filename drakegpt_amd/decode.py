@@ -9,6 +9,7 @@ it, the sampler writes token L into the ids buffer and dg_state_advance moves L 
       attn_decode_append / proj / LN / FFN, lm_head, sample_rows, state_advance
   graph B (sliding-window step, valid for L >= ctx): embed_window mode 1, the eval forward kernels at T = ctx
       (TransformerLM._forward_rows), lm_head on the last row, sample_rows, state_advance
+      Both walk the model's one layer stack (TransformerLM._layers); graph A passes it the attention step above.
 
 Graphs hold raw pointers, so the decoder owns every operand: staged copies of the weights (refreshed on every generate call),
 the K/V caches, the ids buffer, the state and the sampler parameters (always the four-word block of dg_sample_rows_nucleus:
@@ -27,6 +28,7 @@ import torch
 
 from . import ops
 from .engine import capture_after_warmup
+from .model import ControlOperands
 
 
 class DeviceDecoder:
@@ -34,8 +36,7 @@ class DeviceDecoder:
         ctx = model.context_length
         C = model.token_embedding_table.weight.shape[1]
         self.B, self.ctx, self.C = B, ctx, C
-        self.NH = len(model.blocks[0].sa_head.heads)
-        self.H = model.blocks[0].sa_head.heads[0].head_size
+        self.NH, self.H = model._heads()
         self.act, self.split = model.act_dtype, model.split_bf16
         self.device = device
         self._mref = weakref.ref(model)          # the model owns the decoder, not the other way round
@@ -45,20 +46,16 @@ class DeviceDecoder:
         self.ids = torch.zeros((B, self.cap), dtype=torch.int64, device=device)
         self.state = torch.zeros(4, dtype=torch.int32, device=device)
         # four words {inv_temp, top_k, top_p, min_p}: the captured sampler is dg_sample_rows_nucleus, whatever the call asks for
-        self.params = ops.new_sample_params(1.0, None, device, top_p=1.0, min_p=0.0)
+        self.params = ops.new_sample_params(1.0, None, device, four=True)
         self.caches = [torch.zeros((B, ctx, 3 * C), dtype=self.act, device=device) for _ in model.blocks]
         self.row = torch.zeros((B, 3 * C), dtype=self.act, device=device)       # staging: the new token's q/k/v
         self.ws = self.w_lm = self.tok = self.pos = self.lm_bias = None
         self.graphs = None
         # the operands of dg_sample_rows_control, the tail of the second pair of graphs (captured on the first call that asks for a
-        # penalty, a bias or a stop token): every call that uses them rewrites all four first (set_controls)
-        V = model.token_embedding_table.weight.shape[0]
-        self.control = ops.new_sample_control(device=device)
-        self.bias = torch.zeros(V, dtype=torch.float32, device=device)
-        self.counts = torch.zeros((B, V), dtype=torch.int32, device=device)
-        self.lengths = torch.zeros(B, dtype=torch.int32, device=device)
+        # penalty, a bias or a stop token): every call that uses them rewrites all four first (ControlOperands.begin)
+        self.operands = ControlOperands(B, model.token_embedding_table.weight.shape[0], device)
+        self.control, self.bias, self.counts, self.lengths = self.operands.kw().values()
         self.graphs_control = None
-        self._controls = False                 # which tail a step launches: set by capture() / step() / tail() around the step
 
     # ------------------------------------------------------------------ operands
     @torch.no_grad()
@@ -79,50 +76,24 @@ class DeviceDecoder:
                 d.copy_(s)
 
     # ------------------------------------------------------------------ the two steps
-    @torch.no_grad()
-    def set_controls(self, control, bias, t0: int) -> None:
-        """the start of a call with controls: the new block, the bias (a CPU tensor or None: zeros, and the block's use_bias is 0),
-        the counts of the prompt ids[:, :t0] and all rows running -- nothing is inherited from the previous call"""
-        self.control.copy_(control)
-        if bias is None:
-            self.bias.zero_()
-        else:
-            self.bias.copy_(bias)
-        ops.token_counts(self.ids, t0, self.counts.shape[1], self.counts)
-        self.lengths.zero_()
-
-    def _tail(self, logits) -> None:
-        if self._controls:
-            ops.sample_rows(logits, self.state, self.params, ids=self.ids, control=self.control, bias=self.bias, counts=self.counts,
-                            lengths=self.lengths)
-        else:
-            ops.sample_rows(logits, self.state, self.params, ids=self.ids)
+    def tail(self, logits, controls: bool = False) -> None:
+        """sample (controls: dg_sample_rows_control on the decoder's operands) and advance"""
+        ops.sample_rows(logits, self.state, self.params, ids=self.ids, **(self.operands.kw() if controls else {}))
         ops.state_advance(self.state)
 
-    def tail(self, logits, controls: bool = False) -> None:
-        """sample and advance on eager logits (the prefill's last row)"""
-        self._controls = controls
-        self._tail(logits)
-
-    def _step_cached(self) -> None:
+    def _step_cached(self, model, controls: bool) -> None:
         """TransformerLM._decode_step at the device position L - 1"""
-        act, sp = self.act, self.split
-        x = ops.embed_window(self.ids, self.state, self.tok, self.pos, 0)
-        for W, cache in zip(self.ws, self.caches):
-            h, _, _ = ops.layernorm_fwd(x, W["ln1w"], W["ln1b"], act)
-            ops.gemm_nt(h, W["wqkv"], act, out=self.row, split=sp)
-            o = ops.attn_decode_append(self.row, cache, self.state, self.NH, self.H, self.H ** -0.5)
-            x = ops.gemm_nt(o, W["wproj"], torch.float32, bias=W["bproj"], residual=x, split=sp)
-            h, _, _ = ops.layernorm_fwd(x, W["ln2w"], W["ln2b"], act)
-            f = ops.gemm_nt(h, W["w1"], act, bias=W["b1"], relu=True, split=sp)
-            x = ops.gemm_nt(f, W["w2"], torch.float32, bias=W["b2"], residual=x, split=sp)
-        xa = x if act == torch.float32 else ops.cast(x, act)
-        self._tail(ops.gemm_nt(xa, self.w_lm, torch.float32, bias=self.lm_bias, split=sp))
+        def attend(l, h, wqkv):
+            ops.gemm_nt(h, wqkv, self.act, out=self.row, split=self.split)
+            return ops.attn_decode_append(self.row, self.caches[l], self.state, self.NH, self.H, self.H ** -0.5)
 
-    def _step_window(self, model) -> None:
+        x = ops.embed_window(self.ids, self.state, self.tok, self.pos, 0)
+        self.tail(model._lm_logits(model._layers(x, self.ws, attend), self.w_lm, self.lm_bias), controls)
+
+    def _step_window(self, model, controls: bool) -> None:
         """the full forward on the last ctx tokens (the reference algorithm once the window slides)"""
         x = ops.embed_window(self.ids, self.state, self.tok, self.pos, 1).view(self.B * self.ctx, self.C)
-        self._tail(model._forward_rows(x, self.B, self.ctx, None, self.ws, self.w_lm, self.lm_bias))
+        self.tail(model._forward_rows(x, self.B, self.ctx, None, self.ws, self.w_lm, self.lm_bias), controls)
 
     # ------------------------------------------------------------------ capture / replay
     @torch.no_grad()
@@ -130,27 +101,23 @@ class DeviceDecoder:
         """capture both steps once, each after a warm-up run at its own position (engine.capture_after_warmup; the state word is put
         back in between).  A warm-up step writes cache row L - 1 and ids[:, L]: both are rewritten by the real step at that L before
         anything reads them.  controls=True: the second pair, the same steps ending in dg_sample_rows_control; its warm-up also
-        touches counts and lengths, which set_controls rewrites before every use."""
+        touches counts and lengths, which ControlOperands.begin rewrites before every use."""
         if (self.graphs_control if controls else self.graphs) is not None:
             return
-        self._controls = controls
         model = self._mref()
         graphs = []
-        for L, fn in ((1, self._step_cached), (self.ctx, lambda: self._step_window(model))):
+        for L, step in ((1, self._step_cached), (self.ctx, self._step_window)):
             def position(L=L):
                 self.state.copy_(ops.new_rng_state(0, self.device, step=L))
             position()
-            graphs += capture_after_warmup(self.device, [fn], position)
+            graphs += capture_after_warmup(self.device, [lambda step=step: step(model, controls)], position)
         if controls:
             self.graphs_control = tuple(graphs)
         else:
             self.graphs = tuple(graphs)
 
     def step(self, cached: bool, graph: bool = True, controls: bool = False) -> None:
-        self._controls = controls
         if graph:
             (self.graphs_control if controls else self.graphs)[0 if cached else 1].replay()
-        elif cached:
-            self._step_cached()
         else:
-            self._step_window(self._mref())
+            (self._step_cached if cached else self._step_window)(self._mref(), controls)

@@ -21,7 +21,7 @@ from __future__ import annotations
 import math
 import numbers
 from collections import OrderedDict
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -73,23 +73,25 @@ def check_sampling_args(sampler, temperature, top_k, vocab_size: int):
     return t, top_k
 
 
+def _number(x, name) -> float:
+    if isinstance(x, bool):
+        raise ValueError(f"generate: {name} must be a number, got {x!r}")
+    try:
+        return float(x)
+    except (TypeError, ValueError):
+        raise ValueError(f"generate: {name} must be a number, got {x!r}") from None
+
+
 def check_nucleus_args(top_p, min_p):
     """the checks of generate()'s top_p / min_p, like check_sampling_args: plain Python, raised before anything touches a
     device.  Returns (top_p, min_p) as floats, None where left out."""
-    def number(x, name):
-        if isinstance(x, bool):
-            raise ValueError(f"generate: {name} must be a number, got {x!r}")
-        try:
-            return float(x)
-        except (TypeError, ValueError):
-            raise ValueError(f"generate: {name} must be a number, got {x!r}") from None
     if top_p is not None:
-        p = number(top_p, "top_p")
+        p = _number(top_p, "top_p")
         if not (math.isfinite(p) and 0.0 < p <= 1.0):
             raise ValueError(f"generate: top_p must be in (0, 1] (or None), got {top_p!r}")
         top_p = p
     if min_p is not None:
-        p = number(min_p, "min_p")
+        p = _number(min_p, "min_p")
         if not 0.0 <= p <= 1.0:
             raise ValueError(f"generate: min_p must be in [0, 1] (or None), got {min_p!r}")
         min_p = p
@@ -103,14 +105,6 @@ def check_control_args(repetition_penalty, presence_penalty, frequency_penalty, 
     (a CPU fp32 tensor [V] or None), stop (a tuple of ints), pad (int), poll (int), adjust (bool: a penalty or a bias is on)."""
     V = int(vocab_size)
 
-    def number(x, name):
-        if isinstance(x, bool):
-            raise ValueError(f"generate: {name} must be a number, got {x!r}")
-        try:
-            return float(x)
-        except (TypeError, ValueError):
-            raise ValueError(f"generate: {name} must be a number, got {x!r}") from None
-
     def token(x, name):
         if isinstance(x, bool) or not isinstance(x, numbers.Integral):
             raise ValueError(f"generate: {name} must be an integer token id, got {x!r}")
@@ -118,11 +112,11 @@ def check_control_args(repetition_penalty, presence_penalty, frequency_penalty, 
             raise ValueError(f"generate: {name} must be in [0, {V}), got {x!r}")
         return int(x)
 
-    rep = number(repetition_penalty, "repetition_penalty")
+    rep = _number(repetition_penalty, "repetition_penalty")
     if not (math.isfinite(rep) and rep > 0.0):
         raise ValueError(f"generate: repetition_penalty must be finite and > 0, got {repetition_penalty!r}")
-    presence = number(presence_penalty, "presence_penalty")
-    frequency = number(frequency_penalty, "frequency_penalty")
+    presence = _number(presence_penalty, "presence_penalty")
+    frequency = _number(frequency_penalty, "frequency_penalty")
     if not (math.isfinite(presence) and math.isfinite(frequency)):
         raise ValueError("generate: presence_penalty and frequency_penalty must be finite")
     if isinstance(stop_poll, bool) or not isinstance(stop_poll, numbers.Integral) or stop_poll < 1:
@@ -132,7 +126,7 @@ def check_control_args(repetition_penalty, presence_penalty, frequency_penalty, 
         if isinstance(logit_bias, dict):
             bias = torch.zeros(V, dtype=torch.float32)
             for k, v in logit_bias.items():
-                bias[token(k, "a logit_bias token")] = number(v, "a logit_bias value")
+                bias[token(k, "a logit_bias token")] = _number(v, "a logit_bias value")
         else:
             try:
                 bias = torch.as_tensor(logit_bias).detach().to(device="cpu", dtype=torch.float32)
@@ -166,15 +160,10 @@ def check_control_args(repetition_penalty, presence_penalty, frequency_penalty, 
     return dict(rep=rep, presence=presence, frequency=frequency, bias=bias, stop=stop, pad=pad, poll=int(stop_poll), adjust=adjust)
 
 
-def new_control_block(ctl: dict, device) -> Tensor:
-    """check_control_args' dict as the device block of dg_sample_rows_control"""
-    return ops.new_sample_control(repetition_penalty=ctl["rep"], presence_penalty=ctl["presence"], frequency_penalty=ctl["frequency"],
-                                  stop_tokens=ctl["stop"], pad_token=ctl["pad"], use_bias=ctl["bias"] is not None, device=device)
-
-
-def all_rows_finished(lengths: Tensor) -> bool:
-    """the stop-token poll: one device-to-host read of lengths [B]"""
-    return bool((lengths != 0).all())
+def stop_poll_due(poll: int, produced: int, lengths: Optional[Tensor]) -> bool:
+    """the stop-poll rule of both device loops: every `poll` produced tokens (0: no stop tokens, never) one device-to-host read of
+    lengths [B] -- has every row finished?"""
+    return poll > 0 and produced % poll == 0 and bool((lengths != 0).all())
 
 
 def trim_to_longest(ids: Tensor, lengths: Optional[Tensor], total: int) -> Tensor:
@@ -185,37 +174,102 @@ def trim_to_longest(ids: Tensor, lengths: Optional[Tensor], total: int) -> Tenso
     return ids[:, :int(torch.where(n == 0, torch.full_like(n, total), n).max())]
 
 
-class _ControlOperands:
-    """what one generate() call with controls hands to ops.sample_rows: the control block, the bias, the token counts of the whole
-    sequence so far (prompt included, beyond the context window too) and, for the device sampler with stop tokens, lengths"""
+class ControlOperands:
+    """what a generate() call with controls hands to ops.sample_rows (dg_sample_rows_control): the 16-word control block, bias [V],
+    the token counts [B, V] of the whole sequence so far (prompt included, beyond the context window too; the kernel adds the token
+    it writes) and lengths [B], the rows' "finished" state under the device sampler's stop tokens.  The eager loops allocate one
+    per call (fresh); a DeviceDecoder keeps one for good, since its graphs hold the addresses.  begin() starts a call on either."""
 
-    def __init__(self, ctl: dict, idx: Tensor, V: int, lengths: bool):
-        self.stop, self.pad, self.poll, self.adjust = ctl["stop"], ctl["pad"], ctl["poll"], ctl["adjust"]
-        self.V = V
-        self.control = new_control_block(ctl, idx.device)
-        self.counts = ops.token_counts(idx, idx.shape[1], V)
-        self.bias = None if ctl["bias"] is None else ctl["bias"].to(idx.device)
-        self.lengths = torch.zeros(idx.shape[0], dtype=torch.int32, device=idx.device) if lengths and self.stop else None
-        self.finished = torch.zeros(idx.shape[0], dtype=torch.bool)          # the host sampler's own stop state
+    def __init__(self, B: int, V: int, device, bias: bool = True, lengths: bool = True):
+        self.control = ops.new_sample_control(device=device)          # controls off: what a capture's warm-up may safely run on
+        self.bias = torch.zeros(V, dtype=torch.float32, device=device) if bias else None
+        self.counts = torch.zeros((B, V), dtype=torch.int32, device=device)
+        self.lengths = torch.zeros(B, dtype=torch.int32, device=device) if lengths else None
+
+    @classmethod
+    def fresh(cls, ctl: Optional[dict], idx: Tensor, V: int, lengths: bool) -> Optional["ControlOperands"]:
+        """an eager call's own operands, begun on the prompt idx (None without controls): a bias and lengths only where it has them"""
+        if ctl is None:
+            return None
+        cs = cls(idx.shape[0], V, idx.device, bias=ctl["bias"] is not None, lengths=lengths and bool(ctl["stop"]))
+        cs.begin(ctl, idx, idx.shape[1])
+        return cs
+
+    @torch.no_grad()
+    def begin(self, ctl: dict, ids: Tensor, t0: int) -> None:
+        """the start of a call: the block of check_control_args' dict, its bias (None: zeros, and the block's use_bias is 0), the
+        counts of the prompt ids[:, :t0] and all rows running -- nothing is inherited from an earlier call"""
+        self.control.copy_(ops.new_sample_control(
+            repetition_penalty=ctl["rep"], presence_penalty=ctl["presence"], frequency_penalty=ctl["frequency"], stop_tokens=ctl["stop"],
+            pad_token=ctl["pad"], use_bias=ctl["bias"] is not None, device=self.control.device))
+        if self.bias is not None:
+            if ctl["bias"] is None:
+                self.bias.zero_()
+            else:
+                self.bias.copy_(ctl["bias"])
+        ops.token_counts(ids, t0, self.counts.shape[1], self.counts)
+        if self.lengths is not None:
+            self.lengths.zero_()
 
     def kw(self) -> dict:
         return dict(control=self.control, bias=self.bias, counts=self.counts, lengths=self.lengths)
-
-    def host_token(self, nxt: Tensor) -> Tensor:
-        """the host sampler's stop rule on the drawn column nxt [B, 1] (CPU): finished rows get pad_token, a row that draws a stop
-        token keeps it and is finished from the next position on"""
-        if self.stop:
-            nxt = torch.where(self.finished[:, None], torch.full_like(nxt, self.pad), nxt)
-            self.finished = self.finished | torch.isin(nxt[:, 0], torch.tensor(self.stop))
-        return nxt
-
-    def host_done(self) -> bool:
-        return bool(self.stop) and bool(self.finished.all())
 
 
 def draw_seed(generator: Optional[torch.Generator]) -> int:
     """one sampling seed from the CPU generator (the global one unless `generator` is given)"""
     return int(torch.randint(0, 2 ** 62, (1,), generator=generator))
+
+
+class Sampling(NamedTuple):
+    """one checked generate() request: what travels from generate() to the token loops.  Sampling.checked builds it from
+    generate()'s arguments; ctl is check_control_args' dict (None: every control off)."""
+    sampler: str = "host"
+    temperature: float = 1.0
+    top_k: Optional[int] = None
+    top_p: Optional[float] = None
+    min_p: Optional[float] = None
+    ctl: Optional[dict] = None
+    generator: Optional[torch.Generator] = None
+    seed: Optional[int] = None
+
+    @classmethod
+    def checked(cls, vocab_size: int, generator, sampler, temperature, top_k, seed, top_p, min_p, repetition_penalty, presence_penalty,
+                frequency_penalty, logit_bias, stop_tokens, pad_token, stop_poll) -> "Sampling":
+        """the argument checks of generate(), all of them: plain Python, raised before anything touches a device"""
+        temperature, top_k = check_sampling_args(sampler, temperature, top_k, vocab_size)
+        top_p, min_p = check_nucleus_args(top_p, min_p)
+        ctl = check_control_args(repetition_penalty, presence_penalty, frequency_penalty, logit_bias, stop_tokens, pad_token,
+                                 stop_poll, vocab_size)
+        return cls(sampler, temperature, top_k, top_p, min_p, ctl, generator, seed)
+
+    @property
+    def adjust(self) -> bool:
+        """a penalty or a bias is on: the logits change (stop tokens alone change no distribution)"""
+        return self.ctl is not None and self.ctl["adjust"]
+
+    @property
+    def stop(self) -> tuple:
+        return () if self.ctl is None else self.ctl["stop"]
+
+    @property
+    def poll(self) -> int:
+        """the device loops' stop_poll; 0 without stop tokens"""
+        return self.ctl["poll"] if self.stop else 0
+
+    def params(self, device, graph: bool = False) -> Optional[Tensor]:
+        """the parameter block of this request, and with it the kernel entry.  None: the plain softmax, the reference's distribution.
+        Four words {inv_temp, top_k, top_p, min_p} where dg_sample_rows_control runs (host: a penalty or a bias; device: any control,
+        a stop token alone included), for a DeviceDecoder's steps (graph: one capture serves every setting) and with a top_p or a
+        min_p; two words {inv_temp, top_k} otherwise."""
+        four = graph or (self.adjust if self.sampler == "host" else self.ctl is not None)
+        if self.sampler == "host" and not four and (self.temperature, self.top_k, self.top_p, self.min_p) == (1.0, None, None, None):
+            return None
+        return ops.new_sample_params(self.temperature, self.top_k, device, top_p=self.top_p, min_p=self.min_p, four=four)
+
+    def first_state(self, device, t0: int) -> Tensor:
+        """the device sampler's decode state at sequence length t0; the seed is drawn here, once, from the CPU generator if not given"""
+        seed = draw_seed(self.generator) if self.seed is None else self.seed
+        return ops.new_rng_state(int(seed), device, step=t0)
 
 
 class _LM(HipModule):
@@ -280,42 +334,20 @@ class _LM(HipModule):
         loss = self._loss(logits, targets.reshape(B * T))
         return logits, loss
 
-    @torch.no_grad()
-    def _last_probs(self, idx, params=None, cs=None):
-        logits, _ = self(idx)
-        return self._probs(logits[:, -1, :], params, cs)
+    def _window_logits(self, idx):
+        """the host loop's logits source of every model: the full forward on the cropped window, last position"""
+        cond = idx if self.context_length is None else idx[:, -self.context_length:]
+        logits, _ = self(cond.contiguous())
+        return logits[:, -1, :]
 
     @staticmethod
     def _probs(logits, params, cs=None):
         """params None: the plain softmax (the reference's distribution); else the temperature / top-k / top-p / min-p filtered one;
-        with cs (a _ControlOperands) the penalties and the bias are applied by the same kernel, which only reads the counts.
+        with cs (ControlOperands, given when a penalty or a bias is on) the same kernel applies those too and only reads the counts.
         Stop tokens alone change no distribution: the call a run without them makes, so the tokens before a stop are its tokens"""
-        if cs is not None and cs.adjust:
-            return ops.sample_rows(logits, params=params, tokens=False, probs=True, control=cs.control, bias=cs.bias, counts=cs.counts)
-        if params is None:
+        if cs is None and params is None:
             return ops.softmax_rows(logits)
-        return ops.sample_rows(logits, params=params, tokens=False, probs=True)
-
-    @staticmethod
-    def _host_params(device, temperature, top_k, top_p=None, min_p=None, ctl=None):
-        if ctl is not None and ctl["adjust"]:             # dg_sample_rows_control takes the four-word block
-            return ops.new_sample_params(temperature, top_k, device, top_p=1.0 if top_p is None else top_p,
-                                         min_p=0.0 if min_p is None else min_p)
-        if temperature == 1.0 and top_k is None and top_p is None and min_p is None:
-            return None
-        return ops.new_sample_params(temperature, top_k, device, top_p=top_p, min_p=min_p)
-
-    @staticmethod
-    def _host_draw(probs, generator, idx, cs):
-        """one column from the CPU generator (one multinomial per step, controls or not), appended to idx and counted"""
-        nxt = torch.multinomial(probs.cpu(), num_samples=1, generator=generator)
-        if cs is not None:
-            nxt = cs.host_token(nxt)
-        nxt = nxt.to(idx.device)
-        idx = torch.cat((idx, nxt), dim=1)
-        if cs is not None and cs.adjust:
-            ops.token_counts(nxt, 1, cs.V, cs.counts, accumulate=True)
-        return idx, nxt
+        return ops.sample_rows(logits, params=params, tokens=False, probs=True, **({} if cs is None else cs.kw()))
 
     def generate(self, idx, max_new_tokens, generator: Optional[torch.Generator] = None, *, sampler: str = "host",
                  temperature: float = 1.0, top_k: Optional[int] = None, seed: Optional[int] = None,
@@ -338,70 +370,75 @@ class _LM(HipModule):
         first stop token), and the result (B, t0 + n), n <= max_new_tokens, is trimmed to the longest row; before its stop a row
         has the tokens of the same call without stop_tokens.  With the device sampler the host looks at the rows' state every
         stop_poll tokens (the only sync; the result does not depend on it)."""
-        V = self.token_embedding_table.weight.shape[0]
-        temperature, top_k = check_sampling_args(sampler, temperature, top_k, V)
-        top_p, min_p = check_nucleus_args(top_p, min_p)
-        ctl = check_control_args(repetition_penalty, presence_penalty, frequency_penalty, logit_bias, stop_tokens, pad_token,
-                                 stop_poll, V)
-        if sampler == "device":
-            return self._generate_device(idx, max_new_tokens, generator, temperature, top_k, seed, top_p=top_p, min_p=min_p, ctl=ctl)
-        params = self._host_params(idx.device, temperature, top_k, top_p, min_p, ctl)
-        cs = None if ctl is None else _ControlOperands(ctl, idx, V, lengths=False)
-        return self._generate_host(idx, max_new_tokens, generator, params, cs)
+        req = Sampling.checked(self.token_embedding_table.weight.shape[0], generator, sampler, temperature, top_k, seed, top_p, min_p,
+                               repetition_penalty, presence_penalty, frequency_penalty, logit_bias, stop_tokens, pad_token, stop_poll)
+        return (self._generate_device if sampler == "device" else self._generate_host)(idx, max_new_tokens, req)
 
-    def _generate_host(self, idx, max_new_tokens, generator, params, cs=None):
-        """the reference loop: full forward on the cropped window per token, one multinomial on the CPU generator per token"""
+    @torch.no_grad()
+    def _generate_host(self, idx, max_new_tokens, req: Sampling, source=None):
+        """the host loop, the reference's: per token the last-position logits of the sequence so far from `source` (default: the
+        full forward on the cropped window), their distribution, ONE multinomial on the CPU generator, the stop rule, append,
+        count.  Stop rule: a finished row gets pad_token; a row that draws a stop token keeps it and is finished from the next
+        position on; the loop ends once every row is."""
+        V = self.token_embedding_table.weight.shape[0]
+        source = source or self._window_logits
+        params = req.params(idx.device)
+        cs = ControlOperands.fresh(req.ctl, idx, V, lengths=False)
+        finished = torch.zeros(idx.shape[0], dtype=torch.bool)
         for _ in range(max_new_tokens):
-            cond = idx if self.context_length is None else idx[:, -self.context_length:]
-            probs = self._last_probs(cond.contiguous(), params, cs)
-            idx, _ = self._host_draw(probs, generator, idx, cs)
-            if cs is not None and cs.host_done():
+            probs = self._probs(source(idx), params, cs if req.adjust else None)
+            nxt = torch.multinomial(probs.cpu(), num_samples=1, generator=req.generator)
+            if req.stop:
+                nxt = torch.where(finished[:, None], torch.full_like(nxt, req.ctl["pad"]), nxt)
+                finished = finished | torch.isin(nxt[:, 0], torch.tensor(req.stop))
+            nxt = nxt.to(idx.device)
+            idx = torch.cat((idx, nxt), dim=1)
+            if req.adjust:
+                ops.token_counts(nxt, 1, V, cs.counts, accumulate=True)
+            if req.stop and bool(finished.all()):
                 break
         return idx
 
-    def _decode_begin(self, idx, max_new_tokens, generator, temperature, top_k, seed, ids=None, top_p=None, min_p=None):
-        """shared start of the device-sampler paths: checks the prompt once, returns (ids buffer, decode state, params)"""
+    @staticmethod
+    def _prompt_shape(idx):          # the device-sampler paths' first check
         ops._chk(idx, "idx", torch.int64, contiguous=False)
         if idx.dim() != 2 or idx.shape[1] < 1:
             raise ValueError("idx must be (B, T) with T >= 1")
+        return idx.shape
+
+    def _decode_begin(self, idx, req: Sampling, ids, graph: bool = False):
+        """the device-sampler paths' start: the prompt is range-checked once and goes into ids; returns (decode state, params)"""
         self._check_ids(idx, None)
-        B, t0 = idx.shape
-        if seed is None:
-            seed = draw_seed(generator)
-        if ids is None:
-            ids = torch.zeros((B, t0 + max_new_tokens), dtype=torch.int64, device=idx.device)
-        ids[:, :t0] = idx
-        params = ops.new_sample_params(temperature, top_k, idx.device, top_p=top_p, min_p=min_p)
-        return ids, ops.new_rng_state(int(seed), idx.device, step=t0), params
+        ids[:, :idx.shape[1]] = idx
+        return req.first_state(idx.device, idx.shape[1]), req.params(idx.device, graph)
 
     @torch.no_grad()
-    def _generate_device(self, idx, max_new_tokens, generator, temperature, top_k, seed, *, top_p=None, min_p=None, ctl=None):
+    def _generate_device(self, idx, max_new_tokens, req: Sampling):
         """the reference algorithm (full forward on the cropped window per token) with the sampler on the device: the kernel writes
         token L into ids[:, L]; no host copy or sync inside the loop (the ids were range-checked once, sampled ids are in range).
-        With stop tokens the host reads the rows' lengths every ctl["poll"] tokens and leaves once every row is finished."""
-        if ctl is not None:
-            top_p, min_p = 1.0 if top_p is None else top_p, 0.0 if min_p is None else min_p
-        ids, state, params = self._decode_begin(idx, max_new_tokens, generator, temperature, top_k, seed, top_p=top_p, min_p=min_p)
-        t0, ctx = idx.shape[1], self.context_length
-        cs = None if ctl is None else _ControlOperands(ctl, idx, self.token_embedding_table.weight.shape[0], lengths=True)
+        With stop tokens the host reads the rows' lengths every req.poll tokens and leaves once every row is finished."""
+        B, t0 = self._prompt_shape(idx)
+        total, ctx = t0 + max_new_tokens, self.context_length
+        ids = torch.zeros((B, total), dtype=torch.int64, device=idx.device)
+        state, params = self._decode_begin(idx, req, ids)
+        cs = ControlOperands.fresh(req.ctl, idx, self.token_embedding_table.weight.shape[0], lengths=True)
         kw = {} if cs is None else cs.kw()
-        had = "check_ids" in self.__dict__
-        saved = self.check_ids
+        lengths = cs.lengths if req.poll else None
+        saved = self.__dict__.get("check_ids")           # None: the class's default is in force
         self.check_ids = False
         try:
-            for L in range(t0, t0 + max_new_tokens):
+            for L in range(t0, total):
                 lo = 0 if ctx is None else max(0, L - ctx)
                 logits, _ = self(ids[:, lo:L].contiguous())
                 ops.sample_rows(logits[:, -1, :], state, params, ids=ids, **kw)
                 ops.state_advance(state)
-                if cs is not None and cs.lengths is not None and (L + 1 - t0) % cs.poll == 0 and all_rows_finished(cs.lengths):
+                if stop_poll_due(req.poll, L + 1 - t0, lengths):
                     break
         finally:
-            if had:
+            del self.check_ids
+            if saved is not None:
                 self.check_ids = saved
-            else:
-                del self.check_ids
-        return ids if cs is None else trim_to_longest(ids, cs.lengths, t0 + max_new_tokens)
+        return trim_to_longest(ids, lengths, total)
 
 
 class BigramLM(_LM):
@@ -517,47 +554,56 @@ class TransformerLM(_BlocksLM):
                            b1=blk.ffwd.net[0].bias, w2=wp.fwd(blk.ffwd.net[2].weight), b2=blk.ffwd.net[2].bias))
         return ws, wp.fwd(self.lm_head.weight)
 
-    @torch.no_grad()
-    def _decode_step(self, tok_col, t, caches, ws, w_lm):
-        """logits (B, V) of the token at position t; K/V of position t are appended to the caches."""
-        act = self.act_dtype
-        sp = self.split_bf16          # precision bf16x3: split-bf16 contractions
-        B = tok_col.shape[0]
-        NH = len(self.blocks[0].sa_head.heads)
-        H = self.blocks[0].sa_head.heads[0].head_size
-        x = ops.embed_fwd(tok_col, self.token_embedding_table.weight, self.position_embedding_table.weight[t:t + 1]).view(B, -1)
-        for W, cache in zip(ws, caches):
+    def _heads(self):
+        """(number of heads, head size)"""
+        heads = self.blocks[0].sa_head.heads
+        return len(heads), heads[0].head_size
+
+    def _layers(self, x, ws, attend):
+        """the layer stack on the fp32 rows x, written once: per layer LN, attend(l, h, wqkv) -- the QKV GEMM and the attention of
+        the caller's kind, on the normalised rows h -- proj + residual, LN, FFN + residual"""
+        act, sp = self.act_dtype, self.split_bf16          # precision bf16x3: split-bf16 contractions
+        for l, W in enumerate(ws):
             h, _, _ = ops.layernorm_fwd(x, W["ln1w"], W["ln1b"], act)
-            ops.gemm_nt(h, W["wqkv"], act, out=cache[:, t], split=sp)             # q/k/v row t straight into the cache
-            o = ops.attn_decode(cache, t, NH, H, H ** -0.5)
+            o = attend(l, h, W["wqkv"])
             x = ops.gemm_nt(o, W["wproj"], torch.float32, bias=W["bproj"], residual=x, split=sp)
             h, _, _ = ops.layernorm_fwd(x, W["ln2w"], W["ln2b"], act)
             f = ops.gemm_nt(h, W["w1"], act, bias=W["b1"], relu=True, split=sp)
             x = ops.gemm_nt(f, W["w2"], torch.float32, bias=W["b2"], residual=x, split=sp)
-        xa = x if act == torch.float32 else ops.cast(x, act)
-        return ops.gemm_nt(xa, w_lm, torch.float32, bias=self.lm_head.bias, split=sp)
+        return x
+
+    def _lm_logits(self, x, w_lm, lm_bias=None):
+        """the cast and lm_head on the rows x (B, C) -> fp32 logits (B, V); lm_bias: a staged copy to use in place of lm_head.bias"""
+        xa = x if self.act_dtype == torch.float32 else ops.cast(x, self.act_dtype)
+        return ops.gemm_nt(xa, w_lm, torch.float32, bias=self.lm_head.bias if lm_bias is None else lm_bias, split=self.split_bf16)
+
+    @torch.no_grad()
+    def _decode_step(self, tok_col, t, caches, ws, w_lm):
+        """logits (B, V) of the token at position t; K/V of position t are appended to the caches."""
+        NH, H = self._heads()
+
+        def attend(l, h, wqkv):
+            ops.gemm_nt(h, wqkv, self.act_dtype, out=caches[l][:, t], split=self.split_bf16)      # q/k/v row t straight into the cache
+            return ops.attn_decode(caches[l], t, NH, H, H ** -0.5)
+
+        B = tok_col.shape[0]
+        x = ops.embed_fwd(tok_col, self.token_embedding_table.weight, self.position_embedding_table.weight[t:t + 1]).view(B, -1)
+        return self._lm_logits(self._layers(x, ws, attend), w_lm)
 
     @torch.no_grad()
     def _forward_rows(self, x, B, T, caches, ws, w_lm, lm_bias=None):
         """x (B*T, C), the embedded rows of B sequences of T positions -> logits (B, V) of every sequence's last position, through
         the training-forward kernels; caches (nullable): every layer's q/k/v rows [0, T) are also left in its K/V cache."""
-        act = self.act_dtype
-        sp = self.split_bf16          # precision bf16x3: split-bf16 contractions
-        NH = len(self.blocks[0].sa_head.heads)
-        H = self.blocks[0].sa_head.heads[0].head_size
-        for l, W in enumerate(ws):
-            h, _, _ = ops.layernorm_fwd(x, W["ln1w"], W["ln1b"], act)
-            qkv = ops.gemm_nt(h, W["wqkv"], act, split=sp)
+        NH, H = self._heads()
+
+        def attend(l, h, wqkv):
+            qkv = ops.gemm_nt(h, wqkv, self.act_dtype, split=self.split_bf16)
             if caches is not None:
                 caches[l][:, :T].copy_(qkv.view(B, T, -1))
-            o, _ = ops.attn_fwd(qkv, B, T, NH, H, H ** -0.5, 0.0, None, 0)
-            x = ops.gemm_nt(o, W["wproj"], torch.float32, bias=W["bproj"], residual=x, split=sp)
-            h, _, _ = ops.layernorm_fwd(x, W["ln2w"], W["ln2b"], act)
-            f = ops.gemm_nt(h, W["w1"], act, bias=W["b1"], relu=True, split=sp)
-            x = ops.gemm_nt(f, W["w2"], torch.float32, bias=W["b2"], residual=x, split=sp)
-        last = x.view(B, T, -1)[:, -1].contiguous()
-        xa = last if act == torch.float32 else ops.cast(last, act)
-        return ops.gemm_nt(xa, w_lm, torch.float32, bias=self.lm_head.bias if lm_bias is None else lm_bias, split=sp)
+            return ops.attn_fwd(qkv, B, T, NH, H, H ** -0.5, 0.0, None, 0)[0]
+
+        x = self._layers(x, ws, attend)
+        return self._lm_logits(x.view(B, T, -1)[:, -1].contiguous(), w_lm, lm_bias)
 
     @torch.no_grad()
     def _prefill(self, idx, caches, ws, w_lm):
@@ -567,6 +613,25 @@ class TransformerLM(_BlocksLM):
         B, t0 = idx.shape
         x = ops.embed_fwd(idx, self.token_embedding_table.weight, self.position_embedding_table.weight).view(B * t0, -1)
         return self._forward_rows(x, B, t0, caches, ws, w_lm)
+
+    def _kv_logits(self, prompt):
+        """the host loop's second logits source: the prompt's prefill on the first call, then one K/V-cached step per token while
+        the sequence fits the context window; once the window slides every position embedding shifts, the cache is void, and
+        the source hands over to the full forward on the cropped window for good"""
+        self._check_ids(prompt, None)
+        kv = []                                   # (caches, ws, w_lm), made with the prefill
+
+        def source(idx):
+            t = idx.shape[1] - 1
+            if t >= self.context_length:
+                return self._window_logits(idx)
+            if kv:
+                return self._decode_step(idx[:, -1:].contiguous(), t, *kv)
+            ws, w_lm = self._decode_weights()
+            shape = (idx.shape[0], self.context_length, 3 * self.token_embedding_table.weight.shape[1])
+            kv.extend(([torch.zeros(shape, dtype=self.act_dtype, device=idx.device) for _ in self.blocks], ws, w_lm))
+            return self._prefill(idx.contiguous(), *kv)      # the whole prompt in one pass
+        return source
 
     def generate(self, idx, max_new_tokens, generator: Optional[torch.Generator] = None, use_cache: bool = True, *,
                  sampler: str = "host", temperature: float = 1.0, top_k: Optional[int] = None, seed: Optional[int] = None,
@@ -584,39 +649,14 @@ class TransformerLM(_BlocksLM):
         use_cache=True replays one captured graph per token (decode.DeviceDecoder): no host work inside the loop, and the same
         graphs for every setting of the sampler; a call with any control replays a second pair of graphs, captured once, whose
         sampler is dg_sample_rows_control."""
-        V = self.token_embedding_table.weight.shape[0]
-        temperature, top_k = check_sampling_args(sampler, temperature, top_k, V)
-        top_p, min_p = check_nucleus_args(top_p, min_p)
-        ctl = check_control_args(repetition_penalty, presence_penalty, frequency_penalty, logit_bias, stop_tokens, pad_token,
-                                 stop_poll, V)
+        req = Sampling.checked(self.token_embedding_table.weight.shape[0], generator, sampler, temperature, top_k, seed, top_p, min_p,
+                               repetition_penalty, presence_penalty, frequency_penalty, logit_bias, stop_tokens, pad_token, stop_poll)
+        cached = use_cache and not self.training
         if sampler == "device":
-            if not use_cache or self.training:
-                return self._generate_device(idx, max_new_tokens, generator, temperature, top_k, seed, top_p=top_p, min_p=min_p, ctl=ctl)
-            return self._generate_device_cached(idx, max_new_tokens, generator, temperature, top_k, seed, top_p=top_p, min_p=min_p,
-                                                ctl=ctl)
-        params = self._host_params(idx.device, temperature, top_k, top_p, min_p, ctl)
-        if not use_cache or self.training or idx.shape[1] >= self.context_length:
-            cs = None if ctl is None else _ControlOperands(ctl, idx, V, lengths=False)
-            return self._generate_host(idx, max_new_tokens, generator, params, cs)
-        B, t0 = idx.shape
-        self._check_ids(idx, None)
-        cs = None if ctl is None else _ControlOperands(ctl, idx, V, lengths=False)
-        C3 = 3 * self.token_embedding_table.weight.shape[1]
-        ws, w_lm = self._decode_weights()
-        caches = [torch.zeros((B, self.context_length, C3), dtype=self.act_dtype, device=idx.device) for _ in self.blocks]
-        logits = self._prefill(idx.contiguous(), caches, ws, w_lm)      # the whole prompt in one pass
-        produced = 0
-        while produced < max_new_tokens:
-            probs = self._probs(logits, params, cs)
-            idx, nxt = self._host_draw(probs, generator, idx, cs)
-            produced += 1
-            if produced == max_new_tokens or (cs is not None and cs.host_done()):
-                break
-            t = idx.shape[1] - 1
-            if t >= self.context_length:                         # window slides: fall back to the reference algorithm
-                return self._generate_host(idx, max_new_tokens - produced, generator, params, cs)
-            logits = self._decode_step(nxt.contiguous(), t, caches, ws, w_lm)
-        return idx
+            return (self._generate_device_cached if cached else self._generate_device)(idx, max_new_tokens, req)
+        if cached and idx.shape[1] < self.context_length:
+            return self._generate_host(idx, max_new_tokens, req, self._kv_logits(idx))
+        return self._generate_host(idx, max_new_tokens, req)
 
     # ------------------------------------------------------------------ graph-replayed decoding (sampler="device")
     def __getstate__(self):
@@ -625,18 +665,14 @@ class TransformerLM(_BlocksLM):
         return d
 
     @torch.no_grad()
-    def _generate_device_cached(self, idx, max_new_tokens, generator, temperature, top_k, seed, graph: bool = True, *,
-                                top_p=None, min_p=None, ctl=None):
+    def _generate_device_cached(self, idx, max_new_tokens, req: Sampling, graph: bool = True):
         """eager one-pass prefill, sample, advance; then one step per token on the device position L: the K/V-cached step while
         L <= ctx, the full-window step after that.  graph=True replays the two captured graphs of decode.DeviceDecoder;
-        graph=False launches the very same steps eagerly.  ctl (check_control_args' dict): the steps end in
-        dg_sample_rows_control on the decoder's counts / lengths / bias / control block, and graph=True replays the decoder's
-        second pair of graphs; with stop tokens the host reads lengths every ctl["poll"] tokens."""
+        graph=False launches the very same steps eagerly.  With a control the steps end in dg_sample_rows_control on the decoder's
+        operands, and graph=True replays the decoder's second pair of graphs; with stop tokens the host reads lengths every
+        req.poll tokens."""
         from .decode import DeviceDecoder
-        ops._chk(idx, "idx", torch.int64, contiguous=False)
-        if idx.dim() != 2 or idx.shape[1] < 1:
-            raise ValueError("idx must be (B, T) with T >= 1")
-        B, t0 = idx.shape
+        B, t0 = self._prompt_shape(idx)
         total, ctx = t0 + max_new_tokens, self.context_length
         key = (B, idx.device, self.act_dtype, self.split_bf16)
         decs = self.__dict__.setdefault("_decoders", {})
@@ -644,28 +680,23 @@ class TransformerLM(_BlocksLM):
         if dec is None or dec.cap < total:
             dec = decs[key] = DeviceDecoder(self, B, idx.device, total)
         dec.refresh(self)                      # a generate() after an optimizer step sees the new weights
-        controls = ctl is not None
+        controls = req.ctl is not None
         if graph:
             dec.capture(controls)
-        # the decoder's block always has four words (filters off: top_p 1, min_p 0), so one capture serves every setting
-        _, state, params = self._decode_begin(idx, max_new_tokens, generator, temperature, top_k, seed, ids=dec.ids,
-                                              top_p=1.0 if top_p is None else top_p, min_p=0.0 if min_p is None else min_p)
+        state, params = self._decode_begin(idx, req, dec.ids, graph=True)      # the decoder's block: four words, replayed or not
         dec.state.copy_(state)
         dec.params.copy_(params)
         if controls:
-            dec.set_controls(new_control_block(ctl, idx.device), ctl["bias"], t0)
-        poll = ctl["poll"] if controls and ctl["stop"] else 0
+            dec.operands.begin(req.ctl, dec.ids, t0)
+        lengths = dec.lengths if req.poll else None
         L = t0
         if max_new_tokens > 0 and t0 < ctx:
-            logits = self._prefill(idx.contiguous(), dec.caches, dec.ws, dec.w_lm)
-            dec.tail(logits, controls)
+            dec.tail(self._prefill(idx.contiguous(), dec.caches, dec.ws, dec.w_lm), controls)
             L += 1
-        while L < total:
-            if poll and L > t0 and (L - t0) % poll == 0 and all_rows_finished(dec.lengths):
-                break
+        while L < total and not (L > t0 and stop_poll_due(req.poll, L - t0, lengths)):
             dec.step(cached=L <= ctx, graph=graph, controls=controls)
             L += 1
-        return trim_to_longest(dec.ids, dec.lengths if poll else None, total).clone()
+        return trim_to_longest(dec.ids, lengths, total).clone()
 
 
 MODEL_CLASSES = OrderedDict(

@@ -863,14 +863,15 @@ def _f32_bits(x: float) -> int:
 
 
 def new_sample_params(temperature: float, top_k: Optional[int], device, *, top_p: Optional[float] = None,
-                      min_p: Optional[float] = None) -> Tensor:
+                      min_p: Optional[float] = None, four: bool = False) -> Tensor:
     """device {float inv_temp, int32 top_k} of sample_rows (stored as two int32 bit patterns).  temperature 0 = greedy
     (inv_temp 0); top_k None / 0 = off.  inv_temp is 1 / temperature rounded to fp32.
-    With a top_p or a min_p: the four-word block {inv_temp, top_k, float top_p, float min_p} of dg_sample_rows_nucleus
-    (top_p None = 1 = off, min_p None = 0 = off)."""
+    With a top_p or a min_p, or with four=True (what dg_sample_rows_control and a captured sampler take): the four-word block
+    {inv_temp, top_k, float top_p, float min_p} of dg_sample_rows_nucleus (top_p None = 1 = off, min_p None = 0 = off: the one
+    place where that is filled in)."""
     inv = 0.0 if temperature == 0 else 1.0 / float(temperature)
     words = [_f32_bits(inv), int(top_k or 0)]
-    if top_p is not None or min_p is not None:
+    if four or top_p is not None or min_p is not None:
         # a top_p below the smallest fp32 must not round to 0, which the kernel takes as "off": it keeps the maximum alone
         words += [_f32_bits(1.0 if top_p is None else max(float(top_p), 2.0 ** -149)), _f32_bits(0.0 if min_p is None else float(min_p))]
     return torch.tensor(words, dtype=torch.int32, device=device)
@@ -895,6 +896,12 @@ def new_sample_control(*, repetition_penalty: float = 1.0, presence_penalty: flo
     return torch.tensor(words, dtype=torch.int32, device=device)
 
 
+def _chk_counts(what: str, counts: Tensor, M: int, V: int) -> None:
+    _chk(counts, "counts", torch.int32, contiguous=False)
+    if counts.dim() != 2 or counts.shape[0] != M or counts.shape[1] < V or counts.stride(1) != 1:
+        raise RuntimeError(f"{what}: counts must be int32 [M = {M}, >= V = {V}]")
+
+
 def token_counts(ids: Tensor, n: int, V: int, counts: Optional[Tensor] = None, accumulate: bool = False) -> Tensor:
     """int32 [M, V] (or the given counts [M, >= V]): how often each token occurs in ids[m, :n] (dg_token_counts; ids int64 [M, cap],
     rows may be strided, clamped to [0, V) as the embedding does).  accumulate=False zeroes the counts first."""
@@ -906,9 +913,7 @@ def token_counts(ids: Tensor, n: int, V: int, counts: Optional[Tensor] = None, a
         if accumulate:
             raise ValueError("token_counts: accumulate=True needs counts")
         counts = torch.empty((M, V), dtype=torch.int32, device=ids.device)
-    _chk(counts, "counts", torch.int32, contiguous=False)
-    if counts.dim() != 2 or counts.shape[0] != M or counts.shape[1] < V or counts.stride(1) != 1:
-        raise RuntimeError(f"token_counts: counts must be int32 [M = {M}, >= V = {V}]")
+    _chk_counts("token_counts", counts, M, V)
     check(lib.dg_token_counts(_p(ids), max(_ld(ids), n), M, int(n), int(V), _p(counts), _ld(counts), int(bool(accumulate)), _stream()),
           "dg_token_counts")
     return counts
@@ -939,9 +944,7 @@ def sample_rows(logits: Tensor, state: Optional[Tensor] = None, params: Optional
     if control is None and (bias is not None or counts is not None or lengths is not None):
         raise ValueError("sample_rows: bias / counts / lengths need control=new_sample_control(...)")
     if params is None:
-        if control is not None:
-            top_p, min_p = 1.0 if top_p is None else top_p, 0.0 if min_p is None else min_p
-        params = new_sample_params(temperature, top_k, logits.device, top_p=top_p, min_p=min_p)
+        params = new_sample_params(temperature, top_k, logits.device, top_p=top_p, min_p=min_p, four=control is not None)
     _chk(params, "params", torch.int32)
     if control is not None:
         _chk(control, "control", torch.int32)
@@ -952,17 +955,15 @@ def sample_rows(logits: Tensor, state: Optional[Tensor] = None, params: Optional
             if bias.numel() != V:
                 raise RuntimeError(f"sample_rows: bias must be fp32 [V = {V}]")
         if counts is not None:
-            _chk(counts, "counts", torch.int32, contiguous=False)
-            if counts.dim() != 2 or counts.shape[0] != M or counts.shape[1] < V or counts.stride(1) != 1:
-                raise RuntimeError(f"sample_rows: counts must be int32 [M = {M}, >= V = {V}]")
+            _chk_counts("sample_rows", counts, M, V)
         if lengths is not None:
             _chk(lengths, "lengths", torch.int32)
             if lengths.numel() != M or ids is None:
                 raise RuntimeError(f"sample_rows: lengths must be int32 [M = {M}] and needs ids=")
     if params.numel() not in (2, 4):
         raise RuntimeError("sample_rows: params must hold {inv_temp, top_k} or {inv_temp, top_k, top_p, min_p}")
-    entry, name = (lib.dg_sample_rows, "dg_sample_rows") if params.numel() == 2 else (lib.dg_sample_rows_nucleus,
-                                                                                      "dg_sample_rows_nucleus")
+    # the one place that picks the entry, from (control given, block length); control takes its four operands after the rest
+    name = "dg_sample_rows_control" if control is not None else "dg_sample_rows" if params.numel() == 2 else "dg_sample_rows_nucleus"
     if want_tok:
         if state is None:
             if seed is None or L is None:
@@ -981,14 +982,9 @@ def sample_rows(logits: Tensor, state: Optional[Tensor] = None, params: Optional
         out_tok = torch.empty((M,), dtype=torch.int64, device=logits.device)
         tok_ptr = _p(out_tok)
     p_out = torch.empty((M, V), dtype=torch.float32, device=logits.device) if probs else None
-    if control is not None:
-        ldc = 0 if counts is None else _ld(counts)
-        check(lib.dg_sample_rows_control(_p(logits), _ld(logits), M, V, _p(state) if want_tok else None, _p(params), tok_ptr, ld_ids,
-                                         _p(p_out), V, _p(control), _p(bias), _p(counts), ldc, _p(lengths), _stream()),
-              "dg_sample_rows_control")
-    else:
-        check(entry(_p(logits), _ld(logits), M, V, _p(state) if want_tok else None, _p(params), tok_ptr, ld_ids, _p(p_out), V, _stream()),
-              name)
+    extra = () if control is None else (_p(control), _p(bias), _p(counts), 0 if counts is None else _ld(counts), _p(lengths))
+    check(getattr(lib, name)(_p(logits), _ld(logits), M, V, _p(state) if want_tok else None, _p(params), tok_ptr, ld_ids, _p(p_out), V,
+                             *extra, _stream()), name)
     if out_tok is not None and probs:
         return out_tok, p_out
     return out_tok if out_tok is not None else p_out

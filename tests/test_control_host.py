@@ -123,6 +123,36 @@ def test_control_block_packing():
     assert ops.new_sample_params(0.5, 40, cpu).tolist() == [_bits(2.0), 40]
 
 
+def test_the_request_picks_the_parameter_block():
+    """which block, and so which kernel entry, a generate() call gets: one assertion per row of the table (None: ops.softmax_rows;
+    two words: dg_sample_rows; four: dg_sample_rows_nucleus, or dg_sample_rows_control where the operands go with it)"""
+    from drakegpt_amd.model import Sampling
+    cpu = torch.device("cpu")
+
+    def block(sampler, graph=False, **kw):
+        args = dict(temperature=1.0, top_k=None, seed=None, top_p=None, min_p=None, repetition_penalty=1.0, presence_penalty=0.0,
+                    frequency_penalty=0.0, logit_bias=None, stop_tokens=None, pad_token=None, stop_poll=64)
+        assert set(kw) <= set(args)
+        p = Sampling.checked(80, None, sampler, *dict(args, **kw).values()).params(cpu, graph)
+        return None if p is None else p.tolist()
+
+    one, off = _bits(1.0), [_bits(1.0), 0]                     # top_p 1.0 and min_p 0.0: the filters filled in as "off"
+    # host; temperature 1, no top_k / top_p / min_p; no penalty or bias (stop tokens alone count as none): no block
+    assert block("host") is None and block("host", stop_tokens=[3, 4], pad_token=0) is None
+    # host; temperature or top_k only: two words
+    assert block("host", temperature=0.5) == [_bits(2.0), 0] and block("host", top_k=7, stop_tokens=3) == [one, 7]
+    # host; a top_p or a min_p: four words
+    assert block("host", top_p=0.9) == [one, 0, _bits(0.9), 0] and block("host", temperature=0.5, min_p=0.1) == [_bits(2.0), 0, one, _bits(0.1)]
+    # host; a penalty or a bias: four words, filters filled with 1.0 / 0.0
+    assert block("host", repetition_penalty=1.3) == [one, 0] + off and block("host", top_k=5, logit_bias={3: -INF}) == [one, 5] + off
+    # device, eager, no controls: two words, or four with a top_p / min_p
+    assert block("device") == [one, 0] and block("device", top_k=9, min_p=0.2) == [one, 9, one, _bits(0.2)]
+    # device, eager, any control (a stop token alone included): four words
+    assert block("device", stop_tokens=3) == [one, 0] + off and block("device", frequency_penalty=0.5, top_p=0.5) == [one, 0, _bits(0.5), 0]
+    # device, graph: always four words
+    assert block("device", graph=True) == [one, 0] + off and block("device", graph=True, temperature=0.0, top_k=3) == [0, 3] + off
+
+
 A = 0x10000          # a made-up aligned address: nothing is dereferenced on the host, and nothing may be launched
 
 

@@ -278,13 +278,13 @@ def restated(m, idx, seed, n_new=NEW, stop=(), pad=None, **kw):
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
 def test_generate_with_controls_graph_eager_uncached_restated(dev, precision):
-    from drakegpt_amd.model import check_control_args
+    from drakegpt_amd.model import Sampling, check_control_args
     m = lm(dev, precision)
     idx = prompts(dev)
     a = m.generate(idx, NEW, sampler="device", seed=11, **PEN)                  # 2 + 40 tokens: crosses the window at 32
     assert a.shape == (1, T0 + NEW) and torch.equal(a[:, :T0], idx) and BAN not in a[0, T0:].tolist()
     ctl = check_control_args(1.3, 0.2, 0.1, PEN["logit_bias"], None, None, 64, V)
-    b = m._generate_device_cached(idx, NEW, None, 1.0, 30, 11, graph=False, top_p=0.95, ctl=ctl)
+    b = m._generate_device_cached(idx, NEW, Sampling("device", 1.0, 30, 0.95, ctl=ctl, seed=11), graph=False)
     assert a.tolist() == b.tolist()
     assert a.tolist() != m.generate(idx, NEW, sampler="device", seed=11, top_k=30, top_p=0.95).tolist()
     if precision == "fp32":                             # fp32 decoding is bit-identical to the full forward
@@ -378,9 +378,9 @@ def test_stop_tokens_rows_end_at_different_lengths(dev):
     outs = [m.generate(idx, NEW, stop_tokens=stop, pad_token=pad, stop_poll=poll, **kw) for poll in (1, 7, 1000)]
     check_stopped(outs[0], plain, stop, ends, pad)
     assert outs[0].tolist() == outs[1].tolist() == outs[2].tolist()
-    from drakegpt_amd.model import check_control_args
+    from drakegpt_amd.model import Sampling, check_control_args
     ctl = check_control_args(1.0, 0.0, 0.0, None, stop, pad, 7, V)
-    assert m._generate_device_cached(idx, NEW, None, 1.2, None, 5, graph=False, ctl=ctl).tolist() == outs[0].tolist()
+    assert m._generate_device_cached(idx, NEW, Sampling("device", 1.2, ctl=ctl, seed=5), graph=False).tolist() == outs[0].tolist()
     assert m.generate(idx, NEW, stop_tokens=stop, pad_token=pad, stop_poll=7, use_cache=False, **kw).tolist() == outs[0].tolist()
     # the default pad is the first stop token
     d = m.generate(idx, NEW, stop_tokens=stop, **kw)
@@ -394,7 +394,7 @@ def test_stop_tokens_rows_end_at_different_lengths(dev):
     check_stopped(two[0], plain2, stop, ends, pad)
     assert two[0].shape[1] == max(ends) < T0 + NEW
     assert two[0].tolist() == two[1].tolist() == two[2].tolist()
-    assert m._generate_device_cached(idx[:2], NEW, None, 1.2, None, 5, graph=False, ctl=ctl).tolist() == two[0].tolist()
+    assert m._generate_device_cached(idx[:2], NEW, Sampling("device", 1.2, ctl=ctl, seed=5), graph=False).tolist() == two[0].tolist()
     assert m.generate(idx[:2], NEW, stop_tokens=stop, pad_token=pad, use_cache=False, **kw).tolist() == two[0].tolist()
 
 

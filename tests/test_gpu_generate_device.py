@@ -106,7 +106,8 @@ def test_bf16_graph_equals_the_eager_cached_steps(dev):
     """both paths launch the same kernels in the same order; the graph only removes the host from between them"""
     m = lm(dev, "bf16")
     a = m.generate(prompt(dev), 40, sampler="device", seed=21)
-    b = m._generate_device_cached(prompt(dev), 40, None, 1.0, None, 21, graph=False)
+    from drakegpt_amd.model import Sampling
+    b = m._generate_device_cached(prompt(dev), 40, Sampling("device", seed=21), graph=False)
     assert a.tolist() == b.tolist()
     assert m.generate(prompt(dev), 40, sampler="device", seed=22).tolist() != a.tolist()
 

@@ -176,7 +176,8 @@ def test_generate_graph_equals_eager(dev, precision):
     m = lm(dev, precision)
     a = m.generate(prompt(dev), 40, sampler="device", top_p=0.9, top_k=20, seed=11)        # 2 + 40 tokens: crosses the window at 32
     assert a.shape == (1, 42) and torch.equal(a[:, :2], prompt(dev))
-    b = m._generate_device_cached(prompt(dev), 40, None, 1.0, 20, 11, graph=False, top_p=0.9)
+    from drakegpt_amd.model import Sampling
+    b = m._generate_device_cached(prompt(dev), 40, Sampling("device", 1.0, 20, 0.9, seed=11), graph=False)
     assert a.tolist() == b.tolist()
     if precision == "fp32":                             # fp32 decoding is bit-identical to the full forward: re-derive each token
         ref = rederive(m, a, 2, 11, top_k=20, top_p=0.9)
