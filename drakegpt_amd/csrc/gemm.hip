@@ -843,12 +843,30 @@ __global__ __launch_bounds__(768) void gemm_tn_grouped256_kernel(typename TnGrou
         for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const int fr = lane & 15, fg = lane >> 4;
     const int aimg = (wp >> 1) * 16384, acol = (wp & 1) * 64;
-    auto read_frags = [&](u32x4 (&fa)[4], u32x4 (&fb)[4], const char* buf, int ks) {
-        const int r0 = ks * 32 + fg * 8;
+    // The same addresses as tn_frag_bf16(buf + image, ks * 32 + fg * 8, col0 + 16 i, lane), from four per-lane offsets instead
+    // of sixteen: a wave's col0 is a multiple of 64 and 16 i only sets bits 1, 2 of the chunk index, which the swizzle XORs, so
+    // fragment i lies at (fragment 0) ^ 32 i -- taken after the stage offset (a multiple of 16 KB) is added, so that the sixteen
+    // addresses are not hoisted out of the K loop as invariants again -- and ks adds 32 rows (8 KB).
+    int offA[2], offB[2];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) fa[i] = tn_frag_bf16(buf + aimg, r0, acol + i * 16, lane);
+    for (int h = 0; h < 2; ++h) {
+        const int row = fg * 8 + 4 * h + (fr >> 2), sub = ((fr & 3) >> 1), byte = 8 * (fr & 1);
+        offA[h] = aimg + tn_off_bf16(row, (acol >> 3) + sub) + byte;
+        offB[h] = 32768 + tn_off_bf16(row, wq * 8 + sub) + byte;
+    }
+    auto read_frags = [&](u32x4 (&fa)[4], u32x4 (&fb)[4], int stage_off, int ks) {
+        typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+        auto frag = [&](int lo_off, int hi_off) -> u32x4 {
+            bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(lds + lo_off));
+            bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(lds + hi_off));
+            return __builtin_bit_cast(u32x4, (bf16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+        };
 #pragma unroll
-        for (int j = 0; j < 4; ++j) fb[j] = tn_frag_bf16(buf + 32768, r0, wq * 64 + j * 16, lane);
+        for (int i = 0; i < 4; ++i)
+            fa[i] = frag(((stage_off + offA[0]) ^ (32 * i)) + ks * 8192, ((stage_off + offA[1]) ^ (32 * i)) + ks * 8192);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            fb[j] = frag(((stage_off + offB[0]) ^ (32 * j)) + ks * 8192, ((stage_off + offB[1]) ^ (32 * j)) + ks * 8192);
     };
     auto mma_all = [&](const u32x4 (&fa)[4], const u32x4 (&fb)[4]) {
 #pragma unroll
@@ -994,22 +1012,29 @@ __global__ __launch_bounds__(768) void gemm_tn_grouped256_kernel(typename TnGrou
             }
         }
     } else {
-        for (int g = 0; g < total; ++g) {
-            const char* buf = lds + buf_i * TN2_STAGE;
-            read_frags(fa0, fb0, buf, 0);
-            read_frags(fa1, fb1, buf, 1);
-            mma_all(fa0, fb0);
-            mma_all(fa1, fb1);
-            if (++buf_i == TN2_NST) buf_i = 0;
-            if (++kt == cx.kb - cx.ka) {
-                store_tile();
-                kt = 0;
-                next_item();
+        // One counted loop per item inside the loop over all stages: the same stages, barriers and stores in the same order as one
+        // flat loop with an item counter.  Together with the four-offset fragment addresses above it is what lets the register
+        // allocator keep the 64 accumulators in place across the item switch: 166 VGPRs and no scratch, where the flat loop
+        // with sixteen hoisted addresses spilled 218 registers and reloaded accumulators between the stores of every
+        // epilogue (460 -> 422 us per launch at the headline shapes).
+        for (int g = 0; g < total;) {
+            const int nkc = cx.kb - cx.ka;
+            for (int k = 0; k < nkc; ++k) {
+                read_frags(fa0, fb0, buf_i * TN2_STAGE, 0);
+                read_frags(fa1, fb1, buf_i * TN2_STAGE, 1);
+                mma_all(fa0, fb0);
+                mma_all(fa1, fb1);
+                if (++buf_i == TN2_NST) buf_i = 0;
+                if (k + 1 == nkc) {
+                    store_tile();
+                    next_item();
+                }
+                if (++g < total) {
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // every read of stage g has returned: the loaders refill its buffer
+                    __builtin_amdgcn_s_barrier();
+                }
             }
-            if (g + 1 < total) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // every read of stage g has returned: the loaders refill its buffer
-                __builtin_amdgcn_s_barrier();
-            }
+            if (nkc <= 0) next_item();                             // (the host never builds an empty K range)
         }
     }
 }
