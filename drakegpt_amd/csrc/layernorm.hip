@@ -382,7 +382,9 @@ __global__ __launch_bounds__(NTHREADS) void ln_bwd_kernel(LnFuse fz, const TD* _
                             if (fz.g8) {                // (uniform)
                                 float w4[4];
 #pragma unroll
-                                for (int j = 0; j < 4; ++j) { q_m = dg_amax_nan(q_m, gq[j]); w4[j] = dg_fp8_clamp(gq[j] * q_sc, 57344.f); }
+                                // the cast sees the bf16 value, as the separate cast launch did (and as the forward's e4m3 copy does): g8 is
+                                // the e5m2 cast of the g this launch returns; the recorded maximum stays that of the fp32 value
+                                for (int j = 0; j < 4; ++j) { q_m = dg_amax_nan(q_m, gq[j]); w4[j] = dg_fp8_clamp((float)t[j] * q_sc, 57344.f); }
                                 int wq = 0;
                                 wq = __builtin_amdgcn_cvt_pk_bf8_f32(w4[0], w4[1], wq, false);
                                 wq = __builtin_amdgcn_cvt_pk_bf8_f32(w4[2], w4[3], wq, true);

@@ -126,7 +126,8 @@ int dg_layernorm_bwd_fused(const void* dy, int dy_dtype, const float* x, const f
                            float* gbias_part, void* stream);
 /* fp8 mode: the same with g in bf16 AND a second time as OCP e5m2 (g8 [M][C] bytes: the gradient operand of the dX GEMM that
  * runs next) with delayed per-tensor scaling as in dg_fp8_quantize_delayed (g8_parts2 [2][DG_FP8_AMAX_PARTS], step_state,
- * *g8_scale_inv).  n_partials must be DG_FP8_AMAX_PARTS: every workgroup leaves one partial maximum. */
+ * *g8_scale_inv); the cast sees the bf16 value of g, as a separate cast launch would.  n_partials must be DG_FP8_AMAX_PARTS: every
+ * workgroup leaves one partial maximum. */
 int dg_layernorm_bwd_fused_fp8(const void* dy, int dy_dtype, const float* x, const float* gamma, const float* mean,
                                const float* rstd, const void* dresid, void* dx, int resid_dtype,
                                float* dgamma_part, float* dbeta_part, int64_t part_stride, int n_partials,

@@ -194,6 +194,59 @@ def assert_layernorm_stats(mu: Tensor, rs: Tensor, x: Tensor, mean: Tensor, std:
     return out[0], out[1]
 
 
+def layernorm_model(x: Tensor, w: Tensor, b: Tensor, dy: Optional[Tensor] = None, dresid: Optional[Tensor] = None,
+                    keep: Optional[Tensor] = None, p: float = 0.0, eps: float = 1e-5, dtype: torch.dtype = torch.float32) -> dict:
+    """The LayerNorm kernels' own formulas (csrc/layernorm.hip) evaluated with torch on the CPU in ``dtype``: two-pass mean and
+    variance, rstd = 1 / sqrt(var + eps), y = xhat * gamma + beta, and with ``dy``
+
+        g = dy * gamma;  dx = rstd * (g - mean(g) - xhat * mean(g * xhat)) (+ dresid);  gq = dx * keep / (1 - p)
+
+    dtype = float32 is the model whose error against fp64 sets the per-row and per-column bounds of tests/test_gpu_layernorm.py
+    (a reference-side number: every product, sum and square root rounded to fp32, no bf16 rounding -- the caller rounds where a
+    kernel stores bf16); dtype = float64 is the same code as a reference, which tests/test_layernorm_cases_host.py holds against
+    autograd.  Left to the caller's margin: the wave-shuffle summation order and ``rsqrtf`` against torch's order and ``sqrt``.
+    Column sums are returned as their TERMS [M, C] (dgamma: dy * xhat, dbeta: dy, gbias: gq) so that a caller can sum any row
+    range, in fp32 for the model and in fp64 for the reference."""
+    t = lambda v: None if v is None else v.detach().cpu().to(dtype)
+    x, w, b, dy, dresid, keep = t(x), t(w), t(b), t(dy), t(dresid), t(keep)
+    C = x.shape[1]
+    mean = x.sum(1, keepdim=True) / C
+    d = x - mean
+    rstd = 1.0 / ((d * d).sum(1, keepdim=True) / C + eps).sqrt()
+    xhat = d * rstd
+    out = dict(y=xhat * w + b, mean=mean, rstd=rstd, xhat=xhat)
+    if dy is None:
+        return out
+    g = dy * w
+    c1, c2 = g.sum(1, keepdim=True) / C, (g * xhat).sum(1, keepdim=True) / C
+    dx = rstd * (g - c1 - xhat * c2)
+    if dresid is not None:
+        dx = dx + dresid
+    gq = dx if keep is None else dx * keep * torch.tensor(1.0 / (1.0 - p), dtype=dtype)
+    out.update(dx=dx, g=gq, dgamma_terms=dy * xhat, dbeta_terms=dy, gbias_terms=gq)
+    return out
+
+
+LN_MARGIN = 4.0            # the kernels' wave-shuffle summation order and rsqrtf against the model's torch order and sqrt
+
+
+def layernorm_row_bound(model: Tensor, ref: Tensor, C: int, tol: float, cancels: bool = False) -> Tuple[float, float]:
+    """(bound, model's worst row): LN_MARGIN x the worst row of the fp32 model against fp64, and never below the suite's
+    whole-tensor tolerance ``tol`` -- except for the backward's outputs (``cancels``) at C < 32: there dx cancels almost
+    entirely (it lies in the C - 2 dimensions orthogonal to the row's ones and xhat), the whole-tensor tolerance means nothing
+    for it, and the model sets the bound alone."""
+    m = rowwise_rel(model, ref, C).max().item()
+    return (LN_MARGIN * m if cancels and C < 32 else max(tol, LN_MARGIN * m)), m
+
+
+def layernorm_column_bound(model_sum: Tensor, ref_sum: Tensor, ref_terms: Tensor) -> Tuple[Tensor, float]:
+    """per-column bound on a column sum of M terms: LN_MARGIN x (the model's worst column error / sum |term|) x sum |term| of
+    the column itself; returns (bound [C], the model's worst ratio)."""
+    mag = f64(ref_terms).abs().sum(0).clamp_min(1e-300)
+    worst = ((f64(model_sum) - f64(ref_sum)).abs() / mag).max().item()
+    return LN_MARGIN * worst * mag, worst
+
+
 def single_rounding_envelope(value: Tensor, n: int) -> float:
     """an fp32 value that is itself within a few fp32 ulps of fp64 (a length-n reduction feeds it), rounded once:
     envelope = n * 2^-23 * max |value|"""

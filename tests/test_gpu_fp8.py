@@ -266,7 +266,7 @@ def test_gemm_nt_fp8_out_dx_form(dev, M, N, K):
 def test_layernorm_bwd_fused_fp8_emits_the_next_gradient_operand(dev, M, C):
     """the fused LayerNorm backward of the bf16 gradient stream also leaves g = dropout_bwd(dx) as e5m2 with delayed scaling
     (the operand of the fp8 dX GEMM that runs next): dx, g and every partial row bit-identical to the call without fp8_out;
-    g8 = e5m2(g * 57344 / amax_prev) of the unrounded g; one partial maximum per workgroup (exactly 256 of them)"""
+    g8 = e5m2(g * 57344 / amax_prev) of the returned bf16 g (bit for bit in tests/test_gpu_layernorm.py); one partial maximum per workgroup (exactly 256 of them)"""
     from oracle import rng_ref
     from drakegpt_amd import ops
     G, site, seed, step, p = ops.FP8_AMAX_PARTS, 5, 11, 8, 0.2
