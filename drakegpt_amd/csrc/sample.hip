@@ -17,6 +17,9 @@
 //      (logit, count, bias) (no scratch row: the three operands are L2-resident like the row itself).  The thread that writes the
 //      token also does counts[row, token] += 1 and, at a stop token, lengths[row] = L + 1; a row that arrives finished writes pad_id
 //      and returns before it reads a logit.
+//      dg_sample_rows_ragged only (prompts of different lengths walked by one shared L): a row whose span {first, end} has
+//      L < first is forced -- its prompt token is already at ids[row, L] -- and returns next, having read and written nothing; a
+//      row that writes the last token of its budget (L + 1 >= end) marks itself finished like a row at a stop token.
 // No floating-point atomics anywhere: tokens and probs are a pure function of (logits, state, params, row).
 // exp and the prefix sums are fp64: with a few terms kept by top-k the errors of an fp32 expf do not average out of S (measured:
 // probs off by 4.5 x 2^-24 at k = 40), and fp64 is cheap here -- a few passes over one row.  The CDF is then exact to ~1e-14.
@@ -33,7 +36,9 @@ struct SampleControl {
     int32_t stop[DG_SAMPLE_MAX_STOP];
 };
 struct SampleCtlArgs { const SampleControl* control; const float* bias; int32_t* counts; int64_t ldc; int32_t* lengths; };
+struct SampleRagArgs : SampleCtlArgs { const int32_t* spans; };      // dg_sample_rows_ragged: + {first, end} per row
 struct SampleNoCtl {};
+template <bool CTL, bool RAG> using SampleCtlOf = std::conditional_t<RAG, SampleRagArgs, std::conditional_t<CTL, SampleCtlArgs, SampleNoCtl>>;
 
 __device__ __forceinline__ uint32_t f32_key(float z) {          // a < b  <=>  key(a) < key(b)  (no NaNs)
     const uint32_t b = __float_as_uint(z);
@@ -59,11 +64,13 @@ __device__ __forceinline__ float adjust_logit(float x, int32_t c, float inv_rep,
 
 // EXT: params is a SampleParamsEx and the top-p / min-p stage exists; !EXT is dg_sample_rows as it always was
 // CTL: dg_sample_rows_control -- `ctl` holds the control block, bias, counts and lengths; !CTL: an empty struct, no code
-template <int NT, bool EXT, bool CTL = false>
+// RAG: dg_sample_rows_ragged -- CTL with the rows' spans in `ctl` (the launch has checked ids, ld_ids > 0 and lengths); !RAG: no code
+template <int NT, bool EXT, bool CTL = false, bool RAG = false>
 __global__ __launch_bounds__(NT) void sample_rows_kernel(const float* __restrict__ logits, int64_t ldl, int M, int V,
                                                          const uint32_t* __restrict__ state, const SampleParams* __restrict__ params,
                                                          int64_t* __restrict__ ids, int64_t ld_ids, float* __restrict__ probs,
-                                                         int64_t ldp, std::conditional_t<CTL, SampleCtlArgs, SampleNoCtl> ctl) {
+                                                         int64_t ldp, SampleCtlOf<CTL, RAG> ctl) {
+    static_assert(CTL || !RAG, "the ragged entry is a control entry");
     constexpr int NW = NT / 64;
     __shared__ float s_mx[NW];
     __shared__ int s_ix[NW];
@@ -90,6 +97,9 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const float* __restrict
             const uint32_t Lf = state[2];
             if (tid == 0 && (int64_t)Lf < ld_ids) ids[(int64_t)row * ld_ids + Lf] = (int64_t)ctl.control->pad_id;
             return;
+        }
+        if constexpr (RAG) {          // forced: uniform per workgroup, before any barrier; nothing is read but the span, nothing written
+            if ((int64_t)state[2] < (int64_t)ctl.spans[2 * row]) return;
         }
         inv_rep = ctl.control->inv_rep; rpen = ctl.control->rep;
         presence = ctl.control->presence; frequency = ctl.control->frequency;
@@ -131,10 +141,14 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const float* __restrict
         *tok_out = tok;
         if constexpr (CTL) {
             if (crow) crow[tok] = crow[tok] + 1;
+            bool stopped = false;
             if (ctl.lengths && ld_ids > 0) {
                 const int ns = min(ctl.control->n_stop, DG_SAMPLE_MAX_STOP);
                 for (int q = 0; q < ns; ++q)
-                    if (ctl.control->stop[q] == tok) { ctl.lengths[row] = (int32_t)(L + 1u); break; }
+                    if (ctl.control->stop[q] == tok) { ctl.lengths[row] = (int32_t)(L + 1u); stopped = true; break; }
+            }
+            if constexpr (RAG) {      // the last token of the row's budget: finished from the next position on
+                if (!stopped && (int64_t)L + 1 >= (int64_t)ctl.spans[2 * row + 1]) ctl.lengths[row] = (int32_t)(L + 1u);
             }
         }
     };
@@ -302,10 +316,10 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const float* __restrict
     emit(tok);
 }
 
-template <bool EXT, bool CTL = false>
+template <bool EXT, bool CTL = false, bool RAG = false>
 static int sample_rows_launch(const float* logits, int64_t ldl, int M, int V, const uint32_t* state, const void* params,
                               int64_t* ids, int64_t ld_ids, float* probs, int64_t ldp, void* stream,
-                              std::conditional_t<CTL, SampleCtlArgs, SampleNoCtl> ctl = {}) {
+                              SampleCtlOf<CTL, RAG> ctl = {}) {
     if (!logits || !params || M <= 0 || V <= 0 || V > (1 << 20) || ldl < V || ld_ids < 0) return DG_ERR_ARG;
     if (!ids && !probs) return DG_ERR_ARG;
     if (ids && !state) return DG_ERR_ARG;
@@ -315,13 +329,16 @@ static int sample_rows_launch(const float* logits, int64_t ldl, int M, int V, co
         if (ctl.counts && ctl.ldc < V) return DG_ERR_ARG;
         if (ctl.lengths && (!ids || ld_ids == 0)) return DG_ERR_ARG;
     }
+    if constexpr (RAG) {
+        if (!ctl.spans || !ctl.lengths || !ids || ld_ids == 0) return DG_ERR_ARG;
+    }
     hipStream_t s = (hipStream_t)stream;
     const SampleParams* p = (const SampleParams*)params;
     // a chunk of at most 32 (small rows) or V / 1024 (52 at V = 53248) elements per thread
     if (V <= 8192)
-        hipLaunchKernelGGL((sample_rows_kernel<256, EXT, CTL>), dim3(M), dim3(256), 0, s, logits, ldl, M, V, state, p, ids, ld_ids, probs, ldp, ctl);
+        hipLaunchKernelGGL((sample_rows_kernel<256, EXT, CTL, RAG>), dim3(M), dim3(256), 0, s, logits, ldl, M, V, state, p, ids, ld_ids, probs, ldp, ctl);
     else
-        hipLaunchKernelGGL((sample_rows_kernel<1024, EXT, CTL>), dim3(M), dim3(1024), 0, s, logits, ldl, M, V, state, p, ids, ld_ids, probs, ldp, ctl);
+        hipLaunchKernelGGL((sample_rows_kernel<1024, EXT, CTL, RAG>), dim3(M), dim3(1024), 0, s, logits, ldl, M, V, state, p, ids, ld_ids, probs, ldp, ctl);
     DG_LAUNCH_CHECK();
     return DG_OK;
 }
@@ -343,11 +360,18 @@ extern "C" int dg_sample_rows_control(const float* logits, int64_t ldl, int M, i
                                           SampleCtlArgs{(const SampleControl*)control, bias, counts, ldc, lengths});
 }
 
+extern "C" int dg_sample_rows_ragged(const float* logits, int64_t ldl, int M, int V, const uint32_t* state, const void* params,
+                                     int64_t* ids, int64_t ld_ids, float* probs, int64_t ldp, const void* control,
+                                     const float* bias, int32_t* counts, int64_t ldc, int32_t* lengths, const int32_t* spans,
+                                     void* stream) {
+    return sample_rows_launch<true, true, true>(logits, ldl, M, V, state, params, ids, ld_ids, probs, ldp, stream,
+                                                SampleRagArgs{{(const SampleControl*)control, bias, counts, ldc, lengths}, spans});
+}
+
 // counts[m, clamp(ids[m, j])] += 1 for j < n: one workgroup per row; !accumulate zeroes the row's V counts first, and the barrier
 // of that same workgroup orders the zeroes before its own atomics -- no grid-wide ordering is needed
-__global__ __launch_bounds__(256) void token_counts_kernel(const int64_t* __restrict__ ids, int64_t ld_ids, int n, int V,
-                                                           int32_t* __restrict__ counts, int64_t ldc, int accumulate) {
-    const int row = blockIdx.x;
+__device__ __forceinline__ void token_counts_row(const int64_t* __restrict__ ids, int64_t ld_ids, int n, int V,
+                                                 int32_t* __restrict__ counts, int64_t ldc, int accumulate, int row) {
     int32_t* crow = counts + (int64_t)row * ldc;
     if (!accumulate) {
         for (int i = threadIdx.x; i < V; i += 256) crow[i] = 0;
@@ -361,10 +385,33 @@ __global__ __launch_bounds__(256) void token_counts_kernel(const int64_t* __rest
     }
 }
 
+__global__ __launch_bounds__(256) void token_counts_kernel(const int64_t* __restrict__ ids, int64_t ld_ids, int n, int V,
+                                                           int32_t* __restrict__ counts, int64_t ldc, int accumulate) {
+    token_counts_row(ids, ld_ids, n, V, counts, ldc, accumulate, blockIdx.x);
+}
+
+// dg_token_counts_rows: row m counts its own prefix, n = clamp(n_rows[m * n_stride], 0, ld_ids)
+__global__ __launch_bounds__(256) void token_counts_rows_kernel(const int64_t* __restrict__ ids, int64_t ld_ids,
+                                                                const int32_t* __restrict__ n_rows, int64_t n_stride, int V,
+                                                                int32_t* __restrict__ counts, int64_t ldc, int accumulate) {
+    const int row = blockIdx.x;
+    const int64_t n = n_rows[(int64_t)row * n_stride];
+    token_counts_row(ids, ld_ids, (int)(n < 0 ? 0 : (n > ld_ids ? ld_ids : n)), V, counts, ldc, accumulate, row);
+}
+
 extern "C" int dg_token_counts(const int64_t* ids, int64_t ld_ids, int M, int n, int V, int32_t* counts, int64_t ldc,
                                int accumulate, void* stream) {
     if (!ids || !counts || M <= 0 || n < 0 || V <= 0 || ld_ids < n || ldc < V) return DG_ERR_ARG;
     hipLaunchKernelGGL(token_counts_kernel, dim3(M), dim3(256), 0, (hipStream_t)stream, ids, ld_ids, n, V, counts, ldc, accumulate);
+    DG_LAUNCH_CHECK();
+    return DG_OK;
+}
+
+extern "C" int dg_token_counts_rows(const int64_t* ids, int64_t ld_ids, int M, const int32_t* n_rows, int64_t n_stride, int V,
+                                    int32_t* counts, int64_t ldc, int accumulate, void* stream) {
+    if (!ids || !counts || !n_rows || M <= 0 || V <= 0 || ld_ids < 0 || ld_ids > INT32_MAX || n_stride < 0 || ldc < V) return DG_ERR_ARG;
+    hipLaunchKernelGGL(token_counts_rows_kernel, dim3(M), dim3(256), 0, (hipStream_t)stream, ids, ld_ids, n_rows, n_stride, V, counts,
+                       ldc, accumulate);
     DG_LAUNCH_CHECK();
     return DG_OK;
 }

@@ -19,6 +19,12 @@ A call with a penalty, a logit bias or a stop token replays a second pair of gra
 two chains ending in dg_sample_rows_control.  Its operands are the decoder's too -- the 16-word control block, bias [V], the
 token counts [B, V] that the kernel keeps up to date and lengths [B], the rows' "finished" state that the next replay honours --
 and every call that uses them rewrites all four first.  A call without controls replays the first pair, as it always did.
+
+A call with prompt_lengths (rows that start at different lengths) replays a third pair, captured on the first such call: the same
+two chains ending in dg_sample_rows_ragged, which reads one more operand of the decoder's, spans [B, 2], rewritten by every such
+call with the other four.  The shared position L starts at the shortest prompt; a row still inside its prompt is left alone by
+the sampler and reads its next prompt token from ids like any other token.  Which pair a call uses is its mode (MODES); the
+tail, the capture and the step are written once and take it as an argument.
 """
 from __future__ import annotations
 
@@ -29,6 +35,9 @@ import torch
 from . import ops
 from .engine import capture_after_warmup
 from .model import ControlOperands
+
+
+MODES = ("plain", "control", "ragged")          # the sampler entry a step ends in: nucleus, control, ragged
 
 
 class DeviceDecoder:
@@ -50,12 +59,17 @@ class DeviceDecoder:
         self.caches = [torch.zeros((B, ctx, 3 * C), dtype=self.act, device=device) for _ in model.blocks]
         self.row = torch.zeros((B, 3 * C), dtype=self.act, device=device)       # staging: the new token's q/k/v
         self.ws = self.w_lm = self.tok = self.pos = self.lm_bias = None
-        self.graphs = None
+        self.pairs = {}          # mode -> (graph A, graph B), each captured on the first call in that mode
         # the operands of dg_sample_rows_control, the tail of the second pair of graphs (captured on the first call that asks for a
-        # penalty, a bias or a stop token): every call that uses them rewrites all four first (ControlOperands.begin)
-        self.operands = ControlOperands(B, model.token_embedding_table.weight.shape[0], device)
+        # penalty, a bias or a stop token): every call that uses them rewrites all four first (ControlOperands.begin); a call with
+        # prompt_lengths (the third pair, dg_sample_rows_ragged) rewrites spans with them
+        self.operands = ControlOperands(B, model.token_embedding_table.weight.shape[0], device, spans=True)
         self.control, self.bias, self.counts, self.lengths = self.operands.kw().values()
-        self.graphs_control = None
+        self.spans = self.operands.spans
+
+    graphs = property(lambda self: self.pairs.get("plain"))
+    graphs_control = property(lambda self: self.pairs.get("control"))
+    graphs_ragged = property(lambda self: self.pairs.get("ragged"))
 
     # ------------------------------------------------------------------ operands
     @torch.no_grad()
@@ -76,33 +90,36 @@ class DeviceDecoder:
                 d.copy_(s)
 
     # ------------------------------------------------------------------ the two steps
-    def tail(self, logits, controls: bool = False) -> None:
-        """sample (controls: dg_sample_rows_control on the decoder's operands) and advance"""
-        ops.sample_rows(logits, self.state, self.params, ids=self.ids, **(self.operands.kw() if controls else {}))
+    def tail(self, logits, mode: str = "plain") -> None:
+        """sample (control / ragged: dg_sample_rows_control / dg_sample_rows_ragged on the decoder's operands) and advance"""
+        assert mode in MODES, mode
+        ops.sample_rows(logits, self.state, self.params, ids=self.ids, **({} if mode == "plain" else self.operands.kw(mode == "ragged")))
         ops.state_advance(self.state)
 
-    def _step_cached(self, model, controls: bool) -> None:
+    def _step_cached(self, model, mode: str) -> None:
         """TransformerLM._decode_step at the device position L - 1"""
         def attend(l, h, wqkv):
             ops.gemm_nt(h, wqkv, self.act, out=self.row, split=self.split)
             return ops.attn_decode_append(self.row, self.caches[l], self.state, self.NH, self.H, self.H ** -0.5)
 
         x = ops.embed_window(self.ids, self.state, self.tok, self.pos, 0)
-        self.tail(model._lm_logits(model._layers(x, self.ws, attend), self.w_lm, self.lm_bias), controls)
+        self.tail(model._lm_logits(model._layers(x, self.ws, attend), self.w_lm, self.lm_bias), mode)
 
-    def _step_window(self, model, controls: bool) -> None:
+    def _step_window(self, model, mode: str) -> None:
         """the full forward on the last ctx tokens (the reference algorithm once the window slides)"""
         x = ops.embed_window(self.ids, self.state, self.tok, self.pos, 1).view(self.B * self.ctx, self.C)
-        self.tail(model._forward_rows(x, self.B, self.ctx, None, self.ws, self.w_lm, self.lm_bias), controls)
+        self.tail(model._forward_rows(x, self.B, self.ctx, None, self.ws, self.w_lm, self.lm_bias), mode)
 
     # ------------------------------------------------------------------ capture / replay
     @torch.no_grad()
-    def capture(self, controls: bool = False) -> None:
-        """capture both steps once, each after a warm-up run at its own position (engine.capture_after_warmup; the state word is put
-        back in between).  A warm-up step writes cache row L - 1 and ids[:, L]: both are rewritten by the real step at that L before
-        anything reads them.  controls=True: the second pair, the same steps ending in dg_sample_rows_control; its warm-up also
-        touches counts and lengths, which ControlOperands.begin rewrites before every use."""
-        if (self.graphs_control if controls else self.graphs) is not None:
+    def capture(self, mode: str = "plain") -> None:
+        """capture both steps of `mode` once, each after a warm-up run at its own position (engine.capture_after_warmup; the state
+        word is put back in between).  A warm-up step writes cache row L - 1 and ids[:, L]: the call that follows writes its prompt
+        into ids after the capture, and the real step at that L rewrites both before anything reads them.  "control": the second
+        pair, the same steps ending in dg_sample_rows_control; its warm-up also touches counts and lengths, which
+        ControlOperands.begin rewrites before every use.  "ragged": the third pair, ending in dg_sample_rows_ragged; its warm-up
+        runs on whatever spans hold (any values are safe: they only pick which rows sample), and begin rewrites them too."""
+        if mode in self.pairs:
             return
         model = self._mref()
         graphs = []
@@ -110,14 +127,11 @@ class DeviceDecoder:
             def position(L=L):
                 self.state.copy_(ops.new_rng_state(0, self.device, step=L))
             position()
-            graphs += capture_after_warmup(self.device, [lambda step=step: step(model, controls)], position)
-        if controls:
-            self.graphs_control = tuple(graphs)
-        else:
-            self.graphs = tuple(graphs)
+            graphs += capture_after_warmup(self.device, [lambda step=step: step(model, mode)], position)
+        self.pairs[mode] = tuple(graphs)
 
-    def step(self, cached: bool, graph: bool = True, controls: bool = False) -> None:
+    def step(self, cached: bool, graph: bool = True, mode: str = "plain") -> None:
         if graph:
-            (self.graphs_control if controls else self.graphs)[0 if cached else 1].replay()
+            self.pairs[mode][0 if cached else 1].replay()
         else:
-            (self._step_cached if cached else self._step_window)(self._mref(), controls)
+            (self._step_cached if cached else self._step_window)(self._mref(), mode)

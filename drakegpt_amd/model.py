@@ -99,10 +99,11 @@ def check_nucleus_args(top_p, min_p):
 
 
 def check_control_args(repetition_penalty, presence_penalty, frequency_penalty, logit_bias, stop_tokens, pad_token, stop_poll,
-                       vocab_size: int):
+                       vocab_size: int, ragged: bool = False):
     """the checks of generate()'s penalties, logit_bias and stop tokens, like check_nucleus_args: plain Python, raised before
     anything touches a device.  Returns None when every control is off, else a dict: rep / presence / frequency (floats), bias
-    (a CPU fp32 tensor [V] or None), stop (a tuple of ints), pad (int), poll (int), adjust (bool: a penalty or a bias is on)."""
+    (a CPU fp32 tensor [V] or None), stop (a tuple of ints), pad (int), poll (int), adjust (bool: a penalty or a bias is on).
+    ragged: the call has prompt_lengths -- it pads, so it needs a pad_token or stop_tokens, and always gets the dict."""
     V = int(vocab_size)
 
     def token(x, name):
@@ -151,13 +152,45 @@ def check_control_args(repetition_penalty, presence_penalty, frequency_penalty, 
         stop = tuple(token(t, "a stop token") for t in seq)
         if not 1 <= len(stop) <= ops.SAMPLE_MAX_STOP or len(set(stop)) != len(stop):
             raise ValueError(f"generate: stop_tokens must be 1 to {ops.SAMPLE_MAX_STOP} distinct token ids, got {stop_tokens!r}")
-    if pad_token is not None and not stop:
-        raise ValueError("generate: pad_token needs stop_tokens")
+    if pad_token is not None and not stop and not ragged:
+        raise ValueError("generate: pad_token needs stop_tokens or prompt_lengths")
+    if ragged and pad_token is None and not stop:
+        raise ValueError("generate: prompt_lengths needs a pad_token (or stop_tokens, whose first one pads)")
     pad = token(pad_token, "pad_token") if pad_token is not None else (stop[0] if stop else 0)
     adjust = not (rep == 1.0 and presence == 0.0 and frequency == 0.0 and bias is None)       # do the logits change at all
-    if not adjust and not stop:
+    if not adjust and not stop and not ragged:
         return None
     return dict(rep=rep, presence=presence, frequency=frequency, bias=bias, stop=stop, pad=pad, poll=int(stop_poll), adjust=adjust)
+
+
+def check_prompt_lengths(prompt_lengths, shape) -> Optional[tuple]:
+    """the checks of generate()'s prompt_lengths, like check_control_args: plain Python, raised before anything touches a device
+    (a tensor of lengths is read once, here).  B integers, a sequence or an integer tensor [B], with 1 <= p_b <= T for idx of
+    `shape` (B, T).  Returns them as a tuple of ints; None when left out."""
+    if prompt_lengths is None:
+        return None
+    if len(shape) != 2:
+        raise ValueError("generate: prompt_lengths needs idx of shape (B, T)")
+    B, T = int(shape[0]), int(shape[1])
+    if isinstance(prompt_lengths, Tensor):
+        if prompt_lengths.dim() != 1 or prompt_lengths.dtype == torch.bool or prompt_lengths.is_floating_point() \
+                or prompt_lengths.is_complex():
+            raise ValueError(f"generate: a prompt_lengths tensor must be [B] of an integer type, got {prompt_lengths.dtype} "
+                             f"{tuple(prompt_lengths.shape)}")
+        seq = prompt_lengths.tolist()
+    else:
+        try:
+            seq = list(prompt_lengths)
+        except TypeError:
+            raise ValueError(f"generate: prompt_lengths must be a sequence or a tensor of B integers, got {prompt_lengths!r}") from None
+    if len(seq) != B:
+        raise ValueError(f"generate: prompt_lengths must have one entry per row of idx (B = {B}), got {len(seq)}")
+    for p in seq:
+        if isinstance(p, bool) or not isinstance(p, numbers.Integral):
+            raise ValueError(f"generate: a prompt length must be an integer, got {p!r}")
+        if not 1 <= int(p) <= T:
+            raise ValueError(f"generate: a prompt length must be in [1, idx.shape[1] = {T}], got {p!r}")
+    return tuple(int(p) for p in seq)
 
 
 def stop_poll_due(poll: int, produced: int, lengths: Optional[Tensor]) -> bool:
@@ -166,39 +199,53 @@ def stop_poll_due(poll: int, produced: int, lengths: Optional[Tensor]) -> bool:
     return poll > 0 and produced % poll == 0 and bool((lengths != 0).all())
 
 
-def trim_to_longest(ids: Tensor, lengths: Optional[Tensor], total: int) -> Tensor:
-    """ids[:, :n], n = the longest row: a row's final length (stop token included), `total` for a row still running"""
-    if lengths is None:
-        return ids[:, :total]
-    n = lengths.cpu()
-    return ids[:, :int(torch.where(n == 0, torch.full_like(n, total), n).max())]
+def trim_to_longest(ids: Tensor, lengths: Optional[Tensor], total: int, return_lengths: bool = False):
+    """ids[:, :n], n = the longest row: a row's final length (stop token or the end of its budget included), `total` for a row
+    still running.  lengths: the loop's int [B], 0 = running (None: every row ran to `total`).  return_lengths: (ids[:, :n], the
+    rows' final lengths as int64 [B] on ids' device) -- what generate(return_lengths=True) returns."""
+    n = None
+    if lengths is not None:
+        n = lengths.cpu()
+        n = torch.where(n == 0, torch.full_like(n, total), n)
+    out = ids[:, :total if n is None else int(n.max())]
+    if not return_lengths:
+        return out
+    n = torch.full((ids.shape[0],), total) if n is None else n
+    return out, n.to(device=ids.device, dtype=torch.int64)
 
 
 class ControlOperands:
     """what a generate() call with controls hands to ops.sample_rows (dg_sample_rows_control): the 16-word control block, bias [V],
     the token counts [B, V] of the whole sequence so far (prompt included, beyond the context window too; the kernel adds the token
     it writes) and lengths [B], the rows' "finished" state under the device sampler's stop tokens.  The eager loops allocate one
-    per call (fresh); a DeviceDecoder keeps one for good, since its graphs hold the addresses.  begin() starts a call on either."""
+    per call (fresh); a DeviceDecoder keeps one for good, since its graphs hold the addresses.  begin() starts a call on either.
+    spans [B, 2]: the rows' {prompt length, prompt length + budget} of a call with prompt_lengths (dg_sample_rows_ragged)."""
 
-    def __init__(self, B: int, V: int, device, bias: bool = True, lengths: bool = True):
+    def __init__(self, B: int, V: int, device, bias: bool = True, lengths: bool = True, spans: bool = False):
         self.control = ops.new_sample_control(device=device)          # controls off: what a capture's warm-up may safely run on
         self.bias = torch.zeros(V, dtype=torch.float32, device=device) if bias else None
         self.counts = torch.zeros((B, V), dtype=torch.int32, device=device)
         self.lengths = torch.zeros(B, dtype=torch.int32, device=device) if lengths else None
+        self.spans = torch.zeros((B, 2), dtype=torch.int32, device=device) if spans else None
 
     @classmethod
-    def fresh(cls, ctl: Optional[dict], idx: Tensor, V: int, lengths: bool) -> Optional["ControlOperands"]:
-        """an eager call's own operands, begun on the prompt idx (None without controls): a bias and lengths only where it has them"""
+    def fresh(cls, ctl: Optional[dict], idx: Tensor, V: int, lengths: bool, first: Optional[tuple] = None,
+              n_new: int = 0) -> Optional["ControlOperands"]:
+        """an eager call's own operands, begun on the prompt idx (None without controls): a bias, lengths and spans only where it
+        has them (first: the checked prompt_lengths, whose budget ends a row as a stop token does)"""
         if ctl is None:
             return None
-        cs = cls(idx.shape[0], V, idx.device, bias=ctl["bias"] is not None, lengths=lengths and bool(ctl["stop"]))
-        cs.begin(ctl, idx, idx.shape[1])
+        cs = cls(idx.shape[0], V, idx.device, bias=ctl["bias"] is not None, lengths=lengths and (bool(ctl["stop"]) or first is not None),
+                 spans=first is not None)
+        cs.begin(ctl, idx, idx.shape[1], first, n_new)
         return cs
 
     @torch.no_grad()
-    def begin(self, ctl: dict, ids: Tensor, t0: int) -> None:
+    def begin(self, ctl: dict, ids: Tensor, t0: int, first: Optional[tuple] = None, n_new: int = 0) -> None:
         """the start of a call: the block of check_control_args' dict, its bias (None: zeros, and the block's use_bias is 0), the
-        counts of the prompt ids[:, :t0] and all rows running -- nothing is inherited from an earlier call"""
+        counts of the prompt ids[:, :t0] and all rows running -- nothing is inherited from an earlier call.  first (the checked
+        prompt_lengths): spans = {p_b, p_b + n_new}, and row b's counts are those of its own prompt ids[b, :p_b], the whole of it --
+        a row's counts are first read when it first samples, and by then its sequence holds all of its prompt"""
         self.control.copy_(ops.new_sample_control(
             repetition_penalty=ctl["rep"], presence_penalty=ctl["presence"], frequency_penalty=ctl["frequency"], stop_tokens=ctl["stop"],
             pad_token=ctl["pad"], use_bias=ctl["bias"] is not None, device=self.control.device))
@@ -207,12 +254,18 @@ class ControlOperands:
                 self.bias.zero_()
             else:
                 self.bias.copy_(ctl["bias"])
-        ops.token_counts(ids, t0, self.counts.shape[1], self.counts)
+        if first is None:
+            ops.token_counts(ids, t0, self.counts.shape[1], self.counts)
+        else:
+            self.spans.copy_(torch.tensor([[p, p + n_new] for p in first], dtype=torch.int32))
+            ops.token_counts(ids, self.spans[:, 0], self.counts.shape[1], self.counts)
         if self.lengths is not None:
             self.lengths.zero_()
 
-    def kw(self) -> dict:
-        return dict(control=self.control, bias=self.bias, counts=self.counts, lengths=self.lengths)
+    def kw(self, ragged: bool = False) -> dict:
+        """ops.sample_rows' keywords; ragged: with the spans, and so dg_sample_rows_ragged"""
+        kw = dict(control=self.control, bias=self.bias, counts=self.counts, lengths=self.lengths)
+        return dict(kw, spans=self.spans) if ragged else kw
 
 
 def draw_seed(generator: Optional[torch.Generator]) -> int:
@@ -231,16 +284,45 @@ class Sampling(NamedTuple):
     ctl: Optional[dict] = None
     generator: Optional[torch.Generator] = None
     seed: Optional[int] = None
+    prompt_lengths: Optional[tuple] = None          # check_prompt_lengths' tuple: the rows' own prompt lengths in a right-padded idx
+    return_lengths: bool = False
 
     @classmethod
     def checked(cls, vocab_size: int, generator, sampler, temperature, top_k, seed, top_p, min_p, repetition_penalty, presence_penalty,
-                frequency_penalty, logit_bias, stop_tokens, pad_token, stop_poll) -> "Sampling":
-        """the argument checks of generate(), all of them: plain Python, raised before anything touches a device"""
+                frequency_penalty, logit_bias, stop_tokens, pad_token, stop_poll, prompt_lengths=None, shape=(),
+                return_lengths: bool = False) -> "Sampling":
+        """the argument checks of generate(), all of them: plain Python, raised before anything touches a device (shape: idx's,
+        which prompt_lengths is checked against)"""
         temperature, top_k = check_sampling_args(sampler, temperature, top_k, vocab_size)
         top_p, min_p = check_nucleus_args(top_p, min_p)
+        prompt_lengths = check_prompt_lengths(prompt_lengths, shape)
         ctl = check_control_args(repetition_penalty, presence_penalty, frequency_penalty, logit_bias, stop_tokens, pad_token,
-                                 stop_poll, vocab_size)
-        return cls(sampler, temperature, top_k, top_p, min_p, ctl, generator, seed)
+                                 stop_poll, vocab_size, ragged=prompt_lengths is not None)
+        return cls(sampler, temperature, top_k, top_p, min_p, ctl, generator, seed, prompt_lengths, bool(return_lengths))
+
+    @property
+    def ragged(self) -> bool:
+        """the call has prompt_lengths: one shared position walks rows that start at different lengths"""
+        return self.prompt_lengths is not None
+
+    def span(self, T: int, n_new: int) -> tuple:
+        """(the loops' first position, their last + 1) for idx (B, T): (T, T + n_new), or with prompt_lengths
+        (min p_b, max p_b + n_new)"""
+        if self.prompt_lengths is None:
+            return T, T + n_new
+        return min(self.prompt_lengths), max(self.prompt_lengths) + n_new
+
+    def enter(self, idx: Tensor, n_new: int):
+        """prompt_lengths only (else (idx, None)): idx cropped to the longest prompt with pad_token at and beyond every row's own
+        length -- whatever the caller's padding holds never reaches a kernel, the id range check or the result -- and, for a call
+        that asks for no new token, its result"""
+        if self.prompt_lengths is None:
+            return idx, None
+        p = torch.tensor(self.prompt_lengths, device=idx.device)
+        idx = idx[:, :max(self.prompt_lengths)]
+        keep = torch.arange(idx.shape[1], device=idx.device)[None, :] < p[:, None]
+        idx = torch.where(keep, idx, torch.full_like(idx, self.ctl["pad"]))
+        return idx, (trim_to_longest(idx, p, idx.shape[1], self.return_lengths) if n_new < 1 else None)
 
     @property
     def adjust(self) -> bool:
@@ -353,7 +435,7 @@ class _LM(HipModule):
                  temperature: float = 1.0, top_k: Optional[int] = None, seed: Optional[int] = None,
                  top_p: Optional[float] = None, min_p: Optional[float] = None, repetition_penalty: float = 1.0,
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, stop_tokens=None,
-                 pad_token: Optional[int] = None, stop_poll: int = 64):
+                 pad_token: Optional[int] = None, stop_poll: int = 64, prompt_lengths=None, return_lengths: bool = False):
         """ref: src/model.py:611-636.  sampler="host" (default): softmax runs on the GPU; torch.multinomial runs on the host CPU
         generator (the global one unless `generator` is given), as it does in the reference on CPU.  A temperature other than 1
         (0 = greedy) or a top_k filters the distribution on the GPU first (dg_sample_rows); so do top_p (nucleus: the most
@@ -369,9 +451,20 @@ class _LM(HipModule):
         stop_tokens (an int or up to 8): a row that draws one keeps it, every later position of that row is pad_token (default: the
         first stop token), and the result (B, t0 + n), n <= max_new_tokens, is trimmed to the longest row; before its stop a row
         has the tokens of the same call without stop_tokens.  With the device sampler the host looks at the rows' state every
-        stop_poll tokens (the only sync; the result does not depend on it)."""
+        stop_poll tokens (the only sync; the result does not depend on it).
+        prompt_lengths (B integers, 1 <= p_b <= idx.shape[1]): the rows of idx are prompts of different lengths, right-padded;
+        what idx holds at or beyond column p_b is replaced by pad_token on entry and read by nothing.  It needs a pad_token or
+        stop_tokens.  Every row gets up to max_new_tokens tokens after its own prompt: the result (B, n), n = the longest final
+        row, holds per row the prompt, its tokens, then pad_token; a row ends at p_b + max_new_tokens or at its stop token.  One
+        shared position walks all rows from min p_b: a row still inside its prompt keeps its prompt token, a row past it samples
+        (dg_sample_rows_ragged), so row b has the tokens of a call on prompt b alone in that row with the same seed.
+        return_lengths=True: (ids, the rows' final lengths as int64 [B]), in any call."""
         req = Sampling.checked(self.token_embedding_table.weight.shape[0], generator, sampler, temperature, top_k, seed, top_p, min_p,
-                               repetition_penalty, presence_penalty, frequency_penalty, logit_bias, stop_tokens, pad_token, stop_poll)
+                               repetition_penalty, presence_penalty, frequency_penalty, logit_bias, stop_tokens, pad_token, stop_poll,
+                               prompt_lengths, tuple(getattr(idx, "shape", ())), return_lengths)
+        idx, done = req.enter(idx, max_new_tokens)
+        if done is not None:
+            return done
         return (self._generate_device if sampler == "device" else self._generate_host)(idx, max_new_tokens, req)
 
     @torch.no_grad()
@@ -379,25 +472,42 @@ class _LM(HipModule):
         """the host loop, the reference's: per token the last-position logits of the sequence so far from `source` (default: the
         full forward on the cropped window), their distribution, ONE multinomial on the CPU generator, the stop rule, append,
         count.  Stop rule: a finished row gets pad_token; a row that draws a stop token keeps it and is finished from the next
-        position on; the loop ends once every row is."""
+        position on; the loop ends once every row is.  With prompt_lengths the loop starts from idx[:, :min p_b]; a row still
+        inside its prompt takes its prompt token in the place of its draw (forced: already in its counts, and never a stop), and
+        a row that receives the last token of its budget is finished under the same rule."""
         V = self.token_embedding_table.weight.shape[0]
         source = source or self._window_logits
         params = req.params(idx.device)
-        cs = ControlOperands.fresh(req.ctl, idx, V, lengths=False)
+        cs = ControlOperands.fresh(req.ctl, idx, V, lengths=False, first=req.prompt_lengths, n_new=max_new_tokens)
+        t0, total = req.span(idx.shape[1], max_new_tokens)
         finished = torch.zeros(idx.shape[0], dtype=torch.bool)
-        for _ in range(max_new_tokens):
+        ends = req.stop or req.ragged                    # rows can end before the loop does
+        final = torch.zeros(idx.shape[0], dtype=torch.int64) if ends else None          # 0: running
+        if req.ragged:
+            prompt, first = idx.cpu(), torch.tensor(req.prompt_lengths)
+            idx = idx[:, :t0]
+        for L in range(t0, total):
             probs = self._probs(source(idx), params, cs if req.adjust else None)
             nxt = torch.multinomial(probs.cpu(), num_samples=1, generator=req.generator)
-            if req.stop:
+            forced = None
+            if req.ragged and L < prompt.shape[1]:
+                forced = first > L
+                nxt = torch.where(forced[:, None], prompt[:, L:L + 1], nxt)
+            if ends:
                 nxt = torch.where(finished[:, None], torch.full_like(nxt, req.ctl["pad"]), nxt)
-                finished = finished | torch.isin(nxt[:, 0], torch.tensor(req.stop))
+                hit = torch.isin(nxt[:, 0], torch.tensor(req.stop)) if req.stop else torch.zeros_like(finished)
+                if req.ragged:
+                    hit = (hit if forced is None else hit & ~forced) | (first + max_new_tokens <= L + 1)
+                final = torch.where(hit & ~finished, torch.full_like(final, L + 1), final)
+                finished = finished | hit
             nxt = nxt.to(idx.device)
             idx = torch.cat((idx, nxt), dim=1)
             if req.adjust:
-                ops.token_counts(nxt, 1, V, cs.counts, accumulate=True)
-            if req.stop and bool(finished.all()):
+                ops.token_counts(nxt, 1 if forced is None else (~forced).to(device=idx.device, dtype=torch.int32), V, cs.counts,
+                                 accumulate=True)
+            if ends and bool(finished.all()):
                 break
-        return idx
+        return trim_to_longest(idx, final, total, req.return_lengths)
 
     @staticmethod
     def _prompt_shape(idx):          # the device-sampler paths' first check
@@ -406,24 +516,28 @@ class _LM(HipModule):
             raise ValueError("idx must be (B, T) with T >= 1")
         return idx.shape
 
-    def _decode_begin(self, idx, req: Sampling, ids, graph: bool = False):
-        """the device-sampler paths' start: the prompt is range-checked once and goes into ids; returns (decode state, params)"""
+    def _decode_begin(self, idx, req: Sampling, ids, t0: int, graph: bool = False):
+        """the device-sampler paths' start: the prompt is range-checked once and goes into ids; returns (decode state at the first
+        position t0, params)"""
         self._check_ids(idx, None)
         ids[:, :idx.shape[1]] = idx
-        return req.first_state(idx.device, idx.shape[1]), req.params(idx.device, graph)
+        return req.first_state(idx.device, t0), req.params(idx.device, graph)
 
     @torch.no_grad()
     def _generate_device(self, idx, max_new_tokens, req: Sampling):
         """the reference algorithm (full forward on the cropped window per token) with the sampler on the device: the kernel writes
         token L into ids[:, L]; no host copy or sync inside the loop (the ids were range-checked once, sampled ids are in range).
-        With stop tokens the host reads the rows' lengths every req.poll tokens and leaves once every row is finished."""
-        B, t0 = self._prompt_shape(idx)
-        total, ctx = t0 + max_new_tokens, self.context_length
+        With stop tokens the host reads the rows' lengths every req.poll tokens and leaves once every row is finished.
+        With prompt_lengths L starts at min p_b and every step ends in dg_sample_rows_ragged, which leaves the rows still inside
+        their prompts alone."""
+        B, T = self._prompt_shape(idx)
+        (t0, total), ctx = req.span(T, max_new_tokens), self.context_length
         ids = torch.zeros((B, total), dtype=torch.int64, device=idx.device)
-        state, params = self._decode_begin(idx, req, ids)
-        cs = ControlOperands.fresh(req.ctl, idx, self.token_embedding_table.weight.shape[0], lengths=True)
-        kw = {} if cs is None else cs.kw()
-        lengths = cs.lengths if req.poll else None
+        state, params = self._decode_begin(idx, req, ids, t0)
+        cs = ControlOperands.fresh(req.ctl, idx, self.token_embedding_table.weight.shape[0], lengths=True, first=req.prompt_lengths,
+                                   n_new=max_new_tokens)
+        kw = {} if cs is None else cs.kw(req.ragged)
+        lengths = cs.lengths if req.poll or req.ragged else None
         saved = self.__dict__.get("check_ids")           # None: the class's default is in force
         self.check_ids = False
         try:
@@ -438,7 +552,7 @@ class _LM(HipModule):
             del self.check_ids
             if saved is not None:
                 self.check_ids = saved
-        return trim_to_longest(ids, lengths, total)
+        return trim_to_longest(ids, lengths, total, req.return_lengths)
 
 
 class BigramLM(_LM):
@@ -637,7 +751,7 @@ class TransformerLM(_BlocksLM):
                  sampler: str = "host", temperature: float = 1.0, top_k: Optional[int] = None, seed: Optional[int] = None,
                  top_p: Optional[float] = None, min_p: Optional[float] = None, repetition_penalty: float = 1.0,
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, stop_tokens=None,
-                 pad_token: Optional[int] = None, stop_poll: int = 64):
+                 pad_token: Optional[int] = None, stop_poll: int = 64, prompt_lengths=None, return_lengths: bool = False):
         """ref: src/model.py:611-636.  While the sequence still fits the context window the per-layer K/V of the
         tokens seen so far are kept (training layout, [B, ctx, 3C]) and only the new position is computed; once the
         window starts to slide every position embedding shifts, the cache is void, and decoding continues exactly
@@ -648,13 +762,19 @@ class TransformerLM(_BlocksLM):
         included and beyond the context window): as in _LM.generate.  sampler="device" in eval() mode with
         use_cache=True replays one captured graph per token (decode.DeviceDecoder): no host work inside the loop, and the same
         graphs for every setting of the sampler; a call with any control replays a second pair of graphs, captured once, whose
-        sampler is dg_sample_rows_control."""
+        sampler is dg_sample_rows_control.  prompt_lengths / return_lengths: as in _LM.generate; the graph-replayed path prefills
+        idx[:, :min p_b] in one pass, the rows with longer prompts ride along through their remaining prompt tokens one step
+        each, and a third pair of graphs, whose sampler is dg_sample_rows_ragged, is captured on the first such call."""
         req = Sampling.checked(self.token_embedding_table.weight.shape[0], generator, sampler, temperature, top_k, seed, top_p, min_p,
-                               repetition_penalty, presence_penalty, frequency_penalty, logit_bias, stop_tokens, pad_token, stop_poll)
+                               repetition_penalty, presence_penalty, frequency_penalty, logit_bias, stop_tokens, pad_token, stop_poll,
+                               prompt_lengths, tuple(getattr(idx, "shape", ())), return_lengths)
+        idx, done = req.enter(idx, max_new_tokens)
+        if done is not None:
+            return done
         cached = use_cache and not self.training
         if sampler == "device":
             return (self._generate_device_cached if cached else self._generate_device)(idx, max_new_tokens, req)
-        if cached and idx.shape[1] < self.context_length:
+        if cached and req.span(idx.shape[1], 0)[0] < self.context_length:
             return self._generate_host(idx, max_new_tokens, req, self._kv_logits(idx))
         return self._generate_host(idx, max_new_tokens, req)
 
@@ -670,33 +790,36 @@ class TransformerLM(_BlocksLM):
         L <= ctx, the full-window step after that.  graph=True replays the two captured graphs of decode.DeviceDecoder;
         graph=False launches the very same steps eagerly.  With a control the steps end in dg_sample_rows_control on the decoder's
         operands, and graph=True replays the decoder's second pair of graphs; with stop tokens the host reads lengths every
-        req.poll tokens."""
+        req.poll tokens.  With prompt_lengths L starts at min p_b (the prefill is that of idx[:, :min p_b]; none if it does not fit
+        the window), the steps end in dg_sample_rows_ragged, and graph=True replays the decoder's third pair."""
         from .decode import DeviceDecoder
-        B, t0 = self._prompt_shape(idx)
-        total, ctx = t0 + max_new_tokens, self.context_length
+        B, T = self._prompt_shape(idx)
+        (t0, total), ctx = req.span(T, max_new_tokens), self.context_length
         key = (B, idx.device, self.act_dtype, self.split_bf16)
         decs = self.__dict__.setdefault("_decoders", {})
         dec = decs.get(key)
         if dec is None or dec.cap < total:
             dec = decs[key] = DeviceDecoder(self, B, idx.device, total)
         dec.refresh(self)                      # a generate() after an optimizer step sees the new weights
-        controls = req.ctl is not None
+        mode = "ragged" if req.ragged else "plain" if req.ctl is None else "control"
         if graph:
-            dec.capture(controls)
-        state, params = self._decode_begin(idx, req, dec.ids, graph=True)      # the decoder's block: four words, replayed or not
+            dec.capture(mode)
+        state, params = self._decode_begin(idx, req, dec.ids, t0, graph=True)      # the decoder's block: four words, replayed or not
         dec.state.copy_(state)
         dec.params.copy_(params)
-        if controls:
-            dec.operands.begin(req.ctl, dec.ids, t0)
-        lengths = dec.lengths if req.poll else None
+        if mode != "plain":
+            dec.operands.begin(req.ctl, dec.ids, T, req.prompt_lengths, max_new_tokens)
+        lengths = dec.lengths if req.poll or req.ragged else None
         L = t0
-        if max_new_tokens > 0 and t0 < ctx:
-            dec.tail(self._prefill(idx.contiguous(), dec.caches, dec.ws, dec.w_lm), controls)
+        prefill = max_new_tokens > 0 and t0 < ctx
+        if prefill:
+            dec.tail(self._prefill(idx[:, :t0].contiguous(), dec.caches, dec.ws, dec.w_lm), mode)
             L += 1
         while L < total and not (L > t0 and stop_poll_due(req.poll, L - t0, lengths)):
-            dec.step(cached=L <= ctx, graph=graph, controls=controls)
+            dec.step(cached=prefill and L <= ctx, graph=graph, mode=mode)      # no prefill: the caches hold nothing to step on
             L += 1
-        return trim_to_longest(dec.ids, lengths, total).clone()
+        out = trim_to_longest(dec.ids, lengths, total, req.return_lengths)
+        return (out[0].clone(), out[1]) if req.return_lengths else out.clone()
 
 
 MODEL_CLASSES = OrderedDict(

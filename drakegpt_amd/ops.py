@@ -902,18 +902,29 @@ def _chk_counts(what: str, counts: Tensor, M: int, V: int) -> None:
         raise RuntimeError(f"{what}: counts must be int32 [M = {M}, >= V = {V}]")
 
 
-def token_counts(ids: Tensor, n: int, V: int, counts: Optional[Tensor] = None, accumulate: bool = False) -> Tensor:
+def token_counts(ids: Tensor, n, V: int, counts: Optional[Tensor] = None, accumulate: bool = False) -> Tensor:
     """int32 [M, V] (or the given counts [M, >= V]): how often each token occurs in ids[m, :n] (dg_token_counts; ids int64 [M, cap],
-    rows may be strided, clamped to [0, V) as the embedding does).  accumulate=False zeroes the counts first."""
+    rows may be strided, clamped to [0, V) as the embedding does).  accumulate=False zeroes the counts first.
+    n may also be a device int32 tensor [M] of any stride, a prefix length per row, clamped to [0, cap] (dg_token_counts_rows)."""
     _chk(ids, "ids", torch.int64, contiguous=False)
-    if ids.dim() != 2 or ids.stride(1) != 1 or not 0 <= n <= ids.shape[1]:
+    per_row = isinstance(n, torch.Tensor)
+    if ids.dim() != 2 or ids.stride(1) != 1 or not (per_row or 0 <= n <= ids.shape[1]):
         raise RuntimeError("token_counts: ids must be [M, capacity >= n] with unit column stride")
     M = ids.shape[0]
+    if per_row:
+        _chk(n, "n", torch.int32, contiguous=False)
+        # the kernel clamps a row's n to the row stride: whole rows only, so that the clamp is the capacity
+        if n.dim() != 1 or n.shape[0] != M or n.stride(0) < 0 or _ld(ids) != ids.shape[1]:
+            raise RuntimeError(f"token_counts: a per-row n must be int32 [M = {M}] and ids whole rows [M, capacity]")
     if counts is None:
         if accumulate:
             raise ValueError("token_counts: accumulate=True needs counts")
         counts = torch.empty((M, V), dtype=torch.int32, device=ids.device)
     _chk_counts("token_counts", counts, M, V)
+    if per_row:
+        check(lib.dg_token_counts_rows(_p(ids), ids.shape[1], M, _p(n), n.stride(0), int(V), _p(counts), _ld(counts),
+                                       int(bool(accumulate)), _stream()), "dg_token_counts_rows")
+        return counts
     check(lib.dg_token_counts(_p(ids), max(_ld(ids), n), M, int(n), int(V), _p(counts), _ld(counts), int(bool(accumulate)), _stream()),
           "dg_token_counts")
     return counts
@@ -923,12 +934,14 @@ def sample_rows(logits: Tensor, state: Optional[Tensor] = None, params: Optional
                 L: Optional[int] = None, temperature: float = 1.0, top_k: Optional[int] = None, ids: Optional[Tensor] = None,
                 tokens: bool = True, probs: bool = False, top_p: Optional[float] = None, min_p: Optional[float] = None,
                 control: Optional[Tensor] = None, bias: Optional[Tensor] = None, counts: Optional[Tensor] = None,
-                lengths: Optional[Tensor] = None):
+                lengths: Optional[Tensor] = None, spans: Optional[Tensor] = None):
     """one token per row of fp32 logits [M, V] (dg_sample_rows, or dg_sample_rows_nucleus when params has four words;
     include/drakegpt_hip.h states the semantics).
     control: new_sample_control(...) -- dg_sample_rows_control: penalties on counts int32 [M, >= V] (the kernel adds the token
     it writes), bias fp32 [V] (read when the block's use_bias is set), lengths int32 [M] (stop tokens; needs ids).  The
     parameter block built here then always has four words.  Without control: bias / counts / lengths are refused.
+    spans: int32 [M, 2] {first, end} per row -- dg_sample_rows_ragged: a row with L < first keeps the prompt token that ids[m, L]
+    holds and is left alone, a row that writes position end - 1 is finished.  Needs control, lengths and the 2-D ids.
     state: decode state int32[4] {seed_lo, seed_hi, L, 0} (new_rng_state(seed, device, step=L)); built from seed / L when None.
     params: new_sample_params(...); built from temperature / top_k / top_p / min_p when None.
     ids [B, cap] int64: row m's token is written to ids[m, L] by the kernel (nothing is returned for it); otherwise, with
@@ -943,6 +956,8 @@ def sample_rows(logits: Tensor, state: Optional[Tensor] = None, params: Optional
         raise ValueError("sample_rows: nothing to compute (tokens=False, probs=False)")
     if control is None and (bias is not None or counts is not None or lengths is not None):
         raise ValueError("sample_rows: bias / counts / lengths need control=new_sample_control(...)")
+    if spans is not None and (control is None or lengths is None or ids is None):
+        raise ValueError("sample_rows: spans need control=, lengths= and ids=")
     if params is None:
         params = new_sample_params(temperature, top_k, logits.device, top_p=top_p, min_p=min_p, four=control is not None)
     _chk(params, "params", torch.int32)
@@ -960,10 +975,15 @@ def sample_rows(logits: Tensor, state: Optional[Tensor] = None, params: Optional
             _chk(lengths, "lengths", torch.int32)
             if lengths.numel() != M or ids is None:
                 raise RuntimeError(f"sample_rows: lengths must be int32 [M = {M}] and needs ids=")
+        if spans is not None:
+            _chk(spans, "spans", torch.int32)
+            if tuple(spans.shape) != (M, 2):
+                raise RuntimeError(f"sample_rows: spans must be int32 [M = {M}, 2]")
     if params.numel() not in (2, 4):
         raise RuntimeError("sample_rows: params must hold {inv_temp, top_k} or {inv_temp, top_k, top_p, min_p}")
-    # the one place that picks the entry, from (control given, block length); control takes its four operands after the rest
-    name = "dg_sample_rows_control" if control is not None else "dg_sample_rows" if params.numel() == 2 else "dg_sample_rows_nucleus"
+    # the one place that picks the entry, from (spans given, control given, block length); control takes its operands after the rest
+    name = ("dg_sample_rows_ragged" if spans is not None else "dg_sample_rows_control" if control is not None
+            else "dg_sample_rows" if params.numel() == 2 else "dg_sample_rows_nucleus")
     if want_tok:
         if state is None:
             if seed is None or L is None:
@@ -983,6 +1003,8 @@ def sample_rows(logits: Tensor, state: Optional[Tensor] = None, params: Optional
         tok_ptr = _p(out_tok)
     p_out = torch.empty((M, V), dtype=torch.float32, device=logits.device) if probs else None
     extra = () if control is None else (_p(control), _p(bias), _p(counts), 0 if counts is None else _ld(counts), _p(lengths))
+    if spans is not None:
+        extra += (_p(spans),)
     check(getattr(lib, name)(_p(logits), _ld(logits), M, V, _p(state) if want_tok else None, _p(params), tok_ptr, ld_ids, _p(p_out), V,
                              *extra, _stream()), name)
     if out_tok is not None and probs:

@@ -441,12 +441,35 @@ int dg_sample_rows_control(const float* logits, int64_t ldl, int M, int V, const
                            int64_t* ids, int64_t ld_ids, float* probs, int64_t ldp, const void* control,
                            const float* bias, int32_t* counts, int64_t ldc, int32_t* lengths, void* stream);
 
+/* dg_sample_rows_control for a batch whose rows start at different lengths (right-padded prompts) and share one position L.
+ * spans (device): int32 [M, 2], {first, end} per row with 1 <= first < end: first = the row's prompt length, the position of its
+ * first sampled token; end = first + its budget of new tokens.  ids, lengths and ld_ids > 0 are required.  With L = state[2], per
+ * row, decided before anything else:
+ *   lengths[m] != 0:  finished, as in dg_sample_rows_control: pad_id goes to ids[m, L] (L < ld_ids), nothing else happens.
+ *   L < first:        forced -- ids[m, L] already holds a prompt token.  No logit is read (the row may hold anything, NaN
+ *                     included), nothing is drawn, and ids, counts, lengths and the row of probs stay as they are.
+ *   otherwise:        dg_sample_rows_control on the same operands, bit for bit: y, the filters, the fp64 sums, the same u (keyed
+ *                     by (seed, L, row): a row's draws do not depend on what the other rows do), the token rule,
+ *                     counts[m, t] += 1 and the stop rule.  Then, if lengths[m] is still 0 and L + 1 >= end, the thread that
+ *                     wrote the token also writes lengths[m] = L + 1: the budget is used up, and from the next position on the
+ *                     row is padded like a stopped one.
+ * Refused: NULL spans, NULL lengths, NULL ids, ld_ids == 0, and what dg_sample_rows_control refuses. */
+int dg_sample_rows_ragged(const float* logits, int64_t ldl, int M, int V, const uint32_t* state, const void* params,
+                          int64_t* ids, int64_t ld_ids, float* probs, int64_t ldp, const void* control,
+                          const float* bias, int32_t* counts, int64_t ldc, int32_t* lengths, const int32_t* spans, void* stream);
+
 /* Token counts for dg_sample_rows_control: counts[m, clamp(ids[m * ld_ids + j])] += 1 for j < n (n <= ld_ids), ids clamped to
  * [0, V) as in dg_embed_fwd.  accumulate == 0: row m's V counts are zeroed first.  One workgroup per row (its own barrier
  * orders the zeroes before the increments), integer atomics: the result does not depend on an order.  counts: int32 [M, ldc],
  * ldc >= V; columns V..ldc-1 are never touched.  n == 0 with accumulate == 0 just zeroes. */
 int dg_token_counts(const int64_t* ids, int64_t ld_ids, int M, int n, int V, int32_t* counts, int64_t ldc,
                     int accumulate, void* stream);
+
+/* dg_token_counts with a prefix length per row: row m counts ids[m, 0 .. n_m), n_m = clamp(n_rows[m * n_stride], 0, ld_ids)
+ * (n_rows: device int32; the `first` column of dg_sample_rows_ragged's spans is passed with n_stride = 2).  Zeroing, the
+ * clamping of ids, the integer atomics and the untouched columns V..ldc-1: as in dg_token_counts. */
+int dg_token_counts_rows(const int64_t* ids, int64_t ld_ids, int M, const int32_t* n_rows, int64_t n_stride, int V,
+                         int32_t* counts, int64_t ldc, int accumulate, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Cross entropy, mean over rows -- ref: F.cross_entropy at src/model.py:604-607 (K16).
