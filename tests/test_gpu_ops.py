@@ -489,6 +489,23 @@ def _attn_ref(qkv, B, T, NH, H, keep=None, p=0.0):
 #   (3, 100, 2, 64, 0.3)   3.3e-3 (0.76)            1.4e-1 / 2.0e-1 (0.46)   5.1e-3 / 8.7e-3 (0.35)   3.9e-3 / 3.9e-3 (0.33)
 #   (2, 255, 2, 64, 0.1)   2.3e-3 (0.48)            2.1e-1 / 2.7e-1 (0.26)   5.7e-3 / 9.1e-3 (0.21)   2.2e-3 / 3.8e-3 (0.24)   generic kernels
 #   (2, 256, 2, 128, 0.1)  2.0e-3 (0.49)            2.5e-1 / 3.0e-1 (0.28)   7.0e-3 / 5.9e-3 (0.39)   2.1e-3 / 3.7e-3 (0.23)   generic kernels
+# tests/test_gpu_attention_instances.py (the cases of tests/attention_cases.py: every block order, slot rotation and template instance
+# of the MFMA kernels; shapes at 256 CUs; lse within 2e-7 throughout; the fp8 entry points and the one-head launches bit for bit):
+#   one-tile-2 (1, 2, 1, 0)               1.7e-3 (0.45)    1.7e-3 / 1.7e-3 (0.33)   1.8e-3 / 1.8e-3 (0.33)   1.9e-3 / 1.9e-3 (0.33)   dq floored, see attention_cases.reference
+#   one-tile-2 (1, 2, 1, 0.2)             2.0e-3 (0.52)    4.7e-3 / 4.7e-3 (0.33)   5.2e-3 / 5.2e-3 (0.33)   1.9e-3 / 1.9e-3 (0.33)
+#   one-tile-32 (2, 32, 3, 0)             2.9e-3 (0.64)    2.4e-2 / 2.6e-2 (0.30)   5.8e-3 / 5.9e-3 (0.35)   3.7e-3 / 3.7e-3 (0.33)
+#   one-tile-32 (2, 32, 3, 0.2)           3.2e-3 (0.80)    2.0e-1 / 2.0e-1 (0.33)   1.4e-2 / 1.4e-2 (0.33)   3.5e-3 / 3.5e-3 (0.33)
+#   plain-ragged (3, 66, 3, 0.2)          3.7e-3 (0.78)    1.6e-1 / 1.6e-1 (0.41)   8.5e-3 / 8.6e-3 (0.42)   3.8e-3 / 3.8e-3 (0.33)
+#   plain-5-blocks (2, 160, 2, 0)         2.9e-3 (0.74)    1.3e-2 / 1.1e-2 (0.41)   4.6e-3 / 6.2e-3 (0.38)   3.8e-3 / 3.8e-3 (0.33)
+#   plain-5-blocks (2, 160, 2, 0.2)       3.0e-3 (0.76)    2.1e-1 / 2.1e-1 (0.33)   7.0e-3 / 7.1e-3 (0.37)   3.9e-3 / 3.9e-3 (0.33)
+#   pairs-small (2, 128, 3, 0)            2.9e-3 (0.59)    1.6e-1 / 8.2e-2 (0.65)   6.1e-3 / 7.2e-3 (0.34)   4.2e-3 / 4.2e-3 (0.33)
+#   rotation (107, 250, 3, 0.2)           4.1e-3 (0.89)    5.3e-1 / 5.3e-1 (0.37)   1.0e-2 / 1.7e-2 (0.62)   4.5e-3 / 4.5e-3 (0.33)
+#   heavy-size-4 (37, 126, 23, 0.2)       4.4e-3 (0.91)    4.1e-1 / 4.7e-1 (0.33)   2.2e-2 / 2.3e-2 (0.53)   4.9e-3 / 4.9e-3 (0.33)
+#   heavy-size-8 (141, 256, 3, 0)         3.8e-3 (0.79)    2.9e-1 / 2.1e-1 (0.59)   9.5e-3 / 1.3e-2 (0.33)   4.8e-3 / 4.8e-3 (0.33)
+#   heavy-length (1, 512, 3, 0)           3.3e-3 (0.62)    8.3e-3 / 7.2e-3 (0.42)   5.5e-3 / 6.5e-3 (0.39)   4.0e-3 / 4.0e-3 (0.33)
+#   heavy-length (1, 512, 3, 0.2)         3.3e-3 (0.57)    5.1e-1 / 5.1e-1 (0.36)   6.2e-3 / 5.3e-3 (0.39)   4.1e-3 / 4.1e-3 (0.33)
+#   heavy-length-ragged (1, 482, 3, 0)    3.1e-3 (0.59)    2.9e-2 / 2.9e-2 (0.41)   4.6e-3 / 7.8e-3 (0.36)   4.2e-3 / 4.2e-3 (0.33)
+#   heavy-length-ragged (1, 482, 3, 0.2)  3.2e-3 (0.61)    2.1e-1 / 2.1e-1 (0.60)   4.2e-3 / 4.2e-3 (0.38)   4.4e-3 / 4.4e-3 (0.33)
 # (dq's worst groups are the first query rows, where dq cancels and delta comes from the rounded output: see
 # oracle/parity.py, attention_bwd_bounds_by_position; every later row sits at ~4e-3 for kernel and model alike.)  fp32: forward
 # 2e-7 .. 1e-6 per group, backward <= 8e-6 except query row 0 (3.1e-5 at (2, 256, 3, 64, 0.2); fp32 model there 2.3e-5).
