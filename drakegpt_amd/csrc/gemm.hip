@@ -665,16 +665,19 @@ __global__ __launch_bounds__(768) void gemm_tn_ws_kernel(TnParams p) {
 // (of any problem of the group) with ONE continuous stage pipeline and each tile runs over the whole
 // contraction, so there are no split-K slabs to write, re-read and reduce (they were ~790 MB per step)
 // and no per-matrix launch: 651 tiles of 256 K steps instead of 25 launches of <= 256 short workgroups.
-#define TN_MAX_GROUP 64                       // 32 + 64 x 56 B of kernel arguments (limit 4 KB): GPT-2-small's 49 matrices in one launch
+#define TN_MAX_GROUP 64                       // 40 + 64 x 56 = 3624 B of kernel arguments (limit 4 KB): GPT-2-small's 49 matrices in one launch
 struct TnProblem {
     const char* A; const char* B; float* out;
     int lda_b, ldb_b, ldo;                    // byte strides of A and B (< 2 GB), element stride of out
     int P, Q, R, tiles_q, tile_begin;
 };
-// ws: split-K workspace, [total_tiles][8 waves][16 KB] fp32 partials then [total_tiles][8] flags
-struct TnGroup { int n, total_tiles; int splits, tiles_pad; char* ws; unsigned* err; TnProblem pr[TN_MAX_GROUP]; };
+// ws: split-K workspace, [total_tiles][8 waves][16 KB] fp32 partials of THIS launch; flags: [total_tiles][8] hand-over words at a
+// place every launch of the call shares -- behind the partial area of the call's LARGEST launch (tn_group_most_tiles), so that
+// no launch's flags lie in bytes another launch of the same call uses for partials
+struct TnGroup { int n, total_tiles; int splits, tiles_pad; char* ws; unsigned* flags; unsigned* err; TnProblem pr[TN_MAX_GROUP]; };
 // fp8 operands (round 3): e5m2 dY x e4m3 X with one dequantisation factor per operand (device scalars).  Two more pointers per
-// problem: 48 problems per launch keep the kernel arguments under 4 KB (GPT-2-medium's 96 block matrices: two launches).
+// problem: 48 problems per launch keep the kernel arguments under 4 KB (40 + 48 x 72 = 3496 B; GPT-2-medium's 96 block matrices:
+// two launches).
 #define TN_MAX_GROUP8 48
 struct TnProblem8 {
     const char* A; const char* B; float* out;
@@ -682,7 +685,8 @@ struct TnProblem8 {
     int lda_b, ldb_b, ldo;
     int P, Q, R, tiles_q, tile_begin;
 };
-struct TnGroup8 { int n, total_tiles; int splits, tiles_pad; char* ws; unsigned* err; TnProblem8 pr[TN_MAX_GROUP8]; };
+struct TnGroup8 { int n, total_tiles; int splits, tiles_pad; char* ws; unsigned* flags; unsigned* err; TnProblem8 pr[TN_MAX_GROUP8]; };
+static_assert(sizeof(TnGroup) <= 4096 && sizeof(TnGroup8) <= 4096, "kernel arguments: 4 KB");
 template <bool F8> struct TnGroupOf { typedef TnGroup type; };
 template <> struct TnGroupOf<true> { typedef TnGroup8 type; };
 
@@ -885,7 +889,7 @@ __global__ __launch_bounds__(768) void gemm_tn_grouped256_kernel(typename TnGrou
         if (cx.half != 2) {
             // per wave 4 x 4 accumulators of 1 KB (64 lanes x 16 B): 16 KB
             float* part = (float*)(gp.ws + ((size_t)cx.tile * 8 + wave) * 16384);
-            unsigned* flag = (unsigned*)(gp.ws + (size_t)gp.total_tiles * 8 * 16384) + cx.tile * 8 + wave;
+            unsigned* flag = gp.flags + cx.tile * 8 + wave;
             // The partials move as (64 lanes x 16 B) pieces with the sc0 sc1 cache bits: system-scope write-through
             // stores and L2-bypassing loads, i.e. coherent between XCDs without any cache-wide maintenance.  (One relaxed
             // agent-scope atomic per float -- the portable spelling -- cost ~30 us per hand-over.)
@@ -1148,6 +1152,32 @@ __device__ __forceinline__ void gemm_tn_f32_body(const TnParams& p) {
 __global__ __launch_bounds__(256) void gemm_tn_f32_kernel(TnParams p) { gemm_tn_f32_body<false>(p); }
 __global__ __launch_bounds__(256) void gemm_tn_x3_kernel(TnParams p) { gemm_tn_f32_body<true>(p); }
 
+// Every decision of a dg_gemm_tn launch, in one place: dg_gemm_tn launches what this returns and dg_debug_tn_plan reports it.
+enum { TN_K_WS = 0, TN_K_BF16, TN_K_F32, TN_K_X3 };
+static const char* const tn_kernel_names[] = {"gemm_tn_ws_kernel", "gemm_tn_bf16_kernel", "gemm_tn_f32_kernel", "gemm_tn_x3_kernel"};
+struct TnPlan { int kernel, xcd_map, grid_x, grid_y, block, r_per_split, tiles_q, n_tiles; };
+static TnPlan tn_plan(int R, int P, int Q, int n_splits, int dtype, int ncu) {
+    TnPlan pl;
+    pl.tiles_q = (Q + 127) / 128;
+    pl.n_tiles = ((P + 127) / 128) * pl.tiles_q;
+    const int br = dtype == DG_BF16 ? 64 : 32;
+    const int per = (R + n_splits - 1) / n_splits;
+    pl.r_per_split = ((per + br - 1) / br) * br;
+    pl.xcd_map = (n_splits % 8 == 0 || n_splits == 1 || n_splits == 2 || n_splits == 4) ? 1 : 0;
+    pl.grid_x = pl.n_tiles; pl.grid_y = n_splits;
+    if (pl.xcd_map) {
+        const int per_x = n_splits >= 8 ? pl.n_tiles * (n_splits / 8) : (pl.n_tiles + (8 / n_splits) - 1) / (8 / n_splits);
+        pl.grid_x = per_x * 8; pl.grid_y = 1;
+    }
+    // the LDS-DMA kernel owns a CU (128 KB LDS): use it when the launch fits one wave of workgroups,
+    // otherwise two register-staged workgroups per CU finish sooner than a second round
+    const bool one_round = (int64_t)pl.n_tiles * n_splits <= ncu;
+    if (dtype == DG_BF16) pl.kernel = (R % 64 == 0 && one_round) ? TN_K_WS : TN_K_BF16;
+    else pl.kernel = dtype == DG_F32X3 ? TN_K_X3 : TN_K_F32;
+    pl.block = pl.kernel == TN_K_WS ? 768 : 256;
+    return pl;
+}
+
 extern "C" int dg_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb,
                           float* out, int64_t ldo, int64_t split_stride, int n_splits,
                           int R, int P, int Q, int dtype, void* stream) {
@@ -1158,34 +1188,38 @@ extern "C" int dg_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb
     if (lda < P || ldb < Q || ldo < Q) return DG_ERR_ARG;
     if (((P + epc - 1) / epc) * epc > lda || ((Q + epc - 1) / epc) * epc > ldb) return DG_ERR_ARG;
     if (n_splits > 1 && split_stride < (int64_t)(P - 1) * ldo + Q) return DG_ERR_ARG;
+    const TnPlan pl = tn_plan(R, P, Q, n_splits, dtype, dg_num_cus());
     TnParams p;
     p.A = (const char*)A; p.lda_b = lda * esz;
     p.B = (const char*)B; p.ldb_b = ldb * esz;
     p.out = out; p.ldo = ldo; p.split_stride = split_stride;
     p.R = R; p.P = P; p.Q = Q;
-    const int tiles_p = (P + 127) / 128;
-    p.tiles_q = (Q + 127) / 128;
-    p.n_tiles = tiles_p * p.tiles_q;
-    const int br = dtype == DG_BF16 ? 64 : 32;
-    int per = (R + n_splits - 1) / n_splits;
-    p.r_per_split = ((per + br - 1) / br) * br;
+    p.tiles_q = pl.tiles_q;
+    p.n_tiles = pl.n_tiles;
+    p.r_per_split = pl.r_per_split;
     p.n_splits = n_splits;
-    p.xcd_map = (n_splits % 8 == 0 || n_splits == 1 || n_splits == 2 || n_splits == 4) ? 1 : 0;
-    dim3 grid(p.n_tiles, n_splits), block(256);
-    if (p.xcd_map) {
-        const int per_x = n_splits >= 8 ? p.n_tiles * (n_splits / 8) : (p.n_tiles + (8 / n_splits) - 1) / (8 / n_splits);
-        grid = dim3(per_x * 8, 1);
-    }
+    p.xcd_map = pl.xcd_map;
+    const dim3 grid(pl.grid_x, pl.grid_y), block(pl.block);
     hipStream_t s = (hipStream_t)stream;
-    // the LDS-DMA kernel owns a CU (128 KB LDS): use it when the launch fits one wave of workgroups,
-    // otherwise two register-staged workgroups per CU finish sooner than a second round
-    const bool one_round = (int64_t)p.n_tiles * n_splits <= dg_num_cus();
-    if (dtype == DG_BF16 && R % 64 == 0 && one_round)
-        hipLaunchKernelGGL(gemm_tn_ws_kernel, grid, dim3(768), 0, s, p);
-    else if (dtype == DG_BF16) hipLaunchKernelGGL(gemm_tn_bf16_kernel, grid, block, 0, s, p);
-    else if (dtype == DG_F32X3) hipLaunchKernelGGL(gemm_tn_x3_kernel, grid, block, 0, s, p);
-    else hipLaunchKernelGGL(gemm_tn_f32_kernel, grid, block, 0, s, p);
+    switch (pl.kernel) {
+    case TN_K_WS: hipLaunchKernelGGL(gemm_tn_ws_kernel, grid, block, 0, s, p); break;
+    case TN_K_BF16: hipLaunchKernelGGL(gemm_tn_bf16_kernel, grid, block, 0, s, p); break;
+    case TN_K_X3: hipLaunchKernelGGL(gemm_tn_x3_kernel, grid, block, 0, s, p); break;
+    default: hipLaunchKernelGGL(gemm_tn_f32_kernel, grid, block, 0, s, p); break;
+    }
     DG_LAUNCH_CHECK();
+    return DG_OK;
+}
+
+// diagnostic only (tests/tn_cases.py): the plan dg_gemm_tn would launch with `ncu` compute units (0: the device's).  Pure host
+// code, not part of the public header.  out8: kernel, xcd_map, grid_x, grid_y, block, r_per_split, tiles_q, n_tiles.
+extern "C" int dg_debug_tn_plan(int R, int P, int Q, int n_splits, int dtype, int ncu, int* out8, const char** kernel_name) {
+    if (R <= 0 || P <= 0 || Q <= 0 || n_splits <= 0 || ncu < 0 || !out8) return DG_ERR_ARG;
+    if (dtype != DG_BF16 && dtype != DG_F32 && dtype != DG_F32X3) return DG_ERR_DTYPE;
+    const TnPlan pl = tn_plan(R, P, Q, n_splits, dtype, ncu > 0 ? ncu : dg_num_cus());
+    out8[0] = pl.kernel; out8[1] = pl.xcd_map; out8[2] = pl.grid_x; out8[3] = pl.grid_y;
+    out8[4] = pl.block; out8[5] = pl.r_per_split; out8[6] = pl.tiles_q; out8[7] = pl.n_tiles;
+    if (kernel_name) *kernel_name = tn_kernel_names[pl.kernel];
     return DG_OK;
 }
 
@@ -1194,24 +1228,107 @@ static int64_t tn_group_tiles(const dg_tn_problem* problems, int n) {
     for (int i = 0; i < n; ++i) tiles += (int64_t)((problems[i].P + 255) / 256) * ((problems[i].Q + 127) / 128);
     return tiles;
 }
-// split-K workspace for the largest launch group of the call: per 256 x 128 tile 8 x 16 KB of wave partials + 8 flags
+// tiles of the largest launch of a call, whichever operand kind it is made with: the function below has no dtype argument, and
+// bf16 calls are cut into launches of TN_MAX_GROUP problems, fp8 calls into launches of TN_MAX_GROUP8
+static int64_t tn_group_most_tiles(const dg_tn_problem* problems, int n) {
+    int64_t most = 0;
+    for (int maxg : {TN_MAX_GROUP, TN_MAX_GROUP8})
+        for (int base = 0; base < n; base += maxg) {
+            const int64_t t = tn_group_tiles(problems + base, n - base < maxg ? n - base : maxg);
+            if (t > most) most = t;
+        }
+    return most;
+}
+#define TN_PART_BYTES (8 * 16384)             // partials per 256 x 128 tile: 8 MFMA waves x 16 KB
+// split-K workspace of a call: [most][8 x 16 KB] wave partials, [most][8] flags, the sticky error word (last 16 bytes), with
+// most = the tiles of the call's largest launch.  Every launch of the call puts its partials at the front and its flags at
+// most * TN_PART_BYTES (tn_grouped_plan), wherever its own partials end.
 extern "C" int64_t dg_gemm_tn_grouped_workspace_bytes(const dg_tn_problem* problems, int n) {
     if (!problems || n <= 0) return 0;
-    int64_t most = 0;
-    for (int base = 0; base < n; base += TN_MAX_GROUP) {
-        const int64_t t = tn_group_tiles(problems + base, n - base < TN_MAX_GROUP ? n - base : TN_MAX_GROUP);
-        if (t > most) most = t;
+    return tn_group_most_tiles(problems, n) * (TN_PART_BYTES + 8 * 4) + 16;
+}
+
+// Every decision of ONE launch of a dg_gemm_tn_grouped call (problems [first, first + count)), in one place: tn_grouped_launch
+// launches what this returns and dg_debug_tn_grouped_plan reports it.  flag_offset / ws_need: bytes from the workspace's start
+// (ws_need: how far this launch reads or writes it, the error word included; 0 for a launch that is not cut).
+struct TnGroupPlan { int first, count, tiles, tiles_pad, splits, grid; int64_t flag_offset, ws_need; };
+static TnGroupPlan tn_grouped_plan(const dg_tn_problem* problems, int n, int first, bool f8, bool with_ws, int ncu) {
+    const int maxg = f8 ? TN_MAX_GROUP8 : TN_MAX_GROUP, krows = f8 ? 128 : 64;
+    TnGroupPlan pl;
+    pl.first = first;
+    pl.count = n - first < maxg ? n - first : maxg;
+    int nk_min = 1 << 30, nk_max = 0;
+    for (int i = 0; i < pl.count; ++i) {
+        const int nk = problems[first + i].R / krows;
+        if (nk < nk_min) nk_min = nk;
+        if (nk > nk_max) nk_max = nk;
     }
-    return most * (8 * 16384 + 8 * 4) + 16;       // + the sticky error word (last 16 bytes)
+    const int tiles = (int)tn_group_tiles(problems + first, pl.count);
+    pl.tiles = tiles;
+    pl.tiles_pad = (tiles + 7) / 8 * 8;
+    pl.splits = 1;
+    if (with_ws && nk_min >= 2) {
+        // two K halves per tile when that shortens the schedule: rounds x steps per round
+        const int64_t whole = (int64_t)((tiles + ncu - 1) / ncu) * nk_max;
+        const int64_t halves = (int64_t)((2 * pl.tiles_pad + ncu - 1) / ncu) * ((nk_max + 1) / 2);
+        // Cutting EVERY tile is only taken when each workgroup gets one item (2 tiles_pad <= #CUs): the second half of tile t
+        // (workgroup tiles_pad + t) then waits for workgroup t, a lower-numbered one that never waits -- safe whatever part of
+        // the grid is resident.  With several items per workgroup the second halves of tiles [G - tiles_pad % G, G) would sit
+        // on LOWER-numbered workgroups than their producers: a deadlock as soon as fewer than G workgroups are resident.
+        // (With a CU count that is a multiple of 16 the leftover cut below is at least as short whenever cutting every tile
+        // would shorten a multi-round schedule, so the guard only decides on other CU counts.)
+        if (halves < whole && 2 * pl.tiles_pad <= ncu) pl.splits = 2;
+        // cut only the leftover tiles when their halves fit into one half round (see the kernel)
+        const int r = tiles % ncu;
+        if (tiles > ncu && ncu % 16 == 0 && r > 0 && 16 * ((r + 7) / 8) <= ncu) {
+            const int64_t lo = (int64_t)(tiles / ncu) * nk_max + (nk_max + 1) / 2;
+            if (lo <= (pl.splits == 2 ? halves : whole)) pl.splits = 3;
+        }
+    }
+    const int items = pl.splits == 3 ? tiles : pl.splits * pl.tiles_pad;
+    pl.grid = items < ncu ? items : ncu;
+    pl.flag_offset = tn_group_most_tiles(problems, n) * TN_PART_BYTES;
+    // a cut launch uses its partials (tiles <= most: they end at or before flag_offset), its flags and the error word at the
+    // very end of the call's workspace; an uncut one touches none of it
+    pl.ws_need = pl.splits == 1 ? 0 : dg_gemm_tn_grouped_workspace_bytes(problems, n);
+    return pl;
+}
+
+// diagnostic only (tests/tn_cases.py): the launches of dg_gemm_tn_grouped(problems, n, dtype, workspace or NULL) with `ncu`
+// compute units (0: the device's), one row of 8 int64 per launch: first problem, problems, tiles, tiles_pad, splits, grid,
+// flag offset, workspace bytes needed.  Reads R, P, Q of the problems only; pure host code, not part of the public header.
+// Returns the number of launches (at most max_rows are written), or a negative error code.
+extern "C" int dg_debug_tn_grouped_plan(const dg_tn_problem* problems, int n, int dtype, int with_workspace, int ncu,
+                                        int64_t* rows8, int max_rows) {
+    if (!problems || n <= 0 || ncu < 0 || (!rows8 && max_rows > 0)) return DG_ERR_ARG;
+    const bool f8 = dtype == DG_FP8_E5M2;
+    if (dtype != DG_BF16 && !f8) return DG_ERR_DTYPE;
+    for (int i = 0; i < n; ++i)
+        if (problems[i].R <= 0 || problems[i].P <= 0 || problems[i].Q <= 0 || problems[i].R % (f8 ? 128 : 64)) return DG_ERR_ARG;
+    int launches = 0;
+    for (int base = 0; base < n; base += f8 ? TN_MAX_GROUP8 : TN_MAX_GROUP, ++launches) {
+        if (launches >= max_rows) continue;
+        const TnGroupPlan pl = tn_grouped_plan(problems, n, base, f8, with_workspace != 0, ncu > 0 ? ncu : dg_num_cus());
+        int64_t* o = rows8 + 8 * launches;
+        o[0] = pl.first; o[1] = pl.count; o[2] = pl.tiles; o[3] = pl.tiles_pad; o[4] = pl.splits; o[5] = pl.grid;
+        o[6] = pl.flag_offset; o[7] = pl.ws_need;
+    }
+    return launches;
 }
 
 template <typename GroupT, typename ProbT, bool F8, int MAXG>
-static int tn_grouped_launch(const dg_tn_problem* problems, int n, void* workspace, hipStream_t s) {
-    constexpr int KROWS = F8 ? 128 : 64, ESZ = F8 ? 1 : 2;
+static int tn_grouped_launch(const dg_tn_problem* problems, int n, void* workspace, int64_t workspace_bytes, hipStream_t s) {
+    constexpr int ESZ = F8 ? 1 : 2;
+    static_assert(MAXG == (F8 ? TN_MAX_GROUP8 : TN_MAX_GROUP), "tn_grouped_plan cuts the call the same way");
+    const int ncu = dg_num_cus();
+    // nothing is launched unless every launch of the call has its room
+    for (int base = 0; base < n; base += MAXG)
+        if (tn_grouped_plan(problems, n, base, F8, workspace != nullptr, ncu).ws_need > workspace_bytes) return DG_ERR_ARG;
     for (int base = 0; base < n; base += MAXG) {
+        const TnGroupPlan pl = tn_grouped_plan(problems, n, base, F8, workspace != nullptr, ncu);
         GroupT gp;
-        gp.n = n - base < MAXG ? n - base : MAXG;
-        int tiles = 0, nk_min = 1 << 30, nk_max = 0;
+        gp.n = pl.count;
+        int tiles = 0;
         for (int i = 0; i < gp.n; ++i) {
             const dg_tn_problem& q = problems[base + i];
             ProbT& t = gp.pr[i];
@@ -1222,37 +1339,16 @@ static int tn_grouped_launch(const dg_tn_problem* problems, int n, void* workspa
             t.tiles_q = (q.Q + 127) / 128;
             t.tile_begin = tiles;
             tiles += ((q.P + 255) / 256) * t.tiles_q;
-            const int nk = q.R / KROWS;
-            if (nk < nk_min) nk_min = nk;
-            if (nk > nk_max) nk_max = nk;
         }
-        gp.total_tiles = tiles;
-        gp.tiles_pad = (tiles + 7) / 8 * 8;
-        gp.splits = 1;
-        gp.ws = nullptr;
+        if (tiles != pl.tiles) return DG_ERR_ARG;          // (the plan counts tiles with the same formula)
+        gp.total_tiles = pl.tiles;
+        gp.tiles_pad = pl.tiles_pad;
+        gp.splits = pl.splits;
+        const bool cut = pl.splits != 1;
+        gp.ws = cut ? (char*)workspace : nullptr;
+        gp.flags = cut ? (unsigned*)((char*)workspace + pl.flag_offset) : nullptr;
         gp.err = workspace ? (unsigned*)((char*)workspace + dg_gemm_tn_grouped_workspace_bytes(problems, n) - 16) : nullptr;
-        const int ncu = dg_num_cus();
-        if (workspace && nk_min >= 2) {
-            // two K halves per tile when that shortens the schedule: rounds x steps per round
-            const int64_t whole = (int64_t)((tiles + ncu - 1) / ncu) * nk_max;
-            const int64_t halves = (int64_t)((2 * gp.tiles_pad + ncu - 1) / ncu) * ((nk_max + 1) / 2);
-            // Cutting EVERY tile is only taken when each workgroup gets one item (2 tiles_pad <= #CUs): the second half of tile t
-            // (workgroup tiles_pad + t) then waits for workgroup t, a lower-numbered one that never waits -- safe whatever part of
-            // the grid is resident.  With several items per workgroup the second halves of tiles [G - tiles_pad % G, G) would sit
-            // on LOWER-numbered workgroups than their producers: a deadlock as soon as fewer than G workgroups are resident.
-            // (With a CU count that is a multiple of 16 the leftover cut below is at least as short whenever cutting every tile
-            // would shorten a multi-round schedule, so the guard only decides on other CU counts.)
-            if (halves < whole && 2 * gp.tiles_pad <= ncu) { gp.splits = 2; gp.ws = (char*)workspace; }
-            // cut only the leftover tiles when their halves fit into one half round (see the kernel)
-            const int r = tiles % ncu;
-            if (tiles > ncu && ncu % 16 == 0 && r > 0 && 16 * ((r + 7) / 8) <= ncu) {
-                const int64_t lo = (int64_t)(tiles / ncu) * nk_max + (nk_max + 1) / 2;
-                if (lo <= (gp.splits == 2 ? halves : whole)) { gp.splits = 3; gp.ws = (char*)workspace; }
-            }
-        }
-        const int items = gp.splits == 3 ? tiles : gp.splits * gp.tiles_pad;
-        const int grid = items < ncu ? items : ncu;
-        hipLaunchKernelGGL((gemm_tn_grouped256_kernel<0, F8>), dim3(grid), dim3(768), 0, s, gp);
+        hipLaunchKernelGGL((gemm_tn_grouped256_kernel<0, F8>), dim3(pl.grid), dim3(768), 0, s, gp);
         DG_LAUNCH_CHECK();
     }
     return DG_OK;
@@ -1275,6 +1371,6 @@ extern "C" int dg_gemm_tn_grouped(const dg_tn_problem* problems, int n, int dtyp
     }
     if (workspace && (!dg_aligned16(workspace) || workspace_bytes < dg_gemm_tn_grouped_workspace_bytes(problems, n))) return DG_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    if (f8) return tn_grouped_launch<TnGroup8, TnProblem8, true, TN_MAX_GROUP8>(problems, n, workspace, s);
-    return tn_grouped_launch<TnGroup, TnProblem, false, TN_MAX_GROUP>(problems, n, workspace, s);
+    if (f8) return tn_grouped_launch<TnGroup8, TnProblem8, true, TN_MAX_GROUP8>(problems, n, workspace, workspace_bytes, s);
+    return tn_grouped_launch<TnGroup, TnProblem, false, TN_MAX_GROUP>(problems, n, workspace, workspace_bytes, s);
 }

@@ -266,7 +266,15 @@ int dg_gemm_tn_grouped(const dg_tn_problem* problems, int n, int dtype, void* wo
  * first halves run FIRST on even XCDs and their second halves LAST on the next-numbered workgroup.  Under in-order workgroup
  * dispatch the wait therefore resolves whatever part of the grid is resident.  It is bounded all the same (~1 s): a wave
  * that runs out sets the sticky error word in the LAST 16 BYTES of the workspace (uint32, non-zero = some result of some
- * launch since the workspace was zeroed is invalid) instead of hanging the GPU; the host may read it at any sync point. */
+ * launch since the workspace was zeroed is invalid) instead of hanging the GPU; the host may read it at any sync point.
+ * Layout.  A call of more than 64 (bf16) or 48 (fp8) problems is several launches on the one workspace.  With T = the tiles
+ * (256 x 128) of the call's largest launch under EITHER chunking -- the size function has no dtype argument --
+ *   [0, T * 128 KB)                  partials, tile t of a launch at t * 128 KB (8 waves x 16 KB);
+ *   [T * 128 KB, T * 128 KB + 32 T)  hand-over flags, 8 words per tile, at the SAME place for every launch of the call;
+ *   the last 16 bytes                the sticky error word,
+ * so dg_gemm_tn_grouped_workspace_bytes = T * (128 KB + 32) + 16, "the last 16 bytes" are those of that size whatever
+ * workspace_bytes says, and no launch's flags lie where another launch of the call keeps partials.  DG_ERR_ARG, before
+ * anything is launched, if workspace_bytes is less than any launch of the call needs. */
 int64_t dg_gemm_tn_grouped_workspace_bytes(const dg_tn_problem* problems, int n);
 
 /* out[i] = sum_{g < n_partials} partials[g*stride + i], i < n.  Deterministic order. */

@@ -25,6 +25,13 @@ def rel(a, b):
     return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
 
 
+def within(got, ref, A, B, K, name):
+    """every element within the envelope of an fp32 sum of K exact bf16 products (K = R for a whole tile, R + 1 where two K
+    halves are added): a wrong 16-byte chunk or K step that the whole-tensor ratio hides"""
+    from oracle import parity
+    return parity.assert_within_rounding(got, ref, parity.gemm_envelope(A.T, B.T, K=K), ulps=0, name=name)
+
+
 def tiles(P, Q):
     """256 x 128 tiles of a P x Q problem"""
     return -(-P // 256) * -(-Q // 128)
@@ -65,9 +72,11 @@ def test_single_problem(dev, R, P, Q):
     probs = [(A, B, torch.empty(P * Q, device=dev), P, Q)]
     whole = run(probs, None)[0]
     assert rel(whole.view(P, Q), ref) < TOL, rel(whole.view(P, Q), ref)
+    within(whole.view(P, Q), ref, A, B, R, f"{P}x{Q} R={R} whole")
     ws = ops.gemm_tn_grouped_workspace(probs, dev)
     halves = run(probs, ws)[0]                                    # every tile in two K halves, handed over through the workspace
     assert rel(halves.view(P, Q), ref) < TOL, rel(halves.view(P, Q), ref)
+    within(halves.view(P, Q), ref, A, B, R + 1, f"{P}x{Q} R={R} halves")
     assert status(ws) == 0
 
 
@@ -83,10 +92,12 @@ def test_group_of_all(dev, R):
     assert sum(tiles(P, Q) for P, Q in SHAPES) == 66
     for o, ref, (P, Q) in zip(run(probs, None), refs, SHAPES):
         assert rel(o.view(P, Q), ref) < TOL, (P, Q, rel(o.view(P, Q), ref))
+        within(o.view(P, Q), ref, *operands(dev, R, P, Q)[:2], R, f"group {P}x{Q} R={R} whole")
     ws = ops.gemm_tn_grouped_workspace(probs, dev)
     first, second = run(probs, ws), run(probs, ws)
     for a, b, ref, (P, Q) in zip(first, second, refs, SHAPES):
         assert rel(a.view(P, Q), ref) < TOL, (P, Q, rel(a.view(P, Q), ref))
+        within(a.view(P, Q), ref, *operands(dev, R, P, Q)[:2], R + 1, f"group {P}x{Q} R={R} halves")
         assert torch.equal(a, b), (P, Q)
     assert status(ws) == 0
 
@@ -130,6 +141,7 @@ def test_padded_operands_and_output_view(dev, R, P, Q):
                                              w.numel() if w is not None else 0, ops._stream()), "dg_gemm_tn_grouped")
         torch.cuda.synchronize()
         assert rel(out[:, :Q], ref) < TOL, rel(out[:, :Q], ref)
+        within(out[:, :Q], ref, A[:, :P], B[:, :Q], R + 1, f"padded {P}x{Q} R={R}")
         assert torch.isnan(out[:, Q:]).all()
     assert status(ws) == 0
 
@@ -144,4 +156,5 @@ def test_half_height_rows_match_full_height(dev, R):
     for ws in (None, ops.gemm_tn_grouped_workspace(probs, dev)):
         part, full = run(probs, ws)
         assert rel(full.view(768, 384), ref) < TOL
+        within(full.view(768, 384), ref, A, B, R + 1, f"768x384 R={R}")
         assert torch.equal(part.view(640, 384), full.view(768, 384)[:640])

@@ -168,6 +168,11 @@ def test_gemm_tn(dev, dtype, R, P, Q, S):
     out = torch.empty(P, Q, device=dev)
     ops.reduce_partials(part, P * Q, S, out, P * Q)
     assert rel(out, ref) < 3e-6, rel(out, ref)
+    # every element: the fp32 sum of a slab's rows (bf16 products are exact in fp32, an fp32 product is rounded once before it is
+    # added) and the S - 1 additions of dg_reduce_partials -- at most (2) R + S roundings of a running sum bounded by sum |a||b|
+    from oracle import parity
+    K = (1 if dtype == torch.bfloat16 else 2) * R + S
+    parity.assert_within_rounding(out, ref, parity.gemm_envelope(A.T, B.T, K=K), ulps=0, name=f"gemm_tn {dtype} {R}x{P}x{Q} S={S}")
 
 
 @pytest.mark.parametrize("with_short", [True, False])
