@@ -87,14 +87,8 @@ __device__ __forceinline__ float attn_f8_chunk(u32x4 v, float sc, float m, uint8
     float w[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) { const float f = (float)t[e]; m = dg_amax_nan(m, f); w[e] = dg_fp8_clamp(f * sc, fmax); }
-    int lo = 0, hi = 0;
-    if (BF8) {
-        lo = __builtin_amdgcn_cvt_pk_bf8_f32(w[0], w[1], lo, false); lo = __builtin_amdgcn_cvt_pk_bf8_f32(w[2], w[3], lo, true);
-        hi = __builtin_amdgcn_cvt_pk_bf8_f32(w[4], w[5], hi, false); hi = __builtin_amdgcn_cvt_pk_bf8_f32(w[6], w[7], hi, true);
-    } else {
-        lo = __builtin_amdgcn_cvt_pk_fp8_f32(w[0], w[1], lo, false); lo = __builtin_amdgcn_cvt_pk_fp8_f32(w[2], w[3], lo, true);
-        hi = __builtin_amdgcn_cvt_pk_fp8_f32(w[4], w[5], hi, false); hi = __builtin_amdgcn_cvt_pk_fp8_f32(w[6], w[7], hi, true);
-    }
+    int lo, hi;
+    dg_fp8_pack8<BF8>(w, lo, hi);
     typedef int i32x2 __attribute__((ext_vector_type(2)));
     *(i32x2*)q = (i32x2){lo, hi};
     return m;

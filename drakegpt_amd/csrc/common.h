@@ -115,6 +115,32 @@ __device__ __forceinline__ float dg_fp8_scale_of(float amax, float fmax) {      
     return amax == 0.f ? 1.f : (amax < __builtin_inff() ? fmax / amax : __builtin_nanf(""));
 }
 __device__ __forceinline__ float dg_fp8_clamp(float w, float fmax) { return w > fmax ? fmax : (w < -fmax ? -fmax : w); }   // NaN stays NaN
+// four / eight fp32 values (scaled and clamped by the caller) -> one / two dwords of fp8 bytes; BF8: e5m2, else e4m3
+template <bool BF8>
+__device__ __forceinline__ int dg_fp8_pack4(float a, float b, float c, float d) {
+    int w = 0;
+    if (BF8) { w = __builtin_amdgcn_cvt_pk_bf8_f32(a, b, w, false); w = __builtin_amdgcn_cvt_pk_bf8_f32(c, d, w, true); }
+    else { w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, w, false); w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true); }
+    return w;
+}
+template <bool BF8>
+__device__ __forceinline__ void dg_fp8_pack8(const float (&v)[8], int& lo, int& hi) {
+    lo = dg_fp8_pack4<BF8>(v[0], v[1], v[2], v[3]);
+    hi = dg_fp8_pack4<BF8>(v[4], v[5], v[6], v[7]);
+}
+// Delayed scaling, two slots (dg_fp8_quantize_delayed in fp8.hip has the protocol): parts2 = [2][n_parts] partial maxima owned by
+// the call site; the slot of the step word's parity is written by this launch (one entry per workgroup), the other one holds last
+// step's maxima and is reduced to this launch's scale.  How a kernel reduces `prev` is its own (a wave on 256 partials below,
+// a workgroup on n_parts or on 1024 threads at the call sites).
+struct DgFp8Slots { const float* prev; float* next; };
+__device__ __forceinline__ DgFp8Slots dg_fp8_slots(float* parts2, const uint32_t* step_word, int n_parts) {
+    const int parity = (int)(step_word[2] & 1u);
+    return {parts2 + (int64_t)(parity ^ 1) * n_parts, parts2 + (int64_t)parity * n_parts};
+}
+// the maximum of 256 partials, by every wave for itself: four loads per lane, no LDS, no barrier
+__device__ __forceinline__ float dg_fp8_amax_256(const float* prev, int lane) {
+    return wave_amax_nan(dg_amax_nan(dg_amax_nan(prev[lane], prev[64 + lane]), dg_amax_nan(prev[128 + lane], prev[192 + lane])));
+}
 
 // ---------------------------------------------------------------------------------------------
 // typed load/store of one element as float

@@ -48,18 +48,6 @@ extern "C" int dg_fp8_amax(const void* x, int dtype, int64_t n, const int64_t* s
     return DG_OK;
 }
 
-// eight fp32 values -> eight fp8 bytes (two dwords), saturating at fmax after the scale
-template <bool BF8>
-__device__ __forceinline__ void fp8_pack8(const float (&v)[8], int& lo, int& hi) {
-    lo = 0; hi = 0;
-    if (BF8) {
-        lo = __builtin_amdgcn_cvt_pk_bf8_f32(v[0], v[1], lo, false); lo = __builtin_amdgcn_cvt_pk_bf8_f32(v[2], v[3], lo, true);
-        hi = __builtin_amdgcn_cvt_pk_bf8_f32(v[4], v[5], hi, false); hi = __builtin_amdgcn_cvt_pk_bf8_f32(v[6], v[7], hi, true);
-    } else {
-        lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], lo, false); lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], lo, true);
-        hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[4], v[5], hi, false); hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[6], v[7], hi, true);
-    }
-}
 template <typename T>
 __device__ __forceinline__ void fp8_load8(const T* p, float (&v)[8]) {
     if constexpr (sizeof(T) == 2) {
@@ -110,8 +98,8 @@ __global__ __launch_bounds__(256) void fp8_quantize_kernel(const T* __restrict__
 #pragma unroll
             for (int e = 0; e < 8; ++e) { v0[e] = dg_fp8_clamp(v0[e] * sc, fmax); v1[e] = dg_fp8_clamp(v1[e] * sc, fmax); }
             int a, bq, c, d;
-            fp8_pack8<BF8>(v0, a, bq);
-            fp8_pack8<BF8>(v1, c, d);
+            dg_fp8_pack8<BF8>(v0, a, bq);
+            dg_fp8_pack8<BF8>(v1, c, d);
             *(i32x4*)(q + first + i * 16) = (i32x4){a, bq, c, d};
         }
         return;
@@ -122,7 +110,7 @@ __global__ __launch_bounds__(256) void fp8_quantize_kernel(const T* __restrict__
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = dg_fp8_clamp(v[e] * sc, fmax);
         int lo, hi;
-        fp8_pack8<BF8>(v, lo, hi);
+        dg_fp8_pack8<BF8>(v, lo, hi);
         *(i32x2*)(q + first + i * 8) = (i32x2){lo, hi};
     }
 }
@@ -163,11 +151,9 @@ __global__ __launch_bounds__(1024) void fp8_quantize_delayed_kernel(const T* __r
                                                                     float* __restrict__ parts2, const uint32_t* __restrict__ step_word,
                                                                     float* __restrict__ scale_inv) {
     __shared__ float red[16];
-    const int parity = (int)(step_word[2] & 1u);
-    const float* prev = parts2 + (parity ^ 1) * DG_FP8_AMAX_PARTS;
-    float* next = parts2 + parity * DG_FP8_AMAX_PARTS;
+    const DgFp8Slots slot = dg_fp8_slots(parts2, step_word, DG_FP8_AMAX_PARTS);
     const float fmax = BF8 ? FP8_E5M2_MAX : FP8_E4M3_MAX;
-    float am = threadIdx.x < DG_FP8_AMAX_PARTS ? prev[threadIdx.x] : 0.f;
+    float am = threadIdx.x < DG_FP8_AMAX_PARTS ? slot.prev[threadIdx.x] : 0.f;
     am = wave_amax_nan(am);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = am;
     __syncthreads();
@@ -195,8 +181,8 @@ __global__ __launch_bounds__(1024) void fp8_quantize_delayed_kernel(const T* __r
                 v0[e] = dg_fp8_clamp(v0[e] * sc, fmax); v1[e] = dg_fp8_clamp(v1[e] * sc, fmax);
             }
             int a, b, c, d;
-            fp8_pack8<BF8>(v0, a, b);
-            fp8_pack8<BF8>(v1, c, d);
+            dg_fp8_pack8<BF8>(v0, a, b);
+            dg_fp8_pack8<BF8>(v1, c, d);
             *(i32x4*)(q + i * 16) = (i32x4){a, b, c, d};
         }
     } else {
@@ -206,7 +192,7 @@ __global__ __launch_bounds__(1024) void fp8_quantize_delayed_kernel(const T* __r
 #pragma unroll
             for (int e = 0; e < 8; ++e) { m = dg_amax_nan(m, v[e]); v[e] = dg_fp8_clamp(v[e] * sc, fmax); }
             int lo, hi;
-            fp8_pack8<BF8>(v, lo, hi);
+            dg_fp8_pack8<BF8>(v, lo, hi);
             *(i32x2*)(q + i * 8) = (i32x2){lo, hi};
         }
     }
@@ -217,7 +203,7 @@ __global__ __launch_bounds__(1024) void fp8_quantize_delayed_kernel(const T* __r
         float mm = 0.f;
 #pragma unroll
         for (int i = 0; i < 16; ++i) mm = dg_amax_nan(mm, red[i]);
-        next[blockIdx.x] = mm;
+        slot.next[blockIdx.x] = mm;
     }
 }
 

@@ -263,12 +263,9 @@ __global__ __launch_bounds__(768) void gemm_nt_ws_kernel(NtParams p) {
     float q_sc = 1.f, q_m = 0.f;
     float* q_next = nullptr;
     if constexpr (QOUT) {
-        const int parity = (int)(p.q_step[2] & 1u);
-        const float* prev = p.q_parts2 + (parity ^ 1) * 256;
-        q_next = p.q_parts2 + parity * 256;
-        float am = dg_amax_nan(dg_amax_nan(prev[lane], prev[64 + lane]), dg_amax_nan(prev[128 + lane], prev[192 + lane]));
-        am = wave_amax_nan(am);
-        q_sc = dg_fp8_scale_of(am, QMAX);
+        const DgFp8Slots slot = dg_fp8_slots(p.q_parts2, p.q_step, 256);
+        q_next = slot.next;
+        q_sc = dg_fp8_scale_of(dg_fp8_amax_256(slot.prev, lane), QMAX);
         if (wave == 0 && lane == 0) {
             // zeroed with an agent-scope atomic store that is acknowledged (vmcnt) before this wave reaches the first barrier:
             // the other waves' atomic maxima at the end of the launch are then ordered behind it
@@ -542,17 +539,15 @@ __global__ __launch_bounds__(768) void gemm_nt_ws_kernel(NtParams p) {
                 }
                 if constexpr (QOUT) {
                     float w8[8];
-                    int lo = 0, hi = 0;
+                    int lo, hi;
                     if constexpr (EPI == 8) {                 // v >= 0 behind the ReLU: |v| = v, only the upper clamp matters
 #pragma unroll
                         for (int e = 0; e < 8; ++e) { q_m = dg_amax_nan(q_m, v[e]); const float w = v[e] * q_sc; w8[e] = w > QMAX ? QMAX : w; }
-                        lo = __builtin_amdgcn_cvt_pk_fp8_f32(w8[0], w8[1], lo, false); lo = __builtin_amdgcn_cvt_pk_fp8_f32(w8[2], w8[3], lo, true);
-                        hi = __builtin_amdgcn_cvt_pk_fp8_f32(w8[4], w8[5], hi, false); hi = __builtin_amdgcn_cvt_pk_fp8_f32(w8[6], w8[7], hi, true);
+                        dg_fp8_pack8<false>(w8, lo, hi);
                     } else {
 #pragma unroll
                         for (int e = 0; e < 8; ++e) { q_m = dg_amax_nan(q_m, v[e]); w8[e] = dg_fp8_clamp(v[e] * q_sc, QMAX); }
-                        lo = __builtin_amdgcn_cvt_pk_bf8_f32(w8[0], w8[1], lo, false); lo = __builtin_amdgcn_cvt_pk_bf8_f32(w8[2], w8[3], lo, true);
-                        hi = __builtin_amdgcn_cvt_pk_bf8_f32(w8[4], w8[5], hi, false); hi = __builtin_amdgcn_cvt_pk_bf8_f32(w8[6], w8[7], hi, true);
+                        dg_fp8_pack8<true>(w8, lo, hi);
                     }
                     typedef int i32x2 __attribute__((ext_vector_type(2)));
                     *(i32x2*)(p.q8 + (int64_t)row * p.ldq8 + col) = (i32x2){lo, hi};

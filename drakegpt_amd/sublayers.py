@@ -17,8 +17,6 @@ Reference call sites restated here (paths relative to the reference repository r
 """
 from __future__ import annotations
 
-import os
-
 from dataclasses import dataclass
 from typing import Dict, Optional, Tuple
 
@@ -74,9 +72,6 @@ def splits_for_matrix(P: int, Q: int, rows: int, s_max: int, device=None) -> int
         _NCU[key] = torch.cuda.get_device_properties(device).multi_processor_count if torch.cuda.is_available() else 256
     tiles = ((P + 127) // 128) * ((Q + 127) // 128)
     return max(1, min(s_max, _NCU[key] // tiles, max(1, rows // 256)))
-
-
-FUSED_LN_FP8 = os.environ.get("DG_FP8_FUSED_LN", "1") != "0"      # fp8 mode: the fused LayerNorm backward also emits the e5m2 operand (A/B switch)
 
 
 def n_partials_for(rows: int) -> int:
@@ -252,15 +247,12 @@ def _op_dtype(run: Run, k: int, grad: bool = False):
     return None
 
 
-LN_FWD_FP8 = os.environ.get("DG_FP8_FUSED_LNF", "1") != "0"     # fp8 training: LayerNorm outputs leave their launch as e4m3 (A/B: 0 = cast launches)
-
-
 def _ln_fwd(run: Run, x2d: Tensor, ln_w: Tensor, ln_b: Tensor, site: str):
     """LayerNorm forward -> (h, mean, rstd, x8).  Training engine in precision fp8 (history of call site `site` seeded): the output
     leaves the LayerNorm launch as e4m3 with delayed scaling (x8 = (e4m3 copy, scale): what the cast launch in front of the next
     GEMM would have produced one launch later), and where nobody reads the bf16 form (run.fp8_only) that form is not written."""
     C = ln_w.numel()
-    ok = (run.fp8 and run.fp8_sites is not None and run.step_word is not None and run.act == torch.bfloat16 and LN_FWD_FP8
+    ok = (run.fp8 and run.fp8_sites is not None and run.step_word is not None and run.act == torch.bfloat16
           and C % 4 == 0 and C <= 1024 and fp8_k_ok(C) and x2d.dtype == torch.float32)
     key = site + "#ln"
     if ok and not run.fp8_seed and key in run.fp8_sites:
@@ -312,7 +304,7 @@ def _ln_tail(run: Run, dh: Tensor, x2d: Tensor, ln_w: Tensor, mean, rstd, dresid
         f8site = emit[4] if len(emit) > 4 else None
         pq = sink.vector(bias_key, N)[0] if bias_key is not None else None       # None: g only (no sub-layer bias behind it)
         if (f8site is not None and run.fp8 and run.fp8_sites is not None and not run.fp8_seed and f8site in run.fp8_sites
-                and run.step_word is not None and run.act == torch.bfloat16 and ng == ops.FP8_AMAX_PARTS and fp8_k_ok(N) and FUSED_LN_FP8):
+                and run.step_word is not None and run.act == torch.bfloat16 and ng == ops.FP8_AMAX_PARTS and fp8_k_ok(N)):
             dx, g, g8, gs = ops.layernorm_bwd_fused(dh, x2d, ln_w, mean, rstd, dresid, pg, pb, sg, ng, run.act, run.p(p), run.rng, site, pq,
                                                     stream_dtype=run.stream, fp8_out=(run.fp8_sites[f8site], run.step_word),
                                                     fp8_out_only=run.fp8_only)

@@ -1,11 +1,11 @@
 """csrc/layernorm.hip: its host dispatch restated in Python, and the case tables of tests/test_gpu_layernorm.py -- TEST
 INFRASTRUCTURE (CPU).
 
-Three things pick the template instance that an entry point launches: the width class nk = ceil(C / 4 / 64) (float4 slices per
-lane), whether the vector path applies (C % 4 == 0, C <= 2048, every operand 16-byte aligned) and the dtypes of dy, g and the
+Three things pick the template instance that an entry point launches: the width class nk = ceil(C / 256) (float4 slices per
+lane on the vector path), whether the vector path applies (C % 4 == 0, C <= 2048, every operand 16-byte aligned) and the dtypes of dy, g and the
 residual-gradient stream.  ``instance`` follows ``dg_layernorm_fwd``, ``dg_layernorm_fwd_fp8`` and ``ln_bwd_launch`` line by
 line and names the instance (or "rejected"); tests/test_layernorm_cases_host.py holds the tables below against the list of
-instances written out from the LAUNCH* macros: every instance needs a case whose slices are all full and, where its width
+instances written out from the launches of the kernel file: every instance needs a case whose slices are all full and, where its width
 class allows, one whose last slice is partially filled.
 
 The operands and the fp64 reference are computed once per width for ROWS_MAX rows and shared: LayerNorm is row-local, so a
@@ -33,11 +33,14 @@ FP8_AMAX_PARTS = 256
 # the dispatch
 # ---------------------------------------------------------------------------------------------------------------------
 def width_class(C):
-    return (C // 4 + 63) // 64
+    return (C + 255) // 256
 
 
-def bwd_threads(C):
-    return 1024 if C <= 512 else (512 if C <= 1024 else 256)
+WIDTH_TABLE = {1: (1, 1024), 2: (2, 1024), 3: (3, 512), 4: (4, 512)}       # nk -> (LN_MAXV, backward threads); above: (8, 256)
+
+
+def width(C):
+    return WIDTH_TABLE.get(max(width_class(C), 1), (8, 256))
 
 
 def instance(entry, C, aligned=True, dy_dtype=F32, g_dtype=F32, stream_dtype=F32, fp8=False, out_dtype=F32):
@@ -48,12 +51,12 @@ def instance(entry, C, aligned=True, dy_dtype=F32, g_dtype=F32, stream_dtype=F32
     nk = width_class(C)
     if entry == "fwd":
         if not vec:
-            return f"ln_fwd_kernel<{out_dtype},false,1>"
-        return f"ln_fwd_kernel<{out_dtype},true,{max(nk, 1) if nk <= 4 else 8}>"
+            return f"ln_fwd_scalar_kernel<{out_dtype}>"
+        return f"ln_fwd_kernel<{out_dtype},{width(C)[0]}>"
     if entry == "fwd_fp8":
         if C % 4 or C > 64 * 4 * 4 or not aligned:
             return "rejected"
-        return f"ln_fwd_fp8_kernel<{max(nk, 1)}>"
+        return f"ln_fwd_fp8_kernel<{width(C)[0]}>"
     fp8 = fp8 or entry == "bwd_fused_fp8"
     if entry == "bwd":
         if fp8 or stream_dtype != F32:
@@ -69,16 +72,14 @@ def instance(entry, C, aligned=True, dy_dtype=F32, g_dtype=F32, stream_dtype=F32
         return "rejected"
     if stream_dtype == BF16 and (not vec or fuse != 1 or dy_dtype != BF16):
         return "rejected"
-    nt = bwd_threads(C)
+    k, nt = width(C)
     if 2 * (nt // 64) * C * 4 > 64 * 1024:
         return "rejected"
-    if stream_dtype == BF16:
-        k = max(nk, 1)
-        return f"ln_bwd_kernel<bf16,true,{k},{1024 if k <= 2 else 512},1,bf16,pipe>"
     if not vec:
-        return f"ln_bwd_kernel<f32,false,1,{nt},0>"
-    k = max(nk, 1) if nk <= 4 else 8
-    return f"ln_bwd_kernel<{dy_dtype},true,{k},{ {1: 1024, 2: 1024, 3: 512, 4: 512, 8: 256}[k] },{fuse}>"
+        return f"ln_bwd_scalar_kernel<{nt}>"
+    if stream_dtype == BF16:            # the last argument: rows in flight ahead of the one being computed
+        return f"ln_bwd_kernel<bf16,{k},{nt},1,bf16,{1 if k == 2 else 2}>"
+    return f"ln_bwd_kernel<{dy_dtype},{k},{nt},{fuse},f32,0>"
 
 
 def slices(C):

@@ -308,8 +308,9 @@ def test_backward_fused_bf16_stream(dev, c):
 # ---------------------------------------------------------------------------------------------------------------------
 # fp8 forms
 # ---------------------------------------------------------------------------------------------------------------------
-def _fp8_backward(dev, c, M, G):
-    """one launch of the fused fp8 form and of the plain fused form on the same operands; returns what both left"""
+def _fp8_backward(dev, c, M, G, fp8_out_only=False):
+    """one launch of the fused fp8 form and of the plain fused form on the same operands; returns what both left.
+    fp8_out_only: the fp8 form does not write its bf16 g (the returned g is then uninitialised memory)"""
     ops = _ops()
     C, op = c.C, L.operands(c.C)
     ref, mod = L.backward_reference(C, c.dy, c.stream, c.dresid, c.p)
@@ -332,7 +333,7 @@ def _fp8_backward(dev, c, M, G):
     kw = dict(stream_dtype=TORCH[c.stream])
     dx0, g0 = ops.layernorm_bwd_fused(dy, x, w, mean[:M], rstd[:M], dres, P0[0], P0[1], C + PAD, G, torch.bfloat16, c.p, rng, L.SITE, P0[2], **kw)
     dx, g, g8, sinv = ops.layernorm_bwd_fused(dy, x, w, mean[:M], rstd[:M], dres, P1[0], P1[1], C + PAD, G, torch.bfloat16, c.p, rng, L.SITE, P1[2],
-                                              fp8_out=(parts2, rng), **kw)
+                                              fp8_out=(parts2, rng), fp8_out_only=fp8_out_only, **kw)
     torch.cuda.synchronize()
     return dict(ref=ref, mod=mod, dx0=dx0, g0=g0, P0=P0, dx=dx, g=g, g8=g8, sinv=sinv, P1=P1, parts2=parts2.cpu().view(2, G), before=before, wr=wr,
                 amax_prev=amax_prev, gmax=gmax, keep=L.keep_scale(C, c.p)[:M])
@@ -342,15 +343,25 @@ def _bits(t):
     return t.contiguous().view({1: torch.uint8, 2: torch.int16, 4: torch.int32}[t.element_size()])
 
 
-@pytest.mark.parametrize("c", L.FP8_BWD_CASES, ids=lambda c: c.id)
-def test_backward_fused_fp8(dev, c):
+@pytest.mark.parametrize("c,fp8_out_only", [pytest.param(c, only, id=c.id + ("-fp8_out_only" if only else ""))
+                                            for only in (False, True) for c in L.FP8_BWD_CASES])
+def test_backward_fused_fp8(dev, c, fp8_out_only):
     """n_partials = 256 at M = 100 / 300: 156 / 106 workgroups own no rows.  dx, g and the partial rows are what the call without
     fp8_out leaves, bit for bit; every entry of the history slot being written comes back finite, 0 for workgroups without rows,
     the slot's maximum is this step's max |g|; g8 is g at last step's scale within one e5m2 rounding, as
-    tests/test_gpu_fp8.py::test_layernorm_bwd_fused_fp8_emits_the_next_gradient_operand has it at its sizes."""
+    tests/test_gpu_fp8.py::test_layernorm_bwd_fused_fp8_emits_the_next_gradient_operand has it at its sizes.
+    fp8_out_only=True (the kernel's g8_only branch: the bf16 g is not written) leaves the same dx, g8, scale_inv, partial rows and
+    history slot as the run that writes g, bit for bit."""
     C = c.C
     for M, G in c.rows:
         r = _fp8_backward(dev, c, M, G)
+        if fp8_out_only:
+            o = _fp8_backward(dev, c, M, G, fp8_out_only=True)
+            for k in ("dx", "g8", "sinv"):
+                assert torch.equal(_bits(o[k]), _bits(r[k])), f"{c.id} M={M}: {k} differs with fp8_out_only"
+            assert all(torch.equal(_bits(a), _bits(b)) for a, b in zip(o["P1"], r["P1"])), f"{c.id} M={M}: a partial array differs with fp8_out_only"
+            assert torch.equal(_bits(o["parts2"][o["wr"]]), _bits(r["parts2"][r["wr"]])), f"{c.id} M={M}: the written history slot differs with fp8_out_only"
+            continue
         ref, mod, wr = r["ref"], r["mod"], r["wr"]
         assert torch.equal(_bits(r["dx"]), _bits(r["dx0"])) and torch.equal(_bits(r["g"]), _bits(r["g0"]))
         assert all(torch.equal(_bits(a), _bits(b)) for a, b in zip(r["P0"], r["P1"]))

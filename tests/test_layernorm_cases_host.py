@@ -3,8 +3,8 @@ tests/test_gpu_layernorm.py reach every template instance with all slices full a
 partially filled last slice, and the fp32 model of oracle/parity.py, which sets the per-row bounds, stays inside the suite's
 whole-tensor tolerances by itself.
 
-INSTANCES is written out by hand from the LAUNCH / LAUNCH_K / LAUNCH8 / LAUNCH_T / LAUNCH_BP macros of the kernel file, not
-derived from the tables: a new instance in the dispatch has to be added here, and then needs its cases."""
+INSTANCES is written out by hand from the launches of the kernel file (the two forward entry points and ln_bwd_launch, each over
+the width table of ln_with_width), not derived from the tables: a new instance in the dispatch has to be added here, and then needs its cases."""
 import os
 import sys
 
@@ -17,22 +17,21 @@ from oracle import parity as P  # noqa: E402
 
 F32, BF16 = L.F32, L.BF16
 
-# (instance, "scalar" or the number of float4 slices per lane).  The LAUNCH_B forms (the bf16 stream without the prefetch) are
-# left out: they sit behind DG_LN_BWD_PIPE=0, an A/B switch the library reads once per process, and no entry point launches
-# them otherwise.
+# (instance, "scalar" or the number of float4 slices per lane)
+WIDTHS = ((1, 1024), (2, 1024), (3, 512), (4, 512), (8, 256))           # (LN_MAXV, backward threads) of the width table
 INSTANCES = (
-    # dg_layernorm_fwd: LAUNCH_K(TO) = LAUNCH(TO, false, 1) | LAUNCH(TO, true, 1 | 2 | 3 | 4 | 8), TO = float | bf16_t
-    [(f"ln_fwd_kernel<{o},false,1>", "scalar") for o in (F32, BF16)]
-    + [(f"ln_fwd_kernel<{o},true,{k}>", k) for o in (F32, BF16) for k in (1, 2, 3, 4, 8)]
-    # dg_layernorm_fwd_fp8: LAUNCH8(1 | 2 | 3 | 4)
-    + [(f"ln_fwd_fp8_kernel<{k}>", k) for k in (1, 2, 3, 4)]
-    # ln_bwd_launch, fuse == 0: LAUNCH_T(float, false, 1, 1024 | 512 | 256, 0), LAUNCH(true, K, NT, 0) with dy float | bf16_t
-    + [(f"ln_bwd_kernel<f32,false,1,{nt},0>", "scalar") for nt in (1024, 512, 256)]
-    + [(f"ln_bwd_kernel<{d},true,{k},{nt},0>", k) for d in (F32, BF16) for k, nt in ((1, 1024), (2, 1024), (3, 512), (4, 512), (8, 256))]
-    # fuse == 1 (bf16 g) and fuse == 2 (fp32 g): LAUNCH(true, 1 .. 4, NT, F) with dy float | bf16_t
-    + [(f"ln_bwd_kernel<{d},true,{k},{nt},{f}>", k) for f in (1, 2) for d in (F32, BF16) for k, nt in ((1, 1024), (2, 1024), (3, 512), (4, 512))]
-    # the bf16 gradient stream: LAUNCH_BP(1 | 2, 1024), LAUNCH_BP(3 | 4, 512)
-    + [(f"ln_bwd_kernel<bf16,true,{k},{nt},1,bf16,pipe>", k) for k, nt in ((1, 1024), (2, 1024), (3, 512), (4, 512))]
+    # dg_layernorm_fwd: ln_fwd_scalar_kernel<TO> | ln_fwd_kernel<TO, 1 | 2 | 3 | 4 | 8>, TO = float | bf16_t
+    [(f"ln_fwd_scalar_kernel<{o}>", "scalar") for o in (F32, BF16)]
+    + [(f"ln_fwd_kernel<{o},{k}>", k) for o in (F32, BF16) for k, _ in WIDTHS]
+    # dg_layernorm_fwd_fp8: ln_fwd_fp8_kernel<1 | 2 | 3 | 4>
+    + [(f"ln_fwd_fp8_kernel<{k}>", k) for k, _ in WIDTHS[:4]]
+    # ln_bwd_launch, fuse == 0: ln_bwd_scalar_kernel<1024 | 512 | 256>, ln_bwd_kernel<TD, K, NT, 0, float, 0> with dy float | bf16_t
+    + [(f"ln_bwd_scalar_kernel<{nt}>", "scalar") for nt in (1024, 512, 256)]
+    + [(f"ln_bwd_kernel<{d},{k},{nt},0,f32,0>", k) for d in (F32, BF16) for k, nt in WIDTHS]
+    # fuse == 1 (bf16 g) and fuse == 2 (fp32 g): ln_bwd_kernel<TD, 1 .. 4, NT, F, float, 0> with dy float | bf16_t
+    + [(f"ln_bwd_kernel<{d},{k},{nt},{f},f32,0>", k) for f in (1, 2) for d in (F32, BF16) for k, nt in WIDTHS[:4]]
+    # the bf16 gradient stream: two rows in flight, one at LN_MAXV = 2
+    + [(f"ln_bwd_kernel<bf16,{k},{nt},1,bf16,{1 if k == 2 else 2}>", k) for k, nt in WIDTHS[:4]]
 )
 
 
@@ -81,21 +80,53 @@ def test_the_coverage_check_notices_missing_full_or_ragged_rows():
             assert any(g[0] == name for g in coverage_gaps(kept)), (name, want_full)
 
 
+# The ids of test_the_restated_dispatch, one per case below: a case keeps the id it had while the scalar kernels were still the
+# VEC = false instances of ln_fwd_kernel / ln_bwd_kernel and the prefetching ones were spelled "pipe", so that a case is one test
+# over the project's history.  The expected strings are the current spelling.
+DISPATCH_IDS = [
+    "args0-ln_fwd_kernel<f32,true,2>",
+    "args1-ln_fwd_kernel<f32,false,1>",
+    "args2-ln_fwd_kernel<f32,false,1>",
+    "args3-ln_fwd_kernel<f32,true,8>",
+    "args4-ln_fwd_kernel<f32,true,8>",
+    "args5-ln_fwd_kernel<f32,true,1>",
+    "args6-ln_fwd_kernel<f32,false,1>",
+    "args7-ln_fwd_fp8_kernel<1>",
+    "args8-ln_fwd_fp8_kernel<2>",
+    "args9-rejected",
+    "args10-rejected",
+    "args11-ln_bwd_kernel<f32,true,2,1024,0>",
+    "args12-ln_bwd_kernel<bf16,true,2,1024,0>",
+    "args13-ln_bwd_kernel<f32,false,1,1024,0>",
+    "args14-ln_bwd_kernel<f32,false,1,512,0>",
+    "args15-ln_bwd_kernel<f32,false,1,256,0>",
+    "args16-ln_bwd_kernel<f32,true,8,256,0>",
+    "args17-ln_bwd_kernel<f32,true,4,512,0>",
+    "args18-ln_bwd_kernel<f32,true,3,512,0>",
+    "args19-ln_bwd_kernel<bf16,true,2,1024,1>",
+    "args20-ln_bwd_kernel<f32,true,4,512,2>",
+    "args21-ln_bwd_kernel<bf16,true,2,1024,1,bf16,pipe>",
+    "args22-ln_bwd_kernel<bf16,true,4,512,1,bf16,pipe>",
+    "args23-ln_bwd_kernel<bf16,true,2,1024,1,bf16,pipe>",
+    "args24-rejected",
+]
+
+
 @pytest.mark.parametrize("args,want", [
-    (("fwd", 384), "ln_fwd_kernel<f32,true,2>"), (("fwd", 384, False), "ln_fwd_kernel<f32,false,1>"), (("fwd", 4096), "ln_fwd_kernel<f32,false,1>"),
-    (("fwd", 2048), "ln_fwd_kernel<f32,true,8>"), (("fwd", 1028), "ln_fwd_kernel<f32,true,8>"), (("fwd", 4), "ln_fwd_kernel<f32,true,1>"),
-    (("fwd", 3), "ln_fwd_kernel<f32,false,1>"), (("fwd_fp8", 256), "ln_fwd_fp8_kernel<1>"), (("fwd_fp8", 260), "ln_fwd_fp8_kernel<2>"),
+    (("fwd", 384), "ln_fwd_kernel<f32,2>"), (("fwd", 384, False), "ln_fwd_scalar_kernel<f32>"), (("fwd", 4096), "ln_fwd_scalar_kernel<f32>"),
+    (("fwd", 2048), "ln_fwd_kernel<f32,8>"), (("fwd", 1028), "ln_fwd_kernel<f32,8>"), (("fwd", 4), "ln_fwd_kernel<f32,1>"),
+    (("fwd", 3), "ln_fwd_scalar_kernel<f32>"), (("fwd_fp8", 256), "ln_fwd_fp8_kernel<1>"), (("fwd_fp8", 260), "ln_fwd_fp8_kernel<2>"),
     (("fwd_fp8", 1028), "rejected"), (("fwd_fp8", 30), "rejected"),
-    (("bwd", 384), "ln_bwd_kernel<f32,true,2,1024,0>"), (("bwd", 384, True, BF16), "ln_bwd_kernel<bf16,true,2,1024,0>"),
-    (("bwd", 510), "ln_bwd_kernel<f32,false,1,1024,0>"), (("bwd", 1001), "ln_bwd_kernel<f32,false,1,512,0>"),
-    (("bwd", 2046), "ln_bwd_kernel<f32,false,1,256,0>"), (("bwd", 2048), "ln_bwd_kernel<f32,true,8,256,0>"),
-    (("bwd", 772), "ln_bwd_kernel<f32,true,4,512,0>"), (("bwd", 516), "ln_bwd_kernel<f32,true,3,512,0>"),
-    (("bwd_fused", 384, True, BF16, BF16), "ln_bwd_kernel<bf16,true,2,1024,1>"), (("bwd_fused", 1024, True, F32, F32), "ln_bwd_kernel<f32,true,4,512,2>"),
-    (("bwd_fused", 384, True, BF16, BF16, BF16), "ln_bwd_kernel<bf16,true,2,1024,1,bf16,pipe>"),
-    (("bwd_fused", 1024, True, BF16, BF16, BF16), "ln_bwd_kernel<bf16,true,4,512,1,bf16,pipe>"),
-    (("bwd_fused_fp8", 384, True, BF16, BF16, BF16), "ln_bwd_kernel<bf16,true,2,1024,1,bf16,pipe>"),
+    (("bwd", 384), "ln_bwd_kernel<f32,2,1024,0,f32,0>"), (("bwd", 384, True, BF16), "ln_bwd_kernel<bf16,2,1024,0,f32,0>"),
+    (("bwd", 510), "ln_bwd_scalar_kernel<1024>"), (("bwd", 1001), "ln_bwd_scalar_kernel<512>"),
+    (("bwd", 2046), "ln_bwd_scalar_kernel<256>"), (("bwd", 2048), "ln_bwd_kernel<f32,8,256,0,f32,0>"),
+    (("bwd", 772), "ln_bwd_kernel<f32,4,512,0,f32,0>"), (("bwd", 516), "ln_bwd_kernel<f32,3,512,0,f32,0>"),
+    (("bwd_fused", 384, True, BF16, BF16), "ln_bwd_kernel<bf16,2,1024,1,f32,0>"), (("bwd_fused", 1024, True, F32, F32), "ln_bwd_kernel<f32,4,512,2,f32,0>"),
+    (("bwd_fused", 384, True, BF16, BF16, BF16), "ln_bwd_kernel<bf16,2,1024,1,bf16,1>"),
+    (("bwd_fused", 1024, True, BF16, BF16, BF16), "ln_bwd_kernel<bf16,4,512,1,bf16,2>"),
+    (("bwd_fused_fp8", 384, True, BF16, BF16, BF16), "ln_bwd_kernel<bf16,2,1024,1,bf16,1>"),
     (("bwd_fused", 384, True, BF16, F32, F32, True), "rejected"),
-])
+], ids=DISPATCH_IDS)
 def test_the_restated_dispatch(args, want):
     assert L.instance(*args) == want
 
