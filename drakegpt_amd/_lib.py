@@ -149,6 +149,9 @@ SIGNATURES = {
     "dg_attn_fwd_fp8": [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _u32, _i, _vp, _i64, C.POINTER(AttnFp8Out), _vp],
     "dg_attn_bwd_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _f, _f, _vp, _u32, _i, _vp, _i64, C.POINTER(AttnFp8Out), _vp],
     "dg_attn_bwd_workspace_bytes": [_i, _i, _i, _i, _i],
+    "dg_doc_starts": [_vp, _i64, _i, _i, _i64, _vp, _vp],
+    "dg_attn_fwd_doc": [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _u32, _i, _vp, _i64, C.POINTER(AttnFp8Out), _vp, _vp],
+    "dg_attn_bwd_doc": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _f, _f, _vp, _u32, _i, _vp, _i64, C.POINTER(AttnFp8Out), _vp, _vp],
     "dg_attn_decode": [_vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp],
     "dg_attn_decode_append": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
     "dg_embed_window": [_vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],

@@ -33,6 +33,7 @@ SOURCES = [
     "attention.hip",
     "attention_simple.hip",
     "attention_mfma.hip",
+    "attention_mfma_doc.hip",
     "cross_entropy.hip",
     "chain.hip",
     "chain_bwd.hip",
@@ -61,7 +62,9 @@ def build(force: bool = False, save_temps: bool = False, verbose: bool = True) -
     os.makedirs(LIBDIR, exist_ok=True)
     os.makedirs(OBJDIR, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_nt_ws.h"), os.path.join(PKG, "..", "include", "drakegpt_hip.h")]
+    # (attention_mfma.hip: also the text of attention_mfma_doc.hip, which compiles its template kernels a second time)
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_nt_ws.h"), os.path.join(PKG, "..", "include", "drakegpt_hip.h"),
+               os.path.join(CSRC, "attention_mfma.hip")]
     hdr_digest = _digest(headers)
     flags = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17",
              "-Wno-unused-result", "-I", os.path.join(PKG, "..", "include")]

@@ -44,7 +44,26 @@ struct AttnP {
     // optional (round 3, precision fp8; the F8 template instances only): the output a second time as fp8 (o: e4m3, dqkv: e5m2; same
     // [rows][columns] as the bf16 tensor, one byte per element) with delayed per-tensor scaling -- see attn_f8_begin
     uint8_t* q8; float* hist3; const uint32_t* step; float* sinv; int only8;      // only8: the bf16 form is not written
+    // optional (the DOC template instances only): document mask, starts[b*T + t] = first key query t may attend to (dg_doc_starts)
+    const int32_t* starts;
 };
+// Document mask (DOC instances).  starts is non-decreasing along a row with 0 <= starts[t] <= t, so the first key tile a 32-query block
+// q0 .. q0+31 has anything in is the one of its FIRST query: kt0 = starts[b*T + q0] / 32, wave-uniform.  The forward pass and the dQ
+// pass use this one rule, so the keep-mask records the first writes are exactly those the second reads.  Inside the visited tiles a
+// lane (one query column) masks keys below its own start.  Values outside the invariants are clamped to [0, t]: results are then
+// unspecified, but every access stays inside its buffer.
+__device__ __forceinline__ int attn_doc_kt0(const AttnP& p, int b, int qb) {
+    int s = p.starts[(int64_t)b * p.T + qb * TILE];                // (qb * TILE < T for every valid block)
+    s = s < 0 ? 0 : s;
+    const int kt = __builtin_amdgcn_readfirstlane(s / TILE);
+    return kt > qb ? qb : kt;
+}
+__device__ __forceinline__ int attn_doc_qs(const AttnP& p, int b, int qi) {
+    const int t = qi < p.T ? qi : p.T - 1;
+    const int s = p.starts[(int64_t)b * p.T + t];
+    return s < 0 ? 0 : (s > t ? t : s);
+}
+#define ATTN_DOC_FLOOR (-1.0e30f)
 // fp8 copy of an output from the kernel that produces it.  hist3 = [3][64] partial maxima owned by the call site, every one on a
 // 128-byte line of its own (DG_ATTN_F8_HIST floats in all): slot step % 3 collects THIS step's maxima (atomic max on the bit
 // patterns of non-negative floats -- NaN patterns compare above every finite one and poison the scale as everywhere else; wave w ->
@@ -258,7 +277,8 @@ __device__ __forceinline__ void store_N_acc(char* img, const f32x16 (&acc)[2], f
 #define WAVE_LDS_FWD 8192
 // =============================================================================================
 // F8: the output also as e4m3 (AttnP::q8 ...; precision fp8: the operand of the projection and of its weight gradient)
-template <bool DROP, bool KEEP = false, bool F8 = false>      // dropout on the probabilities (compile-time: no per-element uniform branch); KEEP: also leave the keep masks (AttnP::keep)
+// DOC: document mask (AttnP::starts): the tile loop starts at kt0 and every visited tile masks keys below the lane's own start
+template <bool DROP, bool KEEP = false, bool F8 = false, bool DOC = false>      // dropout on the probabilities (compile-time: no per-element uniform branch); KEEP: also leave the keep masks (AttnP::keep)
 __global__ __launch_bounds__(256, 3) void attn_fwd_mfma_kernel(AttnP p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform: block, pointers and loop bounds live in SGPRs
@@ -289,9 +309,11 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_mfma_kernel(AttnP p) {
     // per-register pair offsets are compile-time constants
     const uint32_t wbase = (((uint32_t)(((uint64_t)bh * T + qi) * (uint64_t)T) + 4u * hh) >> 1) * DG_WEYL;
 
+    int kt0 = 0, qs = 0;
+    if constexpr (DOC) { kt0 = attn_doc_kt0(p, b, qb); qs = attn_doc_qs(p, b, qi); }
     u32x4 rk[4], rv[4];
-    tile_load(rk, Kb, ld, 0, T, lane);
-    tile_load(rv, Vb, ld, 0, T, lane);
+    tile_load(rk, Kb, ld, kt0 * TILE, T, lane);
+    tile_load(rv, Vb, ld, kt0 * TILE, T, lane);
     // One key tile.  DIAG (compile time) = the last tile of the block, the only one the causal mask touches and the only
     // one with nothing to prefetch: interior tiles carry no per-element compare / select and no branch at all.
     auto tile = [&](auto diag_tag, int kt) {
@@ -317,10 +339,15 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_mfma_kernel(AttnP p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             if (DIAG && k0 + krow(r, hh) > qi) S[r] = -INFINITY;
+            if (DOC && k0 + krow(r, hh) < qs) S[r] = -INFINITY;
             mx = fmaxf(mx, S[r]);
         }
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64)) * sc;
-        const float mn = fmaxf(m, mx);
+        // (DOC) a visited tile can be wholly masked for a query whose document starts later in the block: m = mx = -inf, and
+        // exp2(m - mn) would be NaN.  A finite floor under mn makes alpha and every probability of such a tile exact zeros; the
+        // first tile with a visible key then sees alpha = exp2(floor - mn) = 0 on zero sums, which is what a row that never
+        // visited the masked tile gets (alpha = exp2(-inf) = 0).
+        const float mn = DOC ? fmaxf(fmaxf(m, mx), ATTN_DOC_FLOOR) : fmaxf(m, mx);
         const float alpha = __builtin_amdgcn_exp2f(m - mn);
         m = mn;
         float ps = 0.f;
@@ -378,7 +405,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_mfma_kernel(AttnP p) {
         }
         __builtin_amdgcn_wave_barrier();
     };
-    for (int kt = 0; kt < qb; ++kt) tile(std::false_type{}, kt);
+    for (int kt = kt0; kt < qb; ++kt) tile(std::false_type{}, kt);
     tile(std::true_type{}, qb);
     lsum += __shfl_xor(lsum, 32, 64);
     if (hh == 0 && qi < T) p.lse[bh * T + qi] = (m + log2f(lsum)) * (1.f / LOG2E);
@@ -406,7 +433,11 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_mfma_kernel(AttnP p) {
 // workgroup barrier per key tile, as in attn_bwd_dkv_tiles_shared_kernel; the loop runs to the workgroup's LAST query block and a
 // wave whose own block is finished only helps loading.  The P | dS staging area and the parked Q fragment stay private.
 #define WG_LDS_DQS (4 * 5120 + 2 * 12288)
-template <bool TILES, bool KB = false, bool F8 = false, bool SH = false>
+// DOC (with TILES only): document mask (AttnP::starts).  The loop starts at the wave's kt0 (SH: at the smallest kt0 of the workgroup's
+// four waves; a wave is active for kt0 <= kt <= qb, the barrier count stays workgroup-uniform), the probability of a key below the
+// lane's own start is selected to 0 next to the diagonal test, and the tiles kt < kt0 the loop skips are stored as zero P | dS
+// records first: the dK/dV tile kernels are unchanged and read every (qb, kt <= qb) record.
+template <bool TILES, bool KB = false, bool F8 = false, bool SH = false, bool DOC = false>
 __global__ __launch_bounds__(256, 3) void attn_bwd_dq_mfma_kernel(AttnP p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform: block, pointers and loop bounds live in SGPRs
@@ -428,6 +459,19 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_mfma_kernel(AttnP p) {
         }
     }
     const int h = (int)(bh % p.NH), b = (int)(bh / p.NH);
+    int kt0 = 0, ktmin = 0;                      // (DOC) this wave's first key tile; (SH) the workgroup's
+    if constexpr (DOC) {
+        ktmin = kt0 = attn_doc_kt0(p, b, qb);
+        if (SH) {                                // (the four blocks of a workgroup belong to one (batch, head) and are all valid)
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                int64_t bh_w; int blk_w; bool v_w;
+                attn_item(p, w, bh_w, blk_w, v_w);
+                const int k_w = attn_doc_kt0(p, b, blk_w);
+                ktmin = k_w < ktmin ? k_w : ktmin;
+            }
+        }
+    }
     const int T = p.T, C = p.NH * HD;
     const int64_t ld = 3 * (int64_t)C;
     const bf16_t* Qb = p.qkv + (int64_t)b * T * ld + h * HD;
@@ -436,6 +480,14 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_mfma_kernel(AttnP p) {
     const bf16_t* dOb = p.dout + (int64_t)b * T * C + h * HD;
     const int q0 = qb * TILE, c = lane & 31, hh = lane >> 5;
     const int qi = q0 + c;
+    if constexpr (DOC && TILES) {
+        const u32x4 z = {0u, 0u, 0u, 0u};
+        for (int kt = 0; kt < kt0; ++kt) {
+            char* tb = p.tiles + attn_tile_index(p, bh, qb, kt);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) *(u32x4*)(tb + (lane + 64 * i) * 16) = z;
+        }
+    }
 
     bf16x8 qf[4], gf[4];
     frags_global(qf, Qb, ld, q0, T, lane);
@@ -478,11 +530,13 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_mfma_kernel(AttnP p) {
         rk[0] = *(const u32x4*)(Kb + row_off(gr, ld) + sch * 8);
         rv[0] = *(const u32x4*)(Vb + row_off(gr, ld) + sch * 8);
     };
-    if (SH) load_q4(0);
+    if (SH) load_q4(ktmin);
     else {
-        tile_load(rk, Kb, ld, 0, T, lane);
-        tile_load(rv, Vb, ld, 0, T, lane);
+        tile_load(rk, Kb, ld, kt0 * TILE, T, lane);
+        tile_load(rv, Vb, ld, kt0 * TILE, T, lane);
     }
+    int qlo = 0;                                                   // (DOC) the lane's first visible key
+    if constexpr (DOC) qlo = attn_doc_qs(p, b, qi);
     unsigned long long st_prev = 0, st_acc[5] = {0, 0, 0, 0, 0};
     const bool st_on = p.stamps != nullptr && wave == 0;          // (wave-uniform)
     auto stamp = [&](int k) {
@@ -493,8 +547,8 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_mfma_kernel(AttnP p) {
         }
     };
     stamp(-1);
-    for (int kt = 0; kt <= (SH ? qmax : qb); ++kt) {
-        const bool active = !SH || kt <= qb;                      // (wave-uniform)
+    for (int kt = DOC ? (SH ? ktmin : kt0) : 0; kt <= (SH ? qmax : qb); ++kt) {
+        const bool active = !SH || (kt <= qb && (!DOC || kt >= kt0));   // (wave-uniform)
         if (SH) {
             imgK = smem + 4 * 5120 + (kt & 1) * 12288;
             imgKt = imgK + 4096;
@@ -584,6 +638,8 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_mfma_kernel(AttnP p) {
                 f32x2 pr2 = {__builtin_amdgcn_exp2f(arg[0]), __builtin_amdgcn_exp2f(arg[1])};
                 if (k0 + krow(r0, hh) > qlim) pr2[0] = 0.f;         // (the diagonal tile: keys behind the query; qlim = INT_MAX elsewhere)
                 if (k0 + krow(r0 + 1, hh) > qlim) pr2[1] = 0.f;
+                if (DOC && k0 + krow(r0, hh) < qlo) pr2[0] = 0.f;   // (keys of an earlier document)
+                if (DOC && k0 + krow(r0 + 1, hh) < qlo) pr2[1] = 0.f;
                 const f32x2 ds2 = pr2 * ((f32x2){dP[r0], dP[r0 + 1]} * kf2 - (f32x2){dl, dl});
                 const f32x2 pk2 = pr2 * kf2;
                 S[r0] = ds2[0]; S[r0 + 1] = ds2[1];
@@ -752,6 +808,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_mfma_kernel(AttnP p) {
 }
 
 // =============================================================================================
+// Everything above: the template kernels, also compiled into attention_mfma_doc.hip (their DOC instances and the launches of
+// those).  Everything below: the non-template kernels and the host side of this file alone.
+#ifndef DG_ATTN_MFMA_DOC_TU
+int dg_attn_fwd_mfma_doc(const AttnP& p, bool f8, dim3 grid, hipStream_t s);
+void dg_attn_dq_mfma_doc(const AttnP& p, bool kb, bool f8, dim3 grid, hipStream_t s);
+
 bool dg_attn_mfma_supported(int B, int T, int NH, int H) {
     // (T even: a lane's adjacent keys then form the element pairs that share a dropout hash)
     // (row offsets inside a batch slab are 24 x 24 -> 32-bit products: row_off)
@@ -966,17 +1028,21 @@ static int attn_f8_fill(AttnP& p, const dg_attn_fp8_out* f8) {
 }
 
 int dg_attn_fwd_mfma(const void* qkv, void* out, float* lse, int B, int T, int NH, int H, float scale, float dp,
-                     const uint32_t* rng, uint32_t site, void* keep, const dg_attn_fp8_out* f8, hipStream_t s) {
+                     const uint32_t* rng, uint32_t site, void* keep, const dg_attn_fp8_out* f8, const int32_t* starts, hipStream_t s) {
     if (dp < 0.f || dp >= 1.f || !dg_aligned16(qkv) || !dg_aligned16(out) || (keep && !dg_aligned16(keep))) return DG_ERR_ARG;
     AttnP p = {};
     fill(p, B, T, NH, scale, dp, rng, site);
     p.qkv = (const bf16_t*)qkv; p.out_w = (bf16_t*)out; p.lse = lse;
     p.keep = (unsigned long long*)keep;
+    p.starts = starts;
     dim3 grid((unsigned)((p.n_items + 3) / 4)), block(256);
     if (f8) {
         if (p.drop && !p.keep) return DG_ERR_ARG;
         if (int rc = attn_f8_fill(p, f8)) return rc;
         if (p.only8) return DG_ERR_ARG;                   // (the dQ pass reads the bf16 output: delta = rowsum(dO o))
+    }
+    if (starts) return dg_attn_fwd_mfma_doc(p, f8 != nullptr, grid, s);          // the document-mask instances (attention_mfma_doc.hip)
+    if (f8) {
         if (p.drop) hipLaunchKernelGGL((attn_fwd_mfma_kernel<true, true, true>), grid, block, 4 * WAVE_LDS_FWD, s, p);
         else hipLaunchKernelGGL((attn_fwd_mfma_kernel<false, false, true>), grid, block, 4 * WAVE_LDS_FWD, s, p);
         DG_LAUNCH_CHECK();
@@ -1007,8 +1073,9 @@ static void attn_dq_launch(const AttnP& p, dim3 grid, hipStream_t s) {
 
 int dg_attn_bwd_mfma(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* delta, void* tiles,
                      int B, int T, int NH, int H, float scale, float dp, const uint32_t* rng, uint32_t site, const void* keep,
-                     const dg_attn_fp8_out* f8, hipStream_t s) {
+                     const dg_attn_fp8_out* f8, const int32_t* starts, hipStream_t s) {
     if (dp < 0.f || dp >= 1.f || !dg_aligned16(qkv) || !dg_aligned16(out) || !dg_aligned16(dout) || !dg_aligned16(dqkv)) return DG_ERR_ARG;
+    if (starts && !tiles) return DG_ERR_ARG;              // (the recompute form has no document variant)
     if (keep && !dg_aligned16(keep)) return DG_ERR_ALIGN;
     if (tiles && !dg_aligned16(tiles)) return DG_ERR_ALIGN;
     AttnP p = {};
@@ -1016,6 +1083,7 @@ int dg_attn_bwd_mfma(const void* qkv, const void* out, const void* dout, const f
     p.qkv = (const bf16_t*)qkv; p.out = (const bf16_t*)out; p.dout = (const bf16_t*)dout; p.dqkv = (bf16_t*)dqkv;
     p.lse_r = lse; p.delta = delta; p.delta_r = delta;
     p.tiles = (char*)tiles;
+    p.starts = starts;
     // keep masks: the tile form only (the recompute form's dQ loop would spill 16 registers with them; it hashes instead)
     p.keep = (keep && p.drop && tiles) ? (unsigned long long*)keep : nullptr;
     if (f8) {
@@ -1027,7 +1095,8 @@ int dg_attn_bwd_mfma(const void* qkv, const void* out, const void* dout, const f
     // no dropout: threshold 0 (keep all), scale 1: bit-identical, faster than a dropout-free dQ build (36 vs 48 us per layer); key read from qkv (>= 384 B)
     AttnP q = p;
     if (!p.drop) { q.thr = 0u; q.inv_keep = 1.f; q.rng = (const uint32_t*)qkv; q.site = 0; }
-    if (!p.tiles) attn_dq_launch<false, false, false>(q, grid, s);
+    if (starts) dg_attn_dq_mfma_doc(q, p.keep != nullptr, f8 != nullptr, grid, s);   // the document-mask instances (attention_mfma_doc.hip)
+    else if (!p.tiles) attn_dq_launch<false, false, false>(q, grid, s);
     else if (!f8) (p.keep ? attn_dq_launch<true, true, false> : attn_dq_launch<true, false, false>)(q, grid, s);
     else (p.keep ? attn_dq_launch<true, true, true> : attn_dq_launch<true, false, true>)(q, grid, s);
     DG_LAUNCH_CHECK();
@@ -1044,3 +1113,4 @@ int dg_attn_bwd_mfma(const void* qkv, const void* out, const void* dout, const f
     DG_LAUNCH_CHECK();
     return DG_OK;
 }
+#endif  // DG_ATTN_MFMA_DOC_TU

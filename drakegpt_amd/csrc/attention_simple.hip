@@ -19,11 +19,20 @@ struct QkvView {
 };
 
 // ---------------------------------------------------------------------------------------------
-template <typename T>
+// DOC (compile time): document mask.  starts[b*Tn + i] = first key query i may see (dg_doc_starts); the loops run over
+// j0 .. i with lane assignment and summation order relative to j0, i.e. those of the document run as a sequence of its own
+// (only the dropout element index stays absolute).  Values outside [0, i] are clamped: the kernel stays inside its buffers.
+__device__ __forceinline__ int doc_first_key(const int32_t* __restrict__ starts, int64_t row, int i) {
+    const int s = starts[row];
+    return s < 0 ? 0 : (s > i ? i : s);
+}
+
+template <typename T, bool DOC = false>
 __global__ void attn_fwd_simple_kernel(const T* __restrict__ qkv, T* __restrict__ out, float* __restrict__ lse,
                                        int B, int Tn, int NH, int H, float scale,
                                        int drop, float inv_keep, uint32_t thr,
-                                       const uint32_t* __restrict__ rng_state, uint32_t site) {
+                                       const uint32_t* __restrict__ rng_state, uint32_t site,
+                                       const int32_t* __restrict__ starts = nullptr) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     float* sc = smem + w * (Tn + H);      // [Tn] scores/probs
@@ -35,10 +44,11 @@ __global__ void attn_fwd_simple_kernel(const T* __restrict__ qkv, T* __restrict_
     const int b = (int)(gid / ((int64_t)Tn * NH));
     QkvView<T> V{qkv, (int64_t)3 * NH * H, NH, H, Tn};
     const T* qr = V.q(b, h, i);
+    const int j0 = DOC ? doc_first_key(starts, (int64_t)b * Tn + i, i) : 0;
     for (int d = lane; d < H; d += 64) qs[d] = to_f32<T>(qr[d]);
     __builtin_amdgcn_wave_barrier();
     float mx = -INFINITY;
-    for (int j = lane; j <= i; j += 64) {
+    for (int j = j0 + lane; j <= i; j += 64) {
         const T* kr = V.k(b, h, j);
         float s = 0.f;
         for (int d = 0; d < H; ++d) s += qs[d] * to_f32<T>(kr[d]);
@@ -48,13 +58,13 @@ __global__ void attn_fwd_simple_kernel(const T* __restrict__ qkv, T* __restrict_
     }
     mx = wave_max(mx);
     float sum = 0.f;
-    for (int j = lane; j <= i; j += 64) { float e = expf(sc[j] - mx); sc[j] = e; sum += e; }
+    for (int j = j0 + lane; j <= i; j += 64) { float e = expf(sc[j] - mx); sc[j] = e; sum += e; }
     sum = wave_sum(sum);
     const float inv = 1.f / sum;
     if (lane == 0) lse[gid] = mx + logf(sum);
     uint32_t key = drop ? dg_site_key_dev(rng_state, site) : 0u;
     const uint32_t ebase = (uint32_t)(gid * (int64_t)Tn);          // ((b*NH+h)*T+i)*T
-    for (int j = lane; j <= i; j += 64) {
+    for (int j = j0 + lane; j <= i; j += 64) {
         float pj = sc[j] * inv;
         if (drop) pj = dg_keep(key, ebase + (uint32_t)j, thr) ? pj * inv_keep : 0.f;
         sc[j] = pj;
@@ -63,19 +73,20 @@ __global__ void attn_fwd_simple_kernel(const T* __restrict__ qkv, T* __restrict_
     T* orow = out + ((int64_t)b * Tn + i) * (NH * H) + h * H;
     for (int d = lane; d < H; d += 64) {
         float o = 0.f;
-        for (int j = 0; j <= i; ++j) o += sc[j] * to_f32<T>(V.v(b, h, j)[d]);
+        for (int j = j0; j <= i; ++j) o += sc[j] * to_f32<T>(V.v(b, h, j)[d]);
         orow[d] = from_f32<T>(o);
     }
 }
 
 // ---------------------------------------------------------------------------------------------
 // dQ pass: one wave per (b,h,i).  Also writes delta[b,h,i] = sum_d dO*O.
-template <typename T>
+template <typename T, bool DOC = false>
 __global__ void attn_bwd_dq_simple_kernel(const T* __restrict__ qkv, const T* __restrict__ out, const T* __restrict__ dout,
                                           const float* __restrict__ lse, T* __restrict__ dqkv, float* __restrict__ delta,
                                           int B, int Tn, int NH, int H, float scale,
                                           int drop, float inv_keep, uint32_t thr,
-                                          const uint32_t* __restrict__ rng_state, uint32_t site) {
+                                          const uint32_t* __restrict__ rng_state, uint32_t site,
+                                          const int32_t* __restrict__ starts = nullptr) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     float* ds = smem + w * (Tn + 2 * H);
@@ -101,7 +112,8 @@ __global__ void attn_bwd_dq_simple_kernel(const T* __restrict__ qkv, const T* __
     const float L = lse[gid];
     uint32_t key = drop ? dg_site_key_dev(rng_state, site) : 0u;
     const uint32_t ebase = (uint32_t)(gid * (int64_t)Tn);
-    for (int j = lane; j <= i; j += 64) {
+    const int j0 = DOC ? doc_first_key(starts, (int64_t)b * Tn + i, i) : 0;
+    for (int j = j0 + lane; j <= i; j += 64) {
         const T* kr = V.k(b, h, j);
         const T* vr = V.v(b, h, j);
         float s = 0.f, dp = 0.f;
@@ -114,18 +126,20 @@ __global__ void attn_bwd_dq_simple_kernel(const T* __restrict__ qkv, const T* __
     T* dq = dqkv + ((int64_t)b * Tn + i) * (3 * NH * H) + h * H;
     for (int d = lane; d < H; d += 64) {
         float a = 0.f;
-        for (int j = 0; j <= i; ++j) a += ds[j] * to_f32<T>(V.k(b, h, j)[d]);
+        for (int j = j0; j <= i; ++j) a += ds[j] * to_f32<T>(V.k(b, h, j)[d]);
         dq[d] = from_f32<T>(a * scale);
     }
 }
 
-// dK/dV pass: one wave per (b,h,j); queries i >= j.
-template <typename T>
+// dK/dV pass: one wave per (b,h,j); queries i >= j.  DOC: ... up to the end of key j's document, i.e. the first query whose
+// first visible key lies behind j (starts is non-decreasing; any other content still gives an end inside (j, Tn]).
+template <typename T, bool DOC = false>
 __global__ void attn_bwd_dkv_simple_kernel(const T* __restrict__ qkv, const T* __restrict__ dout,
                                            const float* __restrict__ lse, const float* __restrict__ delta,
                                            T* __restrict__ dqkv, int B, int Tn, int NH, int H, float scale,
                                            int drop, float inv_keep, uint32_t thr,
-                                           const uint32_t* __restrict__ rng_state, uint32_t site) {
+                                           const uint32_t* __restrict__ rng_state, uint32_t site,
+                                           const int32_t* __restrict__ starts = nullptr) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     float* ds = smem + w * (2 * Tn + 2 * H);     // dS[i]
@@ -142,7 +156,15 @@ __global__ void attn_bwd_dkv_simple_kernel(const T* __restrict__ qkv, const T* _
     __builtin_amdgcn_wave_barrier();
     uint32_t key = drop ? dg_site_key_dev(rng_state, site) : 0u;
     const int64_t bh = (int64_t)b * NH + h;
-    for (int i = j + lane; i < Tn; i += 64) {
+    int iend = Tn;
+    if (DOC) {
+        for (int i0 = j + 1; i0 < Tn; i0 += 64) {                 // (wave-uniform loop: first query that no longer sees key j)
+            const int i = i0 + lane;
+            const unsigned long long hit = __builtin_amdgcn_ballot_w64(i < Tn && starts[(int64_t)b * Tn + i] > j);
+            if (hit) { iend = i0 + __builtin_ctzll(hit); break; }
+        }
+    }
+    for (int i = j + lane; i < iend; i += 64) {
         const T* qr = V.q(b, h, i);
         const T* dor = dout + ((int64_t)b * Tn + i) * (NH * H) + h * H;
         float s = 0.f, dp = 0.f;
@@ -159,7 +181,7 @@ __global__ void attn_bwd_dkv_simple_kernel(const T* __restrict__ qkv, const T* _
     T* dv = dk + NH * H;
     for (int d = lane; d < H; d += 64) {
         float ak = 0.f, av = 0.f;
-        for (int i = j; i < Tn; ++i) {
+        for (int i = j; i < iend; ++i) {
             ak += ds[i] * to_f32<T>(V.q(b, h, i)[d]);
             av += pd[i] * to_f32<T>(dout[((int64_t)b * Tn + i) * (NH * H) + h * H + d]);
         }
@@ -308,7 +330,7 @@ static int check_common(int B, int T, int NH, int H, float p) {
 }
 
 int dg_attn_fwd_simple(const void* qkv, void* out, float* lse, int B, int T, int NH, int H, float scale,
-                       float p, const uint32_t* rng_state, uint32_t site, int dtype, hipStream_t s) {
+                       float p, const uint32_t* rng_state, uint32_t site, int dtype, const int32_t* starts, hipStream_t s) {
     int rc = check_common(B, T, NH, H, p);
     if (rc) return rc;
     int64_t rows = (int64_t)B * NH * T;
@@ -317,18 +339,23 @@ int dg_attn_fwd_simple(const void* qkv, void* out, float* lse, int B, int T, int
     int drop = (p > 0.f && rng_state) ? 1 : 0;
     float ik = 1.f / (1.f - p);
     uint32_t thr = dg_drop_threshold(p);
-    if (dtype == DG_BF16)
-        hipLaunchKernelGGL(attn_fwd_simple_kernel<bf16_t>, grid, block, sm, s, (const bf16_t*)qkv, (bf16_t*)out, lse, B, T, NH, H, scale, drop, ik, thr, rng_state, site);
-    else if (dtype == DG_F32)
-        hipLaunchKernelGGL(attn_fwd_simple_kernel<float>, grid, block, sm, s, (const float*)qkv, (float*)out, lse, B, T, NH, H, scale, drop, ik, thr, rng_state, site);
-    else return DG_ERR_DTYPE;
+    if (dtype != DG_BF16 && dtype != DG_F32) return DG_ERR_DTYPE;
+    if (starts) {
+        if (dtype == DG_BF16)
+            hipLaunchKernelGGL((attn_fwd_simple_kernel<bf16_t, true>), grid, block, sm, s, (const bf16_t*)qkv, (bf16_t*)out, lse, B, T, NH, H, scale, drop, ik, thr, rng_state, site, starts);
+        else
+            hipLaunchKernelGGL((attn_fwd_simple_kernel<float, true>), grid, block, sm, s, (const float*)qkv, (float*)out, lse, B, T, NH, H, scale, drop, ik, thr, rng_state, site, starts);
+    } else if (dtype == DG_BF16)
+        hipLaunchKernelGGL((attn_fwd_simple_kernel<bf16_t>), grid, block, sm, s, (const bf16_t*)qkv, (bf16_t*)out, lse, B, T, NH, H, scale, drop, ik, thr, rng_state, site, (const int32_t*)nullptr);
+    else
+        hipLaunchKernelGGL((attn_fwd_simple_kernel<float>), grid, block, sm, s, (const float*)qkv, (float*)out, lse, B, T, NH, H, scale, drop, ik, thr, rng_state, site, (const int32_t*)nullptr);
     DG_LAUNCH_CHECK();
     return DG_OK;
 }
 
 int dg_attn_bwd_simple(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
                        float* delta, int B, int T, int NH, int H, float scale, float p,
-                       const uint32_t* rng_state, uint32_t site, int dtype, hipStream_t s) {
+                       const uint32_t* rng_state, uint32_t site, int dtype, const int32_t* starts, hipStream_t s) {
     int rc = check_common(B, T, NH, H, p);
     if (rc) return rc;
     int64_t rows = (int64_t)B * NH * T;
@@ -338,14 +365,22 @@ int dg_attn_bwd_simple(const void* qkv, const void* out, const void* dout, const
     int drop = (p > 0.f && rng_state) ? 1 : 0;
     float ik = 1.f / (1.f - p);
     uint32_t thr = dg_drop_threshold(p);
-    if (dtype == DG_BF16) {
-        hipLaunchKernelGGL(attn_bwd_dq_simple_kernel<bf16_t>, grid, block, sm1, s, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse, (bf16_t*)dqkv, delta, B, T, NH, H, scale, drop, ik, thr, rng_state, site);
+    if (dtype == DG_BF16 && starts) {
+        hipLaunchKernelGGL((attn_bwd_dq_simple_kernel<bf16_t, true>), grid, block, sm1, s, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse, (bf16_t*)dqkv, delta, B, T, NH, H, scale, drop, ik, thr, rng_state, site, starts);
         DG_LAUNCH_CHECK();
-        hipLaunchKernelGGL(attn_bwd_dkv_simple_kernel<bf16_t>, grid, block, sm2, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, B, T, NH, H, scale, drop, ik, thr, rng_state, site);
+        hipLaunchKernelGGL((attn_bwd_dkv_simple_kernel<bf16_t, true>), grid, block, sm2, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, B, T, NH, H, scale, drop, ik, thr, rng_state, site, starts);
+    } else if (dtype == DG_F32 && starts) {
+        hipLaunchKernelGGL((attn_bwd_dq_simple_kernel<float, true>), grid, block, sm1, s, (const float*)qkv, (const float*)out, (const float*)dout, lse, (float*)dqkv, delta, B, T, NH, H, scale, drop, ik, thr, rng_state, site, starts);
+        DG_LAUNCH_CHECK();
+        hipLaunchKernelGGL((attn_bwd_dkv_simple_kernel<float, true>), grid, block, sm2, s, (const float*)qkv, (const float*)dout, lse, delta, (float*)dqkv, B, T, NH, H, scale, drop, ik, thr, rng_state, site, starts);
+    } else if (dtype == DG_BF16) {
+        hipLaunchKernelGGL((attn_bwd_dq_simple_kernel<bf16_t>), grid, block, sm1, s, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse, (bf16_t*)dqkv, delta, B, T, NH, H, scale, drop, ik, thr, rng_state, site, (const int32_t*)nullptr);
+        DG_LAUNCH_CHECK();
+        hipLaunchKernelGGL((attn_bwd_dkv_simple_kernel<bf16_t>), grid, block, sm2, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, B, T, NH, H, scale, drop, ik, thr, rng_state, site, (const int32_t*)nullptr);
     } else if (dtype == DG_F32) {
-        hipLaunchKernelGGL(attn_bwd_dq_simple_kernel<float>, grid, block, sm1, s, (const float*)qkv, (const float*)out, (const float*)dout, lse, (float*)dqkv, delta, B, T, NH, H, scale, drop, ik, thr, rng_state, site);
+        hipLaunchKernelGGL((attn_bwd_dq_simple_kernel<float>), grid, block, sm1, s, (const float*)qkv, (const float*)out, (const float*)dout, lse, (float*)dqkv, delta, B, T, NH, H, scale, drop, ik, thr, rng_state, site, (const int32_t*)nullptr);
         DG_LAUNCH_CHECK();
-        hipLaunchKernelGGL(attn_bwd_dkv_simple_kernel<float>, grid, block, sm2, s, (const float*)qkv, (const float*)dout, lse, delta, (float*)dqkv, B, T, NH, H, scale, drop, ik, thr, rng_state, site);
+        hipLaunchKernelGGL((attn_bwd_dkv_simple_kernel<float>), grid, block, sm2, s, (const float*)qkv, (const float*)dout, lse, delta, (float*)dqkv, B, T, NH, H, scale, drop, ik, thr, rng_state, site, (const int32_t*)nullptr);
     } else return DG_ERR_DTYPE;
     DG_LAUNCH_CHECK();
     return DG_OK;

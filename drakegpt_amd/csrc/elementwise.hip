@@ -189,6 +189,38 @@ extern "C" int dg_embed_window(const int64_t* ids, int64_t ld_ids, const uint32_
     return DG_OK;
 }
 
+// Document starts of a packed batch (document-masked attention; no ATen call site in the reference: src/model.py get_batch cuts
+// windows out of one concatenated corpus and Head2.forward src/model_component.py:392-405 masks causally only -- the starts say
+// which keys of :401's tril mask belong to the query's own document).  starts[b, t] = 1 + max{ j < t : ids[b, j] == sep }, else 0:
+// an inclusive max-scan along the row of cand[t] = (t > 0 && ids[b, t-1] == sep) ? t : 0.  One wave per row, 64 positions per round,
+// the running maximum carried in a register: a pure function of the inputs, no atomics.
+__global__ void doc_starts_kernel(const int64_t* __restrict__ ids, int64_t ld_ids, int B, int T, int64_t sep, int32_t* __restrict__ starts) {
+    const int lane = threadIdx.x & 63;
+    const int b = (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    if (b >= B) return;                                            // (whole wave)
+    const int64_t* row = ids + (int64_t)b * ld_ids;
+    int carry = 0;
+    for (int t0 = 0; t0 < T; t0 += 64) {
+        const int t = t0 + lane;
+        int v = (t > 0 && t < T && row[t - 1] == sep) ? t : 0;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int u = __shfl_up(v, d, 64);
+            if (lane >= d) v = v > u ? v : u;
+        }
+        v = v > carry ? v : carry;
+        if (t < T) starts[(int64_t)b * T + t] = v;
+        carry = __shfl(v, 63, 64);
+    }
+}
+
+extern "C" int dg_doc_starts(const int64_t* ids, int64_t ld_ids, int B, int T, int64_t sep, int32_t* starts, void* stream) {
+    if (!ids || !starts || B <= 0 || T <= 0 || ld_ids < T) return DG_ERR_ARG;
+    hipLaunchKernelGGL(doc_starts_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, ids, ld_ids, B, T, sep, starts);
+    DG_LAUNCH_CHECK();
+    return DG_OK;
+}
+
 // zero fill.  NOT hipMemsetAsync: inside a captured hipGraph the runtime's memset node (a fillBufferAligned dispatch whose
 // fill pattern lives in a runtime-owned argument buffer) filled the token-table gradient with garbage on every replay that
 // followed the load of a new code object -- e.g. the first torch `.double()` kernel of the process, launched between two steps

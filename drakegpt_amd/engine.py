@@ -212,8 +212,12 @@ class TrainEngine:
                  max_grad_norm: Optional[float] = None, accum_steps: int = 1, lr_schedule=None, schedule_steps: Optional[int] = None,
                  no_decay=(), label_smoothing: float = 0.0, z_loss: float = 0.0, ema_decay: Optional[float] = None,
                  ema_warmup: bool = False, ignore_index: Optional[int] = None, skip_nonfinite: bool = False,
-                 skip_grad_norm: Optional[float] = None):
-        """skip_nonfinite / skip_grad_norm: the update guard (off by default).  The optimizer update of a
+                 skip_grad_norm: Optional[float] = None, doc_separator: Optional[int] = None):
+        """doc_separator (a token id; None: off, nothing of it exists): document-masked attention.  A document
+        of the packed batch ends WITH this token and no token attends across it, in every program that gathers or embeds a batch
+        (step, micro-step, eval_loss, eval_losses; eager and captured): one dg_doc_starts launch behind the embedding launch fills
+        an int32 [B*T] buffer on the device and every attention call of the program reads it.
+        skip_nonfinite / skip_grad_norm: the update guard (off by default).  The optimizer update of a
         step is applied only if the global gradient norm is at most skip_grad_norm (skip_nonfinite alone: if it is finite) and the
         step's loss is finite; otherwise it is skipped on the device, inside the same captured graph, with no host sync.  A skipped
         step leaves weights, moments, the bf16 shadow, every weight-derived copy, the moving average and the optimizer's step word
@@ -270,6 +274,13 @@ class TrainEngine:
         # count launch right before it; the head's gradient scale is then 1.0 and the 1 / N comes from the device.
         self.ignore_index = ops.check_loss_options(ignore_index=ignore_index)[2]
         self.token_count = None if self.ignore_index is None else torch.zeros(2, dtype=torch.float32, device=self.dev)
+        # the document mask (None: off, nothing below exists): like ignore_index a property of the data, so it holds in every program.
+        # doc_starts = the first visible key of every query of the batch in flight, written by one launch behind the embedding
+        if doc_separator is not None and (isinstance(doc_separator, bool) or not isinstance(doc_separator, int)
+                                          or not 0 <= doc_separator < self.V):
+            raise ValueError(f"doc_separator {doc_separator!r} is not a token id in [0, {self.V})")
+        self.doc_separator = doc_separator
+        self.doc_starts = None if doc_separator is None else torch.zeros(self.M, dtype=torch.int32, device=self.dev)
         # an exponential moving average of the weights, moved on inside the AdamW launch (None: no average, nothing below exists)
         self.ema_decay = ops.check_ema_options(ema_decay, ema_warmup)
         self.ema_warmup = bool(ema_warmup)
@@ -693,6 +704,9 @@ class TrainEngine:
                                     self.param_view("pos"), onehot=onehot).view(M, self.C)
         else:
             h = ops.embed_fwd(x_idx, self.param_view("tok"), self.param_view("pos"), onehot=onehot).view(M, self.C)
+        if self.doc_separator is not None:
+            # right behind the launch that left (or read) the ids; the backward pass of this program reads the same run
+            run.doc_starts = ops.doc_starts(x_idx, self.doc_separator, out=self.doc_starts if M == self.M else None)
         if self.chain_full and ops.block_chain_supported(M, self.C, self.act):
             h, saved = self._blocks_chain(run, h, B, T, want_grad)
             return self._head(run, h, y_idx, want_grad, saved, M)
@@ -727,7 +741,8 @@ class TrainEngine:
         r = ops.block_chain_fwd(2, M, C, x=h, ln1w=P["ln1w"], ln1b=P["ln1b"], wqkv=pk(P["wqkv"]))
         x, h1, m1, r1, qkv = h, r["h1"], r["mean1"], r["rstd1"], r["qkv"]
         for l in range(self.L):
-            o, lse = ops.attn_fwd(qkv, B, T, self.NH, self.H, self.H ** -0.5, p, run.rng, S.site_attn(l), keep=want_grad)
+            o, lse = ops.attn_fwd(qkv, B, T, self.NH, self.H, self.H ** -0.5, p, run.rng, S.site_attn(l), keep=want_grad,
+                                  doc_starts=run.doc_starts)
             last = l == self.L - 1
             if self.chain_warm:
                 # the layer's packed weight stream (wproj | w1 | w2 | the next block's wqkv: contiguous in the packed buffer)
@@ -873,7 +888,8 @@ class TrainEngine:
             S.weight_grad(sink, f"{l}.w2", g, f, C, 4 * C)
             S.weight_grad(sink, f"{l}.w1", r["df"], h2, 4 * C, C)
             S.weight_grad(sink, f"{l}.wproj", r["g2"], o, C, C)
-            dqkv = ops.attn_bwd(qkv, o, r["dout"], lse, B, T, self.NH, self.H, self.H ** -0.5, p, run.rng, S.site_attn(l))
+            dqkv = ops.attn_bwd(qkv, o, r["dout"], lse, B, T, self.NH, self.H, self.H ** -0.5, p, run.rng, S.site_attn(l),
+                                doc_starts=run.doc_starts)
             S.weight_grad(sink, f"{l}.wqkv", dqkv, h1, 3 * C, C)
             return dqkv
 
@@ -1397,6 +1413,8 @@ class TrainEngine:
         meta.update(self._loss_kw)      # only where set: a default engine writes and accepts exactly the files it always did
         if self.ignore_index is not None:
             meta["ignore_index"] = self.ignore_index
+        if getattr(self, "doc_separator", None) is not None:
+            meta["doc_separator"] = self.doc_separator
         if self.ema is not None:
             meta["ema"] = True
         if self.guard is not None:
@@ -1406,7 +1424,7 @@ class TrainEngine:
     def _check_meta(self, saved: dict) -> None:
         """CK.check_compat on the fields every engine has; the loss options in both directions (a field absent on either side reads
         as 0.0: a smoothed state is refused by a default engine as much as the reverse)"""
-        CK.check_compat(saved, {k: v for k, v in self._meta().items() if k not in self._LOSS_FIELDS and k not in ("ema", "ignore_index", "update_guard")})
+        CK.check_compat(saved, {k: v for k, v in self._meta().items() if k not in self._LOSS_FIELDS and k not in ("ema", "ignore_index", "update_guard", "doc_separator")})
         CK.check_ema_meta(saved, self.ema is not None)
         CK.check_guard_meta(saved, self.guard is not None)
         for field in self._LOSS_FIELDS:
@@ -1416,6 +1434,11 @@ class TrainEngine:
         theirs = saved.get("ignore_index")
         if isinstance(theirs, bool) or not (theirs is None or isinstance(theirs, int)) or theirs != self.ignore_index:
             raise ValueError(f"training state: meta.ignore_index differs: saved {theirs!r}, this run has {self.ignore_index!r}")
+        # the document mask changes no state: a file written without it loads into an engine with it and the other way round;
+        # two separators are compared
+        theirs, own = saved.get("doc_separator"), getattr(self, "doc_separator", None)
+        if theirs is not None and own is not None and (isinstance(theirs, bool) or not isinstance(theirs, int) or theirs != own):
+            raise ValueError(f"training state: meta.doc_separator differs: saved {theirs!r}, this run has {own!r}")
 
     def _param_names(self) -> List[str]:
         return [n for n, _ in self.model.named_parameters()]

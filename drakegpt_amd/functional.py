@@ -47,13 +47,15 @@ class AttnFn(torch.autograd.Function):
     """[LayerNorm ->] packed QKV -> causal attention [-> proj -> dropout] [+ residual]"""
 
     @staticmethod
-    def forward(ctx, x, ln_w, ln_b, wqkv, wproj, bproj, rng, act, residual, NH, H, p_attn, p_proj, layer):
+    def forward(ctx, x, ln_w, ln_b, wqkv, wproj, bproj, rng, act, residual, NH, H, p_attn, p_proj, layer, doc_starts=None):
         B, T, Cd = x.shape
         run = _run(act, rng)
+        run.doc_starts = doc_starts
         x2d = x.contiguous().view(B * T, Cd)
         y, saved = S.attn_fwd(run, x2d, ln_w, ln_b, wqkv, wproj, bproj, residual, B, T, NH, H, p_attn, p_proj, layer)
         x2d_s, h, mean, rstd, qkv, o, lse = saved
         ctx.save_for_backward(x2d_s, h, mean, rstd, qkv, o, lse, ln_w, wqkv, wproj, rng)
+        ctx.doc_starts = doc_starts
         ctx.cfg = (act, residual, B, T, NH, H, p_attn, p_proj, layer, bproj is not None)
         return y.view(B, T, -1)
 
@@ -62,6 +64,7 @@ class AttnFn(torch.autograd.Function):
         x2d, h, mean, rstd, qkv, o, lse, ln_w, wqkv, wproj, rng = ctx.saved_tensors
         act, residual, B, T, NH, H, p_attn, p_proj, layer, has_bproj = ctx.cfg
         run = _run(act, rng)
+        run.doc_starts = ctx.doc_starts
         dy2 = dy.contiguous().view(B * T, -1)
         sink = S.LocalSink(B * T, dy.device)
         keys = {"wqkv": "wqkv", "wproj": "wproj", "bproj": "bproj", "ln_w": "ln_w", "ln_b": "ln_b"}
@@ -69,7 +72,7 @@ class AttnFn(torch.autograd.Function):
                         p_attn, p_proj, layer, sink, keys, need_dx=ctx.needs_input_grad[0])
         g = sink.finish()
         return (None if dx is None else dx.view(B, T, -1), g.get("ln_w"), g.get("ln_b"), g["wqkv"], g.get("wproj"),
-                g.get("bproj") if has_bproj else None, None, None, None, None, None, None, None, None)
+                g.get("bproj") if has_bproj else None, None, None, None, None, None, None, None, None, None)
 
 
 class FFNFn(torch.autograd.Function):
@@ -165,8 +168,9 @@ def embed(idx, tok, pos):
     return EmbedFn.apply(idx, tok, pos)
 
 
-def attention(x, ln_w, ln_b, wqkv, wproj, bproj, rng, act, residual, NH, H, p_attn, p_proj, layer):
-    return AttnFn.apply(x, ln_w, ln_b, wqkv, wproj, bproj, rng, act, residual, NH, H, p_attn, p_proj, layer)
+def attention(x, ln_w, ln_b, wqkv, wproj, bproj, rng, act, residual, NH, H, p_attn, p_proj, layer, doc_starts=None):
+    """doc_starts: int32 [B*T] (ops.doc_starts), the document mask of the attention kernels; None: causal only"""
+    return AttnFn.apply(x, ln_w, ln_b, wqkv, wproj, bproj, rng, act, residual, NH, H, p_attn, p_proj, layer, doc_starts)
 
 
 def feed_forward(x, ln_w, ln_b, w1, b1, w2, b2, rng, act, residual, p, layer):

@@ -398,6 +398,37 @@ class _LM(HipModule):
         self.label_smoothing, self.z_loss, self.ignore_index = ops.check_loss_options(label_smoothing, z_loss, ignore_index)
         return self
 
+    # document mask: like ignore_index it describes the data, not the objective -- a plain attribute, applied in train() and eval()
+    doc_separator = None
+
+    def set_doc_separator(self, token_id=None):
+        """token_id (None: off): a document of the packed batch ends WITH this token, and forward(idx, targets) lets no token
+        attend across it -- query t sees the keys from 1 + the last separator before t (dg_doc_starts, the DOC attention
+        kernels), in train() and in eval().  Position embeddings are not reset per document.  generate does not apply the mask."""
+        if token_id is not None:
+            V = self.token_embedding_table.weight.shape[0]
+            if isinstance(token_id, bool) or not isinstance(token_id, int) or not 0 <= token_id < V:
+                raise ValueError(f"doc separator {token_id!r} is not a token id in [0, {V})")
+        self.doc_separator = token_id
+        return self
+
+    def _set_doc_starts(self, starts):
+        from .model_component import Head, _MultiHeadBase
+        for m in self.modules():
+            if isinstance(m, (Head, _MultiHeadBase)):
+                m._doc_starts = starts
+
+    def _unmasked(self, idx):
+        """forward(idx) without the document mask: generate's logits source"""
+        sep = self.doc_separator
+        if sep is None:
+            return self(idx)
+        self.doc_separator = None
+        try:
+            return self(idx)
+        finally:
+            self.doc_separator = sep
+
     def _loss(self, logits, targets):
         if self.training:
             return HF.cross_entropy(logits, targets, self.label_smoothing, self.z_loss, self.ignore_index)
@@ -408,7 +439,14 @@ class _LM(HipModule):
             raise ValueError("idx must be (B, T)")
         self._check_ids(idx, targets)
         rng = self._rng_snapshot(idx.device, self._any_dropout())
-        logits = self._head(self._body(self._embed(idx), rng))
+        if self.doc_separator is None:
+            logits = self._head(self._body(self._embed(idx), rng))
+        else:
+            self._set_doc_starts(ops.doc_starts(idx if idx.stride(1) == 1 else idx.contiguous(), self.doc_separator))
+            try:
+                logits = self._head(self._body(self._embed(idx), rng))
+            finally:
+                self._set_doc_starts(None)
         if targets is None:
             return logits, None
         B, T, V = logits.shape
@@ -419,7 +457,7 @@ class _LM(HipModule):
     def _window_logits(self, idx):
         """the host loop's logits source of every model: the full forward on the cropped window, last position"""
         cond = idx if self.context_length is None else idx[:, -self.context_length:]
-        logits, _ = self(cond.contiguous())
+        logits, _ = self._unmasked(cond.contiguous())
         return logits[:, -1, :]
 
     @staticmethod
@@ -458,7 +496,9 @@ class _LM(HipModule):
         row, holds per row the prompt, its tokens, then pad_token; a row ends at p_b + max_new_tokens or at its stop token.  One
         shared position walks all rows from min p_b: a row still inside its prompt keeps its prompt token, a row past it samples
         (dg_sample_rows_ragged), so row b has the tokens of a call on prompt b alone in that row with the same seed.
-        return_lengths=True: (ids, the rows' final lengths as int64 [B]), in any call."""
+        return_lengths=True: (ids, the rows' final lengths as int64 [B]), in any call.
+        The document mask (set_doc_separator) is NOT applied here: the tokens with a separator set are bit for bit those without.
+        To end a sample at the end of its document, pass stop_tokens=[sep]."""
         req = Sampling.checked(self.token_embedding_table.weight.shape[0], generator, sampler, temperature, top_k, seed, top_p, min_p,
                                repetition_penalty, presence_penalty, frequency_penalty, logit_bias, stop_tokens, pad_token, stop_poll,
                                prompt_lengths, tuple(getattr(idx, "shape", ())), return_lengths)
@@ -543,7 +583,7 @@ class _LM(HipModule):
         try:
             for L in range(t0, total):
                 lo = 0 if ctx is None else max(0, L - ctx)
-                logits, _ = self(ids[:, lo:L].contiguous())
+                logits, _ = self._unmasked(ids[:, lo:L].contiguous())
                 ops.sample_rows(logits[:, -1, :], state, params, ids=ids, **kw)
                 ops.state_advance(state)
                 if stop_poll_due(req.poll, L + 1 - t0, lengths):
@@ -764,7 +804,9 @@ class TransformerLM(_BlocksLM):
         graphs for every setting of the sampler; a call with any control replays a second pair of graphs, captured once, whose
         sampler is dg_sample_rows_control.  prompt_lengths / return_lengths: as in _LM.generate; the graph-replayed path prefills
         idx[:, :min p_b] in one pass, the rows with longer prompts ride along through their remaining prompt tokens one step
-        each, and a third pair of graphs, whose sampler is dg_sample_rows_ragged, is captured on the first such call."""
+        each, and a third pair of graphs, whose sampler is dg_sample_rows_ragged, is captured on the first such call.
+        The document mask (set_doc_separator) is not applied: neither the decode kernels, the prefill nor the graphs know it, and
+        the tokens are bit for bit those without a separator set; stop_tokens=[sep] ends a sample at the end of its document."""
         req = Sampling.checked(self.token_embedding_table.weight.shape[0], generator, sampler, temperature, top_k, seed, top_p, min_p,
                                repetition_penalty, presence_penalty, frequency_penalty, logit_bias, stop_tokens, pad_token, stop_poll,
                                prompt_lengths, tuple(getattr(idx, "shape", ())), return_lengths)

@@ -117,13 +117,15 @@ class Head(HipModule):
         self.register_buffer("tril", torch.tril(torch.ones(context_length, context_length)))
         self._p = 0.0
 
+    _doc_starts = None        # document mask of the forward in flight (set by the language model around its body; None: causal only)
+
     def forward(self, x):
         B, T, C = x.shape
         _check_width(C, self.act_dtype, "embedding_dim")
         _check_width(3 * self.head_size, self.act_dtype, "3*head_size")
         rng = self._rng_snapshot(x.device, self._p > 0.0)
         return HF.attention(x, None, None, _pack_qkv([self]), None, None, rng, self.run_mode, False, 1,
-                            self.head_size, self._p, 0.0, self.layer_index)
+                            self.head_size, self._p, 0.0, self.layer_index, self._doc_starts)
 
 
 class Head2(Head):
@@ -136,6 +138,8 @@ class Head2(Head):
 
 
 class _MultiHeadBase(HipModule):
+    _doc_starts = None        # as Head._doc_starts
+
     def _attend(self, x, ln_w=None, ln_b=None, residual=False, rng="auto"):
         B, T, C = x.shape
         heads = list(self.heads)
@@ -149,7 +153,8 @@ class _MultiHeadBase(HipModule):
         if rng == "auto":
             rng = self._rng_snapshot(x.device, p > 0.0)
         return HF.attention(x, ln_w, ln_b, _pack_qkv(heads), None if proj is None else proj.weight,
-                            None if proj is None else proj.bias, rng, self.run_mode, residual, NH, H, p, p, self.layer_index)
+                            None if proj is None else proj.bias, rng, self.run_mode, residual, NH, H, p, p, self.layer_index,
+                            self._doc_starts)
 
     def forward(self, x):
         return self._attend(x)

@@ -601,9 +601,30 @@ def _attn_fp8_arg(fp8_out, shape, fmt: torch.dtype, dev, only8: bool = False):
     return AttnFp8Out(_p(q8), _p(hist3), _p(step_state), _p(sinv), 1 if only8 else 0), q8, sinv
 
 
+def doc_starts(ids: Tensor, sep: int, out: Optional[Tensor] = None) -> Tensor:
+    """ids int64 [B, T] (rows may be strided) -> int32 [B*T]: starts[b, t] = 1 + the last j < t with ids[b, j] == sep, or 0 -- the
+    first key query t may attend to under the document mask (a document ends WITH its separator)."""
+    if ids.dim() != 2 or ids.dtype != torch.int64 or not ids.is_cuda or (ids.shape[1] > 1 and ids.stride(1) != 1):
+        raise RuntimeError("doc_starts: ids must be a CUDA int64 [B, T] tensor with contiguous rows")
+    B, T = ids.shape
+    if out is None:
+        out = torch.empty(B * T, dtype=torch.int32, device=ids.device)
+    else:
+        _chk_doc_starts(out, B, T)
+    check(lib.dg_doc_starts(_p(ids), ids.stride(0) if B > 1 else T, B, T, int(sep), _p(out), _stream()), "dg_doc_starts")
+    return out
+
+
+def _chk_doc_starts(doc_starts: Tensor, B: int, T: int) -> None:
+    _chk(doc_starts, "doc_starts", torch.int32)
+    if doc_starts.numel() != B * T:
+        raise RuntimeError(f"doc_starts holds {doc_starts.numel()} values, expected B*T = {B * T}")
+
+
 def attn_fwd(qkv: Tensor, B: int, T: int, NH: int, H: int, scale: float, p: float, rng_state: Optional[Tensor], site: int,
-             keep: bool = False, fp8_out=None):
-    """fp8_out = (hist3, step_state) (precision fp8, attn_fp8_out_supported): the output also as e4m3 with delayed scaling -- the
+             keep: bool = False, fp8_out=None, doc_starts: Optional[Tensor] = None):
+    """doc_starts (int32 [B*T], ops.doc_starts): document mask -- query i attends to keys doc_starts[b, i] <= j <= i only.
+    fp8_out = (hist3, step_state) (precision fp8, attn_fp8_out_supported): the output also as e4m3 with delayed scaling -- the
     attribute `dg_fp8` = (e4m3 copy, scale_inv) travels with it.
     keep=True (training with dropout, a backward pass follows): the forward pass also leaves its dropout keep decisions as
     wave masks (dg_attn_keep_bits_bytes; 128 bytes per unmasked 32 x 32 tile) -- they travel with the output as its attribute
@@ -619,7 +640,18 @@ def attn_fwd(qkv: Tensor, B: int, T: int, NH: int, H: int, scale: float, p: floa
         n = int(lib.dg_attn_keep_bits_bytes(B, T, NH, H, dt_code(qkv.dtype)))
         if n > 0:
             kb = torch.empty(n, dtype=torch.uint8, device=qkv.device)
-    if fp8_out is not None:
+    if doc_starts is not None:
+        import ctypes
+        _chk_doc_starts(doc_starts, B, T)
+        arg = None
+        if fp8_out is not None:
+            arg, q8, sinv = _attn_fp8_arg(fp8_out, (B * T, NH * H), torch.float8_e4m3fn, qkv.device)
+        check(lib.dg_attn_fwd_doc(_p(qkv), _p(out), _p(lse), B, T, NH, H, float(scale), float(p), _p(rng_state) if p > 0.0 else None,
+                                  site, dt_code(qkv.dtype), _p(kb), kb.numel() if kb is not None else 0,
+                                  ctypes.byref(arg) if arg is not None else None, _p(doc_starts), _stream()), "dg_attn_fwd_doc")
+        if arg is not None:
+            out.dg_fp8 = (q8, sinv)
+    elif fp8_out is not None:
         import ctypes
         arg, q8, sinv = _attn_fp8_arg(fp8_out, (B * T, NH * H), torch.float8_e4m3fn, qkv.device)
         check(lib.dg_attn_fwd_fp8(_p(qkv), _p(out), _p(lse), B, T, NH, H, float(scale), float(p), _p(rng_state) if p > 0.0 else None,
@@ -636,8 +668,10 @@ def attn_fwd(qkv: Tensor, B: int, T: int, NH: int, H: int, scale: float, p: floa
 
 def attn_bwd(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, B: int, T: int, NH: int, H: int, scale: float, p: float,
              rng_state: Optional[Tensor], site: int, keep_bits: Optional[Tensor] = None, fp8_out=None, fp8_out_only: bool = False, *,
-             tile_scratch: bool = True) -> Tensor:
-    """keep_bits: the forward pass's keep masks (attn_fwd(..., keep=True) leaves them as out.dg_keep); default: taken from `out`.
+             tile_scratch: bool = True, doc_starts: Optional[Tensor] = None) -> Tensor:
+    """doc_starts: the document mask of the forward pass (attn_fwd); on a shape that takes the MFMA kernels it needs the tile
+    scratch (the recompute form of the dK/dV pass has no document variant): ValueError with tile_scratch=False.
+    keep_bits: the forward pass's keep masks (attn_fwd(..., keep=True) leaves them as out.dg_keep); default: taken from `out`.
     fp8_out = (hist3, step_state): dqkv also as e5m2 (attribute `dg_fp8` = (e5m2 copy, scale_inv)); fp8_out_only: the bf16 dqkv is
     not written (marked `dg_unwritten`).
     tile_scratch=False: the workspace holds the delta floats only, and the dK/dV pass recomputes the scores instead of reading the
@@ -653,6 +687,23 @@ def attn_bwd(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, B: int, T: int
     dqkv = torch.empty_like(qkv)
     nws = lib.dg_attn_bwd_workspace_bytes(B, T, NH, H, dt_code(qkv.dtype)) if tile_scratch else B * NH * T * 4
     ws = torch.empty(int(nws), dtype=torch.uint8, device=qkv.device)
+    if doc_starts is not None:
+        import ctypes
+        _chk_doc_starts(doc_starts, B, T)
+        if not tile_scratch and int(lib.dg_attn_keep_bits_bytes(B, T, NH, H, dt_code(qkv.dtype))) > 0:
+            raise ValueError("attn_bwd: doc_starts needs tile_scratch=True on a shape that takes the MFMA kernels")
+        arg = None
+        if fp8_out is not None:
+            arg, q8, sinv = _attn_fp8_arg(fp8_out, tuple(qkv.shape), torch.float8_e5m2, qkv.device, only8=fp8_out_only)
+        check(lib.dg_attn_bwd_doc(_p(qkv), _p(out), _p(dout), _p(lse), _p(dqkv), _p(ws), ws.numel(), B, T, NH, H, float(scale), float(p),
+                                  _p(rng_state) if p > 0.0 else None, site, dt_code(qkv.dtype), _p(keep_bits),
+                                  keep_bits.numel() if keep_bits is not None else 0, ctypes.byref(arg) if arg is not None else None,
+                                  _p(doc_starts), _stream()), "dg_attn_bwd_doc")
+        if arg is not None:
+            dqkv.dg_fp8 = (q8, sinv)
+            if fp8_out_only:
+                dqkv.dg_unwritten = True
+        return dqkv
     if fp8_out is not None:
         import ctypes
         arg, q8, sinv = _attn_fp8_arg(fp8_out, tuple(qkv.shape), torch.float8_e5m2, qkv.device, only8=fp8_out_only)

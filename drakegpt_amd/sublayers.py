@@ -168,6 +168,7 @@ class Run:
     fp8_only: bool = False               # engine, precision fp8 with the fp8 dW: the FFN hidden layer and its gradient are read as fp8
                                          # only (by the next GEMM and by the grouped dW launch), so their bf16 form is not written
     split: bool = False                  # precision = "bf16x3": fp32 operands, every GEMM contracted as split bf16 (hi + lo)
+    doc_starts: Optional[Tensor] = None  # document mask: int32 [B*T] first visible key of every query (ops.doc_starts); None: causal only
 
     def p(self, p: float) -> float:
         return p if (self.rng is not None and p > 0.0) else 0.0
@@ -345,7 +346,7 @@ def attn_fwd(run: Run, x2d: Tensor, ln_w: Optional[Tensor], ln_b: Optional[Tenso
     okey = f"{layer}.o#attn"
     f8 = _attn_fp8_out(run, okey, None, B, T, NH, H, NH * H) if wproj is not None else None
     o, lse = ops.attn_fwd(qkv, B, T, NH, H, H ** -0.5, run.p(p_attn), run.rng, site_attn(layer), keep=True,     # (keep masks: only with dropout on)
-                          fp8_out=f8)
+                          fp8_out=f8, doc_starts=run.doc_starts)
     if wproj is not None and run.fp8_seed:
         _attn_fp8_out(run, okey, o, B, T, NH, H, NH * H)
     if wproj is not None:
@@ -387,7 +388,7 @@ def attn_bwd(run: Run, saved, dy: Tensor, ln_w: Optional[Tensor], wqkv: Tensor, 
     if f8 is not None and run.weights.bwd8(wqkv)[0].shape[1] != wqkv.shape[0]:
         f8 = None                                  # (linear_dx would not take the fp8 GEMM)
     dqkv = ops.attn_bwd(qkv, o, do, lse, B, T, NH, H, H ** -0.5, run.p(p_attn), run.rng, site_attn(layer), fp8_out=f8,
-                        fp8_out_only=f8 is not None and run.fp8_only)
+                        fp8_out_only=f8 is not None and run.fp8_only, doc_starts=run.doc_starts)
     if need_dx and run.fp8_seed:
         _attn_fp8_out(run, gkey, dqkv, B, T, NH, H, wqkv.shape[0])
     weight_grad(sink, keys["wqkv"], dqkv, h, wqkv.shape[0], wqkv.shape[1], split=run.split)

@@ -251,6 +251,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="leave every position whose target is token ID out of the loss, in training and in the evaluation lines; each "
                     "batch's mean is over the targets that remain (F.cross_entropy's ignore_index; default: off).  A resumed run must "
                     "repeat it; not with the fp8 loss head (--precision fp8 at a large vocabulary)")
+    ap.add_argument("--doc-separator", default=None, metavar="TOKEN",
+                    help="document-masked attention: a document of the packed corpus ends with TOKEN and no token attends across it, in "
+                    "training and in the evaluation lines (default: off).  TOKEN is an integer token id, or a single character looked "
+                    "up in the tokenizer's table (needs --data).  Sampling does not apply the mask.  Often combined with --ignore-token")
     ap.add_argument("--ema-decay", type=float, default=None, metavar="D",
                     help="keep an exponential moving average of the weights, ema += (w - ema) * (1 - D) after every optimizer step, "
                     "in (0, 1) (default: off).  Evaluation lines gain val_loss_ema, the final sample is drawn from the average and "
@@ -312,6 +316,27 @@ def parse_args(argv=None):
     if args.state_path is None:
         args.state_path = get_model_path(args.model_dir, args.model, args.scale)[:-len(".pt")] + ".state.pt"
     return args
+
+
+def doc_separator_id(token: Optional[str], encode, vocab_size: int) -> Optional[int]:
+    """--doc-separator TOKEN -> token id: an integer id, or a single character looked up in the tokenizer's table (``encode``, None
+    when the run has no text to build one from).  SystemExit names a character that is not in the vocabulary."""
+    if token is None:
+        return None
+    try:
+        tid = int(token)
+    except ValueError:
+        if len(token) != 1:
+            raise SystemExit(f"--doc-separator: {token!r} is neither an integer token id nor a single character") from None
+        if encode is None:
+            raise SystemExit(f"--doc-separator: the character {token!r} needs the tokenizer's table (--data)") from None
+        try:
+            tid = int(encode(token)[0])
+        except KeyError:
+            raise SystemExit(f"--doc-separator: the character {token!r} is not in the vocabulary") from None
+    if not 0 <= tid < vocab_size:
+        raise SystemExit(f"--doc-separator: token id {tid} is outside the vocabulary [0, {vocab_size})")
+    return tid
 
 
 def _to_cpu(obj):
@@ -393,18 +418,20 @@ def main(argv=None):
     if bool(args.train_data) != bool(args.val_data):
         raise SystemExit("--train-data and --val-data go together")
     decode = lambda ids: " ".join(str(i) for i in ids)      # noqa: E731
+    encode = None                                           # the tokenizer's table, where the run has a text
     if args.train_data:
         # the reference's flow (src/train.py:94-100): token streams from the .pt files, the mapper from the text
         train_data, val_data = load_train_val_data(args.train_data, args.val_data)
         if args.data:
             with open(args.data, "r", encoding="utf-8") as f:
-                _, decode, vocab_size = get_mapper(f.read())
+                encode, decode, vocab_size = get_mapper(f.read())
         else:
             vocab_size = int(max(train_data.max(), val_data.max())) + 1
     elif args.data:
         with open(args.data, "r", encoding="utf-8") as f:
             text = f.read()
         data, decode, vocab_size = encode_text(text)
+        encode = get_mapper(text)[0]
         train_data, val_data = split_train_val(data)
     else:
         vocab_size = DRAKE_VOCAB_SIZE
@@ -414,10 +441,14 @@ def main(argv=None):
 
     params = PRESETS[args.preset] if args.preset else (SCALE_PARAMS if args.scale else PARAMS)
     vocab_size = params.get("vocab_size", vocab_size)
+    doc_sep = doc_separator_id(args.doc_separator, encode, vocab_size)
     model, model_config, params = build_model(args.model, False, params, params, vocab_size, device, args.precision)
     if rank == 0:
         print(f"Selected {args.model} model for training. Model has {model_params(params, args.model, vocab_size)} parameters "
-              f"(reference estimate; actual {sum(p.numel() for p in model.parameters())}).")
+              f"(reference estimate; actual {sum(p.numel() for p in model.parameters())})."
+              + ("" if doc_sep is None else f" Document separator: token {doc_sep} (no attention across it)."))
+    if doc_sep is not None:
+        model.set_doc_separator(doc_sep)          # forward(idx, targets) in train() and eval(); the engine below gets it as well
     B, T = params["batch_size"], params["context_length"]
     base_lr, max_lr = params["base_lr"], params["max_lr"]
 
@@ -432,6 +463,7 @@ def main(argv=None):
                              max_grad_norm=args.grad_clip, accum_steps=K, lr_schedule=table, no_decay=args.no_decay,
                              label_smoothing=args.label_smoothing, z_loss=args.z_loss,
                              **({} if args.ignore_token is None else {"ignore_index": args.ignore_token}),
+                             **({} if doc_sep is None else {"doc_separator": doc_sep}),
                              **guard_kw,
                              **({} if args.ema_decay is None else {"ema_decay": args.ema_decay, "ema_warmup": args.ema_warmup}))
         engine.set_corpus(train_dev)

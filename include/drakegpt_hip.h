@@ -360,6 +360,28 @@ int dg_attn_bwd_fp8(const void* qkv, const void* out, const void* dout, const fl
                     float scale, float dropout_p, const uint32_t* rng_state, uint32_t site,
                     int dtype, const void* keep_bits, int64_t keep_bits_bytes, const dg_attn_fp8_out* fp8, void* stream);
 
+/* Document-masked attention (opt-in): no attention across a separator token of a packed corpus -- ref: get_batch (src/model.py) cuts
+ * its windows out of ONE concatenated text, and Head2.forward src/model_component.py:392-405 (the tril mask of :401) lets a token
+ * attend to the document before it; there is no ATen call site for the mask itself, it is one more compare in the score loops of
+ * K5..K11's kernels.  A document ends WITH its separator:
+ *   starts[b, t] = 1 + max{ j < t : ids[b, j] == sep }, or 0 without such a j     (0 <= starts[t] <= t, non-decreasing in t)
+ * and query i attends to keys starts[i] <= j <= i.  Everything else is dg_attn_fwd's: scale, softmax, dropout without
+ * renormalisation, the dropout element index on absolute positions.  A masked probability and its gradient are exact zeros.
+ * dg_doc_starts: ids int64 [B, ld_ids >= T], starts int32 [B*T]; a max-scan along each row, no atomics. */
+int dg_doc_starts(const int64_t* ids, int64_t ld_ids, int B, int T, int64_t sep, int32_t* starts, void* stream);
+/* dg_attn_fwd_fp8 / dg_attn_bwd_fp8 (fp8 nullable) with the document starts.  starts == NULL: exactly their launches.  On a shape
+ * that takes the MFMA kernels the backward entry needs the tile scratch (workspace of dg_attn_bwd_workspace_bytes): DG_ERR_ARG
+ * without.  The kernels assume the invariants above; other values are clamped to [0, t] (results unspecified, accesses in bounds). */
+int dg_attn_fwd_doc(const void* qkv, void* out, float* lse, int B, int T, int NH, int H,
+                    float scale, float dropout_p, const uint32_t* rng_state, uint32_t site,
+                    int dtype, void* keep_bits, int64_t keep_bits_bytes, const dg_attn_fp8_out* fp8,
+                    const int32_t* starts, void* stream);
+int dg_attn_bwd_doc(const void* qkv, const void* out, const void* dout, const float* lse,
+                    void* dqkv, void* workspace, int64_t workspace_bytes, int B, int T, int NH, int H,
+                    float scale, float dropout_p, const uint32_t* rng_state, uint32_t site,
+                    int dtype, const void* keep_bits, int64_t keep_bits_bytes, const dg_attn_fp8_out* fp8,
+                    const int32_t* starts, void* stream);
+
 /* Single-query attention against a K/V cache for generate() -- ref: src/model.py:625-635 re-runs the
  * whole forward per new token; with the cache only the new position is computed.  qkv_cache:
  * [B, Tcap, 3*NH*H] in the training layout (row = position; the QKV GEMM of the new token writes row t);
