@@ -225,195 +225,236 @@ static int dg_num_cus() {
     return v;
 }
 
-extern "C" int dg_gemm_nt_sign_bits_supported(const dg_gemm_nt_args* a) {
-    if (!a || a->N <= 0 || a->N % 8) return 0;
-    if (a->in_dtype == DG_BF16) return a->K % 64 == 0 && a->K >= 128;
-    return (a->in_dtype == DG_FP8_E4M3 || a->in_dtype == DG_FP8_E5M2) && a->K % 128 == 0 && a->K >= 256;
+// ---------------------------------------------------------------------------------------------
+// NT launch plan.  Every decision of a dg_gemm_nt call, in one place: dg_gemm_nt launches what nt_plan returns, the query entries
+// read the same plan and dg_debug_nt_plan reports it.  Pure host code: the CU count and whether a stamp buffer is set come in.
+const char* dg_nt_ws_bf16(const NtWsKey& k, const NtParams* p, int grid, hipStream_t s) {
+    static const NtWsInstance rows[] = {NT_WS_INSTANCES_BF16(NT_WS_ROW)};
+    for (const NtWsInstance& r : rows) {
+        if (!(r.key == k)) continue;
+        if (p) hipLaunchKernelGGL(r.kernel, dim3(grid), dim3(NT_WS_BLOCK), 0, s, *p);
+        return r.name;
+    }
+    return nullptr;
 }
+static const char* nt_ws_instance(const NtWsKey& k, const NtParams* p, int grid, hipStream_t s) {
+    return k.f8 == 0 ? dg_nt_ws_bf16(k, p, grid, s) : (k.f8 == 3 ? dg_nt_ws_x3(k, p, grid, s) : dg_nt_ws_fp8(k, p, grid, s));
+}
+// the register-staged kernels, by (operands bf16) + (output bf16), and the split-bf16 one
+#define NT_STAGED_ROW(...) {#__VA_ARGS__, __VA_ARGS__}
+static const struct { const char* name; void (*kernel)(NtParams); } nt_staged[] = {
+    NT_STAGED_ROW(gemm_nt_kernel<float,float>), NT_STAGED_ROW(gemm_nt_kernel<bf16_t,float>),
+    NT_STAGED_ROW(gemm_nt_kernel<bf16_t,bf16_t>), NT_STAGED_ROW(gemm_nt_x3_kernel)};
 
-// 128 x 192 tiles of the wave-specialised kernel (otherwise 128 x 128)
-static bool dg_nt_wide(int N) { return N % 192 == 0; }
-// fp8 copy of the output from the epilogue: (EPI 8) the bias + ReLU + sign-bit form with e4m3 operands -> e4m3 copy, or (EPI 9)
-// the sign-bit-masked dX form with column sums and e5m2 gradients -> e5m2 copy; bf16 output, every tile whole and on the
-// vector path, and exactly DG_FP8_AMAX_PARTS persistent workgroups (one partial maximum each).
-extern "C" int dg_gemm_nt_colsum_supported(const dg_gemm_nt_args* a);
-extern "C" int dg_gemm_nt_fp8_out_supported(const dg_gemm_nt_args* a) {
-    if (!a || !dg_gemm_nt_sign_bits_supported(a) || a->out_dtype != DG_BF16 || g_stamp_buffer) return 0;
-    const int bn = dg_nt_wide(a->N) ? 192 : 128;
-    if (a->M % BM || a->N % bn || a->ldc % 8 || !dg_aligned16(a->C)) return 0;
-    const int64_t n_tiles = (int64_t)(a->M / BM) * (a->N / bn);
-    if (dg_num_cus() != DG_FP8_AMAX_PARTS || n_tiles < DG_FP8_AMAX_PARTS) return 0;
-    if (a->in_dtype == DG_FP8_E4M3)
-        return a->bias && dg_aligned16(a->bias) && a->relu && a->sign_bits_out && !a->relu_mask && !a->residual && !a->sign_bits &&
-               !a->colsum_part && !(a->dropout_p > 0.f && a->rng_state);
-    if (a->in_dtype == DG_FP8_E5M2)
-        return a->colsum_part && dg_gemm_nt_colsum_supported(a);
-    return 0;
+// the options of a call that are present, as one mask
+enum { NT_BIAS = 1, NT_RELU = 2, NT_MASK = 4, NT_DROP = 8, NT_RES = 16, NT_BITS_IN = 32, NT_BITS_OUT = 64, NT_COLSUM = 128, NT_FP8_OUT = 256,
+       NT_VALUE_OPTS = 127 };                                   // the seven that change the output's values
+// The specialised epilogues (what each one is: the EPI parameter of gemm_nt_ws_kernel, gemm_nt_ws.h) as data.  A call takes the
+// form whose `need` options are all present and whose `never` options are all absent -- every value option the form does not
+// name is in `never` --, with a bf16 output / the mask prefetch where the form asks for it; any other call, and every stamped
+// run, takes EPI 0.
+struct NtEpiForm { int epi, need, never; bool bf16_out, pf; };
+static constexpr NtEpiForm nt_form(int epi, int need, int never_too, bool bf16_out, bool pf) {
+    return {epi, need, (NT_VALUE_OPTS & ~need) | never_too, bf16_out, pf};
 }
+static constexpr NtEpiForm nt_epi_forms[] = {
+    nt_form(1, 0, 0, false, false),
+    nt_form(2, NT_BIAS | NT_RELU | NT_BITS_OUT, NT_FP8_OUT, true, false),
+    nt_form(8, NT_BIAS | NT_RELU | NT_BITS_OUT | NT_FP8_OUT, 0, true, false),
+    nt_form(3, NT_BIAS | NT_DROP | NT_RES, 0, false, false),
+    nt_form(4, NT_BITS_IN, NT_COLSUM, true, true),
+    nt_form(6, NT_BITS_IN | NT_COLSUM, NT_FP8_OUT, true, true),
+    nt_form(9, NT_BITS_IN | NT_COLSUM | NT_FP8_OUT, 0, true, true),
+    nt_form(5, NT_BIAS, 0, false, false),
+    nt_form(7, NT_BIAS | NT_RES, 0, false, false),
+};
 
 // bytes of the lane-ordered bit mask: one bit per element of every (whole) output tile of the kernel that will run
-extern "C" int64_t dg_gemm_nt_sign_bits_bytes(int M, int N) {
+static int64_t nt_sign_bits_bytes(int M, int N) {
     if (M <= 0 || N <= 0) return 0;
-    const int bn = dg_nt_wide(N) ? 192 : 128;
+    const int bn = N % 192 == 0 ? 192 : 128;
     return (int64_t)((M + BM - 1) / BM) * ((N + bn - 1) / bn) * (BM * bn / 8);
 }
+// Column sums, one partial row per (workgroup, wave row) instead of one per 32 rows of C.  Tile t of workgroup b of G is
+// remap(b + t G) = base(b % 8) + b / 8 + t G / 8, so with (G / 8) % tiles_n == 0 all tiles of a workgroup share one column block
+// and it writes ONE partial row per wave row at the end: 4 G / tiles_n rows, indexed 4 rank + wave row with rank = (b % 8)
+// (G / 8 / tiles_n) + (b / 8) / tiles_n, which numbers the workgroups of one column block 0 .. G / tiles_n - 1.
+static bool nt_cs_accum(int G, int tiles_n) { return G % 8 == 0 && (G / 8) % tiles_n == 0; }
 
-// Column sums in the epilogue: only the sign-bit-masked dX form (the one whose output is the pre-activation gradient a bias
-// gradient is the column sum of), every tile interior and on the vector path, no stamp buffer.
-extern "C" int dg_gemm_nt_colsum_supported(const dg_gemm_nt_args* a) {
-    if (!a || !dg_gemm_nt_sign_bits_supported(a) || !a->sign_bits || a->out_dtype != DG_BF16) return 0;
-    if (a->bias || a->relu || a->relu_mask || a->residual || a->sign_bits_out || (a->dropout_p > 0.f && a->rng_state)) return 0;
-    if (g_stamp_buffer) return 0;
-    const int bn = dg_nt_wide(a->N) ? 192 : 128;
-    return a->M % BM == 0 && a->N % bn == 0 && a->ldc % 8 == 0 && dg_aligned16(a->C);
-}
-// Number of partial rows the call writes (0 = not supported).  Tile t of workgroup b is remap(b + t G) = base(b % 8) + b / 8 +
-// t G / 8, so with (G / 8) % tiles_n == 0 all tiles of a workgroup share one column block and it writes ONE partial row per
-// wave row at the end: 4 G / tiles_n rows, indexed 4 rank + wave row with rank = (b % 8) (G / 8 / tiles_n) + (b / 8) / tiles_n,
-// which numbers the workgroups of one column block 0 .. G / tiles_n - 1.  Otherwise one partial row per 32 rows of C.
-static bool dg_nt_cs_accum(int n_tiles, int tiles_n) {
-    const int G = n_tiles < dg_num_cus() ? n_tiles : dg_num_cus();
-    return G % 8 == 0 && (G / 8) % tiles_n == 0;
-}
-extern "C" int dg_gemm_nt_colsum_rows(const dg_gemm_nt_args* a) {
-    if (!dg_gemm_nt_colsum_supported(a)) return 0;
-    const int bn = dg_nt_wide(a->N) ? 192 : 128;
-    const int tiles_n = a->N / bn, n_tiles = (a->M / BM) * tiles_n;
-    const int G = n_tiles < dg_num_cus() ? n_tiles : dg_num_cus();
-    return dg_nt_cs_accum(n_tiles, tiles_n) ? 4 * G / tiles_n : a->M / 32;
-}
+enum { NT_F_WS = 0, NT_F_STAGED, NT_F_X3 };                     // gemm_nt_ws_kernel, gemm_nt_kernel, gemm_nt_x3_kernel
+struct NtPlan {
+    int rc;                            // what dg_gemm_nt returns; everything down to q8_only is set only with DG_OK
+    int family, staged;                // staged: row of nt_staged (families 1 and 2)
+    NtWsKey inst;                      // family 0: the instance that runs (after the fallback rule below)
+    const char* name;
+    int grid, block;
+    int esz, K, tiles_n, n_tiles, cs_accum, vec_ok, mask_vec_ok, warm_b, drop, q8_only;     // NtParams (K: in the kernel's units)
+    // what the query entries report; these read M, N, K, ldc, the dtypes, C and which options are present, nothing else
+    int bn;                            // tile width
+    int sign_ok, colsum_ok, colsum_rows, fp8_out_ok;
+    int64_t sign_bits_bytes;
+};
 
-int dg_gemm_nt_fp8_launch(const NtParams& p, int f8, int out_dtype, bool pf, bool wide, int epi, dim3 pgrid, hipStream_t s);   // gemm_fp8.hip
-int dg_gemm_nt_x3_launch(const NtParams& p, bool wide, int epi, dim3 pgrid, hipStream_t s);   // gemm_x3.hip
+static NtPlan nt_plan(const dg_gemm_nt_args& a, int ncu, bool stamps) {
+    NtPlan pl = {};
+    const bool bf16 = a.in_dtype == DG_BF16, e4m3 = a.in_dtype == DG_FP8_E4M3, e5m2 = a.in_dtype == DG_FP8_E5M2;
+    const bool fp8 = e4m3 || e5m2, x3 = a.in_dtype == DG_F32X3, out_bf16 = a.out_dtype == DG_BF16;
+    const int esz = fp8 ? 1 : (bf16 ? 2 : 4), osz = out_bf16 ? 2 : 4, epc = 16 / esz;
+    const bool drop = a.dropout_p > 0.f && a.rng_state;
+    const int opts = (a.bias ? NT_BIAS : 0) | (a.relu ? NT_RELU : 0) | (a.relu_mask ? NT_MASK : 0) | (drop ? NT_DROP : 0) |
+                     (a.residual ? NT_RES : 0) | (a.sign_bits ? NT_BITS_IN : 0) | (a.sign_bits_out ? NT_BITS_OUT : 0) |
+                     (a.colsum_part ? NT_COLSUM : 0) | (a.fp8_out ? NT_FP8_OUT : 0);
 
-extern "C" int dg_gemm_nt(const dg_gemm_nt_args* a, void* stream) {
-    if (!a || !a->A || !a->B || !a->C || a->M <= 0 || a->N <= 0 || a->K <= 0) return DG_ERR_ARG;
-    const bool fp8 = a->in_dtype == DG_FP8_E4M3 || a->in_dtype == DG_FP8_E5M2;
-    const bool x3 = a->in_dtype == DG_F32X3;                  // fp32 operands, split-bf16 contraction
-    const int esz = fp8 ? 1 : (a->in_dtype == DG_BF16 ? 2 : 4);
-    const int epc = 16 / esz;
-    if (a->in_dtype != DG_BF16 && a->in_dtype != DG_F32 && !fp8 && !x3) return DG_ERR_DTYPE;
-    if (a->out_dtype != DG_BF16 && a->out_dtype != DG_F32) return DG_ERR_DTYPE;
-    if ((a->in_dtype == DG_F32 || x3) && a->out_dtype == DG_BF16) return DG_ERR_DTYPE;
+    // ---- what is offered
+    const bool wide = a.N % 192 == 0;                           // 128 x 192 tiles of the wave-specialised kernel (otherwise 128 x 128)
+    pl.bn = wide ? 192 : 128;
+    pl.sign_bits_bytes = nt_sign_bits_bytes(a.M, a.N);
+    pl.sign_ok = a.N > 0 && a.N % 8 == 0 && (bf16 ? a.K % 64 == 0 && a.K >= 128 : fp8 && a.K % 128 == 0 && a.K >= 256);
+    // column sums and the fp8 copy: bf16 output, every tile whole and on the vector path, no stamp buffer
+    const bool whole = pl.sign_ok && out_bf16 && !stamps && a.M % BM == 0 && a.N % pl.bn == 0 && a.ldc % 8 == 0 && dg_aligned16(a.C);
+    // column sums: only the sign-bit-masked dX form (the one whose output is the pre-activation gradient a bias gradient is the
+    // column sum of)
+    pl.colsum_ok = whole && (opts & NT_VALUE_OPTS) == NT_BITS_IN;
+    if (pl.colsum_ok) {
+        const int tiles_n = a.N / pl.bn, n_tiles = (a.M / BM) * tiles_n, G = n_tiles < ncu ? n_tiles : ncu;
+        pl.colsum_rows = nt_cs_accum(G, tiles_n) ? 4 * G / tiles_n : a.M / 32;
+    }
+    // fp8 copy of the output: (EPI 8) the bias + ReLU + sign-bit form with e4m3 operands -> e4m3 copy, or (EPI 9) the sign-bit-masked
+    // dX form with column sums and e5m2 gradients -> e5m2 copy; exactly DG_FP8_AMAX_PARTS persistent workgroups (one partial maximum each)
+    pl.fp8_out_ok = whole && ncu == DG_FP8_AMAX_PARTS && (int64_t)(a.M / BM) * (a.N / pl.bn) >= DG_FP8_AMAX_PARTS &&
+                    (e4m3 ? (opts & ~NT_FP8_OUT) == (NT_BIAS | NT_RELU | NT_BITS_OUT) && dg_aligned16(a.bias)
+                          : e5m2 && a.colsum_part && pl.colsum_ok);
+    const NtPlan offers = pl;
+    auto refuse = [&](int rc) { NtPlan r = offers; r.rc = rc; return r; };
+
+    // ---- is the call valid
+    if (!a.A || !a.B || !a.C || a.M <= 0 || a.N <= 0 || a.K <= 0) return refuse(DG_ERR_ARG);
+    if (!bf16 && a.in_dtype != DG_F32 && !fp8 && !x3) return refuse(DG_ERR_DTYPE);
+    if (!out_bf16 && a.out_dtype != DG_F32) return refuse(DG_ERR_DTYPE);
+    if ((a.in_dtype == DG_F32 || x3) && out_bf16) return refuse(DG_ERR_DTYPE);
     if (fp8) {
         // B (the weight operand) is e4m3; per-tensor dequantisation factors are mandatory; only the LDS-DMA kernel has an fp8 form
-        if (a->b_dtype != DG_FP8_E4M3 || !a->scale_a || !a->scale_b || a->relu_mask) return DG_ERR_ARG;
-        if (a->K % 128 || a->K < 256) return DG_ERR_ARG;
-    } else if (a->b_dtype != 0 && a->b_dtype != a->in_dtype && !(x3 && a->b_dtype == DG_F32)) return DG_ERR_DTYPE;
-    if (a->K % epc || a->lda % epc || a->ldb % epc || !dg_aligned16(a->A) || !dg_aligned16(a->B)) return DG_ERR_ALIGN;
-    if (a->lda < a->K || a->ldb < a->K || a->ldc < a->N) return DG_ERR_ARG;
-    if (a->dropout_p < 0.f || a->dropout_p >= 1.f) return DG_ERR_ARG;
-    if (a->sign_bits_out || a->sign_bits) {
-        if (!dg_gemm_nt_sign_bits_supported(a) || a->sign_bits_bytes < dg_gemm_nt_sign_bits_bytes(a->M, a->N) ||
-            (a->sign_bits && a->relu_mask)) return DG_ERR_ARG;
-    }
-    if (a->colsum_part && (!dg_gemm_nt_colsum_supported(a) || a->colsum_rows < dg_gemm_nt_colsum_rows(a) || a->colsum_ld < a->N ||
-                           a->colsum_ld % 4 || !dg_aligned16(a->colsum_part)))
-        return DG_ERR_ARG;
-    if (a->fp8_out && (!dg_gemm_nt_fp8_out_supported(a) || !a->fp8_out_parts2 || !a->fp8_out_step || !a->fp8_out_scale_inv ||
-                       a->ld_fp8_out < a->N || a->ld_fp8_out % 8 || (((uintptr_t)a->fp8_out) & 7)))
-        return DG_ERR_ARG;
-    NtParams p;
-    p.q8 = (unsigned char*)a->fp8_out; p.ldq8 = a->ld_fp8_out; p.q_parts2 = a->fp8_out_parts2; p.q_step = a->fp8_out_step;
-    p.q_scale_inv = a->fp8_out_scale_inv;
-    p.q8_only = (a->fp8_out && a->fp8_out_only) ? 1 : 0;
-    p.A = (const char*)a->A; p.lda_b = a->lda * esz;
-    p.B = (const char*)a->B; p.ldb_b = a->ldb * esz;
-    p.C = a->C; p.ldc = a->ldc;
+        if (a.b_dtype != DG_FP8_E4M3 || !a.scale_a || !a.scale_b || a.relu_mask) return refuse(DG_ERR_ARG);
+        if (a.K % 128 || a.K < 256) return refuse(DG_ERR_ARG);
+    } else if (a.b_dtype != 0 && a.b_dtype != a.in_dtype && !(x3 && a.b_dtype == DG_F32)) return refuse(DG_ERR_DTYPE);
+    if (a.K % epc || a.lda % epc || a.ldb % epc || !dg_aligned16(a.A) || !dg_aligned16(a.B)) return refuse(DG_ERR_ALIGN);
+    if (a.lda < a.K || a.ldb < a.K || a.ldc < a.N) return refuse(DG_ERR_ARG);
+    if (a.dropout_p < 0.f || a.dropout_p >= 1.f) return refuse(DG_ERR_ARG);
+    if ((opts & (NT_BITS_IN | NT_BITS_OUT)) &&
+        (!pl.sign_ok || a.sign_bits_bytes < pl.sign_bits_bytes || (a.sign_bits && a.relu_mask))) return refuse(DG_ERR_ARG);
+    if (a.colsum_part && (!pl.colsum_ok || a.colsum_rows < pl.colsum_rows || a.colsum_ld < a.N || a.colsum_ld % 4 ||
+                          !dg_aligned16(a.colsum_part))) return refuse(DG_ERR_ARG);
+    if (a.fp8_out && (!pl.fp8_out_ok || !a.fp8_out_parts2 || !a.fp8_out_step || !a.fp8_out_scale_inv || a.ld_fp8_out < a.N ||
+                      a.ld_fp8_out % 8 || (((uintptr_t)a.fp8_out) & 7))) return refuse(DG_ERR_ARG);
+
+    // ---- what runs
     // split form (x3_ws): the wave-specialised kernel where K is whole 128-byte steps, at least two; the generic one otherwise
-    const bool x3_ws = x3 && a->K % 32 == 0 && a->K >= 128;
-    p.M = a->M; p.N = a->N;
-    p.K = fp8 ? a->K / 2 : (x3_ws ? 2 * a->K : a->K);        // fp8 / split: K in 2-byte units, the kernel's K step is 128 BYTES
-    p.scale_a = a->scale_a; p.scale_b = a->scale_b;
+    const bool x3_ws = x3 && a.K % 32 == 0 && a.K >= 128;
+    pl.esz = esz;
+    pl.K = fp8 ? a.K / 2 : (x3_ws ? 2 * a.K : a.K);            // fp8 / split: K in 2-byte units, the kernel's K step is 128 BYTES
+    pl.drop = drop;
+    pl.q8_only = (a.fp8_out && a.fp8_out_only) ? 1 : 0;
+    pl.vec_ok = (a.ldc % 4 == 0) && ((((uintptr_t)a.C) % (4 * osz)) == 0) &&
+                (!a.residual || ((a.ldr % 4 == 0) && dg_aligned16(a.residual)));
+    pl.mask_vec_ok = a.relu_mask && (a.ldmask % 4 == 0) && ((((uintptr_t)a.relu_mask) % (4 * esz)) == 0);
+    {   // weights of at most 2 MB (every block Linear of the scaled model; not lm_head at the GPT-2 vocabulary), one touch per
+        // lane (headline step: 2.498 -> 2.478 ms); warm_b = touch rounds of 2 MB each
+        const int64_t wbytes = (int64_t)a.N * a.ldb * esz;
+        pl.warm_b = (wbytes <= ((int64_t)2 << 20) && (a.ldb * esz) % 128 == 0 && (((uintptr_t)a.B) & 127) == 0) ? (int)((wbytes + (2 << 20) - 1) >> 21) : 0;
+    }
+    const int tiles_m = (a.M + BM - 1) / BM;
+    if (!(fp8 || x3_ws || (bf16 && a.K % 64 == 0 && a.K >= 128))) {      // register-staged: one 128 x 128 tile per workgroup
+        pl.family = x3 ? NT_F_X3 : NT_F_STAGED;
+        pl.staged = x3 ? 3 : (bf16 ? 1 : 0) + (out_bf16 ? 1 : 0);
+        pl.name = nt_staged[pl.staged].name;
+        pl.tiles_n = (a.N + BN - 1) / BN;
+        pl.n_tiles = tiles_m * pl.tiles_n;
+        pl.grid = pl.n_tiles; pl.block = 256;
+        return pl;
+    }
+    pl.family = NT_F_WS;
+    pl.tiles_n = (a.N + pl.bn - 1) / pl.bn;
+    pl.n_tiles = tiles_m * pl.tiles_n;
+    pl.grid = pl.n_tiles < ncu ? pl.n_tiles : ncu;              // persistent: one workgroup per CU
+    pl.block = NT_WS_BLOCK;
+    pl.cs_accum = nt_cs_accum(pl.grid, pl.tiles_n) ? 1 : 0;
+    // the mask bits of the sign-bit dX form are prefetched ahead of the epilogue
+    const bool pf = a.sign_bits && pl.vec_ok && (!a.bias || dg_aligned16(a.bias)) && (a.ldc * osz) % 16 == 0 && dg_aligned16(a.C);
+    if (pf && e4m3) return refuse(DG_ERR_ARG);                  // the mask-prefetch form only exists for the dX direction
+    int epi = 0;
+    for (const NtEpiForm& f : nt_epi_forms)
+        if (!stamps && (opts & f.need) == f.need && !(opts & f.never) && (!f.bf16_out || out_bf16) && (!f.pf || pf)) epi = f.epi;
+    // Fallback rule: the exact instance; else the same with EPI 0; else that without the prefetch.  (bf16 and split operands
+    // always find the exact one: their lists hold every form their calls can classify as -- a split call cannot ask for a form
+    // with a bf16 output.  fp8: fp32 output of forms 1 and 5, forward forms on e5m2 operands -> EPI 0; e5m2, prefetch, fp32
+    // output -> EPI 0 without it.)
+    pl.inst = {a.out_dtype, pf, wide ? 6 : 4, epi, e4m3 ? 1 : (e5m2 ? 2 : (x3 ? 3 : 0))};
+    pl.name = nt_ws_instance(pl.inst, nullptr, 0, nullptr);
+    if (!pl.name) { pl.inst.epi = 0; pl.name = nt_ws_instance(pl.inst, nullptr, 0, nullptr); }
+    if (!pl.name) { pl.inst.pf = 0; pl.name = nt_ws_instance(pl.inst, nullptr, 0, nullptr); }
+    return pl.name ? pl : refuse(DG_ERR_ARG);
+}
+
+// the query entries: fields of the plan of the call they are asked about
+extern "C" int dg_gemm_nt_sign_bits_supported(const dg_gemm_nt_args* a) {
+    return a ? nt_plan(*a, dg_num_cus(), g_stamp_buffer != nullptr).sign_ok : 0;
+}
+extern "C" int dg_gemm_nt_fp8_out_supported(const dg_gemm_nt_args* a) {
+    return a ? nt_plan(*a, dg_num_cus(), g_stamp_buffer != nullptr).fp8_out_ok : 0;
+}
+extern "C" int dg_gemm_nt_colsum_supported(const dg_gemm_nt_args* a) {
+    return a ? nt_plan(*a, dg_num_cus(), g_stamp_buffer != nullptr).colsum_ok : 0;
+}
+// number of partial rows the call writes (0 = not supported)
+extern "C" int dg_gemm_nt_colsum_rows(const dg_gemm_nt_args* a) {
+    return a ? nt_plan(*a, dg_num_cus(), g_stamp_buffer != nullptr).colsum_rows : 0;
+}
+extern "C" int64_t dg_gemm_nt_sign_bits_bytes(int M, int N) { return nt_sign_bits_bytes(M, N); }
+
+extern "C" int dg_gemm_nt(const dg_gemm_nt_args* a, void* stream) {
+    if (!a) return DG_ERR_ARG;
+    const NtPlan pl = nt_plan(*a, dg_num_cus(), g_stamp_buffer != nullptr);
+    if (pl.rc != DG_OK) return pl.rc;
+    NtParams p;
+    p.A = (const char*)a->A; p.lda_b = a->lda * pl.esz;
+    p.B = (const char*)a->B; p.ldb_b = a->ldb * pl.esz;
+    p.C = a->C; p.ldc = a->ldc;
+    p.M = a->M; p.N = a->N; p.K = pl.K;
     p.bias = a->bias; p.relu = a->relu;
     p.relu_mask = a->relu_mask; p.ldmask = a->ldmask;
     p.bits_out = a->sign_bits_out; p.bits_in = a->sign_bits;
-    p.colsum_part = a->colsum_part; p.colsum_ld = a->colsum_ld; p.cs_accum = 0;
+    p.colsum_part = a->colsum_part; p.colsum_ld = a->colsum_ld; p.cs_accum = pl.cs_accum;
     p.residual = a->residual; p.ldr = a->ldr;
-    p.drop = (a->dropout_p > 0.f && a->rng_state) ? 1 : 0;
     p.inv_keep = 1.f / (1.f - a->dropout_p);
     p.thr = dg_drop_threshold(a->dropout_p);
+    p.drop = pl.drop;
     p.rng_state = a->rng_state; p.site = a->site;
-    const int osz = a->out_dtype == DG_BF16 ? 2 : 4;
-    p.vec_ok = (a->ldc % 4 == 0) && ((((uintptr_t)a->C) % (4 * osz)) == 0) &&
-               (!a->residual || ((a->ldr % 4 == 0) && dg_aligned16(a->residual)));
-    p.mask_vec_ok = a->relu_mask && (a->ldmask % 4 == 0) && ((((uintptr_t)a->relu_mask) % (4 * esz)) == 0);
-    {   // weights of at most 2 MB (every block Linear of the scaled model; not lm_head at the GPT-2 vocabulary), one touch per
-        // lane (headline step: 2.498 -> 2.478 ms); warm_b = touch rounds of 2 MB each
-        const int64_t wbytes = (int64_t)a->N * a->ldb * esz;
-        p.warm_b = (wbytes <= ((int64_t)2 << 20) && (a->ldb * esz) % 128 == 0 && (((uintptr_t)a->B) & 127) == 0) ? (int)((wbytes + (2 << 20) - 1) >> 21) : 0;
-    }
+    p.tiles_n = pl.tiles_n; p.n_tiles = pl.n_tiles;
+    p.vec_ok = pl.vec_ok; p.mask_vec_ok = pl.mask_vec_ok;
     p.stamps = g_stamp_buffer;
-    const int tiles_m = (a->M + BM - 1) / BM;
-    p.tiles_n = (a->N + BN - 1) / BN;
-    p.n_tiles = tiles_m * p.tiles_n;
-    dim3 grid(p.n_tiles), block(256);
+    p.scale_a = a->scale_a; p.scale_b = a->scale_b;
+    p.warm_b = pl.warm_b;
+    p.q8 = (unsigned char*)a->fp8_out; p.ldq8 = a->ld_fp8_out; p.q8_only = pl.q8_only;
+    p.q_parts2 = a->fp8_out_parts2; p.q_step = a->fp8_out_step; p.q_scale_inv = a->fp8_out_scale_inv;
     hipStream_t s = (hipStream_t)stream;
-    if (fp8 || x3_ws || (a->in_dtype == DG_BF16 && a->K % 64 == 0 && a->K >= 128)) {
-        dim3 pgrid(p.n_tiles < dg_num_cus() ? p.n_tiles : dg_num_cus());
-        // the mask bits of the sign-bit dX form are prefetched ahead of the epilogue
-        const bool pf = a->sign_bits != nullptr && p.vec_ok && (!a->bias || dg_aligned16(a->bias)) &&
-                        (a->ldc * (a->out_dtype == DG_BF16 ? 2 : 4)) % 16 == 0 && dg_aligned16(a->C);
-        const bool wide = dg_nt_wide(a->N);                       // 128 x 192 tiles
-        if (wide) {
-            p.tiles_n = a->N / 192;
-            p.n_tiles = tiles_m * p.tiles_n;
-            pgrid = dim3(p.n_tiles < dg_num_cus() ? p.n_tiles : dg_num_cus());
-        }
-        p.cs_accum = dg_nt_cs_accum(p.n_tiles, p.tiles_n) ? 1 : 0;
-        const dim3 wsb(512 + 64 * WS_NLOAD);
-        // epilogue specialisation (see the kernel's EPI parameter); anything else, and every stamped run, takes the generic form
-        int epi = 0;
-        {
-            const bool plain = !a->bias && !a->relu && !a->relu_mask && !p.drop && !a->residual && !a->sign_bits && !a->sign_bits_out;
-            if (!p.stamps) {
-                if (plain) epi = 1;
-                else if (a->out_dtype == DG_BF16 && a->bias && a->relu && a->sign_bits_out && !a->relu_mask && !p.drop && !a->residual && !a->sign_bits) epi = a->fp8_out ? 8 : 2;
-                else if (a->bias && p.drop && a->residual && !a->relu && !a->relu_mask && !a->sign_bits && !a->sign_bits_out) epi = 3;
-                else if (a->out_dtype == DG_BF16 && pf && !a->bias && !a->relu && !a->relu_mask && !p.drop && !a->residual && !a->sign_bits_out) epi = a->colsum_part ? (a->fp8_out ? 9 : 6) : 4;
-                else if (a->bias && !a->relu && !a->relu_mask && !p.drop && !a->residual && !a->sign_bits && !a->sign_bits_out) epi = 5;
-                else if (a->bias && !p.drop && a->residual && !a->relu && !a->relu_mask && !a->sign_bits && !a->sign_bits_out) epi = 7;
-            }
-        }
-        if (x3) {
-            const int rc = dg_gemm_nt_x3_launch(p, wide, epi, pgrid, s);
-            if (rc != DG_OK) return rc;
-            DG_LAUNCH_CHECK();
-            return DG_OK;
-        }
-        if (fp8) {
-            const int rc = dg_gemm_nt_fp8_launch(p, a->in_dtype == DG_FP8_E5M2 ? 2 : 1, a->out_dtype, pf, wide, epi, pgrid, s);
-            if (rc != DG_OK) return rc;
-            DG_LAUNCH_CHECK();
-            return DG_OK;
-        }
-#define DG_WS_LAUNCH(NJ_) do { \
-            if (epi == 1 && a->out_dtype == DG_BF16) hipLaunchKernelGGL((gemm_nt_ws_kernel<bf16_t, false, NJ_, 1>), pgrid, wsb, 0, s, p); \
-            else if (epi == 1) hipLaunchKernelGGL((gemm_nt_ws_kernel<float, false, NJ_, 1>), pgrid, wsb, 0, s, p); \
-            else if (epi == 2) hipLaunchKernelGGL((gemm_nt_ws_kernel<bf16_t, false, NJ_, 2>), pgrid, wsb, 0, s, p); \
-            else if (epi == 3 && a->out_dtype == DG_BF16) hipLaunchKernelGGL((gemm_nt_ws_kernel<bf16_t, false, NJ_, 3>), pgrid, wsb, 0, s, p); \
-            else if (epi == 3) hipLaunchKernelGGL((gemm_nt_ws_kernel<float, false, NJ_, 3>), pgrid, wsb, 0, s, p); \
-            else if (epi == 4) hipLaunchKernelGGL((gemm_nt_ws_kernel<bf16_t, true, NJ_, 4>), pgrid, wsb, 0, s, p); \
-            else if (epi == 5 && a->out_dtype == DG_BF16) hipLaunchKernelGGL((gemm_nt_ws_kernel<bf16_t, false, NJ_, 5>), pgrid, wsb, 0, s, p); \
-            else if (epi == 5) hipLaunchKernelGGL((gemm_nt_ws_kernel<float, false, NJ_, 5>), pgrid, wsb, 0, s, p); \
-            else if (epi == 6) hipLaunchKernelGGL((gemm_nt_ws_kernel<bf16_t, true, NJ_, 6>), pgrid, wsb, 0, s, p); \
-            else if (epi == 7 && a->out_dtype == DG_BF16) hipLaunchKernelGGL((gemm_nt_ws_kernel<bf16_t, false, NJ_, 7>), pgrid, wsb, 0, s, p); \
-            else if (epi == 7) hipLaunchKernelGGL((gemm_nt_ws_kernel<float, false, NJ_, 7>), pgrid, wsb, 0, s, p); \
-            else if (pf && a->out_dtype == DG_BF16) hipLaunchKernelGGL((gemm_nt_ws_kernel<bf16_t, true, NJ_, 0>), pgrid, wsb, 0, s, p); \
-            else if (pf) hipLaunchKernelGGL((gemm_nt_ws_kernel<float, true, NJ_, 0>), pgrid, wsb, 0, s, p); \
-            else if (a->out_dtype == DG_BF16) hipLaunchKernelGGL((gemm_nt_ws_kernel<bf16_t, false, NJ_, 0>), pgrid, wsb, 0, s, p); \
-            else hipLaunchKernelGGL((gemm_nt_ws_kernel<float, false, NJ_, 0>), pgrid, wsb, 0, s, p); } while (0)
-        if (wide) DG_WS_LAUNCH(6); else DG_WS_LAUNCH(4);
-#undef DG_WS_LAUNCH
-    } else if (a->in_dtype == DG_BF16 && a->out_dtype == DG_BF16)
-        hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, bf16_t>), grid, block, 0, s, p);
-    else if (a->in_dtype == DG_BF16)
-        hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, float>), grid, block, 0, s, p);
-    else if (x3)
-        hipLaunchKernelGGL(gemm_nt_x3_kernel, grid, block, 0, s, p);
-    else
-        hipLaunchKernelGGL((gemm_nt_kernel<float, float>), grid, block, 0, s, p);
+    if (pl.family == NT_F_WS) nt_ws_instance(pl.inst, &p, pl.grid, s);
+    else hipLaunchKernelGGL(nt_staged[pl.staged].kernel, dim3(pl.grid), dim3(pl.block), 0, s, p);
     DG_LAUNCH_CHECK();
+    return DG_OK;
+}
+
+// diagnostic only (tests/nt_cases.py): the plan of dg_gemm_nt(a) with `ncu` compute units (0: the device's, 256 without one) and
+// a stamp buffer set or not.  Pure host code that never launches, not part of the public header.  out24: rc, family, the
+// instance's out_dtype, PF, NJ, EPI, F8, grid, block, K, tiles_n, n_tiles, cs_accum, vec_ok, mask_vec_ok, warm_b, drop, q8_only,
+// tile width, sign bits / column sums offered, colsum_rows, fp8 copy offered, sign_bits_bytes.
+extern "C" int dg_debug_nt_plan(const dg_gemm_nt_args* a, int ncu, int stamps, int64_t* out24, const char** kernel_name) {
+    if (!a || ncu < 0 || !out24) return DG_ERR_ARG;
+    const NtPlan pl = nt_plan(*a, ncu > 0 ? ncu : dg_num_cus(), stamps != 0);
+    const int64_t v[24] = {pl.rc, pl.family, pl.inst.out_dtype, pl.inst.pf, pl.inst.nj, pl.inst.epi, pl.inst.f8, pl.grid, pl.block,
+                           pl.K, pl.tiles_n, pl.n_tiles, pl.cs_accum, pl.vec_ok, pl.mask_vec_ok, pl.warm_b, pl.drop, pl.q8_only,
+                           pl.bn, pl.sign_ok, pl.colsum_ok, pl.colsum_rows, pl.fp8_out_ok, pl.sign_bits_bytes};
+    for (int i = 0; i < 24; ++i) out24[i] = v[i];
+    if (kernel_name) *kernel_name = pl.name ? pl.name : "";
     return DG_OK;
 }
 

@@ -656,3 +656,40 @@ __global__ __launch_bounds__(768) void gemm_nt_ws_kernel(NtParams p) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The instances of gemm_nt_ws_kernel that exist, each at both tile widths: ONE list, X(TO, PF, NJ, EPI, F8).  A translation unit
+// expands the lists of its own F8 (gemm.hip 0, gemm_fp8.hip 1 and 2, gemm_x3.hip 3) with NT_WS_ROW into a table whose rows take
+// their name and their kernel address from the same expansion, and looks instances up in it (dg_nt_ws_*): nt_plan (gemm.hip)
+// asks which instance exists, dg_gemm_nt launches the one the plan names.
+#define NT_WS_BOTH(X, TO, PF, EPI, F8) X(TO, PF, 4, EPI, F8) X(TO, PF, 6, EPI, F8)
+#define NT_WS_INSTANCES_BF16(X) \
+    NT_WS_BOTH(X, bf16_t, false, 0, 0) NT_WS_BOTH(X, float, false, 0, 0) NT_WS_BOTH(X, bf16_t, true, 0, 0) NT_WS_BOTH(X, float, true, 0, 0) \
+    NT_WS_BOTH(X, bf16_t, false, 1, 0) NT_WS_BOTH(X, float, false, 1, 0) NT_WS_BOTH(X, bf16_t, false, 2, 0) \
+    NT_WS_BOTH(X, bf16_t, false, 3, 0) NT_WS_BOTH(X, float, false, 3, 0) NT_WS_BOTH(X, bf16_t, true, 4, 0) \
+    NT_WS_BOTH(X, bf16_t, false, 5, 0) NT_WS_BOTH(X, float, false, 5, 0) NT_WS_BOTH(X, bf16_t, true, 6, 0) \
+    NT_WS_BOTH(X, bf16_t, false, 7, 0) NT_WS_BOTH(X, float, false, 7, 0)
+#define NT_WS_INSTANCES_E4M3(X) \
+    NT_WS_BOTH(X, bf16_t, false, 0, 1) NT_WS_BOTH(X, float, false, 0, 1) NT_WS_BOTH(X, bf16_t, false, 1, 1) \
+    NT_WS_BOTH(X, bf16_t, false, 2, 1) NT_WS_BOTH(X, bf16_t, false, 3, 1) NT_WS_BOTH(X, float, false, 3, 1) \
+    NT_WS_BOTH(X, bf16_t, false, 5, 1) NT_WS_BOTH(X, bf16_t, false, 7, 1) NT_WS_BOTH(X, float, false, 7, 1) \
+    NT_WS_BOTH(X, bf16_t, false, 8, 1)
+#define NT_WS_INSTANCES_E5M2(X) \
+    NT_WS_BOTH(X, bf16_t, false, 0, 2) NT_WS_BOTH(X, float, false, 0, 2) NT_WS_BOTH(X, bf16_t, true, 0, 2) \
+    NT_WS_BOTH(X, bf16_t, false, 1, 2) NT_WS_BOTH(X, bf16_t, true, 4, 2) NT_WS_BOTH(X, bf16_t, true, 6, 2) \
+    NT_WS_BOTH(X, bf16_t, true, 9, 2)
+#define NT_WS_INSTANCES_X3(X) \
+    NT_WS_BOTH(X, float, false, 0, 3) NT_WS_BOTH(X, float, false, 1, 3) NT_WS_BOTH(X, float, false, 3, 3) \
+    NT_WS_BOTH(X, float, false, 5, 3) NT_WS_BOTH(X, float, false, 7, 3)
+
+struct NtWsKey { int out_dtype, pf, nj, epi, f8; };            // out_dtype: DG_BF16 / DG_F32 for TO = bf16_t / float
+inline bool operator==(const NtWsKey& a, const NtWsKey& b) {
+    return a.out_dtype == b.out_dtype && a.pf == b.pf && a.nj == b.nj && a.epi == b.epi && a.f8 == b.f8;
+}
+struct NtWsInstance { NtWsKey key; const char* name; void (*kernel)(NtParams); };
+#define NT_WS_ROW(TO, PF, NJ, EPI, F8) \
+    {{sizeof(TO) == 2 ? DG_BF16 : DG_F32, PF, NJ, EPI, F8}, "gemm_nt_ws_kernel<" #TO "," #PF "," #NJ "," #EPI "," #F8 ">", gemm_nt_ws_kernel<TO, PF, NJ, EPI, F8>},
+#define NT_WS_BLOCK (512 + 64 * WS_NLOAD)
+// One per translation unit: the name of instance k in the unit's table, nullptr when there is none; with p, the instance is launched.
+const char* dg_nt_ws_bf16(const NtWsKey& k, const NtParams* p, int grid, hipStream_t s);   // gemm.hip
+const char* dg_nt_ws_fp8(const NtWsKey& k, const NtParams* p, int grid, hipStream_t s);    // gemm_fp8.hip
+const char* dg_nt_ws_x3(const NtWsKey& k, const NtParams* p, int grid, hipStream_t s);     // gemm_x3.hip

@@ -6,19 +6,12 @@
 // A translation unit of its own so that its kernel variants compile beside gemm.hip's.
 #include "gemm_nt_ws.h"
 
-// Returns 0 when a variant was launched.
-int dg_gemm_nt_x3_launch(const NtParams& p, bool wide, int epi, dim3 pgrid, hipStream_t s) {
-    const dim3 wsb(512 + 64 * WS_NLOAD);
-#define L(NJ_, EPI_) hipLaunchKernelGGL((gemm_nt_ws_kernel<float, false, NJ_, EPI_, 3>), pgrid, wsb, 0, s, p)
-#define X3(NJ_) do { \
-        if (epi == 1) L(NJ_, 1); \
-        else if (epi == 3) L(NJ_, 3); \
-        else if (epi == 5) L(NJ_, 5); \
-        else if (epi == 7) L(NJ_, 7); \
-        else if (epi == 0) L(NJ_, 0); \
-        else return DG_ERR_ARG; } while (0)
-    if (wide) X3(6); else X3(4);
-#undef L
-#undef X3
-    return DG_OK;
+const char* dg_nt_ws_x3(const NtWsKey& k, const NtParams* p, int grid, hipStream_t s) {
+    static const NtWsInstance rows[] = {NT_WS_INSTANCES_X3(NT_WS_ROW)};
+    for (const NtWsInstance& r : rows) {
+        if (!(r.key == k)) continue;
+        if (p) hipLaunchKernelGGL(r.kernel, dim3(grid), dim3(NT_WS_BLOCK), 0, s, *p);
+        return r.name;
+    }
+    return nullptr;
 }
