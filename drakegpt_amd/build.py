@@ -63,8 +63,8 @@ def build(force: bool = False, save_temps: bool = False, verbose: bool = True) -
     os.makedirs(OBJDIR, exist_ok=True)
     hipcc = _hipcc()
     # (attention_mfma.hip: also the text of attention_mfma_doc.hip, which compiles its template kernels a second time)
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_nt_ws.h"), os.path.join(PKG, "..", "include", "drakegpt_hip.h"),
-               os.path.join(CSRC, "attention_mfma.hip")]
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_nt_ws.h"), os.path.join(CSRC, "attention_plan.h"),
+               os.path.join(PKG, "..", "include", "drakegpt_hip.h"), os.path.join(CSRC, "attention_mfma.hip")]
     hdr_digest = _digest(headers)
     flags = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17",
              "-Wno-unused-result", "-I", os.path.join(PKG, "..", "include")]

@@ -17,7 +17,7 @@
 //  * dropout keep = hash(seed, step, site, ((b*NH+h)*T+i)*T+j), regenerated in backward.
 // Scores per (b,h): T*(T+1)/2; FLOP per score element: fwd 4*64, bwd 10*64 (+2 recomputed products
 // because dQ and dK/dV are separate deterministic passes: no atomics, bitwise reproducible).
-#include "common.h"
+#include "attention_plan.h"
 #include <type_traits>
 
 #define HD 64
@@ -809,18 +809,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_mfma_kernel(AttnP p) {
 
 // =============================================================================================
 // Everything above: the template kernels, also compiled into attention_mfma_doc.hip (their DOC instances and the launches of
-// those).  Everything below: the non-template kernels and the host side of this file alone.
+// those).  The instances that exist, X(template arguments but DOC): both units expand these lists into the rows of their tables
+// (attention_plan.h), so a row's name and its kernel address come out of one expansion.  The recompute form of the dQ pass
+// (TILES = false) has one instance, without DOC; attn_plan picks among them.
+#define ATTN_FWD_INSTANCES(X) X(false, false, false) X(true, false, false) X(true, true, false) X(false, false, true) X(true, true, true)
+#define ATTN_DQ_BOTH(X, KB, F8) X(true, KB, F8, false) X(true, KB, F8, true)
+#define ATTN_DQ_TILE_INSTANCES(X) ATTN_DQ_BOTH(X, false, false) ATTN_DQ_BOTH(X, true, false) ATTN_DQ_BOTH(X, false, true) ATTN_DQ_BOTH(X, true, true)
+#define ATTN_DQ_LDS(SH) ((SH) ? WG_LDS_DQS : 4 * WAVE_LDS_DQ)
+// Everything below: the non-template kernels and the host side of this file alone.
 #ifndef DG_ATTN_MFMA_DOC_TU
-int dg_attn_fwd_mfma_doc(const AttnP& p, bool f8, dim3 grid, hipStream_t s);
-void dg_attn_dq_mfma_doc(const AttnP& p, bool kb, bool f8, dim3 grid, hipStream_t s);
-
-bool dg_attn_mfma_supported(int B, int T, int NH, int H) {
-    // (T even: a lane's adjacent keys then form the element pairs that share a dropout hash)
-    // (row offsets inside a batch slab are 24 x 24 -> 32-bit products: row_off)
-    return H == HD && B > 0 && T > 0 && T % 2 == 0 && NH > 0 && (int64_t)B * NH * T * T < ((int64_t)1 << 32) &&
-           T < (1 << 24) && 3 * (int64_t)NH * HD < (1 << 24) && (int64_t)T * 3 * NH * HD < ((int64_t)1 << 32);
-}
-
 
 // =============================================================================================
 // dK/dV from the tiles the dQ pass wrote: wave = 32 keys; per query tile: dV += Pd^T dO, dK += dS^T Q.  No scores, no exp,
@@ -993,124 +990,67 @@ static unsigned long long* g_attn_stamps = nullptr;
 // diagnostic only (tools/attn_dq_stamps.py): not part of the public header
 extern "C" void dg_debug_set_attn_stamps(void* q) { g_attn_stamps = (unsigned long long*)q; }
 
-static void fill(AttnP& p, int B, int T, int NH, float scale, float dp, const uint32_t* rng, uint32_t site) {
+// the six dK/dV kernels, X(kernel, key, LDS bytes): from the dQ pass's tiles (per wave, or with Q / dO tiles shared by a workgroup;
+// each also with the e5m2 copy) or, without tiles, recomputed with and without dropout
+#define ATTN_DKV_INSTANCES(X) \
+    X(attn_bwd_dkv_mfma_kernel<false>, ATTN_DKV_KEY(0, 0, 0), 4 * WAVE_LDS_DKV) X(attn_bwd_dkv_mfma_kernel<true>, ATTN_DKV_KEY(0, 0, 1), 4 * WAVE_LDS_DKV) \
+    X(attn_bwd_dkv_tiles_kernel, ATTN_DKV_KEY(1, 0, 0), 4 * WAVE_LDS_DKVT) X(attn_bwd_dkv_tiles_f8_kernel, ATTN_DKV_KEY(1, 0, 1), 4 * WAVE_LDS_DKVT) \
+    X(attn_bwd_dkv_tiles_shared_kernel, ATTN_DKV_KEY(1, 1, 0), WG_LDS_DKVS) X(attn_bwd_dkv_tiles_shared_f8_kernel, ATTN_DKV_KEY(1, 1, 1), WG_LDS_DKVS)
+#define ATTN_FWD_ROW(DROP, KEEP, F8) \
+    {ATTN_FWD_KEY(DROP, KEEP, F8, false), "attn_fwd_mfma_kernel<" #DROP "," #KEEP "," #F8 ">", attn_fwd_mfma_kernel<DROP, KEEP, F8>, 4 * WAVE_LDS_FWD},
+#define ATTN_DQ_ROW(TILES, KB, F8, SH) \
+    {ATTN_DQ_KEY(TILES, KB, F8, SH, false), "attn_bwd_dq_mfma_kernel<" #TILES "," #KB "," #F8 "," #SH ">", attn_bwd_dq_mfma_kernel<TILES, KB, F8, SH>, ATTN_DQ_LDS(SH)},
+#define ATTN_DKV_ROW(K, KEY, LDS) {KEY, #K, K, LDS},
+
+const AttnRow* dg_attn_mfma_fwd(int key, const AttnP* p, unsigned grid, hipStream_t s) {
+    static const AttnRow rows[] = {ATTN_FWD_INSTANCES(ATTN_FWD_ROW)};
+    const AttnRow* r = attn_find(rows, key);
+    if (r && p) hipLaunchKernelGGL(r->kernel, dim3(grid), dim3(256), r->lds, s, *p);
+    return r;
+}
+const AttnRow* dg_attn_mfma_dq(int key, const AttnP* p, unsigned grid, hipStream_t s) {
+    static const AttnRow rows[] = {ATTN_DQ_ROW(false, false, false, false) ATTN_DQ_TILE_INSTANCES(ATTN_DQ_ROW)};
+    const AttnRow* r = attn_find(rows, key);
+    if (r && p) hipLaunchKernelGGL(r->kernel, dim3(grid), dim3(256), r->lds, s, *p);
+    return r;
+}
+const AttnRow* dg_attn_mfma_dkv(int key, const AttnP* p, unsigned grid, hipStream_t s) {
+    static const AttnRow rows[] = {ATTN_DKV_INSTANCES(ATTN_DKV_ROW)};
+    const AttnRow* r = attn_find(rows, key);
+    if (r && p) hipLaunchKernelGGL(r->kernel, dim3(grid), dim3(256), r->lds, s, *p);
+    return r;
+}
+
+// the launches of a planned call on the MFMA kernels: the caller's pointers and the plan's fields into AttnP, one launch per pass
+int dg_attn_mfma_launch(const AttnPlan& pl, const AttnCall& c, hipStream_t s) {
+    AttnP p = {};
     p.stamps = g_attn_stamps;
-    p.B = B; p.T = T; p.NH = NH; p.nblk = (T + TILE - 1) / TILE;
-    p.n_items = (int64_t)B * NH * p.nblk;
-    p.scale = scale;
-    p.drop = (dp > 0.f && rng) ? 1 : 0;
-    p.inv_keep = 1.f / (1.f - dp);
-    p.thr = dg_drop_threshold(dp);
-    p.rng = rng; p.site = site;
-    static const int ncu = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        return n;
-    }();
-    p.balance = p.nblk % 4 == 0 ? 1 : 0;
-    // heavy-first order when the launch is more than one residency (three 256-thread workgroups per CU)
-    // ... and from 16 blocks on (T >= 512) at any size: with the K / V and Q / dO tiles shared by a workgroup's waves (round 3) the
-    // consecutive blocks of this order beat the equal-cost pairs at one residency too (GPT-2-small B = 8: 11.75 / 11.65 -> 11.66 /
-    // 11.56 ms; no difference at the headline shape's 8 blocks)
-    if (p.balance && ((int64_t)B * NH * (p.nblk / 4) > (int64_t)3 * ncu * 11 / 10 || p.nblk >= 16)) p.balance = 2;
-    p.rot_div = ncu;
-}
-
-int64_t dg_attn_mfma_keep_bytes(int B, int T, int NH) {
-    const int64_t nblk = (T + TILE - 1) / TILE;
-    return (int64_t)B * NH * (nblk * (nblk + 1) / 2) * 128;
-}
-
-static int attn_f8_fill(AttnP& p, const dg_attn_fp8_out* f8) {
-    if (!f8->q8 || !f8->hist3 || !f8->step_state || !f8->scale_inv || !dg_aligned16(f8->q8) || !dg_aligned16(f8->hist3)) return DG_ERR_ARG;
-    p.q8 = (uint8_t*)f8->q8; p.hist3 = f8->hist3; p.step = f8->step_state; p.sinv = f8->scale_inv; p.only8 = f8->only8;
-    return DG_OK;
-}
-
-int dg_attn_fwd_mfma(const void* qkv, void* out, float* lse, int B, int T, int NH, int H, float scale, float dp,
-                     const uint32_t* rng, uint32_t site, void* keep, const dg_attn_fp8_out* f8, const int32_t* starts, hipStream_t s) {
-    if (dp < 0.f || dp >= 1.f || !dg_aligned16(qkv) || !dg_aligned16(out) || (keep && !dg_aligned16(keep))) return DG_ERR_ARG;
-    AttnP p = {};
-    fill(p, B, T, NH, scale, dp, rng, site);
-    p.qkv = (const bf16_t*)qkv; p.out_w = (bf16_t*)out; p.lse = lse;
-    p.keep = (unsigned long long*)keep;
-    p.starts = starts;
-    dim3 grid((unsigned)((p.n_items + 3) / 4)), block(256);
-    if (f8) {
-        if (p.drop && !p.keep) return DG_ERR_ARG;
-        if (int rc = attn_f8_fill(p, f8)) return rc;
-        if (p.only8) return DG_ERR_ARG;                   // (the dQ pass reads the bf16 output: delta = rowsum(dO o))
+    p.B = c.B; p.T = c.T; p.NH = c.NH; p.nblk = pl.nblk; p.n_items = pl.n_items;
+    p.scale = c.scale;
+    p.drop = pl.drop; p.inv_keep = pl.inv_keep; p.thr = pl.thr; p.rng = c.rng_state; p.site = c.site;
+    p.balance = pl.balance; p.rot_div = pl.rot_div;
+    p.qkv = (const bf16_t*)c.qkv;
+    p.starts = c.starts;
+    if (pl.keep) p.keep = (unsigned long long*)c.keep_bits;
+    if (c.bwd) {
+        p.out = (const bf16_t*)c.out; p.dout = (const bf16_t*)c.dout; p.dqkv = (bf16_t*)c.dqkv;
+        p.lse_r = c.lse; p.delta = (float*)c.workspace; p.delta_r = p.delta;
+        if (pl.tiles) p.tiles = (char*)c.workspace + pl.delta_bytes;
+    } else {
+        p.out_w = (bf16_t*)c.out; p.lse = (float*)c.lse;
     }
-    if (starts) return dg_attn_fwd_mfma_doc(p, f8 != nullptr, grid, s);          // the document-mask instances (attention_mfma_doc.hip)
-    if (f8) {
-        if (p.drop) hipLaunchKernelGGL((attn_fwd_mfma_kernel<true, true, true>), grid, block, 4 * WAVE_LDS_FWD, s, p);
-        else hipLaunchKernelGGL((attn_fwd_mfma_kernel<false, false, true>), grid, block, 4 * WAVE_LDS_FWD, s, p);
+    if (c.fp8) {     // forward: out also as e4m3; backward: dqkv also as e5m2 (dQ from the dQ pass, dK / dV from the tile pass, one history, one scale)
+        p.q8 = (uint8_t*)c.fp8->q8; p.hist3 = c.fp8->hist3; p.step = c.fp8->step_state; p.only8 = c.fp8->only8;
+    }
+    for (int i = 0; i < pl.n_launch; ++i) {
+        const AttnLaunch& l = pl.launch[i];
+        AttnP q = p;
+        // no dropout: threshold 0 (keep all), scale 1: bit-identical, faster than a dropout-free dQ build (36 vs 48 us per layer); key read from qkv (>= 384 B)
+        if (l.pass == ATTN_DQ && pl.dq_no_drop) { q.thr = 0u; q.inv_keep = 1.f; q.rng = (const uint32_t*)c.qkv; q.site = 0; }
+        if (l.sinv) q.sinv = c.fp8->scale_inv;
+        attn_row(l.pass, l.key, &q, pl.grid, s);
         DG_LAUNCH_CHECK();
-        return DG_OK;
     }
-    if (p.drop && p.keep) hipLaunchKernelGGL((attn_fwd_mfma_kernel<true, true>), grid, block, 4 * WAVE_LDS_FWD, s, p);
-    else if (p.drop) hipLaunchKernelGGL((attn_fwd_mfma_kernel<true, false>), grid, block, 4 * WAVE_LDS_FWD, s, p);
-    else hipLaunchKernelGGL((attn_fwd_mfma_kernel<false, false>), grid, block, 4 * WAVE_LDS_FWD, s, p);
-    DG_LAUNCH_CHECK();
-    return DG_OK;
-}
-
-// bytes of the optional P|dS tile scratch behind the [B,NH,T] delta floats (0 = shape not covered)
-int64_t dg_attn_bwd_mfma_tile_bytes(int B, int T, int NH) {
-    const int64_t nblk = (T + TILE - 1) / TILE;
-    return (int64_t)B * NH * (nblk * (nblk + 1) / 2) * 4096;
-}
-
-// The dQ pass with shared K / V tiles: the heavy-first order only, where a workgroup's four query blocks are CONSECUTIVE (the shared
-// loop runs to the last of them: three idle tiles at most).  In the equal-cost order (blocks j and nblk - 1 - j in one workgroup) the
-// short waves would sit at the barriers of the long ones: measured slower at the headline shape (2.326 / 2.336 -> 2.344 / 2.342 ms) and
-// no better at GPT-2-small B = 8.  The recompute form (no tiles) has the per-wave form only.
-template <bool TILES, bool KB, bool F8>
-static void attn_dq_launch(const AttnP& p, dim3 grid, hipStream_t s) {
-    if (TILES && p.balance == 2) hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<true, KB, F8, true>), grid, dim3(256), WG_LDS_DQS, s, p);
-    else hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<TILES, KB, F8>), grid, dim3(256), 4 * WAVE_LDS_DQ, s, p);
-}
-
-int dg_attn_bwd_mfma(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* delta, void* tiles,
-                     int B, int T, int NH, int H, float scale, float dp, const uint32_t* rng, uint32_t site, const void* keep,
-                     const dg_attn_fp8_out* f8, const int32_t* starts, hipStream_t s) {
-    if (dp < 0.f || dp >= 1.f || !dg_aligned16(qkv) || !dg_aligned16(out) || !dg_aligned16(dout) || !dg_aligned16(dqkv)) return DG_ERR_ARG;
-    if (starts && !tiles) return DG_ERR_ARG;              // (the recompute form has no document variant)
-    if (keep && !dg_aligned16(keep)) return DG_ERR_ALIGN;
-    if (tiles && !dg_aligned16(tiles)) return DG_ERR_ALIGN;
-    AttnP p = {};
-    fill(p, B, T, NH, scale, dp, rng, site);
-    p.qkv = (const bf16_t*)qkv; p.out = (const bf16_t*)out; p.dout = (const bf16_t*)dout; p.dqkv = (bf16_t*)dqkv;
-    p.lse_r = lse; p.delta = delta; p.delta_r = delta;
-    p.tiles = (char*)tiles;
-    p.starts = starts;
-    // keep masks: the tile form only (the recompute form's dQ loop would spill 16 registers with them; it hashes instead)
-    p.keep = (keep && p.drop && tiles) ? (unsigned long long*)keep : nullptr;
-    if (f8) {
-        // dqkv also as e5m2: dQ from the dQ pass, dK / dV from the tile pass, one history, one scale
-        if (!p.tiles) return DG_ERR_ARG;
-        if (int rc = attn_f8_fill(p, f8)) return rc;
-    }
-    dim3 grid((unsigned)((p.n_items + 3) / 4)), block(256);
-    // no dropout: threshold 0 (keep all), scale 1: bit-identical, faster than a dropout-free dQ build (36 vs 48 us per layer); key read from qkv (>= 384 B)
-    AttnP q = p;
-    if (!p.drop) { q.thr = 0u; q.inv_keep = 1.f; q.rng = (const uint32_t*)qkv; q.site = 0; }
-    if (starts) dg_attn_dq_mfma_doc(q, p.keep != nullptr, f8 != nullptr, grid, s);   // the document-mask instances (attention_mfma_doc.hip)
-    else if (!p.tiles) attn_dq_launch<false, false, false>(q, grid, s);
-    else if (!f8) (p.keep ? attn_dq_launch<true, true, false> : attn_dq_launch<true, false, false>)(q, grid, s);
-    else (p.keep ? attn_dq_launch<true, true, true> : attn_dq_launch<true, false, true>)(q, grid, s);
-    DG_LAUNCH_CHECK();
-    p.sinv = nullptr;                                     // (f8: written by the dQ pass)
-    // the tile pass with Q / dO tiles shared by a workgroup's waves: the balanced block orders (a workgroup = four key blocks of ONE (batch, head))
-    if (p.tiles && p.balance) {
-        if (f8) hipLaunchKernelGGL(attn_bwd_dkv_tiles_shared_f8_kernel, grid, block, WG_LDS_DKVS, s, p);
-        else hipLaunchKernelGGL(attn_bwd_dkv_tiles_shared_kernel, grid, block, WG_LDS_DKVS, s, p);
-    } else if (p.tiles) {
-        if (f8) hipLaunchKernelGGL(attn_bwd_dkv_tiles_f8_kernel, grid, block, 4 * WAVE_LDS_DKVT, s, p);
-        else hipLaunchKernelGGL(attn_bwd_dkv_tiles_kernel, grid, block, 4 * WAVE_LDS_DKVT, s, p);
-    } else if (p.drop) hipLaunchKernelGGL(attn_bwd_dkv_mfma_kernel<true>, grid, block, 4 * WAVE_LDS_DKV, s, p);
-    else hipLaunchKernelGGL(attn_bwd_dkv_mfma_kernel<false>, grid, block, 4 * WAVE_LDS_DKV, s, p);
-    DG_LAUNCH_CHECK();
     return DG_OK;
 }
 #endif  // DG_ATTN_MFMA_DOC_TU

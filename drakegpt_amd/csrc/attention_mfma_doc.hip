@@ -1,30 +1,25 @@
 // The document-mask (DOC) instances of the bf16 MFMA attention kernels and their launches: attn_fwd_mfma_kernel<.., DOC = true> and
 // attn_bwd_dq_mfma_kernel<TILES = true, .., DOC = true>.  The kernels are the templates of attention_mfma.hip, compiled here a
-// second time for these instances only; that file's host dispatch (dg_attn_fwd_mfma, dg_attn_bwd_mfma) fills the launch parameters,
-// calls in here for the one launch that differs and launches the unchanged dK/dV tile kernels itself.
+// second time for these instances only; that file's dg_attn_mfma_launch fills the launch parameters, looks the one launch that
+// differs up in here (attn_row, attention_plan.h) and launches the unchanged dK/dV tile kernels itself.
 // ref: Head2.forward src/model_component.py:392-405 with the tril mask of :401 cut at the document starts (dg_doc_starts).
 #define DG_ATTN_MFMA_DOC_TU
 #include "attention_mfma.hip"
 
-int dg_attn_fwd_mfma_doc(const AttnP& p, bool f8, dim3 grid, hipStream_t s) {
-    const dim3 block(256);
-    if (f8 && p.drop) hipLaunchKernelGGL((attn_fwd_mfma_kernel<true, true, true, true>), grid, block, 4 * WAVE_LDS_FWD, s, p);
-    else if (f8) hipLaunchKernelGGL((attn_fwd_mfma_kernel<false, false, true, true>), grid, block, 4 * WAVE_LDS_FWD, s, p);
-    else if (p.drop && p.keep) hipLaunchKernelGGL((attn_fwd_mfma_kernel<true, true, false, true>), grid, block, 4 * WAVE_LDS_FWD, s, p);
-    else if (p.drop) hipLaunchKernelGGL((attn_fwd_mfma_kernel<true, false, false, true>), grid, block, 4 * WAVE_LDS_FWD, s, p);
-    else hipLaunchKernelGGL((attn_fwd_mfma_kernel<false, false, false, true>), grid, block, 4 * WAVE_LDS_FWD, s, p);
-    DG_LAUNCH_CHECK();
-    return DG_OK;
-}
+#define ATTN_DOC_FWD_ROW(DROP, KEEP, F8) \
+    {ATTN_FWD_KEY(DROP, KEEP, F8, true), "attn_fwd_mfma_kernel<" #DROP "," #KEEP "," #F8 ",true>", attn_fwd_mfma_kernel<DROP, KEEP, F8, true>, 4 * WAVE_LDS_FWD},
+#define ATTN_DOC_DQ_ROW(TILES, KB, F8, SH) \
+    {ATTN_DQ_KEY(TILES, KB, F8, SH, true), "attn_bwd_dq_mfma_kernel<" #TILES "," #KB "," #F8 "," #SH ",true>", attn_bwd_dq_mfma_kernel<TILES, KB, F8, SH, true>, ATTN_DQ_LDS(SH)},
 
-// the shared dQ form in the heavy-first order, the per-wave form elsewhere: the rule of attn_dq_launch
-template <bool KB, bool F8>
-static void dq_launch_doc(const AttnP& p, dim3 grid, hipStream_t s) {
-    if (p.balance == 2) hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<true, KB, F8, true, true>), grid, dim3(256), WG_LDS_DQS, s, p);
-    else hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<true, KB, F8, false, true>), grid, dim3(256), 4 * WAVE_LDS_DQ, s, p);
+const AttnRow* dg_attn_mfma_doc_fwd(int key, const AttnP* p, unsigned grid, hipStream_t s) {
+    static const AttnRow rows[] = {ATTN_FWD_INSTANCES(ATTN_DOC_FWD_ROW)};
+    const AttnRow* r = attn_find(rows, key);
+    if (r && p) hipLaunchKernelGGL(r->kernel, dim3(grid), dim3(256), r->lds, s, *p);
+    return r;
 }
-
-void dg_attn_dq_mfma_doc(const AttnP& p, bool kb, bool f8, dim3 grid, hipStream_t s) {
-    if (!f8) (kb ? dq_launch_doc<true, false> : dq_launch_doc<false, false>)(p, grid, s);
-    else (kb ? dq_launch_doc<true, true> : dq_launch_doc<false, true>)(p, grid, s);
+const AttnRow* dg_attn_mfma_doc_dq(int key, const AttnP* p, unsigned grid, hipStream_t s) {
+    static const AttnRow rows[] = {ATTN_DQ_TILE_INSTANCES(ATTN_DOC_DQ_ROW)};
+    const AttnRow* r = attn_find(rows, key);
+    if (r && p) hipLaunchKernelGGL(r->kernel, dim3(grid), dim3(256), r->lds, s, *p);
+    return r;
 }

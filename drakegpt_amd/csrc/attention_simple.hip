@@ -5,7 +5,7 @@
 //
 // ref: Head2.forward src/model_component.py:392-405:
 //   w = q k^T * scale;  w[j > i] = -inf;  w = softmax(w);  w = dropout(w);  out = w v
-#include "common.h"
+#include "attention_plan.h"
 
 #define AS_WAVES 4
 
@@ -322,66 +322,34 @@ extern "C" int dg_attn_decode_append(const void* qkv_row, void* qkv_cache, void*
 }
 
 // ---------------------------------------------------------------------------------------------
-static int check_common(int B, int T, int NH, int H, float p) {
-    if (B <= 0 || T <= 0 || NH <= 0 || H <= 0 || H > 256 || T > 4096) return DG_ERR_ARG;
-    if (p < 0.f || p >= 1.f) return DG_ERR_ARG;
-    if ((int64_t)B * NH * T * T >= ((int64_t)1 << 32)) return DG_ERR_ARG;   // 32-bit dropout element index
-    return DG_OK;
+// f(element type, document mask) of the call, both as types: one launch per pass below, its argument list written once
+template <typename F>
+static void attn_simple_dispatch(int dtype, bool doc, F f) {
+    if (dtype == DG_BF16) doc ? f((bf16_t*)nullptr, std::true_type()) : f((bf16_t*)nullptr, std::false_type());
+    else doc ? f((float*)nullptr, std::true_type()) : f((float*)nullptr, std::false_type());
 }
 
-int dg_attn_fwd_simple(const void* qkv, void* out, float* lse, int B, int T, int NH, int H, float scale,
-                       float p, const uint32_t* rng_state, uint32_t site, int dtype, const int32_t* starts, hipStream_t s) {
-    int rc = check_common(B, T, NH, H, p);
-    if (rc) return rc;
-    int64_t rows = (int64_t)B * NH * T;
-    dim3 grid((unsigned)((rows + AS_WAVES - 1) / AS_WAVES)), block(64 * AS_WAVES);
-    size_t sm = (size_t)AS_WAVES * (T + H) * sizeof(float);
-    int drop = (p > 0.f && rng_state) ? 1 : 0;
-    float ik = 1.f / (1.f - p);
-    uint32_t thr = dg_drop_threshold(p);
-    if (dtype != DG_BF16 && dtype != DG_F32) return DG_ERR_DTYPE;
-    if (starts) {
-        if (dtype == DG_BF16)
-            hipLaunchKernelGGL((attn_fwd_simple_kernel<bf16_t, true>), grid, block, sm, s, (const bf16_t*)qkv, (bf16_t*)out, lse, B, T, NH, H, scale, drop, ik, thr, rng_state, site, starts);
-        else
-            hipLaunchKernelGGL((attn_fwd_simple_kernel<float, true>), grid, block, sm, s, (const float*)qkv, (float*)out, lse, B, T, NH, H, scale, drop, ik, thr, rng_state, site, starts);
-    } else if (dtype == DG_BF16)
-        hipLaunchKernelGGL((attn_fwd_simple_kernel<bf16_t>), grid, block, sm, s, (const bf16_t*)qkv, (bf16_t*)out, lse, B, T, NH, H, scale, drop, ik, thr, rng_state, site, (const int32_t*)nullptr);
-    else
-        hipLaunchKernelGGL((attn_fwd_simple_kernel<float>), grid, block, sm, s, (const float*)qkv, (float*)out, lse, B, T, NH, H, scale, drop, ik, thr, rng_state, site, (const int32_t*)nullptr);
-    DG_LAUNCH_CHECK();
-    return DG_OK;
-}
-
-int dg_attn_bwd_simple(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
-                       float* delta, int B, int T, int NH, int H, float scale, float p,
-                       const uint32_t* rng_state, uint32_t site, int dtype, const int32_t* starts, hipStream_t s) {
-    int rc = check_common(B, T, NH, H, p);
-    if (rc) return rc;
-    int64_t rows = (int64_t)B * NH * T;
-    dim3 grid((unsigned)((rows + AS_WAVES - 1) / AS_WAVES)), block(64 * AS_WAVES);
-    size_t sm1 = (size_t)AS_WAVES * (T + 2 * H) * sizeof(float);
-    size_t sm2 = (size_t)AS_WAVES * (2 * T + 2 * H) * sizeof(float);
-    int drop = (p > 0.f && rng_state) ? 1 : 0;
-    float ik = 1.f / (1.f - p);
-    uint32_t thr = dg_drop_threshold(p);
-    if (dtype == DG_BF16 && starts) {
-        hipLaunchKernelGGL((attn_bwd_dq_simple_kernel<bf16_t, true>), grid, block, sm1, s, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse, (bf16_t*)dqkv, delta, B, T, NH, H, scale, drop, ik, thr, rng_state, site, starts);
+// the launches of a planned call (attn_plan, attention.hip) on the generic kernels
+int dg_attn_simple_launch(const AttnPlan& pl, const AttnCall& c, hipStream_t s) {
+    const dim3 grid(pl.grid), block(64 * AS_WAVES);
+    float* delta = (float*)c.workspace;
+    for (int i = 0; i < pl.n_launch; ++i) {
+        const AttnLaunch& l = pl.launch[i];
+        attn_simple_dispatch(c.dtype, c.starts != nullptr, [&](auto* t, auto doc) {
+            using T = std::remove_pointer_t<decltype(t)>;
+            constexpr bool DOC = decltype(doc)::value;
+            const T* qkv = (const T*)c.qkv;
+            if (l.pass == ATTN_FWD)
+                hipLaunchKernelGGL((attn_fwd_simple_kernel<T, DOC>), grid, block, l.lds, s, qkv, (T*)c.out, (float*)c.lse,
+                                   c.B, c.T, c.NH, c.H, c.scale, pl.drop, pl.inv_keep, pl.thr, c.rng_state, c.site, c.starts);
+            else if (l.pass == ATTN_DQ)
+                hipLaunchKernelGGL((attn_bwd_dq_simple_kernel<T, DOC>), grid, block, l.lds, s, qkv, (const T*)c.out, (const T*)c.dout, c.lse, (T*)c.dqkv, delta,
+                                   c.B, c.T, c.NH, c.H, c.scale, pl.drop, pl.inv_keep, pl.thr, c.rng_state, c.site, c.starts);
+            else
+                hipLaunchKernelGGL((attn_bwd_dkv_simple_kernel<T, DOC>), grid, block, l.lds, s, qkv, (const T*)c.dout, c.lse, delta, (T*)c.dqkv,
+                                   c.B, c.T, c.NH, c.H, c.scale, pl.drop, pl.inv_keep, pl.thr, c.rng_state, c.site, c.starts);
+        });
         DG_LAUNCH_CHECK();
-        hipLaunchKernelGGL((attn_bwd_dkv_simple_kernel<bf16_t, true>), grid, block, sm2, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, B, T, NH, H, scale, drop, ik, thr, rng_state, site, starts);
-    } else if (dtype == DG_F32 && starts) {
-        hipLaunchKernelGGL((attn_bwd_dq_simple_kernel<float, true>), grid, block, sm1, s, (const float*)qkv, (const float*)out, (const float*)dout, lse, (float*)dqkv, delta, B, T, NH, H, scale, drop, ik, thr, rng_state, site, starts);
-        DG_LAUNCH_CHECK();
-        hipLaunchKernelGGL((attn_bwd_dkv_simple_kernel<float, true>), grid, block, sm2, s, (const float*)qkv, (const float*)dout, lse, delta, (float*)dqkv, B, T, NH, H, scale, drop, ik, thr, rng_state, site, starts);
-    } else if (dtype == DG_BF16) {
-        hipLaunchKernelGGL((attn_bwd_dq_simple_kernel<bf16_t>), grid, block, sm1, s, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse, (bf16_t*)dqkv, delta, B, T, NH, H, scale, drop, ik, thr, rng_state, site, (const int32_t*)nullptr);
-        DG_LAUNCH_CHECK();
-        hipLaunchKernelGGL((attn_bwd_dkv_simple_kernel<bf16_t>), grid, block, sm2, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, B, T, NH, H, scale, drop, ik, thr, rng_state, site, (const int32_t*)nullptr);
-    } else if (dtype == DG_F32) {
-        hipLaunchKernelGGL((attn_bwd_dq_simple_kernel<float>), grid, block, sm1, s, (const float*)qkv, (const float*)out, (const float*)dout, lse, (float*)dqkv, delta, B, T, NH, H, scale, drop, ik, thr, rng_state, site, (const int32_t*)nullptr);
-        DG_LAUNCH_CHECK();
-        hipLaunchKernelGGL((attn_bwd_dkv_simple_kernel<float>), grid, block, sm2, s, (const float*)qkv, (const float*)dout, lse, delta, (float*)dqkv, B, T, NH, H, scale, drop, ik, thr, rng_state, site, (const int32_t*)nullptr);
-    } else return DG_ERR_DTYPE;
-    DG_LAUNCH_CHECK();
+    }
     return DG_OK;
 }

@@ -24,6 +24,19 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 static inline bool dg_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 
+// compute units of the current device, read once (256 where there is none to ask)
+inline int dg_num_cus() {
+    static const int v = [] {
+        int dev = 0, n = 256;
+        if (hipGetDevice(&dev) == hipSuccess) {
+            int x = 0;
+            if (hipDeviceGetAttribute(&x, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && x > 0) n = x;
+        }
+        return n;
+    }();
+    return v;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Optional kernel arguments: a kernel template that ends in a parameter pack `O... o` of distinct plain structs takes each option as
 // one more kernel argument; an instantiation without the option has neither the argument nor a trace of it in its symbol.

@@ -213,18 +213,6 @@ static unsigned long long* g_stamp_buffer = nullptr;
 // diagnostic only (tools/gemm_stamps.py): not part of the public header
 extern "C" void dg_debug_set_stamp_buffer(void* p) { g_stamp_buffer = (unsigned long long*)p; }
 
-static int dg_num_cus() {
-    static const int v = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) {
-            int x = 0;
-            if (hipDeviceGetAttribute(&x, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && x > 0) n = x;
-        }
-        return n;
-    }();
-    return v;
-}
-
 // ---------------------------------------------------------------------------------------------
 // NT launch plan.  Every decision of a dg_gemm_nt call, in one place: dg_gemm_nt launches what nt_plan returns, the query entries
 // read the same plan and dg_debug_nt_plan reports it.  Pure host code: the CU count and whether a stamp buffer is set come in.

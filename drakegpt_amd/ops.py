@@ -621,6 +621,17 @@ def _chk_doc_starts(doc_starts: Tensor, B: int, T: int) -> None:
         raise RuntimeError(f"doc_starts holds {doc_starts.numel()} values, expected B*T = {B * T}")
 
 
+def _attn_entry(base: str, args: tuple, fp8_arg, doc_starts: Optional[Tensor]) -> None:
+    """dg_attn_fwd / dg_attn_bwd; with an fp8 copy their _fp8 form, with document starts their _doc form (fp8 nullable there)"""
+    if doc_starts is not None:
+        name, tail = base + "_doc", (C.byref(fp8_arg) if fp8_arg is not None else None, _p(doc_starts))
+    elif fp8_arg is not None:
+        name, tail = base + "_fp8", (C.byref(fp8_arg),)
+    else:
+        name, tail = base, ()
+    check(getattr(lib, name)(*args, *tail, _stream()), name)
+
+
 def attn_fwd(qkv: Tensor, B: int, T: int, NH: int, H: int, scale: float, p: float, rng_state: Optional[Tensor], site: int,
              keep: bool = False, fp8_out=None, doc_starts: Optional[Tensor] = None):
     """doc_starts (int32 [B*T], ops.doc_starts): document mask -- query i attends to keys doc_starts[b, i] <= j <= i only.
@@ -641,26 +652,14 @@ def attn_fwd(qkv: Tensor, B: int, T: int, NH: int, H: int, scale: float, p: floa
         if n > 0:
             kb = torch.empty(n, dtype=torch.uint8, device=qkv.device)
     if doc_starts is not None:
-        import ctypes
         _chk_doc_starts(doc_starts, B, T)
-        arg = None
-        if fp8_out is not None:
-            arg, q8, sinv = _attn_fp8_arg(fp8_out, (B * T, NH * H), torch.float8_e4m3fn, qkv.device)
-        check(lib.dg_attn_fwd_doc(_p(qkv), _p(out), _p(lse), B, T, NH, H, float(scale), float(p), _p(rng_state) if p > 0.0 else None,
-                                  site, dt_code(qkv.dtype), _p(kb), kb.numel() if kb is not None else 0,
-                                  ctypes.byref(arg) if arg is not None else None, _p(doc_starts), _stream()), "dg_attn_fwd_doc")
-        if arg is not None:
-            out.dg_fp8 = (q8, sinv)
-    elif fp8_out is not None:
-        import ctypes
+    arg = None
+    if fp8_out is not None:
         arg, q8, sinv = _attn_fp8_arg(fp8_out, (B * T, NH * H), torch.float8_e4m3fn, qkv.device)
-        check(lib.dg_attn_fwd_fp8(_p(qkv), _p(out), _p(lse), B, T, NH, H, float(scale), float(p), _p(rng_state) if p > 0.0 else None,
-                                  site, dt_code(qkv.dtype), _p(kb), kb.numel() if kb is not None else 0, ctypes.byref(arg), _stream()),
-              "dg_attn_fwd_fp8")
+    _attn_entry("dg_attn_fwd", (_p(qkv), _p(out), _p(lse), B, T, NH, H, float(scale), float(p), _p(rng_state) if p > 0.0 else None,
+                                site, dt_code(qkv.dtype), _p(kb), kb.numel() if kb is not None else 0), arg, doc_starts)
+    if arg is not None:
         out.dg_fp8 = (q8, sinv)
-    else:
-        check(lib.dg_attn_fwd(_p(qkv), _p(out), _p(lse), B, T, NH, H, float(scale), float(p), _p(rng_state) if p > 0.0 else None,
-                              site, dt_code(qkv.dtype), _p(kb), kb.numel() if kb is not None else 0, _stream()), "dg_attn_fwd")
     if kb is not None:
         out.dg_keep = kb
     return out, lse
@@ -688,35 +687,19 @@ def attn_bwd(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, B: int, T: int
     nws = lib.dg_attn_bwd_workspace_bytes(B, T, NH, H, dt_code(qkv.dtype)) if tile_scratch else B * NH * T * 4
     ws = torch.empty(int(nws), dtype=torch.uint8, device=qkv.device)
     if doc_starts is not None:
-        import ctypes
         _chk_doc_starts(doc_starts, B, T)
         if not tile_scratch and int(lib.dg_attn_keep_bits_bytes(B, T, NH, H, dt_code(qkv.dtype))) > 0:
             raise ValueError("attn_bwd: doc_starts needs tile_scratch=True on a shape that takes the MFMA kernels")
-        arg = None
-        if fp8_out is not None:
-            arg, q8, sinv = _attn_fp8_arg(fp8_out, tuple(qkv.shape), torch.float8_e5m2, qkv.device, only8=fp8_out_only)
-        check(lib.dg_attn_bwd_doc(_p(qkv), _p(out), _p(dout), _p(lse), _p(dqkv), _p(ws), ws.numel(), B, T, NH, H, float(scale), float(p),
-                                  _p(rng_state) if p > 0.0 else None, site, dt_code(qkv.dtype), _p(keep_bits),
-                                  keep_bits.numel() if keep_bits is not None else 0, ctypes.byref(arg) if arg is not None else None,
-                                  _p(doc_starts), _stream()), "dg_attn_bwd_doc")
-        if arg is not None:
-            dqkv.dg_fp8 = (q8, sinv)
-            if fp8_out_only:
-                dqkv.dg_unwritten = True
-        return dqkv
+    arg = None
     if fp8_out is not None:
-        import ctypes
         arg, q8, sinv = _attn_fp8_arg(fp8_out, tuple(qkv.shape), torch.float8_e5m2, qkv.device, only8=fp8_out_only)
-        check(lib.dg_attn_bwd_fp8(_p(qkv), _p(out), _p(dout), _p(lse), _p(dqkv), _p(ws), ws.numel(), B, T, NH, H, float(scale), float(p),
-                                  _p(rng_state) if p > 0.0 else None, site, dt_code(qkv.dtype), _p(keep_bits),
-                                  keep_bits.numel() if keep_bits is not None else 0, ctypes.byref(arg), _stream()), "dg_attn_bwd_fp8")
+    _attn_entry("dg_attn_bwd", (_p(qkv), _p(out), _p(dout), _p(lse), _p(dqkv), _p(ws), ws.numel(), B, T, NH, H, float(scale), float(p),
+                                _p(rng_state) if p > 0.0 else None, site, dt_code(qkv.dtype), _p(keep_bits),
+                                keep_bits.numel() if keep_bits is not None else 0), arg, doc_starts)
+    if arg is not None:
         dqkv.dg_fp8 = (q8, sinv)
         if fp8_out_only:
             dqkv.dg_unwritten = True
-        return dqkv
-    check(lib.dg_attn_bwd(_p(qkv), _p(out), _p(dout), _p(lse), _p(dqkv), _p(ws), ws.numel(), B, T, NH, H, float(scale), float(p),
-                          _p(rng_state) if p > 0.0 else None, site, dt_code(qkv.dtype), _p(keep_bits),
-                          keep_bits.numel() if keep_bits is not None else 0, _stream()), "dg_attn_bwd")
     return dqkv
 
 

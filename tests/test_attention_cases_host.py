@@ -1,10 +1,14 @@
-"""tests/attention_cases.py on the CPU: the port of attn_item is a bijection for every block order, the instance names the
-restated dispatch can return are the hipLaunchKernelGGL targets of csrc/attention_mfma.hip (read from its text: a new instance
-in the kernel file fails here until the dispatch restatement and a case know it), and CASES(ncu) reaches every (order, reason,
-rotation) and every (order, instance) pair for several CU counts, each CU-dependent shape inside its own constraint.  The
-shared reference: chunked over the batch it is the unchunked one, the bounds it sets fail a zeroed group, and the operands of
-the cases with few (batch, head) pairs are well-conditioned for those bounds by a criterion read from the reference alone."""
+"""tests/attention_cases.py on the CPU: for every call of its GRID the attention launch plan (attn_plan of csrc/attention.hip)
+equals what the commit before it launched and answered (tests/golden/attn_plan.json, which itself holds every instance, every
+return code and every block order at every CU count); the four queries agree with the plan; the instance names the plan returns
+are the rows of the instance lists of the two MFMA units, read from the source text, and every unit has one launch site per
+pass; the port of attn_item is a bijection for every block order; CASES(ncu) reaches every (order, reason, rotation) and every
+(order, instance) pair for several CU counts, each CU-dependent shape inside its own constraint.  The shared reference:
+chunked over the batch it is the unchunked one, the bounds it sets fail a zeroed group, and the operands of the cases with few
+(batch, head) pairs are well-conditioned for those bounds by a criterion read from the reference alone."""
+import ctypes as C
 import itertools
+import json
 import os
 import re
 import sys
@@ -17,37 +21,52 @@ import attention_cases as A  # noqa: E402
 from oracle import rng_ref  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCE = os.path.join(ROOT, "drakegpt_amd", "csrc", "attention_mfma.hip")
-NCUS = (64, 104, 256, 304)
-ARITY = {"attn_fwd_mfma_kernel": 3, "attn_bwd_dq_mfma_kernel": 4, "attn_bwd_dkv_mfma_kernel": 1}        # template parameters (defaults: false)
+CSRC = os.path.join(ROOT, "drakegpt_amd", "csrc")
+GOLDEN = os.path.join(ROOT, "tests", "golden", "attn_plan.json")
+NCUS = A.NCUS
+UNITS = ("attention.hip", "attention_simple.hip", "attention_mfma.hip", "attention_mfma_doc.hip")
+GENERIC = {f"attn_{k}_simple_kernel<{t},{d}>" for k in ("fwd", "bwd_dq", "bwd_dkv") for t in ("float", "bf16_t") for d in ("false", "true")}
 
 
-def launch_targets():
-    """the kernels csrc/attention_mfma.hip launches, every template argument written out.  The two launches inside
-    attn_dq_launch<TILES, KB, F8> are expanded with the argument lists the file instantiates it with."""
-    text = open(SOURCE).read()
-    found = re.findall(r"hipLaunchKernelGGL\(\(?(\w+)(?:<([^>]*)>)?\)?,", text)
-    assert len(found) == text.count("hipLaunchKernelGGL") == 13, len(found)
-    dq_args = set(re.findall(r"attn_dq_launch<(\w+), (\w+), (\w+)>", text))
-    assert len(dq_args) == 5, dq_args
-    names = set()
-    for kernel, args in found:
-        if not args:
-            assert kernel not in ARITY, kernel
-            names.add(kernel)
-            continue
-        args = [a.strip() for a in args.split(",")]
-        args += ["false"] * (ARITY[kernel] - len(args))
-        binds = dq_args if set(args) & {"TILES", "KB", "F8"} else {("", "", "")}
-        for t, k, f in binds:
-            sub = [dict(TILES=t, KB=k, F8=f).get(a, a) for a in args]
-            assert set(sub) <= {"true", "false"}, sub
-            names.add(f"{kernel}<{','.join(sub)}>")
-    return names
+def source(name):
+    return open(os.path.join(CSRC, name)).read()
+
+
+def listed_instances():
+    """(non-DOC names, DOC names): what the row macros of the two MFMA units make of the instance lists of attention_mfma.hip"""
+    text, doc = source("attention_mfma.hip"), source("attention_mfma_doc.hip")
+    lists = dict(re.findall(r"#define (ATTN_\w+_INSTANCES)\(X\) (?:\\\n)?((?:.*\\\n)*.*)\n", text))
+    assert sorted(lists) == ["ATTN_DKV_INSTANCES", "ATTN_DQ_TILE_INSTANCES", "ATTN_FWD_INSTANCES"]
+    assert "#define ATTN_DQ_BOTH(X, KB, F8) X(true, KB, F8, false) X(true, KB, F8, true)\n" in text
+    fwd = re.findall(r"X\((\w+), (\w+), (\w+)\)", lists["ATTN_FWD_INSTANCES"])
+    dq = [("true", kb, f8, sh) for kb, f8 in re.findall(r"ATTN_DQ_BOTH\(X, (\w+), (\w+)\)", lists["ATTN_DQ_TILE_INSTANCES"]) for sh in ("false", "true")]
+    dkv = re.findall(r"X\(([\w<>]+), ATTN_DKV_KEY", lists["ATTN_DKV_INSTANCES"])
+    assert len(fwd) == lists["ATTN_FWD_INSTANCES"].count("X(") == 5 and len(dq) == 2 * lists["ATTN_DQ_TILE_INSTANCES"].count("ATTN_DQ_BOTH") == 8
+    assert len(dkv) == lists["ATTN_DKV_INSTANCES"].count("X(") == 6
+    # the row macros: name and kernel from the same arguments; the recompute dQ instance is the one row written out
+    assert '"attn_fwd_mfma_kernel<" #DROP "," #KEEP "," #F8 ">", attn_fwd_mfma_kernel<DROP, KEEP, F8>,' in text
+    assert '"attn_bwd_dq_mfma_kernel<" #TILES "," #KB "," #F8 "," #SH ">", attn_bwd_dq_mfma_kernel<TILES, KB, F8, SH>,' in text
+    assert "#define ATTN_DKV_ROW(K, KEY, LDS) {KEY, #K, K, LDS}," in text
+    assert '"attn_fwd_mfma_kernel<" #DROP "," #KEEP "," #F8 ",true>", attn_fwd_mfma_kernel<DROP, KEEP, F8, true>,' in doc
+    assert '"attn_bwd_dq_mfma_kernel<" #TILES "," #KB "," #F8 "," #SH ",true>", attn_bwd_dq_mfma_kernel<TILES, KB, F8, SH, true>,' in doc
+    assert re.findall(r"rows\[\] = \{(.*)\};", text) == ["ATTN_FWD_INSTANCES(ATTN_FWD_ROW)", "ATTN_DQ_ROW(false, false, false, false) ATTN_DQ_TILE_INSTANCES(ATTN_DQ_ROW)",
+                                                          "ATTN_DKV_INSTANCES(ATTN_DKV_ROW)"]
+    assert re.findall(r"rows\[\] = \{(.*)\};", doc) == ["ATTN_FWD_INSTANCES(ATTN_DOC_FWD_ROW)", "ATTN_DQ_TILE_INSTANCES(ATTN_DOC_DQ_ROW)"]
+    dq_all = [("false",) * 4] + dq
+    plain = {f"attn_fwd_mfma_kernel<{','.join(a)}>" for a in fwd} | {f"attn_bwd_dq_mfma_kernel<{','.join(a)}>" for a in dq_all} | set(dkv)
+    docs = {f"attn_fwd_mfma_kernel<{','.join(a)},true>" for a in fwd} | {f"attn_bwd_dq_mfma_kernel<{','.join(a)},true>" for a in dq}
+    return plain, docs
+
+
+def golden():
+    g = json.load(open(GOLDEN))
+    assert g["grid_sha"] == A.GRID_SHA and g["launch_fields"] == list(A.Launch._fields) and len(g["rows"]) == len(A.GRID)
+    launches = [A.Launch(g["names"][l[0]], *l[1:]) for l in g["launches"]]
+    return [(r[0], tuple(launches[i] for i in r[1:3] if i >= 0), tuple(r[3:])) for r in g["rows"]]
 
 
 def all_instances(ncu=256, orders=(0, 1, 2)):
-    """{(order, kind, name)} over everything the restated dispatch can return: one shape per order, both dropout settings,
+    """{(order, kind, name)} over everything the plan returns for the GPU tests' calls: one shape per order, both dropout settings,
     every form and fp8 setting"""
     shapes = {0: (2, 160, 2), 1: (2, 128, 3), 2: (1, 512, 3)}
     out = set()
@@ -77,13 +96,83 @@ def reached(cases, ncu):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the dispatch
+# the plan
 # ---------------------------------------------------------------------------------------------------------------------
+def test_plan_equals_golden():
+    gold = golden()
+    assert os.path.getsize(GOLDEN) <= os.path.getsize(os.path.join(ROOT, "tests", "golden", "nt_plan.json"))
+    bad = []
+    for c, (rc, launches, q) in zip(A.GRID, gold):
+        p = A.plan(c)
+        got = (p.rc, p.launches, (p.mfma_ok, p.fp8_out_ok, p.keep_bytes, p.workspace_bytes))
+        if got != (rc, launches, q):
+            bad.append((c.name, got, (rc, launches, q)))
+        if p.rc:                                             # a refusal launches nothing
+            assert p.n_launch == 0 and not p.launches, c.name
+        else:
+            assert p.family == int(c.dtype == A.BF16 and p.mfma_ok) and p.passes == ((1, 2) if c.bwd else (0,)) and p.block == 256, c.name
+    assert not bad, (len(bad), bad[:3])
+
+
+def test_golden_holds_every_instance_code_and_order():
+    """over the golden file itself: a grid too thin to reach an instance, a return code or a block order fails here"""
+    gold = golden()
+    plain, docs = listed_instances()
+    names = {l.name for _, ls, _ in gold for l in ls}
+    assert len(plain) == 20 and len(docs) == 13 and names == plain | docs | GENERIC, (plain | docs | GENERIC) ^ names
+    assert {rc for rc, _, _ in gold} == {0, -1, -2, -3}
+    for ncu in NCUS:
+        pairs = {(l.balance, ("length" if l.nblk >= 16 else "size") if l.balance == 2 else None)
+                 for c, (_, ls, _) in zip(A.GRID, gold) if c.ncu == ncu for l in ls if l.nblk}
+        assert pairs == {(0, None), (1, None), (2, "length"), (2, "size")}, (ncu, pairs)
+    # every parameter both ways; the dQ substitution; the tiles behind the delta floats
+    for f in "drop keep rng_is_qkv sinv starts".split():
+        assert {getattr(l, f) for _, ls, _ in gold for l in ls} == {0, 1}, f
+    assert all((l.thr, l.inv_keep, l.site) == (0, A.ONE, 0) for _, ls, _ in gold for l in ls if l.rng_is_qkv)
+    assert all(l.tile_off == -1 or (l.tile_off > 0 and l.tile_off % 256 == 0) for _, ls, _ in gold for l in ls)
+    assert not any(ls[1].sinv for _, ls, _ in gold if len(ls) == 2) and any(ls[0].sinv for _, ls, _ in gold if len(ls) == 2)
+    for f in range(2):
+        assert {q[f] for _, _, q in gold} == {0, 1}
+
+
+def test_queries_agree_with_the_plan():
+    """the public entries read the device's CU count (256 without one); their answers do not depend on it"""
+    lib = A._lib().lib
+    shapes = {(c.B, c.T, c.NH, c.H, c.dtype) for c in A.GRID}
+    assert len(shapes) > 50
+    for s in shapes:
+        for bwd in (0, 1):
+            p = A.plan(A.call(bwd, *s, ncu=0))
+            assert (lib.dg_attn_fp8_out_supported(*s), lib.dg_attn_keep_bits_bytes(*s), lib.dg_attn_bwd_workspace_bytes(*s)) == \
+                   (p.fp8_out_ok, p.keep_bytes, p.workspace_bytes), s
+            assert p.fp8_out_ok == int(p.mfma_ok and s[4] == A.BF16) and (p.keep_bytes > 0) == bool(p.fp8_out_ok), s
+            B, T, NH = s[:3]
+            if min(B, T, NH) > 0:
+                assert p.workspace_bytes - (32 * p.keep_bytes) == -(-B * NH * T * 4 // 256) * 256, s
+            else:
+                assert p.workspace_bytes == 0 and p.keep_bytes == 0
+
+
 def test_instance_names_are_the_launch_targets_of_the_kernel_file():
-    targets = launch_targets()
+    plain, docs = listed_instances()
+    targets = plain
     assert len(targets) == 5 + 9 + 6
     assert len([t for t in targets if t.startswith("attn_fwd")]) == 5 and len([t for t in targets if t.startswith("attn_bwd_dq")]) == 9
     assert {n for _, _, n in all_instances()} == targets
+    assert len(docs) == 5 + 8 and {n for o in (0, 1, 2) for p in (0.0, 0.2) for form in ("tiles", "keep_bits") for fp8 in A.FP8
+                                   for n in A.instances(*{0: (2, 160, 2), 1: (2, 128, 3), 2: (1, 512, 3)}[o], p, 256, form, fp8, doc=True)[:2]} == docs
+    # one launch site per pass per unit, each on the row it looked up; the decode kernels keep theirs
+    sites = {u: source(u).count("hipLaunchKernelGGL") for u in UNITS}
+    assert sites == {"attention.hip": 0, "attention_simple.hip": 3 + 4, "attention_mfma.hip": 3, "attention_mfma_doc.hip": 2}, sites
+    for u, n in (("attention_mfma.hip", 3), ("attention_mfma_doc.hip", 2)):
+        assert source(u).count("if (r && p) hipLaunchKernelGGL(r->kernel, dim3(grid), dim3(256), r->lds, s, *p);") == n
+    simple = source("attention_simple.hip")
+    simple = simple[simple.index("int dg_attn_simple_launch("):]
+    assert re.findall(r"hipLaunchKernelGGL\(\((\w+)<T, DOC>\)", simple) == ["attn_fwd_simple_kernel", "attn_bwd_dq_simple_kernel", "attn_bwd_dkv_simple_kernel"]
+    # the plan is made once per call, and the CU count is read by the extern "C" side only
+    text = source("attention.hip")
+    assert text.count(" attn_plan(") == 4 and text.count("dg_num_cus()") == 3 and "dg_num_cus" not in text[:text.index("static int attn_run(")]
+    assert "attn_mfma_kernel<" not in text and "hipGetDevice" not in "".join(source(u) for u in UNITS)
 
 
 @pytest.mark.parametrize("args,want", [
@@ -218,7 +307,7 @@ def test_cases_cover_every_order_reason_rotation_and_instance(ncu):
     assert set().union(*(c.rotations for c in cases)) == {0, 1, 2}
     got = reached(cases, ncu)
     assert got == all_instances(ncu), sorted(all_instances(ncu) - got)
-    assert {n for _, _, n in got} == launch_targets()
+    assert {n for _, _, n in got} == listed_instances()[0]
     # what the suite did not reach before, by name
     by = {c.name: c for c in cases}
     ins = lambda name, p, form, fp8=None: A.instances(by[name].B, by[name].T, by[name].NH, p, ncu, form, fp8)

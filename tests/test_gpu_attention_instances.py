@@ -1,8 +1,7 @@
 """csrc/attention_mfma.hip, every block order, slot rotation and template instance against fp64: the cases of
-tests/attention_cases.py (the dispatch restated; tests/test_attention_cases_host.py holds it to the kernel file and shows
-that the table reaches every (order, reason, rotation) and every (order, instance) pair).  Each case asserts first, with the CU
-count of the device, that it is the case it is named for.  Nothing here observes which kernel a launch ran: see the module
-docstring of attention_cases.
+tests/attention_cases.py (the dispatch read from the library's launch plan; tests/test_attention_cases_host.py holds that plan
+to a recording of the dispatch it replaced and shows that the table reaches every (order, reason, rotation) and every (order,
+instance) pair).  Each case asserts first, from the plan for the CU count of the device, that it is the case it is named for.
 
 Bounds: the project's own (oracle/parity.py).  Forward: per (row, head) 8e-3, element-wise inside the derived envelope, lse to
 1e-5; rows whose kept probabilities were all dropped exactly zero.  Backward, separately for the three forms (tiles from the dQ
@@ -88,6 +87,7 @@ def _case(dev, name):
     assert A.supported(c.B, c.T, c.NH) and _ops().attn_fp8_out_supported(c.B, c.T, c.NH, H, torch.bfloat16)        # the MFMA family runs
     assert A.order(c.B, c.T, c.NH, ncu) == (c.order, c.reason), (c, ncu)
     assert A.rotations(c.B, c.T, c.NH, ncu) == c.rotations, (c, ncu)
+    assert A.plan(A.call(0, c.B, c.T, c.NH, ncu=0)).rot_div == ncu           # the library plans for this device
     return c
 
 

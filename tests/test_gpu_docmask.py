@@ -59,6 +59,18 @@ def _case(dev, name):
     c = D.case(name)
     assert A.supported(c.B, c.T, c.NH) and _ops().attn_fp8_out_supported(c.B, c.T, c.NH, H, torch.bfloat16)        # the MFMA family runs
     assert A.order(c.B, c.T, c.NH, ncu)[0] == c.order, (c, ncu)
+    assert A.plan(A.call(0, c.B, c.T, c.NH, ncu=0)).rot_div == ncu           # the library plans for this device
+    # the document-mask instances: the shared dQ form in the heavy-first order only, the shared tile pass in the balanced orders
+    b = lambda x: "true" if x else "false"
+    for p in D.PS:
+        for form in FORMS:
+            kb = form == "keep_bits" and p > 0
+            assert A.instances(c.B, c.T, c.NH, p, ncu, form, doc=True) == (
+                f"attn_fwd_mfma_kernel<{b(p > 0)},{b(kb)},false,true>", f"attn_bwd_dq_mfma_kernel<true,{b(kb)},false,{b(c.order == 2)},true>",
+                "attn_bwd_dkv_tiles_shared_kernel" if c.order else "attn_bwd_dkv_tiles_kernel"), (c, p, form)
+        assert A.instances(c.B, c.T, c.NH, p, ncu, "keep_bits" if p > 0 else "tiles", "both", doc=True) == (
+            f"attn_fwd_mfma_kernel<{b(p > 0)},{b(p > 0)},true,true>", f"attn_bwd_dq_mfma_kernel<true,{b(p > 0)},true,{b(c.order == 2)},true>",
+            "attn_bwd_dkv_tiles_shared_f8_kernel" if c.order else "attn_bwd_dkv_tiles_f8_kernel"), (c, p)
     return c
 
 
