@@ -263,13 +263,13 @@ def layernorm_bwd_fused_supported(C: int) -> bool:
     return C % 4 == 0 and C <= 1024
 
 
-def gemm_nt(A: Tensor, Bm: Tensor, out_dtype: torch.dtype, *, N: Optional[int] = None, K: Optional[int] = None,
-            bias: Optional[Tensor] = None, relu: bool = False, relu_mask: Optional[Tensor] = None,
-            residual: Optional[Tensor] = None, dropout_p: float = 0.0, rng_state: Optional[Tensor] = None,
-            site: int = 0, out: Optional[Tensor] = None, sign_bits_out: Optional[Tensor] = None,
-            sign_bits: Optional[Tensor] = None, colsum_part: Optional[Tensor] = None,
-            scale_a: Optional[Tensor] = None, scale_b: Optional[Tensor] = None, fp8_out=None, fp8_out_only: bool = False,
-            split: bool = False) -> Tensor:
+def gemm_nt_args(A: Tensor, Bm: Tensor, out_dtype: torch.dtype, *, N: Optional[int] = None, K: Optional[int] = None,
+                 bias: Optional[Tensor] = None, relu: bool = False, relu_mask: Optional[Tensor] = None,
+                 residual: Optional[Tensor] = None, dropout_p: float = 0.0, rng_state: Optional[Tensor] = None,
+                 site: int = 0, out: Optional[Tensor] = None, sign_bits_out: Optional[Tensor] = None,
+                 sign_bits: Optional[Tensor] = None, colsum_part: Optional[Tensor] = None,
+                 scale_a: Optional[Tensor] = None, scale_b: Optional[Tensor] = None, fp8_out=None, fp8_out_only: bool = False,
+                 split: bool = False):
     """out[M,N] = epilogue(A[M,K] @ Bm[N,K]^T).  A/Bm may carry padding columns beyond K (ld > K).
     split: fp32 A / Bm / relu_mask contracted as split bf16 (hi.hi + hi.lo + lo.hi, precision "bf16x3"); fp32 output.
     fp8_out_only: with fp8_out, do not write `out` (nobody reads the bf16 form); the returned tensor is marked dg_unwritten.
@@ -279,7 +279,10 @@ def gemm_nt(A: Tensor, Bm: Tensor, out_dtype: torch.dtype, *, N: Optional[int] =
     fp8: A float8_e4m3fn (activations) or float8_e5m2 (gradients), Bm float8_e4m3fn, scale_a / scale_b the device scalars
     fp8_quantize returned (out = epilogue(scale_a * scale_b * A @ Bm^T)); K % 128 == 0.
     sign_bits_out / sign_bits: opaque uint8 buffer (new_sign_bits) holding one bit per element, out > 0.
-    colsum_part: fp32 [gemm_nt_colsum_rows(...), N] (rows may be strided): partial rows of the column sums of out."""
+    colsum_part: fp32 [gemm_nt_colsum_rows(...), N] (rows may be strided): partial rows of the column sums of out.
+
+    This is the argument builder: every check of a gemm_nt call and the filled dg_gemm_nt_args; returns (args, out) and launches
+    nothing (gemm_nt makes the call; the tests hand the struct to the library's launch plan)."""
     _chk(A, "A", contiguous=False)
     _chk(Bm, "B", contiguous=False)
     fp8 = A.dtype in FP8_DTYPES
@@ -349,6 +352,12 @@ def gemm_nt(A: Tensor, Bm: Tensor, out_dtype: torch.dtype, *, N: Optional[int] =
             out.dg_unwritten = True
     elif fp8_out_only:
         raise RuntimeError("gemm_nt: fp8_out_only needs fp8_out")
+    return a, out
+
+
+def gemm_nt(A: Tensor, Bm: Tensor, out_dtype: torch.dtype, **options) -> Tensor:
+    """gemm_nt_args(...) and the launch: out[M,N] = epilogue(A[M,K] @ Bm[N,K]^T) on torch's current stream"""
+    a, out = gemm_nt_args(A, Bm, out_dtype, **options)
     check(lib.dg_gemm_nt(C.byref(a), _stream()), "dg_gemm_nt")
     return out
 

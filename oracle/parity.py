@@ -123,6 +123,67 @@ def gemm_envelope(A: Tensor, B: Tensor, K: Optional[int] = None, bias: Optional[
     return e * (K * 2.0 ** -24)
 
 
+def gemm_nt_epilogue_fp64(acc: Tensor, bias: Optional[Tensor] = None, relu: bool = False, sign_mask: Optional[Tensor] = None,
+                          relu_mask: Optional[Tensor] = None, keep: Optional[Tensor] = None, p: float = 0.0,
+                          residual: Optional[Tensor] = None) -> dict:
+    """The epilogue of dg_gemm_nt as csrc/gemm_nt_ws.h describes it, in fp64 on ``acc`` = A B^T (times the fp8 scales), in the
+    kernel's order: + bias, ReLU, the one-bit mask (``sign_mask``: 0 / 1 per element), the tensor-valued mask (kept where
+    ``relu_mask`` > 0: 0.0 and -0.0 both drop), dropout (``keep`` 0 / 1 per element, times 1 / (1 - p)), + residual.  Returns
+    dict(out: the value stored (before the output's rounding), pre: acc + bias, the value whose sign a ReLU decides, bit: out > 0,
+    the emitted sign bit, colsum: column sums of out)."""
+    v = f64(acc).clone()
+    if bias is not None:
+        v = v + f64(bias)
+    pre = v
+    if relu:
+        v = v.clamp_min(0.0)
+    if sign_mask is not None:
+        v = torch.where(f64(sign_mask) != 0, v, torch.zeros_like(v))
+    if relu_mask is not None:
+        v = torch.where(f64(relu_mask) > 0, v, torch.zeros_like(v))
+    if keep is not None:
+        v = v * f64(keep) * (1.0 / (1.0 - p))
+    if residual is not None:
+        v = v + f64(residual)
+    return dict(out=v, pre=pre, bit=v > 0, colsum=v.sum(0))
+
+
+def split_bf16(x: Tensor) -> Tuple[Tensor, Tensor]:
+    """hi = bf16(x), lo = bf16(x - hi) of fp32 values, as fp64 (dg_split_bf16 of csrc/gemm_nt_ws.h)"""
+    x = x.detach().cpu().float()
+    hi = x.bfloat16().float()
+    return hi.double(), (x - hi).bfloat16().double()
+
+
+def x3_emulation(A: Tensor, B: Tensor) -> Tensor:
+    """A B^T of precision "bf16x3" with exact sums: lo_a.hi_b + hi_a.lo_b + hi_a.hi_b in fp64 (the lo.lo term is dropped)"""
+    (ah, al), (bh, bl) = split_bf16(A), split_bf16(B)
+    return al @ bh.T + ah @ bl.T + ah @ bh.T
+
+
+X3_SPLIT = 3 * 2.0 ** -16 * (1 + 2.0 ** -8)
+
+
+def x3_envelope(A: Tensor, B: Tensor, K: Optional[int] = None, bias: Optional[Tensor] = None, resid: Optional[Tensor] = None,
+                keep_scale: Optional[Tensor] = None) -> Tensor:
+    """|bf16x3 result - exact| <= (3 * 2^-16 * (1 + 2^-8) + 3 K * 2^-24) * |A| |B|^T, derived:
+
+    u = 2^-8 is bf16's unit roundoff: 8 significand bits, so the spacing in [2^e, 2^(e+1)) is 2^(e-7) and round-to-nearest moves x
+    by at most 2^(e-8) <= u |x|.  The bound is attained: x = 1 + 2^-8 is a tie, hi = 1, lo = 2^-8 = u |x| / (1 + u) -- so
+    |lo| <= 2^-9 |x| does not hold for every x, and the constant below is four times the one that premise would give.
+    With d = x - hi (exact in fp32), lo = bf16(d), r = d - lo:  |d| <= u |x|,  |lo| <= u (1 + u) |x|,  |r| <= u |d| <= u^2 |x|, and
+    a b - (ha hb + ha lb + la hb) = la lb + ra b + (a - ra) rb, hence per product
+        |error| <= (u^2 (1 + u)^2 + u^2 + (1 + u^2) u^2) |a||b| <= 3 u^2 (1 + u) |a||b|.
+    The bf16 x bf16 products are exact in fp32; the three MFMAs of a K step add 3 K terms to the fp32 accumulator, each add
+    rounded once on a running sum bounded by sum |a||b|: 3 K * 2^-24.  ``bias`` / ``resid`` / ``keep_scale`` (keep / (1 - p) times the
+    0 / 1 masks in front of the residual): the epilogue's at most three further fp32 roundings, 3 * 2^-24 of the magnitudes they
+    act on, which the same coefficient applied to bias and residual covers (3 u^2 > 3 * 2^-24) once K + 1 stands for K."""
+    K = f64(A).shape[1] if K is None else K
+    plain = bias is None and resid is None and keep_scale is None
+    coef = X3_SPLIT + 3 * (K if plain else K + 1) * 2.0 ** -24
+    return gemm_envelope(A, B, 1, bias, resid, keep_scale=keep_scale) * (2.0 ** 24 * coef)
+
+
 def mask_margin(pre: Tensor, envelope: Tensor, max_share: float = 1e-3) -> Tensor:
     """elements whose fp64 pre-activation lies further from zero than the envelope: the sign (ReLU, sign bit) of the kernel's
     fp32 value is then decided.  The others are left out of the comparison, and there must be few of them (a condition on
