@@ -124,8 +124,11 @@ __device__ __forceinline__ float wave_amax_nan(float v) {
     for (int o = 32; o > 0; o >>= 1) v = dg_amax_nan(v, __shfl_xor(v, o, 64));
     return v;
 }
-__device__ __forceinline__ float dg_fp8_scale_of(float amax, float fmax) {      // amax == 0: scale 1; NaN / Inf amax: NaN
-    return amax == 0.f ? 1.f : (amax < __builtin_inff() ? fmax / amax : __builtin_nanf(""));
+// amax == 0: scale 1; NaN / Inf amax: NaN; else min(fmax / amax, 2^126): fmax / amax is +Inf in fp32 below amax = fmax / FLT_MAX (a
+// normal number), and an Inf scale turns every exact zero into a NaN byte and scale_inv into 0.  Under the cap amax * 2^126 < fmax,
+// 0 * scale = 0 and 1 / scale = 2^-126 is normal; at and above amax = fmax * 2^-126 the quotient is what it was, bit for bit.
+__device__ __forceinline__ float dg_fp8_scale_of(float amax, float fmax) {
+    return amax == 0.f ? 1.f : (amax < __builtin_inff() ? fminf(fmax / amax, 0x1p126f) : __builtin_nanf(""));
 }
 __device__ __forceinline__ float dg_fp8_clamp(float w, float fmax) { return w > fmax ? fmax : (w < -fmax ? -fmax : w); }   // NaN stays NaN
 // four / eight fp32 values (scaled and clamped by the caller) -> one / two dwords of fp8 bytes; BF8: e5m2, else e4m3

@@ -215,7 +215,9 @@ int64_t dg_gemm_nt_sign_bits_bytes(int M, int N);
  * {first element, element count}, both multiples of 8 (all weight matrices of the step in one launch).
  * dg_fp8_quantize: q[i] = fp8(clamp(x[i] * FMAX / amax[s])) in format fmt (DG_FP8_E4M3 / DG_FP8_E5M2), one byte per element,
  * with amax[s] = the maximum of segment s's partial maxima, and scale_inv[s] = amax[s] / FMAX (1 when amax is 0), the factor
- * dg_gemm_nt multiplies back.  n % 8 == 0. */
+ * dg_gemm_nt multiplies back.  The scale FMAX / amax is capped at 2^126 (an amax below FMAX * 2^-126, where the quotient runs
+ * towards +Inf in fp32: zeros stay zeros and scale_inv stays a normal 2^-126); every fp8 producer of the library shares the rule.
+ * n % 8 == 0. */
 #define DG_FP8_AMAX_PARTS 256
 int dg_fp8_amax(const void* x, int dtype, int64_t n, const int64_t* seg, int n_seg, float* amax_parts, void* stream);
 int dg_fp8_quantize(const void* x, int dtype, void* q, int fmt, int64_t n, const int64_t* seg, int n_seg,
