@@ -704,12 +704,8 @@ __global__ __launch_bounds__(256) void pack_chain_kernel(const int64_t* __restri
     int64_t ld = one.ld;
     int k = blockIdx.x;
     if (desc) {
-        int d = 0;
-        for (int i = 1; i < n_desc; ++i)
-            if ((int64_t)blockIdx.x >= desc[i * 6 + 4]) d = i;
-        const int64_t* D = desc + d * 6;
+        const int64_t* D = dg_desc_of_block(desc, n_desc, 6, 4, k);
         src = (const unsigned short*)D[0]; dst = (unsigned short*)D[1]; K = (int)D[3]; ld = D[5];
-        k = (int)((int64_t)blockIdx.x - D[4]);
     }
     const int KT = K / 32, c = k / KT, t = k % KT;
     if (!(KT & 1)) {                                                      // (pairs never straddle a column chunk or a matrix: k even <=> t even)

@@ -52,6 +52,28 @@ template <typename T, typename U, typename... O> __host__ __device__ __forceinli
 }
 
 // ---------------------------------------------------------------------------------------------
+// Run-time dtype codes to compile-time types at a launch site: f gets a dg_type<T> tag (bf16_t for DG_BF16, float otherwise: the
+// caller has refused every other code, dg_is_float_dtype).  Nest two calls for a pair of dtypes.
+template <typename T> struct dg_type { using type = T; };
+static inline bool dg_is_float_dtype(int dtype) { return dtype == DG_BF16 || dtype == DG_F32; }
+template <typename F> static inline void dg_with_dtype(int dtype, F&& f) {
+    if (dtype == DG_BF16) f(dg_type<__bf16>{});
+    else f(dg_type<float>{});
+}
+
+// Batched launches (the transposes of elementwise.hip, pack_chain_kernel): desc holds n_desc rows of `words` int64 in device memory,
+// word `first` of a row is the first workgroup of that row's matrix in the 1-D grid (ascending).  Returns this workgroup's row and
+// sets `local` to its index inside the matrix.  A linear scan over the table (a few dozen rows per step).
+__device__ __forceinline__ const int64_t* dg_desc_of_block(const int64_t* __restrict__ desc, int n_desc, int words, int first, int& local) {
+    int d = 0;
+    for (int i = 1; i < n_desc; ++i)
+        if ((int64_t)blockIdx.x >= desc[i * words + first]) d = i;
+    const int64_t* D = desc + d * words;
+    local = (int)((int64_t)blockIdx.x - D[first]);
+    return D;
+}
+
+// ---------------------------------------------------------------------------------------------
 // dropout stream: stateless hash of (seed, step, site, element index).  oracle/rng_ref.py
 // restates exactly this on the host.
 __host__ __device__ inline uint32_t dg_mix32(uint32_t x) {
@@ -127,8 +149,10 @@ __device__ __forceinline__ float wave_amax_nan(float v) {
 // amax == 0: scale 1; NaN / Inf amax: NaN; else min(fmax / amax, 2^126): fmax / amax is +Inf in fp32 below amax = fmax / FLT_MAX (a
 // normal number), and an Inf scale turns every exact zero into a NaN byte and scale_inv into 0.  Under the cap amax * 2^126 < fmax,
 // 0 * scale = 0 and 1 / scale = 2^-126 is normal; at and above amax = fmax * 2^-126 the quotient is what it was, bit for bit.
-__device__ __forceinline__ float dg_fp8_scale_of(float amax, float fmax) {
-    return amax == 0.f ? 1.f : (amax < __builtin_inff() ? fminf(fmax / amax, 0x1p126f) : __builtin_nanf(""));
+// (also a host function: dg_debug_fp8_scale in fp8.hip lets the tests hold this very text to their model, bit for bit)
+#define DG_FP8_SCALE_CAP 0x1p126f
+__host__ __device__ __forceinline__ float dg_fp8_scale_of(float amax, float fmax) {
+    return amax == 0.f ? 1.f : (amax < __builtin_inff() ? fminf(fmax / amax, DG_FP8_SCALE_CAP) : __builtin_nanf(""));
 }
 __device__ __forceinline__ float dg_fp8_clamp(float w, float fmax) { return w > fmax ? fmax : (w < -fmax ? -fmax : w); }   // NaN stays NaN
 // four / eight fp32 values (scaled and clamped by the caller) -> one / two dwords of fp8 bytes; BF8: e5m2, else e4m3

@@ -338,29 +338,25 @@ extern "C" int dg_cast(const void* in, int in_dtype, void* out, int out_dtype, i
     unsigned grid = (unsigned)((n / 4 + 255) / 256);
     if (grid == 0) grid = 1;
     if (grid > 4096) grid = 4096;
-    hipStream_t s = (hipStream_t)stream;
-    if (in_dtype == DG_F32 && out_dtype == DG_BF16)
-        hipLaunchKernelGGL((cast_kernel<float, bf16_t>), dim3(grid), dim3(256), 0, s, (const float*)in, (bf16_t*)out, n);
-    else if (in_dtype == DG_BF16 && out_dtype == DG_F32)
-        hipLaunchKernelGGL((cast_kernel<bf16_t, float>), dim3(grid), dim3(256), 0, s, (const bf16_t*)in, (float*)out, n);
-    else if (in_dtype == DG_F32 && out_dtype == DG_F32)
-        hipLaunchKernelGGL((cast_kernel<float, float>), dim3(grid), dim3(256), 0, s, (const float*)in, (float*)out, n);
-    else
-        return DG_ERR_DTYPE;
+    if (!dg_is_float_dtype(in_dtype) || !dg_is_float_dtype(out_dtype) || (in_dtype == DG_BF16 && out_dtype == DG_BF16)) return DG_ERR_DTYPE;
+    dg_with_dtype(in_dtype, [&](auto ti) { dg_with_dtype(out_dtype, [&](auto to) {
+        using TI = typename decltype(ti)::type;
+        using TO = typename decltype(to)::type;
+        if constexpr (!(std::is_same_v<TI, bf16_t> && std::is_same_v<TO, bf16_t>))
+            hipLaunchKernelGGL((cast_kernel<TI, TO>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const TI*)in, (TO*)out, n);
+    }); });
     DG_LAUNCH_CHECK();
     return DG_OK;
 }
 
-// out[c, r] = in[r, c]; 64x64 tile through LDS (+1 pad: conflict-free column reads)
-template <typename TO>
-__global__ void transpose_cast_kernel(const float* __restrict__ in, int64_t ldi, TO* __restrict__ out,
-                                      int64_t ldo, int R, int Cc) {
+// out[c, r] = in[r, c] for the 64x64 tile at (r0, c0), through LDS (+1 pad: conflict-free column reads); 256 threads
+template <typename TI, typename TO>
+__device__ __forceinline__ void transpose_cast_tile(const TI* in, int64_t ldi, TO* out, int64_t ldo, int R, int Cc, int r0, int c0) {
     __shared__ float tile[64][65];
-    int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
-    int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;   // 256 threads: 4 row-lanes
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;   // 4 row-lanes
     for (int i = ty; i < 64; i += 4) {
         int r = r0 + i, c = c0 + tx;
-        tile[i][tx] = (r < R && c < Cc) ? in[(int64_t)r * ldi + c] : 0.f;
+        tile[i][tx] = (r < R && c < Cc) ? to_f32<TI>(in[(int64_t)r * ldi + c]) : 0.f;
     }
     __syncthreads();
     for (int i = ty; i < 64; i += 4) {
@@ -369,16 +365,21 @@ __global__ void transpose_cast_kernel(const float* __restrict__ in, int64_t ldi,
     }
 }
 
+template <typename TO>
+__global__ void transpose_cast_kernel(const float* __restrict__ in, int64_t ldi, TO* __restrict__ out,
+                                      int64_t ldo, int R, int Cc) {
+    transpose_cast_tile(in, ldi, out, ldo, R, Cc, blockIdx.y * 64, blockIdx.x * 64);
+}
+
 extern "C" int dg_transpose_cast(const float* in, int64_t ldi, void* out, int64_t ldo, int dtype,
                                  int R, int Cc, void* stream) {
     if (!in || !out || R <= 0 || Cc <= 0 || ldi < Cc || ldo < R) return DG_ERR_ARG;
+    if (!dg_is_float_dtype(dtype)) return DG_ERR_DTYPE;
     dim3 grid((Cc + 63) / 64, (unsigned)((ldo + 63) / 64));
-    if (dtype == DG_BF16)
-        hipLaunchKernelGGL(transpose_cast_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, in, ldi, (bf16_t*)out, ldo, R, Cc);
-    else if (dtype == DG_F32)
-        hipLaunchKernelGGL(transpose_cast_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, in, ldi, (float*)out, ldo, R, Cc);
-    else
-        return DG_ERR_DTYPE;
+    dg_with_dtype(dtype, [&](auto to) {
+        using TO = typename decltype(to)::type;
+        hipLaunchKernelGGL(transpose_cast_kernel<TO>, grid, dim3(256), 0, (hipStream_t)stream, in, ldi, (TO*)out, ldo, R, Cc);
+    });
     DG_LAUNCH_CHECK();
     return DG_OK;
 }
@@ -388,27 +389,10 @@ extern "C" int dg_transpose_cast(const float* in, int64_t ldi, void* out, int64_
 // step).  desc (int64 x 8, device memory): {in, out, ldi, ldo, R, Cc, first_tile, tiles_x}
 template <typename TI, typename TO>
 __global__ void transpose_cast_batched_kernel(const int64_t* __restrict__ desc, int n_desc) {
-    __shared__ float tile[64][65];
-    int d = 0;
-    for (int i = 1; i < n_desc; ++i)
-        if ((int64_t)blockIdx.x >= desc[i * 8 + 6]) d = i;
-    const int64_t* D = desc + d * 8;
-    const TI* in = (const TI*)D[0];
-    TO* out = (TO*)D[1];
-    const int64_t ldi = D[2], ldo = D[3];
-    const int R = (int)D[4], Cc = (int)D[5];
-    const int local = (int)((int64_t)blockIdx.x - D[6]), tiles_x = (int)D[7];
-    const int r0 = (local / tiles_x) * 64, c0 = (local % tiles_x) * 64;
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    for (int i = ty; i < 64; i += 4) {
-        int r = r0 + i, c = c0 + tx;
-        tile[i][tx] = (r < R && c < Cc) ? to_f32<TI>(in[(int64_t)r * ldi + c]) : 0.f;
-    }
-    __syncthreads();
-    for (int i = ty; i < 64; i += 4) {
-        int c = c0 + i, r = r0 + tx;
-        if (c < Cc && r < ldo) out[(int64_t)c * ldo + r] = from_f32<TO>(tile[tx][i]);
-    }
+    int local;
+    const int64_t* D = dg_desc_of_block(desc, n_desc, 8, 6, local);
+    const int tiles_x = (int)D[7];
+    transpose_cast_tile((const TI*)D[0], D[2], (TO*)D[1], D[3], (int)D[4], (int)D[5], (local / tiles_x) * 64, (local % tiles_x) * 64);
 }
 
 // bf16 -> bf16 form of the same launch (the engine's W^T refresh after every optimizer step): 16-byte global loads and
@@ -417,15 +401,12 @@ __global__ void transpose_cast_batched_kernel(const int64_t* __restrict__ desc, 
 __global__ __launch_bounds__(256) void transpose_bf16_batched_kernel(const int64_t* __restrict__ desc, int n_desc) {
     constexpr int PITCH = 68;                                   // elements: 136-byte rows, 8-byte aligned pieces
     __shared__ __attribute__((aligned(16))) unsigned short tile[64 * PITCH];
-    int d = 0;
-    for (int i = 1; i < n_desc; ++i)
-        if ((int64_t)blockIdx.x >= desc[i * 8 + 6]) d = i;
-    const int64_t* D = desc + d * 8;
+    int local;
+    const int64_t* D = dg_desc_of_block(desc, n_desc, 8, 6, local);
     const unsigned short* in = (const unsigned short*)D[0];
     unsigned short* out = (unsigned short*)D[1];
     const int64_t ldi = D[2], ldo = D[3];
-    const int R = (int)D[4], Cc = (int)D[5];
-    const int local = (int)((int64_t)blockIdx.x - D[6]), tiles_x = (int)D[7];
+    const int R = (int)D[4], Cc = (int)D[5], tiles_x = (int)D[7];
     const int r0 = (local / tiles_x) * 64, c0 = (local % tiles_x) * 64;
     const bool vec = ((ldi | ldo) % 8 == 0) && ((((uintptr_t)in) | ((uintptr_t)out)) % 16 == 0);
 #pragma unroll
@@ -474,15 +455,12 @@ __global__ __launch_bounds__(256) void transpose_bf16_batched_kernel(const int64
 __global__ __launch_bounds__(256) void transpose_u8_batched_kernel(const int64_t* __restrict__ desc, int n_desc) {
     constexpr int PITCH = 144;                                  // bytes: 16-byte aligned rows, rows 4 apart on different banks
     __shared__ __attribute__((aligned(16))) unsigned char ta[128 * PITCH], tb[128 * PITCH];
-    int d = 0;
-    for (int i = 1; i < n_desc; ++i)
-        if ((int64_t)blockIdx.x >= desc[i * 8 + 6]) d = i;
-    const int64_t* D = desc + d * 8;
+    int local;
+    const int64_t* D = dg_desc_of_block(desc, n_desc, 8, 6, local);
     const unsigned char* in = (const unsigned char*)D[0];
     unsigned char* out = (unsigned char*)D[1];
     const int64_t ldi = D[2], ldo = D[3];
-    const int R = (int)D[4], Cc = (int)D[5];
-    const int local = (int)((int64_t)blockIdx.x - D[6]), tiles_x = (int)D[7];
+    const int R = (int)D[4], Cc = (int)D[5], tiles_x = (int)D[7];
     const int r0 = (local / tiles_x) * 128, c0 = (local % tiles_x) * 128;
     const bool vec = ((ldi | ldo) % 16 == 0) && ((((uintptr_t)in) | ((uintptr_t)out)) % 16 == 0);
 #pragma unroll
@@ -540,15 +518,13 @@ extern "C" int dg_transpose_u8_batched(const int64_t* desc, int n_desc, int tota
 
 extern "C" int dg_transpose_cast_batched(const int64_t* desc, int n_desc, int total_tiles, int in_dtype, int dtype, void* stream) {
     if (!desc || n_desc <= 0 || total_tiles <= 0) return DG_ERR_ARG;
+    if (!dg_is_float_dtype(in_dtype) || !dg_is_float_dtype(dtype) || (in_dtype == DG_BF16 && dtype == DG_F32)) return DG_ERR_DTYPE;
     hipStream_t s = (hipStream_t)stream;
-    if (in_dtype == DG_F32 && dtype == DG_BF16)
-        hipLaunchKernelGGL((transpose_cast_batched_kernel<float, bf16_t>), dim3(total_tiles), dim3(256), 0, s, desc, n_desc);
-    else if (in_dtype == DG_F32 && dtype == DG_F32)
-        hipLaunchKernelGGL((transpose_cast_batched_kernel<float, float>), dim3(total_tiles), dim3(256), 0, s, desc, n_desc);
-    else if (in_dtype == DG_BF16 && dtype == DG_BF16)     // from the bf16 shadow the optimizer just wrote: half the read
+    if (in_dtype == DG_BF16)                              // from the bf16 shadow the optimizer just wrote: half the read
         hipLaunchKernelGGL(transpose_bf16_batched_kernel, dim3(total_tiles), dim3(256), 0, s, desc, n_desc);
-    else
-        return DG_ERR_DTYPE;
+    else dg_with_dtype(dtype, [&](auto to) {
+        hipLaunchKernelGGL((transpose_cast_batched_kernel<float, typename decltype(to)::type>), dim3(total_tiles), dim3(256), 0, s, desc, n_desc);
+    });
     DG_LAUNCH_CHECK();
     return DG_OK;
 }

@@ -553,28 +553,26 @@ def transpose_cast(W: Tensor, out_dtype: torch.dtype, ldo: Optional[int] = None,
     return out
 
 
-def make_transpose_table(pairs, device) -> tuple:
-    """descriptor table for transpose_cast_batched: pairs = [(W [R,C] fp32, Wt [C, ldo])]"""
+def _transpose_table(pairs, device, tile: int) -> tuple:
+    """(table, rows, tiles) of a batched transposition in tile x tile tiles: pairs = [(W [R, C], Wt [C, ldo >= R])]"""
     rows, first = [], 0
     for W, Wt in pairs:
         R, Cc = W.shape
         ldo = Wt.shape[1]
-        tiles_x, tiles_y = (Cc + 63) // 64, (ldo + 63) // 64
+        tiles_x, tiles_y = (Cc + tile - 1) // tile, (ldo + tile - 1) // tile
         rows.append([W.data_ptr(), Wt.data_ptr(), _ld(W), ldo, R, Cc, first, tiles_x])
         first += tiles_x * tiles_y
     return torch.tensor(rows, dtype=torch.int64, device=device), len(rows), first
+
+
+def make_transpose_table(pairs, device) -> tuple:
+    """descriptor table for transpose_cast_batched: pairs = [(W [R,C] fp32 or bf16, Wt [C, ldo])]"""
+    return _transpose_table(pairs, device, 64)
 
 
 def make_transpose_u8_table(pairs, device) -> tuple:
     """descriptor table for transpose_u8_batched: pairs = [(W8 [R, C] one-byte elements, Wt8 [C, ldo >= R])]"""
-    rows, first = [], 0
-    for W, Wt in pairs:
-        R, Cc = W.shape
-        ldo = Wt.shape[1]
-        tiles_x, tiles_y = (Cc + 127) // 128, (ldo + 127) // 128
-        rows.append([W.data_ptr(), Wt.data_ptr(), _ld(W), ldo, R, Cc, first, tiles_x])
-        first += tiles_x * tiles_y
-    return torch.tensor(rows, dtype=torch.int64, device=device), len(rows), first
+    return _transpose_table(pairs, device, 128)
 
 
 def transpose_u8_batched(table: Tensor, n_desc: int, total_tiles: int) -> None:

@@ -1,6 +1,15 @@
 """csrc/fp8.hip (dg_fp8_amax, dg_fp8_quantize, dg_fp8_quantize_delayed) and the scaling rules of csrc/common.h restated on the
 host, and the case tables of tests/test_gpu_fp8_casts.py -- TEST INFRASTRUCTURE (CPU; tests/test_fp8_cases_host.py holds it
-against torch's cast, against the constants of the kernel file and against planted defects).
+against torch's cast, against the library's own plan and against planted defects).
+
+Nothing in the suite can observe WHICH loop a launch took, how many workgroups it had or which of them had work.  The library
+therefore reports its own launch plan through a diagnostic entry (dg_debug_fp8_plan: the host function the three entries
+themselves call, with the predicate the kernels themselves evaluate; pure host code that runs without a GPU), and the class of
+every case below is read from that plan -- there is no second copy of the dispatch here.  The only restatement is ``_partials``,
+the device-side map from a unit of work to its workgroup, (i // block) % parts, with the block, the workgroups per segment and the unit size taken
+from the plan: tests/test_fp8_cases_host.py holds it against a plain loop, holds the kernel names the plan can return against the
+hipLaunchKernelGGL targets read from the source text, and holds the case tables to reach every branch they list.  The GPU tests
+then assert, with the addresses of the tensors they pass, that each case is the case it is named for.
 
 Four parts:
 
@@ -10,10 +19,10 @@ Four parts:
               the integer maximum of the |x| bit patterns (NaN / Inf poison it), scale = min(FMAX / amax, 2^126) (amax 0: 1, NaN /
               Inf: NaN), q = encode(clamp(fp32(x) * scale)) with a comparing clamp (NaN stays NaN, +-Inf saturates),
               scale_inv = fp32(1 / scale).
-  geometry    ``quantize_geometry`` / ``delayed_geometry`` / ``amax_geometry``: which path a launch takes (wide: 16 elements and one
-              16-byte store per lane and trip; narrow: 8 elements, and why), its grid, the trips of the busiest thread and the
-              workgroups without work -- the launch arithmetic at the bottom of each entry of fp8.hip -- and, from the same
-              arithmetic, the partial maximum every workgroup records (``delayed_partials`` / ``amax_partials``).
+  geometry    ``quantize_geometry`` / ``delayed_geometry`` / ``amax_geometry``: readers of the plan -- which path a launch takes
+              (wide: 16 elements and one 16-byte store per lane and trip; narrow: 8 elements, and why), its grid, the trips of the
+              busiest thread and the workgroups without work -- and, with ``_partials``, the partial maximum every workgroup
+              records (``delayed_partials`` / ``amax_partials``).
   cases       the smallest sizes that reach each branch, the operand builders (all bf16 patterns, the rounding boundaries of
               either format for fp32 sources, random segments with a planted maximum and 1e6 fillers in the gaps) and the guard
               bands: every source and every output lies between BAND sentinel elements, the output view filled with the sentinel
@@ -24,13 +33,14 @@ NaN codes are compared as a class (e5m2 has six, e4m3fn two: OCP leaves payload 
 byte is compared exactly.
 
 NOT COVERED, because no sensible size reaches it (named, not approximated):
-  * dg_fp8_quantize without segments: the grid cap of 4096 workgroups needs n > 4096 * 8192 = 33.5 M elements (134 MB as fp32).
-  * dg_fp8_quantize with segments: the blocks_per_seg cap of 128 needs a mean segment above 127 * 8192 = 1.04 M elements, the
-    lower clamp to 1 needs n < n_seg (impossible with segments of at least 8 elements).
+  * dg_fp8_quantize without segments: the cap of the grid needs tens of millions of elements.
+  * dg_fp8_quantize with segments: the cap of blocks_per_seg needs a mean segment of a million elements, the lower clamp to 1
+    needs n < n_seg (impossible with segments of at least 8 elements).
   * an ``x`` that is not 16-byte aligned: both entries refuse it (DG_ERR_ARG), so that term of ``wide`` is always true;
     ``q`` 8-byte aligned is the only alignment reason a case can have.
   * segments whose table entries are not multiples of 8: outside the documented contract of the entry."""
 import collections
+import ctypes as C
 import functools
 
 import numpy as np
@@ -47,13 +57,7 @@ FMAX = {E4M3: 448.0, E5M2: 57344.0}
 SPEC = {E4M3: (4, 3, 7, 0x7F), E5M2: (5, 2, 15, 0x7F)}
 SCALE_CAP = np.float32(2.0 ** 126)
 
-# the launch constants of fp8.hip (tests/test_fp8_cases_host.py reads them out of the source text)
-AMAX_PARTS = 256            # DG_FP8_AMAX_PARTS
-Q_BLOCK = 256               # fp8_amax_kernel, fp8_quantize_kernel
-QD_BLOCK = 1024             # fp8_quantize_delayed_kernel
-SEG_DIV = 256 * 32          # elements per workgroup that size blocks_per_seg
-FLAT_DIV = 256 * 4          # 8-element chunks per workgroup that size the grid without segments
-BPS_CAP, GRID_CAP = 128, 4096
+AMAX_PARTS = 256            # DG_FP8_AMAX_PARTS: the public ABI constant (include/drakegpt_hip.h; tests/test_abi.py holds it)
 
 BAND = 64                   # sentinel elements on either side of every buffer (64 fp32 / bf16 / bytes: 16-byte alignment is kept)
 Q_SENTINEL = 0xA5
@@ -177,71 +181,94 @@ def model_cast(x_f32, amax, fmt, **defect):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the launch geometry
+# the launch geometry: the library's own plan
 # ---------------------------------------------------------------------------------------------------------------------
 SegGeo = collections.namedtuple("SegGeo", "first len wide why units trips busy idle")
-Geo = collections.namedtuple("Geo", "grid bps segs")
-AmaxGeo = collections.namedtuple("AmaxGeo", "grid segs")
+Geo = collections.namedtuple("Geo", "grid bps segs kernel block wgs")
+AmaxGeo = collections.namedtuple("AmaxGeo", "grid segs kernel block wgs")
 AmaxSeg = collections.namedtuple("AmaxSeg", "first len vec nv tail trips idle")
+KIND = {"amax": 0, "quantize": 1, "delayed": 2}
+DT_CODE = {F32: 0, BF16: 1}
+WHY = ("first", "len", "q_align", "x_align")          # the bits of fp8_narrow_terms, lowest first
+BASE = 1 << 20                                         # a made-up 16-byte aligned address for queries without tensors
+DG_ERR_ARG = -1
 
 
 def _cdiv(a, b):
     return -(-a // b)
 
 
-def _why(first, length, q_addr, x_addr):
-    """the terms of ``wide`` in the kernels, one by one; () = wide"""
-    why = []
-    if first % 16:
-        why.append("first")
-    if length % 16:
-        why.append("len")
-    if (q_addr + first) % 16:
-        why.append("q_align")
-    if x_addr % 16:
-        why.append("x_align")
-    return tuple(why)
+@functools.lru_cache(maxsize=1)
+def _lib():
+    from drakegpt_amd import _lib as L
+    lib = L.lib
+    lib.dg_debug_fp8_plan.argtypes = [C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int64), C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_int64),
+                                      C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_char_p)]
+    lib.dg_debug_fp8_plan.restype = C.c_int
+    lib.dg_debug_fp8_constants.argtypes = [C.POINTER(C.c_float)]
+    lib.dg_debug_fp8_constants.restype = None
+    lib.dg_debug_fp8_scale.argtypes = [C.c_float, C.c_int]
+    lib.dg_debug_fp8_scale.restype = C.c_float
+    return L
 
 
-def quantize_geometry(dtype, n, seg=None, x_off=0, q_off=0):
-    """dg_fp8_quantize: x_off / q_off are the byte offsets of the views from a 16-byte boundary"""
-    assert n > 0 and n % 8 == 0 and x_off % 16 == 0 and q_off % 8 == 0, "the entry refuses this call"
-    table = [(0, n)] if seg is None else [tuple(r) for r in seg]
-    ns = len(table)
-    if seg is None:
-        grid, bps = min(max(_cdiv(n // 8, FLAT_DIV), 1), GRID_CAP), 0
-        nb = grid
-    else:
-        bps = min(max(_cdiv(n // ns, SEG_DIV), 1), BPS_CAP)
-        grid, nb = bps * ns, bps
+def plan_rc(entry, dtype, n, seg=None, x_addr=BASE, q_addr=BASE):
+    """(return code, launch words, segment rows, kernel name) of dg_debug_fp8_plan: what the entry launches for a tensor at these
+    byte addresses, or the entry's refusal"""
+    ns = len(seg) if seg is not None else 1
+    table = (C.c_int64 * (2 * ns))(*[w for row in seg for w in row]) if seg is not None else None
+    launch, rows, name = (C.c_int64 * 6)(), (C.c_int64 * (9 * ns))(), C.c_char_p()
+    rc = _lib().lib.dg_debug_fp8_plan(KIND[entry], DT_CODE[dtype], n, table, ns, x_addr, q_addr, launch, rows, ns, C.byref(name))
+    return rc, list(launch), [list(rows[9 * i:9 * i + 9]) for i in range(ns)], name.value.decode() if name.value else None
+
+
+def _plan(entry, dtype, n, seg, x_addr, q_addr):
+    rc, launch, rows, name = plan_rc(entry, dtype, n, seg, x_addr, q_addr)
+    assert rc == 0, f"the entry refuses this call ({rc})"
+    assert launch[5] == len(rows) and launch[4] == launch[3] * launch[1]
+    return launch, rows, name
+
+
+def _cast_geometry(entry, dtype, n, seg, x_addr, q_addr):
+    (grid, block, bps, wgs, _, _), rows, name = _plan(entry, dtype, n, seg, x_addr, q_addr)
     segs = []
-    for first, length in table:
-        why = _why(first, length, q_off, x_off + first * ESZ[dtype])
-        units = length // (8 if why else 16)
-        busy = min(nb, _cdiv(units, Q_BLOCK))
-        segs.append(SegGeo(first, length, not why, why, units, _cdiv(units, nb * Q_BLOCK), busy, nb - busy))
-    return Geo(grid, bps, tuple(segs))
+    for first, length, terms, unit, units, tail, trips, busy, idle in rows:
+        why = tuple(w for i, w in enumerate(WHY) if terms >> i & 1)
+        assert unit == (8 if why else 16) and tail == 0
+        segs.append(SegGeo(first, length, not why, why, units, trips, busy, idle))
+    return Geo(grid, bps, tuple(segs), name, block, wgs)
 
 
-def delayed_geometry(dtype, n, x_off=0, q_off=0):
-    assert n > 0 and n % 8 == 0 and x_off % 16 == 0 and q_off % 8 == 0, "the entry refuses this call"
-    why = _why(0, n, q_off, x_off)
-    units = n // (8 if why else 16)
-    busy = min(AMAX_PARTS, _cdiv(units, QD_BLOCK))
-    return Geo(AMAX_PARTS, 0, (SegGeo(0, n, not why, why, units, _cdiv(units, AMAX_PARTS * QD_BLOCK), busy, AMAX_PARTS - busy),))
+def quantize_geometry(dtype, n, seg=None, x_off=0, q_off=0, x_addr=None, q_addr=None):
+    """dg_fp8_quantize: x_off / q_off are the byte offsets of the views from a 16-byte boundary (or the real addresses)"""
+    return _cast_geometry("quantize", dtype, n, seg, BASE + x_off if x_addr is None else x_addr, BASE + q_off if q_addr is None else q_addr)
 
 
-def amax_geometry(dtype, n, seg=None):
-    table = [(0, n)] if seg is None else [tuple(r) for r in seg]
-    V = 16 // ESZ[dtype]
-    segs = []
-    for first, length in table:
-        nv, tail = length // V, length % V
-        busy = max(min(AMAX_PARTS, _cdiv(nv, Q_BLOCK)), 1 if tail else 0)
-        segs.append(AmaxSeg(first, length, V, nv, tail, _cdiv(nv, AMAX_PARTS * Q_BLOCK), AMAX_PARTS - busy))
-    return AmaxGeo(len(table) * AMAX_PARTS, tuple(segs))
+def delayed_geometry(dtype, n, x_off=0, q_off=0, x_addr=None, q_addr=None):
+    return _cast_geometry("delayed", dtype, n, None, BASE + x_off if x_addr is None else x_addr, BASE + q_off if q_addr is None else q_addr)
 
 
+def amax_geometry(dtype, n, seg=None, x_addr=BASE):
+    (grid, block, _, wgs, _, _), rows, name = _plan("amax", dtype, n, seg, x_addr, 0)
+    return AmaxGeo(grid, tuple(AmaxSeg(first, length, unit, units, tail, trips, idle) for first, length, _, unit, units, tail, trips, _, idle in rows),
+                   name, block, wgs)
+
+
+def constants():
+    """(FP8_E4M3_MAX, FP8_E5M2_MAX, the cap of the scale) as the library holds them"""
+    out = (C.c_float * 3)()
+    _lib().lib.dg_debug_fp8_constants(out)
+    return tuple(np.float32(v) for v in out)
+
+
+def lib_scale_of(amax, fmt):
+    """dg_fp8_scale_of itself, compiled for the host"""
+    return np.float32(_lib().lib.dg_debug_fp8_scale(float(np.float32(amax)), 3 if fmt == E5M2 else 2))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the device-side work map (the one restatement)
+# ---------------------------------------------------------------------------------------------------------------------
 def _partials(bits, unit, block, parts):
     """unit i (``unit`` elements) belongs to workgroup (i // block) % parts: the maximum of the |x| bit patterns per workgroup"""
     nu = bits.size // unit
@@ -257,15 +284,14 @@ def _partials(bits, unit, block, parts):
 
 def delayed_partials(x_f32, geo):
     """slot.next of fp8_quantize_delayed_kernel, all AMAX_PARTS entries, as float32"""
-    g = geo.segs[0]
-    return _partials(abs_bits(x_f32), 16 if g.wide else 8, QD_BLOCK, AMAX_PARTS).view(np.float32)
+    return _partials(abs_bits(x_f32), 16 if geo.segs[0].wide else 8, geo.block, geo.wgs).view(np.float32)
 
 
-def amax_partials(x_f32, seg_geo):
+def amax_partials(x_f32, seg_geo, geo):
     """parts[seg * PARTS + b] of fp8_amax_kernel for one segment: the vector loop, then the scalar tail (fewer than a vector's
     elements, so workgroup 0 takes all of it)"""
     b = abs_bits(x_f32[seg_geo.first:seg_geo.first + seg_geo.len])
-    out = _partials(b, seg_geo.vec, Q_BLOCK, AMAX_PARTS)
+    out = _partials(b, seg_geo.vec, geo.block, geo.wgs)
     if seg_geo.tail:
         out[0] = max(out[0], b[seg_geo.nv * seg_geo.vec:].max())
     return out.view(np.float32)
@@ -606,7 +632,7 @@ def expect_quantize(x, fmt, q_off=0, table=None, **defect):
     view = np.full(x.numel(), Q_SENTINEL, dtype=np.uint8)
     sinv, parts = [], []
     for (first, length), sg in zip(segs, ageo.segs):
-        p = amax_partials(xf, sg)
+        p = amax_partials(xf, sg, ageo)
         codes, si = model_cast(xf[first:first + length], amax_bits(p), fmt, **defect)
         view[first:first + length] = codes
         sinv.append(si)

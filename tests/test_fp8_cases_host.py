@@ -1,6 +1,6 @@
 """tests/fp8_cases.py on the CPU: the hand-written OCP encoder against torch's cast (two independent implementations of the
-rounding), the geometry predictor's constants against the text of csrc/fp8.hip, the case tables of tests/test_gpu_fp8_casts.py
-against the predictor (every branch is reached by a named case), the comparison the GPU test judges with against planted
+rounding), the kernel names the library's launch plan can return against the hipLaunchKernelGGL targets of csrc/fp8.hip (read
+from the source text), the case tables of tests/test_gpu_fp8_casts.py against that plan (every branch is reached by a named case), the comparison the GPU test judges with against planted
 defects (each one must be refused), and the scale rule of dg_fp8_scale_of over a sweep of amax."""
 import os
 import re
@@ -69,31 +69,43 @@ def test_planted_encoders_differ_from_the_real_one():
             assert np.any(F.encode(w, fmt, **kw) != real), kw
 
 
-# --------------------------------------------------------------------------------------------------------------------- constants
-def test_predictor_constants_are_those_of_the_kernel_file():
+# --------------------------------------------------------------------------------------------------------------------- the plan
+def test_plan_kernel_names_are_the_launch_targets():
     hip = _src("drakegpt_amd", "csrc", "fp8.hip")
-    hdr = _src("include", "drakegpt_hip.h")
-    common = _src("drakegpt_amd", "csrc", "common.h")
-    assert int(re.search(r"#define DG_FP8_AMAX_PARTS (\d+)", hdr).group(1)) == F.AMAX_PARTS
-    bounds = {name: int(b) for b, name in re.findall(r"__launch_bounds__\((\d+)\) void (\w+)\(", hip)}
-    assert bounds == {"fp8_amax_kernel": F.Q_BLOCK, "fp8_quantize_kernel": F.Q_BLOCK, "fp8_quantize_delayed_kernel": F.QD_BLOCK}
-    assert re.search(r"fp8_amax_kernel<bf16_t>, grid, dim3\((\d+)\)", hip).group(1) == str(F.Q_BLOCK)
-    assert re.search(r"fp8_quantize_kernel<T, BF8>\), dim3\(grid\), dim3\((\d+)\)", hip).group(1) == str(F.Q_BLOCK)
-    assert re.search(r"fp8_quantize_delayed_kernel<T, BF8>\), dim3\(DG_FP8_AMAX_PARTS\), dim3\((\d+)\)", hip).group(1) == str(F.QD_BLOCK)
-    a, b = re.search(r"bps = \(int\)\(\(n / ns \+ (\d+) \* (\d+) - 1\) / \((\d+) \* (\d+)\)\)", hip).groups()[:2]
-    assert int(a) * int(b) == F.SEG_DIV and (int(a), int(b)) == (256, 32)
-    a, b = re.search(r"int64_t g = \(n / 8 \+ (\d+) \* (\d+) - 1\) / \((\d+) \* (\d+)\)", hip).groups()[:2]
-    assert int(a) * int(b) == F.FLAT_DIV and (int(a), int(b)) == (256, 4)
-    assert int(re.search(r"if \(bps > (\d+)\) bps = \1;", hip).group(1)) == F.BPS_CAP
-    assert int(re.search(r"g > (\d+) \? \1 : g", hip).group(1)) == F.GRID_CAP
-    # strides of the loops: the block size times the number of workgroups
-    assert len(re.findall(r"i \+= \(int64_t\)DG_FP8_AMAX_PARTS \* 256\)", hip)) == 2          # amax: vector loop and tail
-    assert len(re.findall(r"i \+= \(int64_t\)DG_FP8_AMAX_PARTS \* 1024\)", hip)) == 2         # delayed: wide and narrow
-    assert len(re.findall(r"i \+= \(int64_t\)nb \* 256\)", hip)) == 2                         # quantize: wide and narrow
-    assert float(re.search(r"#define FP8_E4M3_MAX ([\d.]+)f", hip).group(1)) == F.FMAX[F.E4M3]
-    assert float(re.search(r"#define FP8_E5M2_MAX ([\d.]+)f", hip).group(1)) == F.FMAX[F.E5M2]
-    cap = re.search(r"fminf\(fmax / amax, (0x1p(\d+)f)\)", common)
-    assert cap and 2.0 ** int(cap.group(2)) == float(F.SCALE_CAP)
+    targets = set(re.findall(r"hipLaunchKernelGGL\(\(?(fp8_\w+)", hip))
+    assert targets == {"fp8_amax_kernel", "fp8_quantize_kernel", "fp8_quantize_delayed_kernel"}
+    names = {F.amax_geometry(d, 1003).kernel for d in F.DTYPES} | {F.quantize_geometry(d, 16).kernel for d in F.DTYPES}
+    names |= {F.quantize_geometry(F.BF16, 32, [(0, 16), (16, 16)]).kernel} | {F.delayed_geometry(d, 16).kernel for d in F.DTYPES}
+    assert names == targets
+    # the launch sites take their geometry from the plan: one launch per entry, each behind a call of fp8_plan
+    entries = ["dg_fp8_amax", "dg_fp8_quantize", "dg_fp8_quantize_delayed", "dg_debug_fp8_plan"]
+    at = [hip.index(f'extern "C" int {e}(') for e in entries]
+    assert at == sorted(at)
+    for e, lo, hi, kernel in zip(entries, at, at[1:], ("fp8_amax_kernel", "fp8_quantize_kernel", "fp8_quantize_delayed_kernel")):
+        body = hip[lo:hi]
+        assert "fp8_plan(" in body and "fp8_check(" in body and re.findall(r"hipLaunchKernelGGL\(\(?(fp8_\w+)", body) == [kernel], e
+        assert "dim3(pl.grid), dim3(pl.block)" in body, e
+    assert hip.count("hipLaunchKernelGGL") == 3 and "fp8_plan(" in hip[at[3]:]
+    # the ABI constant, and the constants of the scale rule as the library holds them
+    assert int(re.search(r"#define DG_FP8_AMAX_PARTS (\d+)", _src("include", "drakegpt_hip.h")).group(1)) == F.AMAX_PARTS
+    assert F.delayed_geometry(F.BF16, 16).grid == F.AMAX_PARTS == F.amax_geometry(F.BF16, 16).wgs
+    assert F.constants() == (np.float32(F.FMAX[F.E4M3]), np.float32(F.FMAX[F.E5M2]), F.SCALE_CAP)
+
+
+def test_plan_values():
+    g = F.quantize_geometry(F.BF16, 16 * 1024 * 2 + 16, q_off=8)
+    assert g[:2] + g[3:] == (5, 0, "fp8_quantize_kernel", 256, 5)
+    assert g.segs == (F.SegGeo(0, 32784, False, ("q_align",), 4098, 4, 5, 0),)
+    g = F.delayed_geometry(F.F32, 2 ** 22 + 2 ** 15 + 16)
+    assert g[:2] + g[3:] == (256, 0, "fp8_quantize_delayed_kernel", 1024, 256)
+    assert g.segs == (F.SegGeo(0, 4227088, True, (), 264193, 2, 256, 0),)
+    g = F.amax_geometry(F.F32, 1003)
+    assert g == F.AmaxGeo(256, (F.AmaxSeg(0, 1003, 4, 250, 3, 1, 255),), "fp8_amax_kernel", 256, 256)
+    g = F.quantize_geometry(F.F32, 4096, [(8, 1024), (2048, 2048)])
+    assert (g.grid, g.bps, g.wgs) == (2, 1, 1) and [s.why for s in g.segs] == [("first", "q_align"), ()]
+    assert F.amax_geometry(F.BF16, 4096, [(8, 1024), (2048, 2048)]).grid == 2 * F.AMAX_PARTS
+    # a real address decides as an offset does
+    assert F.quantize_geometry(F.BF16, 32, x_addr=4096, q_addr=4104).segs[0].why == ("q_align",)
 
 
 # --------------------------------------------------------------------------------------------------------------------- coverage
@@ -111,7 +123,7 @@ def test_every_branch_is_reached_by_a_named_case():
                 reached.add(("quantize", c.dtype, c.fmt, "wide second trip" if s.wide else "narrow second trip"))
             if geo.grid > 1:
                 reached.add(("quantize", c.dtype, c.fmt, "several workgroups"))
-            if s.units % F.Q_BLOCK and geo.grid > 1:
+            if s.units % geo.block and geo.grid > 1:
                 reached.add(("quantize", c.dtype, c.fmt, "ragged last workgroup"))
         else:
             layout, n = F.seg_layout(c.seg)
@@ -124,7 +136,7 @@ def test_every_branch_is_reached_by_a_named_case():
             assert by["narrow_len"].why == ("len",) and by["eight"].why == ("len",) and by["eight"].len == 8
             assert by["wide_100x"].len == 100 * by["wide"].len
             # blocks_per_seg follows the mean: the large segment takes many trips, the small ones leave whole workgroups idle
-            assert 1 < geo.bps < F.BPS_CAP and geo.grid == geo.bps * 6
+            assert geo.bps == 3 and geo.grid == geo.bps * 6                  # (neither clamp of blocks_per_seg: the header names both)
             assert by["wide_100x"].trips >= 8 and by["wide_100x"].idle == 0
             assert all(by[k].idle == geo.bps - 1 for k in kinds if k != "wide_100x")
             # gaps: segments do not touch where a gap was asked for, and never overlap
@@ -141,7 +153,7 @@ def test_every_branch_is_reached_by_a_named_case():
         s, e = geo.segs[0], c.expect
         assert (s.wide, s.why, s.trips, s.idle) == (e["wide"], e["why"], e["trips"], e["idle"]), (c.name, geo)
         if "second" in e:        # workgroups whose threads make a second trip
-            assert F._cdiv(s.units - F.AMAX_PARTS * F.QD_BLOCK, F.QD_BLOCK) == e["second"]
+            assert F._cdiv(s.units - geo.wgs * geo.block, geo.block) == e["second"]
         assert c.step in F.STEPS
         reached.add(("delayed", c.dtype, c.fmt, "wide" if s.wide else "narrow:" + "+".join(s.why)))
         if s.trips > 1:
@@ -183,6 +195,11 @@ def test_geometry_refuses_what_the_entries_refuse():
             F.quantize_geometry(F.BF16, **bad)
         with pytest.raises(AssertionError):
             F.delayed_geometry(F.F32, **bad)
+        # the refusal is the entry's own return code, from the checks the entries themselves run
+        n, x, q = bad["n"], F.BASE + bad.get("x_off", 0), F.BASE + bad.get("q_off", 0)
+        assert F.plan_rc("quantize", F.BF16, n, None, x, q)[0] == F.DG_ERR_ARG and F.plan_rc("delayed", F.F32, n, None, x, q)[0] == F.DG_ERR_ARG
+    assert F.plan_rc("quantize", F.BF16, 16)[0] == 0 and F.plan_rc("delayed", F.F32, 16, None, F.BASE, F.BASE + 8)[0] == 0
+    assert F.plan_rc("amax", F.BF16, 12)[0] == 0 and F.plan_rc("amax", F.BF16, 16, None, F.BASE + 8)[0] == F.DG_ERR_ARG
 
 
 def test_partials_model_follows_the_loops():
@@ -193,17 +210,18 @@ def test_partials_model_follows_the_loops():
     assert not geo.segs[0].wide
     ref = np.zeros(F.AMAX_PARTS, dtype=np.float32)
     for i in range(x.size // 8):
-        b = (i // F.QD_BLOCK) % F.AMAX_PARTS
+        b = (i // 1024) % F.AMAX_PARTS
         ref[b] = max(ref[b], np.abs(x[i * 8:i * 8 + 8]).max())
     assert np.array_equal(F.delayed_partials(x, geo), ref)
     y = x[:1003]
-    sg = F.amax_geometry(F.F32, y.size).segs[0]
+    ageo = F.amax_geometry(F.F32, y.size)
+    sg = ageo.segs[0]
     ref = np.zeros(F.AMAX_PARTS, dtype=np.float32)
     for i in range(sg.nv):
-        b = (i // F.Q_BLOCK) % F.AMAX_PARTS
+        b = (i // 256) % F.AMAX_PARTS
         ref[b] = max(ref[b], np.abs(y[i * 4:i * 4 + 4]).max())
     ref[0] = max(ref[0], np.abs(y[sg.nv * 4:]).max())
-    assert np.array_equal(F.amax_partials(y, sg), ref)
+    assert np.array_equal(F.amax_partials(y, sg, ageo), ref)
     assert F.amax_bits(np.float32([-0.0, -0.0])).view(np.uint32) == 0
     assert np.isnan(F.amax_bits(np.float32([1.0, np.inf, -np.nan]))) and np.isinf(F.amax_bits(np.float32([1.0, -np.inf])))
 
@@ -324,6 +342,8 @@ def test_scale_rule_over_a_sweep_of_amax(fmt):
     sweep = [np.float32(1e-45), np.float32(1e-40), np.nextafter(tiny, np.float32(0)), tiny, np.float32(1e-37),
              np.nextafter(edge, np.float32(0)), edge, np.nextafter(edge, np.float32(1)), fmax * np.float32(2.0 ** -126),
              np.nextafter(fmax * np.float32(2.0 ** -126), np.float32(1)), np.float32(1.0), fmax, flt_max]
+    for a in [np.float32(0.0), np.float32(-0.0), np.float32(np.inf), np.float32(np.nan)] + sweep:      # the library's own function, bit for bit
+        assert F.lib_scale_of(a, fmt).view(np.uint32) == np.float32(F.scale_of(a, fmax)).view(np.uint32) or (np.isnan(F.lib_scale_of(a, fmt)) and np.isnan(F.scale_of(a, fmax))), a
     for a in sweep:
         sc = F.scale_of(a, fmax)
         si = F.scale_inv_of(sc)

@@ -1,7 +1,8 @@
 """csrc/fp8.hip on the GPU, branch by branch (tests/fp8_cases.py has the case tables, the host model and the comparison;
 tests/test_fp8_cases_host.py accepts them on the CPU): dg_fp8_amax, dg_fp8_quantize and dg_fp8_quantize_delayed through
 ops.lib on views between guard bands, byte for byte against the model -- output view, both guard bands, the source, every
-partial maximum, the history slots -- with scale_inv held to 1 ulp of the model's fp32 reciprocal.  Then every finite bf16
+partial maximum, the history slots -- with scale_inv held to 1 ulp of the model's fp32 reciprocal; every launch first asserts
+that the library's plan for the real addresses of its tensors is the plan the case is named for.  Then every finite bf16
 pattern and the rounding boundaries of either format, the non-finite patterns, and an amax below FMAX / FLT_MAX (where
 FMAX / amax is +Inf in fp32) for the two entries of fp8.hip and the four other producers that share dg_fp8_scale_of."""
 import os
@@ -31,6 +32,16 @@ def _np(t):
     return t.detach().cpu().numpy().copy()
 
 
+def _dt(x):
+    return F.BF16 if x.dtype == torch.bfloat16 else F.F32
+
+
+def _is_the_case(real, named):
+    """the library's plan for the tensors actually passed (their real addresses) is the plan the case was named from -- the one
+    tests/test_fp8_cases_host.py holds to the case's expectations and the model's partial maxima are computed with"""
+    assert real == named, (real, named)
+
+
 def _amax_launch(ops, dev, x, table=None):
     """dg_fp8_amax on x (flat CPU tensor) between guard bands -> (source bytes, partials [n_seg * P], the P words behind them)"""
     xb = F.source_buffer(x).to(dev)
@@ -38,6 +49,7 @@ def _amax_launch(ops, dev, x, table=None):
     parts = torch.full(((ns + 1) * P,), GUARD, device=dev)
     seg = torch.tensor(table, dtype=torch.int64, device=dev) if table else None
     assert xb.view.data_ptr() % 16 == 0 and xb.view.numel() == x.numel()
+    _is_the_case(F.amax_geometry(_dt(x), x.numel(), table, x_addr=xb.view.data_ptr()), F.amax_geometry(_dt(x), x.numel(), table))
     ops.check(ops.lib.dg_fp8_amax(ops._p(xb.view), ops.dt_code(x.dtype), x.numel(), ops._p(seg), ns, ops._p(parts), ops._stream()), "dg_fp8_amax")
     torch.cuda.synchronize()
     parts = _np(parts)
@@ -55,6 +67,7 @@ def _quantize_launch(ops, dev, x, fmt, q_off=0, table=None):
     assert xb.view.data_ptr() % 16 == 0 and qb.view.data_ptr() % 16 == q_off and qb.view.numel() == n
     if table:
         assert all(f % 8 == 0 and l % 8 == 0 and 0 <= f and f + l <= n for f, l in table)
+    _is_the_case(F.quantize_geometry(_dt(x), n, table, x_addr=xb.view.data_ptr(), q_addr=qb.view.data_ptr()), F.quantize_geometry(_dt(x), n, table, 0, q_off))
     ops.check(ops.lib.dg_fp8_amax(ops._p(xb.view), ops.dt_code(x.dtype), n, ops._p(seg), ns, ops._p(parts), ops._stream()), "dg_fp8_amax")
     ops.check(ops.lib.dg_fp8_quantize(ops._p(xb.view), ops.dt_code(x.dtype), ops._p(qb.view), ops.dt_code(TFMT[fmt]), n, ops._p(seg), ns,
                                       ops._p(parts), ops._p(sinv[1:]), ops._stream()), "dg_fp8_quantize")
@@ -76,6 +89,7 @@ def _delayed_launch(ops, dev, x, fmt, q_off, prev, step, state=None, parts2=None
         state = ops.new_rng_state(1, dev, step)
     sinv = torch.full((3,), GUARD, device=dev)
     assert xb.view.data_ptr() % 16 == 0 and qb.view.data_ptr() % 16 == q_off and qb.view.numel() == n and parts2.numel() == 2 * P
+    _is_the_case(F.delayed_geometry(_dt(x), n, x_addr=xb.view.data_ptr(), q_addr=qb.view.data_ptr()), F.delayed_geometry(_dt(x), n, 0, q_off))
     ops.check(ops.lib.dg_fp8_quantize_delayed(ops._p(xb.view), ops.dt_code(x.dtype), ops._p(qb.view), ops.dt_code(TFMT[fmt]), n, ops._p(parts2),
                                               ops._p(state), ops._p(sinv[1:]), ops._stream()), "dg_fp8_quantize_delayed")
     torch.cuda.synchronize()
@@ -95,6 +109,10 @@ def test_quantize(dev, case):
     else:
         x, table, _ = F.seg_source(case.dtype, reverse=case.seg)
     want = F.expect_quantize(x, case.fmt, case.q_off, table)
+    geo = F.geometry_of(case)
+    if case.expect:
+        s0, e = geo.segs[0], case.expect
+        assert (s0.wide, s0.why, s0.trips, geo.grid) == (e["wide"], e["why"], e["trips"], e["grid"]), (case.name, geo)
     got = _quantize_launch(ops, dev, x, case.fmt, case.q_off, table)
     _report(f"dg_fp8_quantize {case.name}", F.compare(got, want, case.fmt, case.name))
 
@@ -106,6 +124,8 @@ def test_quantize_delayed(dev, case):
     prev = F.read_slot(np.float32(2.1))                     # last step's range was smaller: the top of this tensor clips
     want = F.expect_delayed(x, case.fmt, case.q_off, prev)
     assert want["amax"] == amax and np.any((want["q"][F.BAND + case.q_off:][:case.n] & 0x7F) == F.encode(np.float32([F.FMAX[case.fmt]]), case.fmt)[0])
+    s0, e = F.geometry_of(case).segs[0], case.expect
+    assert (s0.wide, s0.why, s0.trips, s0.idle) == (e["wide"], e["why"], e["trips"], e["idle"]), (case.name, s0)
     got, _ = _delayed_launch(ops, dev, x, case.fmt, case.q_off, prev, case.step)
     _report(f"dg_fp8_quantize_delayed {case.name}", F.compare(got, want, case.fmt, case.name))
 
@@ -135,8 +155,9 @@ def test_amax(dev, case):
     from drakegpt_amd import ops
     at = F.amax_where(case.dtype, case.n, case.expect)
     x, amax = F.planted_source(case.dtype, case.n, case.n % 1000 + 7, where=at)
-    sg = F.amax_geometry(case.dtype, case.n).segs[0]
-    want = F.amax_partials(F.to_f32(x), sg)
+    ageo = F.amax_geometry(case.dtype, case.n)
+    sg = ageo.segs[0]
+    want = F.amax_partials(F.to_f32(x), sg, ageo)
     xbytes, parts, behind = _amax_launch(ops, dev, x)
     assert np.array_equal(xbytes, F.source_buffer(x).bytes()) and np.all(behind == GUARD)
     assert parts.max() == amax == want.max()
@@ -156,7 +177,7 @@ def test_amax_of_negative_zeros_and_of_segments(dev, dtype):
     assert np.array_equal(xbytes, F.source_buffer(x).bytes()) and np.all(behind == GUARD)
     for i, (sg, a) in enumerate(zip(ageo.segs, amaxes)):
         assert parts[i * P:(i + 1) * P].max() == a, i
-        F._same_bits(parts[i * P:(i + 1) * P], F.amax_partials(F.to_f32(x), sg), f"segment {i}")
+        F._same_bits(parts[i * P:(i + 1) * P], F.amax_partials(F.to_f32(x), sg, ageo), f"segment {i}")
     # a table of fewer segments leaves the partials of the others alone
     _, parts, behind = _amax_launch(ops, dev, x, table[:2])
     assert np.all(behind == GUARD) and parts[P:2 * P].max() == amaxes[1]
