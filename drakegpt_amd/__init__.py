@@ -9,7 +9,7 @@ import importlib
 __version__ = "0.1.0"
 
 _MODEL = ("MODEL_CLASSES", "BigramLM", "BlocksLM", "MultiHeadAttentionLM", "ResidualBlocksLM", "SingleHeadAttentionLM",
-          "TransformerLM", "model_params")
+          "TransformerLM", "model_params", "Generation", "Score")
 _COMPONENT = ("Block", "FeedForward", "FeedForward2", "FeedForward3", "Head", "Head2", "MultiHeadAttention",
               "MultiHeadAttention2", "MultiHeadAttention3", "ResidualBlock", "ResidualBlock2")
 __all__ = list(_MODEL + _COMPONENT)

@@ -161,6 +161,7 @@ SIGNATURES = {
     "dg_sample_rows_ragged": [_vp, _i64, _i, _i, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
     "dg_token_counts": [_vp, _i64, _i, _i, _i, _vp, _i64, _i, _vp],
     "dg_token_counts_rows": [_vp, _i64, _i, _vp, _i64, _i, _vp, _i64, _i, _vp],
+    "dg_token_logprobs": [_vp, _i, _i64, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "dg_cross_entropy": [_vp, _i, _i64, _vp, _vp, _vp, _i64, _i, _f, _vp, _i, _i, _vp],
     "dg_cross_entropy_fp8": [_vp, _i64, _vp, _vp, _vp, _i64, _f, _i, _i, _vp, _i64, _vp],
     "dg_cross_entropy_fused": [_vp, _i64, _vp, _vp, _vp, _i64, _i, _f, _i, _i, _vp, _i64, _i, _vp, _vp, _vp, _f, _vp],

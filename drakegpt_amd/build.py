@@ -40,6 +40,7 @@ SOURCES = [
     "grad_clip.hip",
     "grad_accum.hip",
     "sample.hip",
+    "logprobs.hip",
 ]
 
 

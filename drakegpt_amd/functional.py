@@ -183,3 +183,16 @@ def linear(x, w, b, act):
 
 def cross_entropy(logits, targets, label_smoothing=0.0, z_loss=0.0, ignore_index=None):
     return CrossEntropyFn.apply(logits, targets, label_smoothing, z_loss, ignore_index)
+
+
+@torch.no_grad()
+def token_logprobs(logits, tokens, top_n=0, rank=False):
+    """log_softmax(logits)[..., tokens] for callers who hold logits [..., V] (fp32 or bf16) and tokens [...]: no gradient, one
+    dg_token_logprobs launch and no [.., V] result.  Returns what ops.token_logprobs returns, reshaped to tokens' shape (the
+    top-n pair with one more axis)."""
+    lead = tokens.shape
+    V = logits.shape[-1]
+    res = ops.token_logprobs(logits.reshape(-1, V), tokens.reshape(-1).contiguous(), top_n=top_n, rank=rank)
+    if isinstance(res, tuple):
+        return tuple(r.reshape(*lead, *r.shape[1:]) for r in res)
+    return res.reshape(lead)

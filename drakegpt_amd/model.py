@@ -214,6 +214,90 @@ def trim_to_longest(ids: Tensor, lengths: Optional[Tensor], total: int, return_l
     return out, n.to(device=ids.device, dtype=torch.int64)
 
 
+class Generation(NamedTuple):
+    """what generate(return_logprobs= / top_logprobs= / best_of=) returns.  ids (B, n) and lengths int64 [B]: what
+    generate(return_lengths=True) returns.  logprobs fp32 (B, n), aligned with ids: the model's own log-probability
+    (log_softmax of the raw logits: no temperature, penalty, bias or filter) of every token the row generated, its stop token
+    included; 0.0 at prompt and padded positions, so logprobs.sum(1) is the log-likelihood of what the row generated.
+    top_ids int32 / top_logprobs fp32 (B, n, top_logprobs): the most likely tokens at every generated position, descending,
+    ties by lowest id; -1 / -inf at prompt and padded positions."""
+    ids: Tensor
+    lengths: Tensor
+    logprobs: Tensor
+    top_ids: Tensor
+    top_logprobs: Tensor
+
+
+class Score(NamedTuple):
+    """what score() returns: per target position j (the token idx[:, j + 1] given idx[:, :j + 1]) logprobs fp32 (B, T - 1), ranks
+    int32 (B, T - 1) (0: the model's greedy pick), top_ids int32 / top_logprobs fp32 (B, T - 1, top_logprobs), mask bool
+    (B, T - 1).  Where mask is False (the target lies at or beyond the row's prompt_lengths entry) the four hold 0.0, -1, -1, -inf."""
+    logprobs: Tensor
+    ranks: Tensor
+    top_ids: Tensor
+    top_logprobs: Tensor
+    mask: Tensor
+
+    def perplexity(self) -> float:
+        """exp(-mean log-probability) over the unmasked positions"""
+        n = int(self.mask.sum())
+        return math.exp(-float((self.logprobs.double() * self.mask).sum()) / n) if n else float("nan")
+
+    def accuracy(self, k: int = 1) -> float:
+        """the share of unmasked positions whose target is among the model's k most likely tokens"""
+        n = int(self.mask.sum())
+        return float(((self.ranks < k) & (self.ranks >= 0) & self.mask).sum()) / n if n else float("nan")
+
+
+def check_logprob_args(return_logprobs, top_logprobs, best_of, has_pad: bool):
+    """the checks of generate()'s return_logprobs / top_logprobs / best_of, like check_control_args: plain Python, raised before
+    anything touches a device.  has_pad: the call has a pad_token or stop_tokens.  Returns (return_logprobs, top_logprobs, best_of)."""
+    top = ops.check_top_logprobs(top_logprobs, "generate: top_logprobs")
+    if isinstance(best_of, bool) or not isinstance(best_of, numbers.Integral) or best_of < 1:
+        raise ValueError(f"generate: best_of must be an integer >= 1, got {best_of!r}")
+    if best_of > 1 and not has_pad:
+        raise ValueError("generate: best_of > 1 needs a pad_token (or stop_tokens, whose first one pads)")
+    return bool(return_logprobs), top, int(best_of)
+
+
+def new_score_buffers(B: int, n: int, device) -> tuple:
+    """(logprobs fp32 (B, n) of 0.0, top_ids int32 (B, n, LOGPROBS_MAX_TOP) of -1, top_logprobs fp32 likewise of -inf): what a
+    scored loop starts from -- dg_token_logprobs then writes the scored positions and nothing else"""
+    return (torch.zeros((B, n), dtype=torch.float32, device=device),
+            torch.full((B, n, ops.LOGPROBS_MAX_TOP), -1, dtype=torch.int32, device=device),
+            torch.full((B, n, ops.LOGPROBS_MAX_TOP), -math.inf, dtype=torch.float32, device=device))
+
+
+def make_generation(ids: Tensor, lengths: Optional[Tensor], total: int, logprobs: Tensor, top_ids: Tensor, top_logprobs: Tensor,
+                    top_n: int) -> Generation:
+    """the loops' full-width buffers (ids (B, >= total), logprobs (B, >= total), top_* (B, >= total, >= top_n)) trimmed to the
+    longest row like trim_to_longest; lengths: the loop's int [B], 0 = running"""
+    out, n = trim_to_longest(ids, lengths, total, True)
+    w = out.shape[1]
+    return Generation(out, n, logprobs[:, :w], top_ids[:, :w, :top_n], top_logprobs[:, :w, :top_n])
+
+
+def select_best_of(logprobs: Tensor, lengths: Tensor, prompt_lengths, n: int) -> Tensor:
+    """best_of's choice, on the B * n candidate rows (candidate c of prompt b is row b * n + c): per prompt the row with the highest
+    mean log-probability over its generated tokens (positions [p, length), the stop token included; a row that generated nothing
+    counts as -inf), ties to the lowest c.  Returns the B row indices (int64, CPU)."""
+    lp = logprobs.detach().double().cpu()
+    ln = lengths.detach().cpu().to(torch.int64)
+    p = torch.as_tensor(prompt_lengths, dtype=torch.int64)
+    count = (ln - p).clamp(min=0)
+    mean = torch.where(count > 0, lp.sum(1) / count.clamp(min=1), torch.full_like(lp[:, 0], -math.inf)).view(-1, n)
+    best = mean.max(dim=1, keepdim=True).values
+    first = ((mean == best) | torch.isnan(mean)).to(torch.int64).argmax(dim=1)          # argmax of a 0/1 row: its first 1
+    return torch.arange(mean.shape[0]) * n + first
+
+
+def keep_best_of(gen: Generation, prompt_lengths, n: int, pad: int) -> Generation:
+    """the B kept rows of a B * n-row Generation, trimmed again to the longest of them"""
+    rows = select_best_of(gen.logprobs, gen.lengths, prompt_lengths, n).to(gen.ids.device)
+    w = max(int(gen.lengths[rows].max()), 1)
+    return Generation(gen.ids[rows, :w], gen.lengths[rows], gen.logprobs[rows, :w], gen.top_ids[rows, :w], gen.top_logprobs[rows, :w])
+
+
 class ControlOperands:
     """what a generate() call with controls hands to ops.sample_rows (dg_sample_rows_control): the 16-word control block, bias [V],
     the token counts [B, V] of the whole sequence so far (prompt included, beyond the context window too; the kernel adds the token
@@ -286,19 +370,41 @@ class Sampling(NamedTuple):
     seed: Optional[int] = None
     prompt_lengths: Optional[tuple] = None          # check_prompt_lengths' tuple: the rows' own prompt lengths in a right-padded idx
     return_lengths: bool = False
+    logprobs: bool = False                          # return_logprobs
+    top_logprobs: int = 0
+    best_of: int = 1
 
     @classmethod
     def checked(cls, vocab_size: int, generator, sampler, temperature, top_k, seed, top_p, min_p, repetition_penalty, presence_penalty,
                 frequency_penalty, logit_bias, stop_tokens, pad_token, stop_poll, prompt_lengths=None, shape=(),
-                return_lengths: bool = False) -> "Sampling":
+                return_lengths: bool = False, return_logprobs: bool = False, top_logprobs: int = 0, best_of: int = 1) -> "Sampling":
         """the argument checks of generate(), all of them: plain Python, raised before anything touches a device (shape: idx's,
         which prompt_lengths is checked against)"""
         temperature, top_k = check_sampling_args(sampler, temperature, top_k, vocab_size)
         top_p, min_p = check_nucleus_args(top_p, min_p)
         prompt_lengths = check_prompt_lengths(prompt_lengths, shape)
+        logprobs, top_logprobs, best_of = check_logprob_args(return_logprobs, top_logprobs, best_of,
+                                                             pad_token is not None or stop_tokens is not None)
+        # best_of pads like a ragged call does (its candidates end at different lengths): it always gets the dict
         ctl = check_control_args(repetition_penalty, presence_penalty, frequency_penalty, logit_bias, stop_tokens, pad_token,
-                                 stop_poll, vocab_size, ragged=prompt_lengths is not None)
-        return cls(sampler, temperature, top_k, top_p, min_p, ctl, generator, seed, prompt_lengths, bool(return_lengths))
+                                 stop_poll, vocab_size, ragged=prompt_lengths is not None or best_of > 1)
+        if best_of > 1 and prompt_lengths is not None:
+            prompt_lengths = tuple(p for p in prompt_lengths for _ in range(best_of))          # candidate c of prompt b: row b * n + c
+        return cls(sampler, temperature, top_k, top_p, min_p, ctl, generator, seed, prompt_lengths, bool(return_lengths), logprobs,
+                   top_logprobs, best_of)
+
+    @property
+    def scored(self) -> bool:
+        """the call asks for log-probabilities (return_logprobs, top_logprobs or best_of): it returns a Generation"""
+        return self.logprobs or self.top_logprobs > 0 or self.best_of > 1
+
+    def deliver(self, gen: "Generation", T: int) -> "Generation":
+        """a scored call's result: with best_of the kept row of every prompt (T: idx.shape[1], the prompt length without
+        prompt_lengths)"""
+        if self.best_of == 1:
+            return gen
+        first = self.prompt_lengths if self.prompt_lengths is not None else (T,) * gen.ids.shape[0]
+        return keep_best_of(gen, first, self.best_of, self.ctl["pad"])
 
     @property
     def ragged(self) -> bool:
@@ -316,13 +422,20 @@ class Sampling(NamedTuple):
         """prompt_lengths only (else (idx, None)): idx cropped to the longest prompt with pad_token at and beyond every row's own
         length -- whatever the caller's padding holds never reaches a kernel, the id range check or the result -- and, for a call
         that asks for no new token, its result"""
+        if self.best_of > 1:
+            idx = idx.repeat_interleave(self.best_of, dim=0)
         if self.prompt_lengths is None:
             return idx, None
         p = torch.tensor(self.prompt_lengths, device=idx.device)
         idx = idx[:, :max(self.prompt_lengths)]
         keep = torch.arange(idx.shape[1], device=idx.device)[None, :] < p[:, None]
         idx = torch.where(keep, idx, torch.full_like(idx, self.ctl["pad"]))
-        return idx, (trim_to_longest(idx, p, idx.shape[1], self.return_lengths) if n_new < 1 else None)
+        if n_new >= 1:
+            return idx, None
+        if self.scored:
+            return idx, self.deliver(make_generation(idx, p, idx.shape[1], *new_score_buffers(idx.shape[0], idx.shape[1], idx.device),
+                                                     self.top_logprobs), idx.shape[1])
+        return idx, trim_to_longest(idx, p, idx.shape[1], self.return_lengths)
 
     @property
     def adjust(self) -> bool:
@@ -473,7 +586,8 @@ class _LM(HipModule):
                  temperature: float = 1.0, top_k: Optional[int] = None, seed: Optional[int] = None,
                  top_p: Optional[float] = None, min_p: Optional[float] = None, repetition_penalty: float = 1.0,
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, stop_tokens=None,
-                 pad_token: Optional[int] = None, stop_poll: int = 64, prompt_lengths=None, return_lengths: bool = False):
+                 pad_token: Optional[int] = None, stop_poll: int = 64, prompt_lengths=None, return_lengths: bool = False,
+                 return_logprobs: bool = False, top_logprobs: int = 0, best_of: int = 1):
         """ref: src/model.py:611-636.  sampler="host" (default): softmax runs on the GPU; torch.multinomial runs on the host CPU
         generator (the global one unless `generator` is given), as it does in the reference on CPU.  A temperature other than 1
         (0 = greedy) or a top_k filters the distribution on the GPU first (dg_sample_rows); so do top_p (nucleus: the most
@@ -497,15 +611,61 @@ class _LM(HipModule):
         shared position walks all rows from min p_b: a row still inside its prompt keeps its prompt token, a row past it samples
         (dg_sample_rows_ragged), so row b has the tokens of a call on prompt b alone in that row with the same seed.
         return_lengths=True: (ids, the rows' final lengths as int64 [B]), in any call.
+        return_logprobs=True, top_logprobs=n (0..20) or best_of=n: the call returns a Generation (see there) -- per generated token
+        the model's own log-probability (log_softmax of the raw logits, dg_token_logprobs: no temperature, penalty, bias or filter;
+        the stop token's own position included, 0.0 at prompt and padded positions) and the top_logprobs most likely tokens; one
+        more launch per token, and the tokens are bit for bit those of the call without them.  best_of=n draws n candidates per
+        prompt (row b * n + c) and keeps the one with the highest mean log-probability over its generated tokens, ties to the
+        lowest c; it pads, so it needs a pad_token or stop_tokens.  The numbers equal score() of the returned text.
         The document mask (set_doc_separator) is NOT applied here: the tokens with a separator set are bit for bit those without.
         To end a sample at the end of its document, pass stop_tokens=[sep]."""
         req = Sampling.checked(self.token_embedding_table.weight.shape[0], generator, sampler, temperature, top_k, seed, top_p, min_p,
                                repetition_penalty, presence_penalty, frequency_penalty, logit_bias, stop_tokens, pad_token, stop_poll,
-                               prompt_lengths, tuple(getattr(idx, "shape", ())), return_lengths)
+                               prompt_lengths, tuple(getattr(idx, "shape", ())), return_lengths, return_logprobs, top_logprobs, best_of)
+        T = idx.shape[1] if getattr(idx, "dim", lambda: 0)() == 2 else 0
         idx, done = req.enter(idx, max_new_tokens)
         if done is not None:
             return done
-        return (self._generate_device if sampler == "device" else self._generate_host)(idx, max_new_tokens, req)
+        out = (self._generate_device if sampler == "device" else self._generate_host)(idx, max_new_tokens, req)
+        return req.deliver(out, T) if req.scored else out
+
+    @torch.no_grad()
+    def score(self, idx, prompt_lengths=None, top_logprobs: int = 0) -> Score:
+        """the model's log-probability of every token of idx (B, T) given the tokens before it: per-token log-likelihood,
+        perplexity, accuracy@k.  One forward pass in eval() semantics (no dropout, whatever mode the model is in; like generate,
+        without the document mask) on idx[:, :-1], then ONE dg_token_logprobs launch over its B * (T - 1) rows of logits, read in
+        the dtype the forward wrote them in, with the targets idx[:, 1:] -- no (B * T, V) log-softmax exists at any point.
+        prompt_lengths (B integers, 1 <= p_b <= T): row b holds p_b tokens, right-padded; what lies beyond is read by nothing and
+        the positions whose target lies there are masked.  top_logprobs in [0, 20]: also the most likely tokens per position.
+        The numbers are those generate(return_logprobs=True) reports for the same tokens.  T - 1 must fit the context window."""
+        top_n = ops.check_top_logprobs(top_logprobs, "score: top_logprobs")
+        first = check_prompt_lengths(prompt_lengths, tuple(getattr(idx, "shape", ())))
+        ops._chk(idx, "idx", torch.int64, contiguous=False)
+        if idx.dim() != 2 or idx.shape[1] < 2:
+            raise ValueError("score: idx must be (B, T) with T >= 2")
+        B, T = idx.shape
+        pos = torch.arange(1, T, device=idx.device)[None, :]                      # the targets' positions
+        mask = (pos < torch.tensor(first, device=idx.device)[:, None]) if first is not None else torch.ones((B, T - 1), dtype=torch.bool, device=idx.device)
+        if first is not None:                                                      # the padding never reaches a kernel or the id check
+            idx = idx.clone()
+            idx[:, 1:][~mask] = 0
+        was = self.training
+        self.eval()
+        try:
+            logits, _ = self._unmasked(idx[:, :-1].contiguous())
+        finally:
+            self.train(was)
+        V = logits.shape[-1]
+        res = ops.token_logprobs(logits.view(B * (T - 1), V), idx[:, 1:].reshape(-1), top_n=top_n, rank=True)
+        lp, rk = res[0].view(B, T - 1), res[1].view(B, T - 1)
+        ti = res[2].view(B, T - 1, top_n) if top_n else torch.empty((B, T - 1, 0), dtype=torch.int32, device=idx.device)
+        tl = res[3].view(B, T - 1, top_n) if top_n else torch.empty((B, T - 1, 0), dtype=torch.float32, device=idx.device)
+        if first is not None:
+            lp = torch.where(mask, lp, torch.zeros_like(lp))
+            rk = torch.where(mask, rk, torch.full_like(rk, -1))
+            ti = torch.where(mask[:, :, None], ti, torch.full_like(ti, -1))
+            tl = torch.where(mask[:, :, None], tl, torch.full_like(tl, -math.inf))
+        return Score(lp, rk, ti, tl, mask)
 
     @torch.no_grad()
     def _generate_host(self, idx, max_new_tokens, req: Sampling, source=None):
@@ -526,8 +686,11 @@ class _LM(HipModule):
         if req.ragged:
             prompt, first = idx.cpu(), torch.tensor(req.prompt_lengths)
             idx = idx[:, :t0]
+        scores = new_score_buffers(idx.shape[0], total, idx.device) if req.scored else None
         for L in range(t0, total):
-            probs = self._probs(source(idx), params, cs if req.adjust else None)
+            logits = source(idx)
+            probs = self._probs(logits, params, cs if req.adjust else None)
+            unscored = finished                      # the rows that were finished before this position, or are forced at it
             nxt = torch.multinomial(probs.cpu(), num_samples=1, generator=req.generator)
             forced = None
             if req.ragged and L < prompt.shape[1]:
@@ -542,11 +705,20 @@ class _LM(HipModule):
                 finished = finished | hit
             nxt = nxt.to(idx.device)
             idx = torch.cat((idx, nxt), dim=1)
+            if scores is not None:                   # one dg_token_logprobs launch after the token is placed
+                res = ops.token_logprobs(logits, nxt[:, 0].contiguous(), top_n=req.top_logprobs)
+                keep = ~(unscored if forced is None else unscored | forced).to(idx.device)
+                lp, top = (res[0], res[1:]) if req.top_logprobs else (res, ())
+                scores[0][:, L] = torch.where(keep, lp, torch.zeros_like(lp))
+                for buf, t in zip(scores[1:], top):
+                    buf[:, L, :req.top_logprobs] = torch.where(keep[:, None], t, buf[:, L, :req.top_logprobs])
             if req.adjust:
                 ops.token_counts(nxt, 1 if forced is None else (~forced).to(device=idx.device, dtype=torch.int32), V, cs.counts,
                                  accumulate=True)
             if ends and bool(finished.all()):
                 break
+        if scores is not None:
+            return make_generation(idx, final, total, *scores, req.top_logprobs)
         return trim_to_longest(idx, final, total, req.return_lengths)
 
     @staticmethod
@@ -578,6 +750,10 @@ class _LM(HipModule):
                                    n_new=max_new_tokens)
         kw = {} if cs is None else cs.kw(req.ragged)
         lengths = cs.lengths if req.poll or req.ragged else None
+        scores = new_score_buffers(B, total, idx.device) if req.scored else None
+        skw = None if scores is None else dict(
+            state=state, lengths=None if cs is None else cs.lengths, spans=cs.spans if req.ragged else None, out=scores[0],
+            out_top_ids=scores[1], out_top_lp=scores[2], top_n=torch.tensor([req.top_logprobs], dtype=torch.int32, device=idx.device))
         saved = self.__dict__.get("check_ids")           # None: the class's default is in force
         self.check_ids = False
         try:
@@ -585,6 +761,8 @@ class _LM(HipModule):
                 lo = 0 if ctx is None else max(0, L - ctx)
                 logits, _ = self._unmasked(ids[:, lo:L].contiguous())
                 ops.sample_rows(logits[:, -1, :], state, params, ids=ids, **kw)
+                if skw is not None:                  # one launch after the token is placed, before the position moves on
+                    ops.token_logprobs(logits[:, -1, :], ids, **skw)
                 ops.state_advance(state)
                 if stop_poll_due(req.poll, L + 1 - t0, lengths):
                     break
@@ -592,6 +770,8 @@ class _LM(HipModule):
             del self.check_ids
             if saved is not None:
                 self.check_ids = saved
+        if scores is not None:
+            return make_generation(ids, lengths, total, *scores, req.top_logprobs)
         return trim_to_longest(ids, lengths, total, req.return_lengths)
 
 
@@ -791,7 +971,8 @@ class TransformerLM(_BlocksLM):
                  sampler: str = "host", temperature: float = 1.0, top_k: Optional[int] = None, seed: Optional[int] = None,
                  top_p: Optional[float] = None, min_p: Optional[float] = None, repetition_penalty: float = 1.0,
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, stop_tokens=None,
-                 pad_token: Optional[int] = None, stop_poll: int = 64, prompt_lengths=None, return_lengths: bool = False):
+                 pad_token: Optional[int] = None, stop_poll: int = 64, prompt_lengths=None, return_lengths: bool = False,
+                 return_logprobs: bool = False, top_logprobs: int = 0, best_of: int = 1):
         """ref: src/model.py:611-636.  While the sequence still fits the context window the per-layer K/V of the
         tokens seen so far are kept (training layout, [B, ctx, 3C]) and only the new position is computed; once the
         window starts to slide every position embedding shifts, the cache is void, and decoding continues exactly
@@ -805,20 +986,26 @@ class TransformerLM(_BlocksLM):
         sampler is dg_sample_rows_control.  prompt_lengths / return_lengths: as in _LM.generate; the graph-replayed path prefills
         idx[:, :min p_b] in one pass, the rows with longer prompts ride along through their remaining prompt tokens one step
         each, and a third pair of graphs, whose sampler is dg_sample_rows_ragged, is captured on the first such call.
+        return_logprobs / top_logprobs / best_of: as in _LM.generate; the graph-replayed path replays scored twins of the mode's
+        pair (the same steps with one dg_token_logprobs launch between the sampler and dg_state_advance), captured on the first
+        scored call per mode; a call without them replays the graphs it always did.
         The document mask (set_doc_separator) is not applied: neither the decode kernels, the prefill nor the graphs know it, and
         the tokens are bit for bit those without a separator set; stop_tokens=[sep] ends a sample at the end of its document."""
         req = Sampling.checked(self.token_embedding_table.weight.shape[0], generator, sampler, temperature, top_k, seed, top_p, min_p,
                                repetition_penalty, presence_penalty, frequency_penalty, logit_bias, stop_tokens, pad_token, stop_poll,
-                               prompt_lengths, tuple(getattr(idx, "shape", ())), return_lengths)
+                               prompt_lengths, tuple(getattr(idx, "shape", ())), return_lengths, return_logprobs, top_logprobs, best_of)
+        T = idx.shape[1] if getattr(idx, "dim", lambda: 0)() == 2 else 0
         idx, done = req.enter(idx, max_new_tokens)
         if done is not None:
             return done
         cached = use_cache and not self.training
         if sampler == "device":
-            return (self._generate_device_cached if cached else self._generate_device)(idx, max_new_tokens, req)
-        if cached and req.span(idx.shape[1], 0)[0] < self.context_length:
-            return self._generate_host(idx, max_new_tokens, req, self._kv_logits(idx))
-        return self._generate_host(idx, max_new_tokens, req)
+            out = (self._generate_device_cached if cached else self._generate_device)(idx, max_new_tokens, req)
+        elif cached and req.span(idx.shape[1], 0)[0] < self.context_length:
+            out = self._generate_host(idx, max_new_tokens, req, self._kv_logits(idx))
+        else:
+            out = self._generate_host(idx, max_new_tokens, req)
+        return req.deliver(out, T) if req.scored else out
 
     # ------------------------------------------------------------------ graph-replayed decoding (sampler="device")
     def __getstate__(self):
@@ -844,22 +1031,28 @@ class TransformerLM(_BlocksLM):
             dec = decs[key] = DeviceDecoder(self, B, idx.device, total)
         dec.refresh(self)                      # a generate() after an optimizer step sees the new weights
         mode = "ragged" if req.ragged else "plain" if req.ctl is None else "control"
+        scored = req.scored
         if graph:
-            dec.capture(mode)
+            dec.capture(mode, scored)
         state, params = self._decode_begin(idx, req, dec.ids, t0, graph=True)      # the decoder's block: four words, replayed or not
         dec.state.copy_(state)
         dec.params.copy_(params)
         if mode != "plain":
             dec.operands.begin(req.ctl, dec.ids, T, req.prompt_lengths, max_new_tokens)
+        if scored:
+            dec.begin_scores(req.top_logprobs)         # outside the graphs: zeros, sentinels and the top_n word
         lengths = dec.lengths if req.poll or req.ragged else None
         L = t0
         prefill = max_new_tokens > 0 and t0 < ctx
         if prefill:
-            dec.tail(self._prefill(idx[:, :t0].contiguous(), dec.caches, dec.ws, dec.w_lm), mode)
+            dec.tail(self._prefill(idx[:, :t0].contiguous(), dec.caches, dec.ws, dec.w_lm), mode, scored)
             L += 1
         while L < total and not (L > t0 and stop_poll_due(req.poll, L - t0, lengths)):
-            dec.step(cached=prefill and L <= ctx, graph=graph, mode=mode)      # no prefill: the caches hold nothing to step on
+            dec.step(cached=prefill and L <= ctx, graph=graph, mode=mode, scored=scored)      # no prefill: the caches hold nothing to step on
             L += 1
+        if scored:
+            gen = make_generation(dec.ids, lengths, total, *dec.scores, req.top_logprobs)
+            return Generation(*(t.clone() for t in gen))
         out = trim_to_longest(dec.ids, lengths, total, req.return_lengths)
         return (out[0].clone(), out[1]) if req.return_lengths else out.clone()
 

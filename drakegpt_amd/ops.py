@@ -1053,6 +1053,78 @@ def sample_rows(logits: Tensor, state: Optional[Tensor] = None, params: Optional
     return out_tok if out_tok is not None else p_out
 
 
+LOGPROBS_MAX_TOP = 20        # DG_LOGPROBS_MAX_TOP
+
+
+def check_top_logprobs(top_n, what: str = "top_n") -> int:
+    """an integer in [0, LOGPROBS_MAX_TOP]: plain Python, raised before anything touches a device"""
+    if isinstance(top_n, bool) or not isinstance(top_n, numbers.Integral) or not 0 <= int(top_n) <= LOGPROBS_MAX_TOP:
+        raise ValueError(f"{what} must be an integer in [0, {LOGPROBS_MAX_TOP}], got {top_n!r}")
+    return int(top_n)
+
+
+def token_logprobs(logits: Tensor, tokens: Tensor, *, top_n=0, rank: bool = False, state: Optional[Tensor] = None,
+                   lengths: Optional[Tensor] = None, spans: Optional[Tensor] = None, out: Optional[Tensor] = None,
+                   out_rank: Optional[Tensor] = None, out_top_ids: Optional[Tensor] = None, out_top_lp: Optional[Tensor] = None):
+    """log_softmax of the raw logits [M, V] (fp32 or bf16) at one token per row (dg_token_logprobs; include/drakegpt_hip.h states
+    the arithmetic and its order).  tokens int64 [M]: returns lp fp32 [M]; with rank=True also the token's rank int32 [M] (0 = the
+    greedy pick); with top_n > 0 also the top_n most likely ids int32 [M, top_n] and their lp fp32 [M, top_n] (-1 / -inf where the
+    row has fewer finite entries).  Returns lp alone, or a tuple (lp, [rank,] [top_ids, top_lp]) in that order.
+    The decode form, for a step that a graph replays: tokens int64 [M, cap] with state (the decode state, L = state[2]): the token
+    is tokens[m, L], every output is one the caller owns -- out fp32 [M, cap], out_rank int32 [M, cap], out_top_ids int32 /
+    out_top_lp fp32 [M, cap, LOGPROBS_MAX_TOP], each optional -- written at column L, top_n is a device int32 word that the kernel
+    reads, and rows that lengths [M] / spans [M, 2] (the sampler's) mark as finished before L or as forced are left untouched.
+    Nothing is returned."""
+    _chk(logits, "logits", contiguous=False)
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"token_logprobs: logits must be float32 or bfloat16, got {logits.dtype}")
+    if logits.dim() != 2:
+        raise RuntimeError("token_logprobs: logits must be [M, V]")
+    M, V = logits.shape
+    _chk(tokens, "tokens", torch.int64)
+    dev = logits.device
+    if tokens.dim() == 2:
+        if state is None or tokens.shape[0] != M or tokens.shape[1] < 1:
+            raise RuntimeError(f"token_logprobs: tokens [M = {M}, cap] come with the decode state")
+        _chk(state, "state", torch.int32)
+        if state.numel() != 4:
+            raise RuntimeError("token_logprobs: state must be int32[4]")
+        cap = tokens.shape[1]
+        for t, name, dt, shape in ((out, "out", torch.float32, (M, cap)), (out_rank, "out_rank", torch.int32, (M, cap)),
+                                   (out_top_ids, "out_top_ids", torch.int32, (M, cap, LOGPROBS_MAX_TOP)),
+                                   (out_top_lp, "out_top_lp", torch.float32, (M, cap, LOGPROBS_MAX_TOP)),
+                                   (lengths, "lengths", torch.int32, (M,)), (spans, "spans", torch.int32, (M, 2))):
+            if t is not None:
+                _chk(t, name, dt)
+                if tuple(t.shape) != shape:
+                    raise RuntimeError(f"token_logprobs: {name} must be {shape}, got {tuple(t.shape)}")
+        if (out_top_ids is None) != (out_top_lp is None):
+            raise ValueError("token_logprobs: out_top_ids and out_top_lp come together")
+        if out_top_ids is not None:
+            if not isinstance(top_n, torch.Tensor):
+                raise ValueError("token_logprobs: the decode form reads top_n from a device int32 word")
+            _chk(top_n, "top_n", torch.int32)
+        check(lib.dg_token_logprobs(_p(logits), dt_code(logits.dtype), _ld(logits), M, V, _p(tokens), cap, _p(state), _p(lengths),
+                                    _p(spans), _p(top_n) if out_top_ids is not None else None, _p(out), _p(out_rank),
+                                    _p(out_top_ids), _p(out_top_lp), _stream()), "dg_token_logprobs")
+        return None
+    if tokens.dim() != 1 or tokens.shape[0] != M:
+        raise RuntimeError(f"token_logprobs: tokens must be int64 [M = {M}]")
+    if state is not None or lengths is not None or spans is not None or any(
+            t is not None for t in (out, out_rank, out_top_ids, out_top_lp)):
+        raise ValueError("token_logprobs: state, lengths, spans and the out tensors belong to the decode form (tokens [M, cap])")
+    n = check_top_logprobs(top_n, "token_logprobs: top_n")
+    lp = torch.empty(M, dtype=torch.float32, device=dev)
+    rk = torch.empty(M, dtype=torch.int32, device=dev) if rank else None
+    ti = torch.empty((M, LOGPROBS_MAX_TOP), dtype=torch.int32, device=dev) if n else None
+    tl = torch.empty((M, LOGPROBS_MAX_TOP), dtype=torch.float32, device=dev) if n else None
+    n_dev = torch.tensor([n], dtype=torch.int32, device=dev) if n else None
+    check(lib.dg_token_logprobs(_p(logits), dt_code(logits.dtype), _ld(logits), M, V, _p(tokens), 0, None, None, None, _p(n_dev),
+                                _p(lp), _p(rk), _p(ti), _p(tl), _stream()), "dg_token_logprobs")
+    res = (lp,) + ((rk,) if rank else ()) + ((ti[:, :n], tl[:, :n]) if n else ())
+    return lp if len(res) == 1 else res
+
+
 def embed_window(ids: Tensor, state: Tensor, tok: Tensor, pos: Tensor, mode: int, out: Optional[Tensor] = None) -> Tensor:
     """the embedding of a decode step with the position L = state[2] read on the device (dg_embed_window).
     mode 0: [B, C] = tok[ids[:, L-1]] + pos[L-1];  mode 1: [B, Tw, C] = tok[ids[:, L-Tw:L]] + pos, Tw = rows of pos."""

@@ -223,6 +223,12 @@ def build_parser() -> argparse.ArgumentParser:
                     "from its logit (default 0: off)")
     ap.add_argument("--stop-token", type=int, action="append", default=None, metavar="ID", help="end the sample at this token id "
                     "(repeatable, up to 8; default: none)")
+    ap.add_argument("--sample-logprobs", action="store_true", help="after the sample, print the mean log-probability the model gave "
+                    "its tokens and their perplexity (generate(return_logprobs=True): the raw distribution, whatever the filters)")
+    ap.add_argument("--top-logprobs", type=int, default=0, metavar="N", help="with the sample's log-probabilities, also collect the N "
+                    "most likely tokens per position (0..20) and print how often the sampled token was the most likely one")
+    ap.add_argument("--best-of", type=int, default=1, metavar="N", help="draw N samples and keep the one with the highest mean "
+                    "log-probability (pads with --stop-token's first id, else 0)")
     ap.add_argument("--grad-clip", type=float, default=None, metavar="MAX_NORM",
                     help="clip the gradient to this global 2-norm before every AdamW step (ref: clip_grad_norm_; default: off); each "
                     "evaluation line then also reports the last step's pre-clip norm as grad_norm")
@@ -607,7 +613,22 @@ def main(argv=None):
         path = get_model_path(args.model_dir, args.model, args.scale)
         # --ema-decay: the sample comes from the averaged weights, which are saved beside the raw checkpoint in its format
         with (averaged() if averaged is not None else contextlib.nullcontext()):
-            print(decode(model.generate(idx, max_new_tokens=args.sample, **sample_kw)[0].tolist()))
+            if args.sample_logprobs or args.top_logprobs or args.best_of > 1:
+                if args.best_of > 1 and not args.stop_token:
+                    sample_kw["pad_token"] = 0
+                gen = model.generate(idx, max_new_tokens=args.sample, return_logprobs=True, top_logprobs=args.top_logprobs,
+                                     best_of=args.best_of, **sample_kw)
+                n = int(gen.lengths[0])
+                print(decode(gen.ids[0, :n].tolist()))
+                mean = float(gen.logprobs[0, 1:n].double().mean()) if n > 1 else float("nan")
+                line = f"sample logprob: mean {mean:.4f}, perplexity {math.exp(-mean):.3f} over {n - 1} tokens"
+                if args.top_logprobs:
+                    line += f", top-1 {float((gen.top_ids[0, 1:n, 0] == gen.ids[0, 1:n]).double().mean()):.3f}"
+                if args.best_of > 1:
+                    line += f", best of {args.best_of}"
+                print(line)
+            else:
+                print(decode(model.generate(idx, max_new_tokens=args.sample, **sample_kw)[0].tolist()))
             if averaged is not None and not args.no_save:
                 os.makedirs(args.model_dir, exist_ok=True)
                 ema_path = path[:-len(".pt")] + ".ema.pt"

@@ -504,6 +504,44 @@ int dg_token_counts_rows(const int64_t* ids, int64_t ld_ids, int M, const int32_
                          int32_t* counts, int64_t ldc, int accumulate, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Token log-probabilities: how likely the model found a token, for generate(return_logprobs=) and score().  What OpenAI's
+ * `logprobs`, HF's compute_transition_scores and vLLM report: log_softmax of the RAW logits at the token -- no temperature,
+ * penalty, bias or filter.  One workgroup per row of logits [M, V] (leading dimension ldl; columns V..ldl-1 are never read),
+ * logits_dtype DG_F32 or DG_BF16 (widened exactly).  V <= 2^20.  Per row m, with x the row as fp32:
+ *   m* = max_i x_i (fp32);  d_j = x_j - m*, ONE fp32 rounding (never contracted);  e_j = exp((double)d_j);
+ *   Z  = sum_i e_i in fp64, in the order of dg_sample_rows' S: NT = 256 threads for V <= 8192, else 1024; chunk = ceil(V / NT);
+ *        thread t adds e_j, j in [t * chunk, min((t + 1) * chunk, V)), in index order starting from 0.0; in every wave of 64
+ *        consecutive threads the chunk sums go through an inclusive scan, for o = 1, 2, 4, .., 32: c[l] += c[l - o] for every
+ *        l >= o at once; the wave's total is c[63]; Z = ((0.0 + total_0) + total_1) + ... in wave order.
+ *   lp_j = (float)((double)d_j - log(Z)).  Never log(p_j): a dominated token gets a large finite negative value, not -inf from
+ *        an underflowing p.  x_j = -inf gives -inf; a row without a finite entry gives NaN, as torch.log_softmax does.
+ * The token t of row m, clamped to [0, V) as in dg_embed_fwd, and the output element e:
+ *   ld_tok > 0:  L = state[2] (the decode state {seed_lo, seed_hi, L, 0}); t = tokens[m * ld_tok + L], e = m * ld_tok + L --
+ *                column L of outputs laid out like tokens.  L >= ld_tok: nothing is read or written.
+ *   ld_tok == 0: t = tokens[m], e = m.
+ * Outputs, each nullable:
+ *   tok_lp   fp32  [e]:  lp_t
+ *   tok_rank int32 [e]:  #{i : x_i > x_t} + #{i < t : x_i == x_t} -- 0 exactly when t is what greedy picks
+ *   top_ids  int32 [e * DG_LOGPROBS_MAX_TOP + s], top_lp fp32 likewise (both or neither): slot s < n holds the s-th largest x_i
+ *            > -inf and its lp, descending, ties by lowest index first (the order of the fp32 bit patterns: -0 sorts below
+ *            +0), n = min(top_n, DG_LOGPROBS_MAX_TOP, the number of entries > -inf).  Every other slot of the
+ *            DG_LOGPROBS_MAX_TOP holds id = -1, lp = -inf.
+ * top_n (device int32, nullable = 0) is read by the kernel, so that one captured graph serves every setting; a value above
+ * DG_LOGPROBS_MAX_TOP is clamped, 0 (or no top_ids) runs no selection pass.
+ * Skipped rows -- no logit is read, no byte is written -- need ld_tok > 0; lengths int32 [M] and spans int32 [M, 2] (those of
+ * dg_sample_rows_control / _ragged) are each nullable:
+ *   lengths[m] != 0 && L >= lengths[m]:  the row finished before this position.  Its stop token, at L = lengths[m] - 1, IS scored.
+ *   spans given && L < spans[2 * m]:     the row is forced, still inside its prompt.
+ * Refused, nothing launched: NULL logits or tokens; ld_tok > 0 without state; lengths or spans with ld_tok == 0; top_ids without
+ * top_lp or the reverse; a dtype other than the two; V > 2^20; ldl < V.
+ * No floating-point atomics: a pure function of (logits, tokens, state, lengths, spans, top_n). */
+#define DG_LOGPROBS_MAX_TOP 20
+int dg_token_logprobs(const void* logits, int logits_dtype, int64_t ldl, int M, int V, const int64_t* tokens,
+                      int64_t ld_tok, const uint32_t* state, const int32_t* lengths, const int32_t* spans,
+                      const int32_t* top_n, float* tok_lp, int32_t* tok_rank, int32_t* top_ids, float* top_lp,
+                      void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Cross entropy, mean over rows -- ref: F.cross_entropy at src/model.py:604-607 (K16).
  * loss_rows[m] = logsumexp(logits[m,:]) - logits[m,target[m]].  If dlogits != NULL also writes
  * dlogits[m,n] = (softmax(logits[m,:])[n] - [n == target]) * grad_scale (* *grad_scale_dev) in

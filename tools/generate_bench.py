@@ -6,6 +6,7 @@ the reference's inference.py default, N = 1000 new tokens from a one-token promp
                                    [--top-p P] [--min-p P] [--vocab 80]
                                    [--repetition-penalty R] [--presence-penalty A] [--frequency-penalty F]
                                    [--prompt-lengths 4,64,128,...] [--sampler-launch]
+                                   [--logprobs] [--top-logprobs N]
 
 Two phases are reported separately.  With a one-token prompt the first ctx tokens are made while the sequence still fits the
 window (one prefill, then K/V-cached steps); the rest by the sliding-window algorithm (a full forward per token).  The first
@@ -16,6 +17,9 @@ sampler; --top-p / --min-p are passed only when given, for the same reason.  --v
 at a GPT-2 row).  The three penalty flags are passed only when given too: with one of them the device sampler replays the
 decoder's second pair of graphs (dg_sample_rows_control).  One JSON line per precision.
 
+--logprobs / --top-logprobs N: the same call with return_logprobs=True (and top_logprobs=N): every step also scores its token
+(dg_token_logprobs; with the device sampler inside the decoder's scored twin graphs).  Passed only when given.
+
 --prompt-lengths 4,64,128,... (device sampler; the batch size is the count): one generate(prompt_lengths=...) call on right-padded
 prompts of these lengths, --tokens new tokens per row, against the same prompts as separate B = 1 calls (their times summed) and
 against the rectangular call on B prompts of the longest length, which has no forced steps.  Tokens per second count new tokens
@@ -23,6 +27,11 @@ only.  The three kinds of call alternate within a repeat.
 --sampler-launch: no model -- the time of one sampler launch on [--batch, --vocab] logits with penalties on: dg_sample_rows_control,
 dg_sample_rows_ragged with no forced row, and dg_sample_rows_ragged with every row forced (what a forced step adds), each the
 median over --repeats replays of a graph of 200 such launches (no host work between them), the replays alternating between the three.
+The same mode times the scoring launch alone, dg_token_logprobs in its decode form on the same logits: with top_n = 0, and with
+top_n = --top-logprobs (default 5).
+--score-launch: no model -- the one scoring launch of score() (dg_token_logprobs with ranks, rows = --batch, default 8192 there,
+bf16 logits at --vocab) beside the loss-only dg_cross_entropy launch on the same logits, which reads the same bytes; top_n = 0 and
+--top-logprobs (default 5); medians over --repeats, the kinds alternating.
 """
 import argparse
 import json
@@ -98,6 +107,13 @@ def sampler_launch(args, dev):
     spans = {"ragged_none_forced": torch.tensor([[1, cap]] * M, dtype=torch.int32, device=dev),
              "ragged_all_forced": torch.tensor([[L + 1, cap]] * M, dtype=torch.int32, device=dev)}
     kinds = {"control": {}, **{k: dict(spans=v) for k, v in spans.items()}}
+    # the scoring launch alone: dg_token_logprobs as a decode step makes it, without and with a top-n selection
+    top = args.top_logprobs or 5
+    lp = torch.zeros((M, cap), dtype=torch.float32, device=dev)
+    ti = torch.zeros((M, cap, ops.LOGPROBS_MAX_TOP), dtype=torch.int32, device=dev)
+    tl = torch.zeros((M, cap, ops.LOGPROBS_MAX_TOP), dtype=torch.float32, device=dev)
+    words = {0: torch.zeros(1, dtype=torch.int32, device=dev), top: torch.full((1,), top, dtype=torch.int32, device=dev)}
+    kinds.update({"logprobs_top0": dict(score=0), f"logprobs_top{top}": dict(score=top)})
 
     n = 200
 
@@ -105,7 +121,11 @@ def sampler_launch(args, dev):
         """n launches captured as one graph: a replay costs no host work between them"""
         def run():
             for _ in range(n):
-                ops.sample_rows(logits, state, params, ids=ids, control=ctl, counts=counts, lengths=lengths, **kw)
+                if "score" in kw:
+                    ops.token_logprobs(logits, ids, state=state, lengths=lengths, out=lp, out_top_ids=ti, out_top_lp=tl,
+                                       top_n=words[kw["score"]])
+                else:
+                    ops.sample_rows(logits, state, params, ids=ids, control=ctl, counts=counts, lengths=lengths, **kw)
         run()
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
@@ -134,11 +154,47 @@ def sampler_launch(args, dev):
     print(json.dumps(line), flush=True)
 
 
+def score_launch(args, dev):
+    """--score-launch: microseconds of score()'s scoring launch and of the loss-only cross entropy on the same bf16 logits"""
+    from drakegpt_amd import ops
+    M, V = args.batch, args.vocab
+    g = torch.Generator().manual_seed(0)
+    ld = (V + 7) // 8 * 8
+    buf = torch.zeros((M, ld), dtype=torch.bfloat16)
+    buf[:, :V] = (torch.randn((M, V), generator=g) * 2.0).bfloat16()
+    logits = buf.to(dev)[:, :V]
+    tok = torch.randint(0, V, (M,), generator=g).to(dev)
+    top = args.top_logprobs or 5
+    kinds = {"cross_entropy_loss_only": lambda: ops.cross_entropy(logits, tok, V),
+             "token_logprobs_rank": lambda: ops.token_logprobs(logits, tok, rank=True),
+             f"token_logprobs_rank_top{top}": lambda: ops.token_logprobs(logits, tok, rank=True, top_n=top)}
+
+    def block(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) * 1e3
+
+    for fn in kinds.values():
+        block(fn)
+        block(fn)
+    us = {k: [] for k in kinds}
+    for _ in range(args.repeats):
+        for k, fn in kinds.items():
+            us[k].append(block(fn))
+    line = {"tool": "generate_bench", "mode": "score_launch", "rows": M, "vocab": V, "dtype": "bf16", "repeats": args.repeats,
+            "logits_gb": round(M * ld * 2e-9, 3)}
+    line.update({k + "_us": {kk: round(v, 1) for kk, v in spread(xs).items()} for k, xs in us.items()})
+    print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sampler", default="host", choices=["host", "device"])
     ap.add_argument("--precision", nargs="+", default=["fp32", "bf16"])
-    ap.add_argument("--batch", type=int, default=1)
+    ap.add_argument("--batch", type=int, default=None, help="default 1 (--score-launch: 8192 rows)")
     ap.add_argument("--tokens", type=int, default=1000)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--top-p", type=float, default=None)
@@ -149,11 +205,18 @@ def main():
     ap.add_argument("--frequency-penalty", type=float, default=None)
     ap.add_argument("--prompt-lengths", type=lambda s: [int(x) for x in s.split(",")], default=None)
     ap.add_argument("--sampler-launch", action="store_true")
+    ap.add_argument("--score-launch", action="store_true")
+    ap.add_argument("--logprobs", action="store_true")
+    ap.add_argument("--top-logprobs", type=int, default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("generate_bench needs the GPU: a timing taken anywhere else says nothing")
     cfg = PRESETS["scaled"]
     dev = torch.device("cuda:0")
+    if args.score_launch:
+        args.batch = args.batch or 8192
+        return score_launch(args, dev)
+    args.batch = args.batch or 1
     if args.sampler_launch:
         return sampler_launch(args, dev)
     if args.prompt_lengths is not None:
@@ -168,6 +231,11 @@ def main():
     for name in ("repetition_penalty", "presence_penalty", "frequency_penalty"):
         if getattr(args, name) is not None:
             kw[name] = getattr(args, name)
+    if args.logprobs:
+        kw["return_logprobs"] = True
+    if args.top_logprobs is not None:
+        kw["top_logprobs"] = args.top_logprobs
+    scored = args.logprobs or bool(args.top_logprobs)
     for precision in args.precision:
         torch.manual_seed(42)
         m = D.TransformerLM(V, C, T, NH, NL, cfg["dropout"], precision=precision).to(dev).eval()
@@ -180,7 +248,7 @@ def main():
             out = m.generate(start, n, **kw)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
-            assert out.shape == (args.batch, 1 + n)
+            assert (out.ids if scored else out).shape == (args.batch, 1 + n)
             return dt
 
         timed(args.tokens)                                   # warm-up: code objects, allocator, graph capture
@@ -191,7 +259,8 @@ def main():
         t_short, t_full = statistics.median(short), statistics.median(full)
         line = {"tool": "generate_bench", "sampler": args.sampler, "precision": precision, "batch": args.batch,
                 "vocab": V, "top_p": args.top_p, "min_p": args.min_p, "repetition_penalty": args.repetition_penalty,
-                "presence_penalty": args.presence_penalty, "frequency_penalty": args.frequency_penalty, "tokens": args.tokens, "ctx": T, "repeats": args.repeats,
+                "presence_penalty": args.presence_penalty, "frequency_penalty": args.frequency_penalty, "logprobs": scored, "top_logprobs": args.top_logprobs,
+                "tokens": args.tokens, "ctx": T, "repeats": args.repeats,
                 "total_s": round(t_full, 4), "total_tok_per_s": round(args.batch * args.tokens / t_full, 1),
                 "cached_tokens": n_cached, "cached_s": round(t_short, 4),
                 "cached_tok_per_s": round(args.batch * n_cached / t_short, 1),
